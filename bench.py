@@ -16,9 +16,20 @@ cpp/tests/linear_programming/pdlp_test.cu:145-148).  N > 1 shards the SAME LP (s
 and a column block of A, the slices of xbar and y' are all-gathered over RCCL each step (owner-computes dataflow, the default;
 CUOPT_AMD_SHARD_DATAFLOW / CUOPT_AMD_SHARD_TRANSPORT select the others, `config.parallelism` names what ran).
 
-Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernel (the fused CSR SpMV + dual
-projection), timed with HIP events on the solver's stream by pdlpdev_time_kernel; `cpu_baseline` is the
-C oracle's PDLP loop (oracle/pdlp_oracle.c, kind "port") on the same LP with a bounded iteration budget.
+Prints ONE JSON line (rank 0).  The timed region is exactly --steps iterations (`timed_steps`; --min-seconds S > 0 lengthens it
+to at least S seconds) and `ms_per_step` is its wall time per iteration; `value` = 1000 / ms_per_step.
+
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the line; `roofline`, `cpu_baseline` and
+`time_to_1e-4` are null there.  --full adds the rest, each leg a run of its own after the timed region: `roofline` is for the
+dominant kernel (the fused CSR SpMV + dual projection), timed with HIP events on the solver's stream by pdlpdev_time_kernel;
+`cpu_baseline` is the C oracle's PDLP loop (oracle/pdlp_oracle.c, kind "port") on the same LP with a bounded iteration budget;
+`time_to_1e-4` a solve at the default tolerances, set-up included; the shader clock sampled during the timed region; and for the
+batch workloads the single-LP rate, the thread-pool leg and the reference's dual simplex.
+
+--dump-outputs DIR: what the timed path handed its caller after its last step, as DIR/<name>.npy (float64): primal_solution,
+dual_solution, reduced_cost (cuoptamd_solver_get_solution, rank 0) and result_scalars (RESULT_FIELDS, in that order); the batch
+workloads write lp<index>_<name> per LP.  The inputs are seeded, so two runs with the same arguments compare output for output.
+Above 64 MB in all, every large array is cut to the same fixed, seeded sample of its entries.
 """
 import argparse
 import json
@@ -32,6 +43,41 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E peak, /opt/skills/guides/MI355X_MICROARCH.md
+
+# --dump-outputs: the result fields written as result_scalars.npy (the timings are left out: they differ from run to run)
+RESULT_FIELDS = ("steps_taken", "attempted_steps", "num_restarts", "primal_objective", "dual_objective", "gap", "relative_gap",
+                 "l2_primal_residual", "l2_dual_residual", "l2_relative_primal_residual", "l2_relative_dual_residual", "step_size",
+                 "primal_weight")
+DUMP_BUDGET_BYTES = 60 << 20  # (under the 64 MB the files may take, .npy headers included)
+
+# The clock warm-up's batches run a number of iterations that depends on the clocks; the solvers then start again from their fresh
+# state and run --warmup (rounded up to whole periods) plus these major-iteration periods untimed, the same count in every run.  That
+# is as far in as the timed steps started behind the clock warm-up before (4 batches of 5 periods): on C3 the adaptive step size
+# rejects ~1 % of the attempts of iterations 200-2200 and next to none after iteration 1000, and the headline never included them.
+SETTLE_PERIODS = 20
+
+
+def solver_outputs(result, x, y, rc, prefix=""):
+    """the arrays a caller of the timed path receives: the solution vectors and the result's numbers"""
+    return {prefix + "primal_solution": x, prefix + "dual_solution": y, prefix + "reduced_cost": rc,
+            prefix + "result_scalars": np.array([float(result[k]) for k in RESULT_FIELDS])}
+
+
+def dump_outputs(out_dir, arrays):
+    """writes every array as out_dir/<name>.npy, float64.  When they hold more than DUMP_BUDGET_BYTES, the arrays above 1 MB are all
+    cut to the same share of their entries, at positions drawn with a fixed seed from the array's length alone: the same
+    positions in every run with the same arguments."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64).ravel() for k, v in arrays.items()}
+    large = {k for k, a in arrays.items() if a.nbytes > (1 << 20)}
+    small_bytes = sum(a.nbytes for k, a in arrays.items() if k not in large)
+    large_bytes = sum(arrays[k].nbytes for k in large)
+    share = 1.0 if small_bytes + large_bytes <= DUMP_BUDGET_BYTES else (DUMP_BUDGET_BYTES - small_bytes) / large_bytes
+    for name, a in arrays.items():
+        if name in large and share < 1.0:
+            keep = max(1, int(len(a) * share))
+            a = a[np.sort(np.random.default_rng(len(a)).choice(len(a), size=keep, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def reference_dual_simplex_block(root, cutoff_s=15.0):
@@ -148,17 +194,19 @@ def batch_line(args, p, cfg, K, local_rank, record_fd, t_gen):
         dev.call("prepare_graphs")
     period = max(int(parent.hyper.major_iteration), 1)
     pre = ((max(args.warmup, 2 * period, int(parent.hyper.min_iteration_restart) + period) + period - 1) // period) * period
-    # the single solve's rate in this very process (the yardstick of the aggregate)
-    parent.advance(pre)
-    rates = []
-    for _ in range(4):
-        dev.call("synchronize")
-        t0 = time.perf_counter()
-        parent.advance(25 * period)
-        dev.call("synchronize")
-        rates.append(25 * period / (time.perf_counter() - t0))
-    single = max(rates[1:])
-    parent.reset(tol=0.0, use_graph=graph)
+    single = None
+    if args.full:
+        # the single solve's rate in this very process (the yardstick of the aggregate)
+        parent.advance(pre)
+        rates = []
+        for _ in range(4):
+            dev.call("synchronize")
+            t0 = time.perf_counter()
+            parent.advance(25 * period)
+            dev.call("synchronize")
+            rates.append(25 * period / (time.perf_counter() - t0))
+        single = max(rates[1:])
+        parent.reset(tol=0.0, use_graph=graph)
     sets = [bounds(l) for l in range(1, K)]
     t0 = time.perf_counter()
     clones = [parent.clone(lb, ub) for lb, ub in sets]
@@ -166,6 +214,7 @@ def batch_line(args, p, cfg, K, local_rank, record_fd, t_gen):
     batch = capi.SharedMatrixBatch([parent] + clones)
     layout = dev.layout()
     batch.advance(pre)
+    fixed_pre = pre
     warm_rates, warm_wall = [], 0.0
     while True:
         dev.call("synchronize")
@@ -178,8 +227,19 @@ def batch_line(args, p, cfg, K, local_rank, record_fd, t_gen):
         warm_rates.append(5 * period / dt)
         if (len(warm_rates) >= 3 and all(abs(warm_rates[-i] - warm_rates[-i - 1]) <= 0.02 * warm_rates[-i] for i in (1, 2))) or warm_wall > 4.0:
             break
-    timed_steps = max((max(args.steps, 1) + period - 1) // period, 5) * period
-    timed_steps = max(timed_steps, int(np.ceil(args.min_seconds * warm_rates[-1] / period)) * period)
+    # (the number of clock warm-up batches depends on the clocks: every LP starts again from its fresh state in a new batch and runs a
+    # fixed warm-up (SETTLE_PERIODS), so that the timed steps -- and what --dump-outputs writes -- are the same iterations in every run)
+    batch.close()
+    for s in [parent] + clones:
+        s.reset()
+    batch = capi.SharedMatrixBatch([parent] + clones)
+    if graph:
+        dev.call("prepare_graphs")
+    pre = fixed_pre + SETTLE_PERIODS * period
+    batch.advance(pre)
+    timed_steps = max(args.steps, 1)
+    if args.min_seconds > 0:
+        timed_steps = max(timed_steps, int(np.ceil(args.min_seconds * warm_rates[-1] / period)) * period)
     attempts_before = sum(r["attempted_steps"] for r in batch.advance(0))
     dev.call("synchronize")
     t0 = time.perf_counter()
@@ -188,28 +248,35 @@ def batch_line(args, p, cfg, K, local_rank, record_fd, t_gen):
     elapsed = time.perf_counter() - t0
     assert all(r["status"] == 0 and r["steps_taken"] == pre + timed_steps for r in rs), [(r["status_name"], r["steps_taken"]) for r in rs]
     attempts = sum(r["attempted_steps"] for r in rs) - attempts_before
-    kernels = batch.time_kernels(20)
-    bytes_alg = {
-        # the matrix once, every gathered vector entry of every LP once, the per-LP epilogue streams, the interleaved copy of y'
-        "a_dual": 12 * nnz + 4 * (m + 1) + K * (8 * n + 8 * (4 * m + 2 * m)) + 8 * K * m,
-        "at_step": 12 * nnz + 4 * (n + 1) + K * (8 * m + 8 * (3 * n + n)),
-        "primal": K * 8 * (6 * n + 3 * n),  # x,c,AtY,lb,ub,sum_x r ; x',sum_x w ; xbar interleaved w
-    }
-    dom = "a_dual" if kernels["a_dual"] >= kernels["at_step"] else "at_step"
-    achieved = bytes_alg[dom] / (kernels[dom] * 1e-3) / 1e9
-    ksum = sum(kernels.values())
-    floor_k = 24 * nnz + 4 * (m + n + 2) + K * 8 * (14 * n + 7 * m) + 2 * 8 * K * (n + m)
-    per_attempt_ms = 1e3 * elapsed / max(attempts / K, 1)
-    roofline = dict(bound="hbm", kernel="kb_" + dom + "<%d>" % K, achieved=round(achieved, 1), peak=HBM_PEAK_GBS, unit="GB/s",
-                    frac=round(achieved / HBM_PEAK_GBS, 4), traffic=None, algorithmic_bytes_per_launch=bytes_alg[dom],
-                    avg_launch_ms=round(kernels[dom], 5), per_kernel_ms={k: round(v, 5) for k, v in kernels.items()},
-                    per_kernel_gbs={k: round(bytes_alg[k] / (kernels[k] * 1e-3) / 1e9, 1) for k in bytes_alg},
-                    attempt_kernels_ms=round(ksum, 5), ms_per_lockstep_attempt=round(per_attempt_ms, 5),
-                    attempt_kernels_over_ms_per_attempt=round(ksum / per_attempt_ms, 4),
-                    lockstep_iteration_floor_bytes=floor_k,
-                    iteration_frac_of_peak=round(floor_k * (timed_steps / elapsed) / 1e9 / HBM_PEAK_GBS, 4),
-                    floor_note="fused floor of a lockstep iteration: the matrix twice (A, A^T) ONCE for all LPs, every LP's own 14 n + 7 m "
-                               "vector streams, the two interleaved gather vectors written and read once")
+    if args.dump_outputs:
+        arrays = {}
+        for l, (r, (x, y, z)) in enumerate(zip(rs, batch.solutions())):
+            arrays.update(solver_outputs(r, x, y, z, prefix="lp%02d_" % l))
+        dump_outputs(args.dump_outputs, arrays)
+    roofline = None
+    if args.full:
+        kernels = batch.time_kernels(20)
+        bytes_alg = {
+            # the matrix once, every gathered vector entry of every LP once, the per-LP epilogue streams, the interleaved copy of y'
+            "a_dual": 12 * nnz + 4 * (m + 1) + K * (8 * n + 8 * (4 * m + 2 * m)) + 8 * K * m,
+            "at_step": 12 * nnz + 4 * (n + 1) + K * (8 * m + 8 * (3 * n + n)),
+            "primal": K * 8 * (6 * n + 3 * n),  # x,c,AtY,lb,ub,sum_x r ; x',sum_x w ; xbar interleaved w
+        }
+        dom = "a_dual" if kernels["a_dual"] >= kernels["at_step"] else "at_step"
+        achieved = bytes_alg[dom] / (kernels[dom] * 1e-3) / 1e9
+        ksum = sum(kernels.values())
+        floor_k = 24 * nnz + 4 * (m + n + 2) + K * 8 * (14 * n + 7 * m) + 2 * 8 * K * (n + m)
+        per_attempt_ms = 1e3 * elapsed / max(attempts / K, 1)
+        roofline = dict(bound="hbm", kernel="kb_" + dom + "<%d>" % K, achieved=round(achieved, 1), peak=HBM_PEAK_GBS, unit="GB/s",
+                        frac=round(achieved / HBM_PEAK_GBS, 4), traffic=None, algorithmic_bytes_per_launch=bytes_alg[dom],
+                        avg_launch_ms=round(kernels[dom], 5), per_kernel_ms={k: round(v, 5) for k, v in kernels.items()},
+                        per_kernel_gbs={k: round(bytes_alg[k] / (kernels[k] * 1e-3) / 1e9, 1) for k in bytes_alg},
+                        attempt_kernels_ms=round(ksum, 5), ms_per_lockstep_attempt=round(per_attempt_ms, 5),
+                        attempt_kernels_over_ms_per_attempt=round(ksum / per_attempt_ms, 4),
+                        lockstep_iteration_floor_bytes=floor_k,
+                        iteration_frac_of_peak=round(floor_k * (timed_steps / elapsed) / 1e9 / HBM_PEAK_GBS, 4),
+                        floor_note="fused floor of a lockstep iteration: the matrix twice (A, A^T) ONCE for all LPs, every LP's own 14 n + 7 m "
+                                   "vector streams, the two interleaved gather vectors written and read once")
     batch.close()
     for c in clones:
         c.close()
@@ -217,7 +284,7 @@ def batch_line(args, p, cfg, K, local_rank, record_fd, t_gen):
     # ---- wall clock to the default 1e-4 verdicts, set-ups included: one set-up + K - 1 clones + the lockstep solve against K
     # solves one after the other, each with its own set-up (what K calls of cuOptSolve cost)
     conv = None
-    if not args.no_convergence_run:
+    if args.full and not args.no_convergence_run:
         all_sets = [bounds(0)] + sets
         t0 = time.perf_counter()
         par = capi.Solver(dict(p, lb=all_sets[0][0], ub=all_sets[0][1]), mode=1, device=local_rank)
@@ -240,7 +307,7 @@ def batch_line(args, p, cfg, K, local_rank, record_fd, t_gen):
         conv = dict(statuses=[r["status_name"] for r in rb], iterations=[r["steps_taken"] for r in rb],
                     same_as_the_single_solves=all(a["steps_taken"] == b["steps_taken"] and a["primal_objective"] == b["primal_objective"] for a, b in zip(rb, rs1)),
                     wall_s_lockstep=round(wall_batch, 4), wall_s_one_after_the_other=round(wall_seq, 4), ratio=round(wall_seq / wall_batch, 3))
-    cpu = None if args.no_cpu_baseline else cpu_baseline_block(p)
+    cpu = cpu_baseline_block(p) if args.full and not args.no_cpu_baseline else None
     if cpu is not None:
         cpu["note"] = "the oracle solves one LP at a time: its aggregate over K LPs is this rate"
     info = capi.device_info(local_rank)
@@ -253,7 +320,8 @@ def batch_line(args, p, cfg, K, local_rank, record_fd, t_gen):
                                "the others with a tenth of the upper bounds tightened (seeded); lockstep batch, Stable2 preset, tolerances 0 (fixed "
                                "iteration budget)" % (args.workload, K, m, n, cfg["k"], cfg["seed"], nnz),
                    "rows": m, "cols": n, "nnz": nnz, "lps": K, "parallelism": "single GPU, %d LPs in lockstep" % K},
-        "single_lp_its_per_s_same_process": round(single, 1), "aggregate_over_single": round(K * timed_steps / elapsed / single, 3),
+        "single_lp_its_per_s_same_process": None if single is None else round(single, 1),
+        "aggregate_over_single": None if single is None else round(K * timed_steps / elapsed / single, 3),
         "clone_seconds_per_lp": round(clone_s, 4),
         "roofline": roofline, "cpu_baseline": cpu, "time_to_1e-4": conv, "spmv_layout": layout, "attempted_steps": attempts, "setup_seconds": round(setup_s, 4),
         "generate_seconds": round(t_gen, 2), "device": info["name"], "compute_units": info["compute_units"],
@@ -383,17 +451,22 @@ def small_batch_line(args, K, local_rank, record_fd):
     batch.reset(lb=[base["lb"]] * K, ub=[base["ub"]] * K)
     got, objs, (lbs, ubs) = run(solvers, "small-LP batch: %d workgroups per launch; per round one cuoptamd_batch_branch, one cuoptamd_batch_advance, "
                                 "one cuoptamd_batch_solution_views" % K, batch=batch)
+    if args.dump_outputs:
+        arrays = {}
+        for l, (s, (x, y, z)) in enumerate(zip(solvers, batch.solutions())):
+            arrays.update(solver_outputs(s.result.as_dict(), x, y, z, prefix="lp%04d_" % l))
+        dump_outputs(args.dump_outputs, arrays)
     batch.close()
     for s in reversed(solvers):
         s.close()
     # ---- the same node sequences through a pool of host threads (one solver + one stream per LP; 16 threads)
     # (--no-convergence-run skips this leg: rocprofv3 7.2 crashes in a process that launches from sixteen threads)
     pool, same = None, None
-    if not args.no_convergence_run:
+    if args.full and not args.no_convergence_run:
         pool, same = thread_pool_leg()
     # ---- the reference's dual simplex (oracle/_ref, 1 thread) on a bounded sample of the LAST round's nodes (cold: it has no warm start here)
     cpu = None
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         try:
             from oracle import refbind
             if refbind.available():
@@ -445,9 +518,13 @@ def main():
     ap.add_argument("--workload", default="c3", choices=["c3", "c2", "tiny", "hard", "banded", "staircase", "block_angular", "powerlaw", "multiband", "dense_rows", "c3x10", "banded4",
                              "banded_shuffled", "staircase_shuffled", "block_angular_shuffled", "multiband_shuffled", "c3x100", "c3x200", "c5_batch256", "c5_batch64", "c5_batch1024", "c3_batch16", "c3_batch8", "c3_batch4", "c3_batch2", "c2_batch16", "c2_batch8", "c2_batch4"],
                     help="*_shuffled: the structured family under a seeded random row AND column permutation (the set-up's analysis pass has to find the structure)")
-    ap.add_argument("--min-seconds", type=float, default=10.0, help="lower bound on the duration of the timed region (timed_steps is rounded up): long enough for an outside observer that samples the GPU every few seconds")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-convergence-run", action="store_true")
+    ap.add_argument("--min-seconds", type=float, default=0.0, help="lower bound on the duration of the timed region (timed_steps is rounded up "
+                    "to whole major-iteration periods): long enough for an outside observer that samples the GPU every few seconds; 0 = exactly --steps")
+    ap.add_argument("--full", action="store_true", help="also the legs beyond the headline figure: per-kernel times and roofline, the run to 1e-4, "
+                    "the CPU baselines, the shader clock, the batch workloads' single-LP and thread-pool comparisons")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the timed path computed in its last step as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(with --full) leave out the CPU baselines")
+    ap.add_argument("--no-convergence-run", action="store_true", help="(with --full) leave out the run to 1e-4 and the thread-pool leg")
     ap.add_argument("--force-comm", action="store_true", help="use the RCCL path even with one rank")
     ap.add_argument("--graph-comm", action="store_true", help="capture the collectives of a sharded attempt into the attempt graphs (pdlpdev_set_graph_mode 2)")
     ap.add_argument("--self-launch", action="store_true", help="go through the torch.distributed.run launcher also for one GPU")
@@ -577,10 +654,9 @@ def main():
     # ---- fixed-budget run: iterations / second ------------------------------------------------------
     # A PDLP iteration carries its amortised share of the major-iteration work (every `major_iteration` = 40 steps;
     # additionally EVERY step is a major iteration while the step count is <= min_iteration_restart, pdlp.cu:1082-1084).
-    # Whatever --steps / --warmup say, the timed region therefore (i) starts past that initial phase, on a major-
-    # iteration boundary, with every hipGraph replay size instantiated, and (ii) covers a whole number of
-    # major-iteration periods: timed_steps = steps rounded up to a multiple of the period (at least five periods), (iii) below.  `steps` is reported as
-    # given, `timed_steps` and `warmup_done` as run; ms_per_step = elapsed / timed_steps.
+    # Whatever --warmup says, the timed region therefore (i) starts past that initial phase, on a major-
+    # iteration boundary, with every hipGraph replay size instantiated, and (ii) covers exactly --steps iterations (timed_steps;
+    # --min-seconds lengthens it, (iv) below).  `steps` is reported as given, `timed_steps` and `warmup_done` as run; ms_per_step = elapsed / timed_steps.
     solver = capi.Solver(p, mode=1, tol=0.0, device=local_rank, rank=rank, world=world, comm_id=comm_id)
     setup_s = solver.advance(0)["setup_seconds"]
     dev = solver.device
@@ -590,7 +666,7 @@ def main():
     period = max(int(solver.hyper.major_iteration), 1)
     pre = max(args.warmup, 2 * period, int(solver.hyper.min_iteration_restart) + period)
     pre = ((pre + period - 1) // period) * period
-    timed_steps = max((max(args.steps, 1) + period - 1) // period, 5) * period  # at least five periods: a stable clock
+    timed_steps = max(args.steps, 1)
     solver.advance(pre)
     layout = dev.layout()
     reorder = solver.reorder_info()
@@ -611,6 +687,7 @@ def main():
     # milliseconds below them (measured: the same 200 timed steps gave 4.7 k it/s right after start-up and 5.7 k once warm), so
     # untimed batches of five periods run until two consecutive batches agree within 2 % (at most 4 s).  Every rank takes the same
     # decision: the batch times are max-reduced over the ranks first.
+    fixed_pre = pre
     warm_rates, warm_wall = [], 0.0
     while True:
         dev.call("synchronize")
@@ -626,14 +703,21 @@ def main():
         steady = len(warm_rates) >= 3 and all(abs(warm_rates[-i] - warm_rates[-i - 1]) <= 0.02 * warm_rates[-i] for i in (1, 2))
         if steady or warm_wall > 4.0 or len(warm_rates) >= 100:
             break
-    # (iv) the timed region lasts at least --min-seconds (default 2 s) whatever --steps says, so that an outside observer (the
-    # driver's rocm-smi samples, its own clock) sees the GPU leg: timed_steps is rounded up from the steady rate of the warm-up
-    # batches (max-reduced over the ranks: same decision everywhere); `steps` is echoed as given, `timed_steps` as run.
+    # ... and (v) the number of those batches depends on the clocks: the solver starts again from its fresh state (cuoptamd_solver_reset:
+    # bit for bit a solver created anew) and runs a fixed warm-up (SETTLE_PERIODS), so that the timed steps -- and what --dump-outputs
+    # writes -- are the same iterations in every run with the same arguments
+    solver.reset()
+    if args.graph_comm:  # (the reset went back to the settings' graph mode)
+        dev.call("set_graph_mode", 2)
+    dev.call("prepare_graphs")
+    pre = fixed_pre + SETTLE_PERIODS * period
+    solver.advance(pre)
+    # (iv) with --min-seconds S > 0 the timed region lasts at least S seconds whatever --steps says, so that an outside observer
+    # (rocm-smi samples, its own clock) sees the GPU leg: timed_steps is rounded up from the steady rate of the warm-up batches
+    # (max-reduced over the ranks: same decision everywhere); `steps` is echoed as given, `timed_steps` as run.
     steady_rate = max_over_ranks(warm_rates[-1])
-    timed_steps = max(timed_steps, int(np.ceil(args.min_seconds * steady_rate / period)) * period)
-    dev.call("synchronize")
-    barrier()
-    attempts_before = solver.advance(0)["attempted_steps"]
+    if args.min_seconds > 0:
+        timed_steps = max(timed_steps, int(np.ceil(args.min_seconds * steady_rate / period)) * period)
     dev.call("synchronize")
     barrier()
     # (the shader clock is sampled by a host thread WHILE the timed region runs: a reading taken in front of it would idle the GPU)
@@ -646,7 +730,7 @@ def main():
             if v is not None:
                 sclk_samples.append(v)
             sclk_stop.wait(0.4)
-    sampler = threading.Thread(target=sample_clock, daemon=True) if rank == 0 else None
+    sampler = threading.Thread(target=sample_clock, daemon=True) if rank == 0 and args.full else None
     if sampler:
         sampler.start()
     t0 = time.perf_counter()
@@ -661,7 +745,53 @@ def main():
     assert r["status"] == 0 and steps_done == timed_steps, (r["status_name"], steps_done)
     its_per_s = timed_steps / elapsed
     attempts = r["attempted_steps"]
-    timed_attempts = attempts - attempts_before  # rejected attempts cost a full set of kernels too
+    if rank == 0 and args.dump_outputs:
+        x, y, z = solver.solution()
+        dump_outputs(args.dump_outputs, solver_outputs(r, x, y, z))
+
+    def emit(roofline, conv, cpu):
+        if rank == 0:
+            info = capi.device_info(local_rank)
+            out = {
+                "metric": "pdlp_iterations_per_sec", "value": round(its_per_s, 2), "unit": "iterations/s",
+                "n_gpus": world, "rccl_nranks": world if dist is not None else 0, "steps": args.steps, "warmup": args.warmup, "timed_steps": timed_steps, "warmup_done": pre, "clock_warmup_batches": len(warm_rates),
+                "ms_per_step": round(1e3 * elapsed / timed_steps, 5), "higher_is_better": True,
+                "scaling": "strong", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+                "config": {"workload": "%s: synthetic %s sparse LP S(m=%d,n=%d,k=%d,seed=%d%s), nnz=%d, longest row %d, CSR fp64/int32, "
+                                       "Stable2 preset, tolerances 0 (fixed iteration budget)"
+                                       % (args.workload, ("structured (cuopt_amd/synthetic.py generate_structured)" if structured else "random") + (", rows and columns shuffled (synthetic.shuffled, seed 5)" if shuffle else ""),
+                                          m, n, cfg["k"], cfg["seed"], (",hard" if cfg.get("hard") else "") + (",band=%d" % cfg["band"] if cfg.get("band") else ""),
+                                          nnz, int(np.diff(p["offsets"]).max())),
+                           "rows": m, "cols": n, "nnz": nnz,
+                           "parallelism": ("row-block x%d + RCCL %s" % (world, {1: "all-reduce (replicated primal)", 2: "reduce-scatter / all-gather (sliced primal)",
+                                                                           3: "owner computes: all-gather(xbar) + all-gather(y'), rows and columns of A per rank"}.get(dataflow, "?") + transport)) if world > 1 else "single GPU"},
+                "roofline": roofline, "cpu_baseline": cpu, "time_to_1e-4": conv, "sharding": sharding,
+                "spmv_layout": layout, "setup_reordering": reorder, "attempted_steps": attempts, "setup_seconds": round(setup_s, 4), "generate_seconds": round(t_gen, 2),
+                "device": info["name"], "compute_units": info["compute_units"], "sclk_mhz_during_timed_region": {"samples": len(sclk_samples), "min": min(sclk_samples) if sclk_samples else None, "max": max(sclk_samples) if sclk_samples else None},
+            }
+            sys.stdout.flush()
+            os.write(record_fd, (json.dumps(out) + "\n").encode())
+        if dist is not None:
+            dist.destroy_process_group()
+
+    if not args.full:  # a plain run: the headline figure and nothing else
+        solver.close()
+        emit(None, None, None)
+        return
+
+    # ---- the attempt time the per-kernel times are held against (the guard below), from a run of its own over whole
+    # major-iteration periods and at least 2 s: the timed region above may be a few steps long
+    solver.advance((period - timed_steps % period) % period)
+    dev.call("synchronize")
+    barrier()
+    guard_steps = max(5, int(np.ceil(2.0 * steady_rate / period))) * period
+    guard_attempts_before = solver.advance(0)["attempted_steps"]
+    t0 = time.perf_counter()
+    rg = solver.advance(guard_steps)
+    dev.call("synchronize")
+    barrier()
+    guard_elapsed = max_over_ranks(time.perf_counter() - t0)
+    guard_attempts = rg["attempted_steps"] - guard_attempts_before  # rejected attempts cost a full set of kernels too
 
     # ---- per-kernel timing with HIP events on the solver stream (dominant kernel -> roofline) --------
     r0, r1 = solver.row_range()
@@ -711,10 +841,10 @@ def main():
                     "%s: separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of `bench.py --workload %s` on the tree of round %s (scripts/gpu_session.sh pmc:%s; "
                     "2*FETCH+WRITE KiB, MI355X_MICROARCH.md HBM section) -- NOT measured by this run: counters cannot be read from inside the process%s"
                     % (traffic_file, args.workload, traffic_file.split("/")[1][1:3], args.workload, "" if traffic_file.startswith("profiles/r06") else "; an OLDER round's pass, kept because the kernel's timing has not moved since"))
-    # Guard (round-3 review): the four kernels of an attempt, each timed on its own, must add up to the time of an attempt as the timed
-    # region saw it (the rest is the amortised major-iteration work and the graph's launch gaps).  A call site whose launches are not
+    # Guard (round-3 review): the four kernels of an attempt, each timed on its own, must add up to the time of an attempt as the guard
+    # run above saw it (the rest is the amortised major-iteration work and the graph's launch gaps).  A call site whose launches are not
     # all summed (a multi-launch layout timed as one phase), or a timed region that skipped work, shows up here.
-    per_attempt_ms = 1e3 * elapsed / max(timed_attempts, 1)
+    per_attempt_ms = 1e3 * guard_elapsed / max(guard_attempts, 1)
     ksum = sum(kernels[k] for k in ("PRIMAL", "SPMV_A_DUAL", "SPMV_AT_STEP", "STEP_DECISION"))
     roofline["attempt_kernels_ms"] = round(ksum, 5)
     roofline["ms_per_attempt"] = round(per_attempt_ms, 5)
@@ -744,29 +874,7 @@ def main():
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline_block(p)
 
-    if rank == 0:
-        info = capi.device_info(local_rank)
-        out = {
-            "metric": "pdlp_iterations_per_sec", "value": round(its_per_s, 2), "unit": "iterations/s",
-            "n_gpus": world, "rccl_nranks": world if dist is not None else 0, "steps": args.steps, "warmup": args.warmup, "timed_steps": timed_steps, "warmup_done": pre, "clock_warmup_batches": len(warm_rates),
-            "ms_per_step": round(1e3 * elapsed / timed_steps, 5), "higher_is_better": True,
-            "scaling": "strong", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-            "config": {"workload": "%s: synthetic %s sparse LP S(m=%d,n=%d,k=%d,seed=%d%s), nnz=%d, longest row %d, CSR fp64/int32, "
-                                   "Stable2 preset, tolerances 0 (fixed iteration budget)"
-                                   % (args.workload, ("structured (cuopt_amd/synthetic.py generate_structured)" if structured else "random") + (", rows and columns shuffled (synthetic.shuffled, seed 5)" if shuffle else ""),
-                                      m, n, cfg["k"], cfg["seed"], (",hard" if cfg.get("hard") else "") + (",band=%d" % cfg["band"] if cfg.get("band") else ""),
-                                      nnz, int(np.diff(p["offsets"]).max())),
-                       "rows": m, "cols": n, "nnz": nnz,
-                       "parallelism": ("row-block x%d + RCCL %s" % (world, {1: "all-reduce (replicated primal)", 2: "reduce-scatter / all-gather (sliced primal)",
-                                                                       3: "owner computes: all-gather(xbar) + all-gather(y'), rows and columns of A per rank"}.get(dataflow, "?") + transport)) if world > 1 else "single GPU"},
-            "roofline": roofline, "cpu_baseline": cpu, "time_to_1e-4": conv, "sharding": sharding,
-            "spmv_layout": layout, "setup_reordering": reorder, "attempted_steps": attempts, "setup_seconds": round(setup_s, 4), "generate_seconds": round(t_gen, 2),
-            "device": info["name"], "compute_units": info["compute_units"], "sclk_mhz_during_timed_region": {"samples": len(sclk_samples), "min": min(sclk_samples) if sclk_samples else None, "max": max(sclk_samples) if sclk_samples else None},
-        }
-        sys.stdout.flush()
-        os.write(record_fd, (json.dumps(out) + "\n").encode())
-    if dist is not None:
-        dist.destroy_process_group()
+    emit(roofline, conv, cpu)
 
 
 if __name__ == "__main__":

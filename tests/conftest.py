@@ -12,8 +12,14 @@ os.environ.setdefault("OMP_WAIT_POLICY", "passive")
 # rank's consumer kernel SPINS until its peers' flags arrive.  HIP multiplexes streams onto GPU_MAX_HW_QUEUES hardware queues (default
 # 4): two ranks on one queue = a spinning kernel in front of the producer it waits for = a 5-second timeout (found in round 6, by a
 # test that ran world 2 and world 4 in one process).  One queue per rank; production runs one rank per device and never shares one.
-# Must be in the environment before the HIP runtime initialises, i.e. before cuopt_amd.capi loads the library.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
+# Must be in the environment before the HIP runtime initialises, i.e. before cuopt_amd.capi loads the library.  A smaller value
+# already in the environment (a launcher that exports the runtime's default of 4) is raised: eight ranks cannot share four queues.
+try:
+    _queues = int(os.environ.get("GPU_MAX_HW_QUEUES", "0"))
+except ValueError:
+    _queues = 0
+if _queues < 16:
+    os.environ["GPU_MAX_HW_QUEUES"] = "16"
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:

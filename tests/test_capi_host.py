@@ -123,17 +123,16 @@ def test_mps_round_trip_through_own_writer(golden_problems, tmp_path):
             np.testing.assert_allclose(d[k], p[k], rtol=0, atol=0, err_msg="%s:%s" % (name, k))
 
 
-REF_DIR = "/root/reference/datasets/linear_programming"
+MPS_DIR = os.path.join(ROOT, "tests", "golden", "mps")  # (the reference's datasets/linear_programming/*.mps, stored verbatim)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_DIR), reason="reference datasets only exist in the build container")
 def test_mps_reader_matches_reference_parser_on_all_fixtures(golden_parser):
     """every datasets/linear_programming/*.mps: same accept/reject decision as the reference's parser
     in free-format mode, and identical CSR / bounds / objective when accepted."""
     checked = 0
     for name, ref in sorted(golden_parser.items()):
         h = C.c_void_p()
-        rc = capi.lib.cuOptReadProblem(os.fsencode(os.path.join(REF_DIR, name)), C.byref(h))
+        rc = capi.lib.cuOptReadProblem(os.fsencode(os.path.join(MPS_DIR, name)), C.byref(h))
         if not ref["ok"]:
             assert rc == capi.CUOPT_MPS_PARSE_ERROR, name
             continue
