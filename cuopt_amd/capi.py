@@ -101,7 +101,8 @@ class SolverSettings(C.Structure):
                 ("dual_infeasible_tolerance", c_double), ("save_best_primal_so_far", c_int),
                 ("log_to_console", c_int), ("log_file", c_char_p), ("unbounded_from_feasible_iterates", c_int),
                 ("accept_enabled", c_int), ("accept_tolerance", c_double * 6),
-                ("relative_primal_tolerance_factor", c_double), ("relative_dual_tolerance_factor", c_double)]
+                ("relative_primal_tolerance_factor", c_double), ("relative_dual_tolerance_factor", c_double),
+                ("batch_lanes", c_int)]
 
 
 class Result(C.Structure):

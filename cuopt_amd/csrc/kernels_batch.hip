@@ -15,7 +15,8 @@
 //     accumulates rows t, t + 512, ... in ascending order, the same wave tree (ds_swizzle butterflies) and wave-by-wave sum as
 //     block_reduce (CSR stream layout: workgroup <-> row block, 256 "threads", four waves).  Hence the restriction: each matrix in
 //     the row-sum variant of the panels or in the CSR stream layout, no row beyond 128 entries, no dense segments, columns ascending
-//     within rows (else: not eligible, the caller keeps its independent solves).
+//     within rows (else: not eligible, the caller keeps its independent solves).  Round 7 adds the jagged layout (kbj_*, below) for
+//     parents created with cuoptamd_settings::batch_lanes >= K.
 // What it buys (C3, 1e6 x 1e6, 1e7 nonzeros; profiles/r05_bench_lines.jsonl, c3_batch16 / c3_batch8): 14.7 k iterations/s aggregate
 // over 16 LPs, 10.7 k over 8, against 6.0 k for one -- 2.43x / 1.77x; K = 4: 1.24x; K = 2: 0.80x (two single solves are faster).
 // Why not more: only the MATRIX is shared.  A lockstep iteration of 8 LPs moves 1.85 GB at the fused floor (0.24 GB of matrix once,
@@ -396,6 +397,210 @@ __global__ void __launch_bounds__(kBT) kb_at_step(int W, const int32_t* __restri
   batch_block_partials<K, 2, VW>(S, acc, lp, false, W, w);
 }
 
+// ---- (2), (3) on the JAGGED layout (kernels_jag.hip, spmv_jag.hpp jag_block): the single kernels' workgroups, waves and passes -------
+// A workgroup owns one block of the single layout, a wave its share of the sorted passes, a lane one row of a pass: the lane sums its row
+// for all K LPs in diagonal order -- per entry one value and column, then the K values of that column as ONE contiguous piece of the
+// interleaved vector (64 bytes at K = 8, 128 at K = 16: a block's column window times K stays in L2), and K sums in registers, each the
+// single kernel's chain for its LP.  The LDS cannot hold K interleaved column windows; it holds the K row-sum strips instead (LP-major,
+// an odd pitch P >= the block's rows), which is why a layout built for batches of up to L LPs caps its blocks at kJagBatchRows / L rows
+// (jag_batch_rows).  The fused epilogue then runs thread <-> row as in jag_block: thread t takes rows t, t + T, ... of each LP in
+// ascending order, so its accumulators are jag_block's and block_reduce<Op, K * NQ, WAVES> reduces every LP with jag_block's own tree.
+// Blocks with rows longer than kLongRow (their own workgroups, partials after the blocks') and dense segments are not served: the
+// batch refuses such a side (pdlpdev_batch_create).
+// LDS hazards (round-7 audit, docs/design/10): strip[] is zeroed before barrier B1; every entry is then written by exactly one lane (the
+// lane of its row's pass) and read behind B2 by the epilogue's thread of that row, which (A side) overwrites it with the row's y';
+// the interleaved copy-out reads the strips behind B3.  red[] (after the strips, never aliased) takes each wave's sums of each LP from
+// lane 0 of that wave, one entry per (wave, LP, quantity), and is read behind B4.  No barrier inside the passes.
+template <int K, int WAVES>
+struct JagBatchGeometry {
+  // diagonals requested per round: U x K gathered values in flight per lane (16 waves: half as many, 128 VGPRs a lane)
+  static constexpr int U = (WAVES == 16 ? 16 : 32) / K < 1 ? 1 : (WAVES == 16 ? 16 : 32) / K > 8 ? 8 : (WAVES == 16 ? 16 : 32) / K;
+};
+
+template <int K, int WAVES>
+__device__ __forceinline__ void batch_jag_sums(const JagView& J, int blk, int P, const double* __restrict__ vK, double* strip)
+{
+  constexpr int U = JagBatchGeometry<K, WAVES>::U;
+  const int lane     = threadIdx.x & 63;
+  const int wave     = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int g        = blk * WAVES + wave;
+  const int wbase    = J.win[2 * blk];
+  const int wlen     = J.win[2 * blk + 1];
+  const int s0       = J.set_ptr[blk];
+  int e              = __builtin_amdgcn_readfirstlane(J.tile_e[g]);
+  const int sr0      = __builtin_amdgcn_readfirstlane(J.tile_sr[g]);
+  const int ns       = __builtin_amdgcn_readfirstlane(J.tile_sr[g + 1]) - sr0;
+  for (int p0 = 0; p0 < ns; p0 += 64) {
+    const int i      = p0 + lane;
+    const bool have  = i < ns;
+    const unsigned d = have ? J.sr[sr0 + i] : 0u;
+    const int cnt    = have ? (int)(d >> 16) + 1 : 0;
+    const int lrow   = (int)(d & 0xFFFFu);
+    double sum[K];
+#pragma unroll
+    for (int l = 0; l < K; ++l) sum[l] = 0.0;
+    const int kmax = __builtin_amdgcn_readfirstlane(cnt);  // sorted: lane 0 holds the longest row of the pass
+    for (int k0 = 0; k0 < kmax; k0 += U) {
+      int at[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {  // diagonal k holds one entry per row longer than k: a prefix of the lanes
+        at[u] = e;
+        e += __builtin_popcountll(__ballot(cnt > k0 + u));
+      }
+      double a[U];
+      unsigned sl[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        a[u] = 0.0, sl[u] = 0;
+        if (cnt > k0 + u) {
+          a[u]  = __builtin_nontemporal_load(J.val + at[u] + lane);
+          sl[u] = __builtin_nontemporal_load(J.slot + at[u] + lane);
+        }
+      }
+      unsigned col[U];  // the entry's column: the window's base + slot, or the block's column list at the slot
+#pragma unroll
+      for (int u = 0; u < U; ++u) col[u] = wlen ? (unsigned)wbase + sl[u] : (unsigned)J.set_col[s0 + (int)sl[u]];
+      double2 xv[U][K / 2];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const double2* src = (const double2*)(vK + col[u] * (unsigned)K);
+#pragma unroll
+        for (int h = 0; h < K / 2; ++h) xv[u][h] = cnt > k0 + u ? src[h] : double2{0.0, 0.0};
+      }
+      // lanes past their row's end add +0.0 * 0.0, as in jag_block: no bit changes
+#pragma unroll
+      for (int u = 0; u < U; ++u)
+#pragma unroll
+        for (int h = 0; h < K / 2; ++h) {
+          sum[2 * h]     = sum[2 * h] + a[u] * xv[u][h].x;
+          sum[2 * h + 1] = sum[2 * h + 1] + a[u] * xv[u][h].y;
+        }
+    }
+    if (have)
+#pragma unroll
+      for (int l = 0; l < K; ++l) strip[l * P + lrow] = sum[l];
+  }
+}
+
+// the grid is jag_block's (nlong == 0: the row blocks only); false for the padding workgroups
+__device__ __forceinline__ bool batch_jag_block(const JagView& J, int* blk)
+{
+  if ((int)blockIdx.x >= ((J.nblk + 7) & ~7)) return false;
+  *blk = xcd_remap((int)blockIdx.x, J.nblk);
+  return *blk < J.nblk;
+}
+
+// block_reduce<SumOp, NQ, WAVES> of LP l's accumulators, in two halves: the wave sums go to red[] (its own LDS, after the strips) as the
+// epilogue finishes each LP ...
+template <int NQ, int K>
+__device__ __forceinline__ void batch_jag_wave_sums(double (&acc)[NQ], double* red, int l)
+{
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) {
+    const double v = wave_reduce<SumOp>(acc[q]);
+    if (lane == 0) red[(wave * K + l) * NQ + q] = v;
+  }
+}
+// ... and, behind a barrier, one thread per (LP, quantity) adds the waves' sums up in block_reduce's order
+template <int K, int NQ, int WAVES>
+__device__ __forceinline__ void batch_jag_partials(const double* red, const BatchLp* __restrict__ lp, bool a_side, int nparts, int blk)
+{
+  __syncthreads();  // (B4)
+  if ((int)threadIdx.x < K * NQ) {
+    const int l = threadIdx.x / NQ, q = threadIdx.x % NQ;
+    const BatchLp& L = lp[l];
+    if (loop_active(L.ctl)) {
+      double total = red[l * NQ + q];
+      for (int w = 1; w < WAVES; ++w) total = total + red[(w * K + l) * NQ + q];
+      (a_side ? L.part_a : L.part_at)[(size_t)q * nparts + blk] = total;
+    }
+  }
+}
+
+// rows of A for K LPs on the jagged layout: DualEpilogue per LP (kb_a_dual's expressions), y' also interleaved into yK
+template <int K, int WAVES>
+__global__ void __launch_bounds__(WAVES * 64) kbj_a_dual(JagView J, int P, const BatchLp* __restrict__ lp, const double* __restrict__ xK, double* __restrict__ yK)
+{
+  extern __shared__ __attribute__((aligned(16))) double kbj_lds[];
+  constexpr int T = WAVES * 64;
+  double* red = kbj_lds + K * P;
+  int blk;
+  if (!batch_jag_block(J, &blk)) return;
+  const int row0 = J.row0[blk], brows = J.row0[blk + 1] - row0;
+  for (int f = threadIdx.x; f < K * P; f += T) kbj_lds[f] = 0.0;  // rows without nonzeros
+  __syncthreads();  // (B1)
+  batch_jag_sums<K, WAVES>(J, blk, P, xK, kbj_lds);
+  __syncthreads();  // (B2: the strips are complete)
+  for (int l = 0; l < K; ++l) {
+    const BatchLp& L = lp[l];
+    if (!loop_active(L.ctl)) continue;
+    const int cur      = L.ctl->cur;
+    const double sigma = L.ctl->sigma, weight = L.ctl->step_size;
+    const bool pend    = L.ctl->pending_avg != 0;
+    const double* __restrict__ y = cur ? L.y1 : L.y0;
+    double* __restrict__ yn      = cur ? L.y0 : L.y1;
+    double acc[1]                = {0.0};
+    for (int r = threadIdx.x; r < brows; r += T) {
+      const int i = row0 + r;
+      if (i >= J.rows) continue;
+      const double yi  = y[i];
+      const double lo  = L.lo[i], hi = L.hi[i], sy = pend ? L.sumy[i] : 0.0;
+      double next      = yi - (sigma * kbj_lds[l * P + r]);
+      const double low = next + sigma * lo;
+      const double up  = next + sigma * hi;
+      next             = dmax(low, dmin(up, 0.0));
+      yn[i]            = next;
+      kbj_lds[l * P + r] = next;  // (this thread's own entry: read just above)
+      const double dy = next - yi;
+      acc[0] += dy * dy;
+      if (pend) L.sumy[i] = sy + weight * yi;
+    }
+    batch_jag_wave_sums<1, K>(acc, red, l);
+  }
+  __syncthreads();  // (B3: y' of every LP in the strips) -> whole entries of the interleaved vector
+  for (int f = threadIdx.x; f < brows * K; f += T) yK[(size_t)row0 * K + f] = kbj_lds[(f % K) * P + f / K];
+  batch_jag_partials<K, 1, WAVES>(red, lp, true, J.nblk, blk);
+}
+
+// rows of A^T for K LPs on the jagged layout: StepEpilogue per LP
+template <int K, int WAVES>
+__global__ void __launch_bounds__(WAVES * 64) kbj_at_step(JagView J, int P, const BatchLp* __restrict__ lp, const double* __restrict__ yK)
+{
+  extern __shared__ __attribute__((aligned(16))) double kbj_lds[];
+  constexpr int T = WAVES * 64;
+  double* red = kbj_lds + K * P;
+  int blk;
+  if (!batch_jag_block(J, &blk)) return;
+  const int row0 = J.row0[blk], brows = J.row0[blk + 1] - row0;
+  for (int f = threadIdx.x; f < K * P; f += T) kbj_lds[f] = 0.0;
+  __syncthreads();  // (B1)
+  batch_jag_sums<K, WAVES>(J, blk, P, yK, kbj_lds);
+  __syncthreads();  // (B2)
+  for (int l = 0; l < K; ++l) {
+    const BatchLp& L = lp[l];
+    if (!loop_active(L.ctl)) continue;
+    const int cur = L.ctl->cur;
+    const double* __restrict__ x   = cur ? L.x1 : L.x0;
+    const double* __restrict__ xn  = cur ? L.x0 : L.x1;
+    const double* __restrict__ aty = cur ? L.aty1 : L.aty0;
+    double* __restrict__ atyn      = cur ? L.aty0 : L.aty1;
+    double acc[2]                  = {0.0, 0.0};
+    for (int r = threadIdx.x; r < brows; r += T) {
+      const int j = row0 + r;
+      if (j >= J.rows) continue;
+      const double v  = kbj_lds[l * P + r];
+      atyn[j]         = v;
+      const double dx = xn[j] - x[j];
+      const double t  = v - aty[j];
+      acc[0] += t * dx;
+      acc[1] += dx * dx;
+    }
+    batch_jag_wave_sums<2, K>(acc, red, l);
+  }
+  batch_jag_partials<K, 2, WAVES>(red, lp, false, J.nblk, blk);
+}
+
 // columns ascending within every row?  (the panels add a row's products slab by slab = by ascending column; the batched products
 // walk the CSR row: the same order only then)
 __global__ void __launch_bounds__(256) kb_check_sorted(int rows, const int32_t* __restrict__ off, const int32_t* __restrict__ idx, int* __restrict__ bad)
@@ -417,10 +622,15 @@ struct pdlpdev_batch {
   double *xK = nullptr, *yK = nullptr;
   // the row blocks whose partial sums the products reproduce: the panels of the single-LP layout (512 "threads"), or the row blocks
   // of the CSR stream kernels (256)
+  // ... or the blocks of the jagged layout (kbj_*: the strips of K LPs, pitch P, `lds` bytes of dynamic LDS)
   struct Side {
     int W = 0;
     const int32_t* row0 = nullptr;
     bool panel = false;
+    bool jag = false;
+    JagView jv{};
+    int P = 0;
+    size_t lds = 0;
   } a_side, t_side;
   std::vector<BatchLp> lp_host;  // what lp_dev holds
   std::map<int, hipGraphExec_t> graphs;
@@ -458,6 +668,13 @@ static int batch_fetch_ctl(pdlpdev_batch* b)
   return 0;
 }
 
+template <int K>
+static const void* batch_jag_kernel(const pdlpdev_batch::Side& S, bool a_side)
+{
+  if (a_side) return S.jv.waves == 16 ? (const void*)kbj_a_dual<K, 16> : (const void*)kbj_a_dual<K, 8>;
+  return S.jv.waves == 16 ? (const void*)kbj_at_step<K, 16> : (const void*)kbj_at_step<K, 8>;
+}
+
 // (ev != nullptr: the four dispatches carry start / stop events -- hipExtLaunchKernel's own timestamps, no records between them)
 template <int K>
 static int batch_enqueue_attempt(pdlpdev_batch* b, hipEvent_t* ev = nullptr)
@@ -469,21 +686,38 @@ static int batch_enqueue_attempt(pdlpdev_batch* b, hipEvent_t* ev = nullptr)
   const int32_t *arow0 = b->a_side.row0, *trow0 = b->t_side.row0;
   const bool ap = b->a_side.panel, tp = b->t_side.panel;
   const int pgrid = std::min((n + kBT - 1) / kBT, 4096);
+  // per side: the CSR-walking products (panels / CSR stream), or the jagged layout's
+  const pdlpdev_batch::Side &A = b->a_side, &T = b->t_side;
+  auto jgrid = [](const pdlpdev_batch::Side& S) { return dim3((S.jv.nblk + 7) & ~7); };
   if (ev) {
+    JagView ajv = A.jv, tjv = T.jv;
+    int aP = A.P, tP = T.P;
     void* a0[] = {&b->lp_dev, &n, &b->xK};
     void* a1[] = {&aw, &arow0, &c0->ha_off, &c0->ha_idx, &c0->ha_val, &b->lp_dev, &b->xK, &b->yK};
     void* a2[] = {&tw, &trow0, &c0->hat_off, &c0->hat_idx, &c0->hat_val, &b->lp_dev, &b->yK};
+    void* j1[] = {&ajv, &aP, &b->lp_dev, &b->xK, &b->yK};
+    void* j2[] = {&tjv, &tP, &b->lp_dev, &b->yK};
     void* a3[] = {&b->dargs_dev};
     HIP_TRY(hipExtLaunchKernel((const void*)kb_primal<K>, dim3(pgrid), dim3(kBT), a0, 0, s, ev[0], ev[1], 0));
-    HIP_TRY(hipExtLaunchKernel(ap ? (const void*)kb_a_dual<K, 8> : (const void*)kb_a_dual<K, 4>, dim3(aw), dim3(kBT), a1, 0, s, ev[2], ev[3], 0));
-    HIP_TRY(hipExtLaunchKernel(tp ? (const void*)kb_at_step<K, 8> : (const void*)kb_at_step<K, 4>, dim3(tw), dim3(kBT), a2, 0, s, ev[4], ev[5], 0));
+    if (A.jag)
+      HIP_TRY(hipExtLaunchKernel(batch_jag_kernel<K>(A, true), jgrid(A), dim3(A.jv.waves * 64), j1, A.lds, s, ev[2], ev[3], 0));
+    else
+      HIP_TRY(hipExtLaunchKernel(ap ? (const void*)kb_a_dual<K, 8> : (const void*)kb_a_dual<K, 4>, dim3(aw), dim3(kBT), a1, 0, s, ev[2], ev[3], 0));
+    if (T.jag)
+      HIP_TRY(hipExtLaunchKernel(batch_jag_kernel<K>(T, false), jgrid(T), dim3(T.jv.waves * 64), j2, T.lds, s, ev[4], ev[5], 0));
+    else
+      HIP_TRY(hipExtLaunchKernel(tp ? (const void*)kb_at_step<K, 8> : (const void*)kb_at_step<K, 4>, dim3(tw), dim3(kBT), a2, 0, s, ev[4], ev[5], 0));
     HIP_TRY(hipExtLaunchKernel((const void*)k_step_decision_batch, dim3(K), dim3(1024), a3, 0, s, ev[6], ev[7], 0));
     return 0;
   }
   kb_primal<K><<<pgrid, kBT, 0, s>>>(b->lp_dev, n, b->xK);
-  if (ap) kb_a_dual<K, 8><<<aw, kBT, 0, s>>>(aw, arow0, c0->ha_off, c0->ha_idx, c0->ha_val, b->lp_dev, b->xK, b->yK);
+  if (A.jag && A.jv.waves == 16) kbj_a_dual<K, 16><<<jgrid(A), 1024, A.lds, s>>>(A.jv, A.P, b->lp_dev, b->xK, b->yK);
+  else if (A.jag) kbj_a_dual<K, 8><<<jgrid(A), 512, A.lds, s>>>(A.jv, A.P, b->lp_dev, b->xK, b->yK);
+  else if (ap) kb_a_dual<K, 8><<<aw, kBT, 0, s>>>(aw, arow0, c0->ha_off, c0->ha_idx, c0->ha_val, b->lp_dev, b->xK, b->yK);
   else kb_a_dual<K, 4><<<aw, kBT, 0, s>>>(aw, arow0, c0->ha_off, c0->ha_idx, c0->ha_val, b->lp_dev, b->xK, b->yK);
-  if (tp) kb_at_step<K, 8><<<tw, kBT, 0, s>>>(tw, trow0, c0->hat_off, c0->hat_idx, c0->hat_val, b->lp_dev, b->yK);
+  if (T.jag && T.jv.waves == 16) kbj_at_step<K, 16><<<jgrid(T), 1024, T.lds, s>>>(T.jv, T.P, b->lp_dev, b->yK);
+  else if (T.jag) kbj_at_step<K, 8><<<jgrid(T), 512, T.lds, s>>>(T.jv, T.P, b->lp_dev, b->yK);
+  else if (tp) kb_at_step<K, 8><<<tw, kBT, 0, s>>>(tw, trow0, c0->hat_off, c0->hat_idx, c0->hat_val, b->lp_dev, b->yK);
   else kb_at_step<K, 4><<<tw, kBT, 0, s>>>(tw, trow0, c0->hat_off, c0->hat_idx, c0->hat_val, b->lp_dev, b->yK);
   k_step_decision_batch<<<K, 1024, 0, s>>>(b->dargs_dev);
   LAUNCH_CHECK();
@@ -610,20 +844,42 @@ int pdlpdev_batch_create(pdlpdev_batch** out, pdlpdev_ctx** ctx, int K)
       if (ctx[q] == ctx[l]) return fail(-1, "pdlpdev_batch_create: LP %d and LP %d are the same context (two lanes would share one set of iterates)", q, l);
   for (int l = 0; l < K; ++l) {
     pdlpdev_ctx* c = ctx[l];
-    if (!c || c->ha_off != c0->ha_off || c->hat_off != c0->hat_off || c->pa.v.row0 != c0->pa.v.row0 || c->stream != c0->stream)
+    if (!c || c->ha_off != c0->ha_off || c->hat_off != c0->hat_off || c->pa.v.row0 != c0->pa.v.row0 || c->ja.v.row0 != c0->ja.v.row0 ||
+        c->jat.v.row0 != c0->jat.v.row0 || c->ja.v.val != c0->ja.v.val || c->jat.v.val != c0->jat.v.val || c->stream != c0->stream)
       return fail(-1, "pdlpdev_batch_create: the contexts do not share one matrix (pdlpdev_clone_shared)");
   }
   if ((int64_t)std::max(c0->m, c0->n) * K >= ((int64_t)1 << 32))
     return fail(-7, "pdlpdev_batch_create: not eligible (the interleaved vectors are addressed with 32-bit element offsets: max(m, n) * K < 2^32)");
-  // per side: the row-sum variant of the panels, or the CSR stream layout -- the two whose rows are summed left to right by one lane and
-  // whose per-block reduction the batched products reproduce
+  // per side: the row-sum variant of the panels, the CSR stream layout or the jagged layout -- the three whose rows are summed by one lane
+  // and whose per-block reduction the batched products reproduce
   pdlpdev_batch::Side side[2];
+  HIP_TRY(hipSetDevice(c0->device));
   for (int t = 0; t < 2; ++t) {
     const pdlpdev_ctx::Panels& P = t ? c0->pat : c0->pa;
-    const bool jag = t ? c0->jat.on : c0->ja.on, pb = t ? c0->pbat.on : c0->pba.on;
+    const pdlpdev_ctx::Jag& Jg = t ? c0->jat : c0->ja;
+    const bool jag = Jg.on, pb = t ? c0->pbat.on : c0->pba.on;
     const int nlong = t ? c0->at_nlong : c0->a_nlong;
-    bool ok = !jag && !pb && nlong == 0;
-    if (ok && P.on) {
+    if (jag && c0->batch_lanes < K)
+      return fail(-7, "pdlpdev_batch_create: not eligible (the %s side is in the jagged layout: lockstep batches of %d LPs on it need a parent created "
+                      "with batch_lanes >= %d, cuoptamd_settings::batch_lanes; this one has %d)", t ? "A^T" : "A", K, K, c0->batch_lanes);
+    bool ok = !pb && nlong == 0;
+    if (ok && jag) {
+      if (Jg.v.nlong != 0 || Jg.v.dense_add || Jg.v.nblk <= 0)
+        return fail(-7, "pdlpdev_batch_create: not eligible (the %s side is jagged with %d rows of more than %d entries%s: the jagged lockstep "
+                        "products serve blocks of short rows only)", t ? "A^T" : "A", Jg.v.nlong, kLongRow, Jg.v.dense_add ? " and dense segments" : "");
+      {  // the strips' pitch: odd (conflict-free transposition), at least the largest block's rows
+        std::vector<int32_t> r0((size_t)Jg.v.nblk + 1);
+        HIP_TRY(hipMemcpyAsync(r0.data(), Jg.v.row0, r0.size() * sizeof(int32_t), hipMemcpyDeviceToHost, c0->stream));
+        HIP_TRY(hipStreamSynchronize(c0->stream));
+        int rmax = 1;
+        for (int q = 0; q < Jg.v.nblk; ++q) rmax = std::max(rmax, r0[q + 1] - r0[q]);
+        pdlpdev_batch::Side S;
+        S.W = Jg.v.nblk, S.jag = true, S.jv = Jg.v, S.P = rmax | 1;
+        S.lds = sizeof(double) * ((size_t)K * S.P + (size_t)Jg.v.waves * K * 2);  // (the strips, then the wave sums)
+        if (S.lds > 160 * 1024) return fail(-1, "pdlpdev_batch_create: %d rows in one jagged block do not leave LDS for %d LPs", rmax, K);
+        side[t] = S;
+      }
+    } else if (ok && P.on) {
       ok      = !P.v.seg && !P.v.own_row && !P.v.any_long && !P.v.dense_add;
       side[t] = pdlpdev_batch::Side{P.v.W, P.v.row0, true};
     } else if (ok) {
@@ -631,11 +887,11 @@ int pdlpdev_batch_create(pdlpdev_batch** out, pdlpdev_ctx** ctx, int K)
       ok      = side[t].W > 0 && side[t].row0 != nullptr;
     }
     if (!ok || c0->dense.on || c0->comm || c0->small_resident)
-      return fail(-7, "pdlpdev_batch_create: not eligible (the batched products reproduce the reductions of the row-sum panels and of the CSR stream "
-                      "kernels: both matrices in one of these layouts, no row of more than %d entries, no dense segments, one GPU, not the resident "
-                      "small-LP loop)", kLongRow);
+      return fail(-7, "pdlpdev_batch_create: not eligible (%s side: %s; the batched products reproduce the reductions of the row-sum panels, of the CSR stream "
+                      "kernels and of the jagged layout: both matrices in one of these layouts, no row of more than %d entries, no dense segments, one "
+                      "GPU, not the resident small-LP loop)", t ? "A^T" : "A",
+                      pb ? "gather-free layout" : nlong ? "rows longer than kLongRow" : P.on ? "panels of the long-tail / own-row variant" : "CSR stream", kLongRow);
   }
-  HIP_TRY(hipSetDevice(c0->device));
   {
     struct Flag {  // (released on every way out)
       int* p = nullptr;
@@ -644,14 +900,21 @@ int pdlpdev_batch_create(pdlpdev_batch** out, pdlpdev_ctx** ctx, int K)
     HIP_TRY(hipMalloc((void**)&flag.p, sizeof(int)));
     int* bad = flag.p;
     HIP_TRY(hipMemsetAsync(bad, 0, sizeof(int), c0->stream));
-    kb_check_sorted<<<2048, 256, 0, c0->stream>>>(c0->m, c0->ha_off, c0->ha_idx, bad);
-    kb_check_sorted<<<2048, 256, 0, c0->stream>>>(c0->n, c0->hat_off, c0->hat_idx, bad);
+    // (the jagged products walk a row in its CSR order, as the single kernel does: no condition there)
+    if (!side[0].jag) kb_check_sorted<<<2048, 256, 0, c0->stream>>>(c0->m, c0->ha_off, c0->ha_idx, bad);
+    if (!side[1].jag) kb_check_sorted<<<2048, 256, 0, c0->stream>>>(c0->n, c0->hat_off, c0->hat_idx, bad);
     LAUNCH_CHECK();
     int h = 0;
     HIP_TRY(hipMemcpyAsync(&h, bad, sizeof(int), hipMemcpyDeviceToHost, c0->stream));
     HIP_TRY(hipStreamSynchronize(c0->stream));
     if (h) return fail(-7, "pdlpdev_batch_create: not eligible (column indices are not ascending within the rows)");
   }
+  for (int t = 0; t < 2; ++t)  // (the jagged products' strips: dynamic LDS beyond the default limit; the attribute is per kernel and device)
+    if (side[t].jag) {
+      const void* f = K == 16 ? batch_jag_kernel<16>(side[t], t == 0) : K == 8 ? batch_jag_kernel<8>(side[t], t == 0)
+                    : K == 4  ? batch_jag_kernel<4>(side[t], t == 0)  : batch_jag_kernel<2>(side[t], t == 0);
+      HIP_TRY(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    }
   pdlpdev_batch* b = new pdlpdev_batch();
   *out      = b;
   b->K = K, b->device = c0->device, b->stream = c0->stream;

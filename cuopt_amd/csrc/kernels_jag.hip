@@ -202,6 +202,13 @@ bool jag_geometry(int32_t rows, int mode, int* G_out, int* waves_out, int* wcap_
   return true;
 }
 
+// A solver created for lockstep batches (cuoptamd_settings::batch_lanes) caps its workgroups at kJagBatchRows / batch_lanes rows: the
+// batched products (kernels_batch.hip, kbj_*) keep the row sums of every LP of the batch in LDS, K strips of a workgroup's rows.
+int32_t jag_batch_rows(int32_t brows, int batch_lanes)
+{
+  return batch_lanes > 0 ? std::min<int32_t>(brows, kJagBatchRows / batch_lanes) : brows;
+}
+
 // A workgroup's rows: consecutive, at most `row_cap`, and as many as keep their DISTINCT columns within the LDS window
 // (rows longer than kLongRow do not count: they gather from global memory in workgroups of their own).  Greedy from
 // `first`; returns the end of the block.
@@ -275,13 +282,14 @@ double jag_estimate_on_samples(int nsamples, int32_t brows, int wcap, const int3
 }
 
 // `mode`: 0 = use the layout when filling the LDS column sets costs at most half of the gathers they serve, 1 = always
-JagHost build_jag(int32_t rows, int32_t cols, const int32_t* off, const int32_t* idx, int mode, int cus)
+JagHost build_jag(int32_t rows, int32_t cols, const int32_t* off, const int32_t* idx, int mode, int cus, int batch_lanes)
 {
   JagHost H;
   const int64_t nnz = rows > 0 ? off[rows] : 0;
   if (rows <= 0 || cols <= 0 || nnz <= 0) return H;
   int G = 0, waves = 8, wcap = 0, brows = 0;
   if (!jag_geometry(rows, mode, &G, &waves, &wcap, &brows)) return H;
+  brows           = jag_batch_rows(brows, batch_lanes);
   const int slots = cus * (waves == 16 ? 1 : 2);  // workgroups resident at once: 80 KiB of LDS each (160 KiB with 16 waves)
   auto block_end = [&](ColumnSet& set, int32_t first, int32_t limit, int32_t row_cap) {
     return jag_block_end(set, off, idx, wcap, first, limit, row_cap);

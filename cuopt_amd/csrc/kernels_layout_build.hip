@@ -1257,12 +1257,13 @@ k_jag_block_fill(const int32_t* __restrict__ row0, const int32_t* __restrict__ o
 }  // namespace
 
 int build_jag_device(pdlpdev_ctx* c, pdlpdev_ctx::Jag* dst, int32_t rows, int32_t cols, const int32_t* h_off, const int32_t* d_off, const int32_t* d_idx,
-                     const double* d_val, int mode, int cus)
+                     const double* d_val, int mode, int cus, int batch_lanes)
 {
   const int64_t nnz = rows > 0 ? h_off[rows] : 0;
   if (rows <= 0 || cols <= 0 || nnz <= 0) return 0;
   int G = 0, waves = 8, wcap = 0, brows = 0;
   if (!jag_geometry(rows, mode, &G, &waves, &wcap, &brows)) return 0;
+  brows = jag_batch_rows(brows, batch_lanes);  // (build_jag's cap, the same blocks)
   if (waves != 8) return 1;  // (the 16-wave geometry's table + list do not fit one workgroup's LDS: CUOPT_AMD_TUNE=jag_waves=16 builds on the host)
   hipStream_t s = c->stream;
   const bool timing = getenv("CUOPT_AMD_TIMING") != nullptr;

@@ -11,6 +11,7 @@ int sync_panel_values(pdlpdev_ctx* c);
 int resident_tier(int m, int n, int64_t nnz);
 
 static thread_local int g_create_sharded = 0;  // pdlpdev_create_hint: the next context will run behind a communicator
+static thread_local int g_create_batch_lanes = 0;  // pdlpdev_create_batch_lanes: the next context's jagged layouts serve batches that wide
 
 static int create_impl(pdlpdev_ctx** out, int device, int32_t m, int32_t n, const int32_t* a_offsets,
                        const int32_t* a_indices, const double* a_values, const int32_t* at_offsets,
@@ -22,6 +23,7 @@ extern "C" {
 
 const char* pdlpdev_last_error(void) { return g_err.c_str(); }
 void pdlpdev_create_hint(int sharded) { g_create_sharded = sharded; }
+void pdlpdev_create_batch_lanes(int lanes) { g_create_batch_lanes = lanes; }
 static thread_local pdlpdev_ctx* g_create_stream_donor = nullptr;
 void pdlpdev_create_share_stream(pdlpdev_ctx* donor) { g_create_stream_donor = donor; }
 int pdlpdev_resident_size(int32_t m, int32_t n, int64_t nnz) { return resident_tier(m, n, nnz) >= 0 ? 1 : 0; }
@@ -87,6 +89,10 @@ static int create_impl(pdlpdev_ctx** out, int device, int32_t m, int32_t n, cons
                        const double* hi, const double* lb, const double* ub, pdlpdev_analysis* an)
 {
   roctx::Range range("pdlp: device set-up (upload, layouts)");
+  const int batch_lanes = g_create_batch_lanes;
+  g_create_batch_lanes  = 0;
+  if (batch_lanes != 0 && batch_lanes != 2 && batch_lanes != 4 && batch_lanes != 8 && batch_lanes != 16)
+    return fail(-1, "pdlpdev_create: batch_lanes must be 0, 2, 4, 8 or 16 (got %d)", batch_lanes);
   if (!out || m < 0 || n < 0 || !a_offsets || !at_offsets) return fail(-1, "pdlpdev_create: bad argument");
   if (pdlpdev_device_count() <= device)
     return fail(-5, "pdlpdev_create: no HIP device %d visible (this solver has no CPU fallback)", device);
@@ -105,6 +111,7 @@ static int create_impl(pdlpdev_ctx** out, int device, int32_t m, int32_t n, cons
   };
   ctx         = new pdlpdev_ctx();
   ctx->device = device;
+  ctx->batch_lanes = batch_lanes;
   {
     int cus = 0;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0) ctx->cus = cus;
@@ -411,7 +418,7 @@ static int create_impl(pdlpdev_ctx** out, int device, int32_t m, int32_t n, cons
           return;
         }
         if (!T_idx) T_idx = t_idx_host();
-        ts.jat = build_jag(n, m, T_off, T_idx, mode == "jag" ? 1 : 0, ctx->cus);
+        ts.jat = build_jag(n, m, T_off, T_idx, mode == "jag" ? 1 : 0, ctx->cus, ctx->batch_lanes);
       } else if (an) {
         ts.jat.saving = an->saving_natural[1];
       }
@@ -427,12 +434,12 @@ static int create_impl(pdlpdev_ctx** out, int device, int32_t m, int32_t n, cons
       if (skip_jag_a) {
         ja.saving = an->saving_natural[0];
       } else if (jag_on_device) {
-        on_device = build_jag_device(ctx, &ctx->ja, m, n, A_off, ctx->ha_off, ctx->ha_idx, ctx->ha_val, mode == "jag" ? 1 : 0, ctx->cus);
+        on_device = build_jag_device(ctx, &ctx->ja, m, n, A_off, ctx->ha_off, ctx->ha_idx, ctx->ha_val, mode == "jag" ? 1 : 0, ctx->cus, ctx->batch_lanes);
         if (on_device < 0) return on_device;
         lap("jag A on the device");
       }
       if (on_device == 1) {
-        if (!skip_jag_a) ja = build_jag(m, n, A_off, A_idx_host(), mode == "jag" ? 1 : 0, ctx->cus);
+        if (!skip_jag_a) ja = build_jag(m, n, A_off, A_idx_host(), mode == "jag" ? 1 : 0, ctx->cus, ctx->batch_lanes);
         lap("build_jag A");
         TRY(upload_jag(ctx, &ctx->ja, ja, ctx->ha_off, ctx->ha_idx, ctx->ha_val));
         lap("upload jag A");
@@ -509,11 +516,11 @@ static int create_impl(pdlpdev_ctx** out, int device, int32_t m, int32_t n, cons
     lap("upload A^T");
     bool jat_on_device = false;
     if (ts.want_dev_jag) {
-      int on_device = build_jag_device(ctx, &ctx->jat, n, m, T_off, ctx->hat_off, ctx->hat_idx, ctx->hat_val, mode == "jag" ? 1 : 0, ctx->cus);
+      int on_device = build_jag_device(ctx, &ctx->jat, n, m, T_off, ctx->hat_off, ctx->hat_idx, ctx->hat_val, mode == "jag" ? 1 : 0, ctx->cus, ctx->batch_lanes);
       if (on_device < 0) return on_device;
       if (on_device == 1) {
         if (!T_idx) T_idx = t_idx_host();
-        ts.jat = build_jag(n, m, T_off, T_idx, mode == "jag" ? 1 : 0, ctx->cus);
+        ts.jat = build_jag(n, m, T_off, T_idx, mode == "jag" ? 1 : 0, ctx->cus, ctx->batch_lanes);
       } else {
         jat_on_device = true;
       }

@@ -479,6 +479,7 @@ struct pdlpdev_ctx {
   int rejected_in_a_row = 0;  // attempts enqueued since the last accepted step (pdlpdev_run's guard against endless rejections)
   // graphs
   int use_graph = 1;
+  int batch_lanes = 0;  // jagged layouts built for lockstep batches of up to this many LPs (cuoptamd_settings::batch_lanes)
   bool comm_warm = false;          // one attempt went out eagerly over this communicator (before the first capture)
   bool graph_comm_failed = false;  // capturing the RCCL collectives into an attempt graph failed once: plain launches from then on
   // one allocation for the ~40 problem / iterate vectors of a large LP (each hipMalloc + memset pair costs ~0.1 ms: 3 ms of a 25 ms

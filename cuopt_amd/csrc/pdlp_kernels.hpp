@@ -252,6 +252,7 @@ constexpr unsigned kSegColMask = (1u << kSegColBits) - 1u;
 // (160 KiB, one workgroup per CU: the same 16 waves per CU, twice the rows sharing a window twice as wide) -- chosen per
 // matrix at set-up (8 waves unless CUOPT_AMD_TUNE=jag_waves=16: see build_jag).
 constexpr int kJagMaxGroup = 256;   // rows per wave (2 KiB of row sums)
+constexpr int kJagBatchRows = 16384;  // layouts for lockstep batches of K LPs: at most kJagBatchRows / K rows per workgroup (128 KiB of row sums)
 #ifndef CUOPT_AMD_JAG_U
 #define CUOPT_AMD_JAG_U 8
 #endif

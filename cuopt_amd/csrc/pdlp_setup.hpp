@@ -93,7 +93,7 @@ int gather_working_set_device(pdlpdev_ctx* c, const int32_t* d_idx, int64_t nnz,
 // jagged rows + LDS column sets from the device-resident CSR (kernels_setup.hip): 0 built / not worth it (dst->on says which, dst->saving
 // the layout's estimate), 1 not handled here (the host construction takes over), < 0 error
 int build_jag_device(pdlpdev_ctx* c, pdlpdev_ctx::Jag* dst, int32_t rows, int32_t cols, const int32_t* h_off, const int32_t* d_off, const int32_t* d_idx,
-                     const double* d_val, int mode, int cus);
+                     const double* d_val, int mode, int cus, int batch_lanes = 0);
 // gather-free layout from the device-resident CSR (kernels_setup.hip): 0 built or does not fit (dst->on says which, *why the reason),
 // 1 not handled here (nothing allocated: the host construction takes over), < 0 error
 int build_pb_wide_device(pdlpdev_ctx* c, pdlpdev_ctx::Pb* dst, int32_t rows, int32_t cols, const int32_t* h_off, const int32_t* d_off, const int32_t* d_idx,
@@ -109,4 +109,6 @@ bool panel_plan(PanelHost* P, int32_t rows, int32_t cols, const int32_t* off, in
 // jagged layout (kernels_jag.hip): geometry for a matrix of `rows` rows, and the cost estimate on a MINI CSR that holds `nsamples`
 // row blocks of `brows` consecutive rows each (columns ascending inside a row)
 bool jag_geometry(int32_t rows, int mode, int* G, int* waves, int* wcap, int* brows);
+// rows per workgroup of a jagged layout built for lockstep batches of up to `batch_lanes` LPs (0: brows itself)
+int32_t jag_batch_rows(int32_t brows, int batch_lanes);
 double jag_estimate_on_samples(int nsamples, int32_t brows, int wcap, const int32_t* soff, const int32_t* sidx);

@@ -680,6 +680,7 @@ void cuoptamd_default_settings(cuoptamd_settings* s)
   s->accept_enabled                   = 0;
   for (double& t : s->accept_tolerance) t = 1e-4;
   s->relative_primal_tolerance_factor = s->relative_dual_tolerance_factor = -1.0;
+  s->batch_lanes                      = 0;
 }
 
 // Plain parallel counting sort by column (small matrices, and the fallback of the blocked one below).  Thread t owns a
@@ -1018,6 +1019,7 @@ int cuoptamd_solver_create(cuoptamd_solver** out, const cuoptamd_lp* lp, const c
   if (ag.an && setup_rc == 0) {
     // single GPU: the analysis' device arrays become the context's
     pdlpdev_create_hint(0);
+    pdlpdev_create_batch_lanes(settings->batch_lanes);
     int rc = pdlpdev_create_from_analysis(&s->dev, ag.an, L->c, L->lo, L->hi, L->lb, L->ub);
     // the spent analysis: its workspace goes back at once (a one-slot cache: the next analysis, of this or of another solver, takes it
     // from there), the hipFree calls of the rest -- each a device synchronisation, ~3 ms of a 25 ms set-up -- wait for the solver's end
@@ -1057,10 +1059,12 @@ int cuoptamd_solver_create(cuoptamd_solver** out, const cuoptamd_lp* lp, const c
   }
   {
     pdlpdev_create_hint(world > 1 || comm_id != nullptr);
+    pdlpdev_create_batch_lanes(settings->batch_lanes);
     int rc = setup_rc;
     if (rc == 0)
       rc = pdlpdev_create_overlapped(&s->dev, device, ml, n, off.data(), idx, val, t_off.data(), t_idx.get(), t_val.get(),
                                      &TransposeJob::wait, &job, L->c, L->lo + s->row_begin, L->hi + s->row_begin, L->lb, L->ub);
+    pdlpdev_create_batch_lanes(0);  // (consumed by the creation; not left behind when set-up failed before it)
     if (rc == 0 && fault_injected(rank, world, "create")) rc = -6;
     job.join();
     if (rc != 0 && rc != setup_rc) fail(rc, "pdlpdev_create: %s", rc == -6 ? "injected fault (CUOPT_AMD_TUNE=fault_inject)" : pdlpdev_last_error());
@@ -1955,11 +1959,18 @@ static int shared_matrix_batch_solve(int32_t count, const cuoptamd_lp* lps, cons
     std::vector<cuoptamd_solver*> s;
     ~Slots() { for (size_t i = s.size(); i-- > 0;) cuoptamd_solver_destroy(s[i]); }
   } slots;
+  bool lockstep = true;
   {
     cuoptamd_solver* parent = nullptr;
     int rc_ = cuoptamd_solver_create(&parent, &L0, hyper, settings, nullptr, nullptr, device, 0, 1, nullptr);
     if (parent) slots.s.push_back(parent);
     if (rc_ != 0) return rc_;
+    // A jagged side keeps the LPs one after the other: the jagged lockstep batch (batch_lanes, kbj_*) is bit-identical but measured
+    // SLOWER than one LP after the other at every K (banded 1e6 rows: 0.86x / 0.91x / 0.98x / 0.95x aggregate at K = 2 / 4 / 8 / 16,
+    // profiles/r07_jag_batch.txt) -- and the parent is created with the caller's settings, so the answers stay those of solves
+    // created with them.
+    int32_t lay[8] = {0};
+    if (parent->dev && pdlpdev_layout_info(parent->dev, lay) == 0 && (lay[0] == 3 || lay[3] == 3)) lockstep = false;
   }
   // the solver of slot q takes LP i: the parent as created (i = 0), a new clone, or an existing solver reset to LP i's bounds
   auto take = [&](int q, int i) -> int {
@@ -1973,7 +1984,6 @@ static int shared_matrix_batch_solve(int32_t count, const cuoptamd_lp* lps, cons
   };
   auto solution = [&](int q, int i) { return cuoptamd_solver_get_solution(slots.s[q], x ? x[i] : nullptr, y ? y[i] : nullptr, rc ? rc[i] : nullptr); };
   int done = 0;
-  bool lockstep = true;
   while (done < count) {
     const int left = count - done;
     const int K    = lockstep && left >= 16 ? 16 : lockstep && left >= 8 ? 8 : lockstep && left >= 4 ? 4 : 1;

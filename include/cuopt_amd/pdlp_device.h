@@ -147,6 +147,9 @@ int pdlpdev_create(pdlpdev_ctx** out, int device, int32_t m, int32_t n, const in
 /* the NEXT context created by this thread will run behind a communicator (sharded solve): paths that exist on one GPU only --
  * dense row segments, the resident small-LP kernel -- are not set up */
 void pdlpdev_create_hint(int sharded);
+/* The next context created on this thread builds its jagged layouts for lockstep batches of up to `lanes` LPs (0, 2, 4, 8, 16:
+ * cuoptamd_settings::batch_lanes); reset to 0 by the creation. */
+void pdlpdev_create_batch_lanes(int lanes);
 /* the NEXT context created by this thread runs on `donor`'s stream instead of one of its own (NULL: back to own streams).  For
  * hundreds of small contexts that one host thread drives one after the other or that advance together as a pdlpdev_small_batch:
  * a stream is a hardware queue (~2 ms to create, a few per process).  The donor must be destroyed after its borrowers. */

@@ -122,6 +122,11 @@ typedef struct cuoptamd_settings {
    * (eps_abs + eps_rel * factor) replaced by the caller's values -- the MIP side keeps them fixed across re-solves.
    * Negative (default): computed from the problem. */
   double relative_primal_tolerance_factor, relative_dual_tolerance_factor;
+  /* 0 (default), 2, 4, 8 or 16: the jagged layouts are built so that lockstep batches (cuoptamd_batch_create) of up to this many
+   * clones can run on them -- a workgroup holds at most 16384 / batch_lanes rows, so that the row sums of every LP of the batch
+   * fit its LDS.  Read when the solver is created (reset and clone ignore it; clones share the parent's layouts).  0: the layouts
+   * of a solver that never batches, and cuoptamd_batch_create refuses a jagged parent with -7. */
+  int32_t batch_lanes;
 } cuoptamd_settings;
 
 /* additional_termination_information_t (pdlp/solver_solution.hpp:63-103) + run statistics */
