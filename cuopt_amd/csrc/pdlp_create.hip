@@ -82,6 +82,187 @@ int pdlpdev_create_from_analysis(pdlpdev_ctx** out, pdlpdev_analysis* an, const 
 }
 }  // extern "C"
 
+int layout_policy(LayoutPolicy* p)
+{
+  static const char* const names[] = {"auto", "stream", "panel", "jag", "pb", "timed"};  // (LayoutPolicy::Mode's order)
+  const char* mode = getenv("CUOPT_AMD_SPMV_LAYOUT");
+  const auto* it   = std::find_if(std::begin(names), std::end(names), [&](const char* s) { return strcmp(s, mode ? mode : "auto") == 0; });
+  if (it == std::end(names)) return fail(-1, "CUOPT_AMD_SPMV_LAYOUT must be auto, stream, panel, jag, pb or timed");
+  p->mode = (LayoutPolicy::Mode)(it - std::begin(names));
+  // 1.33 MiB of the gathered vector per slab: measured optimum on the 1e6 x 1e6 random LP (6 slabs: 71 us per
+  // SpMV; 8 slabs of 1 MiB: 74 us; 4 slabs of 2 MiB: 75 us) -- fewer tiles per panel against L2 capacity
+  p->slab_bytes = std::max<int64_t>(64, cuopt_amd::tune_int("slab_bytes", 1398102));
+  p->ws_limit   = cuopt_amd::tune_int("panel_ws_bytes", kPanelWorkingSetBytes);
+  p->pb_device  = cuopt_amd::tune_int("pb_device", 1) != 0;
+  p->jag_device = cuopt_amd::tune_int("jag_device", 1) != 0;
+  return 0;
+}
+
+namespace {
+// One matrix as the layout walk sees it (A: m x n, A^T: n x m).  The walk runs on the host alone when `device` is false: then it
+// neither allocates from the context nor enqueues on its stream, and may run on a thread of its own.
+struct LayoutSide {
+  const char* name = "";
+  int32_t rows = 0, cols = 0;
+  const int32_t* off = nullptr;  // the hot CSR on the host: offsets, and the indices once the host holds them
+  const int32_t* idx = nullptr;
+  pdlpdev_analysis* an = nullptr;  // (null indices: an analysed matrix's, fetched from it on first use)
+  bool transposed = false;
+  const int32_t *d_off = nullptr, *d_idx = nullptr;  // the hot CSR on the device
+  const double* d_val = nullptr;
+  bool device = false;    // an analysed matrix without dense segments: the live gather set is counted and the layouts built there
+  bool skip_jag = false;  // the analysis' sampled estimate already rules the jagged layout out
+  const std::vector<int32_t>* first_seg = nullptr;  // A's dense segments (host panels)
+  pdlpdev_ctx::Jag* jag = nullptr;  // the side's layout slots
+  pdlpdev_ctx::Pb* pb = nullptr;
+  pdlpdev_ctx::Panels* pan = nullptr;
+  std::function<void(const std::string&)> lap;
+  // what the walk leaves: the host constructions (upload_side takes them to the device), the live gather set once counted, and why
+  // the gather-free layout turned the matrix away
+  JagHost jh;
+  PbHost pbh;
+  PanelHost ph;
+  int64_t ws = -1;
+  std::string why;
+  const int32_t* host_idx()
+  {
+    if (!idx) idx = transposed ? analysis_host_t_idx(an) : analysis_host_idx(an);
+    return idx;
+  }
+};
+
+// Panels when the CSR stream kernel's live gather set overflows what an XCD's L2 keeps of it (auto); counted once per side, on the
+// device where the indices are, else on the host -- from the four windows alone when the host does not hold the indices.
+int want_panels(pdlpdev_ctx* ctx, const LayoutPolicy& P, LayoutSide& s, bool* want)
+{
+  const bool timed = P.mode == LayoutPolicy::kTimed, timing = getenv("CUOPT_AMD_TIMING") != nullptr;
+  *want = P.mode == LayoutPolicy::kPanel || (timed && !timing);
+  if (*want || (!timed && (P.mode != LayoutPolicy::kAuto || (int64_t)s.cols * 8 <= P.ws_limit))) return 0;
+  if (s.ws < 0) {
+    int64_t ws = 0;
+    const int rc = s.device ? gather_working_set_device(ctx, s.d_idx, s.off[s.rows], s.cols, &ws) : 1;
+    if (rc < 0) return rc;
+    if (rc == 1 && s.idx) {
+      ws = gather_working_set(s.rows, s.cols, s.off, s.idx);
+    } else if (rc == 1) {  // (beyond ~2e7 columns the device's bitmap leaves the LDS)
+      std::vector<int32_t> sparse;
+      std::vector<std::pair<int64_t, int64_t>> windows;
+      if (analysis_fetch_idx_windows(s.an, s.transposed ? 1 : 0, (int64_t)s.off[s.rows], &sparse, &windows) != 0) return 0;
+      ws = gather_working_set_windows(s.cols, sparse.data(), windows);
+    }
+    s.ws = ws;
+    if (timing)
+      fprintf(stderr, "[cuopt_amd setup]   layout %-3s: live gather set of the stream kernel %.2f MiB (limit %.2f) -> %s\n", s.name,
+              ws / 1048576.0, P.ws_limit / 1048576.0, ws > P.ws_limit ? "panels" : "stream");
+  }
+  *want = timed || s.ws > P.ws_limit;
+  return 0;
+}
+
+// One construction per layout: the device builder where it applies (kernels_layout_build.hip: < 0 error, 0 done -- dst->on says
+// whether the layout was built --, 1 the host must build it), else the host construction, which upload_side takes to the device.
+int side_jag(pdlpdev_ctx* ctx, const LayoutPolicy& P, LayoutSide& s)
+{
+  const int mode = P.mode == LayoutPolicy::kJag ? 1 : 0;
+  const int rc   = s.device && P.jag_device ? build_jag_device(ctx, s.jag, s.rows, s.cols, s.off, s.d_off, s.d_idx, s.d_val, mode, ctx->cus, ctx->batch_lanes) : 1;
+  if (rc == 1) s.jh = build_jag(s.rows, s.cols, s.off, s.host_idx(), mode, ctx->cus, ctx->batch_lanes);
+  s.lap(std::string("jag ") + s.name);
+  return rc < 0 ? rc : 0;
+}
+
+int side_pb(pdlpdev_ctx* ctx, const LayoutPolicy& P, LayoutSide& s)
+{
+  const bool forced = P.mode == LayoutPolicy::kPb;
+  const int rc      = s.device && P.pb_device ? build_pb_device(ctx, s.pb, s.rows, s.cols, s.off, s.d_off, s.d_idx, ctx->cus, forced, &s.why) : 1;
+  if (rc == 1) {
+    s.pbh = build_pb(s.rows, s.cols, s.off, s.host_idx(), ctx->cus, forced);
+    s.why = s.pbh.why;
+  }
+  s.lap(std::string("gather-free ") + s.name);
+  return rc < 0 ? rc : 0;
+}
+
+int side_panels(pdlpdev_ctx* ctx, const LayoutPolicy& P, LayoutSide& s)
+{
+  const bool force = P.mode != LayoutPolicy::kTimed;  // (timed: only where the panels apply at all; pick_layout times them)
+  const int rc     = s.device ? build_panels_device(ctx, s.pan, s.rows, s.cols, s.off, s.d_off, s.d_idx, s.d_val, P.slab_bytes, force) : 1;
+  if (rc == 1) s.ph = build_panels(s.rows, s.cols, s.off, s.host_idx(), P.slab_bytes, force, s.first_seg);
+  s.lap(std::string("panels ") + s.name);
+  return rc < 0 ? rc : 0;
+}
+
+// The candidates of one side, in order: jagged rows, the gather-free layout, slab-major panels; the CSR stream when none is built.
+int layout_walk(pdlpdev_ctx* ctx, const LayoutPolicy& P, LayoutSide& s)
+{
+  if (P.try_jag() && !s.skip_jag) TRY(side_jag(ctx, P, s));
+  if (s.jh.ok || s.jag->on) return 0;
+  bool panels = false;
+  if (P.want_pb(s.cols)) {
+    if (P.mode != LayoutPolicy::kPb) TRY(want_panels(ctx, P, s, &panels));
+    if (P.mode == LayoutPolicy::kPb || panels) TRY(side_pb(ctx, P, s));
+    if (s.pbh.ok || s.pb->on) return 0;
+  }
+  if (P.mode == LayoutPolicy::kStream || P.mode == LayoutPolicy::kJag || P.mode == LayoutPolicy::kPb) return 0;
+  TRY(want_panels(ctx, P, s, &panels));
+  return panels ? side_panels(ctx, P, s) : 0;
+}
+
+// the walk's host constructions to the device (on the main thread, after the walk wherever it ran)
+int upload_side(pdlpdev_ctx* ctx, const LayoutPolicy& P, LayoutSide& s)
+{
+  if (s.jh.ok) TRY(upload_jag(ctx, s.jag, s.jh, s.d_off, s.d_idx, s.d_val));
+  TRY(upload_pb(ctx, s.pb, s.pbh));
+  if (P.mode == LayoutPolicy::kPb && !s.pb->on) return fail(-1, "CUOPT_AMD_SPMV_LAYOUT=pb: %s does not fit the gather-free layout (%s)", s.name, s.why.c_str());
+  return upload_panels(ctx, s.pan, s.ph, s.d_off, s.d_idx, s.d_val);
+}
+
+// A's panels with dense segments: the segments of the own rows (a workgroup each), in own-row order -- those workgroups add them
+int own_segments(pdlpdev_ctx* ctx, const DenseHost& DH, const PanelHost& ha)
+{
+  // (the rows that own segments are a subset of the own rows and both lists ascend)
+  std::vector<int32_t> own_seg(ha.own_row.size() + 1, 0);
+  for (size_t i = 0; i < ha.own_row.size(); ++i) {
+    const int32_t f = DH.first_seg[ha.own_row[i]];
+    int32_t cnt     = 0;
+    for (int32_t q = f; f >= 0 && q < (int32_t)DH.seg_row.size() && DH.seg_row[q] == ha.own_row[i]; ++q) ++cnt;
+    own_seg[i + 1] = own_seg[i] + cnt;
+  }
+  int32_t* d_own_seg = nullptr;
+  TRY(upload_i32(ctx, &d_own_seg, own_seg.data(), own_seg.size()));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  PanelView& v = ctx->pa.v;
+  v.dn_own_seg = d_own_seg, v.dn_seg_c0 = ctx->dense.seg_c0, v.dn_seg_len = ctx->dense.seg_len, v.dn_seg_ptr = ctx->dense.seg_ptr;
+  v.dn_seg_row = ctx->dense.seg_row, v.dn_val = ctx->dense.val;
+  return 0;
+}
+
+// A^T's panels with dense segments: per panel the segments that reach into its column range (ascending rows = segment numbers), for
+// the column epilogue -- when no panel meets more than kPanelDenseSegs and there are no own rows (else k_dense_cols in front, as for
+// the other layouts)
+int column_segments(pdlpdev_ctx* ctx, const DenseHost& DH, const PanelHost& hat)
+{
+  const std::vector<int32_t>& row0 = hat.row0;
+  std::vector<int32_t> pan_ptr(row0.size(), 0), pan_seg;
+  bool fits = true;
+  for (size_t w = 0; w + 1 < row0.size(); ++w) {
+    for (size_t q = 0; q < DH.seg_row.size(); ++q)
+      if (DH.seg_c0[q] < row0[w + 1] && DH.seg_c0[q] + DH.seg_len[q] > row0[w]) pan_seg.push_back((int32_t)q);
+    pan_ptr[w + 1] = (int32_t)pan_seg.size();
+    fits           = fits && pan_ptr[w + 1] - pan_ptr[w] <= kPanelDenseSegs;
+  }
+  if (!fits || !hat.own_row.empty()) return 0;
+  int32_t *d_ptr = nullptr, *d_seg = nullptr;
+  TRY(upload_i32(ctx, &d_ptr, pan_ptr.data(), pan_ptr.size()));
+  TRY(upload_i32(ctx, &d_seg, pan_seg.data(), pan_seg.size()));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  PanelView& v = ctx->pat.v;
+  v.dn_pan_ptr = d_ptr, v.dn_pan_seg = d_seg;
+  v.dn_seg_c0 = ctx->dense.seg_c0, v.dn_seg_len = ctx->dense.seg_len, v.dn_seg_ptr = ctx->dense.seg_ptr;
+  v.dn_seg_row = ctx->dense.seg_row, v.dn_val = ctx->dense.val;
+  return 0;
+}
+}  // namespace
+
 static int create_impl(pdlpdev_ctx** out, int device, int32_t m, int32_t n, const int32_t* a_offsets,
                        const int32_t* a_indices, const double* a_values, const int32_t* at_offsets,
                        const int32_t* at_indices, const double* at_values,
@@ -100,13 +281,13 @@ static int create_impl(pdlpdev_ctx** out, int device, int32_t m, int32_t n, cons
   const bool timing = getenv("CUOPT_AMD_TIMING") != nullptr;
   auto tlast = std::chrono::steady_clock::now();
   pdlpdev_ctx* ctx = nullptr;
-  auto lap = [&](const char* what) {
+  auto lap = [&](const std::string& what) {
     if (!timing) return;
     // (the context's own stream: a device-wide synchronisation would break a graph capture another thread's solver is in the middle of)
     if (ctx && ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     else (void)hipDeviceSynchronize();
     const auto now = std::chrono::steady_clock::now();
-    fprintf(stderr, "[cuopt_amd setup]   dev: %-22s %8.2f ms\n", what, 1e3 * std::chrono::duration<double>(now - tlast).count());
+    fprintf(stderr, "[cuopt_amd setup]   dev: %-22s %8.2f ms\n", what.c_str(), 1e3 * std::chrono::duration<double>(now - tlast).count());
     tlast = now;
   };
   ctx         = new pdlpdev_ctx();
@@ -205,7 +386,6 @@ static int create_impl(pdlpdev_ctx** out, int device, int32_t m, int32_t n, cons
   const bool hot_a     = !hA_off.empty();
   const int32_t* A_off = hot_a ? hA_off.data() : a_offsets;
   const int32_t* A_idx = hot_a ? hA_idx.data() : a_indices;  // (null: an analysed, permuted matrix whose indices stayed on the device)
-  auto A_idx_host = [&]() -> const int32_t* { return A_idx ? A_idx : a_idx_host(); };
   ctx->ha_off = ctx->a_off, ctx->ha_idx = ctx->a_idx, ctx->ha_val = ctx->a_val;
   ctx->dense.hot_nnz = (int64_t)A_off[m];
   if (hot_a) {
@@ -296,202 +476,64 @@ static int create_impl(pdlpdev_ctx** out, int device, int32_t m, int32_t n, cons
   TRY(dev_alloc(ctx, &ctx->rc_scratch, n));
   const size_t slab_rest = ctx->slab_cap - ctx->slab_used;  // (kept for the n-sized buffers allocated after the layouts)
   ctx->slab_cap = ctx->slab_used;
+  LayoutPolicy P;
+  TRY(layout_policy(&P));
+  lap("row blocks + vectors");
   {
-    // layout choice: CUOPT_AMD_SPMV_LAYOUT = auto (default) | stream | panel | jag ; CUOPT_AMD_TUNE=slab_bytes=...
-    // auto is structural (reproducible): the jagged layout when filling its LDS column sets costs at most half of the gathers
-    // they serve (build_jag), else slab-major panels iff the stream kernel's live gather set exceeds an XCD's L2
-    // (gather_working_set), else the CSR stream.  "timed" times panels against the stream on the device (pick_layout).
-    const char* mode_env = getenv("CUOPT_AMD_SPMV_LAYOUT");
-    const std::string mode = mode_env ? mode_env : "auto";
-    // 1.33 MiB of the gathered vector per slab: measured optimum on the 1e6 x 1e6 random LP (6 slabs: 71 us per
-    // SpMV; 8 slabs of 1 MiB: 74 us; 4 slabs of 2 MiB: 75 us) -- fewer tiles per panel against L2 capacity
-    const int64_t slab_bytes = std::max<int64_t>(64, cuopt_amd::tune_int("slab_bytes", 1398102));
-    if (mode != "auto" && mode != "stream" && mode != "panel" && mode != "jag" && mode != "timed" && mode != "pb")
-      return fail(-1, "CUOPT_AMD_SPMV_LAYOUT must be auto, stream, panel, jag, pb or timed");
-    const bool force = mode == "panel";
-    const bool timed = mode == "timed";
-    // gather-free layout: on request, or (auto) where the panels would need more than their 16 slabs to keep a slab in L2
-    auto want_pb = [&](int32_t cols) { return mode == "pb" || (mode == "auto" && (int64_t)cols * 8 > 16 * slab_bytes); };
-    const bool try_jag = mode == "auto" || mode == "jag" || timed;
-    // auto, not jagged: panels when the CSR stream kernel's live gather set overflows what an XCD's L2 keeps of it
-    const int64_t ws_limit = cuopt_amd::tune_int("panel_ws_bytes", kPanelWorkingSetBytes);
-    int64_t ws_at_device = 0, ws_a_device = -1;  // (counted by the main thread: the A^T side's worker must not allocate from the context)
-    bool ws_at_on_host = false;
-    if (an && (mode == "auto" || timed) && (int64_t)m * 8 > ws_limit) {
-      const int rc = gather_working_set_device(ctx, ctx->at_idx, ctx->nnz, m, &ws_at_device);
-      if (rc < 0) return rc;
-      ws_at_on_host = rc == 1;  // (beyond ~2e7 rows the bitmap leaves the LDS: the four windows come to the host)
-    }
-    if (an && !DH.on && (mode == "auto" || timed) && (int64_t)n * 8 > ws_limit) {
-      const int rc = gather_working_set_device(ctx, ctx->a_idx, ctx->nnz, n, &ws_a_device);
-      if (rc < 0) return rc;
-      if (rc == 1) ws_a_device = -1;
-    }
-    auto want_panels = [&](int32_t rows, int32_t cols, const int32_t* off, const int32_t* idx, const char* name) {
-      if (force) return true;
-      if (!timed && (mode != "auto" || (int64_t)cols * 8 <= ws_limit)) return false;
-      if (timed && !getenv("CUOPT_AMD_TIMING")) return true;
-      int64_t ws = 0;
-      const bool a_side = name[1] == '\0';
-      if (a_side && ws_a_device >= 0) {
-        ws = ws_a_device;  // (same windows, counted on the device)
-      } else if (a_side && !idx) {
-        ws = gather_working_set(rows, cols, off, A_idx_host());
-      } else if (idx) {
-        ws = gather_working_set(rows, cols, off, idx);
-      } else if (!ws_at_on_host) {  // (A^T of an analysed matrix: its indices live on the device; the same four windows were counted there)
-        ws = ws_at_device;
-      } else {
-        std::vector<int32_t> sparse;
-        std::vector<std::pair<int64_t, int64_t>> windows;
-        if (analysis_fetch_idx_windows(an, 1, (int64_t)off[rows], &sparse, &windows) != 0) return false;
-        ws = gather_working_set_windows(cols, sparse.data(), windows);
-      }
-      if (getenv("CUOPT_AMD_TIMING"))
-        fprintf(stderr, "[cuopt_amd setup]   layout %-3s: live gather set of the stream kernel %.2f MiB (limit %.2f) -> %s\n", name,
-                ws / 1048576.0, ws_limit / 1048576.0, ws > ws_limit ? "panels" : "stream");
-      return timed || ws > ws_limit;
+    // One walk per side (layout_walk).  A^T's runs on a thread of its own, next to the A side, when no device construction applies
+    // to it (the caller's matrices, or dense segments): the caller's transposition, the hot CSR and the constructions are host work
+    // then, and the main thread uploads what it built after the join.  An analysed matrix has nothing to wait for and little left to
+    // do on the host: its A^T side runs inline, after A^T's uploads (a thread of its own took 3 ms to do 0.5 ms of work next to the
+    // main thread's HIP calls).
+    const bool at_thread = !an || DH.on;
+    auto init_side = [&](LayoutSide& s, int t) {
+      s.name = t ? "A^T" : "A", s.rows = t ? n : m, s.cols = t ? m : n, s.an = an, s.transposed = t != 0;
+      s.device   = an && !DH.on;
+      s.skip_jag = an && an->estimated && !an->permuted && P.mode != LayoutPolicy::kJag && an->saving_natural[t] < 0.35;
+      s.jag = t ? &ctx->jat : &ctx->ja, s.pb = t ? &ctx->pbat : &ctx->pba, s.pan = t ? &ctx->pat : &ctx->pa;
     };
-    lap("row blocks + vectors");
-    // The A^T side's HOST work (waiting for the caller's transposition, the hot CSR, the layouts' construction) runs on a thread of
-    // its own next to the A side's construction and uploads; its uploads follow below, in the order they always had.
-    struct TSide {
-      std::thread worker;
-      std::vector<int32_t> rbt;
-      JagHost jat;
-      PbHost hbt;
-      PanelHost hat;
-      bool want_pb_layout = false, want_dev_panels = false, want_dev_pb = false, panels_pending = false, want_dev_jag = false;
-      ~TSide() { if (worker.joinable()) worker.join(); }
-    } ts;
-    const int32_t* T_off = at_offsets;
-    const int32_t* T_idx = at_indices;
-    // An analysed matrix's A^T lives on the device: its index array comes to the host only for the constructions that still run there
-    // (jagged, gather-free, dense segments); the analysis' sampled estimate already says whether the jagged layout is worth a look.
-    auto t_idx_host = [&]() -> const int32_t* { return an ? analysis_host_t_idx(an) : at_indices; };
-    const bool skip_jag_a  = an && an->estimated && !an->permuted && mode != "jag" && an->saving_natural[0] < 0.35;
-    const bool skip_jag_at = an && an->estimated && !an->permuted && mode != "jag" && an->saving_natural[1] < 0.35;
-    // the gather-free layout is built on the device when the matrices are there (CUOPT_AMD_TUNE=pb_device=0: the host construction,
-    // the tests' reference)
-    const bool pb_on_device = an && !DH.on && cuopt_amd::tune_int("pb_device", 1) != 0;
-    // ... and so is the jagged layout (CUOPT_AMD_TUNE=jag_device=0: on the host)
-    const bool jag_on_device = an && !DH.on && cuopt_amd::tune_int("jag_device", 1) != 0;
+    LayoutSide T;
+    init_side(T, 1);
+    T.off = at_offsets, T.idx = at_indices;  // (the device's hot CSR once it is uploaded, below)
     const auto w0 = std::chrono::steady_clock::now();
-    auto wlap = [&](const char* what) {
-      if (timing) fprintf(stderr, "[cuopt_amd setup]   A^T thread: %-22s at %6.2f ms\n", what, 1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - w0).count());
+    auto wlap = [&](const std::string& what) {
+      if (timing) fprintf(stderr, "[cuopt_amd setup]   A^T thread: %-22s at %6.2f ms\n", what.c_str(), 1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - w0).count());
     };
-    // stage 2 of the A^T side: which layout when it is not the jagged one (the gather-free layout / the panels, built below)
-    auto at_side_rest = [&] {
-      const bool jat_ok = ts.jat.ok || ctx->jat.on;
-      if (!jat_ok && want_pb(m) && (mode == "pb" || want_panels(n, m, T_off, T_idx, "A^T"))) {
-        ts.want_pb_layout = true;
-        if (pb_on_device) {
-          ts.want_dev_pb = true;  // (built on the device by the main thread, below; whether panels are wanted instead is known after that)
-          ts.panels_pending = mode != "stream" && mode != "jag" && mode != "pb";
-          wlap("layouts");
-          return;
-        }
-        if (!T_idx) T_idx = t_idx_host();
-        ts.hbt            = build_pb(n, m, T_off, T_idx, ctx->cus, mode == "pb");
-      }
-      if (mode != "stream" && mode != "jag" && mode != "pb" && !jat_ok && !ts.hbt.ok && want_panels(n, m, T_off, T_idx, "A^T")) {
-        if (an && !DH.on) ts.want_dev_panels = true;  // (built on the device by the main thread, below)
-        else ts.hat = build_panels(n, m, T_off, T_idx, slab_bytes, force || !timed);
-      }
-      wlap("layouts");
-    };
-    auto at_side = [&] {
+    if (at_thread) T.lap = wlap;
+    else T.lap = lap;
+    std::vector<int32_t> rbt;
+    int at_rc = 0;
+    auto at_side = [&](bool walk) {
       if (transpose_ready) transpose_ready(user);
       if ((int64_t)at_offsets[n] != ctx->nnz) return;  // (reported below)
       lat = long_rows(n, at_offsets);
       wlap("long rows");
       if (DH.on) {
-        strip_transpose(DH, &DH, n, at_offsets, t_idx_host());
+        strip_transpose(DH, &DH, n, at_offsets, T.host_idx());
         hT_off.swap(DH.st_off), hT_idx.swap(DH.st_idx), hT_perm.swap(DH.st_perm);
       }
-      if (!hT_off.empty()) T_off = hT_off.data(), T_idx = hT_idx.data();
-      ts.rbt = build_row_blocks(n, T_off);
+      if (!hT_off.empty()) T.off = hT_off.data(), T.idx = hT_idx.data();
+      rbt = build_row_blocks(n, T.off);
       wlap("row blocks");
-      if (try_jag && !skip_jag_at) {
-        if (jag_on_device) {
-          ts.want_dev_jag = true;  // (built on the device by the main thread, below; the rest of this side's decisions follow it)
-          return;
-        }
-        if (!T_idx) T_idx = t_idx_host();
-        ts.jat = build_jag(n, m, T_off, T_idx, mode == "jag" ? 1 : 0, ctx->cus, ctx->batch_lanes);
-      } else if (an) {
-        ts.jat.saving = an->saving_natural[1];
-      }
-      at_side_rest();
+      if (walk) at_rc = layout_walk(ctx, P, T);
     };
-    // (an analysed matrix: nothing to wait for and little left to do on the host -- the A^T side runs inline, behind the A side;
-    // a thread of its own took 3 ms to do 0.5 ms of work next to the main thread's HIP calls)
-    const bool at_thread = !an || (try_jag && !skip_jag_at && !jag_on_device) || DH.on || (want_pb(m) && !pb_on_device);  // (host constructions worth a thread)
-    if (at_thread) ts.worker = std::thread(at_side);
-    if (try_jag) {
-      JagHost ja;
-      int on_device = 1;
-      if (skip_jag_a) {
-        ja.saving = an->saving_natural[0];
-      } else if (jag_on_device) {
-        on_device = build_jag_device(ctx, &ctx->ja, m, n, A_off, ctx->ha_off, ctx->ha_idx, ctx->ha_val, mode == "jag" ? 1 : 0, ctx->cus, ctx->batch_lanes);
-        if (on_device < 0) return on_device;
-        lap("jag A on the device");
-      }
-      if (on_device == 1) {
-        if (!skip_jag_a) ja = build_jag(m, n, A_off, A_idx_host(), mode == "jag" ? 1 : 0, ctx->cus, ctx->batch_lanes);
-        lap("build_jag A");
-        TRY(upload_jag(ctx, &ctx->ja, ja, ctx->ha_off, ctx->ha_idx, ctx->ha_val));
-        lap("upload jag A");
-      }
+    struct Join {
+      std::thread t;
+      ~Join() { if (t.joinable()) t.join(); }
+    } worker;  // (an early return waits for the A^T side too)
+    if (at_thread) worker.t = std::thread(at_side, true);
+    {
+      LayoutSide A;  // (its host constructions go back to the pool at the end of this block)
+      init_side(A, 0);
+      A.off = A_off, A.idx = A_idx, A.d_off = ctx->ha_off, A.d_idx = ctx->ha_idx, A.d_val = ctx->ha_val, A.lap = lap;
+      A.first_seg = DH.on ? &DH.first_seg : nullptr;
+      TRY(layout_walk(ctx, P, A));
+      TRY(upload_side(ctx, P, A));
+      if (ctx->pa.on && DH.on) TRY(own_segments(ctx, DH, A.ph));
+      lap("upload layouts A");
     }
-    if (!ctx->ja.on && want_pb(n) && (mode == "pb" || want_panels(m, n, A_off, A_idx, "A"))) {
-      int on_device = 1;
-      if (pb_on_device) {
-        std::string why;
-        on_device = build_pb_device(ctx, &ctx->pba, m, n, A_off, ctx->ha_off, ctx->ha_idx, ctx->cus, mode == "pb", &why);
-        if (on_device < 0) return on_device;
-        lap("pb A on the device");
-        if (on_device == 0 && !ctx->pba.on && mode == "pb") return fail(-1, "CUOPT_AMD_SPMV_LAYOUT=pb: A does not fit the gather-free layout (%s)", why.c_str());
-      }
-      if (on_device == 1) {
-        PbHost hb = build_pb(m, n, A_off, A_idx_host(), ctx->cus, mode == "pb");
-        lap("build_pb A");
-        if (!hb.ok && mode == "pb") return fail(-1, "CUOPT_AMD_SPMV_LAYOUT=pb: A does not fit the gather-free layout (%s)", hb.why.c_str());
-        TRY(upload_pb(ctx, &ctx->pba, hb));
-        lap("upload pb A");
-      }
-    }
-    if (mode != "stream" && mode != "jag" && mode != "pb" && !ctx->ja.on && !ctx->pba.on && want_panels(m, n, A_off, A_idx, "A")) {
-      PanelHost ha;
-      int on_device = an && !DH.on ? build_panels_device(ctx, &ctx->pa, m, n, A_off, ctx->ha_off, ctx->ha_idx, ctx->ha_val, slab_bytes, force || !timed) : 1;
-      if (on_device < 0) return on_device;
-      if (on_device == 1) {
-        ha = build_panels(m, n, A_off, A_idx_host(), slab_bytes, force || !timed, DH.on ? &DH.first_seg : nullptr);
-        lap("build_panels A");
-        TRY(upload_panels(ctx, &ctx->pa, ha, ctx->ha_off, ctx->ha_idx, ctx->ha_val));
-      }
-      if (ctx->pa.on && DH.on) {
-        // segments of the own rows, in own-row order (the rows that own segments are a subset of the own rows and both lists ascend)
-        std::vector<int32_t> own_seg(ha.own_row.size() + 1, 0);
-        for (size_t i = 0; i < ha.own_row.size(); ++i) {
-          const int32_t f = DH.first_seg[ha.own_row[i]];
-          int32_t cnt     = 0;
-          for (int32_t q = f; f >= 0 && q < (int32_t)DH.seg_row.size() && DH.seg_row[q] == ha.own_row[i]; ++q) ++cnt;
-          own_seg[i + 1] = own_seg[i] + cnt;
-        }
-        int32_t* d_own_seg = nullptr;
-        TRY(upload_i32(ctx, &d_own_seg, own_seg.data(), own_seg.size()));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        PanelView& v = ctx->pa.v;
-        v.dn_own_seg = d_own_seg, v.dn_seg_c0 = ctx->dense.seg_c0, v.dn_seg_len = ctx->dense.seg_len, v.dn_seg_ptr = ctx->dense.seg_ptr;
-        v.dn_seg_row = ctx->dense.seg_row, v.dn_val = ctx->dense.val;
-      }
-      lap("upload panels A");
-      HIP_TRY(hipStreamSynchronize(ctx->stream));  // the staged copies have left the host arrays (back to the pool)
-    }
-    if (!at_thread) at_side();
-    else ts.worker.join();
+    if (at_thread) worker.t.join();
+    else at_side(false);
     lap("wait for the A^T side");
     if ((int64_t)at_offsets[n] != ctx->nnz) return fail(-1, "pdlpdev_create: A and A^T disagree on nnz");
     if (!an) {
@@ -503,86 +545,23 @@ static int create_impl(pdlpdev_ctx** out, int device, int32_t m, int32_t n, cons
     if (ctx->at_nlong) TRY(upload_i32(ctx, &ctx->at_long, lat.data(), lat.size()));
     const bool hot_t = !hT_off.empty();
     ctx->hat_off = ctx->at_off, ctx->hat_idx = ctx->at_idx, ctx->hat_val = ctx->at_val;
-    ctx->hot_nnz_at = (int64_t)T_off[n];
+    ctx->hot_nnz_at = (int64_t)T.off[n];
     if (hot_t) {
-      TRY(upload_i32(ctx, &ctx->hat_off, T_off, (size_t)n + 1));
-      TRY(upload_i32(ctx, &ctx->hat_idx, T_idx, (size_t)ctx->hot_nnz_at, 8));
+      TRY(upload_i32(ctx, &ctx->hat_off, T.off, (size_t)n + 1));
+      TRY(upload_i32(ctx, &ctx->hat_idx, T.idx, (size_t)ctx->hot_nnz_at, 8));
       TRY(dev_alloc(ctx, &ctx->hat_val, (size_t)ctx->hot_nnz_at + 8));
       TRY(upload_i32(ctx, &ctx->dense.s_perm_at, hT_perm.data(), hT_perm.size()));
     }
     if (DH.on) TRY(dev_alloc(ctx, &ctx->dense.add_n, (size_t)n));
-    ctx->at_nb = (int)ts.rbt.size() / 2 - 1;
-    TRY(upload_i32(ctx, &ctx->at_rb, ts.rbt.data(), ts.rbt.size()));
+    ctx->at_nb = (int)rbt.size() / 2 - 1;
+    TRY(upload_i32(ctx, &ctx->at_rb, rbt.data(), rbt.size()));
     lap("upload A^T");
-    bool jat_on_device = false;
-    if (ts.want_dev_jag) {
-      int on_device = build_jag_device(ctx, &ctx->jat, n, m, T_off, ctx->hat_off, ctx->hat_idx, ctx->hat_val, mode == "jag" ? 1 : 0, ctx->cus, ctx->batch_lanes);
-      if (on_device < 0) return on_device;
-      if (on_device == 1) {
-        if (!T_idx) T_idx = t_idx_host();
-        ts.jat = build_jag(n, m, T_off, T_idx, mode == "jag" ? 1 : 0, ctx->cus, ctx->batch_lanes);
-      } else {
-        jat_on_device = true;
-      }
-      lap("jag At on the device");
-    }
-    if (try_jag && !jat_on_device) {
-      TRY(upload_jag(ctx, &ctx->jat, ts.jat, ctx->hat_off, ctx->hat_idx, ctx->hat_val));
-      lap("upload jag At");
-    }
-    if (ts.want_dev_jag) at_side_rest();  // (the decisions that waited for the jagged layout's verdict)
-    if (ts.want_dev_pb) {
-      std::string why;
-      int on_device = build_pb_device(ctx, &ctx->pbat, n, m, T_off, ctx->hat_off, ctx->hat_idx, ctx->cus, mode == "pb", &why);
-      if (on_device < 0) return on_device;
-      if (on_device == 1) {
-        if (!T_idx) T_idx = t_idx_host();
-        ts.hbt = build_pb(n, m, T_off, T_idx, ctx->cus, mode == "pb");
-      } else {
-        ts.want_pb_layout = false;  // (nothing to upload)
-        if (!ctx->pbat.on && mode == "pb") return fail(-1, "CUOPT_AMD_SPMV_LAYOUT=pb: A^T does not fit the gather-free layout (%s)", why.c_str());
-      }
-      lap("pb At on the device");
-      if (ts.panels_pending && !ctx->pbat.on && !ts.hbt.ok && want_panels(n, m, T_off, T_idx, "A^T")) ts.want_dev_panels = true;
-    }
-    if (ts.want_pb_layout) {
-      if (!ts.hbt.ok && mode == "pb") return fail(-1, "CUOPT_AMD_SPMV_LAYOUT=pb: A^T does not fit the gather-free layout (%s)", ts.hbt.why.c_str());
-      TRY(upload_pb(ctx, &ctx->pbat, ts.hbt));
-      lap("upload pb At");
-    }
-    if (ts.want_dev_panels) {
-      const int on_device = build_panels_device(ctx, &ctx->pat, n, m, T_off, ctx->hat_off, ctx->hat_idx, ctx->hat_val, slab_bytes, force || !timed);
-      if (on_device < 0) return on_device;
-      if (on_device == 1) ts.hat = build_panels(n, m, T_off, t_idx_host(), slab_bytes, force || !timed);
-      lap("panels At on the device");
-    }
-    if (ts.hat.ok) {
-      TRY(upload_panels(ctx, &ctx->pat, ts.hat, ctx->hat_off, ctx->hat_idx, ctx->hat_val));
-      if (ctx->pat.on && DH.on) {
-        // per panel of the column side: the segments that reach into its column range, ascending rows (= segment numbers)
-        const std::vector<int32_t>& row0 = ts.hat.row0;
-        std::vector<int32_t> pan_ptr(row0.size(), 0), pan_seg;
-        bool fits = true;
-        for (size_t w = 0; w + 1 < row0.size(); ++w) {
-          for (size_t q = 0; q < DH.seg_row.size(); ++q)
-            if (DH.seg_c0[q] < row0[w + 1] && DH.seg_c0[q] + DH.seg_len[q] > row0[w]) pan_seg.push_back((int32_t)q);
-          pan_ptr[w + 1] = (int32_t)pan_seg.size();
-          fits           = fits && pan_ptr[w + 1] - pan_ptr[w] <= kPanelDenseSegs;
-        }
-        if (fits && ts.hat.own_row.empty()) {  // (else: k_dense_cols in front of the panels, as for the other layouts)
-          int32_t *d_ptr = nullptr, *d_seg = nullptr;
-          TRY(upload_i32(ctx, &d_ptr, pan_ptr.data(), pan_ptr.size()));
-          TRY(upload_i32(ctx, &d_seg, pan_seg.data(), pan_seg.size()));
-          HIP_TRY(hipStreamSynchronize(ctx->stream));
-          PanelView& v = ctx->pat.v;
-          v.dn_pan_ptr = d_ptr, v.dn_pan_seg = d_seg;
-          v.dn_seg_c0 = ctx->dense.seg_c0, v.dn_seg_len = ctx->dense.seg_len, v.dn_seg_ptr = ctx->dense.seg_ptr;
-          v.dn_seg_row = ctx->dense.seg_row, v.dn_val = ctx->dense.val;
-        }
-      }
-      lap("upload panels At");
-    }
-    HIP_TRY(hipStreamSynchronize(ctx->stream));  // the staged copies have left the worker's host arrays
+    T.d_off = ctx->hat_off, T.d_idx = ctx->hat_idx, T.d_val = ctx->hat_val;
+    TRY(at_thread ? at_rc : layout_walk(ctx, P, T));
+    TRY(upload_side(ctx, P, T));
+    if (ctx->pat.on && DH.on) TRY(column_segments(ctx, DH, T.ph));
+    lap("upload layouts A^T");
+    HIP_TRY(hipStreamSynchronize(ctx->stream));  // the staged copies have left the host arrays
   }
   {
     // small LPs: a whole batch of attempts inside one workgroup (CUOPT_AMD_SMALL=0 switches it off)
@@ -612,14 +591,11 @@ static int create_impl(pdlpdev_ctx** out, int device, int32_t m, int32_t n, cons
   lap("fill D");
   TRY(sync_panel_values(ctx));
   lap("panel values (permute)");
-  {
-    const char* mode_env = getenv("CUOPT_AMD_SPMV_LAYOUT");
-    if (mode_env && std::string(mode_env) == "timed") {
-      TRY(pick_layout(ctx, &ctx->pa, m, ctx->a_nb, ctx->a_rb, ctx->ha_off, ctx->ha_idx, ctx->ha_val, ctx->tmp_n, ctx->tmp_m, "A"));
-      lap("layout autotune A");
-      TRY(pick_layout(ctx, &ctx->pat, n, ctx->at_nb, ctx->at_rb, ctx->hat_off, ctx->hat_idx, ctx->hat_val, ctx->tmp_m, ctx->tmp_n, "A^T"));
-      lap("layout autotune");
-    }
+  if (P.mode == LayoutPolicy::kTimed) {
+    TRY(pick_layout(ctx, &ctx->pa, m, ctx->a_nb, ctx->a_rb, ctx->ha_off, ctx->ha_idx, ctx->ha_val, ctx->tmp_n, ctx->tmp_m, "A"));
+    lap("layout autotune A");
+    TRY(pick_layout(ctx, &ctx->pat, n, ctx->at_nb, ctx->at_rb, ctx->hat_off, ctx->hat_idx, ctx->hat_val, ctx->tmp_m, ctx->tmp_n, "A^T"));
+    lap("layout autotune");
   }
   HIP_TRY(hipStreamSynchronize(ctx->stream));
   scratch_free(ctx);  // (the layout constructions' temporaries: both sides are built)

@@ -477,20 +477,19 @@ int pdlpdev_owner_setup(pdlpdev_ctx* ctx, const int32_t* off, const int32_t* idx
   k_scale_matrix<<<grid_for(nc), kBlock, 0, s>>>(nc, ctx->oc_off, ctx->oc_idx, ctx->oc_val, ctx->dc + cb, ctx->ygather);
   if (ctx->oc_nlong) k_scale_matrix_long<<<ctx->oc_nlong, kBlock, 0, s>>>(ctx->oc_long, ctx->oc_off, ctx->oc_idx, ctx->oc_val, ctx->dc + cb, ctx->ygather);
   HIP_TRY(hipGetLastError());
-  // layouts, by the rules of the two other matrices (timed mode counts as auto here)
+  // layouts, by the policy of the two other matrices with two candidates: jagged rows, then panels (timed mode counts as auto here)
   {
-    const char* mode_env = getenv("CUOPT_AMD_SPMV_LAYOUT");
-    std::string mode     = mode_env ? mode_env : "auto";
-    if (mode == "timed") mode = "auto";
-    const int64_t slab_bytes = std::max<int64_t>(64, cuopt_amd::tune_int("slab_bytes", 1398102));
-    const int64_t ws_limit   = cuopt_amd::tune_int("panel_ws_bytes", kPanelWorkingSetBytes);
-    if (nc > 0 && (mode == "auto" || mode == "jag")) {
-      JagHost j = build_jag(nc, (int32_t)gcols, off, ridx.data(), mode == "jag" ? 1 : 0, ctx->cus);
+    LayoutPolicy P;
+    TRY(layout_policy(&P));
+    const LayoutPolicy::Mode mode = P.mode == LayoutPolicy::kTimed ? LayoutPolicy::kAuto : P.mode;
+    if (nc > 0 && (mode == LayoutPolicy::kAuto || mode == LayoutPolicy::kJag)) {
+      JagHost j = build_jag(nc, (int32_t)gcols, off, ridx.data(), mode == LayoutPolicy::kJag ? 1 : 0, ctx->cus);
       TRY(upload_jag(ctx, &ctx->joc, j, ctx->oc_off, ctx->oc_idx, ctx->oc_val));
     }
-    const bool panels = mode == "panel" || (mode == "auto" && gcols * 8 > ws_limit && gather_working_set(nc, (int32_t)gcols, off, ridx.data()) > ws_limit);
+    const bool panels = mode == LayoutPolicy::kPanel ||
+                        (mode == LayoutPolicy::kAuto && gcols * 8 > P.ws_limit && gather_working_set(nc, (int32_t)gcols, off, ridx.data()) > P.ws_limit);
     if (nc > 0 && !ctx->joc.on && panels) {
-      PanelHost h = build_panels(nc, (int32_t)gcols, off, ridx.data(), slab_bytes, true);
+      PanelHost h = build_panels(nc, (int32_t)gcols, off, ridx.data(), P.slab_bytes, true);
       TRY(upload_panels(ctx, &ctx->poc, h, ctx->oc_off, ctx->oc_idx, ctx->oc_val));
     }
   }
@@ -1484,7 +1483,8 @@ int pdlpdev_debug_layout_checksums(pdlpdev_ctx* ctx, uint64_t out[16])
   out[13] = jag(ctx->ja), out[14] = jag(ctx->jat);
   out[15] = (uint64_t)ctx->pa.on | (uint64_t)ctx->pat.on << 1 | (uint64_t)ctx->ja.on << 2 | (uint64_t)ctx->jat.on << 3 |
             (uint64_t)(ctx->pa.on && ctx->pa.v.seg) << 4 | (uint64_t)(ctx->pat.on && ctx->pat.v.seg) << 5 | (uint64_t)ctx->pba.on << 6 |
-            (uint64_t)ctx->pbat.on << 7;
+            (uint64_t)ctx->pbat.on << 7 | (uint64_t)(ctx->pa.v.dn_own_seg != nullptr) << 8 | (uint64_t)(ctx->pat.v.dn_pan_ptr != nullptr) << 9 |
+            (uint64_t)ctx->joc.on << 10 | (uint64_t)ctx->poc.on << 11;
   return 0;
 }
 

@@ -25,6 +25,23 @@ struct PanelHost {
 // what 'auto' decides on.
 constexpr int64_t kPanelWorkingSetBytes = 4 * (int64_t)1048576;  // an XCD's L2; calibration: profiles/r02_layout_rule.txt
 
+// ---- the settings behind the choice of a matrix's SpMV layout, read once per context (layout_policy, pdlp_create.hip) ------------
+// CUOPT_AMD_SPMV_LAYOUT = auto (default) | stream | panel | jag | pb | timed.  auto is structural (reproducible): the jagged layout
+// when filling its LDS column sets costs at most half of the gathers they serve (build_jag), else the gather-free layout where the
+// panels would need more than their 16 slabs to keep a slab in L2, else slab-major panels iff the stream kernel's live gather set
+// exceeds an XCD's L2 (gather_working_set), else the CSR stream.  "timed" times panels against the stream on the device (pick_layout).
+struct LayoutPolicy {
+  enum Mode { kAuto, kStream, kPanel, kJag, kPb, kTimed } mode = kAuto;
+  int64_t slab_bytes = 0;  // CUOPT_AMD_TUNE=slab_bytes: bytes of the gathered vector per panel slab
+  int64_t ws_limit   = 0;  // CUOPT_AMD_TUNE=panel_ws_bytes: the live gather set above which auto takes panels
+  // CUOPT_AMD_TUNE=pb_device=0 / jag_device=0: those layouts are built on the host even when the matrices are on the device (the
+  // tests' reference)
+  bool pb_device = true, jag_device = true;
+  bool try_jag() const { return mode == kAuto || mode == kJag || mode == kTimed; }
+  bool want_pb(int32_t cols) const { return mode == kPb || (mode == kAuto && (int64_t)cols * 8 > 16 * slab_bytes); }
+};
+int layout_policy(LayoutPolicy* p);  // 0, or -1 (with the error text) when CUOPT_AMD_SPMV_LAYOUT names no mode
+
 // ---- sorted jagged rows: host-side construction (structure only; values are permuted on the device) -------------
 struct JagHost {
   bool ok = false;

@@ -210,7 +210,9 @@ int pdlpdev_create_from_analysis(pdlpdev_ctx** out, pdlpdev_analysis* an, const 
 void pdlpdev_analysis_destroy(pdlpdev_analysis* an);
 /* parity hooks of the set-up primitives (tests): stable sort of n (key, value) pairs by the low `bits` bits (vals NULL: iota);
  * exclusive scan of n ints -> n + 1 outputs; FNV-1a checksums of the layout arrays of a context (out[16]: A^T offsets, indices,
- * values; per side panel row0, tile_ptr, rowptr, col, perm; jagged slot / descriptors / perm) */
+ * values; per side panel row0, tile_ptr, rowptr, col, perm; jagged slot / descriptors / perm; out[15] the layout flags: bits 0-7 panels
+ * A / A^T, jagged A / A^T, long-tail panels A / A^T, gather-free A / A^T; bit 8 A's panels add their own rows' dense segments, bit 9
+ * A^T's panels run the dense segments' column epilogue, bits 10 / 11 the sharded owner column block is jagged / in panels) */
 int pdlpdev_debug_sort_pairs(int device, int64_t n, const uint32_t* keys, const uint32_t* vals, int bits, uint32_t* keys_out,
                              uint32_t* vals_out);
 int pdlpdev_debug_scan(int device, int64_t n, const int32_t* in, int32_t* out);
