@@ -274,6 +274,10 @@ _proto("pdlpdev_flush_average", c_int, c_void_p)
 _proto("pdlpdev_make_average", c_int, c_void_p, c_int)
 _proto("pdlpdev_eval", c_int, c_void_p, c_int, c_int, c_double, c_double, c_void_p)
 _proto("pdlpdev_restart", c_int, c_void_p, c_int, c_int, c_void_p)
+_proto("pdlpdev_major_eval", c_int, c_void_p, c_int, c_int, c_double, c_double, c_void_p, c_void_p)
+if hasattr(lib, "pdlpdev_loop_stats"):  # (an older build given through CUOPT_AMD_LIB for an A/B run has neither)
+    _proto("pdlpdev_loop_stats", c_int, c_void_p, c_void_p)
+    _proto("pdlpdev_run_period", c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p)
 _proto("pdlpdev_save_best", c_int, c_void_p, c_int)
 _proto("pdlpdev_trust_region_bounds", c_int, c_void_p, c_int, c_double, c_double, c_double, c_double, c_double, c_double, c_int, c_void_p)
 _proto("pdlpdev_eval_infeasibility", c_int, c_void_p, c_int, c_int, c_void_p)
@@ -322,7 +326,7 @@ _proto("pdlpdev_synthetic_lp", c_int, c_int, c_int, c_int, c_int, C.c_uint64, *(
 BUF = {n: i for i, n in enumerate(
     ["X", "Y", "X_OTHER", "Y_OTHER", "ATY", "ATY_OTHER", "XBAR", "SUM_X", "SUM_Y", "AVG_X", "AVG_Y",
      "DROW", "DCOL", "A_VALUES", "AT_VALUES", "C", "LB", "UB", "LO", "HI", "RC_CURRENT", "RC_AVERAGE",
-     "LAST_RESTART_X", "LAST_RESTART_Y"])}
+     "LAST_RESTART_X", "LAST_RESTART_Y", "ATY_U_CURRENT", "ATY_U_AVERAGE"])}
 KERNEL = {n: i for i, n in enumerate(
     ["PRIMAL", "SPMV_A_DUAL", "SPMV_AT_STEP", "STEP_DECISION", "SPMV_A_PLAIN", "SPMV_AT_PLAIN"])}
 EV = {n: i for i, n in enumerate(
@@ -1067,6 +1071,19 @@ class Device:
         out = np.zeros(len(EV))
         self._ck(lib.pdlpdev_eval(self.handle, which, int(rule_finite), eps_p, eps_d, _ptr(out)))
         return {k: out[i] for k, i in EV.items()}
+
+    def major_eval(self, average_mode=2, rule_finite=True, eps_p=-1.0, eps_d=-1.0):
+        """pdlpdev_major_eval: the raw PDLPDEV_EV_COUNT outputs for the current and the average iterate"""
+        cur, avg = np.zeros(len(EV)), np.zeros(len(EV))
+        self._ck(lib.pdlpdev_major_eval(self.handle, int(average_mode), int(rule_finite), C.c_double(eps_p), C.c_double(eps_d), _ptr(cur), _ptr(avg)))
+        return cur, avg
+
+    def loop_stats(self):
+        """pdlpdev_loop_stats: evaluations of the current iterate that reused A^T y / ran the product, synchronisations inside the
+        loop, empty attempts"""
+        out = np.zeros(4, dtype=np.int64)
+        self._ck(lib.pdlpdev_loop_stats(self.handle, out.ctypes.data_as(C.c_void_p)))
+        return dict(zip(["eval_reused_aty", "eval_product", "loop_syncs", "empty_attempts"], (int(v) for v in out)))
 
     def eval_infeasibility(self, which, rule_finite=True):
         out = np.zeros(4)

@@ -968,6 +968,7 @@ int pdlpdev_batch_run(pdlpdev_batch* b, const int32_t* targets, pdlpdev_ctl* ctl
   HIP_TRY(hipSetDevice(b->device));
   TRY(batch_refresh_table(b));
   const int K = b->K;
+  for (int l = 0; l < K; ++l) loop_state_touched(b->ctx[l]);  // (the batch's kernels move the contexts' iterates and control blocks)
   for (int l = 0; l < K; ++l)
     if (targets[l] > 0) k_set_target<<<1, 1, 0, b->stream>>>(b->ctx[l]->ctl, targets[l]);
   LAUNCH_CHECK();
@@ -1043,6 +1044,7 @@ int pdlpdev_batch_time_kernels(pdlpdev_batch* b, int reps, double avg_ms[4])
   hipEvent_t* ev = scratch.ev;
   for (int l = 0; l < K; ++l) {
     pdlpdev_ctx* c = b->ctx[l];
+    loop_state_touched(c);
     saved[l] = forced[l] = *c->ctl_h;
     forced[l].pending_avg = 1, forced[l].target_steps = saved[l].steps_taken + 1, forced[l].error = 0;
     HIP_TRY(hipMalloc((void**)&sx[l], std::max<size_t>(c->n, 1) * sizeof(double)));

@@ -66,6 +66,7 @@ k_panel_eval_primal(PanelView P, const pdlpdev_ctl* __restrict__ ctl, int which,
                     const double* __restrict__ hi_u, double eps_rel, double* __restrict__ linf_rows,
                     double* __restrict__ ax_out, double* __restrict__ part)
 {
+  if (period_guard_skips(ctl, which)) return;
   const int cur = ctl->cur;
   const double* xv = which == PDLPDEV_AVERAGE ? avgx : (cur ? x1 : x0);
   const double* yv = which == PDLPDEV_AVERAGE ? avgy : (cur ? y1 : y0);
@@ -81,11 +82,59 @@ k_panel_eval_dual(PanelView P, const pdlpdev_ctl* __restrict__ ctl, int which,
                   const double* __restrict__ y1, const double* __restrict__ avgy, EvalDualCore core,
                   double* __restrict__ part)
 {
+  if (period_guard_skips(ctl, which)) return;
   const int cur = ctl->cur;
   core.xhat     = which == PDLPDEV_AVERAGE ? avgx : (cur ? x1 : x0);
   const double* yv = which == PDLPDEV_AVERAGE ? avgy : (cur ? y1 : y0);
   EvalDualEpilogue e{core};
   panel_block<SEG>(P, yv, e, part);
+}
+
+// Product-free twin of k_panel_eval_dual for the CURRENT iterate: the loop's A^T y buffer already holds the very row sums the product
+// above would form (k_panel_at_step / k_panel_at_cur stored them through the same panel_block, dense contributions included), so the
+// epilogue reads them from there.  Same grid, same rows per workgroup, same lane-to-row walk and reduction tree as panel_epilogue /
+// panel_own_row: the four partial sums per workgroup -- and with them k_finalize's result -- are bit for bit the product's.
+// guard != 0 (the fused period path): nothing happens unless the attempts in front reached their target.
+__global__ void __launch_bounds__(kPanelThreads)
+k_panel_eval_dual_from_aty(PanelView P, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ x0, const double* __restrict__ x1,
+                           const double* __restrict__ aty0, const double* __restrict__ aty1, EvalDualCore core,
+                           double* __restrict__ part, int guard)
+{
+  if (guard && !period_reached(ctl)) return;
+  __shared__ double red[kPanelWaves * EvalDualEpilogue::NQ];
+  __shared__ unsigned char own[kPanelMaxRows];  // rows of this panel that have a workgroup of their own (the product's "not mine" marks)
+  const int cur = ctl->cur;
+  core.xhat     = cur ? x1 : x0;
+  const double* __restrict__ src = cur ? aty1 : aty0;
+  EvalDualEpilogue e{core};
+  const int w  = blockIdx.x;
+  const int NP = P.NP ? P.NP : P.W;
+  double acc[EvalDualEpilogue::NQ];
+#pragma unroll
+  for (int q = 0; q < EvalDualEpilogue::NQ; ++q) acc[q] = SumOp::identity();
+  if (w >= NP) {  // panel_own_row: thread 0 alone applies the epilogue, the partials are its sums
+    if (threadIdx.x == 0) {
+      const int r = P.own_row[w - NP];
+      e.row(r, src[r], acc);
+#pragma unroll
+      for (int q = 0; q < EvalDualEpilogue::NQ; ++q) part[(size_t)q * P.W + w] = acc[q];
+    }
+    return;
+  }
+  const int r0 = P.row0[w], nr = P.row0[w + 1] - r0;
+  if (P.own_ptr) {
+    for (int r = threadIdx.x; r < nr; r += kPanelThreads) own[r] = 0;
+    __syncthreads();
+    for (int q = P.own_ptr[w] + (int)threadIdx.x; q < P.own_ptr[w + 1]; q += kPanelThreads) own[P.own_row[q] - r0] = 1;
+    __syncthreads();
+  }
+  for (int r = threadIdx.x; r < nr; r += kPanelThreads)
+    if (!P.own_ptr || !own[r]) e.row(r0 + r, src[r0 + r], acc);
+  block_reduce<SumOp, EvalDualEpilogue::NQ, kPanelWaves>(acc, red);
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int q = 0; q < EvalDualEpilogue::NQ; ++q) part[(size_t)q * P.W + w] = acc[q];
+  }
 }
 
 // explicit instantiations (the launch sites live in another translation unit)

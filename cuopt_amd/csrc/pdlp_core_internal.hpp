@@ -11,6 +11,10 @@ int fetch_ctl(pdlpdev_ctx* ctx, pdlpdev_ctl* out);      // the control block -> 
 void launch_plain(pdlpdev_ctx* ctx, int transpose, const double* vec, double* out);   // out = A vec / A^T vec in the side's layout
 void launch_at_cur(pdlpdev_ctx* ctx, double* out_override, int use_next);             // A^T y of the current (next) iterate
 void dense_part(pdlpdev_ctx* ctx, int transpose, const double* v0, const double* v1, int mode, int in_loop);  // the dense segments' share
+// the kernels of pdlpdev_major_eval, nothing read back (pdlp_eval.hip).  guard != 0: for pdlpdev_run_period -- every kernel is empty unless
+// the attempts in front reached their target, and the last one leaves the control block in scal[kCtlSlot ..)
+int enqueue_major_eval(pdlpdev_ctx* ctx, int average_mode, int rc_rule_finite_bounds, double eps_rel_primal, double eps_rel_dual, int guard);
+void read_major_eval(pdlpdev_ctx* ctx, double* out_current, double* out_average);  // ... and its results out of scal_h
 }
 
 // partial sums one product's epilogue leaves, by the side's layout
@@ -19,7 +23,7 @@ static inline int step_partials(const pdlpdev_ctx* ctx) { return ctx->pbat.on ? 
 
 __global__ void __launch_bounds__(kBlock)
 k_flush_average(int n, int m, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ x0, const double* __restrict__ x1, const double* __restrict__ y0,
-                const double* __restrict__ y1, double* __restrict__ sumx, double* __restrict__ sumy);
+                const double* __restrict__ y1, double* __restrict__ sumx, double* __restrict__ sumy, int guard);
 __global__ void __launch_bounds__(kBlock) k_finalize(const double* __restrict__ part, int nb, int nq, unsigned op_mask, double* __restrict__ out);
 __global__ void __launch_bounds__(kBlock) k_div_inplace(int n, double* __restrict__ v, const double* __restrict__ d);
 __global__ void __launch_bounds__(kBlock) k_div_to(int n, double* __restrict__ out, const double* __restrict__ v, const double* __restrict__ d);

@@ -567,6 +567,7 @@ static int create_impl(pdlpdev_ctx** out, int device, int32_t m, int32_t n, cons
     // small LPs: a whole batch of attempts inside one workgroup (CUOPT_AMD_SMALL=0 switches it off)
     const char* small_env = getenv("CUOPT_AMD_SMALL");
     const int tier        = resident_tier(m, n, ctx->nnz);
+    ctx->eval_reuse_aty   = cuopt_amd::tune_int("eval_reuse_aty", 1) != 0;
     ctx->small_resident   = tier >= 0 && !(small_env && atoi(small_env) == 0) && !ctx->dense.add_m && !ctx->dense.add_n;
     if (small_env && atoi(small_env) != 0 && tier < 0)
       return fail(-1, "CUOPT_AMD_SMALL=1: the LP does not fit the resident kernel (m, n <= 2048, nnz <= 4096 ...)");

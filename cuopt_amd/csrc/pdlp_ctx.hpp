@@ -477,6 +477,19 @@ struct pdlpdev_ctx {
   hipEvent_t prof_ev[2 * kProfPairs] = {};
   int prof_used = 0;
   int rejected_in_a_row = 0;  // attempts enqueued since the last accepted step (pdlpdev_run's guard against endless rejections)
+  // What the host knows about the loop's state without asking the device (pdlpdev_run, pdlpdev_run_period, enqueue_eval):
+  //   aty_valid      aty[cur] holds A^T y[cur] as this side's product kernels form it: after an accepted attempt (k_*_at_step stored
+  //                  A^T y' and the decision flipped to it), until anything else writes y[cur] or flips cur (loop_state_touched
+  //                  below) or the step error comes up.  pdlpdev_compute_aty restores the buffer too, but attempts always follow it
+  //                  before the next evaluation, so it is not counted.  The evaluation of the CURRENT iterate then reads its dual
+  //                  side from there instead of running the product again (CUOPT_AMD_TUNE=eval_reuse_aty=0: never).
+  //   ctl_h_current  the pinned copy of the control block is what the device holds: the read-back behind k_set_target is skipped.
+  bool aty_valid = false, ctl_h_current = false;
+  int eval_reuse_aty = 1;   // CUOPT_AMD_TUNE=eval_reuse_aty
+  int spare_attempts = 0;   // pdlpdev_run_period: empty-unless-needed attempts behind a period's, from the rejections the period before saw
+  // pdlpdev_loop_stats: evaluations of the current iterate that reused A^T y / ran the product, synchronisations inside
+  // pdlpdev_run and pdlpdev_run_period (pdlpdev_major_eval's own included), attempts enqueued that found the target reached
+  int64_t stat_eval_reused = 0, stat_eval_product = 0, stat_loop_syncs = 0, stat_empty_attempts = 0;
   // graphs
   int use_graph = 1;
   int batch_lanes = 0;  // jagged layouts built for lockstep batches of up to this many LPs (cuoptamd_settings::batch_lanes)
@@ -548,6 +561,10 @@ struct pdlpdev_decision_args {
 
 constexpr int kGenericBlocks = 1024;
 constexpr int kScalars       = 64;
+constexpr int kCtlSlot       = 48;  // scal[kCtlSlot ..): the control block as pdlpdev_run_period's last kernel copied it (one read-back for both)
+static_assert(kCtlSlot * sizeof(double) + sizeof(pdlpdev_ctl) <= kScalars * sizeof(double), "the control block fits behind the scalars");
+// the iterate or the control block changed behind the loop's back
+inline void loop_state_touched(pdlpdev_ctx* c) { c->aty_valid = false, c->ctl_h_current = false; }
 
 // Streams (an HSA queue each: ~2 ms to create), the pinned read-back block and the first arena chunk are handed from
 // a destroyed context to the next one created on the same device: back-to-back small solves (cuOptSolve in a loop,

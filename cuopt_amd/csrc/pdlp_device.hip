@@ -292,9 +292,9 @@ k_permute(int64_t n, const int32_t* __restrict__ perm, const double* __restrict_
 __global__ void __launch_bounds__(kBlock)
 k_flush_average(int n, int m, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ x0,
                 const double* __restrict__ x1, const double* __restrict__ y0,
-                const double* __restrict__ y1, double* __restrict__ sumx, double* __restrict__ sumy)
+                const double* __restrict__ y1, double* __restrict__ sumx, double* __restrict__ sumy, int guard)
 {
-  if (ctl->pending_avg == 0) return;
+  if (ctl->pending_avg == 0 || (guard && !period_reached(ctl))) return;
   const int cur           = ctl->cur;
   const double w          = ctl->step_size;
   const double* __restrict__ x = cur ? x1 : x0;
@@ -543,6 +543,7 @@ int fetch_ctl(pdlpdev_ctx* ctx, pdlpdev_ctl* out)
 {
   HIP_TRY(hipMemcpyAsync(ctx->ctl_h, ctx->ctl, sizeof(pdlpdev_ctl), hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
+  ctx->ctl_h_current = true;
   if (out) *out = *ctx->ctl_h;
   return 0;
 }
@@ -597,6 +598,8 @@ int pdlpdev_reset(pdlpdev_ctx* ctx, const double* lb, const double* ub, const do
   HIP_TRY(hipSetDevice(ctx->device));
   if (!ctx->scaled) return fail(-1, "pdlpdev_reset: the problem has not been scaled yet");
   ctx->rejected_in_a_row = 0;
+  ctx->spare_attempts    = 0;
+  loop_state_touched(ctx);
   hipStream_t s = ctx->stream;
   const size_t nb = (size_t)ctx->n * sizeof(double), mb = (size_t)ctx->m * sizeof(double);
   auto put = [&](const double* src, double* unscaled, double* scaled, size_t bytes) -> int {
@@ -681,6 +684,7 @@ int pdlpdev_set_step_params(pdlpdev_ctx* ctx, const pdlpdev_step_params* p)
 int pdlpdev_set_step(pdlpdev_ctx* ctx, double step_size, double primal_weight)
 {
   HIP_TRY(hipSetDevice(ctx->device));
+  ctx->ctl_h_current = false;
   k_set_step<<<1, 1, 0, ctx->stream>>>(ctx->ctl, step_size, primal_weight);
   LAUNCH_CHECK();
   return 0;
@@ -688,6 +692,7 @@ int pdlpdev_set_step(pdlpdev_ctx* ctx, double step_size, double primal_weight)
 int pdlpdev_set_k(pdlpdev_ctx* ctx, int32_t k)
 {
   HIP_TRY(hipSetDevice(ctx->device));
+  ctx->ctl_h_current = false;
   k_set_k<<<1, 1, 0, ctx->stream>>>(ctx->ctl, k);
   LAUNCH_CHECK();
   return 0;
@@ -696,6 +701,7 @@ int pdlpdev_set_initial(pdlpdev_ctx* ctx, const double* x, const double* y)
 {
   HIP_TRY(hipSetDevice(ctx->device));
   TRY(fetch_ctl(ctx, nullptr));
+  ctx->aty_valid = false;
   const int cur = ctx->ctl_h->cur;
   if (x) {
     HIP_TRY(hipMemcpyAsync(ctx->x[cur], x, (size_t)ctx->n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
@@ -1012,6 +1018,120 @@ static int get_graph(pdlpdev_ctx* ctx, int attempts, hipGraphExec_t* out)
   return 0;
 }
 
+// `count` attempts on ctx->stream: replays of the attempt graphs (powers of two up to 64) or plain launches
+static int enqueue_attempts(pdlpdev_ctx* ctx, int remaining)
+{
+  // Sharded solves over RCCL replay attempt graphs too: the collectives are captured with the kernels around them (round 4:
+  // tools/rccl_capture_repro.cpp captures ncclAllGather + ncclAllReduce in every capture mode with both RCCL builds of this image,
+  // and bench.py --force-comm runs the owner dataflow through captured graphs at one rank; round 3's crash inside the capture did
+  // not reproduce after the prune).  A capture that fails is remembered and the solver goes on with plain launches -- the same
+  // sequence of collectives, so ranks that took different paths still meet.  The in-process communicator synchronises on the
+  // host and can never be captured; the direct peer transport is kernels only.
+  const bool rccl_graphs = ctx->comm && !ctx->p2p.on && !ctx->soft && !ctx->graph_comm_failed;
+  bool replayed = false;
+  if (rccl_graphs && ctx->use_graph && !ctx->comm_warm) {
+    // the very first attempt of a solver over RCCL goes out as plain launches: whatever a collective sets up lazily on its first call
+    // (channels, proxies) must not happen inside a stream capture
+    TRY(enqueue_attempt(ctx));
+    ctx->comm_warm = true;
+    remaining -= 1;
+  }
+  if (ctx->use_graph && (!ctx->comm || ctx->p2p.on || rccl_graphs)) {
+    replayed = true;
+    while (remaining > 0) {
+      int chunk = 1;
+      while (chunk * 2 <= remaining && chunk < 64) chunk *= 2;
+      hipGraphExec_t g;
+      const int grc = get_graph(ctx, chunk, &g);
+      if (grc != 0 && rccl_graphs) {  // (nothing of this chunk was enqueued: a failed capture leaves the stream empty)
+        ctx->graph_comm_failed = true;
+        (void)hipGetLastError();
+        replayed = false;
+        break;
+      }
+      TRY(grc);
+      HIP_TRY(hipGraphLaunch(g, ctx->stream));
+      remaining -= chunk;
+    }
+  }
+  if (!replayed) {
+    for (int i = 0; i < remaining; ++i) TRY(enqueue_attempt(ctx));
+  }
+  return 0;
+}
+
+// what a round of attempts left, read from the fresh ctl_h: `before` accepted steps and `attempts_before` attempts existed in front of it
+static int after_round(pdlpdev_ctx* ctx, int before, int attempts_before, int enqueued, int counted /* towards the 64-in-a-row rule */)
+{
+  const pdlpdev_ctl& c = *ctx->ctl_h;
+  const int made       = c.attempts - attempts_before;  // an attempt that found the target reached (or an error raised) did nothing
+  if (!ctx->comm) ctx->stat_empty_attempts += enqueued - made;
+  if (c.steps_taken > before && c.error == 0 && !ctx->comm) ctx->aty_valid = true;  // k_*_at_step stored A^T y' and the decision flipped to it
+  if (c.error != 0) ctx->aty_valid = false;
+  if (ctx->p2p.on && c.error != 0) {  // a wait of the direct peer transport ran out of patience: a peer is gone
+    int fault = 0;
+    HIP_TRY(hipMemcpy(&fault, ctx->p2p.fault, sizeof(int), hipMemcpyDeviceToHost));
+    if (fault) return fail(-6, "direct peer transport: rank %d waited 5 s for another rank's data (a peer failed or is stuck)", ctx->rank);
+  }
+  // every rejection shrinks the step size; 64 in a row leave nothing of it: report it like the reference's invalid step
+  // size instead of re-enqueueing forever.  Counted across rounds AND calls (a call asks for at most one major-iteration
+  // period: 40 steps under Stable2, fewer than 64).  A round without an accepted step consists of real attempts only.
+  ctx->rejected_in_a_row = c.steps_taken == before ? ctx->rejected_in_a_row + counted : 0;
+  if (c.error == 0 && ctx->rejected_in_a_row >= 64) {
+    ctx->rejected_in_a_row = 0;
+    k_set_error<<<1, 1, 0, ctx->stream>>>(ctx->ctl);
+    LAUNCH_CHECK();
+    TRY(fetch_ctl(ctx, nullptr));
+    ctx->stat_loop_syncs += 1;
+    ctx->aty_valid = false;
+  }
+  return 0;
+}
+
+// rounds of attempts until the target is reached or the error flag is up; ctl_h is current on entry and on return
+static int run_rounds(pdlpdev_ctx* ctx, int32_t target_steps, int* rounds)
+{
+  // Each attempt accepts at most one step, so `remaining` attempts can never overshoot; rejected
+  // attempts are made up for in the next round (one control-block read per round, not per step).
+  int guard = 0;
+  while (ctx->ctl_h->error == 0 && ctx->ctl_h->steps_taken < target_steps) {
+    const int before = ctx->ctl_h->steps_taken, attempts_before = ctx->ctl_h->attempts, asked = target_steps - before;
+    TRY(enqueue_attempts(ctx, asked));
+    TRY(fetch_ctl(ctx, nullptr));
+    ctx->stat_loop_syncs += 1;
+    TRY(after_round(ctx, before, attempts_before, asked, asked));
+    if (++guard > 100000) return fail(-6, "pdlpdev_run: no progress");
+  }
+  if (rounds) *rounds += guard;
+  return 0;
+}
+static int run_epilogue(pdlpdev_ctx* ctx, int rounds, pdlpdev_ctl* ctl)
+{
+  if (ctx->rsag && rounds > 0) {
+    // back to replicated primal vectors for everything outside the loop (major iterations, snapshots, the solution): the
+    // current x, its A^T y and the running sum are complete on their owners' slices only
+    const int cur = ctx->ctl_h->cur;
+    TRY(all_gather(ctx, ctx->x[cur], (size_t)ctx->slice));
+    TRY(all_gather(ctx, ctx->aty[cur], (size_t)ctx->slice));
+    TRY(all_gather(ctx, ctx->sumx, (size_t)ctx->slice));
+  }
+  if (ctl) *ctl = *ctx->ctl_h;
+  return 0;
+}
+// k_set_target, and the control block on the host: read back, unless the pinned copy is known to be what the device holds
+static int set_target(pdlpdev_ctx* ctx, int32_t target_steps)
+{
+  k_set_target<<<1, 1, 0, ctx->stream>>>(ctx->ctl, target_steps);
+  LAUNCH_CHECK();
+  if (ctx->ctl_h_current && !ctx->comm) {
+    ctx->ctl_h->target_steps = target_steps;
+    return 0;
+  }
+  TRY(fetch_ctl(ctx, nullptr));
+  ctx->stat_loop_syncs += 1;
+  return 0;
+}
+
 int pdlpdev_run(pdlpdev_ctx* ctx, int32_t target_steps, pdlpdev_ctl* ctl)
 {
   roctx::Range range("pdlp: PDHG attempts");
@@ -1021,78 +1141,66 @@ int pdlpdev_run(pdlpdev_ctx* ctx, int32_t target_steps, pdlpdev_ctl* ctl)
     if (ctl) *ctl = *ctx->ctl_h;
     return 0;
   }
-  k_set_target<<<1, 1, 0, ctx->stream>>>(ctx->ctl, target_steps);
-  LAUNCH_CHECK();
-  TRY(fetch_ctl(ctx, nullptr));
-  // Each attempt accepts at most one step, so `remaining` attempts can never overshoot; rejected
-  // attempts are made up for in the next round (one control-block read per round, not per step).
-  int guard = 0;
-  while (ctx->ctl_h->error == 0 && ctx->ctl_h->steps_taken < target_steps) {
-    int remaining = target_steps - ctx->ctl_h->steps_taken;
-    // Sharded solves over RCCL replay attempt graphs too: the collectives are captured with the kernels around them (round 4:
-    // tools/rccl_capture_repro.cpp captures ncclAllGather + ncclAllReduce in every capture mode with both RCCL builds of this image,
-    // and bench.py --force-comm runs the owner dataflow through captured graphs at one rank; round 3's crash inside the capture did
-    // not reproduce after the prune).  A capture that fails is remembered and the solver goes on with plain launches -- the same
-    // sequence of collectives, so ranks that took different paths still meet.  The in-process communicator synchronises on the
-    // host and can never be captured; the direct peer transport is kernels only.
-    const bool rccl_graphs = ctx->comm && !ctx->p2p.on && !ctx->soft && !ctx->graph_comm_failed;
-    bool replayed = false;
-    if (rccl_graphs && ctx->use_graph && !ctx->comm_warm) {
-      // the very first attempt of a solver over RCCL goes out as plain launches: whatever a collective sets up lazily on its first call
-      // (channels, proxies) must not happen inside a stream capture
-      TRY(enqueue_attempt(ctx));
-      ctx->comm_warm = true;
-      remaining -= 1;
-    }
-    if (ctx->use_graph && (!ctx->comm || ctx->p2p.on || rccl_graphs)) {
-      replayed = true;
-      while (remaining > 0) {
-        int chunk = 1;
-        while (chunk * 2 <= remaining && chunk < 64) chunk *= 2;
-        hipGraphExec_t g;
-        const int grc = get_graph(ctx, chunk, &g);
-        if (grc != 0 && rccl_graphs) {  // (nothing of this chunk was enqueued: a failed capture leaves the stream empty)
-          ctx->graph_comm_failed = true;
-          (void)hipGetLastError();
-          replayed = false;
-          break;
-        }
-        TRY(grc);
-        HIP_TRY(hipGraphLaunch(g, ctx->stream));
-        remaining -= chunk;
-      }
-    }
-    if (!replayed) {
-      for (int i = 0; i < remaining; ++i) TRY(enqueue_attempt(ctx));
-    }
-    const int before = ctx->ctl_h->steps_taken, asked = target_steps - before;
-    TRY(fetch_ctl(ctx, nullptr));
-    if (ctx->p2p.on && ctx->ctl_h->error != 0) {  // a wait of the direct peer transport ran out of patience: a peer is gone
-      int fault = 0;
-      HIP_TRY(hipMemcpy(&fault, ctx->p2p.fault, sizeof(int), hipMemcpyDeviceToHost));
-      if (fault) return fail(-6, "direct peer transport: rank %d waited 5 s for another rank's data (a peer failed or is stuck)", ctx->rank);
-    }
-    // every rejection shrinks the step size; 64 in a row leave nothing of it: report it like the reference's invalid step
-    // size instead of re-enqueueing forever.  Counted across rounds AND calls (a call asks for at most one major-iteration
-    // period: 40 steps under Stable2, fewer than 64)
-    ctx->rejected_in_a_row = ctx->ctl_h->steps_taken == before ? ctx->rejected_in_a_row + asked : 0;
-    if (ctx->ctl_h->error == 0 && ctx->rejected_in_a_row >= 64) {
-      ctx->rejected_in_a_row = 0;
-      k_set_error<<<1, 1, 0, ctx->stream>>>(ctx->ctl);
-      LAUNCH_CHECK();
+  TRY(set_target(ctx, target_steps));
+  int rounds = 0;
+  TRY(run_rounds(ctx, target_steps, &rounds));
+  return run_epilogue(ctx, rounds, ctl);
+}
+
+// One major-iteration period with ONE synchronisation: the attempts up to `target_steps`, a few spare ones (empty launches unless an
+// attempt in front of them was rejected), and behind them the head of the major iteration that is due at the target (pdlpdev_major_eval's
+// kernels, each of which does nothing unless the target was reached), then one read-back of the scalars and the control block.
+// *evaluated = 1: the period was reached and out_current / out_average hold what pdlpdev_major_eval(rq) would have returned.
+// *evaluated = 0: the attempts are done as pdlpdev_run does them (make-up rounds included) and NOTHING of the major iteration has
+// happened -- the context is not eligible (sharded, resident, a layout without guarded evaluation kernels, l-infinity residuals
+// asked for, a control block the host does not hold), the period fell short, or the step error is up; the caller goes on the present way.
+int pdlpdev_run_period(pdlpdev_ctx* ctx, int32_t target_steps, const pdlpdev_small_eval* rq, pdlpdev_ctl* ctl,
+                       double out_current[PDLPDEV_EV_COUNT], double out_average[PDLPDEV_EV_COUNT], int32_t* evaluated)
+{
+  *evaluated = 0;
+  HIP_TRY(hipSetDevice(ctx->device));
+  const bool dense_unfused = ctx->dense.on && !(ctx->pat.v.dn_pan_ptr != nullptr && ctx->pa.v.dn_own_seg != nullptr);
+  const bool eligible = !ctx->comm && !ctx->small_resident && ctx->pa.on && ctx->pat.on && !dense_unfused && ctx->ctl_h_current &&
+                        !(rq->eps_p >= 0.0 && rq->eps_d >= 0.0) && ctx->ctl_h->error == 0 && ctx->ctl_h->steps_taken < target_steps;
+  if (!eligible) return pdlpdev_run(ctx, target_steps, ctl);
+  roctx::Range range("pdlp: PDHG attempts + major iteration evaluation");
+  TRY(set_target(ctx, target_steps));
+  const int before = ctx->ctl_h->steps_taken, attempts_before = ctx->ctl_h->attempts, asked = target_steps - before;
+  const int spare = ctx->spare_attempts;
+  TRY(enqueue_attempts(ctx, asked));
+  if (spare > 0) TRY(enqueue_attempts(ctx, spare));
+  TRY(enqueue_major_eval(ctx, rq->mode, rq->rule_finite, rq->eps_p, rq->eps_d, 1));
+  HIP_TRY(hipMemcpyAsync(ctx->scal_h, ctx->scal, kCtlSlot * sizeof(double) + sizeof(pdlpdev_ctl), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  ctx->stat_loop_syncs += 1;
+  memcpy(ctx->ctl_h, ctx->scal_h + kCtlSlot, sizeof(pdlpdev_ctl));
+  ctx->ctl_h_current = true;
+  // (a period with an accepted step and rejections: the attempts made beyond the accepted ones are the rejections)
+  const int rejected  = (ctx->ctl_h->attempts - attempts_before) - (ctx->ctl_h->steps_taken - before);
+  ctx->spare_attempts = std::max(0, std::min(rejected, 4));
+  TRY(after_round(ctx, before, attempts_before, asked + spare, asked));
+  int rounds = 1;
+  if (ctx->ctl_h->error == 0 && ctx->ctl_h->steps_taken >= target_steps) {
+    *evaluated = 1;
+    read_major_eval(ctx, out_current, out_average);
+  } else {
+    if (ctx->ctl_h->error == 0 && ctx->ctl_h->steps_taken == before && spare > 0 && spare < asked) {
+      // nothing was accepted: the spare attempts were the first ones of the make-up round pdlpdev_run would enqueue now; the rest of
+      // that round follows, so that the 64-in-a-row rule sees the rounds -- and stops after the number of attempts -- it always did
+      TRY(enqueue_attempts(ctx, asked - spare));
       TRY(fetch_ctl(ctx, nullptr));
+      ctx->stat_loop_syncs += 1;
+      TRY(after_round(ctx, before, attempts_before + asked + spare, asked - spare, asked));
+      rounds += 1;
     }
-    if (++guard > 100000) return fail(-6, "pdlpdev_run: no progress");
+    TRY(run_rounds(ctx, target_steps, &rounds));
   }
-  if (ctx->rsag && guard > 0) {
-    // back to replicated primal vectors for everything outside the loop (major iterations, snapshots, the solution): the
-    // current x, its A^T y and the running sum are complete on their owners' slices only
-    const int cur = ctx->ctl_h->cur;
-    TRY(all_gather(ctx, ctx->x[cur], (size_t)ctx->slice));
-    TRY(all_gather(ctx, ctx->aty[cur], (size_t)ctx->slice));
-    TRY(all_gather(ctx, ctx->sumx, (size_t)ctx->slice));
-  }
-  if (ctl) *ctl = *ctx->ctl_h;
+  return run_epilogue(ctx, rounds, ctl);
+}
+
+int pdlpdev_loop_stats(pdlpdev_ctx* ctx, int64_t out[4])
+{
+  out[0] = ctx->stat_eval_reused, out[1] = ctx->stat_eval_product, out[2] = ctx->stat_loop_syncs, out[3] = ctx->stat_empty_attempts;
   return 0;
 }
 
@@ -1144,6 +1252,7 @@ int pdlpdev_get_ctl(pdlpdev_ctx* ctx, pdlpdev_ctl* ctl)
 int pdlpdev_clear_error(pdlpdev_ctx* ctx)
 {
   HIP_TRY(hipSetDevice(ctx->device));
+  ctx->ctl_h_current = false;
   k_clear_error<<<1, 1, 0, ctx->stream>>>(ctx->ctl);
   LAUNCH_CHECK();
   return 0;
@@ -1224,6 +1333,8 @@ static int64_t locate_buffer(pdlpdev_ctx* ctx, int id, double** ptr)
     case PDLPDEV_BUF_RC_AVERAGE: src = ctx->rc[1], count = n; break;
     case PDLPDEV_BUF_LAST_RESTART_X: src = ctx->lrx, count = n; break;
     case PDLPDEV_BUF_LAST_RESTART_Y: src = ctx->lry, count = m; break;
+    case PDLPDEV_BUF_ATY_U_CURRENT: src = ctx->aty_u[PDLPDEV_CURRENT], count = n; break;
+    case PDLPDEV_BUF_ATY_U_AVERAGE: src = ctx->aty_u[PDLPDEV_AVERAGE], count = n; break;
     default: fail(-1, "unknown buffer %d", id); return -1;
   }
   *ptr = src;
@@ -1253,6 +1364,7 @@ int64_t pdlpdev_upload(pdlpdev_ctx* ctx, int id, const void* host, int64_t eleme
     return -1;
   }
   count = std::min(count, elements);
+  ctx->aty_valid = false;  // (an iterate or its A^T y may be what is overwritten)
   if ((id == PDLPDEV_BUF_LB && ctx->ubd.lb_same) || (id == PDLPDEV_BUF_UB && ctx->ubd.ub_same)) {
     // bounds written behind the solver's back: the arrays are read again (and the attempt graphs, which carry the flags by value,
     // are captured again)
@@ -1271,6 +1383,7 @@ int64_t pdlpdev_upload(pdlpdev_ctx* ctx, int id, const void* host, int64_t eleme
 int pdlpdev_set_loop_state(pdlpdev_ctx* ctx, double sum_weights, int32_t its_since_restart, int32_t k)
 {
   HIP_TRY(hipSetDevice(ctx->device));
+  loop_state_touched(ctx);
   k_set_loop_state<<<1, 1, 0, ctx->stream>>>(ctx->ctl, sum_weights, its_since_restart, k);
   LAUNCH_CHECK();
   return 0;
@@ -1299,6 +1412,7 @@ int pdlpdev_time_kernel(pdlpdev_ctx* ctx, int kernel_id, int reps, double* avg_m
   if (reps < 1) reps = 1;
   // save what the timed launches may touch: control block and the running sums
   TRY(fetch_ctl(ctx, nullptr));
+  loop_state_touched(ctx);  // (forced attempts run on the solver's own buffers)
   pdlpdev_ctl saved = *ctx->ctl_h;
   pdlpdev_ctl forced = saved;
   forced.pending_avg  = 1;                       // time the kernels WITH their averaging traffic

@@ -16,8 +16,11 @@ k_make_average(int n, int m, int mode, const pdlpdev_ctl* __restrict__ ctl,
                const double* __restrict__ x0, const double* __restrict__ x1,
                const double* __restrict__ y0, const double* __restrict__ y1,
                const double* __restrict__ sumx, const double* __restrict__ sumy,
-               double* __restrict__ avgx, double* __restrict__ avgy)
+               double* __restrict__ avgx, double* __restrict__ avgy, int32_t* __restrict__ clear_pending)
 {
+  if (period_guard_skips(ctl, mode)) return;
+  // (the head of a major iteration: k_flush_average in front of this launch has consumed the flag, nothing in this kernel reads it)
+  if (clear_pending && blockIdx.x == 0 && threadIdx.x == 0) *clear_pending = 0;
   const int cur = ctl->cur;
   const double* __restrict__ x = cur ? x1 : x0;
   const double* __restrict__ y = cur ? y1 : y0;
@@ -300,28 +303,46 @@ k_restart(int n, int m, int which, int unscaled, const double* __restrict__ dc, 
   restart_block(R, blockIdx.x, gridDim.x, red);
 }
 
+// The reductions behind an evaluation's two products in one launch: out[4..8) from the dual side's partials and, with_primal != 0,
+// out[0..3) from the primal side's (k_finalize twice: the same trees).  For pdlpdev_run_period: ctl_copy receives the control block
+// (whatever the guard says: the host reads both with one copy), and nothing is reduced unless the period's target was reached.
+__global__ void __launch_bounds__(kBlock)
+k_finalize_eval(const double* __restrict__ part_p, int nb_p, const double* __restrict__ part_d, int nb_d, int with_primal,
+                double* __restrict__ out, const pdlpdev_ctl* __restrict__ ctl, int guard, double* __restrict__ ctl_copy)
+{
+  __shared__ double red[8];
+  static_assert(sizeof(pdlpdev_ctl) % sizeof(int32_t) == 0, "copied word by word");
+  if (ctl_copy && threadIdx.x < sizeof(pdlpdev_ctl) / sizeof(int32_t))
+    reinterpret_cast<int32_t*>(ctl_copy)[threadIdx.x] = reinterpret_cast<const int32_t*>(ctl)[threadIdx.x];
+  if (guard && !period_reached(ctl)) return;
+  if (with_primal) finalize_rows(part_p, nb_p, 3, 0u, out, red);
+  finalize_rows(part_d, nb_d, 4, 0u, out + 4, red);
+}
+
 extern "C" {
 
 // ---- major iteration --------------------------------------------------------------------------------
 int pdlpdev_flush_average(pdlpdev_ctx* ctx)
 {
   HIP_TRY(hipSetDevice(ctx->device));
-  k_flush_average<<<grid_for(std::max(ctx->n, ctx->m)), kBlock, 0, ctx->stream>>>(ctx->n, ctx->m, ctx->ctl, ctx->x[0], ctx->x[1], ctx->y[0], ctx->y[1], ctx->sumx, ctx->sumy);
+  k_flush_average<<<grid_for(std::max(ctx->n, ctx->m)), kBlock, 0, ctx->stream>>>(ctx->n, ctx->m, ctx->ctl, ctx->x[0], ctx->x[1], ctx->y[0], ctx->y[1], ctx->sumx, ctx->sumy, 0);
   k_clear_pending<<<1, 1, 0, ctx->stream>>>(ctx->ctl);
   LAUNCH_CHECK();
+  ctx->ctl_h->pending_avg = 0;  // (what the device holds now, should the host copy be current)
   return 0;
 }
 int pdlpdev_make_average(pdlpdev_ctx* ctx, int mode)
 {
   HIP_TRY(hipSetDevice(ctx->device));
-  k_make_average<<<grid_for(std::max(ctx->n, ctx->m)), kBlock, 0, ctx->stream>>>(ctx->n, ctx->m, mode, ctx->ctl, ctx->x[0], ctx->x[1], ctx->y[0], ctx->y[1], ctx->sumx, ctx->sumy, ctx->avgx, ctx->avgy);
+  k_make_average<<<grid_for(std::max(ctx->n, ctx->m)), kBlock, 0, ctx->stream>>>(ctx->n, ctx->m, mode, ctx->ctl, ctx->x[0], ctx->x[1], ctx->y[0], ctx->y[1], ctx->sumx, ctx->sumy, ctx->avgx, ctx->avgy, nullptr);
   LAUNCH_CHECK();
   return 0;
 }
 
 // the launches of one convergence evaluation; results land in sc[0..9) (layout below), nothing is read back
+// (guard, ctl_copy: see enqueue_major_eval)
 static int enqueue_eval(pdlpdev_ctx* ctx, int which, int rc_rule_finite_bounds, double eps_rel_primal,
-                        double eps_rel_dual, double* sc)
+                        double eps_rel_dual, double* sc, int guard = 0, double* ctl_copy = nullptr)
 {
   hipStream_t s = ctx->stream;
   const int n = ctx->n, m = ctx->m;
@@ -329,6 +350,7 @@ static int enqueue_eval(pdlpdev_ctx* ctx, int which, int rc_rule_finite_bounds, 
   const double* altx = which == PDLPDEV_LAST_RESTART ? ctx->lrx : ctx->avgx;
   const double* alty = which == PDLPDEV_LAST_RESTART ? ctx->lry : ctx->avgy;
   const int kw       = which == PDLPDEV_CURRENT ? PDLPDEV_CURRENT : PDLPDEV_AVERAGE;
+  const int kwg      = kw | (guard ? kPeriodGuard : 0);  // (only the panel kernels know the flag: pdlpdev_run_period asks for no other layout)
   // the per-constraint (l-infinity) residuals are only consumed when per_constraint_residual is set: the host
   // driver passes negative eps_rel otherwise and the two extra vectors + four reduction launches are skipped
   const bool want_linf = eps_rel_primal >= 0.0 && eps_rel_dual >= 0.0;
@@ -344,17 +366,26 @@ static int enqueue_eval(pdlpdev_ctx* ctx, int which, int rc_rule_finite_bounds, 
   } else if (ctx->ja.on)
     (void)JAG_LAUNCH(ctx, k_jag_eval_primal, ctx->ja.v, ctx->ctl, kw, ctx->x[0], ctx->x[1], altx, ctx->y[0], ctx->y[1], alty, ctx->dr, ctx->lo_u, ctx->hi_u, eps_rel_primal, linf_m, ctx->ax_u[which], ctx->part_a);
   else if (ctx->pa.on)
-    (ctx->pa.v.seg ? k_panel_eval_primal<true> : k_panel_eval_primal<false>)<<<ctx->pa.v.W, kPanelThreads, 0, s>>>(ctx->pa.v, ctx->ctl, kw, ctx->x[0], ctx->x[1], altx, ctx->y[0], ctx->y[1], alty, ctx->dr, ctx->lo_u, ctx->hi_u, eps_rel_primal, linf_m, ctx->ax_u[which], ctx->part_a);
+    (ctx->pa.v.seg ? k_panel_eval_primal<true> : k_panel_eval_primal<false>)<<<ctx->pa.v.W, kPanelThreads, 0, s>>>(ctx->pa.v, ctx->ctl, kwg, ctx->x[0], ctx->x[1], altx, ctx->y[0], ctx->y[1], alty, ctx->dr, ctx->lo_u, ctx->hi_u, eps_rel_primal, linf_m, ctx->ax_u[which], ctx->part_a);
   else
     k_eval_primal<<<stream_grid(ctx->a_nb), kBlock, 0, s>>>(ctx->a_nb, ctx->a_rb, ctx->ha_off, ctx->ha_idx, ctx->ha_val, ctx->ctl, kw, ctx->x[0], ctx->x[1], altx, ctx->y[0], ctx->y[1], alty, ctx->dr, ctx->lo_u, ctx->hi_u, eps_rel_primal, linf_m, ctx->ax_u[which], ctx->part_a, ctx->dense.add_m);
-  k_finalize<<<1, kBlock, 0, s>>>(ctx->part_a, dual_partials(ctx), 3, 0u, sc + 0);
+  // one reduction launch for both sides of the evaluation where nothing else needs the primal sums in between
+  const bool one_finalize = !ctx->comm && !want_linf;
+  if (!one_finalize) k_finalize<<<1, kBlock, 0, s>>>(ctx->part_a, dual_partials(ctx), 3, 0u, sc + 0);
   if (want_linf) {
     const int g = std::min(grid_for(m), kGenericBlocks);
     k_max_partials<<<g, kBlock, 0, s>>>(m, ctx->tmp_m, ctx->part_g);
     k_finalize<<<1, kBlock, 0, s>>>(ctx->part_g, g, 1, 1u, sc + 3);
   }
   EvalDualCore core{nullptr, ctx->dc, ctx->c_u, ctx->lb_u, ctx->ub_u, eps_rel_dual, rc_rule_finite_bounds, which == PDLPDEV_LAST_RESTART ? ctx->rc_scratch : ctx->rc[which == PDLPDEV_AVERAGE ? 1 : 0], linf_n, ctx->aty_u[which]};
-  if (!ctx->comm) {
+  // The current iterate's A^T y is in the loop's buffer (pdlp_ctx.hpp aty_valid): the product-free twin reads it there.  Behind the
+  // guard the evaluation runs only when the attempts enqueued in front of it accepted a step, which is what makes the buffer valid.
+  const bool reuse = which == PDLPDEV_CURRENT && ctx->eval_reuse_aty && !ctx->comm && ctx->pat.on && (ctx->aty_valid || guard);
+  if (which == PDLPDEV_CURRENT && !ctx->comm) (reuse ? ctx->stat_eval_reused : ctx->stat_eval_product) += 1;
+  if (reuse) {
+    k_panel_eval_dual_from_aty<<<ctx->pat.v.W, kPanelThreads, 0, s>>>(ctx->pat.v, ctx->ctl, ctx->x[0], ctx->x[1], ctx->aty[0], ctx->aty[1], core, ctx->part_at, guard);
+    k_finalize_eval<<<1, kBlock, 0, s>>>(ctx->part_a, dual_partials(ctx), ctx->part_at, step_partials(ctx), one_finalize ? 1 : 0, sc, ctx->ctl, guard, ctl_copy);
+  } else if (!ctx->comm) {
     if (kw == PDLPDEV_AVERAGE) dense_part(ctx, 1, alty, nullptr, 0, 0);
     else dense_part(ctx, 1, ctx->y[0], ctx->y[1], 2, 0);
     if (ctx->pbat.on) {
@@ -364,10 +395,10 @@ static int enqueue_eval(pdlpdev_ctx* ctx, int which, int rc_rule_finite_bounds, 
     } else if (ctx->jat.on)
       (void)JAG_LAUNCH(ctx, k_jag_eval_dual, ctx->jat.v, ctx->ctl, kw, ctx->x[0], ctx->x[1], altx, ctx->y[0], ctx->y[1], alty, core, ctx->part_at);
     else if (ctx->pat.on)
-      (ctx->pat.v.seg ? k_panel_eval_dual<true> : k_panel_eval_dual<false>)<<<ctx->pat.v.W, kPanelThreads, 0, s>>>(ctx->pat.v, ctx->ctl, kw, ctx->x[0], ctx->x[1], altx, ctx->y[0], ctx->y[1], alty, core, ctx->part_at);
+      (ctx->pat.v.seg ? k_panel_eval_dual<true> : k_panel_eval_dual<false>)<<<ctx->pat.v.W, kPanelThreads, 0, s>>>(ctx->pat.v, ctx->ctl, kwg, ctx->x[0], ctx->x[1], altx, ctx->y[0], ctx->y[1], alty, core, ctx->part_at);
     else
       k_eval_dual<<<stream_grid(ctx->at_nb), kBlock, 0, s>>>(ctx->at_nb, ctx->at_rb, ctx->hat_off, ctx->hat_idx, ctx->hat_val, ctx->ctl, kw, ctx->x[0], ctx->x[1], altx, ctx->y[0], ctx->y[1], alty, core, ctx->part_at, ctx->dense.add_n);
-    k_finalize<<<1, kBlock, 0, s>>>(ctx->part_at, step_partials(ctx), 4, 0u, sc + 4);
+    k_finalize_eval<<<1, kBlock, 0, s>>>(ctx->part_a, dual_partials(ctx), ctx->part_at, step_partials(ctx), one_finalize ? 1 : 0, sc, ctx->ctl, guard, ctl_copy);
   } else {
     // partial A^T y of this row block, all-reduced together with the three dual-side row sums
     if (kw == PDLPDEV_AVERAGE) {
@@ -413,15 +444,32 @@ int pdlpdev_major_eval(pdlpdev_ctx* ctx, int average_mode, int rc_rule_finite_bo
   if (ctx->small_resident && !ctx->comm) {
     TRY(resident_major_eval(ctx, average_mode, rc_rule_finite_bounds, want_linf ? 1 : 0, eps_rel_primal, eps_rel_dual));
   } else {
-    TRY(pdlpdev_flush_average(ctx));
-    TRY(pdlpdev_make_average(ctx, average_mode));
-    TRY(enqueue_eval(ctx, PDLPDEV_CURRENT, rc_rule_finite_bounds, eps_rel_primal, eps_rel_dual, ctx->scal));
-    TRY(enqueue_eval(ctx, PDLPDEV_AVERAGE, rc_rule_finite_bounds, eps_rel_primal, eps_rel_dual, ctx->scal + 32));
+    TRY(enqueue_major_eval(ctx, average_mode, rc_rule_finite_bounds, eps_rel_primal, eps_rel_dual, 0));
     TRY(fetch_scalars(ctx, 41));
+    ctx->stat_loop_syncs += 1;
   }
   read_eval(ctx->scal_h, want_linf, out_current);
   read_eval(ctx->scal_h + 32, want_linf, out_average);
   return 0;
+}
+int enqueue_major_eval(pdlpdev_ctx* ctx, int average_mode, int rc_rule_finite_bounds, double eps_rel_primal, double eps_rel_dual, int guard)
+{
+  hipStream_t s = ctx->stream;
+  const int g   = grid_for(std::max(ctx->n, ctx->m));
+  // (k_clear_pending rides on k_make_average: one dependent launch less)
+  k_flush_average<<<g, kBlock, 0, s>>>(ctx->n, ctx->m, ctx->ctl, ctx->x[0], ctx->x[1], ctx->y[0], ctx->y[1], ctx->sumx, ctx->sumy, guard);
+  k_make_average<<<g, kBlock, 0, s>>>(ctx->n, ctx->m, average_mode | (guard ? kPeriodGuard : 0), ctx->ctl, ctx->x[0], ctx->x[1], ctx->y[0], ctx->y[1], ctx->sumx,
+                                      ctx->sumy, ctx->avgx, ctx->avgy, &ctx->ctl->pending_avg);
+  LAUNCH_CHECK();
+  if (!guard) ctx->ctl_h->pending_avg = 0;  // (what the device holds now; behind the guard the read-back says it)
+  TRY(enqueue_eval(ctx, PDLPDEV_CURRENT, rc_rule_finite_bounds, eps_rel_primal, eps_rel_dual, ctx->scal, guard));
+  TRY(enqueue_eval(ctx, PDLPDEV_AVERAGE, rc_rule_finite_bounds, eps_rel_primal, eps_rel_dual, ctx->scal + 32, guard, guard ? ctx->scal + kCtlSlot : nullptr));
+  return 0;
+}
+void read_major_eval(pdlpdev_ctx* ctx, double* out_current, double* out_average)
+{
+  read_eval(ctx->scal_h, false, out_current);
+  read_eval(ctx->scal_h + 32, false, out_average);
 }
 
 int pdlpdev_eval_infeasibility(pdlpdev_ctx* ctx, int which, int rc_rule_finite_bounds, double out[4])
@@ -556,6 +604,7 @@ int pdlpdev_restart(pdlpdev_ctx* ctx, int which, int unscaled_distances, double 
   HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
   const int g = std::min(grid_for(std::max(ctx->n, ctx->m)), kGenericBlocks);
+  loop_state_touched(ctx);
   k_restart<<<g, kBlock, 0, s>>>(ctx->n, ctx->m, which, unscaled_distances, ctx->dc, ctx->dr, ctx->ctl, ctx->x[0], ctx->x[1], ctx->y[0], ctx->y[1], ctx->avgx, ctx->avgy, ctx->lrx, ctx->lry, ctx->sumx, ctx->sumy, ctx->part_g);
   k_finalize<<<1, kBlock, 0, s>>>(ctx->part_g, g, 2, 0u, ctx->scal);
   k_restart_ctl<<<1, 1, 0, s>>>(ctx->ctl);

@@ -128,6 +128,10 @@ extern template __global__ void k_panel_eval_dual<false>(PanelView P, const pdlp
                   const double* __restrict__ avgx, const double* __restrict__ y0,
                   const double* __restrict__ y1, const double* __restrict__ avgy, EvalDualCore core,
                   double* __restrict__ part);
+__global__ void __launch_bounds__(kPanelThreads)
+k_panel_eval_dual_from_aty(PanelView P, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ x0, const double* __restrict__ x1,
+                           const double* __restrict__ aty0, const double* __restrict__ aty1, EvalDualCore core,
+                           double* __restrict__ part, int guard);
 template <int WAVES>
 __global__ void __launch_bounds__(WAVES * 64)
 k_jag_a_dual(JagView J, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ xbar,

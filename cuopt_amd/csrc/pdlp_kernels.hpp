@@ -141,6 +141,18 @@ __device__ __forceinline__ bool loop_active(const pdlpdev_ctl* ctl)
 {
   return ctl->error == 0 && ctl->steps_taken < ctl->target_steps;
 }
+// The mirror image, for what the fused period path enqueues BEHIND a period's attempts (averages, both evaluations): it runs only once
+// the attempts reached their target.  A period that fell short (a rejected attempt beyond the spare ones, a step error) leaves these
+// kernels empty; the host then makes up the attempts and evaluates the present way.
+__device__ __forceinline__ bool period_reached(const pdlpdev_ctl* ctl) { return ctl->steps_taken >= ctl->target_steps; }
+// (the evaluation kernels carry the request for that guard as a flag on their `which` / `mode` argument)
+constexpr int kPeriodGuard = 0x100;
+__device__ __forceinline__ bool period_guard_skips(const pdlpdev_ctl* ctl, int& arg)
+{
+  const bool guarded = (arg & kPeriodGuard) != 0;
+  arg &= ~kPeriodGuard;
+  return guarded && !period_reached(ctl);
+}
 
 // block b executes on XCD (b % 8) (observed dispatch order, speed only): give each XCD one
 // contiguous range of row blocks so that neighbouring rows -- which in real LPs touch neighbouring

@@ -94,6 +94,10 @@ struct cuoptamd_solver {
   int32_t iteration_offset = 0;  // total_pdlp_iterations_ - internal_solver_iterations_
   int32_t attempt_offset   = 0;
   int32_t major_done_at    = -1;
+  // the fused period path (pdlpdev_run_period): the evaluation of the major iteration that is due now, done behind the attempts
+  bool fused_eval_ready = false;
+  pdlpdev_small_eval fused_rq{};
+  double fused_ev[PDLPDEV_EV_COUNT] = {}, fused_ev_avg[PDLPDEV_EV_COUNT] = {};
   bool step_error = false, need_aty = true, last_restart_was_average = false;
   double last_candidate_kkt = 0.0, last_restart_kkt = 0.0;
   // the reference leaves gap_reduction_ratio_last_trial_ uninitialised (pdlp_restart_strategy.cu:160);
@@ -329,14 +333,15 @@ struct HostRange {  // roctx range of a host-side phase (LP/pdlp.cu:541,1227 are
 
 // The head of a major iteration asks the device for: pending average + average iterate + both convergence evaluations
 // (pdlpdev_major_eval; one launch for K LPs of a small-LP batch) ...
-pdlpdev_small_eval major_eval_request(const cuoptamd_solver* s)
+// (at `total_iterations` iterations with `its_since_restart` of them behind the last restart: the fused period path asks ahead of the attempts)
+pdlpdev_small_eval major_eval_request_at(const cuoptamd_solver* s, int32_t total_iterations, int32_t its_since_restart)
 {
   // pdlp.cu:1110-1122: with 0 or 1 steps the average IS the iterate (avoids a*x/x != x);
   // right after a restart the sums are empty and the reference yields zeros.
   int mode = 2;
-  if (s->total_iterations - s->iteration_offset <= 1 && !s->warm_started)  // internal_solver_iterations_ <= 1
+  if (total_iterations - s->iteration_offset <= 1 && !s->warm_started)  // internal_solver_iterations_ <= 1
     mode = 0;
-  else if (s->ctl.its_since_restart == 0)
+  else if (its_since_restart == 0)
     mode = 1;
   pdlpdev_small_eval r;
   r.mode        = mode;
@@ -346,6 +351,7 @@ pdlpdev_small_eval major_eval_request(const cuoptamd_solver* s)
   r.eps_d = s->S.per_constraint_residual ? s->S.relative_dual_tolerance : -1.0;
   return r;
 }
+pdlpdev_small_eval major_eval_request(const cuoptamd_solver* s) { return major_eval_request_at(s, s->total_iterations, s->ctl.its_since_restart); }
 // ... and, when the KKT rule decides to restart, for pdlpdev_restart(which, unscaled) -- whose distances then give the new primal
 // weight (major_restart_done).  The plan is what the head hands back to whoever talks to the device.
 struct MajorPlan {
@@ -363,7 +369,15 @@ int major_iteration(cuoptamd_solver* s, bool* terminated)
   pdlpdev_ctx* dev = s->dev;
   const pdlpdev_small_eval rq = major_eval_request(s);
   double ev[PDLPDEV_EV_COUNT], ev_avg[PDLPDEV_EV_COUNT];
-  DEV(pdlpdev_major_eval(dev, rq.mode, rq.rule_finite, rq.eps_p, rq.eps_d, ev, ev_avg));
+  const pdlpdev_small_eval& fq = s->fused_rq;
+  if (s->fused_eval_ready && fq.mode == rq.mode && fq.rule_finite == rq.rule_finite && fq.eps_p == rq.eps_p && fq.eps_d == rq.eps_d) {
+    // pdlpdev_run_period evaluated behind the attempts, with the request this major iteration makes
+    std::copy(s->fused_ev, s->fused_ev + PDLPDEV_EV_COUNT, ev);
+    std::copy(s->fused_ev_avg, s->fused_ev_avg + PDLPDEV_EV_COUNT, ev_avg);
+  } else {
+    DEV(pdlpdev_major_eval(dev, rq.mode, rq.rule_finite, rq.eps_p, rq.eps_d, ev, ev_avg));
+  }
+  s->fused_eval_ready = false;
   MajorPlan plan;
   int rc = major_head(s, ev, ev_avg, terminated, &plan);
   if (rc != 0 || *terminated || !plan.restart) return rc;
@@ -1153,6 +1167,7 @@ static void reset_host_state(cuoptamd_solver* s)
 {
   const cuoptamd_result blank{};
   s->total_iterations = 0, s->iteration_offset = 0, s->attempt_offset = 0, s->major_done_at = -1;
+  s->fused_eval_ready = false;
   s->step_error = false, s->need_aty = true, s->last_restart_was_average = false;
   s->last_candidate_kkt = 0.0, s->last_restart_kkt = 0.0, s->gap_reduction_ratio_last_trial = 1.0;
   s->best_quality = cuoptamd_solver::Quality{};
@@ -1316,13 +1331,27 @@ int cuoptamd_solver_advance(cuoptamd_solver* s, int32_t max_new_iterations, cuop
   }
   if (s->finished) return leave(0);
   const int32_t budget_end = advance_budget_end(s, max_new_iterations);
+  const bool period_path   = cuopt_amd::tune_int("period_path", 1) != 0;  // (CUOPT_AMD_TUNE=period_path=0: attempts and evaluation apart, as before)
   for (;;) {
     int32_t target = 0;
     bool stop      = false;
     int rc         = advance_to_attempts(s, budget_end, &target, &stop);
     if (rc != 0 || stop) return leave(rc);
-    rc = pdlpdev_run(s->dev, target, &s->ctl);
-    if (rc != 0) return leave(fail(rc, "pdlpdev_run: %s", pdlpdev_last_error()));
+    // The fused period path: when the step count alone says that a major iteration is due exactly at the target (not a step error, not
+    // the artificial restart of Fast1), its evaluation is enqueued behind the attempts and both come back with one synchronisation.
+    const cuoptamd_hyper& H   = s->H;
+    const int32_t total_after = s->iteration_offset + target;
+    const bool due_at_target  = (total_after % H.major_iteration == 0 && total_after > 0) || total_after <= H.min_iteration_restart;
+    if (period_path && s->world == 1 && !H.artificial_restart_in_main_loop && due_at_target) {
+      s->fused_rq       = major_eval_request_at(s, total_after, s->ctl.its_since_restart + (target - s->ctl.steps_taken));
+      int32_t evaluated = 0;
+      rc = pdlpdev_run_period(s->dev, target, &s->fused_rq, &s->ctl, s->fused_ev, s->fused_ev_avg, &evaluated);
+      if (rc != 0) return leave(fail(rc, "pdlpdev_run_period: %s", pdlpdev_last_error()));
+      s->fused_eval_ready = evaluated != 0;
+    } else {
+      rc = pdlpdev_run(s->dev, target, &s->ctl);
+      if (rc != 0) return leave(fail(rc, "pdlpdev_run: %s", pdlpdev_last_error()));
+    }
     advance_after_attempts(s);
   }
 }

@@ -110,6 +110,8 @@ enum {
   PDLPDEV_BUF_RC_CURRENT, /* reduced costs from the last eval(CURRENT)  n */
   PDLPDEV_BUF_RC_AVERAGE, /*                                            n */
   PDLPDEV_BUF_LAST_RESTART_X, PDLPDEV_BUF_LAST_RESTART_Y,
+  PDLPDEV_BUF_ATY_U_CURRENT, /* A^T y of the unscaled problem from the last eval(CURRENT)  n */
+  PDLPDEV_BUF_ATY_U_AVERAGE, /*                                                            n */
   PDLPDEV_BUF_COUNT
 };
 
@@ -396,6 +398,20 @@ int pdlpdev_eval(pdlpdev_ctx* ctx, int which, int rc_rule_finite_bounds, double 
  * eval(AVERAGE), with a single read-back (one launch in total for LPs on the resident small-LP path). */
 int pdlpdev_major_eval(pdlpdev_ctx* ctx, int average_mode, int rc_rule_finite_bounds, double eps_rel_primal,
                        double eps_rel_dual, double out_current[PDLPDEV_EV_COUNT], double out_average[PDLPDEV_EV_COUNT]);
+/* One major-iteration period with one synchronisation: pdlpdev_run(target_steps) with the pdlpdev_major_eval(rq) that is due AT the
+ * target enqueued right behind the attempts -- plus a few spare attempts, as many as the period before saw rejections (at most 4), which
+ * like every attempt do nothing once the target is reached.  The evaluation's kernels do nothing UNLESS the target was reached.
+ * *evaluated = 1: out_current / out_average are what pdlpdev_major_eval would return now.  *evaluated = 0: the attempts are done as
+ * pdlpdev_run does them, nothing of the major iteration has happened (context not eligible: sharded, resident small-LP path, a layout
+ * other than the panels, l-infinity residuals requested, a control block the host does not hold; or the period fell short of the
+ * spare attempts; or the step error is up) and the caller calls pdlpdev_major_eval itself.  The caller must KNOW that a major
+ * iteration is due at target_steps and what it will request. */
+int pdlpdev_run_period(pdlpdev_ctx* ctx, int32_t target_steps, const pdlpdev_small_eval* rq, pdlpdev_ctl* ctl,
+                       double out_current[PDLPDEV_EV_COUNT], double out_average[PDLPDEV_EV_COUNT], int32_t* evaluated);
+/* Read-only counters since create: out = {evaluations of the current iterate that read A^T y from the loop's buffer, ... that ran the
+ * product, host synchronisations inside pdlpdev_run / pdlpdev_run_period / pdlpdev_major_eval, attempts enqueued that found their
+ * target reached (empty launches)}.  Single-GPU, non-resident contexts. */
+int pdlpdev_loop_stats(pdlpdev_ctx* ctx, int64_t out[4]);
 /* Infeasibility information of the iterate evaluated by the LAST pdlpdev_eval(which) call (its A x and
  * A^T y are reused; the iterate itself is the ray estimate, infeasibility_information.cu:176-223):
  * out = {max_primal_ray_infeasibility, primal_ray_linear_objective, max_dual_ray_infeasibility,
