@@ -86,7 +86,16 @@ class Hyper(C.Structure):
                 ("update_primal_weight_on_initial_solution", c_int),
                 ("update_step_size_on_initial_solution", c_int),
                 ("handle_some_primal_gradients_on_finite_bounds_as_residuals", c_int),
-                ("project_initial_primal", c_int)]
+                ("project_initial_primal", c_int),
+                # trailing fields, not in the reference: algorithm 0 = PDHG with averages, 1 = restarted reflected Halpern
+                ("algorithm", c_int), ("halpern_power_max_products", c_int),
+                ("halpern_step_safety", c_double), ("halpern_power_tolerance", c_double)]
+
+
+class Halpern(C.Structure):
+    """pdlpdev_halpern: the scalars of the reflected Halpern mode"""
+    _fields_ = [("r", c_double), ("r_first", c_double), ("r2", c_double), ("r2_min", c_double),
+                ("k", c_int), ("reserved", c_int)]
 
 
 class SolverSettings(C.Structure):
@@ -322,11 +331,19 @@ _proto("pdlpdev_resident_size", c_int, c_int, c_int, C.c_int64)
 _proto("pdlpdev_batch_time_kernels", c_int, c_void_p, c_int, c_void_p)
 _proto("pdlpdev_synthetic_lp", c_int, c_int, c_int, c_int, c_int, C.c_uint64, *([c_void_p] * 8))
 
+if hasattr(lib, "pdlpdev_set_halpern"):  # (an older build given through CUOPT_AMD_LIB has no Halpern mode)
+    _proto("pdlpdev_create_no_resident", None, c_int)
+    _proto("pdlpdev_set_halpern", c_int, c_void_p, c_int)
+    _proto("pdlpdev_spectral_norm", c_int, c_void_p, c_double, c_int, P(c_double), P(c_int))
+    _proto("pdlpdev_halpern_restart", c_int, c_void_p, c_double, c_void_p, P(Ctl))
+    _proto("pdlpdev_get_halpern", c_int, c_void_p, P(Halpern))
+PDLP_SOLVER_MODE_HALPERN1 = 4  # CUOPT_AMD_PDLP_SOLVER_MODE_HALPERN1 (cuopt_c_ext.h)
+
 # ids of pdlp_device.h
 BUF = {n: i for i, n in enumerate(
     ["X", "Y", "X_OTHER", "Y_OTHER", "ATY", "ATY_OTHER", "XBAR", "SUM_X", "SUM_Y", "AVG_X", "AVG_Y",
      "DROW", "DCOL", "A_VALUES", "AT_VALUES", "C", "LB", "UB", "LO", "HI", "RC_CURRENT", "RC_AVERAGE",
-     "LAST_RESTART_X", "LAST_RESTART_Y", "ATY_U_CURRENT", "ATY_U_AVERAGE"])}
+     "LAST_RESTART_X", "LAST_RESTART_Y", "ATY_U_CURRENT", "ATY_U_AVERAGE", "LAST_RESTART_ATY"])}
 KERNEL = {n: i for i, n in enumerate(
     ["PRIMAL", "SPMV_A_DUAL", "SPMV_AT_STEP", "STEP_DECISION", "SPMV_A_PLAIN", "SPMV_AT_PLAIN"])}
 EV = {n: i for i, n in enumerate(
@@ -1053,6 +1070,28 @@ class Device:
         c = Ctl()
         self._ck(lib.pdlpdev_run(self.handle, int(target_steps), C.byref(c)))
         return c
+
+    # ---- reflected Halpern mode (pdlp_device.h) ----
+    def set_halpern(self, on=True):
+        self._ck(lib.pdlpdev_set_halpern(self.handle, int(bool(on))))
+
+    def spectral_norm(self, rel_tol=1e-6, max_products=5000):
+        """pdlpdev_spectral_norm -> (sigma_max of the scaled matrix, products of A^T A the power iteration formed)"""
+        sig, cnt = c_double(), c_int()
+        self._ck(lib.pdlpdev_spectral_norm(self.handle, float(rel_tol), int(max_products), C.byref(sig), C.byref(cnt)))
+        return sig.value, cnt.value
+
+    def halpern_restart(self, theta=-1.0):
+        """pdlpdev_halpern_restart -> (||x - x0||, ||y - y0||, control block); theta < 0: anchor and counters only"""
+        dist, c = np.zeros(2), Ctl()
+        self._ck(lib.pdlpdev_halpern_restart(self.handle, float(theta), _ptr(dist), C.byref(c)))
+        return float(dist[0]), float(dist[1]), c
+
+    def halpern(self):
+        """the Halpern scalars as the last run / restart / ctl() read them back: dict(r, r_first, r2, r2_min, k)"""
+        h = Halpern()
+        self._ck(lib.pdlpdev_get_halpern(self.handle, C.byref(h)))
+        return dict(r=h.r, r_first=h.r_first, r2=h.r2, r2_min=h.r2_min, k=h.k)
 
     def download(self, name, count):
         out = np.zeros(int(count))

@@ -20,6 +20,7 @@
 #include <thread>
 #include <vector>
 
+#include "cuopt_amd/cuopt_c_ext.h"
 #include "cuopt_amd/pdlp_solver.h"
 #include "host_parallel.hpp"
 #include "mps_reader.hpp"
@@ -98,7 +99,7 @@ struct Settings {
               {CUOPT_PRIMAL_INFEASIBLE_TOLERANCE, &primal_infeasible_tolerance, 0.0, 1e-1},
               {CUOPT_DUAL_INFEASIBLE_TOLERANCE, &dual_infeasible_tolerance, 0.0, 1e-1}};
     ints = {{CUOPT_ITERATION_LIMIT, &iteration_limit, 0, INT_MAX},
-            {CUOPT_PDLP_SOLVER_MODE, &pdlp_solver_mode, CUOPT_PDLP_SOLVER_MODE_STABLE1, CUOPT_PDLP_SOLVER_MODE_FAST1},
+            {CUOPT_PDLP_SOLVER_MODE, &pdlp_solver_mode, CUOPT_PDLP_SOLVER_MODE_STABLE1, CUOPT_AMD_PDLP_SOLVER_MODE_HALPERN1},
             {CUOPT_METHOD, &method, CUOPT_METHOD_CONCURRENT, CUOPT_METHOD_DUAL_SIMPLEX},
             {CUOPT_NUM_CPU_THREADS, &num_cpu_threads, -1, INT_MAX},
             {"amd_num_gpus", &num_gpus, 0, 16},
@@ -772,9 +773,11 @@ cuopt_int_t cuOptSolve(cuOptOptimizationProblem problem, cuOptSolverSettings set
     st.first_primal_feasible   = s->first_primal_feasible;
     // a simplex would prove infeasibility / unboundedness: the emulation runs PDLP WITH its infeasibility detection
     // (small LPs only -- large ones keep the reference PDLP's default, detection off unless asked for)
-    st.detect_infeasibility        = s->infeasibility_detection || simplex_grade;
+    // (the reflected Halpern mode has no infeasibility detection: the emulation leaves it off there; a caller who asks for it by name
+    //  gets the solver's refusal)
+    st.detect_infeasibility        = s->infeasibility_detection || (simplex_grade && hyper.algorithm != 1);
     st.strict_infeasibility        = s->strict_infeasibility;
-    st.unbounded_from_feasible_iterates = simplex_grade;  // a simplex would say UNBOUNDED
+    st.unbounded_from_feasible_iterates = simplex_grade && hyper.algorithm != 1;  // a simplex would say UNBOUNDED (needs the detection)
     st.primal_infeasible_tolerance = s->primal_infeasible_tolerance;
     st.dual_infeasible_tolerance   = s->dual_infeasible_tolerance;
     st.save_best_primal_so_far     = s->save_best_primal_so_far;
@@ -954,11 +957,13 @@ cuopt_int_t cuOptSolve(cuOptOptimizationProblem problem, cuOptSolverSettings set
       std::snprintf(info, sizeof info,
                     "{\"engine\": \"%s\", \"requested_method\": \"%s\", \"crossover_requested\": %s, \"simplex_grade_emulation\": %s, "
                     "\"dual_simplex_consulted\": %s, \"dual_simplex_status\": %d, \"crossover\": \"%s\", "
-                    "\"answered_by\": \"%s\", \"gpus\": %d, \"iterations\": %d, \"simplex_grade_attempt_iterations\": %d}",
+                    "\"answered_by\": \"%s\", \"gpus\": %d, \"iterations\": %d, \"simplex_grade_attempt_iterations\": %d, "
+                    "\"pdlp_algorithm\": \"%s\"}",
                     engine_answered ? "dual_simplex" : "pdlp", method_name, s->crossover ? "true" : "false", simplex_grade ? "true" : "false",
                     engine_ran ? "true" : "false", (int)sx.status, crossover_by, answered.c_str(), gpus,
                     res.steps_taken + (answered == "requested_tolerances_after_simplex_grade_budget" ? first_attempt_steps : 0),
-                    answered == "requested_tolerances_after_simplex_grade_budget" ? first_attempt_steps : 0);
+                    answered == "requested_tolerances_after_simplex_grade_budget" ? first_attempt_steps : 0,
+                    hyper.algorithm == 1 ? "reflected_halpern" : "pdhg_average");
       sol->solve_info = info;
       if (other_method || s->crossover) say("cuopt_amd: " + sol->solve_info + "\n");
     }

@@ -774,6 +774,8 @@ int pdlpdev_clone_shared(pdlpdev_ctx** out, pdlpdev_ctx* parent)
   c->shared_with_parent = true;
   c->parent = nullptr;  // (set once the clone is complete: a failed clone is destroyed without touching the parent's count)
   c->scal_h = nullptr, c->ctl_h = nullptr;  // (the parent's pinned block until the clone has its own: a clone that fails below must not free it)
+  // (likewise the parent's Halpern block and anchor: the mode is the clone's to switch on -- pdlpdev_set_halpern gives it its own)
+  c->halpern = false, c->lraty = nullptr, c->hal = nullptr, c->hal_h = nullptr;
   c->clones_alive = 0, c->batches_alive = 0, c->rows_private = false;
   c->bytes = 0, c->slab = nullptr, c->slab_cap = c->slab_used = 0, c->arena = nullptr, c->arena_used = 0, c->first_chunk = nullptr;
   c->bestx = c->besty = c->bestrc = nullptr;
@@ -848,6 +850,8 @@ int pdlpdev_batch_create(pdlpdev_batch** out, pdlpdev_ctx** ctx, int K)
         c->jat.v.row0 != c0->jat.v.row0 || c->ja.v.val != c0->ja.v.val || c->jat.v.val != c0->jat.v.val || c->stream != c0->stream)
       return fail(-1, "pdlpdev_batch_create: the contexts do not share one matrix (pdlpdev_clone_shared)");
   }
+  for (int l = 0; l < K; ++l)
+    if (ctx[l]->halpern) return fail(-7, "pdlpdev_batch_create: not eligible (LP %d is in reflected Halpern mode: the lockstep kernels carry the averaging iteration only)", l);
   if ((int64_t)std::max(c0->m, c0->n) * K >= ((int64_t)1 << 32))
     return fail(-7, "pdlpdev_batch_create: not eligible (the interleaved vectors are addressed with 32-bit element offsets: max(m, n) * K < 2^32)");
   // per side: the row-sum variant of the panels, the CSR stream layout or the jagged layout -- the three whose rows are summed by one lane

@@ -36,6 +36,31 @@ k_jag_at_step(JagView J, const pdlpdev_ctl* __restrict__ ctl, const double* __re
   jag_block<decltype(e), WAVES>(J, cur ? y0 : y1 /* y' */, e, part);
 }
 
+// Halpern twins (pdlp_epilogues.hpp)
+template <int WAVES>
+__global__ void __launch_bounds__(WAVES * 64)
+k_jag_a_halpern(JagView J, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ xbar,
+                double* __restrict__ y0, double* __restrict__ y1, const double* __restrict__ lo,
+                const double* __restrict__ hi, HalpernArgs h, double* __restrict__ part)
+{
+  if (!loop_active(ctl)) return;
+  const int cur = ctl->cur;
+  HalpernDualEpilogue e{cur ? y1 : y0, cur ? y0 : y1, h.ty, h.y0, lo, hi, ctl->sigma, HalpernWeights(h.hal)};
+  jag_block<decltype(e), WAVES>(J, xbar, e, part);
+}
+
+template <int WAVES>
+__global__ void __launch_bounds__(WAVES * 64)
+k_jag_at_halpern(JagView J, const pdlpdev_ctl* __restrict__ ctl, double* __restrict__ x0, double* __restrict__ x1,
+                 double* __restrict__ aty0, double* __restrict__ aty1, HalpernArgs h, double* __restrict__ part)
+{
+  if (!loop_active(ctl)) return;
+  const int cur = ctl->cur;
+  HalpernStepEpilogue e{cur ? x1 : x0, cur ? x0 : x1, cur ? aty1 : aty0, cur ? aty0 : aty1, h.x0, h.aty0,
+                        halpern_last_step(ctl) ? h.tx : nullptr, HalpernWeights(h.hal)};
+  jag_block<decltype(e), WAVES>(J, h.ty /* y' */, e, part);
+}
+
 template <int WAVES>
 __global__ void __launch_bounds__(WAVES * 64)
 k_jag_at_cur(JagView J, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ y0,
@@ -88,6 +113,16 @@ k_jag_eval_dual(JagView J, const pdlpdev_ctl* __restrict__ ctl, int which,
 }
 
 // explicit instantiations (the launch sites live in another translation unit)
+template __global__ void k_jag_a_halpern<8>(JagView J, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ xbar,
+                double* __restrict__ y0, double* __restrict__ y1, const double* __restrict__ lo,
+                const double* __restrict__ hi, HalpernArgs h, double* __restrict__ part);
+template __global__ void k_jag_a_halpern<16>(JagView J, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ xbar,
+                double* __restrict__ y0, double* __restrict__ y1, const double* __restrict__ lo,
+                const double* __restrict__ hi, HalpernArgs h, double* __restrict__ part);
+template __global__ void k_jag_at_halpern<8>(JagView J, const pdlpdev_ctl* __restrict__ ctl, double* __restrict__ x0, double* __restrict__ x1,
+                 double* __restrict__ aty0, double* __restrict__ aty1, HalpernArgs h, double* __restrict__ part);
+template __global__ void k_jag_at_halpern<16>(JagView J, const pdlpdev_ctl* __restrict__ ctl, double* __restrict__ x0, double* __restrict__ x1,
+                 double* __restrict__ aty0, double* __restrict__ aty1, HalpernArgs h, double* __restrict__ part);
 template __global__ void k_jag_a_dual<8>(JagView J, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ xbar,
              double* __restrict__ y0, double* __restrict__ y1, const double* __restrict__ lo,
              const double* __restrict__ hi, double* __restrict__ sumy, double* __restrict__ part, double* __restrict__ ycopy,

@@ -36,6 +36,31 @@ k_panel_at_step(PanelView P, const pdlpdev_ctl* __restrict__ ctl, const double* 
   panel_block<SEG>(P, cur ? y0 : y1 /* y' */, e, part);
 }
 
+// Halpern twins (pdlp_epilogues.hpp)
+template <bool SEG>
+__global__ void __launch_bounds__(kPanelThreads)
+k_panel_a_halpern(PanelView P, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ xbar,
+                  double* __restrict__ y0, double* __restrict__ y1, const double* __restrict__ lo,
+                  const double* __restrict__ hi, HalpernArgs h, double* __restrict__ part)
+{
+  if (!loop_active(ctl)) return;
+  const int cur = ctl->cur;
+  HalpernDualEpilogue e{cur ? y1 : y0, cur ? y0 : y1, h.ty, h.y0, lo, hi, ctl->sigma, HalpernWeights(h.hal)};
+  panel_block<SEG>(P, xbar, e, part);
+}
+
+template <bool SEG>
+__global__ void __launch_bounds__(kPanelThreads)
+k_panel_at_halpern(PanelView P, const pdlpdev_ctl* __restrict__ ctl, double* __restrict__ x0, double* __restrict__ x1,
+                   double* __restrict__ aty0, double* __restrict__ aty1, HalpernArgs h, double* __restrict__ part)
+{
+  if (!loop_active(ctl)) return;
+  const int cur = ctl->cur;
+  HalpernStepEpilogue e{cur ? x1 : x0, cur ? x0 : x1, cur ? aty1 : aty0, cur ? aty0 : aty1, h.x0, h.aty0,
+                        halpern_last_step(ctl) ? h.tx : nullptr, HalpernWeights(h.hal)};
+  panel_block<SEG>(P, h.ty /* y' */, e, part);
+}
+
 // panel twin of k_spmv_at_cur (A^T y of the iterate / of the trial iterate, optionally into `out_override`)
 template <bool SEG>
 __global__ void __launch_bounds__(kPanelThreads)
@@ -138,6 +163,16 @@ k_panel_eval_dual_from_aty(PanelView P, const pdlpdev_ctl* __restrict__ ctl, con
 }
 
 // explicit instantiations (the launch sites live in another translation unit)
+template __global__ void k_panel_a_halpern<true>(PanelView P, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ xbar,
+                  double* __restrict__ y0, double* __restrict__ y1, const double* __restrict__ lo,
+                  const double* __restrict__ hi, HalpernArgs h, double* __restrict__ part);
+template __global__ void k_panel_a_halpern<false>(PanelView P, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ xbar,
+                  double* __restrict__ y0, double* __restrict__ y1, const double* __restrict__ lo,
+                  const double* __restrict__ hi, HalpernArgs h, double* __restrict__ part);
+template __global__ void k_panel_at_halpern<true>(PanelView P, const pdlpdev_ctl* __restrict__ ctl, double* __restrict__ x0, double* __restrict__ x1,
+                   double* __restrict__ aty0, double* __restrict__ aty1, HalpernArgs h, double* __restrict__ part);
+template __global__ void k_panel_at_halpern<false>(PanelView P, const pdlpdev_ctl* __restrict__ ctl, double* __restrict__ x0, double* __restrict__ x1,
+                   double* __restrict__ aty0, double* __restrict__ aty1, HalpernArgs h, double* __restrict__ part);
 template __global__ void k_panel_a_dual<true>(PanelView P, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ xbar,
                double* __restrict__ y0, double* __restrict__ y1, const double* __restrict__ lo,
                const double* __restrict__ hi, double* __restrict__ sumy, double* __restrict__ part, double* __restrict__ ycopy,

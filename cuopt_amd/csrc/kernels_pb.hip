@@ -51,6 +51,34 @@ k_pb_at_step(PbView V, const pdlpdev_ctl* __restrict__ ctl, const double* __rest
   else pb_rows_block(V, e, part, pb_lds);
 }
 
+// Halpern twins (pdlp_epilogues.hpp); phase P in front of k_pb_at_halpern gathers y' from its own buffer (mode 0)
+template <bool WIDE>
+__global__ void __launch_bounds__(WIDE ? kPbwThreads : kPbThreads)
+k_pb_a_halpern(PbView V, const pdlpdev_ctl* __restrict__ ctl, double* __restrict__ y0, double* __restrict__ y1, const double* __restrict__ lo,
+               const double* __restrict__ hi, HalpernArgs h, double* __restrict__ part)
+{
+  extern __shared__ __attribute__((aligned(16))) double pb_lds[];
+  if (!loop_active(ctl)) return;
+  const int cur = ctl->cur;
+  HalpernDualEpilogue e{cur ? y1 : y0, cur ? y0 : y1, h.ty, h.y0, lo, hi, ctl->sigma, HalpernWeights(h.hal)};
+  if constexpr (WIDE) pbw_rows_block(V, e, part, pb_lds);
+  else pb_rows_block(V, e, part, pb_lds);
+}
+
+template <bool WIDE>
+__global__ void __launch_bounds__(WIDE ? kPbwThreads : kPbThreads)
+k_pb_at_halpern(PbView V, const pdlpdev_ctl* __restrict__ ctl, double* __restrict__ x0, double* __restrict__ x1,
+                double* __restrict__ aty0, double* __restrict__ aty1, HalpernArgs h, double* __restrict__ part)
+{
+  extern __shared__ __attribute__((aligned(16))) double pb_lds[];
+  if (!loop_active(ctl)) return;
+  const int cur = ctl->cur;
+  HalpernStepEpilogue e{cur ? x1 : x0, cur ? x0 : x1, cur ? aty1 : aty0, cur ? aty0 : aty1, h.x0, h.aty0,
+                        halpern_last_step(ctl) ? h.tx : nullptr, HalpernWeights(h.hal)};
+  if constexpr (WIDE) pbw_rows_block(V, e, part, pb_lds);
+  else pb_rows_block(V, e, part, pb_lds);
+}
+
 template <bool WIDE>
 __global__ void __launch_bounds__(WIDE ? kPbwThreads : kPbThreads)
 k_pb_at_cur(PbView V, const pdlpdev_ctl* __restrict__ ctl, double* __restrict__ aty0, double* __restrict__ aty1,
@@ -101,6 +129,14 @@ k_pb_eval_dual(PbView V, const pdlpdev_ctl* __restrict__ ctl, int which, const d
 }
 
 // explicit instantiations (the launch sites live in another translation unit)
+template __global__ void k_pb_a_halpern<false>(PbView V, const pdlpdev_ctl* __restrict__ ctl, double* __restrict__ y0, double* __restrict__ y1, const double* __restrict__ lo,
+               const double* __restrict__ hi, HalpernArgs h, double* __restrict__ part);
+template __global__ void k_pb_a_halpern<true>(PbView V, const pdlpdev_ctl* __restrict__ ctl, double* __restrict__ y0, double* __restrict__ y1, const double* __restrict__ lo,
+               const double* __restrict__ hi, HalpernArgs h, double* __restrict__ part);
+template __global__ void k_pb_at_halpern<false>(PbView V, const pdlpdev_ctl* __restrict__ ctl, double* __restrict__ x0, double* __restrict__ x1,
+                double* __restrict__ aty0, double* __restrict__ aty1, HalpernArgs h, double* __restrict__ part);
+template __global__ void k_pb_at_halpern<true>(PbView V, const pdlpdev_ctl* __restrict__ ctl, double* __restrict__ x0, double* __restrict__ x1,
+                double* __restrict__ aty0, double* __restrict__ aty1, HalpernArgs h, double* __restrict__ part);
 template __global__ void k_pb_products<512>(PbView V, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ v0, const double* __restrict__ v1, int mode, int in_loop);
 template __global__ void k_pb_products<1024>(PbView V, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ v0, const double* __restrict__ v1, int mode, int in_loop);
 template __global__ void k_pb_a_dual<false>(PbView V, const pdlpdev_ctl* __restrict__ ctl, double* __restrict__ y0, double* __restrict__ y1, const double* __restrict__ lo,

@@ -15,6 +15,9 @@ void dense_part(pdlpdev_ctx* ctx, int transpose, const double* v0, const double*
 // the attempts in front reached their target, and the last one leaves the control block in scal[kCtlSlot ..)
 int enqueue_major_eval(pdlpdev_ctx* ctx, int average_mode, int rc_rule_finite_bounds, double eps_rel_primal, double eps_rel_dual, int guard);
 void read_major_eval(pdlpdev_ctx* ctx, double* out_current, double* out_average);  // ... and its results out of scal_h
+// Halpern mode: the evaluation of T(z^k) (the average slots) alone, results in scal[32 ..), same guard (pdlp_eval.hip)
+int enqueue_halpern_eval(pdlpdev_ctx* ctx, int rc_rule_finite_bounds, double eps_rel_primal, double eps_rel_dual, int guard);
+void launch_restart_current(pdlpdev_ctx* ctx, int g);  // k_restart(CURRENT, scaled distances) -> part_g
 }
 
 // partial sums one product's epilogue leaves, by the side's layout

@@ -11,6 +11,7 @@ int sync_panel_values(pdlpdev_ctx* c);
 int resident_tier(int m, int n, int64_t nnz);
 
 static thread_local int g_create_sharded = 0;  // pdlpdev_create_hint: the next context will run behind a communicator
+static thread_local int g_create_no_resident = 0;  // pdlpdev_create_no_resident: the next context stays off the resident small-LP path
 static thread_local int g_create_batch_lanes = 0;  // pdlpdev_create_batch_lanes: the next context's jagged layouts serve batches that wide
 
 static int create_impl(pdlpdev_ctx** out, int device, int32_t m, int32_t n, const int32_t* a_offsets,
@@ -23,6 +24,7 @@ extern "C" {
 
 const char* pdlpdev_last_error(void) { return g_err.c_str(); }
 void pdlpdev_create_hint(int sharded) { g_create_sharded = sharded; }
+void pdlpdev_create_no_resident(int no_resident) { g_create_no_resident = no_resident; }
 void pdlpdev_create_batch_lanes(int lanes) { g_create_batch_lanes = lanes; }
 static thread_local pdlpdev_ctx* g_create_stream_donor = nullptr;
 void pdlpdev_create_share_stream(pdlpdev_ctx* donor) { g_create_stream_donor = donor; }
@@ -568,7 +570,8 @@ static int create_impl(pdlpdev_ctx** out, int device, int32_t m, int32_t n, cons
     const char* small_env = getenv("CUOPT_AMD_SMALL");
     const int tier        = resident_tier(m, n, ctx->nnz);
     ctx->eval_reuse_aty   = cuopt_amd::tune_int("eval_reuse_aty", 1) != 0;
-    ctx->small_resident   = tier >= 0 && !(small_env && atoi(small_env) == 0) && !ctx->dense.add_m && !ctx->dense.add_n;
+    ctx->small_resident   = tier >= 0 && !(small_env && atoi(small_env) == 0) && !ctx->dense.add_m && !ctx->dense.add_n && !g_create_no_resident;
+    g_create_no_resident  = 0;
     if (small_env && atoi(small_env) != 0 && tier < 0)
       return fail(-1, "CUOPT_AMD_SMALL=1: the LP does not fit the resident kernel (m, n <= 2048, nnz <= 4096 ...)");
   }
@@ -621,6 +624,7 @@ void pdlpdev_destroy(pdlpdev_ctx* ctx)
   if (ctx->p2p.base) (void)hipFree(ctx->p2p.base);
   if (ctx->comm && !ctx->soft) comm_cache::release(ctx->comm_key);
   for (void* p : ctx->allocs) (void)hipFree(p);
+  if (ctx->hal_h) (void)hipHostFree(ctx->hal_h);
   const bool whole = ctx->stream && ctx->scal_h && ctx->first_chunk && !ctx->shared_with_parent && !ctx->stream_borrowed;
   if (!(whole && give_recycled(Recycled{ctx->device, ctx->stream, ctx->scal_h, ctx->first_chunk}))) {
     if (ctx->first_chunk) (void)hipFree(ctx->first_chunk);

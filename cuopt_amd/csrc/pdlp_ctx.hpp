@@ -409,6 +409,11 @@ struct pdlpdev_ctx {
   double *scal_h = nullptr;                      // pinned mirror
   pdlpdev_ctl *ctl = nullptr, *ctl_h = nullptr;  // device control block + pinned mirror
   pdlpdev_step_params sp = {0.3, 0.6, 0.5, 0.5};
+  // restarted reflected-Halpern mode (pdlpdev_set_halpern): z^k lives in the iterate buffers, T(z^k) of a run's last step in avgx / avgy
+  // (avgy is also the vector the A^T product gathers), the anchor in lrx / lry / lraty; the mode's scalars in a block of their own
+  bool halpern = false;
+  double* lraty = nullptr;                                  // A^T y of the anchor
+  pdlpdev_halpern *hal = nullptr, *hal_h = nullptr;         // device block + pinned mirror (read back with the control block)
   // multi-GPU
   rccl::comm_t comm = nullptr;  // non-null also marks "sharded mode" when the soft communicator is used
   softcomm::Comm* soft = nullptr;

@@ -230,6 +230,85 @@ k_step_decision_batch(const pdlpdev_decision_args* __restrict__ args)
   step_decision_workgroup(a.ctl, a.part_dy, a.nb_dy, a.part_t, a.nb_t, nullptr, a.sp);
 }
 
+// The decision of a Halpern step (docs/design/04d_halpern_mode.md): nothing to decide -- a step never fails -- but the same one workgroup
+// on the critical path: the partials are added in k_step_decision's order, the fixed-point error of the step is formed in PDHG's metric
+//   r_k^2 = (w / eta) ||dx||^2 + 2 dy.(A dx) + ||dy||^2 / (eta w),   dy.(A dx) = dx.(A^T y' - A^T y^k) = StepEpilogue's first sum,
+// the counters advance and the buffers flip.  A NaN or an overflow raises the step error like an invalid movement does.
+__global__ void __launch_bounds__(kDecisionThreads)
+k_halpern_decision(pdlpdev_ctl* __restrict__ ctl, pdlpdev_halpern* __restrict__ hal, const double* __restrict__ part_dy, int nb_dy,
+                   const double* __restrict__ part_t, int nb_t)
+{
+  __shared__ double red[3 * 16];
+  pdlpdev_ctl lc = *ctl;
+  if (!(lc.error == 0 && lc.steps_taken < lc.target_steps)) return;
+  const int t   = threadIdx.x;
+  double acc[3] = {0.0, 0.0, 0.0};
+#pragma unroll 4
+  for (int i = t; i < nb_dy; i += kDecisionThreads) acc[0] += part_dy[i];
+#pragma unroll 4
+  for (int i = t; i < nb_t; i += kDecisionThreads) {
+    acc[1] += part_t[i];
+    acc[2] += part_t[nb_t + i];
+  }
+  block_sum_fast<3, kDecisionThreads / 64>(acc, red);
+  if (t != 0) return;
+  pdlpdev_halpern lh = *hal;
+  const double dy2 = acc[0], interaction = acc[1], dx2 = acc[2];
+  const double eta = lc.step_size, w = lc.primal_weight;
+  const double r2  = (w / eta) * dx2 + 2.0 * interaction + dy2 / (eta * w);
+  lc.last_interaction = interaction;
+  lc.last_movement    = r2;
+  lc.last_dx2         = dx2;
+  lc.last_dy2         = dy2;
+  lc.attempts += 1;
+  if (!(r2 == r2) || !(r2 < 1.0e100)) {
+    lc.error = 1;
+  } else {
+    const double r = sqrt(dmax(r2, 0.0));
+    lh.r = r, lh.r2 = r2;
+    if (lh.k == 0) lh.r_first = r;
+    lh.r2_min = dmin(lh.r2_min, r2);
+    lh.k += 1;
+    *hal = lh;
+  }
+  lc.k += 1;
+  lc.cur ^= 1;
+  lc.steps_taken += 1;
+  lc.its_since_restart += 1;
+  *ctl = lc;
+}
+__global__ void k_halpern_clear(pdlpdev_halpern* hal)
+{
+  hal->r = hal->r_first = hal->r2 = 0.0;
+  hal->r2_min = __builtin_huge_val();
+  hal->k = 0, hal->reserved = 0;
+}
+// behind k_restart + k_finalize (dist2 = the two squared distances): the smoothed primal weight on the device, the anchor's A^T y, k <- 0
+__global__ void k_halpern_restart_ctl(pdlpdev_ctl* ctl, pdlpdev_halpern* hal, double* dist2, double theta)
+{
+  const double dx = sqrt(dist2[0]), dy = sqrt(dist2[1]);
+  dist2[0] = dx, dist2[1] = dy;
+  if (theta >= 0.0 && dx > 1.0e-10 && dy > 1.0e-10) {
+    const double w     = exp(theta * log(dy / dx) + (1.0 - theta) * log(ctl->primal_weight));
+    ctl->primal_weight = w;
+    ctl->tau           = ctl->step_size / w;
+    ctl->sigma         = ctl->step_size * w;
+  }
+  ctl->its_since_restart = 0;
+  hal->k                 = 0;
+}
+__global__ void __launch_bounds__(kBlock)
+k_copy_current(int n, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ v0, const double* __restrict__ v1, double* __restrict__ out)
+{
+  const double* __restrict__ v = ctl->cur ? v1 : v0;
+  for (int i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) out[i] = v[i];
+}
+// power iteration (pdlpdev_spectral_norm): out = v / d
+__global__ void __launch_bounds__(kBlock) k_div_by_scalar(int n, double* __restrict__ out, const double* __restrict__ v, double d)
+{
+  for (int i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) out[i] = v[i] / d;
+}
+
 // direct peer transport of a sharded solve: wait for every rank's three step-size sums (landed in this rank's block), add them
 // up in rank order -- the same bits on every rank -- and take the decision
 // (one workgroup, so the whole scalar exchange lives in this kernel: its own three sums from the partials of the two SpMV kernels,
@@ -542,6 +621,7 @@ int fetch_scalars(pdlpdev_ctx* ctx, int count)
 int fetch_ctl(pdlpdev_ctx* ctx, pdlpdev_ctl* out)
 {
   HIP_TRY(hipMemcpyAsync(ctx->ctl_h, ctx->ctl, sizeof(pdlpdev_ctl), hipMemcpyDeviceToHost, ctx->stream));
+  if (ctx->halpern) HIP_TRY(hipMemcpyAsync(ctx->hal_h, ctx->hal, sizeof(pdlpdev_halpern), hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
   ctx->ctl_h_current = true;
   if (out) *out = *ctx->ctl_h;
@@ -646,6 +726,10 @@ int pdlpdev_reset(pdlpdev_ctx* ctx, const double* lb, const double* ub, const do
   for (double* v : {ctx->xbar, ctx->sumx, ctx->avgx, ctx->lrx}) HIP_TRY(hipMemsetAsync(v, 0, nb, s));
   for (double* v : {ctx->sumy, ctx->avgy, ctx->lry}) HIP_TRY(hipMemsetAsync(v, 0, mb, s));
   HIP_TRY(hipMemsetAsync(ctx->ctl, 0, sizeof(pdlpdev_ctl), s));
+  if (ctx->halpern) {  // (the mode stays; its anchor and scalars go back to their state after scaling)
+    HIP_TRY(hipMemsetAsync(ctx->lraty, 0, nb, s));
+    k_halpern_clear<<<1, 1, 0, s>>>(ctx->hal);
+  }
   LAUNCH_CHECK();
   return 0;
 }
@@ -812,8 +896,39 @@ void dense_part(pdlpdev_ctx* ctx, int transpose, const double* v0, const double*
   }
 }
 // launch helpers: pick the layout (jagged rows with LDS column sets, slab-major panels, CSR stream)
+static inline HalpernArgs halpern_args(const pdlpdev_ctx* ctx) { return HalpernArgs{ctx->hal, ctx->avgx, ctx->avgy, ctx->lrx, ctx->lry, ctx->lraty}; }
+// the two products of a Halpern step: the twins' launch sites with the Halpern kernels; the A^T product gathers y' from its own buffer
+static void launch_a_halpern(pdlpdev_ctx* ctx)
+{
+  const HalpernArgs h = halpern_args(ctx);
+  dense_part(ctx, 0, ctx->xbar, nullptr, 0, 1);
+  if (ctx->pba.on) {
+    (void)pb_products(ctx, ctx->pba, ctx->xbar, nullptr, 0, 1);
+    (void)pb_rows(ctx, k_pb_a_halpern, ctx->pba, ctx->ctl, ctx->y[0], ctx->y[1], ctx->lo, ctx->hi, h, ctx->part_a);
+  } else if (ctx->ja.on)
+    (void)JAG_LAUNCH(ctx, k_jag_a_halpern, ctx->ja.v, ctx->ctl, ctx->xbar, ctx->y[0], ctx->y[1], ctx->lo, ctx->hi, h, ctx->part_a);
+  else if (ctx->pa.on)
+    launch_k(ctx, ctx->pa.v.seg ? k_panel_a_halpern<true> : k_panel_a_halpern<false>, ctx->pa.v.W, kPanelThreads, 0, ctx->pa.v, ctx->ctl, ctx->xbar, ctx->y[0], ctx->y[1], ctx->lo, ctx->hi, h, ctx->part_a);
+  else
+    launch_k(ctx, k_spmv_a_halpern, stream_grid(ctx->a_nb), kBlock, 0, ctx->a_nb, ctx->a_rb, ctx->ha_off, ctx->ha_idx, ctx->ha_val, ctx->ctl, ctx->xbar, ctx->y[0], ctx->y[1], ctx->lo, ctx->hi, h, ctx->part_a, ctx->dense.add_m);
+}
+static void launch_at_halpern(pdlpdev_ctx* ctx)
+{
+  const HalpernArgs h = halpern_args(ctx);
+  dense_part(ctx, 1, ctx->avgy, nullptr, 0, 1);
+  if (ctx->pbat.on) {
+    (void)pb_products(ctx, ctx->pbat, ctx->avgy, nullptr, 0, 1);
+    (void)pb_rows(ctx, k_pb_at_halpern, ctx->pbat, ctx->ctl, ctx->x[0], ctx->x[1], ctx->aty[0], ctx->aty[1], h, ctx->part_at);
+  } else if (ctx->jat.on)
+    (void)JAG_LAUNCH(ctx, k_jag_at_halpern, ctx->jat.v, ctx->ctl, ctx->x[0], ctx->x[1], ctx->aty[0], ctx->aty[1], h, ctx->part_at);
+  else if (ctx->pat.on)
+    launch_k(ctx, ctx->pat.v.seg ? k_panel_at_halpern<true> : k_panel_at_halpern<false>, ctx->pat.v.W, kPanelThreads, 0, ctx->pat.v, ctx->ctl, ctx->x[0], ctx->x[1], ctx->aty[0], ctx->aty[1], h, ctx->part_at);
+  else
+    launch_k(ctx, k_spmv_at_halpern, stream_grid(ctx->at_nb), kBlock, 0, ctx->at_nb, ctx->at_rb, ctx->hat_off, ctx->hat_idx, ctx->hat_val, ctx->ctl, ctx->x[0], ctx->x[1], ctx->aty[0], ctx->aty[1], h, ctx->part_at, ctx->dense.add_n);
+}
 static void launch_a_dual(pdlpdev_ctx* ctx, double* ycopy = nullptr, const p2pdev::Push* push = nullptr)
 {
+  if (ctx->halpern) return launch_a_halpern(ctx);
   dense_part(ctx, 0, ctx->xbar, nullptr, 0, 1);
   if (ctx->pba.on) {
     (void)pb_products(ctx, ctx->pba, ctx->xbar, nullptr, 0, 1);
@@ -827,6 +942,7 @@ static void launch_a_dual(pdlpdev_ctx* ctx, double* ycopy = nullptr, const p2pde
 }
 static void launch_at_step(pdlpdev_ctx* ctx)
 {
+  if (ctx->halpern) return launch_at_halpern(ctx);
   dense_part(ctx, 1, ctx->y[0], ctx->y[1], 1, 1);
   if (ctx->pbat.on) {
     (void)pb_products(ctx, ctx->pbat, ctx->y[0], ctx->y[1], 1, 1);  // y' = the trial dual
@@ -879,6 +995,7 @@ void launch_plain(pdlpdev_ctx* ctx, int transpose, const double* vec, double* ou
 }
 static void launch_decision(pdlpdev_ctx* ctx)
 {
+  if (ctx->halpern) return launch_k(ctx, k_halpern_decision, 1, kDecisionThreads, 0, ctx->ctl, ctx->hal, ctx->part_a, dual_partials(ctx), ctx->part_at, step_partials(ctx));
   launch_k(ctx, k_step_decision, 1, kDecisionThreads, 0, ctx->ctl, ctx->part_a, dual_partials(ctx), ctx->part_at, step_partials(ctx), nullptr, ctx->sp);
 }
 
@@ -900,6 +1017,9 @@ static void launch_oc_step(pdlpdev_ctx* ctx)
 static int enqueue_attempt(pdlpdev_ctx* ctx)
 {
   const int n = ctx->n;
+  // (a context in Halpern mode is never sharded: the single-GPU sequence at the end of this function, whose three launch helpers pick
+  //  the Halpern kernels -- k_primal is the same, pending_avg stays 0)
+  if (ctx->halpern && ctx->comm) return fail(-7, "reflected Halpern mode: not available behind a communicator");
   if (ctx->owner) {
     if (!ctx->oc_off) return fail(-1, "owner-computes dataflow: pdlpdev_owner_setup was not called");
     const size_t cs = (size_t)ctx->rank * ctx->slice;
@@ -1166,10 +1286,15 @@ int pdlpdev_run_period(pdlpdev_ctx* ctx, int32_t target_steps, const pdlpdev_sma
   roctx::Range range("pdlp: PDHG attempts + major iteration evaluation");
   TRY(set_target(ctx, target_steps));
   const int before = ctx->ctl_h->steps_taken, attempts_before = ctx->ctl_h->attempts, asked = target_steps - before;
-  const int spare = ctx->spare_attempts;
+  const int spare = ctx->halpern ? 0 : ctx->spare_attempts;  // (a Halpern step never fails: a period is exactly `asked` steps)
   TRY(enqueue_attempts(ctx, asked));
   if (spare > 0) TRY(enqueue_attempts(ctx, spare));
-  TRY(enqueue_major_eval(ctx, rq->mode, rq->rule_finite, rq->eps_p, rq->eps_d, 1));
+  if (ctx->halpern) {
+    TRY(enqueue_halpern_eval(ctx, rq->rule_finite, rq->eps_p, rq->eps_d, 1));
+    HIP_TRY(hipMemcpyAsync(ctx->hal_h, ctx->hal, sizeof(pdlpdev_halpern), hipMemcpyDeviceToHost, ctx->stream));
+  } else {
+    TRY(enqueue_major_eval(ctx, rq->mode, rq->rule_finite, rq->eps_p, rq->eps_d, 1));
+  }
   HIP_TRY(hipMemcpyAsync(ctx->scal_h, ctx->scal, kCtlSlot * sizeof(double) + sizeof(pdlpdev_ctl), hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
   ctx->stat_loop_syncs += 1;
@@ -1335,6 +1460,10 @@ static int64_t locate_buffer(pdlpdev_ctx* ctx, int id, double** ptr)
     case PDLPDEV_BUF_LAST_RESTART_Y: src = ctx->lry, count = m; break;
     case PDLPDEV_BUF_ATY_U_CURRENT: src = ctx->aty_u[PDLPDEV_CURRENT], count = n; break;
     case PDLPDEV_BUF_ATY_U_AVERAGE: src = ctx->aty_u[PDLPDEV_AVERAGE], count = n; break;
+    case PDLPDEV_BUF_LAST_RESTART_ATY:
+      if (!ctx->lraty) { fail(-1, "buffer %d exists in Halpern mode only", id); return -1; }
+      src = ctx->lraty, count = n;
+      break;
     default: fail(-1, "unknown buffer %d", id); return -1;
   }
   *ptr = src;
@@ -1389,6 +1518,91 @@ int pdlpdev_set_loop_state(pdlpdev_ctx* ctx, double sum_weights, int32_t its_sin
   return 0;
 }
 
+// ---- restarted reflected-Halpern mode ----------------------------------------------------------------------
+static void drop_graphs(pdlpdev_ctx* ctx)
+{
+  for (auto& kv : ctx->graphs) (void)hipGraphExecDestroy(kv.second);
+  ctx->graphs.clear();
+}
+int pdlpdev_set_halpern(pdlpdev_ctx* ctx, int on)
+{
+  HIP_TRY(hipSetDevice(ctx->device));
+  if ((on != 0) == ctx->halpern) return 0;
+  if (on) {
+    if (ctx->comm) return fail(-7, "reflected Halpern mode: not available for a sharded solver");
+    if (ctx->small_resident) return fail(-7, "reflected Halpern mode: the context is on the resident small-LP path (pdlpdev_create_no_resident before its creation)");
+    if (!ctx->scaled) return fail(-1, "pdlpdev_set_halpern: call after pdlpdev_scale_problem");
+    if (!ctx->lraty) TRY(dev_alloc(ctx, &ctx->lraty, (size_t)ctx->n));
+    if (!ctx->hal) TRY(dev_alloc(ctx, &ctx->hal, 1));
+    if (!ctx->hal_h) HIP_TRY(hipHostMalloc((void**)&ctx->hal_h, sizeof(pdlpdev_halpern)));
+    k_halpern_clear<<<1, 1, 0, ctx->stream>>>(ctx->hal);
+    LAUNCH_CHECK();
+    *ctx->hal_h        = pdlpdev_halpern{};
+    ctx->hal_h->r2_min = HUGE_VAL;
+  }
+  ctx->halpern = on != 0;
+  loop_state_touched(ctx);
+  drop_graphs(ctx);  // (the attempt graphs hold the other mode's kernels)
+  return 0;
+}
+int pdlpdev_get_halpern(pdlpdev_ctx* ctx, pdlpdev_halpern* out)
+{
+  if (!ctx->halpern) return fail(-1, "pdlpdev_get_halpern: the context is not in Halpern mode");
+  *out = *ctx->hal_h;
+  return 0;
+}
+int pdlpdev_spectral_norm(pdlpdev_ctx* ctx, double rel_tol, int32_t max_products, double* sigma_max, int32_t* products)
+{
+  HIP_TRY(hipSetDevice(ctx->device));
+  if (ctx->comm) return fail(-7, "pdlpdev_spectral_norm: single GPU only");
+  if (ctx->small_resident) return fail(-7, "pdlpdev_spectral_norm: not on the resident small-LP path");
+  hipStream_t s = ctx->stream;
+  const int n   = ctx->n;
+  double* v = ctx->tmp_n;  // the normalised iterate; A v -> tmp_m; A^T A v -> xbar
+  k_fill<<<grid_for(n), kBlock, 0, s>>>(n, v, 1.0 / sqrt((double)n));
+  double est = 0.0;
+  int done   = 0;
+  while (done < max_products) {
+    launch_plain(ctx, 0, v, ctx->tmp_m);
+    launch_plain(ctx, 1, ctx->tmp_m, ctx->xbar);
+    TRY(reduce_vec(ctx, 1, n, ctx->xbar, nullptr, 0));
+    TRY(fetch_scalars(ctx, 1));
+    done += 1;
+    const double s2 = sqrt(ctx->scal_h[0]);  // ||A^T A v||, v of unit length: the estimate of sigma_max^2 (from below)
+    if (!(s2 > 0.0)) {
+      est = 0.0;
+      break;
+    }
+    k_div_by_scalar<<<grid_for(n), kBlock, 0, s>>>(n, v, ctx->xbar, s2);  // v <- A^T A v / s2
+    LAUNCH_CHECK();
+    const bool settled = fabs(s2 - est) <= rel_tol * s2;
+    est                = s2;
+    if (settled) break;
+  }
+  HIP_TRY(hipMemsetAsync(ctx->xbar, 0, (size_t)n * sizeof(double), s));
+  if (sigma_max) *sigma_max = sqrt(est);
+  if (products) *products = done;
+  return 0;
+}
+int pdlpdev_halpern_restart(pdlpdev_ctx* ctx, double theta, double dist[2], pdlpdev_ctl* ctl)
+{
+  HIP_TRY(hipSetDevice(ctx->device));
+  if (!ctx->halpern) return fail(-1, "pdlpdev_halpern_restart: the context is not in Halpern mode");
+  hipStream_t s = ctx->stream;
+  const int g   = std::min(grid_for(std::max(ctx->n, ctx->m)), kGenericBlocks);
+  // distances to the anchor and anchor <- iterate: the KKT restart's kernel with the current iterate as the candidate
+  launch_restart_current(ctx, g);
+  k_finalize<<<1, kBlock, 0, s>>>(ctx->part_g, g, 2, 0u, ctx->scal);
+  k_copy_current<<<grid_for(ctx->n), kBlock, 0, s>>>(ctx->n, ctx->ctl, ctx->aty[0], ctx->aty[1], ctx->lraty);
+  k_halpern_restart_ctl<<<1, 1, 0, s>>>(ctx->ctl, ctx->hal, ctx->scal, theta);
+  LAUNCH_CHECK();
+  HIP_TRY(hipMemcpyAsync(ctx->scal_h, ctx->scal, 2 * sizeof(double), hipMemcpyDeviceToHost, s));
+  TRY(fetch_ctl(ctx, ctl));  // (the weight changed on the device; aty[cur] is untouched, so aty_valid keeps its value)
+  ctx->stat_loop_syncs += 1;
+  if (dist) dist[0] = ctx->scal_h[0], dist[1] = ctx->scal_h[1];
+  return 0;
+}
+
 // ---- measurement / parity hooks ------------------------------------------------------------------------
 int pdlpdev_spmv(pdlpdev_ctx* ctx, int transpose, const double* x, double* y)
 {
@@ -1415,14 +1629,19 @@ int pdlpdev_time_kernel(pdlpdev_ctx* ctx, int kernel_id, int reps, double* avg_m
   loop_state_touched(ctx);  // (forced attempts run on the solver's own buffers)
   pdlpdev_ctl saved = *ctx->ctl_h;
   pdlpdev_ctl forced = saved;
-  forced.pending_avg  = 1;                       // time the kernels WITH their averaging traffic
-  forced.target_steps = saved.steps_taken + 1;   // and not as no-ops
-  forced.error        = 0;
+  forced.pending_avg  = ctx->halpern ? 0 : 1;    // time the kernels WITH their averaging traffic (Halpern mode has none)
+  forced.target_steps = saved.steps_taken + (ctx->halpern ? 2 : 1);  // and not as no-ops (Halpern: nor as the last step of a run, the
+  forced.error        = 0;                                            //  only one that stores x')
+  const pdlpdev_halpern saved_hal = ctx->halpern ? *ctx->hal_h : pdlpdev_halpern{};
+  // (Halpern mode: no sums are touched; what the forced steps overwrite is T(z^k) in the average slots -- y' on every step, x' on none
+  //  of them, both saved so that an evaluation behind the hook still sees the point of the last real step)
+  double* const keep_n = ctx->halpern ? ctx->avgx : ctx->sumx;
+  double* const keep_m = ctx->halpern ? ctx->avgy : ctx->sumy;
   double *sx = nullptr, *sy = nullptr;
   HIP_TRY(hipMalloc((void**)&sx, std::max<size_t>(ctx->n, 1) * sizeof(double)));
   HIP_TRY(hipMalloc((void**)&sy, std::max<size_t>(ctx->m, 1) * sizeof(double)));
-  HIP_TRY(hipMemcpyAsync(sx, ctx->sumx, (size_t)ctx->n * sizeof(double), hipMemcpyDeviceToDevice, s));
-  HIP_TRY(hipMemcpyAsync(sy, ctx->sumy, (size_t)ctx->m * sizeof(double), hipMemcpyDeviceToDevice, s));
+  HIP_TRY(hipMemcpyAsync(sx, keep_n, (size_t)ctx->n * sizeof(double), hipMemcpyDeviceToDevice, s));
+  HIP_TRY(hipMemcpyAsync(sy, keep_m, (size_t)ctx->m * sizeof(double), hipMemcpyDeviceToDevice, s));
   HIP_TRY(hipMemcpyAsync(ctx->ctl, &forced, sizeof(forced), hipMemcpyHostToDevice, s));
   HIP_TRY(hipStreamSynchronize(s));
   for (hipEvent_t& e : ctx->prof_ev) HIP_TRY(hipEventCreate(&e));
@@ -1482,9 +1701,10 @@ int pdlpdev_time_kernel(pdlpdev_ctx* ctx, int kernel_id, int reps, double* avg_m
   }
   if (avg_ms) *avg_ms = (double)ms / reps;
   // restore
-  HIP_TRY(hipMemcpyAsync(ctx->sumx, sx, (size_t)ctx->n * sizeof(double), hipMemcpyDeviceToDevice, s));
-  HIP_TRY(hipMemcpyAsync(ctx->sumy, sy, (size_t)ctx->m * sizeof(double), hipMemcpyDeviceToDevice, s));
+  HIP_TRY(hipMemcpyAsync(keep_n, sx, (size_t)ctx->n * sizeof(double), hipMemcpyDeviceToDevice, s));
+  HIP_TRY(hipMemcpyAsync(keep_m, sy, (size_t)ctx->m * sizeof(double), hipMemcpyDeviceToDevice, s));
   HIP_TRY(hipMemcpyAsync(ctx->ctl, &saved, sizeof(saved), hipMemcpyHostToDevice, s));
+  if (ctx->halpern) HIP_TRY(hipMemcpyAsync(ctx->hal, &saved_hal, sizeof(saved_hal), hipMemcpyHostToDevice, s));
   HIP_TRY(hipStreamSynchronize(s));
   for (hipEvent_t& e : ctx->prof_ev) (void)hipEventDestroy(e), e = nullptr;
   (void)hipFree(sx), (void)hipFree(sy);

@@ -133,6 +133,83 @@ struct StepEpilogue {
   __device__ __forceinline__ void row(int j, double v, double (&acc)[2]) { apply(j, v, load(j), acc); }
 };
 
+// ---- restarted reflected-Halpern mode (docs/design/04d_halpern_mode.md): the same two products, the epilogues carry the combination
+//      z^{k+1} = w (2 T(z^k) - z^k) + (1 - w) z^0.  Every added access is one coalesced 8-byte stream per row next to the ones
+//      above (no LDS, nothing gathered).
+struct HalpernWeights {
+  double w, w0;  // w_k = (k + 1) / (k + 2) and 1 - w_k
+  __device__ __forceinline__ explicit HalpernWeights(const pdlpdev_halpern* hal)
+  {
+    const double k = (double)hal->k;
+    w              = (k + 1.0) / (k + 2.0);
+    w0             = 1.0 - w;
+  }
+  __device__ __forceinline__ double combine(double t, double z, double z0) const { return w * (2.0 * t - z) + w0 * z0; }
+};
+// (2h) rows of A: y' as in DualEpilogue -> yp (the vector the A^T product gathers, and the dual half of T(z^k)), ||dy||^2 partial,
+//      y^{k+1} -> yn
+struct HalpernDualEpilogue {
+  static constexpr int NQ = 1;
+  using Op = SumOp;
+  const double* __restrict__ y;
+  double* __restrict__ yn;
+  double* __restrict__ yp;
+  const double* __restrict__ y0;
+  const double* __restrict__ lo;
+  const double* __restrict__ hi;
+  double sigma;
+  HalpernWeights hw;
+  __device__ __forceinline__ void row(int i, double v, double (&acc)[1])
+  {
+    const double yi  = y[i];
+    double next      = yi - (sigma * v);
+    const double low = next + sigma * lo[i];
+    const double up  = next + sigma * hi[i];
+    next             = dmax(low, dmin(up, 0.0));
+    yp[i]            = next;
+    const double dy  = next - yi;
+    acc[0] += dy * dy;
+    yn[i] = hw.combine(next, yi, y0[i]);
+  }
+};
+// (3h) rows of A^T: v = A^T y' with StepEpilogue's two sums (dx . (A^T y' - A^T y^k) = dy . A dx, ||dx||^2), then x^{k+1} over x'
+//      (read and written by the same lane) and A^T y^{k+1} by the same linear combination; xp (null except on the last step of a
+//      run): x', the primal half of T(z^k), survives there
+struct HalpernStepEpilogue {
+  static constexpr int NQ = 2;
+  using Op = SumOp;
+  const double* __restrict__ x;
+  double* __restrict__ xn;
+  const double* __restrict__ aty;
+  double* __restrict__ atyn;
+  const double* __restrict__ x0;
+  const double* __restrict__ aty0;
+  double* __restrict__ xp;
+  HalpernWeights hw;
+  __device__ __forceinline__ void row(int j, double v, double (&acc)[2])
+  {
+    const double xj = x[j], xt = xn[j], a = aty[j];
+    const double dx = xt - xj;
+    const double t  = v - a;
+    acc[0] += t * dx;
+    acc[1] += dx * dx;
+    if (xp) xp[j] = xt;
+    xn[j]   = hw.combine(xt, xj, x0[j]);
+    atyn[j] = hw.combine(v, a, aty0[j]);
+  }
+};
+// what the kernels of a Halpern step take besides their twins' arguments (by value: a handful of pointers)
+struct HalpernArgs {
+  const pdlpdev_halpern* __restrict__ hal;
+  double* __restrict__ tx;          // T(z^k), primal half (the AVERAGE slot)
+  double* __restrict__ ty;          // T(z^k), dual half: what the A^T product gathers
+  const double* __restrict__ x0;    // the anchor
+  const double* __restrict__ y0;
+  const double* __restrict__ aty0;
+};
+// x' is kept on the last step of a run only (the evaluation behind it reads it; every other step would store 8 n bytes for nobody)
+__device__ __forceinline__ bool halpern_last_step(const pdlpdev_ctl* ctl) { return ctl->steps_taken + 1 >= ctl->target_steps; }
+
 // (plain SpMV: A^T y at start / after restart-to-average; parity hook; multi-GPU partial products)
 struct StoreEpilogue {
   static constexpr int NQ = 0;

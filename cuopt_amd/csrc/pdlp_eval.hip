@@ -441,6 +441,15 @@ int pdlpdev_major_eval(pdlpdev_ctx* ctx, int average_mode, int rc_rule_finite_bo
   roctx::Range range("pdlp: major iteration evaluation (averages + convergence information)");
   HIP_TRY(hipSetDevice(ctx->device));
   const bool want_linf = eps_rel_primal >= 0.0 && eps_rel_dual >= 0.0;
+  if (ctx->halpern) {
+    // one point to evaluate: T(z^k) of the last step, which the step kernels left in the average slots (no sums, no average to form)
+    TRY(enqueue_halpern_eval(ctx, rc_rule_finite_bounds, eps_rel_primal, eps_rel_dual, 0));
+    TRY(fetch_scalars(ctx, 41));
+    ctx->stat_loop_syncs += 1;
+    read_eval(ctx->scal_h + 32, want_linf, out_average);
+    read_eval(ctx->scal_h + 32, want_linf, out_current);
+    return 0;
+  }
   if (ctx->small_resident && !ctx->comm) {
     TRY(resident_major_eval(ctx, average_mode, rc_rule_finite_bounds, want_linf ? 1 : 0, eps_rel_primal, eps_rel_dual));
   } else {
@@ -466,9 +475,13 @@ int enqueue_major_eval(pdlpdev_ctx* ctx, int average_mode, int rc_rule_finite_bo
   TRY(enqueue_eval(ctx, PDLPDEV_AVERAGE, rc_rule_finite_bounds, eps_rel_primal, eps_rel_dual, ctx->scal + 32, guard, guard ? ctx->scal + kCtlSlot : nullptr));
   return 0;
 }
+int enqueue_halpern_eval(pdlpdev_ctx* ctx, int rc_rule_finite_bounds, double eps_rel_primal, double eps_rel_dual, int guard)
+{
+  return enqueue_eval(ctx, PDLPDEV_AVERAGE, rc_rule_finite_bounds, eps_rel_primal, eps_rel_dual, ctx->scal + 32, guard, guard ? ctx->scal + kCtlSlot : nullptr);
+}
 void read_major_eval(pdlpdev_ctx* ctx, double* out_current, double* out_average)
 {
-  read_eval(ctx->scal_h, false, out_current);
+  read_eval(ctx->halpern ? ctx->scal_h + 32 : ctx->scal_h, false, out_current);
   read_eval(ctx->scal_h + 32, false, out_average);
 }
 
@@ -599,6 +612,11 @@ int pdlpdev_trust_region_bounds(pdlpdev_ctx* ctx, int which, double wp, double w
   return 0;
 }
 
+// k_restart with the current iterate as the candidate, scaled distances (pdlpdev_halpern_restart): partials in part_g
+void launch_restart_current(pdlpdev_ctx* ctx, int g)
+{
+  k_restart<<<g, kBlock, 0, ctx->stream>>>(ctx->n, ctx->m, PDLPDEV_CURRENT, 0, ctx->dc, ctx->dr, ctx->ctl, ctx->x[0], ctx->x[1], ctx->y[0], ctx->y[1], ctx->avgx, ctx->avgy, ctx->lrx, ctx->lry, ctx->sumx, ctx->sumy, ctx->part_g);
+}
 int pdlpdev_restart(pdlpdev_ctx* ctx, int which, int unscaled_distances, double dist2[2])
 {
   HIP_TRY(hipSetDevice(ctx->device));

@@ -283,3 +283,71 @@ k_dense_rows_finish(DenseView D, int nrows, const pdlpdev_ctl* __restrict__ ctl,
 __global__ void __launch_bounds__(kBlock)
 k_dense_cols(DenseView D, int n, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ v0, const double* __restrict__ v1, int mode,
              int in_loop, double* __restrict__ add);
+
+// ---- restarted reflected-Halpern mode: the twins of k_*_a_dual / k_*_at_step with the Halpern epilogues (pdlp_epilogues.hpp) ----
+__global__ void __launch_bounds__(kBlock)
+k_spmv_a_halpern(int nb, const int32_t* __restrict__ rb, const int32_t* __restrict__ off,
+                 const int32_t* __restrict__ idx, const double* __restrict__ val,
+                 const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ xbar,
+                 double* __restrict__ y0, double* __restrict__ y1, const double* __restrict__ lo,
+                 const double* __restrict__ hi, HalpernArgs h, double* __restrict__ part, const double* __restrict__ dadd);
+__global__ void __launch_bounds__(kBlock)
+k_spmv_at_halpern(int nb, const int32_t* __restrict__ rb, const int32_t* __restrict__ off,
+                  const int32_t* __restrict__ idx, const double* __restrict__ val,
+                  const pdlpdev_ctl* __restrict__ ctl, double* __restrict__ x0, double* __restrict__ x1,
+                  double* __restrict__ aty0, double* __restrict__ aty1, HalpernArgs h,
+                  double* __restrict__ part, const double* __restrict__ dadd);
+template <bool SEG>
+__global__ void __launch_bounds__(kPanelThreads)
+k_panel_a_halpern(PanelView P, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ xbar,
+                  double* __restrict__ y0, double* __restrict__ y1, const double* __restrict__ lo,
+                  const double* __restrict__ hi, HalpernArgs h, double* __restrict__ part);
+extern template __global__ void k_panel_a_halpern<true>(PanelView P, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ xbar,
+                  double* __restrict__ y0, double* __restrict__ y1, const double* __restrict__ lo,
+                  const double* __restrict__ hi, HalpernArgs h, double* __restrict__ part);
+extern template __global__ void k_panel_a_halpern<false>(PanelView P, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ xbar,
+                  double* __restrict__ y0, double* __restrict__ y1, const double* __restrict__ lo,
+                  const double* __restrict__ hi, HalpernArgs h, double* __restrict__ part);
+template <bool SEG>
+__global__ void __launch_bounds__(kPanelThreads)
+k_panel_at_halpern(PanelView P, const pdlpdev_ctl* __restrict__ ctl, double* __restrict__ x0, double* __restrict__ x1,
+                   double* __restrict__ aty0, double* __restrict__ aty1, HalpernArgs h, double* __restrict__ part);
+extern template __global__ void k_panel_at_halpern<true>(PanelView P, const pdlpdev_ctl* __restrict__ ctl, double* __restrict__ x0, double* __restrict__ x1,
+                   double* __restrict__ aty0, double* __restrict__ aty1, HalpernArgs h, double* __restrict__ part);
+extern template __global__ void k_panel_at_halpern<false>(PanelView P, const pdlpdev_ctl* __restrict__ ctl, double* __restrict__ x0, double* __restrict__ x1,
+                   double* __restrict__ aty0, double* __restrict__ aty1, HalpernArgs h, double* __restrict__ part);
+template <int WAVES>
+__global__ void __launch_bounds__(WAVES * 64)
+k_jag_a_halpern(JagView J, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ xbar,
+                double* __restrict__ y0, double* __restrict__ y1, const double* __restrict__ lo,
+                const double* __restrict__ hi, HalpernArgs h, double* __restrict__ part);
+extern template __global__ void k_jag_a_halpern<8>(JagView J, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ xbar,
+                double* __restrict__ y0, double* __restrict__ y1, const double* __restrict__ lo,
+                const double* __restrict__ hi, HalpernArgs h, double* __restrict__ part);
+extern template __global__ void k_jag_a_halpern<16>(JagView J, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ xbar,
+                double* __restrict__ y0, double* __restrict__ y1, const double* __restrict__ lo,
+                const double* __restrict__ hi, HalpernArgs h, double* __restrict__ part);
+template <int WAVES>
+__global__ void __launch_bounds__(WAVES * 64)
+k_jag_at_halpern(JagView J, const pdlpdev_ctl* __restrict__ ctl, double* __restrict__ x0, double* __restrict__ x1,
+                 double* __restrict__ aty0, double* __restrict__ aty1, HalpernArgs h, double* __restrict__ part);
+extern template __global__ void k_jag_at_halpern<8>(JagView J, const pdlpdev_ctl* __restrict__ ctl, double* __restrict__ x0, double* __restrict__ x1,
+                 double* __restrict__ aty0, double* __restrict__ aty1, HalpernArgs h, double* __restrict__ part);
+extern template __global__ void k_jag_at_halpern<16>(JagView J, const pdlpdev_ctl* __restrict__ ctl, double* __restrict__ x0, double* __restrict__ x1,
+                 double* __restrict__ aty0, double* __restrict__ aty1, HalpernArgs h, double* __restrict__ part);
+template <bool WIDE>
+__global__ void __launch_bounds__(WIDE ? kPbwThreads : kPbThreads)
+k_pb_a_halpern(PbView V, const pdlpdev_ctl* __restrict__ ctl, double* __restrict__ y0, double* __restrict__ y1, const double* __restrict__ lo,
+               const double* __restrict__ hi, HalpernArgs h, double* __restrict__ part);
+extern template __global__ void k_pb_a_halpern<false>(PbView V, const pdlpdev_ctl* __restrict__ ctl, double* __restrict__ y0, double* __restrict__ y1, const double* __restrict__ lo,
+               const double* __restrict__ hi, HalpernArgs h, double* __restrict__ part);
+extern template __global__ void k_pb_a_halpern<true>(PbView V, const pdlpdev_ctl* __restrict__ ctl, double* __restrict__ y0, double* __restrict__ y1, const double* __restrict__ lo,
+               const double* __restrict__ hi, HalpernArgs h, double* __restrict__ part);
+template <bool WIDE>
+__global__ void __launch_bounds__(WIDE ? kPbwThreads : kPbThreads)
+k_pb_at_halpern(PbView V, const pdlpdev_ctl* __restrict__ ctl, double* __restrict__ x0, double* __restrict__ x1,
+                double* __restrict__ aty0, double* __restrict__ aty1, HalpernArgs h, double* __restrict__ part);
+extern template __global__ void k_pb_at_halpern<false>(PbView V, const pdlpdev_ctl* __restrict__ ctl, double* __restrict__ x0, double* __restrict__ x1,
+                double* __restrict__ aty0, double* __restrict__ aty1, HalpernArgs h, double* __restrict__ part);
+extern template __global__ void k_pb_at_halpern<true>(PbView V, const pdlpdev_ctl* __restrict__ ctl, double* __restrict__ x0, double* __restrict__ x1,
+                double* __restrict__ aty0, double* __restrict__ aty1, HalpernArgs h, double* __restrict__ part);

@@ -100,6 +100,12 @@ struct cuoptamd_solver {
   double fused_ev[PDLPDEV_EV_COUNT] = {}, fused_ev_avg[PDLPDEV_EV_COUNT] = {};
   bool step_error = false, need_aty = true, last_restart_was_average = false;
   double last_candidate_kkt = 0.0, last_restart_kkt = 0.0;
+  // reflected Halpern mode (H.algorithm == 1): the fixed-point error at the previous restart check since the last restart (< 0: none),
+  // the device's Halpern scalars as the last attempts left them, and what the power iteration found
+  double halpern_r_prev = -1.0;
+  pdlpdev_halpern hal{};
+  double sigma_max = 0.0;
+  int32_t power_products = 0;
   // the reference leaves gap_reduction_ratio_last_trial_ uninitialised (pdlp_restart_strategy.cu:160);
   // 1.0 is the published algorithm's start value (same choice as the oracle)
   double gap_reduction_ratio_last_trial = 1.0;
@@ -179,6 +185,10 @@ void preset_stable2(cuoptamd_hyper& h)
   h.update_step_size_on_initial_solution                       = 0;
   h.handle_some_primal_gradients_on_finite_bounds_as_residuals = 0;
   h.project_initial_primal                                     = 1;
+  h.algorithm                                                  = 0;
+  h.halpern_power_max_products                                 = 5000;
+  h.halpern_step_safety                                        = 0.998;
+  h.halpern_power_tolerance                                    = 1e-6;
 }
 
 Convergence to_convergence(const cuoptamd_solver* s, const double* ev)
@@ -409,6 +419,55 @@ double major_restart_done(cuoptamd_solver* s, const MajorPlan& plan, const doubl
   return nw;
 }
 
+// ---- pieces of a major iteration's termination logic shared by the averaging modes (major_head) and the Halpern mode ----------------
+// settings.accept_tolerance: iterate `which` met the looser set first -- snapshot it (the best buffers) with its statistics
+int keep_accepted_point(cuoptamd_solver* s, int which)
+{
+  DEV(pdlpdev_save_best(s->dev, which));
+  fill_result(s, kOptimal, which);
+  if (s->H.algorithm == 1) s->result.returned_average = 0;  // (the Halpern mode's "average" slots hold T(z^k): no average)
+  s->accepted_result = s->result;
+  s->have_accepted   = true;
+  return 0;
+}
+// check_limits, pdlp.cu:264-331 (time first, then iterations): *done / *status when one is reached
+int check_limits(cuoptamd_solver* s, bool* done, int* status)
+{
+  const double tl = s->S.time_limit;
+  double elapsed  = std::isfinite(tl) ? seconds_since(s->solve_start) : 0.0;
+  if (std::isfinite(tl) && s->world > 1) DEV(pdlpdev_agree_max(s->dev, &elapsed));  // every rank must stop together
+  if (std::isfinite(tl) && elapsed * 1000.0 >= tl * 1000.0)
+    *done = true, *status = kTimeLimit;
+  else if (s->total_iterations - s->iteration_offset >= s->S.iteration_limit)  // internal_solver_iterations_
+    *done = true, *status = kIterationLimit;
+  return 0;
+}
+// the solve ends with `status` at iterate `which` -- or, where a limit ends it, at the stored best / accepted point if there is one
+void finish_solve(cuoptamd_solver* s, int status, int which)
+{
+  if ((status == kTimeLimit || status == kIterationLimit) && s->S.save_best_primal_so_far && s->have_best) {
+    const int nr = s->result.num_restarts, nm = s->result.num_major_iterations;
+    s->result                      = s->best_result;  // the stored point and its statistics
+    s->result.status               = status;
+    s->result.num_restarts         = nr;
+    s->result.num_major_iterations = nm;
+    s->returned_which              = PDLPDEV_BEST;
+  } else if ((status == kTimeLimit || status == kIterationLimit) && s->have_accepted) {
+    const int nr = s->result.num_restarts, nm = s->result.num_major_iterations;
+    const int steps = s->ctl.steps_taken, attempts = s->ctl.attempts;
+    s->result                      = s->accepted_result;  // Optimal at the tolerances the caller asked for
+    s->result.num_restarts         = nr;
+    s->result.num_major_iterations = nm;
+    s->result.steps_taken          = steps;  // the work that was done, not the moment of acceptance
+    s->result.attempted_steps      = attempts;
+    s->result.accepted_at_looser_tolerances = 1;
+    s->returned_which              = PDLPDEV_BEST;
+  } else {
+    fill_result(s, status, which);
+    if (s->H.algorithm == 1) s->result.returned_average = 0;
+  }
+}
+
 int major_head(cuoptamd_solver* s, const double* ev, const double* ev_avg, bool* terminated, MajorPlan* plan)
 {
   const cuoptamd_hyper& H = s->H;
@@ -483,43 +542,17 @@ int major_head(cuoptamd_solver* s, const double* ev, const double* ev_avg, bool*
     if (ac || aa) {
       const int aw = (ac && aa) ? (kkt_score(s->conv_current, w) < kkt_score(s->conv_average, w) ? PDLPDEV_CURRENT : PDLPDEV_AVERAGE)
                                 : (aa ? PDLPDEV_AVERAGE : PDLPDEV_CURRENT);
-      DEV(pdlpdev_save_best(dev, aw));
-      fill_result(s, kOptimal, aw);
-      s->accepted_result = s->result;
-      s->have_accepted   = true;
+      { int rc = keep_accepted_point(s, aw); if (rc) return rc; }
     }
   }
   if (s->total_iterations % 1000 == 0) log_iteration(s, s->conv_current);  // pdlp.cu:798
-  if (!done) {  // check_limits, pdlp.cu:264-331 (time first, then iterations)
-    const double tl = s->S.time_limit;
-    double elapsed  = std::isfinite(tl) ? seconds_since(s->solve_start) : 0.0;
-    if (std::isfinite(tl) && s->world > 1) DEV(pdlpdev_agree_max(dev, &elapsed));  // every rank must stop together
-    if (std::isfinite(tl) && elapsed * 1000.0 >= tl * 1000.0)
-      done = true, status = kTimeLimit, which = PDLPDEV_CURRENT;
-    else if (s->total_iterations - s->iteration_offset >= s->S.iteration_limit)  // internal_solver_iterations_
-      done = true, status = kIterationLimit, which = PDLPDEV_CURRENT;
+  if (!done) {
+    int rc = check_limits(s, &done, &status);
+    if (rc) return rc;
+    if (done) which = PDLPDEV_CURRENT;
   }
   if (done) {
-    if ((status == kTimeLimit || status == kIterationLimit) && s->S.save_best_primal_so_far && s->have_best) {
-      const int nr = s->result.num_restarts, nm = s->result.num_major_iterations;
-      s->result                      = s->best_result;  // the stored point and its statistics
-      s->result.status               = status;
-      s->result.num_restarts         = nr;
-      s->result.num_major_iterations = nm;
-      s->returned_which              = PDLPDEV_BEST;
-    } else if ((status == kTimeLimit || status == kIterationLimit) && s->have_accepted) {
-      const int nr = s->result.num_restarts, nm = s->result.num_major_iterations;
-      const int steps = s->ctl.steps_taken, attempts = s->ctl.attempts;
-      s->result                      = s->accepted_result;  // Optimal at the tolerances the caller asked for
-      s->result.num_restarts         = nr;
-      s->result.num_major_iterations = nm;
-      s->result.steps_taken          = steps;  // the work that was done, not the moment of acceptance
-      s->result.attempted_steps      = attempts;
-      s->result.accepted_at_looser_tolerances = 1;
-      s->returned_which              = PDLPDEV_BEST;
-    } else {
-      fill_result(s, status, which);
-    }
+    finish_solve(s, status, which);
     *terminated = true;
     return 0;
   }
@@ -604,6 +637,94 @@ int major_head(cuoptamd_solver* s, const double* ev, const double* ev_avg, bool*
   return 0;
 }
 
+// ---- the major iteration of the reflected Halpern mode (docs/design/04d_halpern_mode.md) ------------------------------------------
+// One point is evaluated: T(z^k) of the period's last step (the plain PDHG output, which the step kernels left in the device's average
+// slots), with the termination rule of the averaging modes.  Then the restart tests on the fixed-point error r of that step against
+// r_first, the error of the first step after the last restart:
+//   r <= sufficient * r_first,  or  r <= necessary * r_first and r > r at the previous check,  or  k >= artificial * total steps.
+// A restart moves the anchor to z^k and smooths the primal weight towards ||y^k - y^0|| / ||x^k - x^0|| (on the device).
+bool halpern_mode(const cuoptamd_solver* s) { return s->H.algorithm == 1; }
+const char kHalpernName[] = "reflected Halpern mode (algorithm = 1, solver mode 4)";
+
+// settings and hyper-parameters of the averaging iteration that would be silently ignored (or would silently move the constant step)
+const char* halpern_meaningless_setting(const cuoptamd_hyper* h, const cuoptamd_settings* st)
+{
+  if (st->initial_k >= 0) return "initial_k";
+  if (st->strict_infeasibility) return "strict_infeasibility";
+  if (st->unbounded_from_feasible_iterates) return "unbounded_from_feasible_iterates";
+  if (h && h->update_step_size_on_initial_solution) return "update_step_size_on_initial_solution";
+  if (h && h->update_primal_weight_on_initial_solution) return "update_primal_weight_on_initial_solution";
+  return nullptr;
+}
+const char* halpern_refused_setting(const cuoptamd_settings* st)
+{
+  if (st->detect_infeasibility) return "detect_infeasibility";
+  if (st->save_best_primal_so_far) return "save_best_primal_so_far";
+  if (st->first_primal_feasible) return "first_primal_feasible";
+  return halpern_meaningless_setting(nullptr, st);
+}
+
+int halpern_major_iteration(cuoptamd_solver* s, bool* terminated)
+{
+  HostRange range("pdlp: major iteration (Halpern: termination + restart logic)");
+  pdlpdev_ctx* dev        = s->dev;
+  const cuoptamd_hyper& H = s->H;
+  *terminated             = false;
+  const pdlpdev_small_eval rq = major_eval_request(s);
+  double ev[PDLPDEV_EV_COUNT], ev_t[PDLPDEV_EV_COUNT];
+  const pdlpdev_small_eval& fq = s->fused_rq;
+  if (s->fused_eval_ready && fq.rule_finite == rq.rule_finite && fq.eps_p == rq.eps_p && fq.eps_d == rq.eps_d) {
+    std::copy(s->fused_ev_avg, s->fused_ev_avg + PDLPDEV_EV_COUNT, ev_t);
+  } else {
+    DEV(pdlpdev_major_eval(dev, 0, rq.rule_finite, rq.eps_p, rq.eps_d, ev, ev_t));
+  }
+  s->fused_eval_ready = false;
+  s->result.num_major_iterations += 1;
+  s->conv_average = to_convergence(s, ev_t);
+  s->conv_current = s->conv_average;
+  const int t     = verdict(s, s->conv_average);
+  bool done = false;
+  int status = kNumericalError;
+  if (s->total_iterations > 1) {
+    if (t == kOptimal) done = true, status = kOptimal;
+    if (!done && s->step_error) {
+      fill_result(s, kNumericalError, PDLPDEV_AVERAGE);
+      s->result.returned_average = 0;
+      *terminated                = true;
+      return 0;
+    }
+  }
+  if (!done && s->S.accept_enabled && !s->have_accepted && s->total_iterations > 1 && accepted_by_looser(s, s->conv_average)) {
+    int rc = keep_accepted_point(s, PDLPDEV_AVERAGE);
+    if (rc) return rc;
+  }
+  if (s->total_iterations % 1000 == 0) log_iteration(s, s->conv_average);
+  if (!done) {
+    int rc = check_limits(s, &done, &status);
+    if (rc) return rc;
+  }
+  if (done) {
+    finish_solve(s, status, PDLPDEV_AVERAGE);  // (the device's average slots hold T(z^k): the point returned, and no average)
+    *terminated = true;
+    return 0;
+  }
+  // ---- restart tests ----
+  const double r = s->hal.r, r_first = s->hal.r_first;
+  bool restart = false;
+  if (r <= H.sufficient_reduction_for_restart * r_first) restart = true;
+  else if (r <= H.necessary_reduction_for_restart * r_first && s->halpern_r_prev >= 0.0 && r > s->halpern_r_prev) restart = true;
+  else if ((double)s->hal.k >= H.artificial_restart_threshold * (double)s->total_iterations) restart = true;
+  s->halpern_r_prev = r;
+  if (restart) {
+    double dist[2];
+    DEV(pdlpdev_halpern_restart(dev, H.primal_weight_update_smoothing, dist, &s->ctl));
+    DEV(pdlpdev_get_halpern(dev, &s->hal));
+    s->result.num_restarts += 1;
+    s->halpern_r_prev = -1.0;
+  }
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -666,6 +787,10 @@ void cuoptamd_hyper_preset(int mode, cuoptamd_hyper* h)
     h->artificial_restart_in_main_loop                            = 1;
     h->handle_some_primal_gradients_on_finite_bounds_as_residuals = 1;
     h->project_initial_primal                                     = 0;
+  } else if (mode == 4) {  // Halpern1 (not a reference preset): Stable2's scaling, initial weight and period; no early major iterations
+    h->algorithm                      = 1;
+    h->min_iteration_restart          = 0;
+    h->primal_weight_update_smoothing = 0.99;
   }
 }
 
@@ -852,6 +977,7 @@ static int start_run(cuoptamd_solver* s, const double* init_x, const double* ini
   // set_relative_{primal,dual}_tolerance_factor (pdlp.cu:209-231): the caller's ||b|| / ||c|| for the termination rule
   if (settings->relative_primal_tolerance_factor >= 0.0) s->norm_b = settings->relative_primal_tolerance_factor;
   if (settings->relative_dual_tolerance_factor >= 0.0) s->norm_c = settings->relative_dual_tolerance_factor;
+  if (halpern_mode(s)) DEV(pdlpdev_set_halpern(s->dev, 1));  // (a fresh context or a clone; a context that is reset keeps the mode)
   double step = s->computed_step, weight = s->computed_weight;
   if (settings->initial_step_size >= 0.0) step = settings->initial_step_size;  // pdlp.cu:1014-1021
   if (settings->initial_primal_weight >= 0.0) weight = settings->initial_primal_weight;
@@ -906,6 +1032,13 @@ static int start_run(cuoptamd_solver* s, const double* init_x, const double* ini
     s->result.initial_primal_weight = weight;
   }
   if (hyper->project_initial_primal) DEV(pdlpdev_project_primal(s->dev));  // pdlp.cu:1041-1056
+  if (halpern_mode(s)) {
+    // the anchor z^0 of the first Halpern cycle: the projected starting point with its A^T y
+    DEV(pdlpdev_compute_aty(s->dev));
+    s->need_aty = false;
+    DEV(pdlpdev_halpern_restart(s->dev, -1.0, nullptr, &s->ctl));
+    DEV(pdlpdev_get_halpern(s->dev, &s->hal));
+  } else
   DEV(pdlpdev_get_ctl(s->dev, &s->ctl));
   s->result.norm_b = s->norm_b, s->result.norm_c = s->norm_c;
   s->result.step_size = step, s->result.primal_weight = weight;
@@ -942,6 +1075,17 @@ int cuoptamd_solver_create(cuoptamd_solver** out, const cuoptamd_lp* lp, const c
     std::fprintf(stderr, "[cuopt_amd setup] %-28s %8.2f ms\n", what, 1e3 * std::chrono::duration<double>(now - last).count());
     last = now;
   };
+  if (hyper->algorithm != 0 && hyper->algorithm != 1) return fail(-1, "cuoptamd_solver_create: algorithm must be 0 (PDHG with averages) or 1 (reflected Halpern)");
+  if (hyper->algorithm == 1) {
+    // what the mode does not have is refused by name, not ignored
+    if (world > 1 || comm_id != nullptr) return fail(-7, "%s: sharded solvers (world > 1, a communicator) are not supported", kHalpernName);
+    if (settings->detect_infeasibility) return fail(-7, "%s: detect_infeasibility is not supported (the rays of the averaging iteration are not formed)", kHalpernName);
+    if (settings->save_best_primal_so_far) return fail(-7, "%s: save_best_primal_so_far is not supported", kHalpernName);
+    if (settings->first_primal_feasible) return fail(-7, "%s: first_primal_feasible is not supported", kHalpernName);
+    if (const char* bad = halpern_meaningless_setting(hyper, settings)) return fail(-7, "%s: %s has no meaning in this mode and is not accepted", kHalpernName, bad);
+    if (!(hyper->halpern_step_safety > 0.0 && hyper->halpern_step_safety < 1.0)) return fail(-1, "%s: halpern_step_safety must lie in (0, 1)", kHalpernName);
+    if (hyper->major_iteration < 1 || hyper->artificial_restart_in_main_loop) return fail(-1, "%s: needs major_iteration >= 1 and no artificial restart in the main loop", kHalpernName);
+  }
   cuoptamd_solver* s = new cuoptamd_solver();
   *out               = s;
   s->H = *hyper, s->S = *settings;
@@ -1033,8 +1177,10 @@ int cuoptamd_solver_create(cuoptamd_solver** out, const cuoptamd_lp* lp, const c
   if (ag.an && setup_rc == 0) {
     // single GPU: the analysis' device arrays become the context's
     pdlpdev_create_hint(0);
+    pdlpdev_create_no_resident(hyper->algorithm == 1);
     pdlpdev_create_batch_lanes(settings->batch_lanes);
     int rc = pdlpdev_create_from_analysis(&s->dev, ag.an, L->c, L->lo, L->hi, L->lb, L->ub);
+    pdlpdev_create_no_resident(0);  // (consumed by the creation; not left behind when it failed early)
     // the spent analysis: its workspace goes back at once (a one-slot cache: the next analysis, of this or of another solver, takes it
     // from there), the hipFree calls of the rest -- each a device synchronisation, ~3 ms of a 25 ms set-up -- wait for the solver's end
     // (CUOPT_AMD_TUNE=keep_analysis_max_nnz: the size up to which they do)
@@ -1073,12 +1219,14 @@ int cuoptamd_solver_create(cuoptamd_solver** out, const cuoptamd_lp* lp, const c
   }
   {
     pdlpdev_create_hint(world > 1 || comm_id != nullptr);
+    pdlpdev_create_no_resident(hyper->algorithm == 1);
     pdlpdev_create_batch_lanes(settings->batch_lanes);
     int rc = setup_rc;
     if (rc == 0)
       rc = pdlpdev_create_overlapped(&s->dev, device, ml, n, off.data(), idx, val, t_off.data(), t_idx.get(), t_val.get(),
                                      &TransposeJob::wait, &job, L->c, L->lo + s->row_begin, L->hi + s->row_begin, L->lb, L->ub);
     pdlpdev_create_batch_lanes(0);  // (consumed by the creation; not left behind when set-up failed before it)
+    pdlpdev_create_no_resident(0);
     if (rc == 0 && fault_injected(rank, world, "create")) rc = -6;
     job.join();
     if (rc != 0 && rc != setup_rc) fail(rc, "pdlpdev_create: %s", rc == -6 ? "injected fault (CUOPT_AMD_TUNE=fault_inject)" : pdlpdev_last_error());
@@ -1147,6 +1295,12 @@ int cuoptamd_solver_create(cuoptamd_solver** out, const cuoptamd_lp* lp, const c
   }
   if (!hyper->compute_initial_step_size_before_scaling) { int rc = initial_step_size(); if (rc) return rc; }
   if (!hyper->compute_initial_primal_weight_before_scaling) { int rc = initial_primal_weight(); if (rc) return rc; }
+  if (hyper->algorithm == 1) {
+    // the constant step size: eta * sigma_max(scaled A) = halpern_step_safety < 1 keeps PDHG's metric positive definite
+    DEV(pdlpdev_spectral_norm(s->dev, hyper->halpern_power_tolerance, hyper->halpern_power_max_products, &s->sigma_max, &s->power_products));
+    step = s->sigma_max > 0.0 ? hyper->halpern_step_safety / s->sigma_max : 1.0;
+    lap("power iteration (sigma_max)");
+  }
   s->computed_step = step, s->computed_weight = weight;
   { int rc = start_run(s, init_x, init_y); if (rc) return rc; }
   lap("initial step/weight/iterate");
@@ -1170,6 +1324,7 @@ static void reset_host_state(cuoptamd_solver* s)
   s->fused_eval_ready = false;
   s->step_error = false, s->need_aty = true, s->last_restart_was_average = false;
   s->last_candidate_kkt = 0.0, s->last_restart_kkt = 0.0, s->gap_reduction_ratio_last_trial = 1.0;
+  s->halpern_r_prev = -1.0, s->hal = pdlpdev_halpern{};
   s->best_quality = cuoptamd_solver::Quality{};
   s->best_quality.objective = s->maximize ? -std::numeric_limits<double>::infinity() : std::numeric_limits<double>::infinity();
   s->have_best = false, s->best_result = blank;
@@ -1184,6 +1339,8 @@ int cuoptamd_solver_reset(cuoptamd_solver* s, const double* lb, const double* ub
 {
   if (!s) return fail(-1, "cuoptamd_solver_reset: null solver");
   const auto t0 = clock_type::now();
+  if (settings && halpern_mode(s))  // (refused before anything of the solver changes: it stays usable with its present settings)
+    if (const char* bad = halpern_refused_setting(settings)) return fail(-7, "cuoptamd_solver_reset: %s: %s is not supported", kHalpernName, bad);
   if (settings) {
     s->S = *settings;
     if (settings->log_file && settings->log_file[0]) s->log_path = settings->log_file;
@@ -1226,6 +1383,7 @@ static bool major_due(const cuoptamd_solver* s)
 {
   const cuoptamd_hyper& H = s->H;
   const int32_t it = s->total_iterations;
+  if (halpern_mode(s)) return ((it % H.major_iteration == 0 && it > 0) || s->step_error) && s->major_done_at != it;  // (T(z^k) exists after a step)
   const bool major = (it % H.major_iteration == 0 && it > 0) || it <= H.min_iteration_restart;
   // should_do_artificial_restart (pdlp_restart_strategy.cu:939-961), Fast1 only
   const bool artificial = H.artificial_restart_in_main_loop && s->ctl.its_since_restart >= H.artificial_restart_threshold * it;
@@ -1270,7 +1428,7 @@ static int advance_to_attempts(cuoptamd_solver* s, int32_t budget_end, int32_t* 
   if (s->total_iterations >= s->H.major_iteration && fault_injected(s->rank, s->world, "advance")) return fail(-6, "injected fault (CUOPT_AMD_TUNE=fault_inject)");
   if (major_due(s)) {
     bool terminated = false;
-    int rc          = major_iteration(s, &terminated);
+    int rc          = halpern_mode(s) ? halpern_major_iteration(s, &terminated) : major_iteration(s, &terminated);
     if (rc != 0) return rc;
     major_was_done(s, terminated);
     if (terminated) {
@@ -1296,6 +1454,7 @@ static int advance_to_attempts(cuoptamd_solver* s, int32_t budget_end, int32_t* 
 }
 static void advance_after_attempts(cuoptamd_solver* s)  // (s->ctl: the control block the attempts left)
 {
+  if (halpern_mode(s)) (void)pdlpdev_get_halpern(s->dev, &s->hal);  // (read back with the control block)
   s->total_iterations = s->iteration_offset + s->ctl.steps_taken;
   if (s->ctl.error) s->step_error = true;
 }
@@ -1305,6 +1464,9 @@ static void advance_begin(cuoptamd_solver* s, clock_type::time_point t0)
   s->started     = true;
   s->solve_start = t0;
   log_line(s, "PDLP on gfx950: %d constraints, %d variables\n", s->m_global, s->n);
+  if (halpern_mode(s))
+    log_line(s, "restarted reflected Halpern iteration: sigma_max %.6e (%d products), step size %.6e, primal weight %.6e\n", s->sigma_max,
+             s->power_products, s->result.initial_step_size, s->result.initial_primal_weight);
   log_line(s, "   Iter    Primal Obj.      Dual Obj.    Gap        Primal Res.  Dual Res.   Time\n");  // pdlp.cu:1077-1080
 }
 static int32_t advance_budget_end(const cuoptamd_solver* s, int32_t max_new_iterations)
@@ -1397,6 +1559,7 @@ int cuoptamd_batch_create(cuoptamd_solver** solvers, int K, cuoptamd_batch** out
   std::vector<pdlpdev_ctx*> ctx(K);
   for (int l = 0; l < K; ++l) {
     if (!solvers[l] || !solvers[l]->dev) return fail(-1, "cuoptamd_batch_create: null solver");
+    if (halpern_mode(solvers[l])) return fail(-7, "cuoptamd_batch_create: LP %d runs the %s, which has no lockstep batch (solve them one after the other)", l, kHalpernName);
     ctx[l] = solvers[l]->dev;
   }
   // small LPs first: any number of them, any matrices, a workgroup each
@@ -1694,6 +1857,7 @@ int cuoptamd_solve_sharded(const cuoptamd_lp* lp, const cuoptamd_hyper* hyper, c
 {
   if (!lp || !hyper || !settings || !result) return fail(-1, "cuoptamd_solve_sharded: null argument");
   if (gpus < 1 || gpus > 16) return fail(-1, "cuoptamd_solve_sharded: 1..16 row blocks");
+  if (hyper->algorithm == 1) return fail(-7, "cuoptamd_solve_sharded: the %s runs on one GPU only", kHalpernName);
   if (!soft_communicator && pdlpdev_device_count() < gpus)
     return fail(-5, "cuoptamd_solve_sharded: %d GPUs requested, %d visible (there is no CPU fallback)", gpus,
                 pdlpdev_device_count());
@@ -1768,6 +1932,7 @@ int cuoptamd_solve_sharded(const cuoptamd_lp* lp, const cuoptamd_hyper* hyper, c
 int cuoptamd_solver_get_warm_start(cuoptamd_solver* s, cuoptamd_warm_start* ws)
 {
   if (!s || !ws || !s->dev) return fail(-1, "cuoptamd_solver_get_warm_start: null argument");
+  if (halpern_mode(s)) return fail(-7, "cuoptamd_solver_get_warm_start: the %s has no warm-start snapshot (its state is not the averaging iteration's)", kHalpernName);
   // Sharded solver: the primal-side vectors are replicated, of the dual-side (m-sized) vectors this rank owns rows
   // [row_begin, row_end): they land at their global positions, the other rows are zeroed -- the snapshots of all ranks
   // add up to the full one (pdlp.cu:468-489 copies whole vectors).
@@ -1846,6 +2011,7 @@ int cuoptamd_solver_get_warm_start(cuoptamd_solver* s, cuoptamd_warm_start* ws)
 int cuoptamd_solver_set_warm_start(cuoptamd_solver* s, const cuoptamd_warm_start* ws)
 {
   if (!s || !ws || !s->dev) return fail(-1, "cuoptamd_solver_set_warm_start: null argument");
+  if (halpern_mode(s)) return fail(-7, "cuoptamd_solver_set_warm_start: the %s takes no warm-start snapshot", kHalpernName);
   if (s->started) return fail(-1, "cuoptamd_solver_set_warm_start: the solver has already been advanced");
   if ((ws->n_variables != 0 && ws->n_variables != s->n) || (ws->n_constraints != 0 && ws->n_constraints != s->m_global))
     return fail(-1, "cuoptamd_solver_set_warm_start: the snapshot belongs to a %d x %d problem, this one is %d x %d",

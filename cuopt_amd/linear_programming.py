@@ -59,6 +59,7 @@ class PDLPSolverMode(IntEnum):  # solver_settings.py:63-96
     Stable2 = 1
     Methodical1 = 2
     Fast1 = 3
+    Halpern1 = 4  # not in the reference: restarted reflected Halpern iteration, constant step size (CUOPT_AMD_PDLP_SOLVER_MODE_HALPERN1)
 
     def __str__(self):
         return "%d" % self.value
@@ -476,7 +477,9 @@ def Solve(data_model, solver_settings=None, log_file=""):
     try:
         r = s.advance()
         x, y, z = s.solution()
-        snap = PDLPWarmStartData._from_capi(s.get_warm_start()) if r["status"] not in (0, 6) else None
+        # (the Halpern mode has no warm-start snapshot: its state is not the averaging iteration's)
+        halpern = int(st[CUOPT_PDLP_SOLVER_MODE]) == int(PDLPSolverMode.Halpern1)
+        snap = PDLPWarmStartData._from_capi(s.get_warm_start()) if r["status"] not in (0, 6) and not halpern else None
     finally:
         s.close()
     return Solution(ProblemCategory.LP, _named(data_model, x), time.perf_counter() - t0, x, y, z, r["status"],

@@ -8,6 +8,11 @@
  *                            simplex-grade tolerances (1e-8) with the requested tolerances as acceptance set
  *                            (cuoptamd_settings::accept_tolerance).  -1 (default) = the key simplex_grade of the
  *                            CUOPT_AMD_TUNE environment string (CUOPT_AMD_TUNE=simplex_grade=0), else on.
+ * Extra value of CUOPT_PDLP_SOLVER_MODE (constants.h stops at CUOPT_PDLP_SOLVER_MODE_FAST1 = 3):
+ *   CUOPT_AMD_PDLP_SOLVER_MODE_HALPERN1 = 4: the restarted reflected Halpern iteration with a constant step size
+ *                            (cuoptamd_hyper_preset(4), docs/design/04d_halpern_mode.md).  One GPU; infeasibility detection,
+ *                            save_best_primal_so_far and first_primal_feasible are refused with a validation error, and the
+ *                            simplex-grade emulation leaves the infeasibility detection it would switch on off.
  */
 #ifndef CUOPT_AMD_CUOPT_C_EXT_H
 #define CUOPT_AMD_CUOPT_C_EXT_H
@@ -17,6 +22,7 @@
 
 #define CUOPT_AMD_NUM_GPUS "amd_num_gpus"
 #define CUOPT_AMD_SIMPLEX_GRADE "amd_simplex_grade"
+#define CUOPT_AMD_PDLP_SOLVER_MODE_HALPERN1 4
 
 #ifdef __cplusplus
 extern "C" {
@@ -26,7 +32,7 @@ extern "C" {
  * C++ / Python API only: cpp/include/cuopt/linear_programming/pdlp/solver_solution.hpp:63-103) */
 cuopt_int_t cuOptAmdGetPdlpStats(cuOptSolution solution, cuoptamd_result* stats);
 
-/* which engine / attempt answered the request, as one JSON object:
+/* which engine / attempt answered the request, as one JSON object (also "pdlp_algorithm": "pdhg_average" | "reflected_halpern"):
  * {"engine": "pdlp" | "dual_simplex", "requested_method": "Concurrent|DualSimplex|PDLP", "crossover_requested": bool,
  *  "simplex_grade_emulation": bool, "dual_simplex_consulted": bool, "dual_simplex_status": 1..9 (cuoptamd_dual_simplex),
  *  "crossover": "none" | "dual_simplex_from_the_pdlp_point" | "not_done_..." | "not_needed_vertex_from_the_dual_simplex",

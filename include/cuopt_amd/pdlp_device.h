@@ -58,6 +58,17 @@ typedef struct pdlpdev_ctl {
   int32_t its_since_restart;
 } pdlpdev_ctl;
 
+/* Scalars of the restarted reflected-Halpern mode (pdlpdev_set_halpern), a block of their own next to the control block: the
+ * kernels of the averaging modes never see it, and the batch code keeps copying pdlpdev_ctl by size. */
+typedef struct pdlpdev_halpern {
+  double r;       /* fixed-point error of the last step: sqrt(max(r2, 0))                                   */
+  double r_first; /* ... of the first step after the last restart                                           */
+  double r2;      /* (w/eta) ||dx||^2 + 2 dy.(A dx) + ||dy||^2 / (eta w) of the last step, as it was summed */
+  double r2_min;  /* smallest r2 since the mode was switched on / the last pdlpdev_reset (>= 0 when eta sigma_max < 1) */
+  int32_t k;      /* steps since the last restart: the next step combines with w_k = (k + 1) / (k + 2)      */
+  int32_t reserved;
+} pdlpdev_halpern;
+
 /* hyper-parameters the device kernels need (subset of pdlp_hyper_params.cuh:20-58) */
 typedef struct pdlpdev_step_params {
   double reduction_exponent;        /* default_reduction_exponent   */
@@ -112,6 +123,7 @@ enum {
   PDLPDEV_BUF_LAST_RESTART_X, PDLPDEV_BUF_LAST_RESTART_Y,
   PDLPDEV_BUF_ATY_U_CURRENT, /* A^T y of the unscaled problem from the last eval(CURRENT)  n */
   PDLPDEV_BUF_ATY_U_AVERAGE, /*                                                            n */
+  PDLPDEV_BUF_LAST_RESTART_ATY, /* Halpern mode: A^T y of the anchor (scaled)               n */
   PDLPDEV_BUF_COUNT
 };
 
@@ -124,6 +136,8 @@ enum {
   PDLPDEV_K_SPMV_A_PLAIN, /* y = A x (unfused CSR SpMV)                          */
   PDLPDEV_K_SPMV_AT_PLAIN,
   PDLPDEV_K_ITERATION,    /* the whole 4-kernel attempt                          */
+  /* (a context in Halpern mode brackets its own kernels under the same ids: K_SPMV_A_DUAL = k_*_a_halpern, K_SPMV_AT_STEP =
+   *  k_*_at_halpern, K_STEP_DECISION = k_halpern_decision) */
   PDLPDEV_K_COUNT
 };
 
@@ -149,6 +163,9 @@ int pdlpdev_create(pdlpdev_ctx** out, int device, int32_t m, int32_t n, const in
 /* the NEXT context created by this thread will run behind a communicator (sharded solve): paths that exist on one GPU only --
  * dense row segments, the resident small-LP kernel -- are not set up */
 void pdlpdev_create_hint(int sharded);
+/* the NEXT context created by this thread stays off the resident small-LP path whatever its size (a context that will be put into
+ * Halpern mode: the one-workgroup loop knows the averaging iteration only); reset to 0 by the creation */
+void pdlpdev_create_no_resident(int no_resident);
 /* The next context created on this thread builds its jagged layouts for lockstep batches of up to `lanes` LPs (0, 2, 4, 8, 16:
  * cuoptamd_settings::batch_lanes); reset to 0 by the creation. */
 void pdlpdev_create_batch_lanes(int lanes);
@@ -381,6 +398,28 @@ int pdlpdev_prepare_graphs(pdlpdev_ctx* ctx);
 int pdlpdev_copy_in(void* dst, const void* src, size_t bytes);
 void pdlpdev_range_push(const char* name);
 void pdlpdev_range_pop(void);
+
+/* ---- restarted reflected-Halpern mode (no counterpart in the reference; docs/design/04d_halpern_mode.md) ----------------------
+ * z^{k+1} = w_k (2 T(z^k) - z^k) + (1 - w_k) z^0, w_k = (k + 1) / (k + 2), T = one PDHG step as k_primal and the dual epilogue
+ * compute it, z^0 = the iterate at the last restart, constant step size: a step never fails.  The iterate buffers hold z^k (x, y and
+ * A^T y, the last formed by the same linear combination from A^T y', A^T y^k and A^T y^0); T(z^k) of the LAST step of a run lives in
+ * the AVERAGE slots (PDLPDEV_AVERAGE of pdlpdev_eval / pdlpdev_get_solution, PDLPDEV_BUF_AVG_X / _Y), which this mode does not use
+ * for anything else, so the evaluation of "the average" is the evaluation of T(z^k).
+ * pdlpdev_set_halpern: before the first step (after scaling), single GPU, not the resident small-LP path (-7 otherwise).  Switching the
+ * mode on or off drops the captured graphs.  pdlpdev_reset keeps the mode and puts its scalars and anchor back to zero. */
+int pdlpdev_set_halpern(pdlpdev_ctx* ctx, int on);
+/* sigma_max of the scaled matrix by power iteration on A^T A through the solver's own plain products, from the start vector
+ * 1 / sqrt(n), until the estimate of sigma_max^2 moves by at most rel_tol relative or max_products products of A^T A were formed;
+ * deterministic.  *products: how many were.  Single GPU; uses xbar and the two tmp vectors as scratch (before the first step). */
+int pdlpdev_spectral_norm(pdlpdev_ctx* ctx, double rel_tol, int32_t max_products, double* sigma_max, int32_t* products);
+/* Restart of the Halpern iteration at the current iterate: dist[0] = ||x^k - x^0||_2, dist[1] = ||y^k - y^0||_2 (scaled space, NOT
+ * squared); when both exceed 1e-10 and theta >= 0 the primal weight becomes exp(theta log(dist[1] / dist[0]) + (1 - theta) log w) on
+ * the device (tau, sigma follow); anchor <- iterate (x, y and its A^T y), k <- 0, its_since_restart <- 0.  theta < 0: the anchor and
+ * the counters only (the start of a solve).  *ctl (may be NULL) receives the control block afterwards. */
+int pdlpdev_halpern_restart(pdlpdev_ctx* ctx, double theta, double dist[2], pdlpdev_ctl* ctl);
+/* the Halpern scalars as the last pdlpdev_run / pdlpdev_run_period / pdlpdev_halpern_restart / pdlpdev_get_ctl read them back together
+ * with the control block */
+int pdlpdev_get_halpern(pdlpdev_ctx* ctx, pdlpdev_halpern* out);
 
 /* ---- major iteration -------------------------------------------------------------------------- */
 /* adds a still-pending accepted iterate to the running sums */

@@ -73,6 +73,16 @@ typedef struct cuoptamd_hyper {
   int32_t update_step_size_on_initial_solution;
   int32_t handle_some_primal_gradients_on_finite_bounds_as_residuals;
   int32_t project_initial_primal;
+  /* ---- trailing fields, not in the reference (cuoptamd_hyper_preset fills them for every mode) ----
+   * algorithm 0: PDHG with the adaptive step-size rule, running averages and KKT / trust-region restarts (the reference's; the four
+   * cuOpt presets).  1: restarted reflected Halpern iteration with a constant step size (preset 4, docs/design/04d_halpern_mode.md):
+   * eta = halpern_step_safety / sigma_max(scaled A), sigma_max by power iteration on A^T A until the estimate of sigma_max^2 moves by
+   * at most halpern_power_tolerance relative or halpern_power_max_products products; restarts on the fixed-point error with
+   * sufficient_ / necessary_reduction_for_restart and artificial_restart_threshold; primal_weight_update_smoothing at a restart. */
+  int32_t algorithm;
+  int32_t halpern_power_max_products;
+  double halpern_step_safety;
+  double halpern_power_tolerance;
 } cuoptamd_hyper;
 
 /* pdlp_solver_settings_t subset (pdlp/solver_settings.hpp:70-224) */
@@ -212,7 +222,10 @@ int cuoptamd_dual_simplex_from(const cuoptamd_lp* lp, const double* x0, const do
 
 const char* cuoptamd_last_error(void);
 
-/* presets, mode numbering as CUOPT_PDLP_SOLVER_MODE_* (0 Stable1, 1 Stable2, 2 Methodical1, 3 Fast1) */
+/* presets, mode numbering as CUOPT_PDLP_SOLVER_MODE_* (0 Stable1, 1 Stable2, 2 Methodical1, 3 Fast1) and, beyond the reference's,
+ * 4 = Halpern1 (CUOPT_AMD_PDLP_SOLVER_MODE_HALPERN1, cuopt_c_ext.h): Stable2's scaling and initial primal weight, algorithm = 1.  A
+ * Halpern solver runs on one GPU and refuses, with a message that names the mode: sharded creation, warm-start snapshots,
+ * detect_infeasibility, save_best_primal_so_far, first_primal_feasible; cuoptamd_batch_create answers -7 for it. */
 void cuoptamd_hyper_preset(int mode, cuoptamd_hyper* h);
 void cuoptamd_default_settings(cuoptamd_settings* s);
 

@@ -1,0 +1,147 @@
+#!/usr/bin/env python3
+"""Measurements of the restarted reflected-Halpern mode (solver mode 4) against Stable2 -> profiles/r09_halpern.jsonl.
+
+  python scripts/halpern_compare.py [--out FILE] [--only cost|convergence] [--workloads c3,c2,...] [--parent-lib libcuopt.so]
+
+* cost of a step: ms per step in mode 4 against ms per ATTEMPT of Stable2 (solves to a fixed iteration count from a warmed
+  solver: wall time over attempted steps, five alternating runs each), plus the per-kernel durations of both modes from
+  pdlpdev_time_kernel.  --parent-lib runs the Stable2 leg on another build of the library (a child process per leg: one process
+  holds one library), which is how the step of this tree is compared with the attempt of the commit before it.
+* iterations and wall time to 1e-4 and to 1e-8, mode 4 against Stable2 of the same build, on the synthetic families and the
+  golden LPs with more than 50 rows.  Reported whichever way they fall; Stable2 stays the default preset.
+Every record is one JSON line: {"kind": "cost" | "kernels" | "convergence", ...}; --out is written anew by every run.
+
+Each leg is a child process of its own under a time limit sized to the leg.  The first leg that fails, is killed by a signal or
+runs out of its time ends the whole run with a non-zero exit: nothing more is started on a GPU that has just shown trouble."""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def problem(name):
+    import numpy as np
+    from cuopt_amd import synthetic
+    if name in synthetic.CONFIGS:
+        return synthetic.generate(**synthetic.CONFIGS[name])
+    if name == "hard":
+        return synthetic.generate(**dict(synthetic.CONFIGS["c3"], hard=True))
+    if name in ("staircase", "block_angular"):
+        return synthetic.generate_structured(name, m=1_000_000, n=1_000_000, k=10, seed=7)
+    raw = json.load(open(os.path.join(ROOT, "tests", "golden", "problems.json")))[name]
+    dec = lambda v: np.array([np.inf if x == "inf" else -np.inf if x == "-inf" else x for x in v], dtype=np.float64)
+    return dict(m=raw["m"], n=raw["n"], offsets=np.array(raw["offsets"], np.int32), indices=np.array(raw["indices"], np.int32),
+                values=dec(raw["values"]), c=dec(raw["c"]), lo=dec(raw["lo"]), hi=dec(raw["hi"]), lb=dec(raw["lb"]), ub=dec(raw["ub"]),
+                maximize=bool(raw["maximize"]), objective_offset=float(raw["objective_offset"]))
+
+
+def cost_leg(name, mode, steps, runs):
+    """ms per attempted step of `mode`, `runs` times: a solver advanced by `steps` iterations after a warm-up of 200"""
+    from cuopt_amd import capi
+    p = problem(name)
+    out = []
+    for _ in range(runs):
+        s = capi.Solver(p, mode=mode, tol=1e-30)
+        s.advance(200)
+        before = s.result.attempted_steps
+        t0 = time.perf_counter()
+        r = s.advance(steps)
+        dt = time.perf_counter() - t0
+        out.append(1e3 * dt / max(1, r["attempted_steps"] - before))
+        if mode == 4 or len(out) == runs:
+            kernels = {k: s.device.time_kernel(k, reps=20) for k in ("PRIMAL", "SPMV_A_DUAL", "SPMV_AT_STEP", "STEP_DECISION")}
+        s.close()
+    return dict(ms_per_step=out, kernels_ms=kernels)
+
+
+def convergence_leg(name, mode, tol, limit):
+    from cuopt_amd import capi
+    p = problem(name)
+    s = capi.Solver(p, mode=mode, tol=tol, iteration_limit=limit)
+    r = s.advance()
+    lay = s.device.layout()
+    s.close()
+    return dict(status=r["status_name"], iterations=r["steps_taken"], attempts=r["attempted_steps"], restarts=r["num_restarts"],
+                loop_seconds=r["loop_seconds"], setup_seconds=r["setup_seconds"], objective=r["primal_objective"],
+                layout=[lay["A"]["layout"], lay["At"]["layout"]])
+
+
+def child(args):
+    leg = json.loads(args.child)
+    if leg["kind"] == "cost":
+        print(json.dumps(cost_leg(leg["workload"], leg["mode"], leg["steps"], leg["runs"])))
+    else:
+        print(json.dumps(convergence_leg(leg["workload"], leg["mode"], leg["tol"], leg["limit"])))
+
+
+def leg_seconds(leg):
+    """time limit of a leg: the LP's generation and set-up (a minute at 1e7 nonzeros on a slow host) plus the steps it may take at a
+    pessimistic millisecond each"""
+    steps = leg["steps"] + 200 if leg["kind"] == "cost" else leg["limit"]
+    return 90 + steps // 1000
+
+
+def run_child(leg, lib=None):
+    env = dict(os.environ)
+    if lib:
+        env["CUOPT_AMD_LIB"] = os.path.abspath(lib)
+    try:
+        out = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", json.dumps(leg)], env=env, capture_output=True, text=True,
+                             timeout=leg_seconds(leg))
+    except subprocess.TimeoutExpired:
+        sys.exit("halpern_compare: leg %s ran out of its %d s: stopping, nothing more is started on this GPU" % (leg, leg_seconds(leg)))
+    if out.returncode != 0:
+        sys.exit("halpern_compare: leg %s ended with status %d: stopping, nothing more is started on this GPU\n%s" % (leg, out.returncode, out.stderr[-2000:]))
+    return json.loads(out.stdout.strip().splitlines()[-1])
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r09_halpern.jsonl"))
+    ap.add_argument("--only", default=None, choices=["cost", "convergence"])
+    ap.add_argument("--workloads", default=None)
+    ap.add_argument("--parent-lib", default=None)
+    ap.add_argument("--steps", type=int, default=6000)
+    ap.add_argument("--limit", type=int, default=200000)
+    ap.add_argument("--child", default=None)
+    args = ap.parse_args()
+    if args.child:
+        return child(args)
+    open(args.out, "w").close()
+
+    def emit(rec):
+        print(json.dumps(rec), flush=True)
+        with open(args.out, "a") as f:
+            f.write(json.dumps(rec) + "\n")
+
+    if args.only in (None, "cost"):
+        for w in (args.workloads.split(",") if args.workloads else ["c3", "c2", "banded"]):
+            stable, halpern = [], []
+            steps = args.steps * (20 if w == "c2" else 1)  # (c2: 0.03 ms per step -- a timed window of a second, like the others')
+            for _ in range(5):  # alternating: the two legs see the same machine state
+                a = run_child(dict(kind="cost", workload=w, mode=1, steps=steps, runs=1), lib=args.parent_lib)
+                b = run_child(dict(kind="cost", workload=w, mode=4, steps=steps, runs=1))
+                stable += a["ms_per_step"]
+                halpern += b["ms_per_step"]
+            emit(dict(kind="cost", workload=w, steps=steps, stable2_library="parent" if args.parent_lib else "this build", stable2_ms_per_attempt=stable,
+                      halpern_ms_per_step=halpern, ratio_of_medians=sorted(halpern)[2] / sorted(stable)[2]))
+            emit(dict(kind="kernels", workload=w, stable2_ms=a["kernels_ms"], halpern_ms=b["kernels_ms"]))
+    if args.only in (None, "convergence"):
+        names = args.workloads.split(",") if args.workloads else ["c3", "c2", "hard", "banded", "staircase", "block_angular", "afiro",
+                                                                  "mip-50v-10-free-bound-relaxation", "mip-neos5-free-bound-relaxation",
+                                                                  "mip-sudoku-relaxation", "mip-cod105_max-relaxation"]
+        for w in names:
+            for tol in (1e-4, 1e-8):
+                rec = dict(kind="convergence", workload=w, tol=tol)
+                for mode, key in ((1, "stable2"), (4, "halpern")):
+                    rec[key] = run_child(dict(kind="convergence", workload=w, mode=mode, tol=tol, limit=args.limit))
+                emit(rec)
+
+
+if __name__ == "__main__":
+    main()
