@@ -111,7 +111,7 @@ class SolverSettings(C.Structure):
                 ("log_to_console", c_int), ("log_file", c_char_p), ("unbounded_from_feasible_iterates", c_int),
                 ("accept_enabled", c_int), ("accept_tolerance", c_double * 6),
                 ("relative_primal_tolerance_factor", c_double), ("relative_dual_tolerance_factor", c_double),
-                ("batch_lanes", c_int)]
+                ("batch_lanes", c_int), ("halpern_resident", c_int)]
 
 
 class Result(C.Structure):
@@ -323,6 +323,8 @@ _proto("cuoptamd_batch_get_solutions", c_int, c_void_p, c_void_p, c_void_p, c_vo
 _proto("cuoptamd_batch_branch", c_int, c_void_p, c_void_p, c_void_p, c_void_p)
 _proto("cuoptamd_batch_solution_views", c_int, c_void_p, c_void_p, c_void_p, c_void_p)
 _proto("cuoptamd_batch_device", c_void_p, c_void_p)
+_proto("pdlpdev_small_batch_create", c_int, P(c_void_p), P(c_void_p), c_int)  # (the device layer's K-workgroup batch of resident LPs)
+_proto("pdlpdev_small_batch_destroy", None, c_void_p)
 _proto("pdlpdev_create_share_stream", None, c_void_p)
 _proto("pdlpdev_debug_ipc_export", c_int, c_int, c_int, c_void_p, P(c_void_p))
 _proto("pdlpdev_debug_ipc_store", c_int, c_int, c_void_p, c_int, c_double)

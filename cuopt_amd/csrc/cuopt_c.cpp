@@ -65,6 +65,7 @@ struct Settings {
   // CUOPT_AMD_NUM_GPUS environment variable, default 1) and the simplex-grade emulation switch (-1 = the key simplex_grade of
   // the CUOPT_AMD_TUNE environment string, default on)
   int32_t num_gpus = 0, simplex_grade = -1;
+  int32_t halpern_resident = 0;  // reflected Halpern mode: LPs of resident size run inside one workgroup (cuoptamd_settings::halpern_resident)
   int32_t dual_simplex = -1;  // the dual simplex engine: -1 = CUOPT_AMD_DUAL_SIMPLEX (default on), 0 off, 1 on
   bool infeasibility_detection = false, strict_infeasibility = false, per_constraint_residual = false,
        save_best_primal_so_far = false, first_primal_feasible = false, log_to_console = true,
@@ -104,7 +105,8 @@ struct Settings {
             {CUOPT_NUM_CPU_THREADS, &num_cpu_threads, -1, INT_MAX},
             {"amd_num_gpus", &num_gpus, 0, 16},
             {"amd_simplex_grade", &simplex_grade, -1, 1},
-            {"amd_dual_simplex", &dual_simplex, -1, 1}};
+            {"amd_dual_simplex", &dual_simplex, -1, 1},
+            {CUOPT_AMD_HALPERN_RESIDENT, &halpern_resident, 0, 1}};
     bools = {{CUOPT_INFEASIBILITY_DETECTION, &infeasibility_detection},
              {CUOPT_STRICT_INFEASIBILITY, &strict_infeasibility},
              {CUOPT_PER_CONSTRAINT_RESIDUAL, &per_constraint_residual},
@@ -782,6 +784,7 @@ cuopt_int_t cuOptSolve(cuOptOptimizationProblem problem, cuOptSolverSettings set
     st.dual_infeasible_tolerance   = s->dual_infeasible_tolerance;
     st.save_best_primal_so_far     = s->save_best_primal_so_far;
     st.log_to_console              = s->log_to_console;
+    st.halpern_resident            = s->halpern_resident;
     st.log_file                    = s->log_file.empty() ? nullptr : s->log_file.c_str();
     auto say = [&](const std::string& line) {
       if (s->log_to_console) std::fputs(line.c_str(), stdout), std::fflush(stdout);
@@ -815,6 +818,7 @@ cuopt_int_t cuOptSolve(cuOptOptimizationProblem problem, cuOptSolverSettings set
     double first_attempt_seconds = 0.0;
     int32_t first_attempt_steps = 0, first_attempt_attempts = 0;  // work of a simplex-grade attempt that a second solve followed
     bool second_leg = false;  // ... inside a Concurrent race (the simplex kept running)
+    int halpern_resident_ran = 0;  // the solver that answered ran the Halpern mode on the resident small-LP path
     std::string answered = simplex_grade && tightened ? "simplex_grade_1e-8" : "requested_tolerances";
     sol->x.assign(p->n, 0.0), sol->y.assign(p->m, 0.0), sol->rc.assign(p->n, 0.0);
     auto take_simplex = [&]() {  // the dual simplex's verdict as the solve's result
@@ -848,6 +852,10 @@ cuopt_int_t cuOptSolve(cuOptOptimizationProblem problem, cuOptSolverSettings set
         cuoptamd_solver_destroy(solver);
         if (rc == -7) return error(CUOPT_VALIDATION_ERROR, "ValidationError", msg);
         return error(CUOPT_RUNTIME_ERROR, "RuntimeError", msg);
+      }
+      {
+        int32_t lay[8] = {0};
+        if (hyper.algorithm == 1 && pdlpdev_layout_info(cuoptamd_solver_device(solver), lay) == 0) halpern_resident_ran = lay[0] == 2;
       }
       if (racing) {
         // Concurrent: the simplex on a host thread, PDLP here in batches of a few major iterations; the first verdict wins
@@ -958,12 +966,12 @@ cuopt_int_t cuOptSolve(cuOptOptimizationProblem problem, cuOptSolverSettings set
                     "{\"engine\": \"%s\", \"requested_method\": \"%s\", \"crossover_requested\": %s, \"simplex_grade_emulation\": %s, "
                     "\"dual_simplex_consulted\": %s, \"dual_simplex_status\": %d, \"crossover\": \"%s\", "
                     "\"answered_by\": \"%s\", \"gpus\": %d, \"iterations\": %d, \"simplex_grade_attempt_iterations\": %d, "
-                    "\"pdlp_algorithm\": \"%s\"}",
+                    "\"pdlp_algorithm\": \"%s\", \"halpern_resident\": %d}",
                     engine_answered ? "dual_simplex" : "pdlp", method_name, s->crossover ? "true" : "false", simplex_grade ? "true" : "false",
                     engine_ran ? "true" : "false", (int)sx.status, crossover_by, answered.c_str(), gpus,
                     res.steps_taken + (answered == "requested_tolerances_after_simplex_grade_budget" ? first_attempt_steps : 0),
                     answered == "requested_tolerances_after_simplex_grade_budget" ? first_attempt_steps : 0,
-                    hyper.algorithm == 1 ? "reflected_halpern" : "pdhg_average");
+                    hyper.algorithm == 1 ? "reflected_halpern" : "pdhg_average", halpern_resident_ran);
       sol->solve_info = info;
       if (other_method || s->crossover) say("cuopt_amd: " + sol->solve_info + "\n");
     }

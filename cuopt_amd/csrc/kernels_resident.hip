@@ -5,6 +5,7 @@
 // cpp/src/mip/relaxed_lp/relaxed_lp.cu:53-127 -- one LP keeps ONE of the chip's 256 CUs busy, 256 LPs keep all of them).
 #include "pdlp_ctx.hpp"
 #include "pdlp_layouts.hpp"
+#include "resident_common.hpp"  // lds_row_sum, the tiers, MajorSmallArgs + small_rows: shared with kernels_resident_halpern.hip
 
 // ------------------------------------------------------------------------------------------------
 // Small LPs (MIP-style repeated re-solves, BASELINE config 5): the whole batch of PDHG attempts between two
@@ -25,19 +26,6 @@ struct SmallView {
   const double *a_val, *at_val, *c, *lb, *ub, *lo, *hi;
   double *x0, *x1, *y0, *y1, *aty0, *aty1, *sumx, *sumy;
 };
-// prod[a..b) added up strictly left to right; eight LDS reads are in flight before the first add
-__device__ __forceinline__ double lds_row_sum(const double* prod, int a, int b)
-{
-  double acc = 0.0;
-  for (int k = a; k < b; k += 8) {
-    double p[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) p[i] = prod[k + i < b ? k + i : a];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) acc = k + i < b ? acc + p[i] : acc;
-  }
-  return acc;
-}
 // LDS hazards of the resident loop (round-6 audit), barriers B1 ... B5 of an attempt (B5 sits inside block_sum_fast):
 //   xbar_s  written in the primal phase (own columns) before B1, gathered before B2; next written after B5 of the same attempt.
 //   prod    written before B2 (A xbar products, own slots) and before B4 (A^T y' products); read by the row sums before B3 / B5;
@@ -203,9 +191,7 @@ __global__ void __launch_bounds__(T) k_pdhg_resident_batch(const ResidentArgs* _
   const ResidentArgs& A = args[list[blockIdx.x]];
   resident_body<T, Q, U>(A.V, A.ctl, A.ctl_host, A.sp, A.target_steps, max_attempts, lds);
 }
-// the three instantiations, smallest first: (lanes, elements per lane, nonzeros per lane)
-struct ResidentTier { int T, Q, U; };
-constexpr ResidentTier kResidentTiers[3] = {{256, 2, 8}, {512, 2, 16}, {512, 4, 8}};
+// the three instantiations (kResidentTiers, resident_common.hpp), smallest first
 int resident_tier(int m, int n, int64_t nnz)
 {
   for (int i = 0; i < 3; ++i) {
@@ -213,11 +199,6 @@ int resident_tier(int m, int n, int64_t nnz)
     if (m <= r.Q * r.T && n <= r.Q * r.T && nnz <= (int64_t)r.U * r.T) return i;
   }
   return -1;
-}
-static size_t resident_lds_bytes(int tier)
-{
-  const ResidentTier& r = kResidentTiers[tier];
-  return sizeof(double) * (size_t)r.T * (7 * r.Q + r.U);
 }
 template <int T, int Q, int U>
 static int launch_resident(hipStream_t s, int tier, const SmallView& V, pdlpdev_ctl* ctl, pdlpdev_ctl* ctl_host,
@@ -237,33 +218,9 @@ static int launch_resident(hipStream_t s, int tier, const SmallView& V, pdlpdev_
 }
 
 
-// single-workgroup head of a major iteration (pdlpdev_major_eval) for LPs on the resident path
-struct MajorSmallArgs {
-  int m, n, mode, rule_finite, want_linf;
-  double eps_p, eps_d;
-  const int32_t *a_off, *a_idx, *at_off, *at_idx;
-  const double *a_val, *at_val;
-  pdlpdev_ctl* ctl;
-  double *x0, *x1, *y0, *y1, *sumx, *sumy, *avgx, *avgy;
-  const double *dr, *dc, *c_u, *lb_u, *ub_u, *lo_u, *hi_u;
-  double *linf_m, *linf_n, *ax_cur, *ax_avg, *aty_cur, *aty_avg, *rc_cur, *rc_avg;
-  double* sc;  // current at sc[0..9), average at sc[32..41)  (pinned host memory: no read-back copy)
-  int guard_target = -1;  // >= 0 (evaluation enqueued right behind the attempts of a small-LP batch): only if the attempts reached this
-                          // accepted-step count or raised the step-size error -- i.e. only if a major iteration is what comes next
-};
-constexpr int kMajorThreads = 1024;
-// M vec for a matrix of <= 8192 nonzeros: all products in parallel into LDS, then every row is added up left to
-// right by one lane (same order as every other SpMV here)
-template <class Epi, int NQ>
-__device__ __forceinline__ void small_rows(int rows, const int32_t* __restrict__ off, const int32_t* __restrict__ idx,
-                                           const double* __restrict__ val, const double* vec, double* prod, Epi& e,
-                                           double (&acc)[NQ])
-{
-  const int nnz = off[rows];
-  for (int k = threadIdx.x; k < nnz; k += kMajorThreads) prod[k] = val[k] * vec[idx[k]];
-  __syncthreads();
-  for (int r = threadIdx.x; r < rows; r += kMajorThreads) e.row(r, lds_row_sum(prod, off[r], off[r + 1]), acc);
-}
+// single-workgroup head of a major iteration (pdlpdev_major_eval) for LPs on the resident path: MajorSmallArgs, small_rows
+// (resident_common.hpp)
+// (k_major_small_halpern in kernels_resident_halpern.hip carries a copy of the `which == 1` pass below: a change here is made there too)
 __device__ __forceinline__ void major_small_body(const MajorSmallArgs& A, double* prod /* nnz doubles of LDS */)
 {
   __shared__ double red[4 * kMajorThreads / 64];
@@ -345,15 +302,6 @@ static SmallView small_view(const pdlpdev_ctx* ctx)
   return SmallView{ctx->m, ctx->n, (int)ctx->nnz, ctx->a_off, ctx->a_idx, ctx->at_off, ctx->at_idx, ctx->a_val, ctx->at_val,
                    ctx->c, ctx->lb, ctx->ub, ctx->lo, ctx->hi, ctx->x[0], ctx->x[1], ctx->y[0], ctx->y[1], ctx->aty[0],
                    ctx->aty[1], ctx->sumx, ctx->sumy};
-}
-static MajorSmallArgs major_args(const pdlpdev_ctx* ctx, int average_mode, int rc_rule_finite_bounds, int want_linf, double eps_rel_primal, double eps_rel_dual)
-{
-  return MajorSmallArgs{ctx->m, ctx->n, average_mode, rc_rule_finite_bounds, want_linf, eps_rel_primal, eps_rel_dual,
-                        ctx->a_off, ctx->a_idx, ctx->at_off, ctx->at_idx, ctx->a_val, ctx->at_val, ctx->ctl,
-                        ctx->x[0], ctx->x[1], ctx->y[0], ctx->y[1], ctx->sumx, ctx->sumy, ctx->avgx, ctx->avgy,
-                        ctx->dr, ctx->dc, ctx->c_u, ctx->lb_u, ctx->ub_u, ctx->lo_u, ctx->hi_u, ctx->tmp_m, ctx->tmp_n,
-                        ctx->ax_u[PDLPDEV_CURRENT], ctx->ax_u[PDLPDEV_AVERAGE], ctx->aty_u[PDLPDEV_CURRENT],
-                        ctx->aty_u[PDLPDEV_AVERAGE], ctx->rc[0], ctx->rc[1], ctx->scal_h};
 }
 static int major_lds_attribute(int device)
 {
@@ -559,6 +507,8 @@ int pdlpdev_small_batch_create(pdlpdev_small_batch** out, pdlpdev_ctx** ctx, int
     if (!c) return fail(-1, "pdlpdev_small_batch_create: null context");
     if (!c->small_resident || c->comm || c->pat.on || c->jat.on || c->pbat.on || c->dense.on)
       return fail(-7, "pdlpdev_small_batch_create: LP %d is not on the resident small-LP path", l);
+    if (c->halpern)  // (the batch's loop, evaluation and restart are the averaging iteration's)
+      return fail(-7, "pdlpdev_small_batch_create: LP %d is in reflected Halpern mode, which has no K-workgroup batch (solve them one after the other)", l);
     if (c->device != ctx[0]->device) return fail(-7, "pdlpdev_small_batch_create: the LPs sit on different devices");
     for (int q = 0; q < l; ++q)
       if (ctx[q] == c) return fail(-1, "pdlpdev_small_batch_create: LP %d and LP %d are the same context", q, l);

@@ -1257,7 +1257,7 @@ int pdlpdev_run(pdlpdev_ctx* ctx, int32_t target_steps, pdlpdev_ctl* ctl)
   roctx::Range range("pdlp: PDHG attempts");
   HIP_TRY(hipSetDevice(ctx->device));
   if (ctx->small_resident && !ctx->comm) {  // the whole loop inside one workgroup (kernels_resident.hip)
-    TRY(resident_run(ctx, target_steps));
+    TRY(ctx->halpern ? resident_halpern_run(ctx, target_steps) : resident_run(ctx, target_steps));
     if (ctl) *ctl = *ctx->ctl_h;
     return 0;
   }
@@ -1272,13 +1272,30 @@ int pdlpdev_run(pdlpdev_ctx* ctx, int32_t target_steps, pdlpdev_ctl* ctl)
 // kernels, each of which does nothing unless the target was reached), then one read-back of the scalars and the control block.
 // *evaluated = 1: the period was reached and out_current / out_average hold what pdlpdev_major_eval(rq) would have returned.
 // *evaluated = 0: the attempts are done as pdlpdev_run does them (make-up rounds included) and NOTHING of the major iteration has
-// happened -- the context is not eligible (sharded, resident, a layout without guarded evaluation kernels, l-infinity residuals
-// asked for, a control block the host does not hold), the period fell short, or the step error is up; the caller goes on the present way.
+// happened -- the context is not eligible (sharded, resident in an averaging mode, a layout without guarded evaluation kernels,
+// l-infinity residuals asked for, a control block the host does not hold), the period fell short, or the step error is up; the caller
+// goes on the present way.
+// A resident context in Halpern mode is always eligible and takes a branch of its own: the one-workgroup loop kernel with its target,
+// the one-workgroup evaluation of T(z^k) guarded behind it (l-infinity residuals included), one synchronisation; *evaluated = 1 unless
+// the step error came up or a launch hit its step cap.
 int pdlpdev_run_period(pdlpdev_ctx* ctx, int32_t target_steps, const pdlpdev_small_eval* rq, pdlpdev_ctl* ctl,
                        double out_current[PDLPDEV_EV_COUNT], double out_average[PDLPDEV_EV_COUNT], int32_t* evaluated)
 {
   *evaluated = 0;
   HIP_TRY(hipSetDevice(ctx->device));
+  if (ctx->halpern && ctx->small_resident && !ctx->comm) {
+    // the resident Halpern loop: the loop kernel with its target, the one-workgroup evaluation of T(z^k) right behind it (it computes
+    // the l-infinity residuals itself, so that request stays on this path), one synchronisation for both
+    roctx::Range range("pdlp: Halpern steps + evaluation (resident)");
+    const bool want_linf = rq->eps_p >= 0.0 && rq->eps_d >= 0.0;
+    TRY(resident_halpern_period(ctx, target_steps, rq->rule_finite, want_linf ? 1 : 0, rq->eps_p, rq->eps_d, evaluated));
+    if (*evaluated) {
+      read_eval(ctx->scal_h + 32, want_linf, out_current);
+      read_eval(ctx->scal_h + 32, want_linf, out_average);
+    }
+    if (ctl) *ctl = *ctx->ctl_h;
+    return 0;
+  }
   const bool dense_unfused = ctx->dense.on && !(ctx->pat.v.dn_pan_ptr != nullptr && ctx->pa.v.dn_own_seg != nullptr);
   const bool eligible = !ctx->comm && !ctx->small_resident && ctx->pa.on && ctx->pat.on && !dense_unfused && ctx->ctl_h_current &&
                         !(rq->eps_p >= 0.0 && rq->eps_d >= 0.0) && ctx->ctl_h->error == 0 && ctx->ctl_h->steps_taken < target_steps;
@@ -1530,7 +1547,7 @@ int pdlpdev_set_halpern(pdlpdev_ctx* ctx, int on)
   if ((on != 0) == ctx->halpern) return 0;
   if (on) {
     if (ctx->comm) return fail(-7, "reflected Halpern mode: not available for a sharded solver");
-    if (ctx->small_resident) return fail(-7, "reflected Halpern mode: the context is on the resident small-LP path (pdlpdev_create_no_resident before its creation)");
+    // (a context on the resident small-LP path runs the mode inside one workgroup: kernels_resident_halpern.hip)
     if (!ctx->scaled) return fail(-1, "pdlpdev_set_halpern: call after pdlpdev_scale_problem");
     if (!ctx->lraty) TRY(dev_alloc(ctx, &ctx->lraty, (size_t)ctx->n));
     if (!ctx->hal) TRY(dev_alloc(ctx, &ctx->hal, 1));
@@ -1555,7 +1572,7 @@ int pdlpdev_spectral_norm(pdlpdev_ctx* ctx, double rel_tol, int32_t max_products
 {
   HIP_TRY(hipSetDevice(ctx->device));
   if (ctx->comm) return fail(-7, "pdlpdev_spectral_norm: single GPU only");
-  if (ctx->small_resident) return fail(-7, "pdlpdev_spectral_norm: not on the resident small-LP path");
+  // (a resident context keeps its stream-layout arrays: launch_plain runs the layout's plain products on it, as pdlpdev_compute_aty does)
   hipStream_t s = ctx->stream;
   const int n   = ctx->n;
   double* v = ctx->tmp_n;  // the normalised iterate; A v -> tmp_m; A^T A v -> xbar

@@ -443,9 +443,13 @@ int pdlpdev_major_eval(pdlpdev_ctx* ctx, int average_mode, int rc_rule_finite_bo
   const bool want_linf = eps_rel_primal >= 0.0 && eps_rel_dual >= 0.0;
   if (ctx->halpern) {
     // one point to evaluate: T(z^k) of the last step, which the step kernels left in the average slots (no sums, no average to form)
-    TRY(enqueue_halpern_eval(ctx, rc_rule_finite_bounds, eps_rel_primal, eps_rel_dual, 0));
-    TRY(fetch_scalars(ctx, 41));
-    ctx->stat_loop_syncs += 1;
+    if (ctx->small_resident && !ctx->comm) {  // (one workgroup, results straight into the pinned block)
+      TRY(resident_halpern_eval(ctx, rc_rule_finite_bounds, want_linf ? 1 : 0, eps_rel_primal, eps_rel_dual));
+    } else {
+      TRY(enqueue_halpern_eval(ctx, rc_rule_finite_bounds, eps_rel_primal, eps_rel_dual, 0));
+      TRY(fetch_scalars(ctx, 41));
+      ctx->stat_loop_syncs += 1;
+    }
     read_eval(ctx->scal_h + 32, want_linf, out_average);
     read_eval(ctx->scal_h + 32, want_linf, out_current);
     return 0;

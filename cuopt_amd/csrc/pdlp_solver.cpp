@@ -820,6 +820,7 @@ void cuoptamd_default_settings(cuoptamd_settings* s)
   for (double& t : s->accept_tolerance) t = 1e-4;
   s->relative_primal_tolerance_factor = s->relative_dual_tolerance_factor = -1.0;
   s->batch_lanes                      = 0;
+  s->halpern_resident                 = 0;
 }
 
 // Plain parallel counting sort by column (small matrices, and the fallback of the blocked one below).  Thread t owns a
@@ -1177,7 +1178,7 @@ int cuoptamd_solver_create(cuoptamd_solver** out, const cuoptamd_lp* lp, const c
   if (ag.an && setup_rc == 0) {
     // single GPU: the analysis' device arrays become the context's
     pdlpdev_create_hint(0);
-    pdlpdev_create_no_resident(hyper->algorithm == 1);
+    pdlpdev_create_no_resident(hyper->algorithm == 1 && !settings->halpern_resident);
     pdlpdev_create_batch_lanes(settings->batch_lanes);
     int rc = pdlpdev_create_from_analysis(&s->dev, ag.an, L->c, L->lo, L->hi, L->lb, L->ub);
     pdlpdev_create_no_resident(0);  // (consumed by the creation; not left behind when it failed early)
@@ -1219,7 +1220,7 @@ int cuoptamd_solver_create(cuoptamd_solver** out, const cuoptamd_lp* lp, const c
   }
   {
     pdlpdev_create_hint(world > 1 || comm_id != nullptr);
-    pdlpdev_create_no_resident(hyper->algorithm == 1);
+    pdlpdev_create_no_resident(hyper->algorithm == 1 && !settings->halpern_resident);
     pdlpdev_create_batch_lanes(settings->batch_lanes);
     int rc = setup_rc;
     if (rc == 0)
@@ -2218,6 +2219,7 @@ static int shared_matrix_batch_solve(int32_t count, const cuoptamd_lp* lps, cons
 static int small_lp_batch_solve(int32_t count, const cuoptamd_lp* lps, const cuoptamd_hyper* hyper, const cuoptamd_settings* settings, int device,
                                 int max_threads, cuoptamd_result* results, double** x, double** y, double** rc)
 {
+  if (hyper->algorithm == 1 && settings->halpern_resident) return kNotShared;  // (no K-workgroup batch in that mode: each LP runs its own resident loop)
   for (int i = 0; i < count; ++i) {
     const cuoptamd_lp& L = lps[i];
     if (L.m <= 0 || L.n <= 0 || !L.offsets || !pdlpdev_resident_size(L.m, L.n, L.offsets[L.m])) return kNotShared;

@@ -1,0 +1,66 @@
+// What the two translation units of the resident small-LP path share (kernels_resident.hip: the averaging loop, its evaluation and the
+// K-workgroup batch; kernels_resident_halpern.hip: the reflected-Halpern loop and its evaluation): the row sum every one-workgroup
+// kernel uses, the three tiers, and the argument record + row walker of the one-workgroup evaluation.
+#pragma once
+#include "pdlp_ctx.hpp"
+#include "pdlp_layouts.hpp"
+
+// prod[a..b) added up strictly left to right; eight LDS reads are in flight before the first add
+__device__ __forceinline__ double lds_row_sum(const double* prod, int a, int b)
+{
+  double acc = 0.0;
+  for (int k = a; k < b; k += 8) {
+    double p[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) p[i] = prod[k + i < b ? k + i : a];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) acc = k + i < b ? acc + p[i] : acc;
+  }
+  return acc;
+}
+
+// the three instantiations, smallest first: (lanes, elements per lane, nonzeros per lane)
+struct ResidentTier { int T, Q, U; };
+constexpr ResidentTier kResidentTiers[3] = {{256, 2, 8}, {512, 2, 16}, {512, 4, 8}};
+inline size_t resident_lds_bytes(int tier)
+{
+  const ResidentTier& r = kResidentTiers[tier];
+  return sizeof(double) * (size_t)r.T * (7 * r.Q + r.U);
+}
+
+// single-workgroup head of a major iteration (pdlpdev_major_eval) for LPs on the resident path
+struct MajorSmallArgs {
+  int m, n, mode, rule_finite, want_linf;  // mode 0 / 1 / 2: the average k_major_small forms; 3: none, the average slots are evaluated
+  double eps_p, eps_d;                     //                 as the Halpern loop left them (k_major_small_halpern)
+  const int32_t *a_off, *a_idx, *at_off, *at_idx;
+  const double *a_val, *at_val;
+  pdlpdev_ctl* ctl;
+  double *x0, *x1, *y0, *y1, *sumx, *sumy, *avgx, *avgy;
+  const double *dr, *dc, *c_u, *lb_u, *ub_u, *lo_u, *hi_u;
+  double *linf_m, *linf_n, *ax_cur, *ax_avg, *aty_cur, *aty_avg, *rc_cur, *rc_avg;
+  double* sc;  // current at sc[0..9), average at sc[32..41)  (pinned host memory: no read-back copy)
+  int guard_target = -1;  // >= 0 (evaluation enqueued right behind the attempts of a small-LP batch): only if the attempts reached this
+                          // accepted-step count or raised the step-size error -- i.e. only if a major iteration is what comes next
+};
+constexpr int kMajorThreads = 1024;
+// M vec for a matrix of <= 8192 nonzeros: all products in parallel into LDS, then every row is added up left to
+// right by one lane (same order as every other SpMV here)
+template <class Epi, int NQ>
+__device__ __forceinline__ void small_rows(int rows, const int32_t* __restrict__ off, const int32_t* __restrict__ idx,
+                                           const double* __restrict__ val, const double* vec, double* prod, Epi& e,
+                                           double (&acc)[NQ])
+{
+  const int nnz = off[rows];
+  for (int k = threadIdx.x; k < nnz; k += kMajorThreads) prod[k] = val[k] * vec[idx[k]];
+  __syncthreads();
+  for (int r = threadIdx.x; r < rows; r += kMajorThreads) e.row(r, lds_row_sum(prod, off[r], off[r + 1]), acc);
+}
+inline MajorSmallArgs major_args(const pdlpdev_ctx* ctx, int average_mode, int rc_rule_finite_bounds, int want_linf, double eps_rel_primal, double eps_rel_dual)
+{
+  return MajorSmallArgs{ctx->m, ctx->n, average_mode, rc_rule_finite_bounds, want_linf, eps_rel_primal, eps_rel_dual,
+                        ctx->a_off, ctx->a_idx, ctx->at_off, ctx->at_idx, ctx->a_val, ctx->at_val, ctx->ctl,
+                        ctx->x[0], ctx->x[1], ctx->y[0], ctx->y[1], ctx->sumx, ctx->sumy, ctx->avgx, ctx->avgy,
+                        ctx->dr, ctx->dc, ctx->c_u, ctx->lb_u, ctx->ub_u, ctx->lo_u, ctx->hi_u, ctx->tmp_m, ctx->tmp_n,
+                        ctx->ax_u[PDLPDEV_CURRENT], ctx->ax_u[PDLPDEV_AVERAGE], ctx->aty_u[PDLPDEV_CURRENT],
+                        ctx->aty_u[PDLPDEV_AVERAGE], ctx->rc[0], ctx->rc[1], ctx->scal_h};
+}

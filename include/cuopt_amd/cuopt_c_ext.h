@@ -8,6 +8,10 @@
  *                            simplex-grade tolerances (1e-8) with the requested tolerances as acceptance set
  *                            (cuoptamd_settings::accept_tolerance).  -1 (default) = the key simplex_grade of the
  *                            CUOPT_AMD_TUNE environment string (CUOPT_AMD_TUNE=simplex_grade=0), else on.
+ *   CUOPT_AMD_HALPERN_RESIDENT  1 / 0 (default 0): under CUOPT_AMD_PDLP_SOLVER_MODE_HALPERN1 an LP of resident size (m, n <= 2048,
+ *                            nnz <= 4096 ... 8192) runs a whole period of steps inside one workgroup with the LP on chip
+ *                            (cuoptamd_settings::halpern_resident).  Larger LPs, and every LP under CUOPT_AMD_SMALL=0, take the
+ *                            multi-launch kernels; ignored by the other solver modes.  cuOptAmdGetSolveInfo says what ran.
  * Extra value of CUOPT_PDLP_SOLVER_MODE (constants.h stops at CUOPT_PDLP_SOLVER_MODE_FAST1 = 3):
  *   CUOPT_AMD_PDLP_SOLVER_MODE_HALPERN1 = 4: the restarted reflected Halpern iteration with a constant step size
  *                            (cuoptamd_hyper_preset(4), docs/design/04d_halpern_mode.md).  One GPU; infeasibility detection,
@@ -22,6 +26,7 @@
 
 #define CUOPT_AMD_NUM_GPUS "amd_num_gpus"
 #define CUOPT_AMD_SIMPLEX_GRADE "amd_simplex_grade"
+#define CUOPT_AMD_HALPERN_RESIDENT "amd_halpern_resident"
 #define CUOPT_AMD_PDLP_SOLVER_MODE_HALPERN1 4
 
 #ifdef __cplusplus
@@ -36,7 +41,8 @@ cuopt_int_t cuOptAmdGetPdlpStats(cuOptSolution solution, cuoptamd_result* stats)
  * {"engine": "pdlp" | "dual_simplex", "requested_method": "Concurrent|DualSimplex|PDLP", "crossover_requested": bool,
  *  "simplex_grade_emulation": bool, "dual_simplex_consulted": bool, "dual_simplex_status": 1..9 (cuoptamd_dual_simplex),
  *  "crossover": "none" | "dual_simplex_from_the_pdlp_point" | "not_done_..." | "not_needed_vertex_from_the_dual_simplex",
- *  "answered_by": "...", "gpus": N, "iterations": K, "simplex_grade_attempt_iterations": K0}
+ *  "answered_by": "...", "gpus": N, "iterations": K, "simplex_grade_attempt_iterations": K0,
+ *  "halpern_resident": 0 | 1 (the PDLP solver of this call ran the reflected Halpern mode on the resident small-LP path)}
  * (the reference runs its dual simplex / crossover for such requests, LP/solve.cu:383-443,467-547; here an own simplex code on
  * the host -- cuoptamd_dual_simplex[_from], LPs of up to 200 000 rows -- answers DualSimplex requests, races PDLP under
  * Concurrent and crosses PDLP's point over to a vertex; beyond its limits PDLP serves the request, and the call says so

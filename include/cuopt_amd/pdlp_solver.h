@@ -137,6 +137,14 @@ typedef struct cuoptamd_settings {
    * fit its LDS.  Read when the solver is created (reset and clone ignore it; clones share the parent's layouts).  0: the layouts
    * of a solver that never batches, and cuoptamd_batch_create refuses a jagged parent with -7. */
   int32_t batch_lanes;
+  /* Reflected Halpern mode (cuoptamd_hyper::algorithm == 1) only: non-zero lets an LP of resident size run the mode inside one
+   * workgroup with the LP on chip (a whole period of steps in one launch, the evaluation of T(z^k) right behind it: two launches and
+   * one synchronisation per period instead of four launches per step).  Read when the solver is created.  0 (default): the
+   * multi-launch kernels, as before.  An LP that is not of resident size, or CUOPT_AMD_SMALL=0, silently takes the multi-launch
+   * path (cuoptamd_solver_layout says which one runs); ignored when algorithm == 0.  A solver that runs on the resident path has
+   * no clones: cuoptamd_solver_clone answers -7 for it, as for every resident solver (the multi-launch mode 4 can be cloned);
+   * cuoptamd_batch_solve then solves the LPs independently, each in its own resident loop. */
+  int32_t halpern_resident;
 } cuoptamd_settings;
 
 /* additional_termination_information_t (pdlp/solver_solution.hpp:63-103) + run statistics */

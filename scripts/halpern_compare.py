@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Measurements of the restarted reflected-Halpern mode (solver mode 4) against Stable2 -> profiles/r09_halpern.jsonl.
 
-  python scripts/halpern_compare.py [--out FILE] [--only cost|convergence] [--workloads c3,c2,...] [--parent-lib libcuopt.so]
+  python scripts/halpern_compare.py [--out FILE] [--only cost|convergence|small] [--workloads c3,c2,...] [--parent-lib libcuopt.so]
 
 * cost of a step: ms per step in mode 4 against ms per ATTEMPT of Stable2 (solves to a fixed iteration count from a warmed
   solver: wall time over attempted steps, five alternating runs each), plus the per-kernel durations of both modes from
@@ -9,7 +9,12 @@
   holds one library), which is how the step of this tree is compared with the attempt of the commit before it.
 * iterations and wall time to 1e-4 and to 1e-8, mode 4 against Stable2 of the same build, on the synthetic families and the
   golden LPs with more than 50 rows.  Reported whichever way they fall; Stable2 stays the default preset.
-Every record is one JSON line: {"kind": "cost" | "kernels" | "convergence", ...}; --out is written anew by every run.
+* --only small (not part of the default run): the golden LPs of resident size at 1e-4 and 1e-8 in three variants -- mode 4 in the
+  resident one-workgroup loop (halpern_resident = 1), mode 4 on the multi-launch path (--parent-lib: on that build, which is how the
+  commit before the setting is measured), Stable2 -- five alternating rounds, one child process per variant and round; a record
+  per LP and tolerance with all runs, their median and their spread (min, max), plus steps/s of the three loops over 4000
+  steps of 50v-10 at tol = 0, likewise.
+Every record is one JSON line: {"kind": "cost" | "kernels" | "convergence" | "small" | "small_rate", ...}; --out is written anew by every run.
 
 Each leg is a child process of its own under a time limit sized to the leg.  The first leg that fails, is killed by a signal or
 runs out of its time ends the whole run with a non-zero exit: nothing more is started on a GPU that has just shown trouble."""
@@ -71,9 +76,42 @@ def convergence_leg(name, mode, tol, limit):
                 layout=[lay["A"]["layout"], lay["At"]["layout"]])
 
 
+SMALL = ["afiro", "mip-50v-10-free-bound-relaxation", "mip-neos5-free-bound-relaxation", "mip-sudoku-relaxation"]
+
+
+def small_leg(names, mode, resident, limit):
+    """every LP of `names` at 1e-4 and 1e-8 in one process (a warm-up solve of the first LP in front), then the loop's rate on 50v-10"""
+    from cuopt_amd import capi
+    kw = dict(halpern_resident=1) if resident else {}
+    out = {}
+    for i, name in enumerate([names[0]] + names):
+        p = problem(name)
+        for tol in (1e-4, 1e-8):
+            s = capi.Solver(p, mode=mode, tol=tol, iteration_limit=limit, **kw)
+            r = s.advance()
+            out["%s@%g" % (name, tol)] = dict(status=r["status_name"], iterations=r["steps_taken"], restarts=r["num_restarts"], loop_seconds=r["loop_seconds"],
+                                               resident=bool(s.device.layout()["resident"]))
+            s.close()
+    s = capi.Solver(problem(SMALL[1]), mode=mode, tol=0.0, **kw)
+    s.advance(400)
+    t0 = time.perf_counter()
+    s.advance(4000)
+    s.device.call("synchronize")
+    out["rate"] = 4000 / (time.perf_counter() - t0)
+    s.close()
+    return out
+
+
+def summary(values):
+    v = sorted(values)
+    return dict(runs=values, median=v[len(v) // 2], min=v[0], max=v[-1])
+
+
 def child(args):
     leg = json.loads(args.child)
-    if leg["kind"] == "cost":
+    if leg["kind"] == "small":
+        print(json.dumps(small_leg(leg["workloads"], leg["mode"], leg["resident"], leg["limit"])))
+    elif leg["kind"] == "cost":
         print(json.dumps(cost_leg(leg["workload"], leg["mode"], leg["steps"], leg["runs"])))
     else:
         print(json.dumps(convergence_leg(leg["workload"], leg["mode"], leg["tol"], leg["limit"])))
@@ -82,6 +120,8 @@ def child(args):
 def leg_seconds(leg):
     """time limit of a leg: the LP's generation and set-up (a minute at 1e7 nonzeros on a slow host) plus the steps it may take at a
     pessimistic millisecond each"""
+    if leg["kind"] == "small":
+        return 240
     steps = leg["steps"] + 200 if leg["kind"] == "cost" else leg["limit"]
     return 90 + steps // 1000
 
@@ -103,7 +143,7 @@ def run_child(leg, lib=None):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r09_halpern.jsonl"))
-    ap.add_argument("--only", default=None, choices=["cost", "convergence"])
+    ap.add_argument("--only", default=None, choices=["cost", "convergence", "small"])
     ap.add_argument("--workloads", default=None)
     ap.add_argument("--parent-lib", default=None)
     ap.add_argument("--steps", type=int, default=6000)
@@ -131,6 +171,22 @@ def main():
             emit(dict(kind="cost", workload=w, steps=steps, stable2_library="parent" if args.parent_lib else "this build", stable2_ms_per_attempt=stable,
                       halpern_ms_per_step=halpern, ratio_of_medians=sorted(halpern)[2] / sorted(stable)[2]))
             emit(dict(kind="kernels", workload=w, stable2_ms=a["kernels_ms"], halpern_ms=b["kernels_ms"]))
+    if args.only == "small":
+        names = args.workloads.split(",") if args.workloads else SMALL
+        variants = (("halpern_resident", 4, True, None), ("halpern_multi_launch", 4, False, args.parent_lib), ("stable2", 1, False, None))
+        runs = {v[0]: [] for v in variants}
+        for _ in range(5):  # alternating: the variants see the same machine state
+            for key, mode, resident, lib in variants:
+                runs[key].append(run_child(dict(kind="small", workloads=names, mode=mode, resident=resident, limit=args.limit), lib=lib))
+        for w in names:
+            for tol in (1e-4, 1e-8):
+                rec = dict(kind="small", workload=w, tol=tol, multi_launch_library="parent" if args.parent_lib else "this build")
+                for key in runs:
+                    legs = [r["%s@%g" % (w, tol)] for r in runs[key]]
+                    rec[key] = dict(status=legs[0]["status"], iterations=legs[0]["iterations"], restarts=legs[0]["restarts"], resident=legs[0]["resident"],
+                                    same_iterations_in_every_run=len({l["iterations"] for l in legs}) == 1, loop_seconds=summary([l["loop_seconds"] for l in legs]))
+                emit(rec)
+        emit(dict(kind="small_rate", workload=SMALL[1], steps=4000, steps_per_second={key: summary([r["rate"] for r in runs[key]]) for key in runs}))
     if args.only in (None, "convergence"):
         names = args.workloads.split(",") if args.workloads else ["c3", "c2", "hard", "banded", "staircase", "block_angular", "afiro",
                                                                   "mip-50v-10-free-bound-relaxation", "mip-neos5-free-bound-relaxation",
