@@ -638,7 +638,7 @@ struct pdlpdev_batch {
 
 static BatchLp batch_lp_of(const pdlpdev_ctx* c)
 {
-  return BatchLp{c->ctl, c->y[0], c->y[1], c->sumy, c->lo, c->hi, c->x[0], c->x[1], c->aty[0], c->aty[1], c->sumx, c->c, c->lb, c->ub, c->ubd, c->part_a, c->part_at};
+  return BatchLp{c->ctl, c->y[0], c->y[1], c->sumy, c->lo, c->hi, c->x[0], c->x[1], c->aty[0], c->aty[1], c->sumx, c->c, c->lb, c->ub, c->ubd, c->A.part, c->At.part};
 }
 
 // A reset that gives a member row bounds of its own moves its lo / hi (pdlpdev_reset: copy on change): the table the kernels read
@@ -693,8 +693,8 @@ static int batch_enqueue_attempt(pdlpdev_batch* b, hipEvent_t* ev = nullptr)
     JagView ajv = A.jv, tjv = T.jv;
     int aP = A.P, tP = T.P;
     void* a0[] = {&b->lp_dev, &n, &b->xK};
-    void* a1[] = {&aw, &arow0, &c0->ha_off, &c0->ha_idx, &c0->ha_val, &b->lp_dev, &b->xK, &b->yK};
-    void* a2[] = {&tw, &trow0, &c0->hat_off, &c0->hat_idx, &c0->hat_val, &b->lp_dev, &b->yK};
+    void* a1[] = {&aw, &arow0, &c0->A.hot.off, &c0->A.hot.idx, &c0->A.hot.val, &b->lp_dev, &b->xK, &b->yK};
+    void* a2[] = {&tw, &trow0, &c0->At.hot.off, &c0->At.hot.idx, &c0->At.hot.val, &b->lp_dev, &b->yK};
     void* j1[] = {&ajv, &aP, &b->lp_dev, &b->xK, &b->yK};
     void* j2[] = {&tjv, &tP, &b->lp_dev, &b->yK};
     void* a3[] = {&b->dargs_dev};
@@ -713,12 +713,12 @@ static int batch_enqueue_attempt(pdlpdev_batch* b, hipEvent_t* ev = nullptr)
   kb_primal<K><<<pgrid, kBT, 0, s>>>(b->lp_dev, n, b->xK);
   if (A.jag && A.jv.waves == 16) kbj_a_dual<K, 16><<<jgrid(A), 1024, A.lds, s>>>(A.jv, A.P, b->lp_dev, b->xK, b->yK);
   else if (A.jag) kbj_a_dual<K, 8><<<jgrid(A), 512, A.lds, s>>>(A.jv, A.P, b->lp_dev, b->xK, b->yK);
-  else if (ap) kb_a_dual<K, 8><<<aw, kBT, 0, s>>>(aw, arow0, c0->ha_off, c0->ha_idx, c0->ha_val, b->lp_dev, b->xK, b->yK);
-  else kb_a_dual<K, 4><<<aw, kBT, 0, s>>>(aw, arow0, c0->ha_off, c0->ha_idx, c0->ha_val, b->lp_dev, b->xK, b->yK);
+  else if (ap) kb_a_dual<K, 8><<<aw, kBT, 0, s>>>(aw, arow0, c0->A.hot.off, c0->A.hot.idx, c0->A.hot.val, b->lp_dev, b->xK, b->yK);
+  else kb_a_dual<K, 4><<<aw, kBT, 0, s>>>(aw, arow0, c0->A.hot.off, c0->A.hot.idx, c0->A.hot.val, b->lp_dev, b->xK, b->yK);
   if (T.jag && T.jv.waves == 16) kbj_at_step<K, 16><<<jgrid(T), 1024, T.lds, s>>>(T.jv, T.P, b->lp_dev, b->yK);
   else if (T.jag) kbj_at_step<K, 8><<<jgrid(T), 512, T.lds, s>>>(T.jv, T.P, b->lp_dev, b->yK);
-  else if (tp) kb_at_step<K, 8><<<tw, kBT, 0, s>>>(tw, trow0, c0->hat_off, c0->hat_idx, c0->hat_val, b->lp_dev, b->yK);
-  else kb_at_step<K, 4><<<tw, kBT, 0, s>>>(tw, trow0, c0->hat_off, c0->hat_idx, c0->hat_val, b->lp_dev, b->yK);
+  else if (tp) kb_at_step<K, 8><<<tw, kBT, 0, s>>>(tw, trow0, c0->At.hot.off, c0->At.hot.idx, c0->At.hot.val, b->lp_dev, b->yK);
+  else kb_at_step<K, 4><<<tw, kBT, 0, s>>>(tw, trow0, c0->At.hot.off, c0->At.hot.idx, c0->At.hot.val, b->lp_dev, b->yK);
   k_step_decision_batch<<<K, 1024, 0, s>>>(b->dargs_dev);
   LAUNCH_CHECK();
   return 0;
@@ -822,10 +822,8 @@ int pdlpdev_clone_shared(pdlpdev_ctx** out, pdlpdev_ctx* parent)
     TRY(dev_alloc(c, &c->aty_u[i], n));
   }
   TRY(dev_alloc(c, &c->rc_scratch, n));
-  const int pa_w = std::max({c->a_nb, c->pa.on ? c->pa.v.W : 0, c->ja.on ? c->ja.v.nblk + c->ja.v.nlong : 0, c->pba.on ? c->pba.v.B : 0, 1});
-  const int pt_w = std::max({c->at_nb, c->pat.on ? c->pat.v.W : 0, c->jat.on ? c->jat.v.nblk + c->jat.v.nlong : 0, c->pbat.on ? c->pbat.v.B : 0, 1});
-  TRY(dev_alloc(c, &c->part_a, (size_t)8 * pa_w));
-  TRY(dev_alloc(c, &c->part_at, (size_t)8 * pt_w));
+  TRY(dev_alloc(c, &c->A.part, (size_t)8 * c->A.max_partials()));
+  TRY(dev_alloc(c, &c->At.part, (size_t)8 * c->At.max_partials()));
   TRY(dev_alloc(c, &c->part_g, (size_t)8 * 2048));
   TRY(dev_alloc(c, &c->scal, kScalars));
   TRY(dev_alloc(c, &c->ctl, 1));
@@ -846,8 +844,8 @@ int pdlpdev_batch_create(pdlpdev_batch** out, pdlpdev_ctx** ctx, int K)
       if (ctx[q] == ctx[l]) return fail(-1, "pdlpdev_batch_create: LP %d and LP %d are the same context (two lanes would share one set of iterates)", q, l);
   for (int l = 0; l < K; ++l) {
     pdlpdev_ctx* c = ctx[l];
-    if (!c || c->ha_off != c0->ha_off || c->hat_off != c0->hat_off || c->pa.v.row0 != c0->pa.v.row0 || c->ja.v.row0 != c0->ja.v.row0 ||
-        c->jat.v.row0 != c0->jat.v.row0 || c->ja.v.val != c0->ja.v.val || c->jat.v.val != c0->jat.v.val || c->stream != c0->stream)
+    if (!c || c->A.hot.off != c0->A.hot.off || c->At.hot.off != c0->At.hot.off || c->A.pan.v.row0 != c0->A.pan.v.row0 || c->A.jag.v.row0 != c0->A.jag.v.row0 ||
+        c->At.jag.v.row0 != c0->At.jag.v.row0 || c->A.jag.v.val != c0->A.jag.v.val || c->At.jag.v.val != c0->At.jag.v.val || c->stream != c0->stream)
       return fail(-1, "pdlpdev_batch_create: the contexts do not share one matrix (pdlpdev_clone_shared)");
   }
   for (int l = 0; l < K; ++l)
@@ -858,19 +856,21 @@ int pdlpdev_batch_create(pdlpdev_batch** out, pdlpdev_ctx** ctx, int K)
   // and whose per-block reduction the batched products reproduce
   pdlpdev_batch::Side side[2];
   HIP_TRY(hipSetDevice(c0->device));
+  const pdlpdev_ctx::MatrixSide* const matrix[2] = {&c0->A, &c0->At};
   for (int t = 0; t < 2; ++t) {
-    const pdlpdev_ctx::Panels& P = t ? c0->pat : c0->pa;
-    const pdlpdev_ctx::Jag& Jg = t ? c0->jat : c0->ja;
-    const bool jag = Jg.on, pb = t ? c0->pbat.on : c0->pba.on;
-    const int nlong = t ? c0->at_nlong : c0->a_nlong;
+    const pdlpdev_ctx::MatrixSide& M = *matrix[t];
+    const pdlpdev_ctx::Panels& P = M.pan;
+    const pdlpdev_ctx::Jag& Jg = M.jag;
+    const bool jag = Jg.on, pb = M.pb.on;
+    const int nlong = M.nlong;
     if (jag && c0->batch_lanes < K)
       return fail(-7, "pdlpdev_batch_create: not eligible (the %s side is in the jagged layout: lockstep batches of %d LPs on it need a parent created "
-                      "with batch_lanes >= %d, cuoptamd_settings::batch_lanes; this one has %d)", t ? "A^T" : "A", K, K, c0->batch_lanes);
+                      "with batch_lanes >= %d, cuoptamd_settings::batch_lanes; this one has %d)", M.name, K, K, c0->batch_lanes);
     bool ok = !pb && nlong == 0;
     if (ok && jag) {
       if (Jg.v.nlong != 0 || Jg.v.dense_add || Jg.v.nblk <= 0)
         return fail(-7, "pdlpdev_batch_create: not eligible (the %s side is jagged with %d rows of more than %d entries%s: the jagged lockstep "
-                        "products serve blocks of short rows only)", t ? "A^T" : "A", Jg.v.nlong, kLongRow, Jg.v.dense_add ? " and dense segments" : "");
+                        "products serve blocks of short rows only)", M.name, Jg.v.nlong, kLongRow, Jg.v.dense_add ? " and dense segments" : "");
       {  // the strips' pitch: odd (conflict-free transposition), at least the largest block's rows
         std::vector<int32_t> r0((size_t)Jg.v.nblk + 1);
         HIP_TRY(hipMemcpyAsync(r0.data(), Jg.v.row0, r0.size() * sizeof(int32_t), hipMemcpyDeviceToHost, c0->stream));
@@ -887,13 +887,13 @@ int pdlpdev_batch_create(pdlpdev_batch** out, pdlpdev_ctx** ctx, int K)
       ok      = !P.v.seg && !P.v.own_row && !P.v.any_long && !P.v.dense_add;
       side[t] = pdlpdev_batch::Side{P.v.W, P.v.row0, true};
     } else if (ok) {
-      side[t] = pdlpdev_batch::Side{t ? c0->at_nb : c0->a_nb, t ? c0->at_rb : c0->a_rb, false};
+      side[t] = pdlpdev_batch::Side{M.nb, M.rb, false};
       ok      = side[t].W > 0 && side[t].row0 != nullptr;
     }
     if (!ok || c0->dense.on || c0->comm || c0->small_resident)
       return fail(-7, "pdlpdev_batch_create: not eligible (%s side: %s; the batched products reproduce the reductions of the row-sum panels, of the CSR stream "
                       "kernels and of the jagged layout: both matrices in one of these layouts, no row of more than %d entries, no dense segments, one "
-                      "GPU, not the resident small-LP loop)", t ? "A^T" : "A",
+                      "GPU, not the resident small-LP loop)", M.name,
                       pb ? "gather-free layout" : nlong ? "rows longer than kLongRow" : P.on ? "panels of the long-tail / own-row variant" : "CSR stream", kLongRow);
   }
   {
@@ -905,8 +905,8 @@ int pdlpdev_batch_create(pdlpdev_batch** out, pdlpdev_ctx** ctx, int K)
     int* bad = flag.p;
     HIP_TRY(hipMemsetAsync(bad, 0, sizeof(int), c0->stream));
     // (the jagged products walk a row in its CSR order, as the single kernel does: no condition there)
-    if (!side[0].jag) kb_check_sorted<<<2048, 256, 0, c0->stream>>>(c0->m, c0->ha_off, c0->ha_idx, bad);
-    if (!side[1].jag) kb_check_sorted<<<2048, 256, 0, c0->stream>>>(c0->n, c0->hat_off, c0->hat_idx, bad);
+    if (!side[0].jag) kb_check_sorted<<<2048, 256, 0, c0->stream>>>(c0->m, c0->A.hot.off, c0->A.hot.idx, bad);
+    if (!side[1].jag) kb_check_sorted<<<2048, 256, 0, c0->stream>>>(c0->n, c0->At.hot.off, c0->At.hot.idx, bad);
     LAUNCH_CHECK();
     int h = 0;
     HIP_TRY(hipMemcpyAsync(&h, bad, sizeof(int), hipMemcpyDeviceToHost, c0->stream));
@@ -931,7 +931,7 @@ int pdlpdev_batch_create(pdlpdev_batch** out, pdlpdev_ctx** ctx, int K)
     pdlpdev_ctx* c = ctx[l];
     b->ctx[l]      = c;
     h[l]     = batch_lp_of(c);
-    dargs[l] = pdlpdev_decision_args{c->ctl, c->part_a, side[0].W, c->part_at, side[1].W, c->sp};
+    dargs[l] = pdlpdev_decision_args{c->ctl, c->A.part, side[0].W, c->At.part, side[1].W, c->sp};
     c->batches_alive += 1;
   }
   HIP_TRY(hipMalloc((void**)&b->lp_dev, K * sizeof(BatchLp)));

@@ -495,9 +495,9 @@ int upload_panels(pdlpdev_ctx* c, pdlpdev_ctx::Panels* dst, const PanelHost& h, 
 // and the slower one is dropped.  This is how the structural rule of 'auto' (gather_working_set) was calibrated; it is
 // not the default because two close timings make the choice -- and with it the grouping of the reduction partials, the
 // step sizes and the iteration count -- differ from run to run.
-int pick_layout(pdlpdev_ctx* c, pdlpdev_ctx::Panels* pn, int rows, int nb, const int32_t* rb, const int32_t* off,
-                       const int32_t* idx, const double* val, const double* vec, double* out, const char* name)
+int pick_layout(pdlpdev_ctx* c, pdlpdev_ctx::MatrixSide* side, const double* vec, double* out)
 {
+  pdlpdev_ctx::Panels* pn = &side->pan;
   if (!pn->on) return 0;
   hipEvent_t e0, e1;
   HIP_TRY(hipEventCreate(&e0));
@@ -508,7 +508,7 @@ int pick_layout(pdlpdev_ctx* c, pdlpdev_ctx::Panels* pn, int rows, int nb, const
       for (int rep = 0; rep < 4; ++rep) {
         if (rep == 1) HIP_TRY(hipEventRecord(e0, c->stream));
         if (which == 0)
-          k_spmv_plain<<<stream_grid(nb), kBlock, 0, c->stream>>>(nb, rb, off, idx, val, vec, out, (const double*)nullptr);
+          k_spmv_plain<<<stream_grid(side->nb), kBlock, 0, c->stream>>>(side->nb, side->rb, side->hot.off, side->hot.idx, side->hot.val, vec, out, (const double*)nullptr);
         else
           (pn->v.seg ? k_panel_plain<true> : k_panel_plain<false>)<<<pn->v.W, kPanelThreads, 0, c->stream>>>(pn->v, vec, out);
       }
@@ -523,9 +523,8 @@ int pick_layout(pdlpdev_ctx* c, pdlpdev_ctx::Panels* pn, int rows, int nb, const
     }
   (void)hipEventDestroy(e0), (void)hipEventDestroy(e1);
   if (getenv("CUOPT_AMD_TIMING"))
-    fprintf(stderr, "[cuopt_amd setup]   layout %-3s: stream %.1f us, panels %.1f us -> %s\n", name, ms_stream * 1e3 / 3,
+    fprintf(stderr, "[cuopt_amd setup]   layout %-3s: stream %.1f us, panels %.1f us -> %s\n", side->name, ms_stream * 1e3 / 3,
             ms_panel * 1e3 / 3, ms_stream <= ms_panel ? "stream" : "panels");
   if (ms_stream <= ms_panel) pn->on = false;
-  (void)rows;
   return 0;
 }

@@ -299,7 +299,7 @@ __global__ void __launch_bounds__(kMajorThreads) k_major_small_batch(const Major
 // ---- one LP: the small-LP branches of pdlpdev_run / pdlpdev_major_eval ----------------------------------------------------------------
 static SmallView small_view(const pdlpdev_ctx* ctx)
 {
-  return SmallView{ctx->m, ctx->n, (int)ctx->nnz, ctx->a_off, ctx->a_idx, ctx->at_off, ctx->at_idx, ctx->a_val, ctx->at_val,
+  return SmallView{ctx->m, ctx->n, (int)ctx->nnz, ctx->A.full.off, ctx->A.full.idx, ctx->At.full.off, ctx->At.full.idx, ctx->A.full.val, ctx->At.full.val,
                    ctx->c, ctx->lb, ctx->ub, ctx->lo, ctx->hi, ctx->x[0], ctx->x[1], ctx->y[0], ctx->y[1], ctx->aty[0],
                    ctx->aty[1], ctx->sumx, ctx->sumy};
 }
@@ -505,7 +505,7 @@ int pdlpdev_small_batch_create(pdlpdev_small_batch** out, pdlpdev_ctx** ctx, int
   for (int l = 0; l < K; ++l) {
     const pdlpdev_ctx* c = ctx[l];
     if (!c) return fail(-1, "pdlpdev_small_batch_create: null context");
-    if (!c->small_resident || c->comm || c->pat.on || c->jat.on || c->pbat.on || c->dense.on)
+    if (!c->small_resident || c->comm || c->At.layout() != pdlpdev_ctx::MatrixSide::kStream || c->dense.on)
       return fail(-7, "pdlpdev_small_batch_create: LP %d is not on the resident small-LP path", l);
     if (c->halpern)  // (the batch's loop, evaluation and restart are the averaging iteration's)
       return fail(-7, "pdlpdev_small_batch_create: LP %d is in reflected Halpern mode, which has no K-workgroup batch (solve them one after the other)", l);
@@ -521,7 +521,7 @@ int pdlpdev_small_batch_create(pdlpdev_small_batch** out, pdlpdev_ctx** ctx, int
   for (int l = 0; l < K; ++l) {
     b->tier.push_back(resident_tier(ctx[l]->m, ctx[l]->n, ctx[l]->nnz));
     b->major_lds = std::max(b->major_lds, sizeof(double) * (size_t)std::max<int64_t>(ctx[l]->nnz, 1));
-    blocks += std::max(ctx[l]->at_nb, std::min(grid_for(std::max(ctx[l]->n, ctx[l]->m)), kGenericBlocks));
+    blocks += std::max(ctx[l]->At.nb, std::min(grid_for(std::max(ctx[l]->n, ctx[l]->m)), kGenericBlocks));
   }
   b->at_blocks_cap = blocks;
   auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
@@ -679,8 +679,8 @@ int pdlpdev_small_batch_prepare(pdlpdev_small_batch* b, const int32_t* clear_err
     if (ce || sw) b->ops[nops++] = CtlOp{b->ctx[l]->ctl, ce ? 1 : 0, sw ? 1 : 0, sw ? primal_weight[l] : 0.0};
     if (compute_aty && compute_aty[l]) {
       pdlpdev_ctx* c = b->ctx[l];
-      b->at[l]       = StreamAtCurArgs{c->at_nb, c->at_rb, c->hat_off, c->hat_idx, c->hat_val, c->ctl, c->y[0], c->y[1], c->aty[0], c->aty[1]};
-      for (int q = 0; q < c->at_nb; ++q) b->blk[blocks++] = make_int2(l, q);
+      b->at[l]       = StreamAtCurArgs{c->At.nb, c->At.rb, c->At.hot.off, c->At.hot.idx, c->At.hot.val, c->ctl, c->y[0], c->y[1], c->aty[0], c->aty[1]};
+      for (int q = 0; q < c->At.nb; ++q) b->blk[blocks++] = make_int2(l, q);
       ++nat;
     }
   }

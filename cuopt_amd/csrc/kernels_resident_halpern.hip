@@ -243,7 +243,7 @@ __global__ void __launch_bounds__(kMajorThreads) k_major_small_halpern(MajorSmal
 
 static HalpernSmallView halpern_view(const pdlpdev_ctx* ctx)
 {
-  return HalpernSmallView{ctx->m, ctx->n, (int)ctx->nnz, ctx->a_off, ctx->a_idx, ctx->at_off, ctx->at_idx, ctx->a_val, ctx->at_val,
+  return HalpernSmallView{ctx->m, ctx->n, (int)ctx->nnz, ctx->A.full.off, ctx->A.full.idx, ctx->At.full.off, ctx->At.full.idx, ctx->A.full.val, ctx->At.full.val,
                           ctx->c, ctx->lb, ctx->ub, ctx->lo, ctx->hi, ctx->x[0], ctx->x[1], ctx->y[0], ctx->y[1], ctx->aty[0],
                           ctx->aty[1], ctx->lrx, ctx->lry, ctx->lraty, ctx->avgx, ctx->avgy};
 }

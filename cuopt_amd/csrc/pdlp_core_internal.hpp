@@ -10,7 +10,6 @@ int fetch_scalars(pdlpdev_ctx* ctx, int count);         // scal[0..count) -> sca
 int fetch_ctl(pdlpdev_ctx* ctx, pdlpdev_ctl* out);      // the control block -> ctl_h (and *out)
 void launch_plain(pdlpdev_ctx* ctx, int transpose, const double* vec, double* out);   // out = A vec / A^T vec in the side's layout
 void launch_at_cur(pdlpdev_ctx* ctx, double* out_override, int use_next);             // A^T y of the current (next) iterate
-void dense_part(pdlpdev_ctx* ctx, int transpose, const double* v0, const double* v1, int mode, int in_loop);  // the dense segments' share
 // the kernels of pdlpdev_major_eval, nothing read back (pdlp_eval.hip).  guard != 0: for pdlpdev_run_period -- every kernel is empty unless
 // the attempts in front reached their target, and the last one leaves the control block in scal[kCtlSlot ..)
 int enqueue_major_eval(pdlpdev_ctx* ctx, int average_mode, int rc_rule_finite_bounds, double eps_rel_primal, double eps_rel_dual, int guard);
@@ -19,10 +18,6 @@ void read_major_eval(pdlpdev_ctx* ctx, double* out_current, double* out_average)
 int enqueue_halpern_eval(pdlpdev_ctx* ctx, int rc_rule_finite_bounds, double eps_rel_primal, double eps_rel_dual, int guard);
 void launch_restart_current(pdlpdev_ctx* ctx, int g);  // k_restart(CURRENT, scaled distances) -> part_g
 }
-
-// partial sums one product's epilogue leaves, by the side's layout
-static inline int dual_partials(const pdlpdev_ctx* ctx) { return ctx->pba.on ? ctx->pba.v.B : ctx->ja.on ? ctx->ja.v.nblk + ctx->ja.v.nlong : ctx->pa.on ? ctx->pa.v.W : ctx->a_nb; }
-static inline int step_partials(const pdlpdev_ctx* ctx) { return ctx->pbat.on ? ctx->pbat.v.B : ctx->jat.on ? ctx->jat.v.nblk + ctx->jat.v.nlong : ctx->pat.on ? ctx->pat.v.W : ctx->at_nb; }
 
 __global__ void __launch_bounds__(kBlock)
 k_flush_average(int n, int m, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ x0, const double* __restrict__ x1, const double* __restrict__ y0,

@@ -115,9 +115,7 @@ struct LayoutSide {
   bool device = false;    // an analysed matrix without dense segments: the live gather set is counted and the layouts built there
   bool skip_jag = false;  // the analysis' sampled estimate already rules the jagged layout out
   const std::vector<int32_t>* first_seg = nullptr;  // A's dense segments (host panels)
-  pdlpdev_ctx::Jag* jag = nullptr;  // the side's layout slots
-  pdlpdev_ctx::Pb* pb = nullptr;
-  pdlpdev_ctx::Panels* pan = nullptr;
+  pdlpdev_ctx::MatrixSide* side = nullptr;  // the context's side: its layout slots are what the walk fills
   std::function<void(const std::string&)> lap;
   // what the walk leaves: the host constructions (upload_side takes them to the device), the live gather set once counted, and why
   // the gather-free layout turned the matrix away
@@ -166,7 +164,7 @@ int want_panels(pdlpdev_ctx* ctx, const LayoutPolicy& P, LayoutSide& s, bool* wa
 int side_jag(pdlpdev_ctx* ctx, const LayoutPolicy& P, LayoutSide& s)
 {
   const int mode = P.mode == LayoutPolicy::kJag ? 1 : 0;
-  const int rc   = s.device && P.jag_device ? build_jag_device(ctx, s.jag, s.rows, s.cols, s.off, s.d_off, s.d_idx, s.d_val, mode, ctx->cus, ctx->batch_lanes) : 1;
+  const int rc   = s.device && P.jag_device ? build_jag_device(ctx, &s.side->jag, s.rows, s.cols, s.off, s.d_off, s.d_idx, s.d_val, mode, ctx->cus, ctx->batch_lanes) : 1;
   if (rc == 1) s.jh = build_jag(s.rows, s.cols, s.off, s.host_idx(), mode, ctx->cus, ctx->batch_lanes);
   s.lap(std::string("jag ") + s.name);
   return rc < 0 ? rc : 0;
@@ -175,7 +173,7 @@ int side_jag(pdlpdev_ctx* ctx, const LayoutPolicy& P, LayoutSide& s)
 int side_pb(pdlpdev_ctx* ctx, const LayoutPolicy& P, LayoutSide& s)
 {
   const bool forced = P.mode == LayoutPolicy::kPb;
-  const int rc      = s.device && P.pb_device ? build_pb_device(ctx, s.pb, s.rows, s.cols, s.off, s.d_off, s.d_idx, ctx->cus, forced, &s.why) : 1;
+  const int rc      = s.device && P.pb_device ? build_pb_device(ctx, &s.side->pb, s.rows, s.cols, s.off, s.d_off, s.d_idx, ctx->cus, forced, &s.why) : 1;
   if (rc == 1) {
     s.pbh = build_pb(s.rows, s.cols, s.off, s.host_idx(), ctx->cus, forced);
     s.why = s.pbh.why;
@@ -187,7 +185,7 @@ int side_pb(pdlpdev_ctx* ctx, const LayoutPolicy& P, LayoutSide& s)
 int side_panels(pdlpdev_ctx* ctx, const LayoutPolicy& P, LayoutSide& s)
 {
   const bool force = P.mode != LayoutPolicy::kTimed;  // (timed: only where the panels apply at all; pick_layout times them)
-  const int rc     = s.device ? build_panels_device(ctx, s.pan, s.rows, s.cols, s.off, s.d_off, s.d_idx, s.d_val, P.slab_bytes, force) : 1;
+  const int rc     = s.device ? build_panels_device(ctx, &s.side->pan, s.rows, s.cols, s.off, s.d_off, s.d_idx, s.d_val, P.slab_bytes, force) : 1;
   if (rc == 1) s.ph = build_panels(s.rows, s.cols, s.off, s.host_idx(), P.slab_bytes, force, s.first_seg);
   s.lap(std::string("panels ") + s.name);
   return rc < 0 ? rc : 0;
@@ -197,12 +195,12 @@ int side_panels(pdlpdev_ctx* ctx, const LayoutPolicy& P, LayoutSide& s)
 int layout_walk(pdlpdev_ctx* ctx, const LayoutPolicy& P, LayoutSide& s)
 {
   if (P.try_jag() && !s.skip_jag) TRY(side_jag(ctx, P, s));
-  if (s.jh.ok || s.jag->on) return 0;
+  if (s.jh.ok || s.side->jag.on) return 0;
   bool panels = false;
   if (P.want_pb(s.cols)) {
     if (P.mode != LayoutPolicy::kPb) TRY(want_panels(ctx, P, s, &panels));
     if (P.mode == LayoutPolicy::kPb || panels) TRY(side_pb(ctx, P, s));
-    if (s.pbh.ok || s.pb->on) return 0;
+    if (s.pbh.ok || s.side->pb.on) return 0;
   }
   if (P.mode == LayoutPolicy::kStream || P.mode == LayoutPolicy::kJag || P.mode == LayoutPolicy::kPb) return 0;
   TRY(want_panels(ctx, P, s, &panels));
@@ -212,10 +210,10 @@ int layout_walk(pdlpdev_ctx* ctx, const LayoutPolicy& P, LayoutSide& s)
 // the walk's host constructions to the device (on the main thread, after the walk wherever it ran)
 int upload_side(pdlpdev_ctx* ctx, const LayoutPolicy& P, LayoutSide& s)
 {
-  if (s.jh.ok) TRY(upload_jag(ctx, s.jag, s.jh, s.d_off, s.d_idx, s.d_val));
-  TRY(upload_pb(ctx, s.pb, s.pbh));
-  if (P.mode == LayoutPolicy::kPb && !s.pb->on) return fail(-1, "CUOPT_AMD_SPMV_LAYOUT=pb: %s does not fit the gather-free layout (%s)", s.name, s.why.c_str());
-  return upload_panels(ctx, s.pan, s.ph, s.d_off, s.d_idx, s.d_val);
+  if (s.jh.ok) TRY(upload_jag(ctx, &s.side->jag, s.jh, s.d_off, s.d_idx, s.d_val));
+  TRY(upload_pb(ctx, &s.side->pb, s.pbh));
+  if (P.mode == LayoutPolicy::kPb && !s.side->pb.on) return fail(-1, "CUOPT_AMD_SPMV_LAYOUT=pb: %s does not fit the gather-free layout (%s)", s.name, s.why.c_str());
+  return upload_panels(ctx, &s.side->pan, s.ph, s.d_off, s.d_idx, s.d_val);
 }
 
 // A's panels with dense segments: the segments of the own rows (a workgroup each), in own-row order -- those workgroups add them
@@ -232,7 +230,7 @@ int own_segments(pdlpdev_ctx* ctx, const DenseHost& DH, const PanelHost& ha)
   int32_t* d_own_seg = nullptr;
   TRY(upload_i32(ctx, &d_own_seg, own_seg.data(), own_seg.size()));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
-  PanelView& v = ctx->pa.v;
+  PanelView& v = ctx->A.pan.v;
   v.dn_own_seg = d_own_seg, v.dn_seg_c0 = ctx->dense.seg_c0, v.dn_seg_len = ctx->dense.seg_len, v.dn_seg_ptr = ctx->dense.seg_ptr;
   v.dn_seg_row = ctx->dense.seg_row, v.dn_val = ctx->dense.val;
   return 0;
@@ -257,7 +255,7 @@ int column_segments(pdlpdev_ctx* ctx, const DenseHost& DH, const PanelHost& hat)
   TRY(upload_i32(ctx, &d_ptr, pan_ptr.data(), pan_ptr.size()));
   TRY(upload_i32(ctx, &d_seg, pan_seg.data(), pan_seg.size()));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
-  PanelView& v = ctx->pat.v;
+  PanelView& v = ctx->At.pan.v;
   v.dn_pan_ptr = d_ptr, v.dn_pan_seg = d_seg;
   v.dn_seg_c0 = ctx->dense.seg_c0, v.dn_seg_len = ctx->dense.seg_len, v.dn_seg_ptr = ctx->dense.seg_ptr;
   v.dn_seg_row = ctx->dense.seg_row, v.dn_val = ctx->dense.val;
@@ -300,6 +298,8 @@ static int create_impl(pdlpdev_ctx** out, int device, int32_t m, int32_t n, cons
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0) ctx->cus = cus;
   }
   ctx->m = m, ctx->n = n, ctx->nnz = a_offsets[m];
+  ctx->A.name = "A", ctx->A.rows = m, ctx->A.cols = n;
+  ctx->At.name = "A^T", ctx->At.rows = n, ctx->At.cols = m;
   *out = ctx;
   {
     Recycled r;
@@ -331,8 +331,8 @@ static int create_impl(pdlpdev_ctx** out, int device, int32_t m, int32_t n, cons
   // touched before transpose_ready returns).
   if (an) {
     // adopted: both matrices are the analysis' device arrays (allocated with the 8 spare entries the stream kernel may over-read)
-    ctx->a_off = an->A.off, ctx->a_idx = an->A.idx, ctx->a_val = an->A.val;
-    ctx->at_off = an->At.off, ctx->at_idx = an->At.idx, ctx->at_val = an->At.val;
+    ctx->A.full  = pdlpdev_ctx::Csr{an->A.off, an->A.idx, an->A.val};
+    ctx->At.full = pdlpdev_ctx::Csr{an->At.off, an->At.idx, an->At.val};
     for (void* p : {(void*)an->A.off, (void*)an->A.idx, (void*)an->A.val, (void*)an->At.off, (void*)an->At.idx, (void*)an->At.val}) {
       an->owned.erase(std::remove(an->owned.begin(), an->owned.end(), p), an->owned.end());
       ctx->allocs.push_back(p);
@@ -340,9 +340,9 @@ static int create_impl(pdlpdev_ctx** out, int device, int32_t m, int32_t n, cons
     an->adopted = true;
     ctx->bytes += (int64_t)(2 * (nnz + 8) * 12 + ((size_t)m + n + 2) * 4);
   } else {
-    TRY(upload_i32(ctx, &ctx->a_off, a_offsets, (size_t)m + 1));
-    TRY(upload_i32(ctx, &ctx->a_idx, a_indices, nnz, 8));  // +8: the vector loads of the stream kernel may over-read
-    TRY(upload_f64(ctx, &ctx->a_val, a_values, nnz, 8));
+    TRY(upload_i32(ctx, &ctx->A.full.off, a_offsets, (size_t)m + 1));
+    TRY(upload_i32(ctx, &ctx->A.full.idx, a_indices, nnz, 8));  // +8: the vector loads of the stream kernel may over-read
+    TRY(upload_f64(ctx, &ctx->A.full.val, a_values, nnz, 8));
   }
   lap("alloc + upload A");
   auto long_rows = [](int32_t rows, const int32_t* off) {
@@ -357,8 +357,8 @@ static int create_impl(pdlpdev_ctx** out, int device, int32_t m, int32_t n, cons
     return v;
   };
   std::vector<int32_t> la = long_rows(m, a_offsets), lat;  // alive until the stream is synchronised at the end
-  ctx->a_nlong = (int)la.size();
-  if (ctx->a_nlong) TRY(upload_i32(ctx, &ctx->a_long, la.data(), la.size()));
+  ctx->A.nlong = (int)la.size();
+  if (ctx->A.nlong) TRY(upload_i32(ctx, &ctx->A.longs, la.data(), la.size()));
   // dense row segments leave the hot loop's copy of the matrix (single-GPU solves)
   const bool one_gpu = !g_create_sharded;
   g_create_sharded   = 0;
@@ -388,12 +388,12 @@ static int create_impl(pdlpdev_ctx** out, int device, int32_t m, int32_t n, cons
   const bool hot_a     = !hA_off.empty();
   const int32_t* A_off = hot_a ? hA_off.data() : a_offsets;
   const int32_t* A_idx = hot_a ? hA_idx.data() : a_indices;  // (null: an analysed, permuted matrix whose indices stayed on the device)
-  ctx->ha_off = ctx->a_off, ctx->ha_idx = ctx->a_idx, ctx->ha_val = ctx->a_val;
-  ctx->dense.hot_nnz = (int64_t)A_off[m];
+  ctx->A.hot = ctx->A.full;
+  ctx->A.hot_nnz = (int64_t)A_off[m];
   if (hot_a) {
-    TRY(upload_i32(ctx, &ctx->ha_off, A_off, (size_t)m + 1));
-    TRY(upload_i32(ctx, &ctx->ha_idx, A_idx, (size_t)ctx->dense.hot_nnz, 8));
-    TRY(dev_alloc(ctx, &ctx->ha_val, (size_t)ctx->dense.hot_nnz + 8));
+    TRY(upload_i32(ctx, &ctx->A.hot.off, A_off, (size_t)m + 1));
+    TRY(upload_i32(ctx, &ctx->A.hot.idx, A_idx, (size_t)ctx->A.hot_nnz, 8));
+    TRY(dev_alloc(ctx, &ctx->A.hot.val, (size_t)ctx->A.hot_nnz + 8));
     TRY(upload_i32(ctx, &ctx->dense.s_perm_a, hA_perm.data(), hA_perm.size()));
   }
   if (DH.on) {
@@ -418,11 +418,11 @@ static int create_impl(pdlpdev_ctx** out, int device, int32_t m, int32_t n, cons
     D.on = true;
     if (timing) fprintf(stderr, "[cuopt_amd setup]   dense: %d segments in %d rows, %lld of %lld nonzeros stored index-free\n", D.nseg, D.nrows, (long long)D.nent, (long long)ctx->nnz);
   }
-  if (DH.on) TRY(dev_alloc(ctx, &ctx->dense.add_m, (size_t)m));
+  if (DH.on) TRY(dev_alloc(ctx, &ctx->A.dense_add, (size_t)m));
   std::vector<int32_t> rba = build_row_blocks(m, A_off);
   lap("row blocks A");
-  ctx->a_nb = (int)rba.size() / 2 - 1;
-  TRY(upload_i32(ctx, &ctx->a_rb, rba.data(), rba.size()));
+  ctx->A.nb = (int)rba.size() / 2 - 1;
+  TRY(upload_i32(ctx, &ctx->A.rb, rba.data(), rba.size()));
   if ((int64_t)m + n >= 262144) {
     // the vectors below (24 of n (+ pad), 15 of m entries) out of one zero-filled allocation
     const size_t bytes = (24 * ((size_t)n + kSlicePad + 32) + 15 * ((size_t)m + 32)) * sizeof(double);
@@ -488,14 +488,13 @@ static int create_impl(pdlpdev_ctx** out, int device, int32_t m, int32_t n, cons
     // do on the host: its A^T side runs inline, after A^T's uploads (a thread of its own took 3 ms to do 0.5 ms of work next to the
     // main thread's HIP calls).
     const bool at_thread = !an || DH.on;
-    auto init_side = [&](LayoutSide& s, int t) {
-      s.name = t ? "A^T" : "A", s.rows = t ? n : m, s.cols = t ? m : n, s.an = an, s.transposed = t != 0;
+    auto init_side = [&](LayoutSide& s, pdlpdev_ctx::MatrixSide* side, int t) {
+      s.side = side, s.name = side->name, s.rows = side->rows, s.cols = side->cols, s.an = an, s.transposed = t != 0;
       s.device   = an && !DH.on;
       s.skip_jag = an && an->estimated && !an->permuted && P.mode != LayoutPolicy::kJag && an->saving_natural[t] < 0.35;
-      s.jag = t ? &ctx->jat : &ctx->ja, s.pb = t ? &ctx->pbat : &ctx->pba, s.pan = t ? &ctx->pat : &ctx->pa;
     };
     LayoutSide T;
-    init_side(T, 1);
+    init_side(T, &ctx->At, 1);
     T.off = at_offsets, T.idx = at_indices;  // (the device's hot CSR once it is uploaded, below)
     const auto w0 = std::chrono::steady_clock::now();
     auto wlap = [&](const std::string& what) {
@@ -526,12 +525,12 @@ static int create_impl(pdlpdev_ctx** out, int device, int32_t m, int32_t n, cons
     if (at_thread) worker.t = std::thread(at_side, true);
     {
       LayoutSide A;  // (its host constructions go back to the pool at the end of this block)
-      init_side(A, 0);
-      A.off = A_off, A.idx = A_idx, A.d_off = ctx->ha_off, A.d_idx = ctx->ha_idx, A.d_val = ctx->ha_val, A.lap = lap;
+      init_side(A, &ctx->A, 0);
+      A.off = A_off, A.idx = A_idx, A.d_off = ctx->A.hot.off, A.d_idx = ctx->A.hot.idx, A.d_val = ctx->A.hot.val, A.lap = lap;
       A.first_seg = DH.on ? &DH.first_seg : nullptr;
       TRY(layout_walk(ctx, P, A));
       TRY(upload_side(ctx, P, A));
-      if (ctx->pa.on && DH.on) TRY(own_segments(ctx, DH, A.ph));
+      if (ctx->A.pan.on && DH.on) TRY(own_segments(ctx, DH, A.ph));
       lap("upload layouts A");
     }
     if (at_thread) worker.t.join();
@@ -539,29 +538,29 @@ static int create_impl(pdlpdev_ctx** out, int device, int32_t m, int32_t n, cons
     lap("wait for the A^T side");
     if ((int64_t)at_offsets[n] != ctx->nnz) return fail(-1, "pdlpdev_create: A and A^T disagree on nnz");
     if (!an) {
-      TRY(upload_i32(ctx, &ctx->at_off, at_offsets, (size_t)n + 1));
-      TRY(upload_i32(ctx, &ctx->at_idx, at_indices, nnz, 8));
-      TRY(upload_f64(ctx, &ctx->at_val, at_values, nnz, 8));
+      TRY(upload_i32(ctx, &ctx->At.full.off, at_offsets, (size_t)n + 1));
+      TRY(upload_i32(ctx, &ctx->At.full.idx, at_indices, nnz, 8));
+      TRY(upload_f64(ctx, &ctx->At.full.val, at_values, nnz, 8));
     }
-    ctx->at_nlong = (int)lat.size();
-    if (ctx->at_nlong) TRY(upload_i32(ctx, &ctx->at_long, lat.data(), lat.size()));
+    ctx->At.nlong = (int)lat.size();
+    if (ctx->At.nlong) TRY(upload_i32(ctx, &ctx->At.longs, lat.data(), lat.size()));
     const bool hot_t = !hT_off.empty();
-    ctx->hat_off = ctx->at_off, ctx->hat_idx = ctx->at_idx, ctx->hat_val = ctx->at_val;
-    ctx->hot_nnz_at = (int64_t)T.off[n];
+    ctx->At.hot = ctx->At.full;
+    ctx->At.hot_nnz = (int64_t)T.off[n];
     if (hot_t) {
-      TRY(upload_i32(ctx, &ctx->hat_off, T.off, (size_t)n + 1));
-      TRY(upload_i32(ctx, &ctx->hat_idx, T.idx, (size_t)ctx->hot_nnz_at, 8));
-      TRY(dev_alloc(ctx, &ctx->hat_val, (size_t)ctx->hot_nnz_at + 8));
+      TRY(upload_i32(ctx, &ctx->At.hot.off, T.off, (size_t)n + 1));
+      TRY(upload_i32(ctx, &ctx->At.hot.idx, T.idx, (size_t)ctx->At.hot_nnz, 8));
+      TRY(dev_alloc(ctx, &ctx->At.hot.val, (size_t)ctx->At.hot_nnz + 8));
       TRY(upload_i32(ctx, &ctx->dense.s_perm_at, hT_perm.data(), hT_perm.size()));
     }
-    if (DH.on) TRY(dev_alloc(ctx, &ctx->dense.add_n, (size_t)n));
-    ctx->at_nb = (int)rbt.size() / 2 - 1;
-    TRY(upload_i32(ctx, &ctx->at_rb, rbt.data(), rbt.size()));
+    if (DH.on) TRY(dev_alloc(ctx, &ctx->At.dense_add, (size_t)n));
+    ctx->At.nb = (int)rbt.size() / 2 - 1;
+    TRY(upload_i32(ctx, &ctx->At.rb, rbt.data(), rbt.size()));
     lap("upload A^T");
-    T.d_off = ctx->hat_off, T.d_idx = ctx->hat_idx, T.d_val = ctx->hat_val;
+    T.d_off = ctx->At.hot.off, T.d_idx = ctx->At.hot.idx, T.d_val = ctx->At.hot.val;
     TRY(at_thread ? at_rc : layout_walk(ctx, P, T));
     TRY(upload_side(ctx, P, T));
-    if (ctx->pat.on && DH.on) TRY(column_segments(ctx, DH, T.ph));
+    if (ctx->At.pan.on && DH.on) TRY(column_segments(ctx, DH, T.ph));
     lap("upload layouts A^T");
     HIP_TRY(hipStreamSynchronize(ctx->stream));  // the staged copies have left the host arrays
   }
@@ -570,20 +569,19 @@ static int create_impl(pdlpdev_ctx** out, int device, int32_t m, int32_t n, cons
     const char* small_env = getenv("CUOPT_AMD_SMALL");
     const int tier        = resident_tier(m, n, ctx->nnz);
     ctx->eval_reuse_aty   = cuopt_amd::tune_int("eval_reuse_aty", 1) != 0;
-    ctx->small_resident   = tier >= 0 && !(small_env && atoi(small_env) == 0) && !ctx->dense.add_m && !ctx->dense.add_n && !g_create_no_resident;
+    ctx->small_resident   = tier >= 0 && !(small_env && atoi(small_env) == 0) && !ctx->A.dense_add && !ctx->At.dense_add && !g_create_no_resident;
     g_create_no_resident  = 0;
     if (small_env && atoi(small_env) != 0 && tier < 0)
       return fail(-1, "CUOPT_AMD_SMALL=1: the LP does not fit the resident kernel (m, n <= 2048, nnz <= 4096 ...)");
   }
-  // every layout adds what the dense segments / the extracted long rows contribute ahead of its epilogue (null: nothing to add)
-  ctx->pa.v.dense_add = ctx->ja.v.dense_add = ctx->pba.v.dense_add = ctx->dense.add_m;
-  ctx->pat.v.dense_add = ctx->jat.v.dense_add = ctx->pbat.v.dense_add = ctx->dense.add_n;
-  // ... except the panels, whose kernels add the segments themselves (own-row workgroups / the column epilogue): no launch in front
-  if (ctx->pa.v.dn_own_seg) ctx->pa.v.dense_add = nullptr;
-  if (ctx->pat.v.dn_pan_ptr) ctx->pat.v.dense_add = nullptr;
   ctx->slab_cap += slab_rest;
-  TRY(dev_alloc(ctx, &ctx->part_a, (size_t)8 * std::max({ctx->a_nb, ctx->pba.on ? ctx->pba.v.B : 0, ctx->pa.on ? ctx->pa.v.W : 0, ctx->ja.on ? ctx->ja.v.nblk + ctx->ja.v.nlong : 0, 1})));
-  TRY(dev_alloc(ctx, &ctx->part_at, (size_t)8 * std::max({ctx->at_nb, ctx->pbat.on ? ctx->pbat.v.B : 0, ctx->pat.on ? ctx->pat.v.W : 0, ctx->jat.on ? ctx->jat.v.nblk + ctx->jat.v.nlong : 0, 1})));
+  for (pdlpdev_ctx::MatrixSide* s : {&ctx->A, &ctx->At}) {
+    // every layout adds what the dense segments contribute ahead of its epilogue (null: nothing to add) -- except the panels whose
+    // kernels add the segments themselves (own-row workgroups / the column epilogue): no launch in front
+    s->pan.v.dense_add = s->jag.v.dense_add = s->pb.v.dense_add = s->dense_add;
+    if (s->pan.v.dn_own_seg || s->pan.v.dn_pan_ptr) s->pan.v.dense_add = nullptr;
+    TRY(dev_alloc(ctx, &s->part, (size_t)8 * s->max_partials()));
+  }
   TRY(dev_alloc(ctx, &ctx->part_g, (size_t)8 * 2048));
   TRY(dev_alloc(ctx, &ctx->scal, kScalars));
   TRY(dev_alloc(ctx, &ctx->ctl, 1));
@@ -596,9 +594,9 @@ static int create_impl(pdlpdev_ctx** out, int device, int32_t m, int32_t n, cons
   TRY(sync_panel_values(ctx));
   lap("panel values (permute)");
   if (P.mode == LayoutPolicy::kTimed) {
-    TRY(pick_layout(ctx, &ctx->pa, m, ctx->a_nb, ctx->a_rb, ctx->ha_off, ctx->ha_idx, ctx->ha_val, ctx->tmp_n, ctx->tmp_m, "A"));
+    TRY(pick_layout(ctx, &ctx->A, ctx->tmp_n, ctx->tmp_m));
     lap("layout autotune A");
-    TRY(pick_layout(ctx, &ctx->pat, n, ctx->at_nb, ctx->at_rb, ctx->hat_off, ctx->hat_idx, ctx->hat_val, ctx->tmp_m, ctx->tmp_n, "A^T"));
+    TRY(pick_layout(ctx, &ctx->At, ctx->tmp_m, ctx->tmp_n));
     lap("layout autotune");
   }
   HIP_TRY(hipStreamSynchronize(ctx->stream));

@@ -295,11 +295,7 @@ struct pdlpdev_ctx {
   hipStream_t stream = nullptr;
   int32_t m = 0, n = 0;
   int64_t nnz = 0;
-  // matrices (values are scaled in place by pdlpdev_scale_problem)
-  int32_t *a_off = nullptr, *a_idx = nullptr, *at_off = nullptr, *at_idx = nullptr;
-  double *a_val = nullptr, *at_val = nullptr;
-  int32_t *a_rb = nullptr, *at_rb = nullptr;  // row-block boundaries of the stream kernels
-  int a_nb = 0, at_nb = 0;
+  int cus = 256;  // compute units of the device (hipDeviceProp_t::multiProcessorCount)
   // slab-major row panels (optional second layout of the same nonzeros, see pdlp_kernels.hpp)
   struct Panels {
     bool on = false;
@@ -307,11 +303,7 @@ struct pdlpdev_ctx {
     int32_t* perm = nullptr;  // position in CSR order of each panel-order nonzero
     double* val   = nullptr;
     int64_t nent  = 0;        // nonzeros inside the panels (rows with a workgroup of their own are read from the CSR)
-  } pa, pat;
-  int cus = 256;  // compute units of the device (hipDeviceProp_t::multiProcessorCount)
-  // rows of A / of A^T with more than kLongRow nonzeros (set-up kernels give each a workgroup instead of a lane)
-  int32_t *a_long = nullptr, *at_long = nullptr;
-  int a_nlong = 0, at_nlong = 0;
+  };
   // sorted jagged rows with LDS column sets (third layout, structured matrices; pdlp_kernels.hpp)
   struct Jag {
     bool on = false;
@@ -320,11 +312,71 @@ struct pdlpdev_ctx {
     double* val   = nullptr;
     int64_t nent  = 0;
     double saving = 0.0;      // share of the global gathers the LDS column sets save (build_jag)
-  } ja, jat;
+  };
+  // gather-free layout (fourth layout: huge unstructured matrices; pdlp_kernels.hpp "pb")
+  struct Pb {
+    bool on = false;
+    PbView v{};
+    int32_t* perm = nullptr;  // position in CSR order of each padded P-order entry (-1: padding)
+    double* val   = nullptr;
+    int64_t np    = 0;        // padded entries
+    int p_threads = 512;      // phase P workgroup: 512 (8192-column panels) or 1024 (16384)
+    double pad    = 1.0;      // padded entries / nonzeros
+  };
+  struct Csr {
+    int32_t *off = nullptr, *idx = nullptr;
+    double* val = nullptr;
+  };
+  // What one matrix owns for the hot loop.  The context holds three: A (m x n), A^T (n x m) and, under the owner-computes dataflow, the
+  // rank's column block.  At most one of the three layout slots is on; the CSR stream is the layout of a side with none.  The product
+  // launches go through launch_product (pdlp_launch.hpp), the only other place that knows the four-way choice.
+  struct MatrixSide {
+    const char* name = "";
+    int32_t rows = 0, cols = 0;
+    Csr full;  // as uploaded (values are scaled in place by pdlpdev_scale_problem): the set-up kernels (norms, scaling) run on it
+    Csr hot;   // what the hot loop multiplies: `full` unless dense segments left the matrix (Dense below)
+    int64_t hot_nnz = 0;
+    int32_t* rb = nullptr;  // row-block boundaries of the stream kernels
+    int nb = 0;
+    int32_t* longs = nullptr;  // rows with more than kLongRow nonzeros (set-up kernels give each a workgroup instead of a lane)
+    int nlong = 0;
+    Panels pan;
+    Jag jag;
+    Pb pb;
+    double* part = nullptr;       // per-workgroup partials of the side's fused epilogue (8 quantities each)
+    double* dense_add = nullptr;  // what the dense segments contribute to the product, per row of this side (null: no segments)
+    enum Layout { kStream = 0, kPanel = 1, kJag = 3, kPb = 4 };  // (the numbers pdlpdev_layout_info reports)
+    Layout layout() const { return pb.on ? kPb : jag.on ? kJag : pan.on ? kPanel : kStream; }
+    // partial sums the side's epilogue leaves / the most any layout the side may still run leaves (the buffer's size)
+    int partials() const
+    {
+      switch (layout()) {
+        case kPb: return pb.v.B;
+        case kJag: return jag.v.nblk + jag.v.nlong;
+        case kPanel: return pan.v.W;
+        default: return nb;
+      }
+    }
+    int max_partials() const { return std::max({nb, pb.on ? pb.v.B : 0, pan.on ? pan.v.W : 0, jag.on ? jag.v.nblk + jag.v.nlong : 0, 1}); }
+    // pdlpdev_layout_info's triple: the layout, its workgroups (bins / row blocks / panels), and a figure of merit of its own
+    void info(int32_t out[3]) const
+    {
+      out[0] = layout();
+      switch (layout()) {
+        case kPb: out[1] = pb.v.B, out[2] = (int)(100.0 * (pb.pad - 1.0) + 0.5); break;
+        case kJag: out[1] = jag.v.nblk, out[2] = (int)(100.0 * jag.saving + 0.5); break;
+        case kPanel: out[1] = pan.v.W, out[2] = pan.v.S; break;
+        default: out[1] = nb, out[2] = 1;
+      }
+    }
+    // the panel kernels add the dense segments themselves (own-row workgroups of A, the column epilogue of A^T): no launches in front
+    bool fuses_dense() const { return pan.on && (pan.v.dn_own_seg != nullptr || pan.v.dn_pan_ptr != nullptr); }
+  };
+  MatrixSide A, At;
   // Dense row segments (runs of >= kDenseMin consecutive columns inside a row: budget / convexity / linking constraints that
   // run through a block of variables) are stored INDEX-FREE, 8 bytes per entry instead of 12, and multiplied by two streaming
   // kernels of their own (k_dense_rows: lane <-> entry, the vector read coalesced; k_dense_cols: lane <-> column, the rows that
-  // cover it in ascending order); the four layouts then work on the sparse remainder ("hot" CSR: ha_* / hat_*, the matrices
+  // cover it in ascending order); the four layouts then work on the sparse remainder (each side's "hot" CSR, the matrices
   // without the segments' entries) and add what the segments contribute ahead of their fused epilogues (dense_plus).  The
   // set-up kernels (norms, scaling) keep running on the full CSR.  Rows / columns a segment touches are compared with the
   // oracle at the long-row tolerance (their sums are split in two).
@@ -340,24 +392,8 @@ struct pdlpdev_ctx {
     int32_t *tile_ptr = nullptr, *tile_seg = nullptr, *tile_id = nullptr;  // per 256-column tile some segment overlaps: those segments, ascending rows
     int32_t *perm = nullptr, *s_perm_a = nullptr, *s_perm_at = nullptr;  // positions in the FULL CSR of A / A / A^T
     double* val = nullptr;                   // nent: the segments' values, row after row
-    double *add_m = nullptr, *add_n = nullptr;  // what the segments contribute to A v (per row) / A^T v (per column)
     int32_t* tile_slot = nullptr;               // per 256-column tile: its index in tile_ptr, -1 where no segment overlaps it
-    bool fused_a = false, fused_at = false;     // the panel kernels of that side add the segments themselves (no launches in front)
-    int64_t hot_nnz = 0;
   } dense;
-  int64_t hot_nnz_at = 0;
-  int32_t *ha_off = nullptr, *ha_idx = nullptr, *hat_off = nullptr, *hat_idx = nullptr;  // the CSR the hot loop multiplies:
-  double *ha_val = nullptr, *hat_val = nullptr;                                          // a_* / at_* unless dense.on
-  // gather-free layout (fourth layout: huge unstructured matrices; pdlp_kernels.hpp "pb")
-  struct Pb {
-    bool on = false;
-    PbView v{};
-    int32_t* perm = nullptr;  // position in CSR order of each padded P-order entry (-1: padding)
-    double* val   = nullptr;
-    int64_t np    = 0;        // padded entries
-    int p_threads = 512;      // phase P workgroup: 512 (8192-column panels) or 1024 (16384)
-    double pad    = 1.0;      // padded entries / nonzeros
-  } pba, pbat;
   // problem vectors: scaled working copies and the unscaled originals
   double *c = nullptr, *lb = nullptr, *ub = nullptr, *lo = nullptr, *hi = nullptr;
   // all lower (upper) bounds are the same 0 or infinity: k_primal takes the constant instead of streaming the array
@@ -402,8 +438,7 @@ struct pdlpdev_ctx {
   double *ax_u[3] = {nullptr, nullptr, nullptr}, *aty_u[3] = {nullptr, nullptr, nullptr};  // unscaled A x / A^T y of pdlpdev_eval(which)
   double* rc_scratch = nullptr;  // reduced costs of eval(LAST_RESTART): never returned
   double *bestx = nullptr, *besty = nullptr, *bestrc = nullptr;  // save_best_primal_so_far snapshot (scaled x, y)
-  // reductions
-  double *part_a = nullptr, *part_at = nullptr;  // per-row-block partials (8 quantities each)
+  // reductions (each side's own partials: MatrixSide::part)
   double *part_g = nullptr;                      // generic grid-stride partials
   double *scal = nullptr;                        // device scalars (outputs of finalize kernels)
   double *scal_h = nullptr;                      // pinned mirror
@@ -435,14 +470,7 @@ struct pdlpdev_ctx {
   bool owner = false;
   int ypad = 0;               // entries per rank in the gathered dual vector: the largest row block, a multiple of 16
   double* ygather = nullptr;  // world * ypad: rank q's y' at [q * ypad, ...); also the gather vector of the column block
-  int32_t oc_rows = 0;        // columns of A this rank owns (= rows of the column block)
-  int64_t oc_nnz = 0;
-  int32_t *oc_off = nullptr, *oc_idx = nullptr, *oc_rb = nullptr, *oc_long = nullptr;
-  double* oc_val = nullptr;
-  int oc_nb = 0, oc_nlong = 0;
-  Panels poc;
-  Jag joc;
-  double* part_oc = nullptr;
+  MatrixSide Oc;              // the column block: rows = the columns of A this rank owns, cols = the gathered dual's length
   // HALO exchange of the owner-computes dataflow (round 5).  A rank's rows touch only the columns of its own slice plus, on a
   // structured LP (a band, a staircase -- as given or as the set-up's reordering found it), a few thousand columns at the edges of
   // its neighbours' slices; its columns likewise touch its own rows plus the edges of the neighbours' row blocks.  Then the two

@@ -458,20 +458,20 @@ k_unscale(int n, const double* __restrict__ v, const double* __restrict__ d, dou
 // panel values <- current CSR values (after upload and again after scale_problem)
 int sync_panel_values(pdlpdev_ctx* c)
 {
-  const int64_t hot = c->dense.hot_nnz, hot_t = c->hot_nnz_at;
-  // first the hot copies of the matrices, the segments' and the extracted rows' values, from the full (just scaled) CSR
-  if (c->ha_val != c->a_val) k_permute<<<grid_for(hot), kBlock, 0, c->stream>>>(hot, c->dense.s_perm_a, c->a_val, c->ha_val);
-  if (c->hat_val != c->at_val) k_permute<<<grid_for(hot_t), kBlock, 0, c->stream>>>(hot_t, c->dense.s_perm_at, c->at_val, c->hat_val);
-  if (c->dense.on) k_permute<<<grid_for(c->dense.nent), kBlock, 0, c->stream>>>(c->dense.nent, c->dense.perm, c->a_val, c->dense.val);
-  (void)hot, (void)hot_t;
-  if (c->pa.on) k_permute<<<grid_for(c->pa.nent), kBlock, 0, c->stream>>>(c->pa.nent, c->pa.perm, c->ha_val, c->pa.val);
-  if (c->pat.on) k_permute<<<grid_for(c->pat.nent), kBlock, 0, c->stream>>>(c->pat.nent, c->pat.perm, c->hat_val, c->pat.val);
-  if (c->ja.on) k_permute<<<grid_for(c->ja.nent), kBlock, 0, c->stream>>>(c->ja.nent, c->ja.perm, c->ha_val, c->ja.val);
-  if (c->jat.on) k_permute<<<grid_for(c->jat.nent), kBlock, 0, c->stream>>>(c->jat.nent, c->jat.perm, c->hat_val, c->jat.val);
-  if (c->pba.on) k_permute_pad<<<grid_for(c->pba.np), kBlock, 0, c->stream>>>(c->pba.np, c->pba.perm, c->ha_val, c->pba.val);
-  if (c->pbat.on) k_permute_pad<<<grid_for(c->pbat.np), kBlock, 0, c->stream>>>(c->pbat.np, c->pbat.perm, c->hat_val, c->pbat.val);
-  if (c->poc.on) k_permute<<<grid_for(c->poc.nent), kBlock, 0, c->stream>>>(c->poc.nent, c->poc.perm, c->oc_val, c->poc.val);
-  if (c->joc.on) k_permute<<<grid_for(c->joc.nent), kBlock, 0, c->stream>>>(c->joc.nent, c->joc.perm, c->oc_val, c->joc.val);
+  // first the hot copies of the matrices and the segments' values, from the full (just scaled) CSR
+  if (c->A.hot.val != c->A.full.val) k_permute<<<grid_for(c->A.hot_nnz), kBlock, 0, c->stream>>>(c->A.hot_nnz, c->dense.s_perm_a, c->A.full.val, c->A.hot.val);
+  if (c->At.hot.val != c->At.full.val) k_permute<<<grid_for(c->At.hot_nnz), kBlock, 0, c->stream>>>(c->At.hot_nnz, c->dense.s_perm_at, c->At.full.val, c->At.hot.val);
+  if (c->dense.on) k_permute<<<grid_for(c->dense.nent), kBlock, 0, c->stream>>>(c->dense.nent, c->dense.perm, c->A.full.val, c->dense.val);
+  // then each layout's values from its side's hot CSR: panels of A, A^T, jagged rows of A, A^T, gather-free of A, A^T, the column block's
+  const pdlpdev_ctx::MatrixSide* sides[] = {&c->A, &c->At};
+  for (const auto* s : sides)
+    if (s->pan.on) k_permute<<<grid_for(s->pan.nent), kBlock, 0, c->stream>>>(s->pan.nent, s->pan.perm, s->hot.val, s->pan.val);
+  for (const auto* s : sides)
+    if (s->jag.on) k_permute<<<grid_for(s->jag.nent), kBlock, 0, c->stream>>>(s->jag.nent, s->jag.perm, s->hot.val, s->jag.val);
+  for (const auto* s : sides)
+    if (s->pb.on) k_permute_pad<<<grid_for(s->pb.np), kBlock, 0, c->stream>>>(s->pb.np, s->pb.perm, s->hot.val, s->pb.val);
+  if (c->Oc.pan.on) k_permute<<<grid_for(c->Oc.pan.nent), kBlock, 0, c->stream>>>(c->Oc.pan.nent, c->Oc.pan.perm, c->Oc.hot.val, c->Oc.pan.val);
+  if (c->Oc.jag.on) k_permute<<<grid_for(c->Oc.jag.nent), kBlock, 0, c->stream>>>(c->Oc.jag.nent, c->Oc.jag.perm, c->Oc.hot.val, c->Oc.jag.val);
   HIP_TRY(hipGetLastError());
   return 0;
 }
@@ -496,7 +496,6 @@ __global__ void __launch_bounds__(kBlock) k_slice_ranges(int64_t nnz, const int3
 
 extern "C" {
 
-static inline int oc_partials(const pdlpdev_ctx* ctx) { return ctx->joc.on ? ctx->joc.v.nblk + ctx->joc.v.nlong : ctx->poc.on ? ctx->poc.v.W : ctx->oc_nb; }
 int pdlpdev_owner_slice(pdlpdev_ctx* ctx, int32_t* col_begin, int32_t* ncols)
 {
   if (!ctx->owner) return fail(-1, "pdlpdev_owner_slice: the solver does not run the owner-computes dataflow");
@@ -523,7 +522,7 @@ int pdlpdev_owner_setup(pdlpdev_ctx* ctx, const int32_t* off, const int32_t* idx
   const int64_t gcols = (int64_t)ctx->world * ctx->ypad;
   if (gcols >= ((int64_t)1 << 31)) return fail(-1, "pdlpdev_owner_setup: gathered dual too long");
   const int64_t nnz = nc > 0 ? off[nc] : 0;
-  ctx->oc_rows = nc, ctx->oc_nnz = nnz;
+  ctx->Oc.name = "column block", ctx->Oc.rows = nc, ctx->Oc.cols = (int32_t)gcols, ctx->Oc.hot_nnz = nnz;
   // global row -> position in the gathered dual (rank q's rows at [q * ypad, ...))
   std::vector<int32_t> ridx((size_t)std::max<int64_t>(nnz, 1));
   {
@@ -537,24 +536,25 @@ int pdlpdev_owner_setup(pdlpdev_ctx* ctx, const int32_t* off, const int32_t* idx
       }
     }
   }
-  TRY(upload_i32(ctx, &ctx->oc_off, off, (size_t)nc + 1));
-  TRY(upload_i32(ctx, &ctx->oc_idx, ridx.data(), (size_t)nnz, 8));
-  TRY(upload_f64(ctx, &ctx->oc_val, val, (size_t)nnz, 8));
+  TRY(upload_i32(ctx, &ctx->Oc.hot.off, off, (size_t)nc + 1));
+  TRY(upload_i32(ctx, &ctx->Oc.hot.idx, ridx.data(), (size_t)nnz, 8));
+  TRY(upload_f64(ctx, &ctx->Oc.hot.val, val, (size_t)nnz, 8));
+  ctx->Oc.full = ctx->Oc.hot;
   TRY(dev_alloc(ctx, &ctx->ygather, (size_t)gcols + kSlicePad));
   std::vector<int32_t> longs;
   for (int32_t r = 0; r < nc; ++r)
     if (off[r + 1] - off[r] > kLongRow) longs.push_back(r);
-  ctx->oc_nlong = (int)longs.size();
-  if (ctx->oc_nlong) TRY(upload_i32(ctx, &ctx->oc_long, longs.data(), longs.size()));
+  ctx->Oc.nlong = (int)longs.size();
+  if (ctx->Oc.nlong) TRY(upload_i32(ctx, &ctx->Oc.longs, longs.data(), longs.size()));
   std::vector<int32_t> rb = build_row_blocks(nc, off);
-  ctx->oc_nb = (int)rb.size() / 2 - 1;
-  TRY(upload_i32(ctx, &ctx->oc_rb, rb.data(), rb.size()));
+  ctx->Oc.nb = (int)rb.size() / 2 - 1;
+  TRY(upload_i32(ctx, &ctx->Oc.rb, rb.data(), rb.size()));
   // scaling: D_r of every rank's rows in the gathered layout (ygather doubles as the staging buffer), then (val * D_c[j]) * D_r[i]
   hipStream_t s = ctx->stream;
   HIP_TRY(hipMemcpyAsync(ctx->ygather + (size_t)ctx->rank * ctx->ypad, ctx->dr, (size_t)ctx->m * sizeof(double), hipMemcpyDeviceToDevice, s));
   TRY(all_gather(ctx, ctx->ygather, (size_t)ctx->ypad));
-  k_scale_matrix<<<grid_for(nc), kBlock, 0, s>>>(nc, ctx->oc_off, ctx->oc_idx, ctx->oc_val, ctx->dc + cb, ctx->ygather);
-  if (ctx->oc_nlong) k_scale_matrix_long<<<ctx->oc_nlong, kBlock, 0, s>>>(ctx->oc_long, ctx->oc_off, ctx->oc_idx, ctx->oc_val, ctx->dc + cb, ctx->ygather);
+  k_scale_matrix<<<grid_for(nc), kBlock, 0, s>>>(nc, ctx->Oc.hot.off, ctx->Oc.hot.idx, ctx->Oc.hot.val, ctx->dc + cb, ctx->ygather);
+  if (ctx->Oc.nlong) k_scale_matrix_long<<<ctx->Oc.nlong, kBlock, 0, s>>>(ctx->Oc.longs, ctx->Oc.hot.off, ctx->Oc.hot.idx, ctx->Oc.hot.val, ctx->dc + cb, ctx->ygather);
   HIP_TRY(hipGetLastError());
   // layouts, by the policy of the two other matrices with two candidates: jagged rows, then panels (timed mode counts as auto here)
   {
@@ -563,23 +563,23 @@ int pdlpdev_owner_setup(pdlpdev_ctx* ctx, const int32_t* off, const int32_t* idx
     const LayoutPolicy::Mode mode = P.mode == LayoutPolicy::kTimed ? LayoutPolicy::kAuto : P.mode;
     if (nc > 0 && (mode == LayoutPolicy::kAuto || mode == LayoutPolicy::kJag)) {
       JagHost j = build_jag(nc, (int32_t)gcols, off, ridx.data(), mode == LayoutPolicy::kJag ? 1 : 0, ctx->cus);
-      TRY(upload_jag(ctx, &ctx->joc, j, ctx->oc_off, ctx->oc_idx, ctx->oc_val));
+      TRY(upload_jag(ctx, &ctx->Oc.jag, j, ctx->Oc.hot.off, ctx->Oc.hot.idx, ctx->Oc.hot.val));
     }
     const bool panels = mode == LayoutPolicy::kPanel ||
                         (mode == LayoutPolicy::kAuto && gcols * 8 > P.ws_limit && gather_working_set(nc, (int32_t)gcols, off, ridx.data()) > P.ws_limit);
-    if (nc > 0 && !ctx->joc.on && panels) {
+    if (nc > 0 && !ctx->Oc.jag.on && panels) {
       PanelHost h = build_panels(nc, (int32_t)gcols, off, ridx.data(), P.slab_bytes, true);
-      TRY(upload_panels(ctx, &ctx->poc, h, ctx->oc_off, ctx->oc_idx, ctx->oc_val));
+      TRY(upload_panels(ctx, &ctx->Oc.pan, h, ctx->Oc.hot.off, ctx->Oc.hot.idx, ctx->Oc.hot.val));
     }
   }
-  TRY(dev_alloc(ctx, &ctx->part_oc, (size_t)8 * std::max(oc_partials(ctx), 1)));
+  TRY(dev_alloc(ctx, &ctx->Oc.part, (size_t)8 * std::max(ctx->Oc.partials(), 1)));
   {
     const char* tr = getenv("CUOPT_AMD_SHARD_TRANSPORT");
     if (tr && std::string(tr) == "p2p") TRY(p2p_setup(ctx));
     else if (tr && std::string(tr) != "collective") return fail(-1, "CUOPT_AMD_SHARD_TRANSPORT must be collective or p2p");
   }
-  if (ctx->poc.on) k_permute<<<grid_for(ctx->poc.nent), kBlock, 0, s>>>(ctx->poc.nent, ctx->poc.perm, ctx->oc_val, ctx->poc.val);
-  if (ctx->joc.on) k_permute<<<grid_for(ctx->joc.nent), kBlock, 0, s>>>(ctx->joc.nent, ctx->joc.perm, ctx->oc_val, ctx->joc.val);
+  if (ctx->Oc.pan.on) k_permute<<<grid_for(ctx->Oc.pan.nent), kBlock, 0, s>>>(ctx->Oc.pan.nent, ctx->Oc.pan.perm, ctx->Oc.hot.val, ctx->Oc.pan.val);
+  if (ctx->Oc.jag.on) k_permute<<<grid_for(ctx->Oc.jag.nent), kBlock, 0, s>>>(ctx->Oc.jag.nent, ctx->Oc.jag.perm, ctx->Oc.hot.val, ctx->Oc.jag.val);
   HIP_TRY(hipGetLastError());
   {
     // what this rank references outside its own slice / rows: per peer one range of xbar (the rank's rows of A, on the device) and
@@ -591,7 +591,7 @@ int pdlpdev_owner_setup(pdlpdev_ctx* ctx, const int32_t* off, const int32_t* idx
     TRY(dev_alloc(ctx, &d_hi, 16));
     HIP_TRY(hipMemcpyAsync(d_lo, xl.data(), W * sizeof(int32_t), hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(d_hi, xh.data(), W * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    if (ctx->nnz > 0) k_slice_ranges<<<grid_for(ctx->nnz, 8), kBlock, 0, s>>>(ctx->nnz, ctx->a_idx, ctx->slice, W, d_lo, d_hi);
+    if (ctx->nnz > 0) k_slice_ranges<<<grid_for(ctx->nnz, 8), kBlock, 0, s>>>(ctx->nnz, ctx->A.full.idx, ctx->slice, W, d_lo, d_hi);
     HIP_TRY(hipMemcpyAsync(xl.data(), d_lo, W * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(xh.data(), d_hi, W * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
@@ -660,7 +660,7 @@ int pdlpdev_agree_max(pdlpdev_ctx* ctx, double* value)
 int pdlpdev_init_norms(pdlpdev_ctx* ctx, double out[3])
 {
   HIP_TRY(hipSetDevice(ctx->device));
-  TRY(reduce_vec(ctx, 0, ctx->nnz, ctx->a_val, nullptr, 0));
+  TRY(reduce_vec(ctx, 0, ctx->nnz, ctx->A.full.val, nullptr, 0));
   TRY(reduce_vec(ctx, 1, ctx->n, ctx->c, nullptr, 1));
   TRY(reduce_vec(ctx, 2, ctx->m, ctx->lo, ctx->hi, 2));
   TRY(allreduce(ctx, ctx->scal + 0, 1, rccl::kMax));
@@ -880,123 +880,41 @@ int pdlpdev_compute_aty(pdlpdev_ctx* ctx)
 }
 
 
-// dense row segments: their share of A v (transpose = 0) / A^T v lands in dense.add_m / add_n right before the layout's kernel adds it
-void dense_part(pdlpdev_ctx* ctx, int transpose, const double* v0, const double* v1, int mode, int in_loop)
-{
-  const pdlpdev_ctx::Dense& D = ctx->dense;
-  const bool fused            = transpose ? (ctx->pat.on && ctx->pat.v.dn_pan_ptr != nullptr) : (ctx->pa.on && ctx->pa.v.dn_own_seg != nullptr);
-  if (D.on && !fused) {
-    DenseView V{D.row, D.row_seg, D.seg_row, D.seg_c0, D.seg_len, D.seg_ptr, D.tile_ptr, D.tile_seg, D.tile_id, D.val, D.ch_seg, D.ch_k0, D.row_ch, D.ch_part};
-    if (transpose) {
-      launch_k(ctx, k_dense_cols, D.ntiles, kBlock, 0, V, ctx->n, ctx->ctl, v0, v1, mode, in_loop, D.add_n);
-    } else {
-      launch_k(ctx, k_dense_rows, D.nchunks, kBlock, 0, V, ctx->ctl, v0, v1, mode, in_loop);
-      launch_k(ctx, k_dense_rows_finish, (D.nrows + kBlock - 1) / kBlock, kBlock, 0, V, D.nrows, ctx->ctl, in_loop, D.add_m);
-    }
-  }
-}
-// launch helpers: pick the layout (jagged rows with LDS column sets, slab-major panels, CSR stream)
+// the products of an attempt and the plain ones, each in its side's layout (launch_product)
 static inline HalpernArgs halpern_args(const pdlpdev_ctx* ctx) { return HalpernArgs{ctx->hal, ctx->avgx, ctx->avgy, ctx->lrx, ctx->lry, ctx->lraty}; }
-// the two products of a Halpern step: the twins' launch sites with the Halpern kernels; the A^T product gathers y' from its own buffer
-static void launch_a_halpern(pdlpdev_ctx* ctx)
-{
-  const HalpernArgs h = halpern_args(ctx);
-  dense_part(ctx, 0, ctx->xbar, nullptr, 0, 1);
-  if (ctx->pba.on) {
-    (void)pb_products(ctx, ctx->pba, ctx->xbar, nullptr, 0, 1);
-    (void)pb_rows(ctx, k_pb_a_halpern, ctx->pba, ctx->ctl, ctx->y[0], ctx->y[1], ctx->lo, ctx->hi, h, ctx->part_a);
-  } else if (ctx->ja.on)
-    (void)JAG_LAUNCH(ctx, k_jag_a_halpern, ctx->ja.v, ctx->ctl, ctx->xbar, ctx->y[0], ctx->y[1], ctx->lo, ctx->hi, h, ctx->part_a);
-  else if (ctx->pa.on)
-    launch_k(ctx, ctx->pa.v.seg ? k_panel_a_halpern<true> : k_panel_a_halpern<false>, ctx->pa.v.W, kPanelThreads, 0, ctx->pa.v, ctx->ctl, ctx->xbar, ctx->y[0], ctx->y[1], ctx->lo, ctx->hi, h, ctx->part_a);
-  else
-    launch_k(ctx, k_spmv_a_halpern, stream_grid(ctx->a_nb), kBlock, 0, ctx->a_nb, ctx->a_rb, ctx->ha_off, ctx->ha_idx, ctx->ha_val, ctx->ctl, ctx->xbar, ctx->y[0], ctx->y[1], ctx->lo, ctx->hi, h, ctx->part_a, ctx->dense.add_m);
-}
-static void launch_at_halpern(pdlpdev_ctx* ctx)
-{
-  const HalpernArgs h = halpern_args(ctx);
-  dense_part(ctx, 1, ctx->avgy, nullptr, 0, 1);
-  if (ctx->pbat.on) {
-    (void)pb_products(ctx, ctx->pbat, ctx->avgy, nullptr, 0, 1);
-    (void)pb_rows(ctx, k_pb_at_halpern, ctx->pbat, ctx->ctl, ctx->x[0], ctx->x[1], ctx->aty[0], ctx->aty[1], h, ctx->part_at);
-  } else if (ctx->jat.on)
-    (void)JAG_LAUNCH(ctx, k_jag_at_halpern, ctx->jat.v, ctx->ctl, ctx->x[0], ctx->x[1], ctx->aty[0], ctx->aty[1], h, ctx->part_at);
-  else if (ctx->pat.on)
-    launch_k(ctx, ctx->pat.v.seg ? k_panel_at_halpern<true> : k_panel_at_halpern<false>, ctx->pat.v.W, kPanelThreads, 0, ctx->pat.v, ctx->ctl, ctx->x[0], ctx->x[1], ctx->aty[0], ctx->aty[1], h, ctx->part_at);
-  else
-    launch_k(ctx, k_spmv_at_halpern, stream_grid(ctx->at_nb), kBlock, 0, ctx->at_nb, ctx->at_rb, ctx->hat_off, ctx->hat_idx, ctx->hat_val, ctx->ctl, ctx->x[0], ctx->x[1], ctx->aty[0], ctx->aty[1], h, ctx->part_at, ctx->dense.add_n);
-}
+// (Halpern mode: the twins' kernels; its A^T product gathers y' from its own buffer, which the kernels take inside HalpernArgs)
 static void launch_a_dual(pdlpdev_ctx* ctx, double* ycopy = nullptr, const p2pdev::Push* push = nullptr)
 {
-  if (ctx->halpern) return launch_a_halpern(ctx);
-  dense_part(ctx, 0, ctx->xbar, nullptr, 0, 1);
-  if (ctx->pba.on) {
-    (void)pb_products(ctx, ctx->pba, ctx->xbar, nullptr, 0, 1);
-    (void)pb_rows(ctx, k_pb_a_dual, ctx->pba, ctx->ctl, ctx->y[0], ctx->y[1], ctx->lo, ctx->hi, ctx->sumy, ctx->part_a, ycopy, push);
-  } else if (ctx->ja.on)
-    (void)JAG_LAUNCH(ctx, k_jag_a_dual, ctx->ja.v, ctx->ctl, ctx->xbar, ctx->y[0], ctx->y[1], ctx->lo, ctx->hi, ctx->sumy, ctx->part_a, ycopy, push);
-  else if (ctx->pa.on)
-    launch_k(ctx, ctx->pa.v.seg ? k_panel_a_dual<true> : k_panel_a_dual<false>, ctx->pa.v.W, kPanelThreads, 0, ctx->pa.v, ctx->ctl, ctx->xbar, ctx->y[0], ctx->y[1], ctx->lo, ctx->hi, ctx->sumy, ctx->part_a, ycopy, push);
-  else
-    launch_k(ctx, k_spmv_a_dual, stream_grid(ctx->a_nb), kBlock, 0, ctx->a_nb, ctx->a_rb, ctx->ha_off, ctx->ha_idx, ctx->ha_val, ctx->ctl, ctx->xbar, ctx->y[0], ctx->y[1], ctx->lo, ctx->hi, ctx->sumy, ctx->part_a, ycopy, push, ctx->dense.add_m);
+  const Gathered g{ctx->xbar, nullptr, 0, 1};
+  const auto pre  = std::make_tuple(ctx->ctl);
+  const auto vecs = std::make_tuple(ctx->xbar);
+  if (ctx->halpern) (void)launch_product(ctx, ctx->A, products::a_halpern, g, pre, vecs, std::make_tuple(ctx->y[0], ctx->y[1], ctx->lo, ctx->hi, halpern_args(ctx), ctx->A.part));
+  else (void)launch_product(ctx, ctx->A, products::a_dual, g, pre, vecs, std::make_tuple(ctx->y[0], ctx->y[1], ctx->lo, ctx->hi, ctx->sumy, ctx->A.part, ycopy, push));
 }
 static void launch_at_step(pdlpdev_ctx* ctx)
 {
-  if (ctx->halpern) return launch_at_halpern(ctx);
-  dense_part(ctx, 1, ctx->y[0], ctx->y[1], 1, 1);
-  if (ctx->pbat.on) {
-    (void)pb_products(ctx, ctx->pbat, ctx->y[0], ctx->y[1], 1, 1);  // y' = the trial dual
-    (void)pb_rows(ctx, k_pb_at_step, ctx->pbat, ctx->ctl, ctx->x[0], ctx->x[1], ctx->aty[0], ctx->aty[1], ctx->part_at);
-  } else if (ctx->jat.on)
-    (void)JAG_LAUNCH(ctx, k_jag_at_step, ctx->jat.v, ctx->ctl, ctx->y[0], ctx->y[1], ctx->x[0], ctx->x[1], ctx->aty[0], ctx->aty[1], ctx->part_at);
-  else if (ctx->pat.on)
-    launch_k(ctx, ctx->pat.v.seg ? k_panel_at_step<true> : k_panel_at_step<false>, ctx->pat.v.W, kPanelThreads, 0, ctx->pat.v, ctx->ctl, ctx->y[0], ctx->y[1], ctx->x[0], ctx->x[1], ctx->aty[0], ctx->aty[1], ctx->part_at);
-  else
-    launch_k(ctx, k_spmv_at_step, stream_grid(ctx->at_nb), kBlock, 0, ctx->at_nb, ctx->at_rb, ctx->hat_off, ctx->hat_idx, ctx->hat_val, ctx->ctl, ctx->y[0], ctx->y[1], ctx->x[0], ctx->x[1], ctx->aty[0], ctx->aty[1], ctx->part_at, ctx->dense.add_n);
+  const auto pre = std::make_tuple(ctx->ctl);
+  if (ctx->halpern)
+    (void)launch_product(ctx, ctx->At, products::at_halpern, Gathered{ctx->avgy, nullptr, 0, 1}, pre, std::make_tuple(),
+                         std::make_tuple(ctx->x[0], ctx->x[1], ctx->aty[0], ctx->aty[1], halpern_args(ctx), ctx->At.part));
+  else  // y' = the trial dual
+    (void)launch_product(ctx, ctx->At, products::at_step, Gathered{ctx->y[0], ctx->y[1], 1, 1}, pre, std::make_tuple(ctx->y[0], ctx->y[1]),
+                         std::make_tuple(ctx->x[0], ctx->x[1], ctx->aty[0], ctx->aty[1], ctx->At.part));
 }
 void launch_at_cur(pdlpdev_ctx* ctx, double* out_override, int use_next)
 {
-  dense_part(ctx, 1, ctx->y[0], ctx->y[1], use_next ? 1 : 2, 0);
-  if (ctx->pbat.on) {
-    (void)pb_products(ctx, ctx->pbat, ctx->y[0], ctx->y[1], use_next ? 1 : 2, 0);
-    (void)pb_rows(ctx, k_pb_at_cur, ctx->pbat, ctx->ctl, ctx->aty[0], ctx->aty[1], out_override, use_next);
-  } else if (ctx->jat.on)
-    (void)JAG_LAUNCH(ctx, k_jag_at_cur, ctx->jat.v, ctx->ctl, ctx->y[0], ctx->y[1], ctx->aty[0], ctx->aty[1], out_override, use_next);
-  else if (ctx->pat.on)
-    launch_k(ctx, ctx->pat.v.seg ? k_panel_at_cur<true> : k_panel_at_cur<false>, ctx->pat.v.W, kPanelThreads, 0, ctx->pat.v, ctx->ctl, ctx->y[0], ctx->y[1], ctx->aty[0], ctx->aty[1], out_override, use_next);
-  else
-    launch_k(ctx, k_spmv_at_cur, stream_grid(ctx->at_nb), kBlock, 0, ctx->at_nb, ctx->at_rb, ctx->hat_off, ctx->hat_idx, ctx->hat_val, ctx->ctl, ctx->y[0], ctx->y[1], ctx->aty[0], ctx->aty[1], out_override, use_next, ctx->dense.add_n);
+  (void)launch_product(ctx, ctx->At, products::at_cur, Gathered{ctx->y[0], ctx->y[1], use_next ? 1 : 2, 0}, std::make_tuple(ctx->ctl),
+                       std::make_tuple(ctx->y[0], ctx->y[1]), std::make_tuple(ctx->aty[0], ctx->aty[1], out_override, use_next));
 }
 // plain y = A x (transpose = 0) or y = A^T x through the layout the solver iterates with
 void launch_plain(pdlpdev_ctx* ctx, int transpose, const double* vec, double* out)
 {
-  dense_part(ctx, transpose, vec, nullptr, 0, 0);
-  if (transpose) {
-    if (ctx->pbat.on) {
-      (void)pb_products(ctx, ctx->pbat, vec, nullptr, 0, 0);
-      (void)pb_rows(ctx, k_pb_plain, ctx->pbat, out);
-    } else if (ctx->jat.on)
-      (void)JAG_LAUNCH(ctx, k_jag_plain, ctx->jat.v, vec, out);
-    else if (ctx->pat.on)
-      launch_k(ctx, ctx->pat.v.seg ? k_panel_plain<true> : k_panel_plain<false>, ctx->pat.v.W, kPanelThreads, 0, ctx->pat.v, vec, out);
-    else
-      launch_k(ctx, k_spmv_plain, stream_grid(ctx->at_nb), kBlock, 0, ctx->at_nb, ctx->at_rb, ctx->hat_off, ctx->hat_idx, ctx->hat_val, vec, out, ctx->dense.add_n);
-  } else {
-    if (ctx->pba.on) {
-      (void)pb_products(ctx, ctx->pba, vec, nullptr, 0, 0);
-      (void)pb_rows(ctx, k_pb_plain, ctx->pba, out);
-    } else if (ctx->ja.on)
-      (void)JAG_LAUNCH(ctx, k_jag_plain, ctx->ja.v, vec, out);
-    else if (ctx->pa.on)
-      launch_k(ctx, ctx->pa.v.seg ? k_panel_plain<true> : k_panel_plain<false>, ctx->pa.v.W, kPanelThreads, 0, ctx->pa.v, vec, out);
-    else
-      launch_k(ctx, k_spmv_plain, stream_grid(ctx->a_nb), kBlock, 0, ctx->a_nb, ctx->a_rb, ctx->ha_off, ctx->ha_idx, ctx->ha_val, vec, out, ctx->dense.add_m);
-  }
+  (void)launch_product(ctx, transpose ? ctx->At : ctx->A, products::plain, Gathered{vec, nullptr, 0, 0}, std::make_tuple(), std::make_tuple(vec), std::make_tuple(out));
 }
 static void launch_decision(pdlpdev_ctx* ctx)
 {
-  if (ctx->halpern) return launch_k(ctx, k_halpern_decision, 1, kDecisionThreads, 0, ctx->ctl, ctx->hal, ctx->part_a, dual_partials(ctx), ctx->part_at, step_partials(ctx));
-  launch_k(ctx, k_step_decision, 1, kDecisionThreads, 0, ctx->ctl, ctx->part_a, dual_partials(ctx), ctx->part_at, step_partials(ctx), nullptr, ctx->sp);
+  if (ctx->halpern) return launch_k(ctx, k_halpern_decision, 1, kDecisionThreads, 0, ctx->ctl, ctx->hal, ctx->A.part, ctx->A.partials(), ctx->At.part, ctx->At.partials());
+  launch_k(ctx, k_step_decision, 1, kDecisionThreads, 0, ctx->ctl, ctx->A.part, ctx->A.partials(), ctx->At.part, ctx->At.partials(), nullptr, ctx->sp);
 }
 
 // owner-computes dataflow: A^T y' of this rank's columns from the gathered y' (complete sums) + the step statistics of the slice
@@ -1005,12 +923,8 @@ static void launch_oc_step(pdlpdev_ctx* ctx)
   const size_t cs = (size_t)ctx->rank * ctx->slice;
   double *x0 = ctx->x[0] + cs, *x1 = ctx->x[1] + cs, *t0 = ctx->aty[0] + cs, *t1 = ctx->aty[1] + cs;
   const double* yg = ctx->ygather;  // the trial dual of every rank, whichever ping-pong buffer it lives in
-  if (ctx->joc.on)
-    (void)JAG_LAUNCH(ctx, k_jag_at_step, ctx->joc.v, ctx->ctl, yg, yg, x0, x1, t0, t1, ctx->part_oc);
-  else if (ctx->poc.on)
-    launch_k(ctx, ctx->poc.v.seg ? k_panel_at_step<true> : k_panel_at_step<false>, ctx->poc.v.W, kPanelThreads, 0, ctx->poc.v, ctx->ctl, yg, yg, x0, x1, t0, t1, ctx->part_oc);
-  else
-    launch_k(ctx, k_spmv_at_step, stream_grid(ctx->oc_nb), kBlock, 0, ctx->oc_nb, ctx->oc_rb, ctx->oc_off, ctx->oc_idx, ctx->oc_val, ctx->ctl, yg, yg, x0, x1, t0, t1, ctx->part_oc, (const double*)nullptr);
+  (void)launch_product(ctx, ctx->Oc, products::at_step, Gathered{yg, yg, 1, 1}, std::make_tuple(ctx->ctl), std::make_tuple(yg, yg),
+                       std::make_tuple(x0, x1, t0, t1, ctx->Oc.part));
 }
 
 // one PDHG attempt = 4 launches (single GPU) on ctx->stream
@@ -1021,7 +935,7 @@ static int enqueue_attempt(pdlpdev_ctx* ctx)
   //  the Halpern kernels -- k_primal is the same, pending_avg stays 0)
   if (ctx->halpern && ctx->comm) return fail(-7, "reflected Halpern mode: not available behind a communicator");
   if (ctx->owner) {
-    if (!ctx->oc_off) return fail(-1, "owner-computes dataflow: pdlpdev_owner_setup was not called");
+    if (!ctx->Oc.hot.off) return fail(-1, "owner-computes dataflow: pdlpdev_owner_setup was not called");
     const size_t cs = (size_t)ctx->rank * ctx->slice;
     const int len   = (int)std::max<int64_t>(0, std::min<int64_t>(ctx->slice, (int64_t)n - (int64_t)cs));
     launch_k(ctx, k_primal, grid_for(len), kBlock, 0, len, ctx->ctl, ctx->x[0] + cs, ctx->x[1] + cs, ctx->aty[0] + cs, ctx->aty[1] + cs,
@@ -1055,7 +969,7 @@ static int enqueue_attempt(pdlpdev_ctx* ctx)
       if (ctx->halo.on) pull_ranges(1, ctx->ygather, P.off_y);
       else pull(1, ctx->ygather, P.off_y, ctx->ypad);
       launch_oc_step(ctx);
-      launch_k(ctx, k_step_decision_p2p, 1, kBlock, 0, ctx->ctl, ctx->part_a, dual_partials(ctx), ctx->part_oc, oc_partials(ctx),
+      launch_k(ctx, k_step_decision_p2p, 1, kBlock, 0, ctx->ctl, ctx->A.part, ctx->A.partials(), ctx->Oc.part, ctx->Oc.partials(),
                reinterpret_cast<const double*>(P.base + P.off_s), flags, W, P.epoch, P.fault, ctx->sp, P.push_dev + 2);
       LAUNCH_CHECK();
       return 0;
@@ -1067,7 +981,7 @@ static int enqueue_attempt(pdlpdev_ctx* ctx)
     if (ctx->halo.on) TRY(halo_exchange(ctx, 1, ctx->ygather));
     else TRY(all_gather(ctx, ctx->ygather, (size_t)ctx->ypad));
     launch_oc_step(ctx);
-    launch_k(ctx, k_pack_step_sums, 1, kBlock, 0, ctx->part_a, dual_partials(ctx), ctx->part_oc, oc_partials(ctx), ctx->rs_scal);
+    launch_k(ctx, k_pack_step_sums, 1, kBlock, 0, ctx->A.part, ctx->A.partials(), ctx->Oc.part, ctx->Oc.partials(), ctx->rs_scal);
     LAUNCH_CHECK();
     TRY(allreduce(ctx, ctx->rs_scal, 3, rccl::kSum));
     launch_k(ctx, k_step_decision, 1, kDecisionThreads, 0, ctx->ctl, nullptr, 0, ctx->rs_scal + 1, 1, ctx->rs_scal, ctx->sp);
@@ -1090,7 +1004,7 @@ static int enqueue_attempt(pdlpdev_ctx* ctx)
     TRY(reduce_scatter(ctx, ctx->ar_buf, ctx->rs_buf, (size_t)ctx->slice));
     const int g = std::min(grid_for(len), kGenericBlocks);
     launch_k(ctx, k_step_stats, g, kBlock, 0, len, g, ctx->ctl, ctx->rs_buf, ctx->x[0] + cs, ctx->x[1] + cs, ctx->aty[0] + cs, ctx->aty[1] + cs, ctx->part_g);
-    launch_k(ctx, k_pack_step_sums, 1, kBlock, 0, ctx->part_a, dual_partials(ctx), ctx->part_g, g, ctx->rs_scal);
+    launch_k(ctx, k_pack_step_sums, 1, kBlock, 0, ctx->A.part, ctx->A.partials(), ctx->part_g, g, ctx->rs_scal);
     LAUNCH_CHECK();
     TRY(allreduce(ctx, ctx->rs_scal, 3, rccl::kSum));
     launch_k(ctx, k_step_decision, 1, kDecisionThreads, 0, ctx->ctl, nullptr, 0, ctx->rs_scal + 1, 1, ctx->rs_scal, ctx->sp);
@@ -1105,7 +1019,7 @@ static int enqueue_attempt(pdlpdev_ctx* ctx)
   } else {
     // partial A^T y' of this row block -> ar_buf[0..n), ||dy||^2 partial -> ar_buf[n]; ONE all-reduce
     launch_at_cur(ctx, ctx->ar_buf, 1);
-    launch_k(ctx, k_sum_partials_to, 1, kBlock, 0, ctx->part_a, dual_partials(ctx), ctx->ar_buf + n);
+    launch_k(ctx, k_sum_partials_to, 1, kBlock, 0, ctx->A.part, ctx->A.partials(), ctx->ar_buf + n);
     LAUNCH_CHECK();
     TRY(allreduce(ctx, ctx->ar_buf, (size_t)n + 1, rccl::kSum));
     const int g = std::min(grid_for(n), kGenericBlocks);
@@ -1296,8 +1210,9 @@ int pdlpdev_run_period(pdlpdev_ctx* ctx, int32_t target_steps, const pdlpdev_sma
     if (ctl) *ctl = *ctx->ctl_h;
     return 0;
   }
-  const bool dense_unfused = ctx->dense.on && !(ctx->pat.v.dn_pan_ptr != nullptr && ctx->pa.v.dn_own_seg != nullptr);
-  const bool eligible = !ctx->comm && !ctx->small_resident && ctx->pa.on && ctx->pat.on && !dense_unfused && ctx->ctl_h_current &&
+  const bool both_panels   = ctx->A.layout() == pdlpdev_ctx::MatrixSide::kPanel && ctx->At.layout() == pdlpdev_ctx::MatrixSide::kPanel;
+  const bool dense_unfused = ctx->dense.on && !(ctx->At.fuses_dense() && ctx->A.fuses_dense());
+  const bool eligible = !ctx->comm && !ctx->small_resident && both_panels && !dense_unfused && ctx->ctl_h_current &&
                         !(rq->eps_p >= 0.0 && rq->eps_d >= 0.0) && ctx->ctl_h->error == 0 && ctx->ctl_h->steps_taken < target_steps;
   if (!eligible) return pdlpdev_run(ctx, target_steps, ctl);
   roctx::Range range("pdlp: PDHG attempts + major iteration evaluation");
@@ -1464,8 +1379,8 @@ static int64_t locate_buffer(pdlpdev_ctx* ctx, int id, double** ptr)
     case PDLPDEV_BUF_AVG_Y: src = ctx->avgy, count = m; break;
     case PDLPDEV_BUF_DROW: src = ctx->dr, count = m; break;
     case PDLPDEV_BUF_DCOL: src = ctx->dc, count = n; break;
-    case PDLPDEV_BUF_A_VALUES: src = ctx->a_val, count = nnz; break;
-    case PDLPDEV_BUF_AT_VALUES: src = ctx->at_val, count = nnz; break;
+    case PDLPDEV_BUF_A_VALUES: src = ctx->A.full.val, count = nnz; break;
+    case PDLPDEV_BUF_AT_VALUES: src = ctx->At.full.val, count = nnz; break;
     case PDLPDEV_BUF_C: src = ctx->c, count = n; break;
     case PDLPDEV_BUF_LB: src = ctx->lb, count = n; break;
     case PDLPDEV_BUF_UB: src = ctx->ub, count = n; break;
@@ -1751,13 +1666,8 @@ int pdlpdev_layout_info(pdlpdev_ctx* ctx, int32_t out[8])
 {
   // per matrix: layout (0 CSR stream, 1 slab-major panels, 2 resident single-workgroup loop, 3 jagged rows + LDS column
   // sets), workgroups, slabs (panels) or percent of the global gathers the LDS sets save (jagged)
-  out[0] = ctx->pba.on ? 4 : ctx->ja.on ? 3 : ctx->pa.on ? 1 : 0;
-  out[1] = ctx->pba.on ? ctx->pba.v.B : ctx->ja.on ? ctx->ja.v.nblk : ctx->pa.on ? ctx->pa.v.W : ctx->a_nb;
-  out[2] = ctx->pba.on ? (int)(100.0 * (ctx->pba.pad - 1.0) + 0.5) : ctx->ja.on ? (int)(100.0 * ctx->ja.saving + 0.5) : ctx->pa.on ? ctx->pa.v.S : 1;
-  out[3] = ctx->pbat.on ? 4 : ctx->jat.on ? 3 : ctx->pat.on ? 1 : 0;
-  out[4] = ctx->pbat.on ? ctx->pbat.v.B : ctx->jat.on ? ctx->jat.v.nblk : ctx->pat.on ? ctx->pat.v.W : ctx->at_nb;
-  out[5] = ctx->pbat.on ? (int)(100.0 * (ctx->pbat.pad - 1.0) + 0.5) : ctx->jat.on ? (int)(100.0 * ctx->jat.saving + 0.5) : ctx->pat.on ? ctx->pat.v.S : 1;
-  out[6] = ctx->pa.on && ctx->pa.v.seg, out[7] = ctx->pat.on && ctx->pat.v.seg;  // panels: the long-tail variant (row sums by nonzero)
+  ctx->A.info(out), ctx->At.info(out + 3);
+  out[6] = ctx->A.pan.on && ctx->A.pan.v.seg, out[7] = ctx->At.pan.on && ctx->At.pan.v.seg;  // panels: the long-tail variant (row sums by nonzero)
   if (ctx->small_resident) out[0] = out[3] = 2;
   return 0;
 }
@@ -1779,9 +1689,9 @@ int pdlpdev_debug_layout_checksums(pdlpdev_ctx* ctx, uint64_t out[16])
   HIP_TRY(hipStreamSynchronize(ctx->stream));
   for (int i = 0; i < 16; ++i) out[i] = 0;
   const size_t nnz = (size_t)ctx->nnz;
-  out[0] = checksum_device(ctx, ctx->at_off, ((size_t)ctx->n + 1) * 4);
-  out[1] = checksum_device(ctx, ctx->at_idx, nnz * 4);
-  out[2] = checksum_device(ctx, ctx->at_val, nnz * 8);
+  out[0] = checksum_device(ctx, ctx->At.full.off, ((size_t)ctx->n + 1) * 4);
+  out[1] = checksum_device(ctx, ctx->At.full.idx, nnz * 4);
+  out[2] = checksum_device(ctx, ctx->At.full.val, nnz * 8);
   auto panels = [&](const pdlpdev_ctx::Panels& P, int32_t rows, uint64_t* o) {
     if (!P.on) return;
     const int NP = P.v.NP ? P.v.NP : P.v.W;
@@ -1791,8 +1701,8 @@ int pdlpdev_debug_layout_checksums(pdlpdev_ctx* ctx, uint64_t out[16])
     o[3] = checksum_device(ctx, P.v.col, (size_t)P.nent * 4);
     o[4] = checksum_device(ctx, P.perm, (size_t)P.nent * 4);
   };
-  panels(ctx->pa, ctx->m, out + 3);
-  panels(ctx->pat, ctx->n, out + 8);
+  panels(ctx->A.pan, ctx->m, out + 3);
+  panels(ctx->At.pan, ctx->n, out + 8);
   auto gather_free = [&](const pdlpdev_ctx::Pb& P, int64_t side_nnz, uint64_t* o) {  // (a side is in ONE layout: the panels' slots)
     if (!P.on) return;
     const PbView& v = P.v;
@@ -1817,8 +1727,8 @@ int pdlpdev_debug_layout_checksums(pdlpdev_ctx* ctx, uint64_t out[16])
     o[3] = checksum_device(ctx, v.pos, (size_t)side_nnz * 2) ^ (checksum_device(ctx, v.sr, (size_t)v.rows * 4) * 3);
     o[4] ^= (checksum_device(ctx, v.bin_grp, ((size_t)v.B + 1) * 4) * 11) ^ (checksum_device(ctx, v.grp_pos, ((size_t)groups + 1) * 4) * 13);
   };
-  gather_free(ctx->pba, ctx->dense.on ? ctx->dense.hot_nnz : ctx->nnz, out + 3);
-  gather_free(ctx->pbat, ctx->dense.on ? ctx->hot_nnz_at : ctx->nnz, out + 8);
+  gather_free(ctx->A.pb, ctx->dense.on ? ctx->A.hot_nnz : ctx->nnz, out + 3);
+  gather_free(ctx->At.pb, ctx->dense.on ? ctx->At.hot_nnz : ctx->nnz, out + 8);
   auto jag = [&](const pdlpdev_ctx::Jag& J) -> uint64_t {
     if (!J.on) return 0;
     int32_t nsr = 0, nset = 0;
@@ -1831,11 +1741,11 @@ int pdlpdev_debug_layout_checksums(pdlpdev_ctx* ctx, uint64_t out[16])
            (checksum_device(ctx, J.v.set_col, (size_t)nset * 4) * 23) ^ (checksum_device(ctx, J.v.lr_ptr, ((size_t)J.v.nblk + 1) * 4) * 29) ^
            (checksum_device(ctx, J.v.lr_row, (size_t)J.v.nlong * 4) * 31) ^ (uint64_t)J.v.waves * 37;
   };
-  out[13] = jag(ctx->ja), out[14] = jag(ctx->jat);
-  out[15] = (uint64_t)ctx->pa.on | (uint64_t)ctx->pat.on << 1 | (uint64_t)ctx->ja.on << 2 | (uint64_t)ctx->jat.on << 3 |
-            (uint64_t)(ctx->pa.on && ctx->pa.v.seg) << 4 | (uint64_t)(ctx->pat.on && ctx->pat.v.seg) << 5 | (uint64_t)ctx->pba.on << 6 |
-            (uint64_t)ctx->pbat.on << 7 | (uint64_t)(ctx->pa.v.dn_own_seg != nullptr) << 8 | (uint64_t)(ctx->pat.v.dn_pan_ptr != nullptr) << 9 |
-            (uint64_t)ctx->joc.on << 10 | (uint64_t)ctx->poc.on << 11;
+  out[13] = jag(ctx->A.jag), out[14] = jag(ctx->At.jag);
+  out[15] = (uint64_t)ctx->A.pan.on | (uint64_t)ctx->At.pan.on << 1 | (uint64_t)ctx->A.jag.on << 2 | (uint64_t)ctx->At.jag.on << 3 |
+            (uint64_t)(ctx->A.pan.on && ctx->A.pan.v.seg) << 4 | (uint64_t)(ctx->At.pan.on && ctx->At.pan.v.seg) << 5 | (uint64_t)ctx->A.pb.on << 6 |
+            (uint64_t)ctx->At.pb.on << 7 | (uint64_t)(ctx->A.pan.v.dn_own_seg != nullptr) << 8 | (uint64_t)(ctx->At.pan.v.dn_pan_ptr != nullptr) << 9 |
+            (uint64_t)ctx->Oc.jag.on << 10 | (uint64_t)ctx->Oc.pan.on << 11;
   return 0;
 }
 

@@ -350,28 +350,21 @@ static int enqueue_eval(pdlpdev_ctx* ctx, int which, int rc_rule_finite_bounds, 
   const double* altx = which == PDLPDEV_LAST_RESTART ? ctx->lrx : ctx->avgx;
   const double* alty = which == PDLPDEV_LAST_RESTART ? ctx->lry : ctx->avgy;
   const int kw       = which == PDLPDEV_CURRENT ? PDLPDEV_CURRENT : PDLPDEV_AVERAGE;
-  const int kwg      = kw | (guard ? kPeriodGuard : 0);  // (only the panel kernels know the flag: pdlpdev_run_period asks for no other layout)
+  const int kwg      = kw | (guard ? kPeriodGuard : 0);  // (only the panel kernels know the flag: guarded_eval_layouts turned every other layout away)
   // the per-constraint (l-infinity) residuals are only consumed when per_constraint_residual is set: the host
   // driver passes negative eps_rel otherwise and the two extra vectors + four reduction launches are skipped
   const bool want_linf = eps_rel_primal >= 0.0 && eps_rel_dual >= 0.0;
   double* linf_m = want_linf ? ctx->tmp_m : nullptr;
   double* linf_n = want_linf ? ctx->tmp_n : nullptr;
   // layout of sc: [0..2] primal sums, [3] primal linf, [4..7] dual sums, [8] dual linf
-  if (kw == PDLPDEV_AVERAGE) dense_part(ctx, 0, altx, nullptr, 0, 0);
-  else dense_part(ctx, 0, ctx->x[0], ctx->x[1], 2, 0);
-  if (ctx->pba.on) {
-    if (kw == PDLPDEV_AVERAGE) TRY(pb_products(ctx, ctx->pba, altx, nullptr, 0, 0));
-    else TRY(pb_products(ctx, ctx->pba, ctx->x[0], ctx->x[1], 2, 0));
-    TRY(pb_rows(ctx, k_pb_eval_primal, ctx->pba, ctx->ctl, kw, ctx->y[0], ctx->y[1], alty, ctx->dr, ctx->lo_u, ctx->hi_u, eps_rel_primal, linf_m, ctx->ax_u[which], ctx->part_a));
-  } else if (ctx->ja.on)
-    (void)JAG_LAUNCH(ctx, k_jag_eval_primal, ctx->ja.v, ctx->ctl, kw, ctx->x[0], ctx->x[1], altx, ctx->y[0], ctx->y[1], alty, ctx->dr, ctx->lo_u, ctx->hi_u, eps_rel_primal, linf_m, ctx->ax_u[which], ctx->part_a);
-  else if (ctx->pa.on)
-    (ctx->pa.v.seg ? k_panel_eval_primal<true> : k_panel_eval_primal<false>)<<<ctx->pa.v.W, kPanelThreads, 0, s>>>(ctx->pa.v, ctx->ctl, kwg, ctx->x[0], ctx->x[1], altx, ctx->y[0], ctx->y[1], alty, ctx->dr, ctx->lo_u, ctx->hi_u, eps_rel_primal, linf_m, ctx->ax_u[which], ctx->part_a);
-  else
-    k_eval_primal<<<stream_grid(ctx->a_nb), kBlock, 0, s>>>(ctx->a_nb, ctx->a_rb, ctx->ha_off, ctx->ha_idx, ctx->ha_val, ctx->ctl, kw, ctx->x[0], ctx->x[1], altx, ctx->y[0], ctx->y[1], alty, ctx->dr, ctx->lo_u, ctx->hi_u, eps_rel_primal, linf_m, ctx->ax_u[which], ctx->part_a, ctx->dense.add_m);
+  // the vectors the two products gather: the alternative iterate itself, or the current one as the control block names it
+  const bool alt = kw == PDLPDEV_AVERAGE;
+  TRY(launch_product(ctx, ctx->A, products::eval_primal, alt ? Gathered{altx, nullptr, 0, 0} : Gathered{ctx->x[0], ctx->x[1], 2, 0}, std::make_tuple(ctx->ctl, kwg),
+                     std::make_tuple(ctx->x[0], ctx->x[1], altx),
+                     std::make_tuple(ctx->y[0], ctx->y[1], alty, ctx->dr, ctx->lo_u, ctx->hi_u, eps_rel_primal, linf_m, ctx->ax_u[which], ctx->A.part)));
   // one reduction launch for both sides of the evaluation where nothing else needs the primal sums in between
   const bool one_finalize = !ctx->comm && !want_linf;
-  if (!one_finalize) k_finalize<<<1, kBlock, 0, s>>>(ctx->part_a, dual_partials(ctx), 3, 0u, sc + 0);
+  if (!one_finalize) k_finalize<<<1, kBlock, 0, s>>>(ctx->A.part, ctx->A.partials(), 3, 0u, sc + 0);
   if (want_linf) {
     const int g = std::min(grid_for(m), kGenericBlocks);
     k_max_partials<<<g, kBlock, 0, s>>>(m, ctx->tmp_m, ctx->part_g);
@@ -380,25 +373,15 @@ static int enqueue_eval(pdlpdev_ctx* ctx, int which, int rc_rule_finite_bounds, 
   EvalDualCore core{nullptr, ctx->dc, ctx->c_u, ctx->lb_u, ctx->ub_u, eps_rel_dual, rc_rule_finite_bounds, which == PDLPDEV_LAST_RESTART ? ctx->rc_scratch : ctx->rc[which == PDLPDEV_AVERAGE ? 1 : 0], linf_n, ctx->aty_u[which]};
   // The current iterate's A^T y is in the loop's buffer (pdlp_ctx.hpp aty_valid): the product-free twin reads it there.  Behind the
   // guard the evaluation runs only when the attempts enqueued in front of it accepted a step, which is what makes the buffer valid.
-  const bool reuse = which == PDLPDEV_CURRENT && ctx->eval_reuse_aty && !ctx->comm && ctx->pat.on && (ctx->aty_valid || guard);
+  const bool reuse = which == PDLPDEV_CURRENT && ctx->eval_reuse_aty && !ctx->comm && ctx->At.layout() == pdlpdev_ctx::MatrixSide::kPanel && (ctx->aty_valid || guard);
   if (which == PDLPDEV_CURRENT && !ctx->comm) (reuse ? ctx->stat_eval_reused : ctx->stat_eval_product) += 1;
   if (reuse) {
-    k_panel_eval_dual_from_aty<<<ctx->pat.v.W, kPanelThreads, 0, s>>>(ctx->pat.v, ctx->ctl, ctx->x[0], ctx->x[1], ctx->aty[0], ctx->aty[1], core, ctx->part_at, guard);
-    k_finalize_eval<<<1, kBlock, 0, s>>>(ctx->part_a, dual_partials(ctx), ctx->part_at, step_partials(ctx), one_finalize ? 1 : 0, sc, ctx->ctl, guard, ctl_copy);
+    k_panel_eval_dual_from_aty<<<ctx->At.pan.v.W, kPanelThreads, 0, s>>>(ctx->At.pan.v, ctx->ctl, ctx->x[0], ctx->x[1], ctx->aty[0], ctx->aty[1], core, ctx->At.part, guard);
+    k_finalize_eval<<<1, kBlock, 0, s>>>(ctx->A.part, ctx->A.partials(), ctx->At.part, ctx->At.partials(), one_finalize ? 1 : 0, sc, ctx->ctl, guard, ctl_copy);
   } else if (!ctx->comm) {
-    if (kw == PDLPDEV_AVERAGE) dense_part(ctx, 1, alty, nullptr, 0, 0);
-    else dense_part(ctx, 1, ctx->y[0], ctx->y[1], 2, 0);
-    if (ctx->pbat.on) {
-      if (kw == PDLPDEV_AVERAGE) TRY(pb_products(ctx, ctx->pbat, alty, nullptr, 0, 0));
-      else TRY(pb_products(ctx, ctx->pbat, ctx->y[0], ctx->y[1], 2, 0));
-      TRY(pb_rows(ctx, k_pb_eval_dual, ctx->pbat, ctx->ctl, kw, ctx->x[0], ctx->x[1], altx, core, ctx->part_at));
-    } else if (ctx->jat.on)
-      (void)JAG_LAUNCH(ctx, k_jag_eval_dual, ctx->jat.v, ctx->ctl, kw, ctx->x[0], ctx->x[1], altx, ctx->y[0], ctx->y[1], alty, core, ctx->part_at);
-    else if (ctx->pat.on)
-      (ctx->pat.v.seg ? k_panel_eval_dual<true> : k_panel_eval_dual<false>)<<<ctx->pat.v.W, kPanelThreads, 0, s>>>(ctx->pat.v, ctx->ctl, kwg, ctx->x[0], ctx->x[1], altx, ctx->y[0], ctx->y[1], alty, core, ctx->part_at);
-    else
-      k_eval_dual<<<stream_grid(ctx->at_nb), kBlock, 0, s>>>(ctx->at_nb, ctx->at_rb, ctx->hat_off, ctx->hat_idx, ctx->hat_val, ctx->ctl, kw, ctx->x[0], ctx->x[1], altx, ctx->y[0], ctx->y[1], alty, core, ctx->part_at, ctx->dense.add_n);
-    k_finalize_eval<<<1, kBlock, 0, s>>>(ctx->part_a, dual_partials(ctx), ctx->part_at, step_partials(ctx), one_finalize ? 1 : 0, sc, ctx->ctl, guard, ctl_copy);
+    TRY(launch_product(ctx, ctx->At, products::eval_dual, alt ? Gathered{alty, nullptr, 0, 0} : Gathered{ctx->y[0], ctx->y[1], 2, 0},
+                       std::make_tuple(ctx->ctl, kwg, ctx->x[0], ctx->x[1], altx), std::make_tuple(ctx->y[0], ctx->y[1], alty), std::make_tuple(core, ctx->At.part)));
+    k_finalize_eval<<<1, kBlock, 0, s>>>(ctx->A.part, ctx->A.partials(), ctx->At.part, ctx->At.partials(), one_finalize ? 1 : 0, sc, ctx->ctl, guard, ctl_copy);
   } else {
     // partial A^T y of this row block, all-reduced together with the three dual-side row sums
     if (kw == PDLPDEV_AVERAGE) {
@@ -465,8 +448,16 @@ int pdlpdev_major_eval(pdlpdev_ctx* ctx, int average_mode, int rc_rule_finite_bo
   read_eval(ctx->scal_h + 32, want_linf, out_average);
   return 0;
 }
+// the guard travels inside `which`, and only the panel kernels know the flag (pdlpdev_run_period asks for it on panel contexts alone)
+static int guarded_eval_layouts(const pdlpdev_ctx* ctx, int guard, const char* who)
+{
+  const auto panel = pdlpdev_ctx::MatrixSide::kPanel;
+  if (guard && !(ctx->A.layout() == panel && ctx->At.layout() == panel)) return fail(-1, "%s: a guarded evaluation needs slab-major panels on both sides", who);
+  return 0;
+}
 int enqueue_major_eval(pdlpdev_ctx* ctx, int average_mode, int rc_rule_finite_bounds, double eps_rel_primal, double eps_rel_dual, int guard)
 {
+  TRY(guarded_eval_layouts(ctx, guard, "enqueue_major_eval"));
   hipStream_t s = ctx->stream;
   const int g   = grid_for(std::max(ctx->n, ctx->m));
   // (k_clear_pending rides on k_make_average: one dependent launch less)
@@ -481,6 +472,7 @@ int enqueue_major_eval(pdlpdev_ctx* ctx, int average_mode, int rc_rule_finite_bo
 }
 int enqueue_halpern_eval(pdlpdev_ctx* ctx, int rc_rule_finite_bounds, double eps_rel_primal, double eps_rel_dual, int guard)
 {
+  TRY(guarded_eval_layouts(ctx, guard, "enqueue_halpern_eval"));
   return enqueue_eval(ctx, PDLPDEV_AVERAGE, rc_rule_finite_bounds, eps_rel_primal, eps_rel_dual, ctx->scal + 32, guard, guard ? ctx->scal + kCtlSlot : nullptr);
 }
 void read_major_eval(pdlpdev_ctx* ctx, double* out_current, double* out_average)

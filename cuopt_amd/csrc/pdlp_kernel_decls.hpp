@@ -1,8 +1,22 @@
 // Prototypes of the SpMV kernels, which are DEFINED one layout per translation unit (kernels_<layout>.hip) and launched from the
-// core (pdlp_device.hip); the templated ones are instantiated explicitly where they are defined.  Generated once from the
-// definitions when the file was split (round 4); keep the two in step.
+// core through launch_product (pdlp_launch.hpp); the templated ones are instantiated explicitly where they are defined.  A templated
+// kernel's parameter list is written ONCE here: the macros below turn it into the template's declaration and the explicit-instantiation
+// declarations of its two variants.  The panel and the jagged kernel of a product take the same arguments behind their view; the
+// gather-free row kernel takes them without the gathered vectors, which phase P (k_pb_products) consumed.
 #pragma once
 #include "pdlp_epilogues.hpp"
+
+#define KERNEL_PAIR(TPARAM, BOUNDS, NAME, V0, V1, ...)                            \
+  template <TPARAM>                                                               \
+  __global__ void __launch_bounds__(BOUNDS) NAME(__VA_ARGS__);                    \
+  extern template __global__ void NAME<V0>(__VA_ARGS__);                          \
+  extern template __global__ void NAME<V1>(__VA_ARGS__);
+// k_panel_<product><SEG> (SEG: the long-tail variant) and k_jag_<product><WAVES> (the two geometries)
+#define ROW_KERNELS(PRODUCT, ...)                                                              \
+  KERNEL_PAIR(bool SEG, kPanelThreads, k_panel_##PRODUCT, true, false, PanelView P, __VA_ARGS__) \
+  KERNEL_PAIR(int WAVES, WAVES * 64, k_jag_##PRODUCT, 8, 16, JagView J, __VA_ARGS__)
+// k_pb_<product><WIDE> (phase R: WIDE = the wide-bin skeleton, 1024 threads; otherwise the image-in-LDS skeleton, 512)
+#define PB_KERNEL(PRODUCT, ...) KERNEL_PAIR(bool WIDE, WIDE ? kPbwThreads : kPbThreads, k_pb_##PRODUCT, false, true, PbView V, __VA_ARGS__)
 
 __global__ void __launch_bounds__(kBlock)
 k_spmv_a_dual(int nb, const int32_t* __restrict__ rb, const int32_t* __restrict__ off,
@@ -44,238 +58,23 @@ k_eval_dual(int nb, const int32_t* __restrict__ rb, const int32_t* __restrict__ 
             const double* __restrict__ x1, const double* __restrict__ avgx,
             const double* __restrict__ y0, const double* __restrict__ y1,
             const double* __restrict__ avgy, EvalDualCore core, double* __restrict__ part, const double* __restrict__ dadd);
-template <bool SEG>
-__global__ void __launch_bounds__(kPanelThreads)
-k_panel_a_dual(PanelView P, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ xbar,
-               double* __restrict__ y0, double* __restrict__ y1, const double* __restrict__ lo,
-               const double* __restrict__ hi, double* __restrict__ sumy, double* __restrict__ part, double* __restrict__ ycopy,
-               const p2pdev::Push* __restrict__ push);
-extern template __global__ void k_panel_a_dual<true>(PanelView P, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ xbar,
-               double* __restrict__ y0, double* __restrict__ y1, const double* __restrict__ lo,
-               const double* __restrict__ hi, double* __restrict__ sumy, double* __restrict__ part, double* __restrict__ ycopy,
-               const p2pdev::Push* __restrict__ push);
-extern template __global__ void k_panel_a_dual<false>(PanelView P, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ xbar,
-               double* __restrict__ y0, double* __restrict__ y1, const double* __restrict__ lo,
-               const double* __restrict__ hi, double* __restrict__ sumy, double* __restrict__ part, double* __restrict__ ycopy,
-               const p2pdev::Push* __restrict__ push);
-template <bool SEG>
-__global__ void __launch_bounds__(kPanelThreads)
-k_panel_at_step(PanelView P, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ y0,
-                const double* __restrict__ y1, const double* __restrict__ x0,
-                const double* __restrict__ x1, double* __restrict__ aty0, double* __restrict__ aty1,
-                double* __restrict__ part);
-extern template __global__ void k_panel_at_step<true>(PanelView P, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ y0,
-                const double* __restrict__ y1, const double* __restrict__ x0,
-                const double* __restrict__ x1, double* __restrict__ aty0, double* __restrict__ aty1,
-                double* __restrict__ part);
-extern template __global__ void k_panel_at_step<false>(PanelView P, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ y0,
-                const double* __restrict__ y1, const double* __restrict__ x0,
-                const double* __restrict__ x1, double* __restrict__ aty0, double* __restrict__ aty1,
-                double* __restrict__ part);
-template <bool SEG>
-__global__ void __launch_bounds__(kPanelThreads)
-k_panel_at_cur(PanelView P, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ y0,
-               const double* __restrict__ y1, double* __restrict__ aty0, double* __restrict__ aty1,
-               double* __restrict__ out_override, int use_next);
-extern template __global__ void k_panel_at_cur<true>(PanelView P, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ y0,
-               const double* __restrict__ y1, double* __restrict__ aty0, double* __restrict__ aty1,
-               double* __restrict__ out_override, int use_next);
-extern template __global__ void k_panel_at_cur<false>(PanelView P, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ y0,
-               const double* __restrict__ y1, double* __restrict__ aty0, double* __restrict__ aty1,
-               double* __restrict__ out_override, int use_next);
-template <bool SEG>
-__global__ void __launch_bounds__(kPanelThreads)
-k_panel_plain(PanelView P, const double* __restrict__ vec, double* __restrict__ out);
-extern template __global__ void k_panel_plain<true>(PanelView P, const double* __restrict__ vec, double* __restrict__ out);
-extern template __global__ void k_panel_plain<false>(PanelView P, const double* __restrict__ vec, double* __restrict__ out);
-template <bool SEG>
-__global__ void __launch_bounds__(kPanelThreads)
-k_panel_eval_primal(PanelView P, const pdlpdev_ctl* __restrict__ ctl, int which,
-                    const double* __restrict__ x0, const double* __restrict__ x1,
-                    const double* __restrict__ avgx, const double* __restrict__ y0,
-                    const double* __restrict__ y1, const double* __restrict__ avgy,
-                    const double* __restrict__ dr, const double* __restrict__ lo_u,
-                    const double* __restrict__ hi_u, double eps_rel, double* __restrict__ linf_rows,
-                    double* __restrict__ ax_out, double* __restrict__ part);
-extern template __global__ void k_panel_eval_primal<true>(PanelView P, const pdlpdev_ctl* __restrict__ ctl, int which,
-                    const double* __restrict__ x0, const double* __restrict__ x1,
-                    const double* __restrict__ avgx, const double* __restrict__ y0,
-                    const double* __restrict__ y1, const double* __restrict__ avgy,
-                    const double* __restrict__ dr, const double* __restrict__ lo_u,
-                    const double* __restrict__ hi_u, double eps_rel, double* __restrict__ linf_rows,
-                    double* __restrict__ ax_out, double* __restrict__ part);
-extern template __global__ void k_panel_eval_primal<false>(PanelView P, const pdlpdev_ctl* __restrict__ ctl, int which,
-                    const double* __restrict__ x0, const double* __restrict__ x1,
-                    const double* __restrict__ avgx, const double* __restrict__ y0,
-                    const double* __restrict__ y1, const double* __restrict__ avgy,
-                    const double* __restrict__ dr, const double* __restrict__ lo_u,
-                    const double* __restrict__ hi_u, double eps_rel, double* __restrict__ linf_rows,
-                    double* __restrict__ ax_out, double* __restrict__ part);
-template <bool SEG>
-__global__ void __launch_bounds__(kPanelThreads)
-k_panel_eval_dual(PanelView P, const pdlpdev_ctl* __restrict__ ctl, int which,
-                  const double* __restrict__ x0, const double* __restrict__ x1,
-                  const double* __restrict__ avgx, const double* __restrict__ y0,
-                  const double* __restrict__ y1, const double* __restrict__ avgy, EvalDualCore core,
-                  double* __restrict__ part);
-extern template __global__ void k_panel_eval_dual<true>(PanelView P, const pdlpdev_ctl* __restrict__ ctl, int which,
-                  const double* __restrict__ x0, const double* __restrict__ x1,
-                  const double* __restrict__ avgx, const double* __restrict__ y0,
-                  const double* __restrict__ y1, const double* __restrict__ avgy, EvalDualCore core,
-                  double* __restrict__ part);
-extern template __global__ void k_panel_eval_dual<false>(PanelView P, const pdlpdev_ctl* __restrict__ ctl, int which,
-                  const double* __restrict__ x0, const double* __restrict__ x1,
-                  const double* __restrict__ avgx, const double* __restrict__ y0,
-                  const double* __restrict__ y1, const double* __restrict__ avgy, EvalDualCore core,
-                  double* __restrict__ part);
+ROW_KERNELS(a_dual, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ xbar, double* __restrict__ y0, double* __restrict__ y1, const double* __restrict__ lo, const double* __restrict__ hi, double* __restrict__ sumy, double* __restrict__ part, double* __restrict__ ycopy, const p2pdev::Push* __restrict__ push)
+PB_KERNEL(a_dual, const pdlpdev_ctl* __restrict__ ctl, double* __restrict__ y0, double* __restrict__ y1, const double* __restrict__ lo, const double* __restrict__ hi, double* __restrict__ sumy, double* __restrict__ part, double* __restrict__ ycopy, const p2pdev::Push* __restrict__ push)
+ROW_KERNELS(at_step, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ y0, const double* __restrict__ y1, const double* __restrict__ x0, const double* __restrict__ x1, double* __restrict__ aty0, double* __restrict__ aty1, double* __restrict__ part)
+PB_KERNEL(at_step, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ x0, const double* __restrict__ x1, double* __restrict__ aty0, double* __restrict__ aty1, double* __restrict__ part)
+ROW_KERNELS(at_cur, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ y0, const double* __restrict__ y1, double* __restrict__ aty0, double* __restrict__ aty1, double* __restrict__ out_override, int use_next)
+PB_KERNEL(at_cur, const pdlpdev_ctl* __restrict__ ctl, double* __restrict__ aty0, double* __restrict__ aty1, double* __restrict__ out_override, int use_next)
+ROW_KERNELS(plain, const double* __restrict__ vec, double* __restrict__ out)
+PB_KERNEL(plain, double* __restrict__ out)
+ROW_KERNELS(eval_primal, const pdlpdev_ctl* __restrict__ ctl, int which, const double* __restrict__ x0, const double* __restrict__ x1, const double* __restrict__ avgx, const double* __restrict__ y0, const double* __restrict__ y1, const double* __restrict__ avgy, const double* __restrict__ dr, const double* __restrict__ lo_u, const double* __restrict__ hi_u, double eps_rel, double* __restrict__ linf_rows, double* __restrict__ ax_out, double* __restrict__ part)
+PB_KERNEL(eval_primal, const pdlpdev_ctl* __restrict__ ctl, int which, const double* __restrict__ y0, const double* __restrict__ y1, const double* __restrict__ avgy, const double* __restrict__ dr, const double* __restrict__ lo_u, const double* __restrict__ hi_u, double eps_rel, double* __restrict__ linf_rows, double* __restrict__ ax_out, double* __restrict__ part)
+ROW_KERNELS(eval_dual, const pdlpdev_ctl* __restrict__ ctl, int which, const double* __restrict__ x0, const double* __restrict__ x1, const double* __restrict__ avgx, const double* __restrict__ y0, const double* __restrict__ y1, const double* __restrict__ avgy, EvalDualCore core, double* __restrict__ part)
+PB_KERNEL(eval_dual, const pdlpdev_ctl* __restrict__ ctl, int which, const double* __restrict__ x0, const double* __restrict__ x1, const double* __restrict__ avgx, EvalDualCore core, double* __restrict__ part)
 __global__ void __launch_bounds__(kPanelThreads)
 k_panel_eval_dual_from_aty(PanelView P, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ x0, const double* __restrict__ x1,
                            const double* __restrict__ aty0, const double* __restrict__ aty1, EvalDualCore core,
                            double* __restrict__ part, int guard);
-template <int WAVES>
-__global__ void __launch_bounds__(WAVES * 64)
-k_jag_a_dual(JagView J, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ xbar,
-             double* __restrict__ y0, double* __restrict__ y1, const double* __restrict__ lo,
-             const double* __restrict__ hi, double* __restrict__ sumy, double* __restrict__ part, double* __restrict__ ycopy,
-             const p2pdev::Push* __restrict__ push);
-extern template __global__ void k_jag_a_dual<8>(JagView J, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ xbar,
-             double* __restrict__ y0, double* __restrict__ y1, const double* __restrict__ lo,
-             const double* __restrict__ hi, double* __restrict__ sumy, double* __restrict__ part, double* __restrict__ ycopy,
-             const p2pdev::Push* __restrict__ push);
-extern template __global__ void k_jag_a_dual<16>(JagView J, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ xbar,
-             double* __restrict__ y0, double* __restrict__ y1, const double* __restrict__ lo,
-             const double* __restrict__ hi, double* __restrict__ sumy, double* __restrict__ part, double* __restrict__ ycopy,
-             const p2pdev::Push* __restrict__ push);
-template <int WAVES>
-__global__ void __launch_bounds__(WAVES * 64)
-k_jag_at_step(JagView J, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ y0,
-              const double* __restrict__ y1, const double* __restrict__ x0,
-              const double* __restrict__ x1, double* __restrict__ aty0, double* __restrict__ aty1,
-              double* __restrict__ part);
-extern template __global__ void k_jag_at_step<8>(JagView J, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ y0,
-              const double* __restrict__ y1, const double* __restrict__ x0,
-              const double* __restrict__ x1, double* __restrict__ aty0, double* __restrict__ aty1,
-              double* __restrict__ part);
-extern template __global__ void k_jag_at_step<16>(JagView J, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ y0,
-              const double* __restrict__ y1, const double* __restrict__ x0,
-              const double* __restrict__ x1, double* __restrict__ aty0, double* __restrict__ aty1,
-              double* __restrict__ part);
-template <int WAVES>
-__global__ void __launch_bounds__(WAVES * 64)
-k_jag_at_cur(JagView J, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ y0,
-             const double* __restrict__ y1, double* __restrict__ aty0, double* __restrict__ aty1,
-             double* __restrict__ out_override, int use_next);
-extern template __global__ void k_jag_at_cur<8>(JagView J, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ y0,
-             const double* __restrict__ y1, double* __restrict__ aty0, double* __restrict__ aty1,
-             double* __restrict__ out_override, int use_next);
-extern template __global__ void k_jag_at_cur<16>(JagView J, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ y0,
-             const double* __restrict__ y1, double* __restrict__ aty0, double* __restrict__ aty1,
-             double* __restrict__ out_override, int use_next);
-template <int WAVES>
-__global__ void __launch_bounds__(WAVES * 64)
-k_jag_plain(JagView J, const double* __restrict__ vec, double* __restrict__ out);
-extern template __global__ void k_jag_plain<8>(JagView J, const double* __restrict__ vec, double* __restrict__ out);
-extern template __global__ void k_jag_plain<16>(JagView J, const double* __restrict__ vec, double* __restrict__ out);
-template <int WAVES>
-__global__ void __launch_bounds__(WAVES * 64)
-k_jag_eval_primal(JagView J, const pdlpdev_ctl* __restrict__ ctl, int which,
-                  const double* __restrict__ x0, const double* __restrict__ x1,
-                  const double* __restrict__ avgx, const double* __restrict__ y0,
-                  const double* __restrict__ y1, const double* __restrict__ avgy,
-                  const double* __restrict__ dr, const double* __restrict__ lo_u,
-                  const double* __restrict__ hi_u, double eps_rel, double* __restrict__ linf_rows,
-                  double* __restrict__ ax_out, double* __restrict__ part);
-extern template __global__ void k_jag_eval_primal<8>(JagView J, const pdlpdev_ctl* __restrict__ ctl, int which,
-                  const double* __restrict__ x0, const double* __restrict__ x1,
-                  const double* __restrict__ avgx, const double* __restrict__ y0,
-                  const double* __restrict__ y1, const double* __restrict__ avgy,
-                  const double* __restrict__ dr, const double* __restrict__ lo_u,
-                  const double* __restrict__ hi_u, double eps_rel, double* __restrict__ linf_rows,
-                  double* __restrict__ ax_out, double* __restrict__ part);
-extern template __global__ void k_jag_eval_primal<16>(JagView J, const pdlpdev_ctl* __restrict__ ctl, int which,
-                  const double* __restrict__ x0, const double* __restrict__ x1,
-                  const double* __restrict__ avgx, const double* __restrict__ y0,
-                  const double* __restrict__ y1, const double* __restrict__ avgy,
-                  const double* __restrict__ dr, const double* __restrict__ lo_u,
-                  const double* __restrict__ hi_u, double eps_rel, double* __restrict__ linf_rows,
-                  double* __restrict__ ax_out, double* __restrict__ part);
-template <int WAVES>
-__global__ void __launch_bounds__(WAVES * 64)
-k_jag_eval_dual(JagView J, const pdlpdev_ctl* __restrict__ ctl, int which,
-                const double* __restrict__ x0, const double* __restrict__ x1,
-                const double* __restrict__ avgx, const double* __restrict__ y0,
-                const double* __restrict__ y1, const double* __restrict__ avgy, EvalDualCore core,
-                double* __restrict__ part);
-extern template __global__ void k_jag_eval_dual<8>(JagView J, const pdlpdev_ctl* __restrict__ ctl, int which,
-                const double* __restrict__ x0, const double* __restrict__ x1,
-                const double* __restrict__ avgx, const double* __restrict__ y0,
-                const double* __restrict__ y1, const double* __restrict__ avgy, EvalDualCore core,
-                double* __restrict__ part);
-extern template __global__ void k_jag_eval_dual<16>(JagView J, const pdlpdev_ctl* __restrict__ ctl, int which,
-                const double* __restrict__ x0, const double* __restrict__ x1,
-                const double* __restrict__ avgx, const double* __restrict__ y0,
-                const double* __restrict__ y1, const double* __restrict__ avgy, EvalDualCore core,
-                double* __restrict__ part);
-template <int THREADS>
-__global__ void __launch_bounds__(THREADS)
-k_pb_products(PbView V, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ v0, const double* __restrict__ v1, int mode, int in_loop);
-extern template __global__ void k_pb_products<512>(PbView V, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ v0, const double* __restrict__ v1, int mode, int in_loop);
-extern template __global__ void k_pb_products<1024>(PbView V, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ v0, const double* __restrict__ v1, int mode, int in_loop);
-// (phase R: WIDE = the wide-bin skeleton, 1024 threads; otherwise the image-in-LDS skeleton, 512)
-template <bool WIDE>
-__global__ void __launch_bounds__(WIDE ? kPbwThreads : kPbThreads)
-k_pb_a_dual(PbView V, const pdlpdev_ctl* __restrict__ ctl, double* __restrict__ y0, double* __restrict__ y1, const double* __restrict__ lo,
-            const double* __restrict__ hi, double* __restrict__ sumy, double* __restrict__ part, double* __restrict__ ycopy,
-            const p2pdev::Push* __restrict__ push);
-extern template __global__ void k_pb_a_dual<false>(PbView V, const pdlpdev_ctl* __restrict__ ctl, double* __restrict__ y0, double* __restrict__ y1, const double* __restrict__ lo,
-            const double* __restrict__ hi, double* __restrict__ sumy, double* __restrict__ part, double* __restrict__ ycopy,
-            const p2pdev::Push* __restrict__ push);
-extern template __global__ void k_pb_a_dual<true>(PbView V, const pdlpdev_ctl* __restrict__ ctl, double* __restrict__ y0, double* __restrict__ y1, const double* __restrict__ lo,
-            const double* __restrict__ hi, double* __restrict__ sumy, double* __restrict__ part, double* __restrict__ ycopy,
-            const p2pdev::Push* __restrict__ push);
-template <bool WIDE>
-__global__ void __launch_bounds__(WIDE ? kPbwThreads : kPbThreads)
-k_pb_at_step(PbView V, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ x0, const double* __restrict__ x1,
-             double* __restrict__ aty0, double* __restrict__ aty1, double* __restrict__ part);
-extern template __global__ void k_pb_at_step<false>(PbView V, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ x0, const double* __restrict__ x1,
-             double* __restrict__ aty0, double* __restrict__ aty1, double* __restrict__ part);
-extern template __global__ void k_pb_at_step<true>(PbView V, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ x0, const double* __restrict__ x1,
-             double* __restrict__ aty0, double* __restrict__ aty1, double* __restrict__ part);
-template <bool WIDE>
-__global__ void __launch_bounds__(WIDE ? kPbwThreads : kPbThreads)
-k_pb_at_cur(PbView V, const pdlpdev_ctl* __restrict__ ctl, double* __restrict__ aty0, double* __restrict__ aty1,
-            double* __restrict__ out_override, int use_next);
-extern template __global__ void k_pb_at_cur<false>(PbView V, const pdlpdev_ctl* __restrict__ ctl, double* __restrict__ aty0, double* __restrict__ aty1,
-            double* __restrict__ out_override, int use_next);
-extern template __global__ void k_pb_at_cur<true>(PbView V, const pdlpdev_ctl* __restrict__ ctl, double* __restrict__ aty0, double* __restrict__ aty1,
-            double* __restrict__ out_override, int use_next);
-template <bool WIDE>
-__global__ void __launch_bounds__(WIDE ? kPbwThreads : kPbThreads)
-k_pb_plain(PbView V, double* __restrict__ out);
-extern template __global__ void k_pb_plain<false>(PbView V, double* __restrict__ out);
-extern template __global__ void k_pb_plain<true>(PbView V, double* __restrict__ out);
-template <bool WIDE>
-__global__ void __launch_bounds__(WIDE ? kPbwThreads : kPbThreads)
-k_pb_eval_primal(PbView V, const pdlpdev_ctl* __restrict__ ctl, int which, const double* __restrict__ y0, const double* __restrict__ y1,
-                 const double* __restrict__ avgy, const double* __restrict__ dr, const double* __restrict__ lo_u,
-                 const double* __restrict__ hi_u, double eps_rel, double* __restrict__ linf_rows, double* __restrict__ ax_out,
-                 double* __restrict__ part);
-extern template __global__ void k_pb_eval_primal<false>(PbView V, const pdlpdev_ctl* __restrict__ ctl, int which, const double* __restrict__ y0, const double* __restrict__ y1,
-                 const double* __restrict__ avgy, const double* __restrict__ dr, const double* __restrict__ lo_u,
-                 const double* __restrict__ hi_u, double eps_rel, double* __restrict__ linf_rows, double* __restrict__ ax_out,
-                 double* __restrict__ part);
-extern template __global__ void k_pb_eval_primal<true>(PbView V, const pdlpdev_ctl* __restrict__ ctl, int which, const double* __restrict__ y0, const double* __restrict__ y1,
-                 const double* __restrict__ avgy, const double* __restrict__ dr, const double* __restrict__ lo_u,
-                 const double* __restrict__ hi_u, double eps_rel, double* __restrict__ linf_rows, double* __restrict__ ax_out,
-                 double* __restrict__ part);
-template <bool WIDE>
-__global__ void __launch_bounds__(WIDE ? kPbwThreads : kPbThreads)
-k_pb_eval_dual(PbView V, const pdlpdev_ctl* __restrict__ ctl, int which, const double* __restrict__ x0, const double* __restrict__ x1,
-               const double* __restrict__ avgx, EvalDualCore core, double* __restrict__ part);
-extern template __global__ void k_pb_eval_dual<false>(PbView V, const pdlpdev_ctl* __restrict__ ctl, int which, const double* __restrict__ x0, const double* __restrict__ x1,
-               const double* __restrict__ avgx, EvalDualCore core, double* __restrict__ part);
-extern template __global__ void k_pb_eval_dual<true>(PbView V, const pdlpdev_ctl* __restrict__ ctl, int which, const double* __restrict__ x0, const double* __restrict__ x1,
-               const double* __restrict__ avgx, EvalDualCore core, double* __restrict__ part);
+KERNEL_PAIR(int THREADS, THREADS, k_pb_products, 512, 1024, PbView V, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ v0, const double* __restrict__ v1, int mode, int in_loop)
 __global__ void __launch_bounds__(kBlock)
 k_dense_rows(DenseView D, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ v0, const double* __restrict__ v1, int mode, int in_loop);
 __global__ void __launch_bounds__(kBlock)
@@ -297,57 +96,7 @@ k_spmv_at_halpern(int nb, const int32_t* __restrict__ rb, const int32_t* __restr
                   const pdlpdev_ctl* __restrict__ ctl, double* __restrict__ x0, double* __restrict__ x1,
                   double* __restrict__ aty0, double* __restrict__ aty1, HalpernArgs h,
                   double* __restrict__ part, const double* __restrict__ dadd);
-template <bool SEG>
-__global__ void __launch_bounds__(kPanelThreads)
-k_panel_a_halpern(PanelView P, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ xbar,
-                  double* __restrict__ y0, double* __restrict__ y1, const double* __restrict__ lo,
-                  const double* __restrict__ hi, HalpernArgs h, double* __restrict__ part);
-extern template __global__ void k_panel_a_halpern<true>(PanelView P, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ xbar,
-                  double* __restrict__ y0, double* __restrict__ y1, const double* __restrict__ lo,
-                  const double* __restrict__ hi, HalpernArgs h, double* __restrict__ part);
-extern template __global__ void k_panel_a_halpern<false>(PanelView P, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ xbar,
-                  double* __restrict__ y0, double* __restrict__ y1, const double* __restrict__ lo,
-                  const double* __restrict__ hi, HalpernArgs h, double* __restrict__ part);
-template <bool SEG>
-__global__ void __launch_bounds__(kPanelThreads)
-k_panel_at_halpern(PanelView P, const pdlpdev_ctl* __restrict__ ctl, double* __restrict__ x0, double* __restrict__ x1,
-                   double* __restrict__ aty0, double* __restrict__ aty1, HalpernArgs h, double* __restrict__ part);
-extern template __global__ void k_panel_at_halpern<true>(PanelView P, const pdlpdev_ctl* __restrict__ ctl, double* __restrict__ x0, double* __restrict__ x1,
-                   double* __restrict__ aty0, double* __restrict__ aty1, HalpernArgs h, double* __restrict__ part);
-extern template __global__ void k_panel_at_halpern<false>(PanelView P, const pdlpdev_ctl* __restrict__ ctl, double* __restrict__ x0, double* __restrict__ x1,
-                   double* __restrict__ aty0, double* __restrict__ aty1, HalpernArgs h, double* __restrict__ part);
-template <int WAVES>
-__global__ void __launch_bounds__(WAVES * 64)
-k_jag_a_halpern(JagView J, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ xbar,
-                double* __restrict__ y0, double* __restrict__ y1, const double* __restrict__ lo,
-                const double* __restrict__ hi, HalpernArgs h, double* __restrict__ part);
-extern template __global__ void k_jag_a_halpern<8>(JagView J, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ xbar,
-                double* __restrict__ y0, double* __restrict__ y1, const double* __restrict__ lo,
-                const double* __restrict__ hi, HalpernArgs h, double* __restrict__ part);
-extern template __global__ void k_jag_a_halpern<16>(JagView J, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ xbar,
-                double* __restrict__ y0, double* __restrict__ y1, const double* __restrict__ lo,
-                const double* __restrict__ hi, HalpernArgs h, double* __restrict__ part);
-template <int WAVES>
-__global__ void __launch_bounds__(WAVES * 64)
-k_jag_at_halpern(JagView J, const pdlpdev_ctl* __restrict__ ctl, double* __restrict__ x0, double* __restrict__ x1,
-                 double* __restrict__ aty0, double* __restrict__ aty1, HalpernArgs h, double* __restrict__ part);
-extern template __global__ void k_jag_at_halpern<8>(JagView J, const pdlpdev_ctl* __restrict__ ctl, double* __restrict__ x0, double* __restrict__ x1,
-                 double* __restrict__ aty0, double* __restrict__ aty1, HalpernArgs h, double* __restrict__ part);
-extern template __global__ void k_jag_at_halpern<16>(JagView J, const pdlpdev_ctl* __restrict__ ctl, double* __restrict__ x0, double* __restrict__ x1,
-                 double* __restrict__ aty0, double* __restrict__ aty1, HalpernArgs h, double* __restrict__ part);
-template <bool WIDE>
-__global__ void __launch_bounds__(WIDE ? kPbwThreads : kPbThreads)
-k_pb_a_halpern(PbView V, const pdlpdev_ctl* __restrict__ ctl, double* __restrict__ y0, double* __restrict__ y1, const double* __restrict__ lo,
-               const double* __restrict__ hi, HalpernArgs h, double* __restrict__ part);
-extern template __global__ void k_pb_a_halpern<false>(PbView V, const pdlpdev_ctl* __restrict__ ctl, double* __restrict__ y0, double* __restrict__ y1, const double* __restrict__ lo,
-               const double* __restrict__ hi, HalpernArgs h, double* __restrict__ part);
-extern template __global__ void k_pb_a_halpern<true>(PbView V, const pdlpdev_ctl* __restrict__ ctl, double* __restrict__ y0, double* __restrict__ y1, const double* __restrict__ lo,
-               const double* __restrict__ hi, HalpernArgs h, double* __restrict__ part);
-template <bool WIDE>
-__global__ void __launch_bounds__(WIDE ? kPbwThreads : kPbThreads)
-k_pb_at_halpern(PbView V, const pdlpdev_ctl* __restrict__ ctl, double* __restrict__ x0, double* __restrict__ x1,
-                double* __restrict__ aty0, double* __restrict__ aty1, HalpernArgs h, double* __restrict__ part);
-extern template __global__ void k_pb_at_halpern<false>(PbView V, const pdlpdev_ctl* __restrict__ ctl, double* __restrict__ x0, double* __restrict__ x1,
-                double* __restrict__ aty0, double* __restrict__ aty1, HalpernArgs h, double* __restrict__ part);
-extern template __global__ void k_pb_at_halpern<true>(PbView V, const pdlpdev_ctl* __restrict__ ctl, double* __restrict__ x0, double* __restrict__ x1,
-                double* __restrict__ aty0, double* __restrict__ aty1, HalpernArgs h, double* __restrict__ part);
+ROW_KERNELS(a_halpern, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ xbar, double* __restrict__ y0, double* __restrict__ y1, const double* __restrict__ lo, const double* __restrict__ hi, HalpernArgs h, double* __restrict__ part)
+PB_KERNEL(a_halpern, const pdlpdev_ctl* __restrict__ ctl, double* __restrict__ y0, double* __restrict__ y1, const double* __restrict__ lo, const double* __restrict__ hi, HalpernArgs h, double* __restrict__ part)
+ROW_KERNELS(at_halpern, const pdlpdev_ctl* __restrict__ ctl, double* __restrict__ x0, double* __restrict__ x1, double* __restrict__ aty0, double* __restrict__ aty1, HalpernArgs h, double* __restrict__ part)
+PB_KERNEL(at_halpern, const pdlpdev_ctl* __restrict__ ctl, double* __restrict__ x0, double* __restrict__ x1, double* __restrict__ aty0, double* __restrict__ aty1, HalpernArgs h, double* __restrict__ part)

@@ -112,8 +112,7 @@ PanelHost build_panels(int32_t rows, int32_t cols, const int32_t* off, const int
                               int64_t slab_bytes, bool force, const std::vector<int32_t>* dense_first_seg = nullptr);
 int upload_panels(pdlpdev_ctx* c, pdlpdev_ctx::Panels* dst, const PanelHost& h, const int32_t* d_off, const int32_t* d_idx,
                          const double* d_val);
-int pick_layout(pdlpdev_ctx* c, pdlpdev_ctx::Panels* pn, int rows, int nb, const int32_t* rb, const int32_t* off,
-                       const int32_t* idx, const double* val, const double* vec, double* out, const char* name);
+int pick_layout(pdlpdev_ctx* c, pdlpdev_ctx::MatrixSide* side, const double* vec, double* out);
 JagHost build_jag(int32_t rows, int32_t cols, const int32_t* off, const int32_t* idx, int mode, int cus, int batch_lanes = 0);
 int upload_jag(pdlpdev_ctx* c, pdlpdev_ctx::Jag* dst, const JagHost& h, const int32_t* d_off, const int32_t* d_idx,
                       const double* d_val);

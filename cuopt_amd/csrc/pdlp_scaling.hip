@@ -171,9 +171,23 @@ __global__ void __launch_bounds__(kBlock) k_scale_matrix_long(const int32_t* __r
   for (int k = off[r] + (int)threadIdx.x; k < off[r + 1]; k += kBlock) val[k] = val[k] * ds * d_other[idx[k]];
 }
 
+// (the row blocks were cut on the hot CSR: the set-up kernels, which run on the full one, use them when the two are the same)
+static bool stream_blocks_usable(const pdlpdev_ctx::MatrixSide& M) { return M.hot.off == M.full.off && M.nb > 0; }
+// one side's row norms of a scaling pass -> out (A: per row, A^T: per column)
+template <bool TRANSPOSED, bool POW>
+static void row_norms(pdlpdev_ctx* ctx, const pdlpdev_ctx::MatrixSide& M, double e, double* out)
+{
+  const pdlpdev_ctx::Csr& F = M.full;
+  hipStream_t s = ctx->stream;
+  if (stream_blocks_usable(M)) k_row_norm_blocks<TRANSPOSED, POW><<<M.nb, kBlock, 0, s>>>(M.nb, M.rb, F.off, F.idx, F.val, ctx->dr, ctx->dc, e, out);
+  else k_row_norm<TRANSPOSED, POW><<<grid_for(M.rows), kBlock, 0, s>>>(M.rows, F.off, F.idx, F.val, ctx->dr, ctx->dc, e, out);
+  if (M.nlong) k_row_norm_long<TRANSPOSED, POW><<<M.nlong, kBlock, 0, s>>>(M.longs, F.off, F.idx, F.val, ctx->dr, ctx->dc, e, out);
+}
+
 extern "C" {
 
 // ---- setup ----------------------------------------------------------------------------------------
+
 int pdlpdev_scaling_compute(pdlpdev_ctx* ctx, int do_ruiz, int ruiz_iterations, int do_pc, double alpha)
 {
   roctx::Range range("pdlp: Ruiz + Pock-Chambolle scaling");
@@ -183,26 +197,12 @@ int pdlpdev_scaling_compute(pdlpdev_ctx* ctx, int do_ruiz, int ruiz_iterations, 
   k_fill<<<grid_for(m), kBlock, 0, s>>>(m, ctx->dr, 1.0);
   k_fill<<<grid_for(n), kBlock, 0, s>>>(n, ctx->dc, 1.0);
   auto pass = [&](bool pow_mode, double e_row, double e_col) -> int {
-    // (the row blocks were cut on the hot CSR: usable when that is the full one)
-    const bool blocks_a = ctx->ha_off == ctx->a_off && ctx->a_nb > 0, blocks_t = ctx->hat_off == ctx->at_off && ctx->at_nb > 0;
     if (!pow_mode) {
-      if (blocks_a) k_row_norm_blocks<false, false><<<ctx->a_nb, kBlock, 0, s>>>(ctx->a_nb, ctx->a_rb, ctx->a_off, ctx->a_idx, ctx->a_val, ctx->dr, ctx->dc, 1.0, ctx->tmp_m);
-      else
-      k_row_norm<false, false><<<grid_for(m), kBlock, 0, s>>>(m, ctx->a_off, ctx->a_idx, ctx->a_val, ctx->dr, ctx->dc, 1.0, ctx->tmp_m);
-      if (ctx->a_nlong) k_row_norm_long<false, false><<<ctx->a_nlong, kBlock, 0, s>>>(ctx->a_long, ctx->a_off, ctx->a_idx, ctx->a_val, ctx->dr, ctx->dc, 1.0, ctx->tmp_m);
-      if (blocks_t) k_row_norm_blocks<true, false><<<ctx->at_nb, kBlock, 0, s>>>(ctx->at_nb, ctx->at_rb, ctx->at_off, ctx->at_idx, ctx->at_val, ctx->dr, ctx->dc, 1.0, ctx->tmp_n);
-      else
-      k_row_norm<true, false><<<grid_for(n), kBlock, 0, s>>>(n, ctx->at_off, ctx->at_idx, ctx->at_val, ctx->dr, ctx->dc, 1.0, ctx->tmp_n);
-      if (ctx->at_nlong) k_row_norm_long<true, false><<<ctx->at_nlong, kBlock, 0, s>>>(ctx->at_long, ctx->at_off, ctx->at_idx, ctx->at_val, ctx->dr, ctx->dc, 1.0, ctx->tmp_n);
+      row_norms<false, false>(ctx, ctx->A, 1.0, ctx->tmp_m);
+      row_norms<true, false>(ctx, ctx->At, 1.0, ctx->tmp_n);
     } else {
-      if (blocks_a) k_row_norm_blocks<false, true><<<ctx->a_nb, kBlock, 0, s>>>(ctx->a_nb, ctx->a_rb, ctx->a_off, ctx->a_idx, ctx->a_val, ctx->dr, ctx->dc, e_row, ctx->tmp_m);
-      else
-      k_row_norm<false, true><<<grid_for(m), kBlock, 0, s>>>(m, ctx->a_off, ctx->a_idx, ctx->a_val, ctx->dr, ctx->dc, e_row, ctx->tmp_m);
-      if (ctx->a_nlong) k_row_norm_long<false, true><<<ctx->a_nlong, kBlock, 0, s>>>(ctx->a_long, ctx->a_off, ctx->a_idx, ctx->a_val, ctx->dr, ctx->dc, e_row, ctx->tmp_m);
-      if (blocks_t) k_row_norm_blocks<true, true><<<ctx->at_nb, kBlock, 0, s>>>(ctx->at_nb, ctx->at_rb, ctx->at_off, ctx->at_idx, ctx->at_val, ctx->dr, ctx->dc, e_col, ctx->tmp_n);
-      else
-      k_row_norm<true, true><<<grid_for(n), kBlock, 0, s>>>(n, ctx->at_off, ctx->at_idx, ctx->at_val, ctx->dr, ctx->dc, e_col, ctx->tmp_n);
-      if (ctx->at_nlong) k_row_norm_long<true, true><<<ctx->at_nlong, kBlock, 0, s>>>(ctx->at_long, ctx->at_off, ctx->at_idx, ctx->at_val, ctx->dr, ctx->dc, e_col, ctx->tmp_n);
+      row_norms<false, true>(ctx, ctx->A, e_row, ctx->tmp_m);
+      row_norms<true, true>(ctx, ctx->At, e_col, ctx->tmp_n);
     }
     LAUNCH_CHECK();
     // row-block sharding: a column's norm is spread over the ranks
@@ -224,14 +224,15 @@ int pdlpdev_scale_problem(pdlpdev_ctx* ctx)
   HIP_TRY(hipSetDevice(ctx->device));
   if (ctx->scaled) return fail(-1, "problem already scaled");
   hipStream_t s = ctx->stream;
-  if (ctx->ha_off == ctx->a_off && ctx->a_nb > 0) k_scale_matrix_blocks<<<ctx->a_nb, kBlock, 0, s>>>(ctx->a_nb, ctx->a_rb, ctx->a_off, ctx->a_idx, ctx->a_val, ctx->dr, ctx->dc);
-  else
-  k_scale_matrix<<<grid_for(ctx->m), kBlock, 0, s>>>(ctx->m, ctx->a_off, ctx->a_idx, ctx->a_val, ctx->dr, ctx->dc);
-  if (ctx->a_nlong) k_scale_matrix_long<<<ctx->a_nlong, kBlock, 0, s>>>(ctx->a_long, ctx->a_off, ctx->a_idx, ctx->a_val, ctx->dr, ctx->dc);
-  if (ctx->hat_off == ctx->at_off && ctx->at_nb > 0) k_scale_matrix_blocks<<<ctx->at_nb, kBlock, 0, s>>>(ctx->at_nb, ctx->at_rb, ctx->at_off, ctx->at_idx, ctx->at_val, ctx->dc, ctx->dr);
-  else
-  k_scale_matrix<<<grid_for(ctx->n), kBlock, 0, s>>>(ctx->n, ctx->at_off, ctx->at_idx, ctx->at_val, ctx->dc, ctx->dr);
-  if (ctx->at_nlong) k_scale_matrix_long<<<ctx->at_nlong, kBlock, 0, s>>>(ctx->at_long, ctx->at_off, ctx->at_idx, ctx->at_val, ctx->dc, ctx->dr);
+  const double* d[2] = {ctx->dr, ctx->dc};
+  int t = 0;
+  for (const pdlpdev_ctx::MatrixSide* M : {&ctx->A, &ctx->At}) {  // (val * d_self[row]) * d_other[column], each side by its own rows
+    const pdlpdev_ctx::Csr& F = M->full;
+    if (stream_blocks_usable(*M)) k_scale_matrix_blocks<<<M->nb, kBlock, 0, s>>>(M->nb, M->rb, F.off, F.idx, F.val, d[t], d[1 - t]);
+    else k_scale_matrix<<<grid_for(M->rows), kBlock, 0, s>>>(M->rows, F.off, F.idx, F.val, d[t], d[1 - t]);
+    if (M->nlong) k_scale_matrix_long<<<M->nlong, kBlock, 0, s>>>(M->longs, F.off, F.idx, F.val, d[t], d[1 - t]);
+    ++t;
+  }
   k_scale_vectors<<<grid_for(std::max(ctx->m, ctx->n)), kBlock, 0, s>>>(ctx->n, ctx->m, ctx->c, ctx->lb, ctx->ub, ctx->dc, ctx->lo, ctx->hi, ctx->dr);
   LAUNCH_CHECK();
   ctx->scaled = true;

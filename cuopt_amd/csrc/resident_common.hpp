@@ -58,7 +58,7 @@ __device__ __forceinline__ void small_rows(int rows, const int32_t* __restrict__
 inline MajorSmallArgs major_args(const pdlpdev_ctx* ctx, int average_mode, int rc_rule_finite_bounds, int want_linf, double eps_rel_primal, double eps_rel_dual)
 {
   return MajorSmallArgs{ctx->m, ctx->n, average_mode, rc_rule_finite_bounds, want_linf, eps_rel_primal, eps_rel_dual,
-                        ctx->a_off, ctx->a_idx, ctx->at_off, ctx->at_idx, ctx->a_val, ctx->at_val, ctx->ctl,
+                        ctx->A.full.off, ctx->A.full.idx, ctx->At.full.off, ctx->At.full.idx, ctx->A.full.val, ctx->At.full.val, ctx->ctl,
                         ctx->x[0], ctx->x[1], ctx->y[0], ctx->y[1], ctx->sumx, ctx->sumy, ctx->avgx, ctx->avgy,
                         ctx->dr, ctx->dc, ctx->c_u, ctx->lb_u, ctx->ub_u, ctx->lo_u, ctx->hi_u, ctx->tmp_m, ctx->tmp_n,
                         ctx->ax_u[PDLPDEV_CURRENT], ctx->ax_u[PDLPDEV_AVERAGE], ctx->aty_u[PDLPDEV_CURRENT],
