@@ -345,12 +345,14 @@ PDLP_SOLVER_MODE_HALPERN1 = 4  # CUOPT_AMD_PDLP_SOLVER_MODE_HALPERN1 (cuopt_c_ex
 BUF = {n: i for i, n in enumerate(
     ["X", "Y", "X_OTHER", "Y_OTHER", "ATY", "ATY_OTHER", "XBAR", "SUM_X", "SUM_Y", "AVG_X", "AVG_Y",
      "DROW", "DCOL", "A_VALUES", "AT_VALUES", "C", "LB", "UB", "LO", "HI", "RC_CURRENT", "RC_AVERAGE",
-     "LAST_RESTART_X", "LAST_RESTART_Y", "ATY_U_CURRENT", "ATY_U_AVERAGE", "LAST_RESTART_ATY"])}
+     "LAST_RESTART_X", "LAST_RESTART_Y", "ATY_U_CURRENT", "ATY_U_AVERAGE", "LAST_RESTART_ATY",
+     "AX_U_CURRENT", "AX_U_AVERAGE"])}
 KERNEL = {n: i for i, n in enumerate(
     ["PRIMAL", "SPMV_A_DUAL", "SPMV_AT_STEP", "STEP_DECISION", "SPMV_A_PLAIN", "SPMV_AT_PLAIN"])}
 EV = {n: i for i, n in enumerate(
     ["CX", "DUAL_SUM", "PRES2", "DRES2", "X2", "Y2", "LINF_PRES_REL", "LINF_DRES_REL"])}
 CURRENT, AVERAGE = 0, 1
+LAST_RESTART = 2  # PDLPDEV_LAST_RESTART: pdlpdev_eval / pdlpdev_trust_region_bounds only
 
 
 class CuOptError(RuntimeError):

@@ -1396,6 +1396,8 @@ static int64_t locate_buffer(pdlpdev_ctx* ctx, int id, double** ptr)
       if (!ctx->lraty) { fail(-1, "buffer %d exists in Halpern mode only", id); return -1; }
       src = ctx->lraty, count = n;
       break;
+    case PDLPDEV_BUF_AX_U_CURRENT: src = ctx->ax_u[PDLPDEV_CURRENT], count = m; break;
+    case PDLPDEV_BUF_AX_U_AVERAGE: src = ctx->ax_u[PDLPDEV_AVERAGE], count = m; break;
     default: fail(-1, "unknown buffer %d", id); return -1;
   }
   *ptr = src;

@@ -124,6 +124,8 @@ enum {
   PDLPDEV_BUF_ATY_U_CURRENT, /* A^T y of the unscaled problem from the last eval(CURRENT)  n */
   PDLPDEV_BUF_ATY_U_AVERAGE, /*                                                            n */
   PDLPDEV_BUF_LAST_RESTART_ATY, /* Halpern mode: A^T y of the anchor (scaled)               n */
+  PDLPDEV_BUF_AX_U_CURRENT, /* A x of the unscaled problem from the last eval(CURRENT)    m */
+  PDLPDEV_BUF_AX_U_AVERAGE, /*                                                            m */
   PDLPDEV_BUF_COUNT
 };
 

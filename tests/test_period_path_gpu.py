@@ -12,6 +12,7 @@ import pytest
 from conftest import set_tune
 
 from cuopt_amd import capi, synthetic
+from eval_lps import with_long_column as _with_long_column
 
 pytestmark = pytest.mark.gpu
 
@@ -19,23 +20,6 @@ pytestmark = pytest.mark.gpu
 @pytest.fixture(autouse=True)
 def multi_launch_kernels(monkeypatch):
     monkeypatch.setenv("CUOPT_AMD_SMALL", "0")  # these LPs are small: keep them off the resident one-workgroup path
-
-
-def _with_long_column(p, col, count, seed=3):
-    """p with `count` nonzeros in column `col` (the rows of A^T are the columns of A: the twin kernel walks those)"""
-    rng = np.random.default_rng(seed)
-    m, off, idx, val = p["m"], p["offsets"], p["indices"], p["values"]
-    rows = np.repeat(np.arange(m), np.diff(off))
-    keep = idx != col
-    add_rows = np.sort(rng.choice(m, size=count, replace=False))
-    r = np.concatenate([rows[keep], add_rows])
-    c = np.concatenate([idx[keep], np.full(count, col)])
-    v = np.concatenate([val[keep], 0.05 * rng.standard_normal(count)])
-    order = np.lexsort((c, r))
-    q = dict(p)
-    q["offsets"] = np.concatenate([[0], np.cumsum(np.bincount(r, minlength=m))]).astype(np.int32)
-    q["indices"], q["values"] = c[order].astype(np.int32), v[order]
-    return q
 
 
 def _case(name):
