@@ -18,8 +18,7 @@ k_spmv_a_halpern(int nb, const int32_t* __restrict__ rb, const int32_t* __restri
                  const double* __restrict__ hi, HalpernArgs h, double* __restrict__ part, const double* __restrict__ dadd)
 {
   if (!loop_active(ctl)) return;
-  const int cur = ctl->cur;
-  HalpernDualEpilogue e{cur ? y1 : y0, cur ? y0 : y1, h.ty, h.y0, lo, hi, ctl->sigma, HalpernWeights(h.hal)};
+  HalpernDualEpilogue e = HalpernDualEpilogue::make(ctl, y0, y1, lo, hi, h);
   csr_stream_block(nb, rb, off, idx, val, xbar, e, part, dadd);
 }
 
@@ -31,8 +30,6 @@ k_spmv_at_halpern(int nb, const int32_t* __restrict__ rb, const int32_t* __restr
                   double* __restrict__ part, const double* __restrict__ dadd)
 {
   if (!loop_active(ctl)) return;
-  const int cur = ctl->cur;
-  HalpernStepEpilogue e{cur ? x1 : x0, cur ? x0 : x1, cur ? aty1 : aty0, cur ? aty0 : aty1, h.x0, h.aty0,
-                        halpern_last_step(ctl) ? h.tx : nullptr, HalpernWeights(h.hal)};
+  HalpernStepEpilogue e = HalpernStepEpilogue::make(ctl, x0, x1, aty0, aty1, h);
   csr_stream_block(nb, rb, off, idx, val, h.ty /* y' */, e, part, dadd);
 }

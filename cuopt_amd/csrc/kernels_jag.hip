@@ -16,9 +16,7 @@ k_jag_a_dual(JagView J, const pdlpdev_ctl* __restrict__ ctl, const double* __res
              const p2pdev::Push* __restrict__ push)
 {
   if (!loop_active(ctl)) return;
-  const int cur = ctl->cur;
-  DualEpilogue e{cur ? y1 : y0, cur ? y0 : y1, lo, hi, sumy, ctl->sigma, ctl->step_size,
-                 ctl->pending_avg != 0, ycopy, push};
+  DualEpilogue e = DualEpilogue::make(ctl, y0, y1, lo, hi, sumy, ycopy, push);
   jag_block<decltype(e), WAVES>(J, xbar, e, part);
   if (push) p2pdev::count_exchange(push);
 }
@@ -31,9 +29,8 @@ k_jag_at_step(JagView J, const pdlpdev_ctl* __restrict__ ctl, const double* __re
               double* __restrict__ part)
 {
   if (!loop_active(ctl)) return;
-  const int cur = ctl->cur;
-  StepEpilogue e{cur ? x1 : x0, cur ? x0 : x1, cur ? aty1 : aty0, cur ? aty0 : aty1};
-  jag_block<decltype(e), WAVES>(J, cur ? y0 : y1 /* y' */, e, part);
+  StepEpilogue e = StepEpilogue::make(ctl, x0, x1, aty0, aty1);
+  jag_block<decltype(e), WAVES>(J, ctl->cur ? y0 : y1 /* y' */, e, part);
 }
 
 // Halpern twins (pdlp_epilogues.hpp)
@@ -44,8 +41,7 @@ k_jag_a_halpern(JagView J, const pdlpdev_ctl* __restrict__ ctl, const double* __
                 const double* __restrict__ hi, HalpernArgs h, double* __restrict__ part)
 {
   if (!loop_active(ctl)) return;
-  const int cur = ctl->cur;
-  HalpernDualEpilogue e{cur ? y1 : y0, cur ? y0 : y1, h.ty, h.y0, lo, hi, ctl->sigma, HalpernWeights(h.hal)};
+  HalpernDualEpilogue e = HalpernDualEpilogue::make(ctl, y0, y1, lo, hi, h);
   jag_block<decltype(e), WAVES>(J, xbar, e, part);
 }
 
@@ -55,9 +51,7 @@ k_jag_at_halpern(JagView J, const pdlpdev_ctl* __restrict__ ctl, double* __restr
                  double* __restrict__ aty0, double* __restrict__ aty1, HalpernArgs h, double* __restrict__ part)
 {
   if (!loop_active(ctl)) return;
-  const int cur = ctl->cur;
-  HalpernStepEpilogue e{cur ? x1 : x0, cur ? x0 : x1, cur ? aty1 : aty0, cur ? aty0 : aty1, h.x0, h.aty0,
-                        halpern_last_step(ctl) ? h.tx : nullptr, HalpernWeights(h.hal)};
+  HalpernStepEpilogue e = HalpernStepEpilogue::make(ctl, x0, x1, aty0, aty1, h);
   jag_block<decltype(e), WAVES>(J, h.ty /* y' */, e, part);
 }
 
@@ -68,7 +62,7 @@ k_jag_at_cur(JagView J, const pdlpdev_ctl* __restrict__ ctl, const double* __res
              double* __restrict__ out_override, int use_next)
 {
   const int cur = ctl->cur ^ (use_next ? 1 : 0);
-  StoreEpilogue e{out_override ? out_override : (cur ? aty1 : aty0)};
+  StoreEpilogue e = StoreEpilogue::iterate(cur, aty0, aty1, out_override);
   jag_block<decltype(e), WAVES>(J, cur ? y1 : y0, e, nullptr);
 }
 
@@ -91,8 +85,8 @@ k_jag_eval_primal(JagView J, const pdlpdev_ctl* __restrict__ ctl, int which,
                   double* __restrict__ ax_out, double* __restrict__ part)
 {
   const int cur = ctl->cur;
-  const double* xv = which == PDLPDEV_AVERAGE ? avgx : (cur ? x1 : x0);
-  const double* yv = which == PDLPDEV_AVERAGE ? avgy : (cur ? y1 : y0);
+  const double* xv = evaluated(cur, which, x0, x1, avgx);
+  const double* yv = evaluated(cur, which, y0, y1, avgy);
   EvalPrimalEpilogue e{yv, dr, lo_u, hi_u, eps_rel, linf_rows, ax_out};
   jag_block<decltype(e), WAVES>(J, xv, e, part);
 }
@@ -106,71 +100,21 @@ k_jag_eval_dual(JagView J, const pdlpdev_ctl* __restrict__ ctl, int which,
                 double* __restrict__ part)
 {
   const int cur = ctl->cur;
-  core.xhat     = which == PDLPDEV_AVERAGE ? avgx : (cur ? x1 : x0);
-  const double* yv = which == PDLPDEV_AVERAGE ? avgy : (cur ? y1 : y0);
+  core.xhat        = evaluated(cur, which, x0, x1, avgx);
+  const double* yv = evaluated(cur, which, y0, y1, avgy);
   EvalDualEpilogue e{core};
   jag_block<decltype(e), WAVES>(J, yv, e, part);
 }
 
-// explicit instantiations (the launch sites live in another translation unit)
-template __global__ void k_jag_a_halpern<8>(JagView J, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ xbar,
-                double* __restrict__ y0, double* __restrict__ y1, const double* __restrict__ lo,
-                const double* __restrict__ hi, HalpernArgs h, double* __restrict__ part);
-template __global__ void k_jag_a_halpern<16>(JagView J, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ xbar,
-                double* __restrict__ y0, double* __restrict__ y1, const double* __restrict__ lo,
-                const double* __restrict__ hi, HalpernArgs h, double* __restrict__ part);
-template __global__ void k_jag_at_halpern<8>(JagView J, const pdlpdev_ctl* __restrict__ ctl, double* __restrict__ x0, double* __restrict__ x1,
-                 double* __restrict__ aty0, double* __restrict__ aty1, HalpernArgs h, double* __restrict__ part);
-template __global__ void k_jag_at_halpern<16>(JagView J, const pdlpdev_ctl* __restrict__ ctl, double* __restrict__ x0, double* __restrict__ x1,
-                 double* __restrict__ aty0, double* __restrict__ aty1, HalpernArgs h, double* __restrict__ part);
-template __global__ void k_jag_a_dual<8>(JagView J, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ xbar,
-             double* __restrict__ y0, double* __restrict__ y1, const double* __restrict__ lo,
-             const double* __restrict__ hi, double* __restrict__ sumy, double* __restrict__ part, double* __restrict__ ycopy,
-             const p2pdev::Push* __restrict__ push);
-template __global__ void k_jag_a_dual<16>(JagView J, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ xbar,
-             double* __restrict__ y0, double* __restrict__ y1, const double* __restrict__ lo,
-             const double* __restrict__ hi, double* __restrict__ sumy, double* __restrict__ part, double* __restrict__ ycopy,
-             const p2pdev::Push* __restrict__ push);
-template __global__ void k_jag_at_step<8>(JagView J, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ y0,
-              const double* __restrict__ y1, const double* __restrict__ x0,
-              const double* __restrict__ x1, double* __restrict__ aty0, double* __restrict__ aty1,
-              double* __restrict__ part);
-template __global__ void k_jag_at_step<16>(JagView J, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ y0,
-              const double* __restrict__ y1, const double* __restrict__ x0,
-              const double* __restrict__ x1, double* __restrict__ aty0, double* __restrict__ aty1,
-              double* __restrict__ part);
-template __global__ void k_jag_at_cur<8>(JagView J, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ y0,
-             const double* __restrict__ y1, double* __restrict__ aty0, double* __restrict__ aty1,
-             double* __restrict__ out_override, int use_next);
-template __global__ void k_jag_at_cur<16>(JagView J, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ y0,
-             const double* __restrict__ y1, double* __restrict__ aty0, double* __restrict__ aty1,
-             double* __restrict__ out_override, int use_next);
-template __global__ void k_jag_plain<8>(JagView J, const double* __restrict__ vec, double* __restrict__ out);
-template __global__ void k_jag_plain<16>(JagView J, const double* __restrict__ vec, double* __restrict__ out);
-template __global__ void k_jag_eval_primal<8>(JagView J, const pdlpdev_ctl* __restrict__ ctl, int which,
-                  const double* __restrict__ x0, const double* __restrict__ x1,
-                  const double* __restrict__ avgx, const double* __restrict__ y0,
-                  const double* __restrict__ y1, const double* __restrict__ avgy,
-                  const double* __restrict__ dr, const double* __restrict__ lo_u,
-                  const double* __restrict__ hi_u, double eps_rel, double* __restrict__ linf_rows,
-                  double* __restrict__ ax_out, double* __restrict__ part);
-template __global__ void k_jag_eval_primal<16>(JagView J, const pdlpdev_ctl* __restrict__ ctl, int which,
-                  const double* __restrict__ x0, const double* __restrict__ x1,
-                  const double* __restrict__ avgx, const double* __restrict__ y0,
-                  const double* __restrict__ y1, const double* __restrict__ avgy,
-                  const double* __restrict__ dr, const double* __restrict__ lo_u,
-                  const double* __restrict__ hi_u, double eps_rel, double* __restrict__ linf_rows,
-                  double* __restrict__ ax_out, double* __restrict__ part);
-template __global__ void k_jag_eval_dual<8>(JagView J, const pdlpdev_ctl* __restrict__ ctl, int which,
-                const double* __restrict__ x0, const double* __restrict__ x1,
-                const double* __restrict__ avgx, const double* __restrict__ y0,
-                const double* __restrict__ y1, const double* __restrict__ avgy, EvalDualCore core,
-                double* __restrict__ part);
-template __global__ void k_jag_eval_dual<16>(JagView J, const pdlpdev_ctl* __restrict__ ctl, int which,
-                const double* __restrict__ x0, const double* __restrict__ x1,
-                const double* __restrict__ avgx, const double* __restrict__ y0,
-                const double* __restrict__ y1, const double* __restrict__ avgy, EvalDualCore core,
-                double* __restrict__ part);
+// explicit instantiations (the launch sites live in another translation unit), from the lists of pdlp_kernel_decls.hpp
+INSTANTIATE_JAG(A_HALPERN_KERNELS)
+INSTANTIATE_JAG(AT_HALPERN_KERNELS)
+INSTANTIATE_JAG(A_DUAL_KERNELS)
+INSTANTIATE_JAG(AT_STEP_KERNELS)
+INSTANTIATE_JAG(AT_CUR_KERNELS)
+INSTANTIATE_JAG(PLAIN_KERNELS)
+INSTANTIATE_JAG(EVAL_PRIMAL_KERNELS)
+INSTANTIATE_JAG(EVAL_DUAL_KERNELS)
 
 // ================================================================================================
 // host side of the layout

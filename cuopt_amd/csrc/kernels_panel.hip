@@ -16,9 +16,7 @@ k_panel_a_dual(PanelView P, const pdlpdev_ctl* __restrict__ ctl, const double* _
                const p2pdev::Push* __restrict__ push)
 {
   if (!loop_active(ctl)) return;
-  const int cur = ctl->cur;
-  DualEpilogue e{cur ? y1 : y0, cur ? y0 : y1, lo, hi, sumy, ctl->sigma, ctl->step_size,
-                 ctl->pending_avg != 0, ycopy, push};
+  DualEpilogue e = DualEpilogue::make(ctl, y0, y1, lo, hi, sumy, ycopy, push);
   panel_block<SEG>(P, xbar, e, part);
   if (push) p2pdev::count_exchange(push);
 }
@@ -31,9 +29,8 @@ k_panel_at_step(PanelView P, const pdlpdev_ctl* __restrict__ ctl, const double* 
                 double* __restrict__ part)
 {
   if (!loop_active(ctl)) return;
-  const int cur = ctl->cur;
-  StepEpilogue e{cur ? x1 : x0, cur ? x0 : x1, cur ? aty1 : aty0, cur ? aty0 : aty1};
-  panel_block<SEG>(P, cur ? y0 : y1 /* y' */, e, part);
+  StepEpilogue e = StepEpilogue::make(ctl, x0, x1, aty0, aty1);
+  panel_block<SEG>(P, ctl->cur ? y0 : y1 /* y' */, e, part);
 }
 
 // Halpern twins (pdlp_epilogues.hpp)
@@ -44,8 +41,7 @@ k_panel_a_halpern(PanelView P, const pdlpdev_ctl* __restrict__ ctl, const double
                   const double* __restrict__ hi, HalpernArgs h, double* __restrict__ part)
 {
   if (!loop_active(ctl)) return;
-  const int cur = ctl->cur;
-  HalpernDualEpilogue e{cur ? y1 : y0, cur ? y0 : y1, h.ty, h.y0, lo, hi, ctl->sigma, HalpernWeights(h.hal)};
+  HalpernDualEpilogue e = HalpernDualEpilogue::make(ctl, y0, y1, lo, hi, h);
   panel_block<SEG>(P, xbar, e, part);
 }
 
@@ -55,9 +51,7 @@ k_panel_at_halpern(PanelView P, const pdlpdev_ctl* __restrict__ ctl, double* __r
                    double* __restrict__ aty0, double* __restrict__ aty1, HalpernArgs h, double* __restrict__ part)
 {
   if (!loop_active(ctl)) return;
-  const int cur = ctl->cur;
-  HalpernStepEpilogue e{cur ? x1 : x0, cur ? x0 : x1, cur ? aty1 : aty0, cur ? aty0 : aty1, h.x0, h.aty0,
-                        halpern_last_step(ctl) ? h.tx : nullptr, HalpernWeights(h.hal)};
+  HalpernStepEpilogue e = HalpernStepEpilogue::make(ctl, x0, x1, aty0, aty1, h);
   panel_block<SEG>(P, h.ty /* y' */, e, part);
 }
 
@@ -69,7 +63,7 @@ k_panel_at_cur(PanelView P, const pdlpdev_ctl* __restrict__ ctl, const double* _
                double* __restrict__ out_override, int use_next)
 {
   const int cur = ctl->cur ^ (use_next ? 1 : 0);
-  StoreEpilogue e{out_override ? out_override : (cur ? aty1 : aty0)};
+  StoreEpilogue e = StoreEpilogue::iterate(cur, aty0, aty1, out_override);
   panel_block<SEG>(P, cur ? y1 : y0, e, nullptr);
 }
 
@@ -93,8 +87,8 @@ k_panel_eval_primal(PanelView P, const pdlpdev_ctl* __restrict__ ctl, int which,
 {
   if (period_guard_skips(ctl, which)) return;
   const int cur = ctl->cur;
-  const double* xv = which == PDLPDEV_AVERAGE ? avgx : (cur ? x1 : x0);
-  const double* yv = which == PDLPDEV_AVERAGE ? avgy : (cur ? y1 : y0);
+  const double* xv = evaluated(cur, which, x0, x1, avgx);
+  const double* yv = evaluated(cur, which, y0, y1, avgy);
   EvalPrimalEpilogue e{yv, dr, lo_u, hi_u, eps_rel, linf_rows, ax_out};
   panel_block<SEG>(P, xv, e, part);
 }
@@ -109,8 +103,8 @@ k_panel_eval_dual(PanelView P, const pdlpdev_ctl* __restrict__ ctl, int which,
 {
   if (period_guard_skips(ctl, which)) return;
   const int cur = ctl->cur;
-  core.xhat     = which == PDLPDEV_AVERAGE ? avgx : (cur ? x1 : x0);
-  const double* yv = which == PDLPDEV_AVERAGE ? avgy : (cur ? y1 : y0);
+  core.xhat        = evaluated(cur, which, x0, x1, avgx);
+  const double* yv = evaluated(cur, which, y0, y1, avgy);
   EvalDualEpilogue e{core};
   panel_block<SEG>(P, yv, e, part);
 }
@@ -129,8 +123,8 @@ k_panel_eval_dual_from_aty(PanelView P, const pdlpdev_ctl* __restrict__ ctl, con
   __shared__ double red[kPanelWaves * EvalDualEpilogue::NQ];
   __shared__ unsigned char own[kPanelMaxRows];  // rows of this panel that have a workgroup of their own (the product's "not mine" marks)
   const int cur = ctl->cur;
-  core.xhat     = cur ? x1 : x0;
-  const double* __restrict__ src = cur ? aty1 : aty0;
+  core.xhat                      = evaluated(cur, PDLPDEV_CURRENT, x0, x1, nullptr);
+  const double* __restrict__ src = evaluated(cur, PDLPDEV_CURRENT, aty0, aty1, nullptr);
   EvalDualEpilogue e{core};
   const int w  = blockIdx.x;
   const int NP = P.NP ? P.NP : P.W;
@@ -162,65 +156,15 @@ k_panel_eval_dual_from_aty(PanelView P, const pdlpdev_ctl* __restrict__ ctl, con
   }
 }
 
-// explicit instantiations (the launch sites live in another translation unit)
-template __global__ void k_panel_a_halpern<true>(PanelView P, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ xbar,
-                  double* __restrict__ y0, double* __restrict__ y1, const double* __restrict__ lo,
-                  const double* __restrict__ hi, HalpernArgs h, double* __restrict__ part);
-template __global__ void k_panel_a_halpern<false>(PanelView P, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ xbar,
-                  double* __restrict__ y0, double* __restrict__ y1, const double* __restrict__ lo,
-                  const double* __restrict__ hi, HalpernArgs h, double* __restrict__ part);
-template __global__ void k_panel_at_halpern<true>(PanelView P, const pdlpdev_ctl* __restrict__ ctl, double* __restrict__ x0, double* __restrict__ x1,
-                   double* __restrict__ aty0, double* __restrict__ aty1, HalpernArgs h, double* __restrict__ part);
-template __global__ void k_panel_at_halpern<false>(PanelView P, const pdlpdev_ctl* __restrict__ ctl, double* __restrict__ x0, double* __restrict__ x1,
-                   double* __restrict__ aty0, double* __restrict__ aty1, HalpernArgs h, double* __restrict__ part);
-template __global__ void k_panel_a_dual<true>(PanelView P, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ xbar,
-               double* __restrict__ y0, double* __restrict__ y1, const double* __restrict__ lo,
-               const double* __restrict__ hi, double* __restrict__ sumy, double* __restrict__ part, double* __restrict__ ycopy,
-               const p2pdev::Push* __restrict__ push);
-template __global__ void k_panel_a_dual<false>(PanelView P, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ xbar,
-               double* __restrict__ y0, double* __restrict__ y1, const double* __restrict__ lo,
-               const double* __restrict__ hi, double* __restrict__ sumy, double* __restrict__ part, double* __restrict__ ycopy,
-               const p2pdev::Push* __restrict__ push);
-template __global__ void k_panel_at_step<true>(PanelView P, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ y0,
-                const double* __restrict__ y1, const double* __restrict__ x0,
-                const double* __restrict__ x1, double* __restrict__ aty0, double* __restrict__ aty1,
-                double* __restrict__ part);
-template __global__ void k_panel_at_step<false>(PanelView P, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ y0,
-                const double* __restrict__ y1, const double* __restrict__ x0,
-                const double* __restrict__ x1, double* __restrict__ aty0, double* __restrict__ aty1,
-                double* __restrict__ part);
-template __global__ void k_panel_at_cur<true>(PanelView P, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ y0,
-               const double* __restrict__ y1, double* __restrict__ aty0, double* __restrict__ aty1,
-               double* __restrict__ out_override, int use_next);
-template __global__ void k_panel_at_cur<false>(PanelView P, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ y0,
-               const double* __restrict__ y1, double* __restrict__ aty0, double* __restrict__ aty1,
-               double* __restrict__ out_override, int use_next);
-template __global__ void k_panel_plain<true>(PanelView P, const double* __restrict__ vec, double* __restrict__ out);
-template __global__ void k_panel_plain<false>(PanelView P, const double* __restrict__ vec, double* __restrict__ out);
-template __global__ void k_panel_eval_primal<true>(PanelView P, const pdlpdev_ctl* __restrict__ ctl, int which,
-                    const double* __restrict__ x0, const double* __restrict__ x1,
-                    const double* __restrict__ avgx, const double* __restrict__ y0,
-                    const double* __restrict__ y1, const double* __restrict__ avgy,
-                    const double* __restrict__ dr, const double* __restrict__ lo_u,
-                    const double* __restrict__ hi_u, double eps_rel, double* __restrict__ linf_rows,
-                    double* __restrict__ ax_out, double* __restrict__ part);
-template __global__ void k_panel_eval_primal<false>(PanelView P, const pdlpdev_ctl* __restrict__ ctl, int which,
-                    const double* __restrict__ x0, const double* __restrict__ x1,
-                    const double* __restrict__ avgx, const double* __restrict__ y0,
-                    const double* __restrict__ y1, const double* __restrict__ avgy,
-                    const double* __restrict__ dr, const double* __restrict__ lo_u,
-                    const double* __restrict__ hi_u, double eps_rel, double* __restrict__ linf_rows,
-                    double* __restrict__ ax_out, double* __restrict__ part);
-template __global__ void k_panel_eval_dual<true>(PanelView P, const pdlpdev_ctl* __restrict__ ctl, int which,
-                  const double* __restrict__ x0, const double* __restrict__ x1,
-                  const double* __restrict__ avgx, const double* __restrict__ y0,
-                  const double* __restrict__ y1, const double* __restrict__ avgy, EvalDualCore core,
-                  double* __restrict__ part);
-template __global__ void k_panel_eval_dual<false>(PanelView P, const pdlpdev_ctl* __restrict__ ctl, int which,
-                  const double* __restrict__ x0, const double* __restrict__ x1,
-                  const double* __restrict__ avgx, const double* __restrict__ y0,
-                  const double* __restrict__ y1, const double* __restrict__ avgy, EvalDualCore core,
-                  double* __restrict__ part);
+// explicit instantiations (the launch sites live in another translation unit), from the lists of pdlp_kernel_decls.hpp
+INSTANTIATE_PANEL(A_HALPERN_KERNELS)
+INSTANTIATE_PANEL(AT_HALPERN_KERNELS)
+INSTANTIATE_PANEL(A_DUAL_KERNELS)
+INSTANTIATE_PANEL(AT_STEP_KERNELS)
+INSTANTIATE_PANEL(AT_CUR_KERNELS)
+INSTANTIATE_PANEL(PLAIN_KERNELS)
+INSTANTIATE_PANEL(EVAL_PRIMAL_KERNELS)
+INSTANTIATE_PANEL(EVAL_DUAL_KERNELS)
 
 // ================================================================================================
 // host side of the layout

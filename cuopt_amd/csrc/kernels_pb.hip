@@ -14,13 +14,7 @@ k_pb_products(PbView V, const pdlpdev_ctl* __restrict__ ctl, const double* __res
 {
   extern __shared__ __attribute__((aligned(16))) double pb_lds[];
   if (in_loop && !loop_active(ctl)) return;
-  // mode 0: v0.  1: cur ? v0 : v1 (the trial iterate of a ping-pong pair).  2: cur ? v1 : v0 (the current one).
-  const double* vec = v0;
-  if (mode != 0) {
-    const bool cur = ctl->cur != 0;
-    vec            = (cur == (mode == 1)) ? v0 : v1;
-  }
-  pb_products_block<THREADS>(V, vec, pb_lds);
+  pb_products_block<THREADS>(V, pick_vector(ctl, v0, v1, mode), pb_lds);
 }
 
 template <bool WIDE>
@@ -31,8 +25,7 @@ k_pb_a_dual(PbView V, const pdlpdev_ctl* __restrict__ ctl, double* __restrict__ 
 {
   extern __shared__ __attribute__((aligned(16))) double pb_lds[];
   if (!loop_active(ctl)) return;
-  const int cur = ctl->cur;
-  DualEpilogue e{cur ? y1 : y0, cur ? y0 : y1, lo, hi, sumy, ctl->sigma, ctl->step_size, ctl->pending_avg != 0, ycopy, push};
+  DualEpilogue e = DualEpilogue::make(ctl, y0, y1, lo, hi, sumy, ycopy, push);
   if constexpr (WIDE) pbw_rows_block(V, e, part, pb_lds);
   else pb_rows_block(V, e, part, pb_lds);
   if (push) p2pdev::count_exchange(push);
@@ -45,8 +38,7 @@ k_pb_at_step(PbView V, const pdlpdev_ctl* __restrict__ ctl, const double* __rest
 {
   extern __shared__ __attribute__((aligned(16))) double pb_lds[];
   if (!loop_active(ctl)) return;
-  const int cur = ctl->cur;
-  StepEpilogue e{cur ? x1 : x0, cur ? x0 : x1, cur ? aty1 : aty0, cur ? aty0 : aty1};
+  StepEpilogue e = StepEpilogue::make(ctl, x0, x1, aty0, aty1);
   if constexpr (WIDE) pbw_rows_block(V, e, part, pb_lds);
   else pb_rows_block(V, e, part, pb_lds);
 }
@@ -59,8 +51,7 @@ k_pb_a_halpern(PbView V, const pdlpdev_ctl* __restrict__ ctl, double* __restrict
 {
   extern __shared__ __attribute__((aligned(16))) double pb_lds[];
   if (!loop_active(ctl)) return;
-  const int cur = ctl->cur;
-  HalpernDualEpilogue e{cur ? y1 : y0, cur ? y0 : y1, h.ty, h.y0, lo, hi, ctl->sigma, HalpernWeights(h.hal)};
+  HalpernDualEpilogue e = HalpernDualEpilogue::make(ctl, y0, y1, lo, hi, h);
   if constexpr (WIDE) pbw_rows_block(V, e, part, pb_lds);
   else pb_rows_block(V, e, part, pb_lds);
 }
@@ -72,9 +63,7 @@ k_pb_at_halpern(PbView V, const pdlpdev_ctl* __restrict__ ctl, double* __restric
 {
   extern __shared__ __attribute__((aligned(16))) double pb_lds[];
   if (!loop_active(ctl)) return;
-  const int cur = ctl->cur;
-  HalpernStepEpilogue e{cur ? x1 : x0, cur ? x0 : x1, cur ? aty1 : aty0, cur ? aty0 : aty1, h.x0, h.aty0,
-                        halpern_last_step(ctl) ? h.tx : nullptr, HalpernWeights(h.hal)};
+  HalpernStepEpilogue e = HalpernStepEpilogue::make(ctl, x0, x1, aty0, aty1, h);
   if constexpr (WIDE) pbw_rows_block(V, e, part, pb_lds);
   else pb_rows_block(V, e, part, pb_lds);
 }
@@ -86,7 +75,7 @@ k_pb_at_cur(PbView V, const pdlpdev_ctl* __restrict__ ctl, double* __restrict__ 
 {
   extern __shared__ __attribute__((aligned(16))) double pb_lds[];
   const int cur = ctl->cur ^ (use_next ? 1 : 0);
-  StoreEpilogue e{out_override ? out_override : (cur ? aty1 : aty0)};
+  StoreEpilogue e = StoreEpilogue::iterate(cur, aty0, aty1, out_override);
   if constexpr (WIDE) pbw_rows_block(V, e, nullptr, pb_lds);
   else pb_rows_block(V, e, nullptr, pb_lds);
 }
@@ -108,6 +97,8 @@ k_pb_eval_primal(PbView V, const pdlpdev_ctl* __restrict__ ctl, int which, const
                  double* __restrict__ part)
 {
   extern __shared__ __attribute__((aligned(16))) double pb_lds[];
+  // evaluated() of pdlp_epilogues.hpp, written out: with ONE pick per kernel the compiler keeps the load of ctl->cur inside the
+  // branch `which` decides, and the call leaves it in front (k_pb_eval_dual likewise; 07_measurement.md, round 13)
   const int cur    = ctl->cur;
   const double* yv = which == PDLPDEV_AVERAGE ? avgy : (cur ? y1 : y0);
   EvalPrimalEpilogue e{yv, dr, lo_u, hi_u, eps_rel, linf_rows, ax_out};
@@ -122,51 +113,22 @@ k_pb_eval_dual(PbView V, const pdlpdev_ctl* __restrict__ ctl, int which, const d
 {
   extern __shared__ __attribute__((aligned(16))) double pb_lds[];
   const int cur = ctl->cur;
-  core.xhat     = which == PDLPDEV_AVERAGE ? avgx : (cur ? x1 : x0);
+  core.xhat     = which == PDLPDEV_AVERAGE ? avgx : (cur ? x1 : x0);  // evaluated(), written out: see k_pb_eval_primal
   EvalDualEpilogue e{core};
   if constexpr (WIDE) pbw_rows_block(V, e, part, pb_lds);
   else pb_rows_block(V, e, part, pb_lds);
 }
 
-// explicit instantiations (the launch sites live in another translation unit)
-template __global__ void k_pb_a_halpern<false>(PbView V, const pdlpdev_ctl* __restrict__ ctl, double* __restrict__ y0, double* __restrict__ y1, const double* __restrict__ lo,
-               const double* __restrict__ hi, HalpernArgs h, double* __restrict__ part);
-template __global__ void k_pb_a_halpern<true>(PbView V, const pdlpdev_ctl* __restrict__ ctl, double* __restrict__ y0, double* __restrict__ y1, const double* __restrict__ lo,
-               const double* __restrict__ hi, HalpernArgs h, double* __restrict__ part);
-template __global__ void k_pb_at_halpern<false>(PbView V, const pdlpdev_ctl* __restrict__ ctl, double* __restrict__ x0, double* __restrict__ x1,
-                double* __restrict__ aty0, double* __restrict__ aty1, HalpernArgs h, double* __restrict__ part);
-template __global__ void k_pb_at_halpern<true>(PbView V, const pdlpdev_ctl* __restrict__ ctl, double* __restrict__ x0, double* __restrict__ x1,
-                double* __restrict__ aty0, double* __restrict__ aty1, HalpernArgs h, double* __restrict__ part);
-template __global__ void k_pb_products<512>(PbView V, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ v0, const double* __restrict__ v1, int mode, int in_loop);
-template __global__ void k_pb_products<1024>(PbView V, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ v0, const double* __restrict__ v1, int mode, int in_loop);
-template __global__ void k_pb_a_dual<false>(PbView V, const pdlpdev_ctl* __restrict__ ctl, double* __restrict__ y0, double* __restrict__ y1, const double* __restrict__ lo,
-            const double* __restrict__ hi, double* __restrict__ sumy, double* __restrict__ part, double* __restrict__ ycopy,
-            const p2pdev::Push* __restrict__ push);
-template __global__ void k_pb_a_dual<true>(PbView V, const pdlpdev_ctl* __restrict__ ctl, double* __restrict__ y0, double* __restrict__ y1, const double* __restrict__ lo,
-            const double* __restrict__ hi, double* __restrict__ sumy, double* __restrict__ part, double* __restrict__ ycopy,
-            const p2pdev::Push* __restrict__ push);
-template __global__ void k_pb_at_step<false>(PbView V, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ x0, const double* __restrict__ x1,
-             double* __restrict__ aty0, double* __restrict__ aty1, double* __restrict__ part);
-template __global__ void k_pb_at_step<true>(PbView V, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ x0, const double* __restrict__ x1,
-             double* __restrict__ aty0, double* __restrict__ aty1, double* __restrict__ part);
-template __global__ void k_pb_at_cur<false>(PbView V, const pdlpdev_ctl* __restrict__ ctl, double* __restrict__ aty0, double* __restrict__ aty1,
-            double* __restrict__ out_override, int use_next);
-template __global__ void k_pb_at_cur<true>(PbView V, const pdlpdev_ctl* __restrict__ ctl, double* __restrict__ aty0, double* __restrict__ aty1,
-            double* __restrict__ out_override, int use_next);
-template __global__ void k_pb_plain<false>(PbView V, double* __restrict__ out);
-template __global__ void k_pb_plain<true>(PbView V, double* __restrict__ out);
-template __global__ void k_pb_eval_primal<false>(PbView V, const pdlpdev_ctl* __restrict__ ctl, int which, const double* __restrict__ y0, const double* __restrict__ y1,
-                 const double* __restrict__ avgy, const double* __restrict__ dr, const double* __restrict__ lo_u,
-                 const double* __restrict__ hi_u, double eps_rel, double* __restrict__ linf_rows, double* __restrict__ ax_out,
-                 double* __restrict__ part);
-template __global__ void k_pb_eval_primal<true>(PbView V, const pdlpdev_ctl* __restrict__ ctl, int which, const double* __restrict__ y0, const double* __restrict__ y1,
-                 const double* __restrict__ avgy, const double* __restrict__ dr, const double* __restrict__ lo_u,
-                 const double* __restrict__ hi_u, double eps_rel, double* __restrict__ linf_rows, double* __restrict__ ax_out,
-                 double* __restrict__ part);
-template __global__ void k_pb_eval_dual<false>(PbView V, const pdlpdev_ctl* __restrict__ ctl, int which, const double* __restrict__ x0, const double* __restrict__ x1,
-               const double* __restrict__ avgx, EvalDualCore core, double* __restrict__ part);
-template __global__ void k_pb_eval_dual<true>(PbView V, const pdlpdev_ctl* __restrict__ ctl, int which, const double* __restrict__ x0, const double* __restrict__ x1,
-               const double* __restrict__ avgx, EvalDualCore core, double* __restrict__ part);
+// explicit instantiations (the launch sites live in another translation unit), from the lists of pdlp_kernel_decls.hpp
+INSTANTIATE_PB(A_HALPERN_KERNELS)
+INSTANTIATE_PB(AT_HALPERN_KERNELS)
+PB_PRODUCTS_KERNEL(KERNEL_PAIR_INSTANTIATE)
+INSTANTIATE_PB(A_DUAL_KERNELS)
+INSTANTIATE_PB(AT_STEP_KERNELS)
+INSTANTIATE_PB(AT_CUR_KERNELS)
+INSTANTIATE_PB(PLAIN_KERNELS)
+INSTANTIATE_PB(EVAL_PRIMAL_KERNELS)
+INSTANTIATE_PB(EVAL_DUAL_KERNELS)
 
 // ================================================================================================
 // host side of the layout

@@ -15,9 +15,7 @@ k_spmv_a_dual(int nb, const int32_t* __restrict__ rb, const int32_t* __restrict_
               const p2pdev::Push* __restrict__ push, const double* __restrict__ dadd)
 {
   if (!loop_active(ctl)) return;
-  const int cur = ctl->cur;
-  DualEpilogue e{cur ? y1 : y0, cur ? y0 : y1, lo, hi, sumy, ctl->sigma, ctl->step_size,
-                 ctl->pending_avg != 0, ycopy, push};
+  DualEpilogue e = DualEpilogue::make(ctl, y0, y1, lo, hi, sumy, ycopy, push);
   csr_stream_block(nb, rb, off, idx, val, xbar, e, part, dadd);
   if (push) p2pdev::count_exchange(push);
 }
@@ -31,9 +29,8 @@ k_spmv_at_step(int nb, const int32_t* __restrict__ rb, const int32_t* __restrict
                double* __restrict__ part, const double* __restrict__ dadd)
 {
   if (!loop_active(ctl)) return;
-  const int cur = ctl->cur;
-  StepEpilogue e{cur ? x1 : x0, cur ? x0 : x1, cur ? aty1 : aty0, cur ? aty0 : aty1};
-  csr_stream_block(nb, rb, off, idx, val, cur ? y0 : y1 /* y' */, e, part, dadd);
+  StepEpilogue e = StepEpilogue::make(ctl, x0, x1, aty0, aty1);
+  csr_stream_block(nb, rb, off, idx, val, ctl->cur ? y0 : y1 /* y' */, e, part, dadd);
 }
 
 // plain SpMV (A^T y at start / after restart-to-average; parity hook; multi-GPU partial products)
@@ -55,7 +52,7 @@ k_spmv_at_cur(int nb, const int32_t* __restrict__ rb, const int32_t* __restrict_
               double* __restrict__ out_override, int use_next, const double* __restrict__ dadd)
 {
   const int cur = ctl->cur ^ (use_next ? 1 : 0);
-  StoreEpilogue e{out_override ? out_override : (cur ? aty1 : aty0)};
+  StoreEpilogue e = StoreEpilogue::iterate(cur, aty0, aty1, out_override);
   csr_stream_block(nb, rb, off, idx, val, cur ? y1 : y0, e, nullptr, dadd);
 }
 
@@ -65,7 +62,7 @@ __global__ void __launch_bounds__(kBlock) k_spmv_at_cur_batch(const StreamAtCurA
   const int2 b            = blk[blockIdx.x];
   const StreamAtCurArgs A = args[b.x];
   const int cur           = A.ctl->cur;
-  StoreEpilogue e{cur ? A.aty1 : A.aty0};
+  StoreEpilogue e         = StoreEpilogue::iterate(cur, A.aty0, A.aty1, nullptr);
   csr_stream_block(A.nb, A.rb, A.off, A.idx, A.val, cur ? A.y1 : A.y0, e, nullptr, nullptr, b.y);
 }
 int launch_stream_at_cur_batch(hipStream_t s, const StreamAtCurArgs* args, const int2* blk, int blocks)
@@ -86,8 +83,8 @@ k_eval_primal(int nb, const int32_t* __restrict__ rb, const int32_t* __restrict_
               double* __restrict__ linf_rows, double* __restrict__ ax_out, double* __restrict__ part, const double* __restrict__ dadd)
 {
   const int cur = ctl->cur;
-  const double* xv = which == PDLPDEV_AVERAGE ? avgx : (cur ? x1 : x0);
-  const double* yv = which == PDLPDEV_AVERAGE ? avgy : (cur ? y1 : y0);
+  const double* xv = evaluated(cur, which, x0, x1, avgx);
+  const double* yv = evaluated(cur, which, y0, y1, avgy);
   EvalPrimalEpilogue e{yv, dr, lo_u, hi_u, eps_rel, linf_rows, ax_out};
   csr_stream_block(nb, rb, off, idx, val, xv, e, part, dadd);
 }
@@ -101,17 +98,14 @@ k_eval_dual(int nb, const int32_t* __restrict__ rb, const int32_t* __restrict__ 
             const double* __restrict__ avgy, EvalDualCore core, double* __restrict__ part, const double* __restrict__ dadd)
 {
   const int cur = ctl->cur;
-  core.xhat     = which == PDLPDEV_AVERAGE ? avgx : (cur ? x1 : x0);
-  const double* yv = which == PDLPDEV_AVERAGE ? avgy : (cur ? y1 : y0);
+  core.xhat        = evaluated(cur, which, x0, x1, avgx);
+  const double* yv = evaluated(cur, which, y0, y1, avgy);
   EvalDualEpilogue e{core};
   csr_stream_block(nb, rb, off, idx, val, yv, e, part, dadd);
 }
 
 // ================================================================================================
 // host side of the layout
-// ================================================================================================
-// ================================================================================================
-// host side of the device layer
 // ================================================================================================
 // Greedy partition of the rows into stream blocks: at most kNnzBlock nonzeros and
 // kMaxRowsPerBlock rows per block; a row longer than the LDS tile gets a block of its own.

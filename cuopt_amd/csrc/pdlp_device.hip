@@ -885,7 +885,7 @@ static inline HalpernArgs halpern_args(const pdlpdev_ctx* ctx) { return HalpernA
 // (Halpern mode: the twins' kernels; its A^T product gathers y' from its own buffer, which the kernels take inside HalpernArgs)
 static void launch_a_dual(pdlpdev_ctx* ctx, double* ycopy = nullptr, const p2pdev::Push* push = nullptr)
 {
-  const Gathered g{ctx->xbar, nullptr, 0, 1};
+  const Gathered g = Gathered::fixed(ctx->xbar, true);
   const auto pre  = std::make_tuple(ctx->ctl);
   const auto vecs = std::make_tuple(ctx->xbar);
   if (ctx->halpern) (void)launch_product(ctx, ctx->A, products::a_halpern, g, pre, vecs, std::make_tuple(ctx->y[0], ctx->y[1], ctx->lo, ctx->hi, halpern_args(ctx), ctx->A.part));
@@ -895,21 +895,21 @@ static void launch_at_step(pdlpdev_ctx* ctx)
 {
   const auto pre = std::make_tuple(ctx->ctl);
   if (ctx->halpern)
-    (void)launch_product(ctx, ctx->At, products::at_halpern, Gathered{ctx->avgy, nullptr, 0, 1}, pre, std::make_tuple(),
+    (void)launch_product(ctx, ctx->At, products::at_halpern, Gathered::fixed(ctx->avgy, true), pre, std::make_tuple(),
                          std::make_tuple(ctx->x[0], ctx->x[1], ctx->aty[0], ctx->aty[1], halpern_args(ctx), ctx->At.part));
   else  // y' = the trial dual
-    (void)launch_product(ctx, ctx->At, products::at_step, Gathered{ctx->y[0], ctx->y[1], 1, 1}, pre, std::make_tuple(ctx->y[0], ctx->y[1]),
+    (void)launch_product(ctx, ctx->At, products::at_step, Gathered::trial(ctx->y[0], ctx->y[1], true), pre, std::make_tuple(ctx->y[0], ctx->y[1]),
                          std::make_tuple(ctx->x[0], ctx->x[1], ctx->aty[0], ctx->aty[1], ctx->At.part));
 }
 void launch_at_cur(pdlpdev_ctx* ctx, double* out_override, int use_next)
 {
-  (void)launch_product(ctx, ctx->At, products::at_cur, Gathered{ctx->y[0], ctx->y[1], use_next ? 1 : 2, 0}, std::make_tuple(ctx->ctl),
+  (void)launch_product(ctx, ctx->At, products::at_cur, use_next ? Gathered::trial(ctx->y[0], ctx->y[1]) : Gathered::current(ctx->y[0], ctx->y[1]), std::make_tuple(ctx->ctl),
                        std::make_tuple(ctx->y[0], ctx->y[1]), std::make_tuple(ctx->aty[0], ctx->aty[1], out_override, use_next));
 }
 // plain y = A x (transpose = 0) or y = A^T x through the layout the solver iterates with
 void launch_plain(pdlpdev_ctx* ctx, int transpose, const double* vec, double* out)
 {
-  (void)launch_product(ctx, transpose ? ctx->At : ctx->A, products::plain, Gathered{vec, nullptr, 0, 0}, std::make_tuple(), std::make_tuple(vec), std::make_tuple(out));
+  (void)launch_product(ctx, transpose ? ctx->At : ctx->A, products::plain, Gathered::fixed(vec), std::make_tuple(), std::make_tuple(vec), std::make_tuple(out));
 }
 static void launch_decision(pdlpdev_ctx* ctx)
 {
@@ -923,7 +923,7 @@ static void launch_oc_step(pdlpdev_ctx* ctx)
   const size_t cs = (size_t)ctx->rank * ctx->slice;
   double *x0 = ctx->x[0] + cs, *x1 = ctx->x[1] + cs, *t0 = ctx->aty[0] + cs, *t1 = ctx->aty[1] + cs;
   const double* yg = ctx->ygather;  // the trial dual of every rank, whichever ping-pong buffer it lives in
-  (void)launch_product(ctx, ctx->Oc, products::at_step, Gathered{yg, yg, 1, 1}, std::make_tuple(ctx->ctl), std::make_tuple(yg, yg),
+  (void)launch_product(ctx, ctx->Oc, products::at_step, Gathered::trial(yg, yg, true), std::make_tuple(ctx->ctl), std::make_tuple(yg, yg),
                        std::make_tuple(x0, x1, t0, t1, ctx->Oc.part));
 }
 

@@ -71,6 +71,12 @@ __device__ __forceinline__ bool wait_flags(const unsigned long long* flags, int 
 }
 }  // namespace p2pdev
 
+// ---- the fused epilogues ---------------------------------------------------------------------------------------------------------
+// A product's HEAD -- which buffer of a ping-pong pair is the current iterate and which the next, which scalars of the control block
+// the epilogue carries -- is written once, in the `make` next to the epilogue's fields; the product's kernel in each layout
+// (kernels_stream / _halpern / _panel / _jag / _pb .hip) calls it with its own pointers.  The kernels keep their guard
+// (loop_active, period_guard_skips), the choice of the vector their walker gathers, and the walker's call.
+
 // (2) rows of A: v = A xbar (stream SpMV) -> dual projection (utils.cuh:97-112) -> ||dy||^2 partial,
 //     plus the deferred dual averaging.
 struct DualEpilogue {
@@ -107,6 +113,12 @@ struct DualEpilogue {
     if (pend) sumy[i] = o.sum + weight * yi;
   }
   __device__ __forceinline__ void row(int i, double v, double (&acc)[1]) { apply(i, v, load(i), acc); }
+  static __device__ __forceinline__ DualEpilogue make(const pdlpdev_ctl* ctl, double* y0, double* y1, const double* lo, const double* hi,
+                                                      double* sumy, double* ycopy, const p2pdev::Push* push)
+  {
+    const int cur = ctl->cur;
+    return DualEpilogue{cur ? y1 : y0, cur ? y0 : y1, lo, hi, sumy, ctl->sigma, ctl->step_size, ctl->pending_avg != 0, ycopy, push};
+  }
 };
 
 // (3) rows of A^T: AtY' = A^T y' (stream SpMV) fused with the step-size statistics
@@ -131,6 +143,11 @@ struct StepEpilogue {
     acc[1] += dx * dx;
   }
   __device__ __forceinline__ void row(int j, double v, double (&acc)[2]) { apply(j, v, load(j), acc); }
+  static __device__ __forceinline__ StepEpilogue make(const pdlpdev_ctl* ctl, const double* x0, const double* x1, double* aty0, double* aty1)
+  {
+    const int cur = ctl->cur;
+    return StepEpilogue{cur ? x1 : x0, cur ? x0 : x1, cur ? aty1 : aty0, cur ? aty0 : aty1};
+  }
 };
 
 // ---- restarted reflected-Halpern mode (docs/design/04d_halpern_mode.md): the same two products, the epilogues carry the combination
@@ -146,6 +163,17 @@ struct HalpernWeights {
   }
   __device__ __forceinline__ double combine(double t, double z, double z0) const { return w * (2.0 * t - z) + w0 * z0; }
 };
+// what the kernels of a Halpern step take besides their twins' arguments (by value: a handful of pointers)
+struct HalpernArgs {
+  const pdlpdev_halpern* __restrict__ hal;
+  double* __restrict__ tx;          // T(z^k), primal half (the AVERAGE slot)
+  double* __restrict__ ty;          // T(z^k), dual half: what the A^T product gathers
+  const double* __restrict__ x0;    // the anchor
+  const double* __restrict__ y0;
+  const double* __restrict__ aty0;
+};
+// x' is kept on the last step of a run only (the evaluation behind it reads it; every other step would store 8 n bytes for nobody)
+__device__ __forceinline__ bool halpern_last_step(const pdlpdev_ctl* ctl) { return ctl->steps_taken + 1 >= ctl->target_steps; }
 // (2h) rows of A: y' as in DualEpilogue -> yp (the vector the A^T product gathers, and the dual half of T(z^k)), ||dy||^2 partial,
 //      y^{k+1} -> yn
 struct HalpernDualEpilogue {
@@ -170,6 +198,12 @@ struct HalpernDualEpilogue {
     const double dy  = next - yi;
     acc[0] += dy * dy;
     yn[i] = hw.combine(next, yi, y0[i]);
+  }
+  static __device__ __forceinline__ HalpernDualEpilogue make(const pdlpdev_ctl* ctl, double* y0, double* y1, const double* lo, const double* hi,
+                                                             const HalpernArgs& h)
+  {
+    const int cur = ctl->cur;
+    return HalpernDualEpilogue{cur ? y1 : y0, cur ? y0 : y1, h.ty, h.y0, lo, hi, ctl->sigma, HalpernWeights(h.hal)};
   }
 };
 // (3h) rows of A^T: v = A^T y' with StepEpilogue's two sums (dx . (A^T y' - A^T y^k) = dy . A dx, ||dx||^2), then x^{k+1} over x'
@@ -197,18 +231,14 @@ struct HalpernStepEpilogue {
     xn[j]   = hw.combine(xt, xj, x0[j]);
     atyn[j] = hw.combine(v, a, aty0[j]);
   }
+  static __device__ __forceinline__ HalpernStepEpilogue make(const pdlpdev_ctl* ctl, double* x0, double* x1, double* aty0, double* aty1,
+                                                             const HalpernArgs& h)
+  {
+    const int cur = ctl->cur;
+    return HalpernStepEpilogue{cur ? x1 : x0, cur ? x0 : x1, cur ? aty1 : aty0, cur ? aty0 : aty1, h.x0, h.aty0,
+                               halpern_last_step(ctl) ? h.tx : nullptr, HalpernWeights(h.hal)};
+  }
 };
-// what the kernels of a Halpern step take besides their twins' arguments (by value: a handful of pointers)
-struct HalpernArgs {
-  const pdlpdev_halpern* __restrict__ hal;
-  double* __restrict__ tx;          // T(z^k), primal half (the AVERAGE slot)
-  double* __restrict__ ty;          // T(z^k), dual half: what the A^T product gathers
-  const double* __restrict__ x0;    // the anchor
-  const double* __restrict__ y0;
-  const double* __restrict__ aty0;
-};
-// x' is kept on the last step of a run only (the evaluation behind it reads it; every other step would store 8 n bytes for nobody)
-__device__ __forceinline__ bool halpern_last_step(const pdlpdev_ctl* ctl) { return ctl->steps_taken + 1 >= ctl->target_steps; }
 
 // (plain SpMV: A^T y at start / after restart-to-average; parity hook; multi-GPU partial products)
 struct StoreEpilogue {
@@ -216,7 +246,21 @@ struct StoreEpilogue {
   using Op = SumOp;
   double* __restrict__ out;
   __device__ __forceinline__ void row(int r, double v, double (&)[1]) { out[r] = v; }
+  // A^T y of the iterate on side `side` of the ping-pong pairs (ctl->cur: the current one, flipped: the trial iterate) into that
+  // side's buffer, or into `out_override`; the kernel gathers the same side of y
+  static __device__ __forceinline__ StoreEpilogue iterate(int side, double* aty0, double* aty1, double* out_override)
+  {
+    return StoreEpilogue{out_override ? out_override : (side ? aty1 : aty0)};
+  }
 };
+
+// The iterate an evaluation looks at: the running average, or the current side of a ping-pong pair (x and y alike).  It also picks
+// the current side of a pair that has no average, the A^T y buffers of k_panel_eval_dual_from_aty: `which` is PDLPDEV_CURRENT there
+// and `avg` null, never read.
+__device__ __forceinline__ const double* evaluated(int cur, int which, const double* v0, const double* v1, const double* avg)
+{
+  return which == PDLPDEV_AVERAGE ? avg : (cur ? v1 : v0);
+}
 
 // Convergence information, primal side (convergence_information.cu:221-248 + row part of :323-366):
 // rows of the SCALED A against the SCALED iterate; (A x)_i = (A^ x^)_i / D_r,i and y_i = y^_i D_r,i
@@ -313,10 +357,18 @@ struct DenseView {
 
 constexpr int kDenseChunk = 4096;
 
-// the gathered vector of a call site, picked on the device like the layouts do (see k_pb_products)
+// Which vector a product gathers, where a kernel is told so by its `mode` argument and picks it on the device (phase P of the
+// gather-free layout, the dense segments' kernels).  ONE encoding for the host (Gathered, pdlp_launch.hpp) and the device; the values
+// are those the kernels have always been launched with.
+enum GatherMode : int {
+  kGatherFixed   = 0,  // v0, as it is
+  kGatherTrial   = 1,  // of the ping-pong pair (v0, v1) the trial iterate, which the step in flight wrote: cur ? v0 : v1
+  kGatherCurrent = 2,  // ... the current iterate: cur ? v1 : v0
+};
+static_assert(kGatherFixed == 0 && kGatherTrial == 1 && kGatherCurrent == 2, "the values of the kernels' `mode` argument");
 __device__ __forceinline__ const double* pick_vector(const pdlpdev_ctl* ctl, const double* v0, const double* v1, int mode)
 {
-  if (mode == 0) return v0;
+  if (mode == kGatherFixed) return v0;
   const bool cur = ctl->cur != 0;
-  return (cur == (mode == 1)) ? v0 : v1;
+  return (cur == (mode == kGatherTrial)) ? v0 : v1;
 }

@@ -359,7 +359,7 @@ static int enqueue_eval(pdlpdev_ctx* ctx, int which, int rc_rule_finite_bounds, 
   // layout of sc: [0..2] primal sums, [3] primal linf, [4..7] dual sums, [8] dual linf
   // the vectors the two products gather: the alternative iterate itself, or the current one as the control block names it
   const bool alt = kw == PDLPDEV_AVERAGE;
-  TRY(launch_product(ctx, ctx->A, products::eval_primal, alt ? Gathered{altx, nullptr, 0, 0} : Gathered{ctx->x[0], ctx->x[1], 2, 0}, std::make_tuple(ctx->ctl, kwg),
+  TRY(launch_product(ctx, ctx->A, products::eval_primal, alt ? Gathered::fixed(altx) : Gathered::current(ctx->x[0], ctx->x[1]), std::make_tuple(ctx->ctl, kwg),
                      std::make_tuple(ctx->x[0], ctx->x[1], altx),
                      std::make_tuple(ctx->y[0], ctx->y[1], alty, ctx->dr, ctx->lo_u, ctx->hi_u, eps_rel_primal, linf_m, ctx->ax_u[which], ctx->A.part)));
   // one reduction launch for both sides of the evaluation where nothing else needs the primal sums in between
@@ -379,7 +379,7 @@ static int enqueue_eval(pdlpdev_ctx* ctx, int which, int rc_rule_finite_bounds, 
     k_panel_eval_dual_from_aty<<<ctx->At.pan.v.W, kPanelThreads, 0, s>>>(ctx->At.pan.v, ctx->ctl, ctx->x[0], ctx->x[1], ctx->aty[0], ctx->aty[1], core, ctx->At.part, guard);
     k_finalize_eval<<<1, kBlock, 0, s>>>(ctx->A.part, ctx->A.partials(), ctx->At.part, ctx->At.partials(), one_finalize ? 1 : 0, sc, ctx->ctl, guard, ctl_copy);
   } else if (!ctx->comm) {
-    TRY(launch_product(ctx, ctx->At, products::eval_dual, alt ? Gathered{alty, nullptr, 0, 0} : Gathered{ctx->y[0], ctx->y[1], 2, 0},
+    TRY(launch_product(ctx, ctx->At, products::eval_dual, alt ? Gathered::fixed(alty) : Gathered::current(ctx->y[0], ctx->y[1]),
                        std::make_tuple(ctx->ctl, kwg, ctx->x[0], ctx->x[1], altx), std::make_tuple(ctx->y[0], ctx->y[1], alty), std::make_tuple(core, ctx->At.part)));
     k_finalize_eval<<<1, kBlock, 0, s>>>(ctx->A.part, ctx->A.partials(), ctx->At.part, ctx->At.partials(), one_finalize ? 1 : 0, sc, ctx->ctl, guard, ctl_copy);
   } else {

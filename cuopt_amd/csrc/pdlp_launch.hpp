@@ -1,11 +1,12 @@
 // Launch helpers shared by the translation units of the core (pdlp_device.hip: set-up, the attempt, results; pdlp_eval.hip: the major
 // iteration): argument packing for hipExtLaunchKernel-style launches with the context's timing hooks, the per-layout launch wrappers
 // (the two geometries of the jagged kernels, the two launches of a gather-free product), and launch_product, which takes one product
-// of one matrix side to the kernels of the side's layout.  Static state (the "attribute already set" lists) is per translation unit:
+// of one matrix side to the kernels of the side's layout.  Static state (the "attribute already set" list) is per translation unit:
 // setting a kernel's attribute twice is harmless.
 #pragma once
 #include <algorithm>
 #include <mutex>
+#include <tuple>
 #include <utility>
 #include <vector>
 
@@ -32,59 +33,44 @@ static void launch_k(pdlpdev_ctx* c, void (*kernel)(KArgs...), dim3 grid, dim3 b
   }
   kernel<<<grid, block, lds, c->stream>>>(static_cast<KArgs>(args)...);
 }
-// Launch of a jagged-layout kernel: 80 or 160 KiB of dynamic LDS (the attribute is per kernel and device, set once)
+// A kernel that takes more dynamic LDS than the default limit allows: the attribute is per kernel and device, and set ONCE, under the
+// lock, the first time the triple (kernel, device, size) comes by.  A kernel's launches all ask for the same size today (jag by
+// WAVES, pb by WIDE, phase P always 160 KiB); the size is part of the key so that one which ever asks for a second size gets it set.
+static int allow_dynamic_lds(const void* kernel, int device, size_t bytes)
+{
+  static std::mutex mu;
+  static std::vector<std::tuple<const void*, int, size_t>> done;
+  std::lock_guard<std::mutex> lock(mu);
+  const std::tuple<const void*, int, size_t> key(kernel, device, bytes);
+  if (std::find(done.begin(), done.end(), key) == done.end()) {
+    HIP_TRY(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    done.push_back(key);
+  }
+  return 0;
+}
+// Launch of a jagged-layout kernel: 80 or 160 KiB of dynamic LDS
 template <typename... KArgs, typename... Args>
 static int jag_launch(pdlpdev_ctx* c, void (*kernel)(JagView, KArgs...), const JagView& v, Args... args)
 {
-  static std::mutex mu;
-  static std::vector<std::pair<const void*, int>> done;
   const size_t lds = jag_lds_bytes(v.waves);
-  {
-    std::lock_guard<std::mutex> lock(mu);
-    const std::pair<const void*, int> key((const void*)kernel, c->device);
-    if (std::find(done.begin(), done.end(), key) == done.end()) {
-      HIP_TRY(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      done.push_back(key);
-    }
-  }
+  TRY(allow_dynamic_lds((const void*)kernel, c->device, lds));
   launch_k(c, kernel, ((v.nblk + 7) & ~7) + v.nlong, v.waves * 64, lds, v, args...);
   return 0;
 }
-// the two launches of a gather-free SpMV: phase P with the gathered vector picked on the device (mode: see k_pb_products), ...
+// the two launches of a gather-free SpMV: phase P with the gathered vector picked on the device (mode: GatherMode), ...
 static int pb_products(pdlpdev_ctx* c, const pdlpdev_ctx::Pb& L, const double* v0, const double* v1, int mode, int in_loop)
 {
-  static std::mutex mu;
-  static std::vector<std::pair<int, int>> done;
-  {
-    std::lock_guard<std::mutex> lock(mu);
-    const std::pair<int, int> key(L.p_threads, c->device);
-    if (std::find(done.begin(), done.end(), key) == done.end()) {
-      if (L.p_threads == 1024) HIP_TRY(hipFuncSetAttribute((const void*)k_pb_products<1024>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      else HIP_TRY(hipFuncSetAttribute((const void*)k_pb_products<512>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      done.push_back(key);
-    }
-  }
-  const int grid   = (L.v.nwg + 7) & ~7;
-  const size_t lds = sizeof(double) << L.v.panel_shift;
-  if (L.p_threads == 1024) launch_k(c, k_pb_products<1024>, grid, 1024, lds, L.v, c->ctl, v0, v1, mode, in_loop);
-  else launch_k(c, k_pb_products<512>, grid, 512, lds, L.v, c->ctl, v0, v1, mode, in_loop);
+  const auto kernel = L.p_threads == 1024 ? k_pb_products<1024> : k_pb_products<512>;
+  TRY(allow_dynamic_lds((const void*)kernel, c->device, 160 * 1024));
+  launch_k(c, kernel, (L.v.nwg + 7) & ~7, L.p_threads == 1024 ? 1024 : 512, sizeof(double) << L.v.panel_shift, L.v, c->ctl, v0, v1, mode, in_loop);
   return 0;
 }
 // ... and phase R with the epilogue of the call site (two skeletons: the image in LDS, or -- wide bins -- the accumulators in LDS)
 template <typename... KArgs, typename... Args>
 static int pb_rows_launch(pdlpdev_ctx* c, void (*kernel)(PbView, KArgs...), const pdlpdev_ctx::Pb& L, Args... args)
 {
-  static std::mutex mu;
-  static std::vector<std::pair<const void*, int>> done;
-  const size_t lds  = L.v.wide ? kPbwLdsBytes : kPbLdsBytes;
-  {
-    std::lock_guard<std::mutex> lock(mu);
-    const std::pair<const void*, int> key((const void*)kernel, c->device);
-    if (std::find(done.begin(), done.end(), key) == done.end()) {
-      HIP_TRY(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      done.push_back(key);
-    }
-  }
+  const size_t lds = L.v.wide ? kPbwLdsBytes : kPbLdsBytes;
+  TRY(allow_dynamic_lds((const void*)kernel, c->device, lds));
   launch_k(c, kernel, (L.v.B + 7) & ~7, L.v.wide ? kPbwThreads : kPbThreads, lds, L.v, args...);
   return 0;
 }
@@ -117,10 +103,14 @@ inline const auto a_halpern   = PRODUCT_KERNELS(k_spmv_a_halpern, a_halpern);
 inline const auto at_halpern  = PRODUCT_KERNELS(k_spmv_at_halpern, at_halpern);
 }  // namespace products
 
-// the vector a product gathers, as the device picks it: v0, or v0 / v1 by the control block (mode: see k_pb_products)
+// the vector a product gathers, as the device picks it (GatherMode, pdlp_epilogues.hpp): one vector as it is, or the trial / the
+// current side of a ping-pong pair by the control block; in_loop: the product belongs to an attempt (its kernels ask loop_active)
 struct Gathered {
   const double *v0, *v1;
   int mode, in_loop;
+  static Gathered fixed(const double* v, bool in_loop = false) { return {v, nullptr, kGatherFixed, in_loop ? 1 : 0}; }
+  static Gathered trial(const double* v0, const double* v1, bool in_loop = false) { return {v0, v1, kGatherTrial, in_loop ? 1 : 0}; }
+  static Gathered current(const double* v0, const double* v1, bool in_loop = false) { return {v0, v1, kGatherCurrent, in_loop ? 1 : 0}; }
 };
 // dense row segments: their share of the product lands in the side's dense_add right before the layout's kernel adds it -- unless the
 // side's panels add the segments themselves; the owner-computes column block has none
@@ -139,6 +129,8 @@ static void dense_prologue(pdlpdev_ctx* c, const pdlpdev_ctx::MatrixSide& s, con
 // The launches of one product: the dense prologue, then the layout's kernel (the gather-free layout: phase P, then its row kernel).
 // The kernel's arguments come in three groups behind the layout's own leading ones: `pre`, `vecs` (the gathered vectors' pointers:
 // the gather-free row kernel goes without them, phase P consumed `g`) and `post`; the stream kernel ends with the side's dense_add.
+// Together they are the product's list in pdlp_kernel_decls.hpp: <PRODUCT>_KERNELS' ROW line is pre + vecs + post, its PB line
+// pre + post.  `g` names the same vector for the kernels that pick it on the device (Gathered's makers above).
 // Returns the code of an attribute call that failed (launch errors are left to the caller's hipGetLastError, as ever).
 template <class K, class... Pre, class... Vecs, class... Post>
 static int launch_product(pdlpdev_ctx* c, const pdlpdev_ctx::MatrixSide& s, const K& k, const Gathered& g, const std::tuple<Pre...>& pre,
