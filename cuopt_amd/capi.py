@@ -276,6 +276,8 @@ _proto("pdlpdev_project_primal", c_int, c_void_p)
 _proto("pdlpdev_compute_aty", c_int, c_void_p)
 _proto("pdlpdev_run", c_int, c_void_p, c_int, P(Ctl))
 _proto("pdlpdev_get_ctl", c_int, c_void_p, P(Ctl))
+if hasattr(lib, "pdlpdev_debug_attempts"):  # (an older build given through CUOPT_AMD_LIB has no one-attempt hook)
+    _proto("pdlpdev_debug_attempts", c_int, c_void_p, c_int, P(Ctl))
 _proto("pdlpdev_clear_error", c_int, c_void_p)
 _proto("pdlpdev_set_graph_mode", c_int, c_void_p, c_int)
 _proto("pdlpdev_prepare_graphs", c_int, c_void_p)
@@ -292,6 +294,7 @@ _proto("pdlpdev_trust_region_bounds", c_int, c_void_p, c_int, c_double, c_double
 _proto("pdlpdev_eval_infeasibility", c_int, c_void_p, c_int, c_int, c_void_p)
 _proto("pdlpdev_get_solution", c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p)
 _proto("pdlpdev_download", C.c_int64, c_void_p, c_int, c_void_p, C.c_int64)
+_proto("pdlpdev_upload", C.c_int64, c_void_p, c_int, c_void_p, C.c_int64)
 _proto("pdlpdev_spmv", c_int, c_void_p, c_int, c_void_p, c_void_p)
 _proto("pdlpdev_time_kernel", c_int, c_void_p, c_int, c_int, P(c_double))
 _proto("pdlpdev_synchronize", c_int, c_void_p)
@@ -1075,6 +1078,12 @@ class Device:
         self._ck(lib.pdlpdev_run(self.handle, int(target_steps), C.byref(c)))
         return c
 
+    def attempts(self, count=1):
+        """pdlpdev_debug_attempts: `count` attempts as run() enqueues them and NO make-up round -> the control block behind them"""
+        c = Ctl()
+        self._ck(lib.pdlpdev_debug_attempts(self.handle, int(count), C.byref(c)))
+        return c
+
     # ---- reflected Halpern mode (pdlp_device.h) ----
     def set_halpern(self, on=True):
         self._ck(lib.pdlpdev_set_halpern(self.handle, int(bool(on))))
@@ -1103,6 +1112,13 @@ class Device:
         if got < 0:
             raise CuOptError(int(got), lib.pdlpdev_last_error().decode())
         return out[:got]
+
+    def upload(self, name, values):
+        """pdlpdev_upload: overwrite a buffer (scaled space); the whole of `values` must fit"""
+        values = _f64(values)
+        got = lib.pdlpdev_upload(self.handle, BUF[name], _ptr(values), len(values))
+        if got != len(values):
+            raise CuOptError(int(min(got, -1)), lib.pdlpdev_last_error().decode())
 
     def spmv(self, x, transpose=False, rows=None):
         x = _f64(x)

@@ -1181,6 +1181,28 @@ int pdlpdev_run(pdlpdev_ctx* ctx, int32_t target_steps, pdlpdev_ctl* ctl)
   return run_epilogue(ctx, rounds, ctl);
 }
 
+// Parity hook: `count` attempts as pdlpdev_run enqueues them (same kernels, graph replay or plain launches), one read-back, after_round's
+// bookkeeping -- and NO make-up round, so a rejected attempt is there to be looked at: the trial iterate in the other side of the
+// ping-pong pairs, the decision's inputs in the control block.
+int pdlpdev_debug_attempts(pdlpdev_ctx* ctx, int count, pdlpdev_ctl* ctl)
+{
+  HIP_TRY(hipSetDevice(ctx->device));
+  if (ctx->small_resident || ctx->comm || ctx->halpern)
+    return fail(-7, "pdlpdev_debug_attempts: the multi-launch averaging attempt only (not the resident small-LP path, a sharded context or Halpern mode)");
+  if (count < 1 || count > 64) return fail(-1, "pdlpdev_debug_attempts: count must be 1 .. 64");
+  TRY(fetch_ctl(ctx, nullptr));
+  const int before = ctx->ctl_h->steps_taken, attempts_before = ctx->ctl_h->attempts;
+  TRY(set_target(ctx, before + count));
+  if (ctx->ctl_h->error == 0) {
+    TRY(enqueue_attempts(ctx, count));
+    TRY(fetch_ctl(ctx, nullptr));
+    ctx->stat_loop_syncs += 1;
+    TRY(after_round(ctx, before, attempts_before, count, count));
+  }
+  if (ctl) *ctl = *ctx->ctl_h;
+  return 0;
+}
+
 // One major-iteration period with ONE synchronisation: the attempts up to `target_steps`, a few spare ones (empty launches unless an
 // attempt in front of them was rejected), and behind them the head of the major iteration that is due at the target (pdlpdev_major_eval's
 // kernels, each of which does nothing unless the target was reached), then one read-back of the scalars and the control block.

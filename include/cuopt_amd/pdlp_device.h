@@ -502,6 +502,13 @@ int pdlpdev_spmv(pdlpdev_ctx* ctx, int transpose, const double* x, double* y);
 /* `reps` back-to-back launches of one kernel bracketed by HIP events on the solver stream;
  * *avg_ms = average duration of one launch.  State is not advanced (target_steps trick). */
 int pdlpdev_time_kernel(pdlpdev_ctx* ctx, int kernel_id, int reps, double* avg_ms);
+/* `count` (1 .. 64) PDHG attempts and nothing else: the target becomes steps_taken + count, the attempts go out exactly as pdlpdev_run
+ * enqueues them (the same kernels; graph replay or plain launches as pdlpdev_set_graph_mode says), the control block is read back into
+ * *ctl (may be NULL) and the host's bookkeeping of a round is done -- but NO make-up round follows a rejection.  After a rejected
+ * attempt the iterate is untouched, the trial iterate (x', y', A^T y') sits in the _OTHER buffers and last_interaction / last_movement /
+ * last_dx2 / last_dy2 are the decision's inputs (tests/attempt_reference.py checks every one of them).  With the step error up nothing
+ * is enqueued.  -7: the resident small-LP path, a sharded context, Halpern mode. */
+int pdlpdev_debug_attempts(pdlpdev_ctx* ctx, int count, pdlpdev_ctl* ctl);
 /* device-side generation of the iterate is not needed; but benches need a sync point */
 int pdlpdev_synchronize(pdlpdev_ctx* ctx);
 /* bytes of device memory held by the context */

@@ -1,0 +1,274 @@
+"""CPU: the restatement of one adaptive PDHG attempt (tests/attempt_reference.py) against numbers worked out by hand and against the C
+oracle, and the scenario of tests/test_attempt_layouts_gpu.py (tests/attempt_scenario.py) on a plain float64 stand-in for the device,
+on every LP and seed the GPU test uses: the stand-in stays inside every derived bound, and the scenario has the properties the GPU
+test relies on (accepted steps from both sides of the ping-pong pairs, attempts with and without a pending average, a forced rejection
+with step / limit >= 2, no natural decision within 1e-6 of a tie)."""
+import numpy as np
+import pytest
+
+import attempt_reference as ar
+import attempt_scenario as sc
+import eval_reference as er
+from cuopt_amd import synthetic
+from eval_lps import SEEDS, WIDE_N, edge_lp
+from oracle import orcbind
+
+INF = np.inf
+# (long_col, dense, seed[, columns]): what the GPU test builds
+LPS = [(4500, False, SEEDS[0]), (2400, False, SEEDS[0]), (4500, True, SEEDS[1]), (2400, True, SEEDS[1]), (2400, False, SEEDS[0], WIDE_N)]
+LP_IDS = ["col4500", "col2400", "dense-col4500", "dense-col2400", "col2400-60000-columns"]
+SP_EXACT = dict(reduction_exponent=1.0, growth_exponent=2.0, primal_distance_smoothing=0.5, dual_distance_smoothing=0.5)  # (k + 2)^-1, ^-2: exact
+
+
+def step_params(mode=1):
+    h, H = orcbind.hyper_preset(mode), orcbind.H
+    return {k: float(h[H["ORC_H_" + k.upper()]]) for k in ("reduction_exponent", "growth_exponent", "primal_distance_smoothing", "dual_distance_smoothing")}
+
+
+def scaling_of(p):
+    """Ruiz 10 + Pock-Chambolle alpha 1: what pdlpdev_scaling_compute(1, 10, 1, 1.0) gives (test_kernels_gpu: bit for bit)"""
+    h, H = orcbind.hyper_preset(1), orcbind.H
+    h[H["ORC_H_DO_RUIZ"]], h[H["ORC_H_RUIZ_ITERATIONS"]], h[H["ORC_H_DO_POCK_CHAMBOLLE"]], h[H["ORC_H_ALPHA_POCK_CHAMBOLLE"]] = 1, 10, 1, 1.0
+    return orcbind.compute_scaling(p["m"], p["n"], p["offsets"], p["indices"], p["values"], h)
+
+
+def ctl_of(**over):
+    c = dict(step_size=0.0, primal_weight=1.0, tau=0.0, sigma=0.0, sum_weights=0.0, last_interaction=0.0, last_movement=0.0, last_dx2=0.0,
+             last_dy2=0.0, k=0, cur=0, pending_avg=0, steps_taken=0, attempts=0, target_steps=1 << 30, error=0, its_since_restart=0)
+    c.update(over)
+    return c
+
+
+def arrays(**kw):
+    return {k: np.array(v, dtype=np.float64) for k, v in kw.items()}
+
+
+def stages(S, prob, ctl, st, sp, exact):
+    """the attempt stage by stage, each from the reference's own output of the stage in front -> (x', xbar, y', A^T y', sums, decision)"""
+    p = ar.primal(prob, ctl, st)
+    d = ar.dual(S, prob, ctl, st, p["xbar"], exact)
+    a = ar.aty_product(S, prob, d["y"], exact)
+    s = ar.step_sums(st, p["xn"], d["y"], a["aty"], exact)
+    dec = ar.decision(ctl, float(s["dy2"][0]), float(s["inter"][0]), float(s["dx2"][0]), sp)
+    return p, d, a, s, dec
+
+
+@pytest.mark.parametrize("exact", [False, True], ids=["longdouble", "fractions"])
+def test_accepted_attempt_by_hand(exact):
+    """A = [1 2; 0 1], c = (-1, -2), 0 <= x, x_1 <= 1, row 0: <= 1, row 1: = 2; from x = y = 0 with step 1/2 at weight 2
+    (tau = 1/4, sigma = 1).  Every number is a dyadic rational except the limit 9/11.
+       x' = (1/4, 1/2), xbar = (1/2, 1), A xbar = (5/2, 1)
+       row 0: next = -5/2, up = -3/2 < 0, low = -inf: y' = -3/2          row 1: next = -1, low = up = 1, min(up, 0) = 0: y' = 1
+       A^T y' = (-3/2, -2); dx = (1/4, 1/2), dy = (-3/2, 1): dx2 = 5/16, dy2 = 13/4, interaction = -3/8 - 1 = -11/8
+       movement = (1/2) 2 (5/16) + (1/4) (13/4) = 9/8, limit = 9/11 >= 1/2: accepted, margin 11/18
+       k = 1: s1 = (1 - 1/2) 9/11, s2 = (1 + 1/4) 1/2 = 5/8: the new step is s1"""
+    exact = exact or not er.LONGDOUBLE_IS_EXTENDED
+    S = ar.Structure(2, 2, [0, 2, 3], [0, 1, 1])
+    prob = arrays(A_VALUES=[1, 2, 1], C=[-1, -2], LB=[0, 0], UB=[INF, 1], LO=[-INF, 2], HI=[1, 2])
+    st = arrays(X=[0, 0], Y=[0, 0], ATY=[0, 0], SUM_X=[1, 1], SUM_Y=[2, 2])
+    ctl = ctl_of(step_size=0.5, primal_weight=2.0, tau=0.25, sigma=1.0)
+    p, d, a, s, dec = stages(S, prob, ctl, st, SP_EXACT, exact)
+    np.testing.assert_array_equal(p["xn"], [0.25, 0.5])
+    np.testing.assert_array_equal(p["xbar"], [0.5, 1.0])
+    np.testing.assert_array_equal(p["sumx"], [1, 1])  # (nothing pending: untouched)
+    np.testing.assert_array_equal(d["y"], [-1.5, 1.0])
+    np.testing.assert_array_equal(d["sumy"], [2, 2])
+    assert not d["branch_tie"].any()
+    # bounds: sigma (L + 16) u S + 8 u (|y| + sigma |v| + sigma |b|), S = |v| = (5/2, 1), b = (1, 2), L = (2, 1)
+    np.testing.assert_allclose(d["bound"], [(18 * 2.5 + 8 * 3.5) * er.U, (17 * 1.0 + 8 * 3.0) * er.U], rtol=1e-15)
+    np.testing.assert_array_equal(a["aty"], [-1.5, -2.0])
+    np.testing.assert_allclose(a["bound"], [17 * 1.5 * er.U, 18 * 4.0 * er.U], rtol=1e-15)  # |a y'| sums: 3/2 and 3 + 1
+    assert (float(s["dx2"][0]), float(s["dy2"][0]), float(s["inter"][0])) == (0.3125, 3.25, -1.375)
+    assert s["inter"][1] == 18 * er.U * 1.375 and s["dx2"][1] == 18 * er.U * 0.3125 and s["dy2"][1] == 18 * er.U * 3.25
+    c = dec["ctl"]
+    assert dec["accepted"] and c["last_movement"] == 1.125 and dec["limit"] == 1.125 / 1.375 and dec["margin"] == pytest.approx(11 / 18, rel=1e-15)
+    assert c["step_size"] == 0.5 * (1.125 / 1.375) and c["tau"] == c["step_size"] / 2.0 and c["sigma"] == c["step_size"] * 2.0
+    assert (c["k"], c["attempts"], c["steps_taken"], c["its_since_restart"], c["cur"], c["pending_avg"], c["error"]) == (1, 1, 1, 1, 1, 1, 0)
+    assert c["sum_weights"] == c["step_size"]
+    # ... and check_attempt accepts exactly this as a device's answer, and names a stage when one number is off
+    before = dict(st, ctl=ctl, X_OTHER=np.zeros(2), Y_OTHER=np.zeros(2), ATY_OTHER=np.zeros(2))
+    after = dict(ctl=dict(c, target_steps=1), X=p["xn"], Y=d["y"], ATY=a["aty"], X_OTHER=st["X"], Y_OTHER=st["Y"], ATY_OTHER=st["ATY"],
+                 SUM_X=st["SUM_X"], SUM_Y=st["SUM_Y"], XBAR=p["xbar"])
+    before["ctl"]["target_steps"] = 1
+    r = ar.check_attempt(S, prob, SP_EXACT, before, after, exact=exact)
+    assert r["accepted"] and r["ratios"] == dict(y=0.0, aty=0.0, dy2=0.0, dx2=0.0, inter=0.0)
+    for key, value, stage in (("Y", [-1.5, 1.0 + 2.0 ** -40], "y'"), ("ATY", [-1.5 + 2.0 ** -40, -2.0], "A^T y'"), ("SUM_Y", [2, 2.5], "SUM_Y"),
+                              ("XBAR", [0.5, np.nextafter(1.0, 2.0)], "xbar")):
+        with pytest.raises(AssertionError, match=stage.replace("^", r"\^")):
+            ar.check_attempt(S, prob, SP_EXACT, before, dict(after, **{key: np.array(value)}), exact=exact)
+    for key, value, stage in (("last_dy2", 3.25 * (1 + 2.0 ** -40), "dy2"), ("sum_weights", 0.5, "sum_weights"), ("pending_avg", 0, "pending_avg")):
+        with pytest.raises(AssertionError, match=stage):
+            ar.check_attempt(S, prob, SP_EXACT, before, dict(after, ctl=dict(after["ctl"], **{key: value})), exact=exact)
+
+
+@pytest.mark.parametrize("exact", [False, True], ids=["longdouble", "fractions"])
+def test_rejected_attempt_by_hand(exact):
+    """A = [1 0 2; 0 1 0], c = (-1, 0, 0), x >= 0, x_2 <= 0, row 0: = 3, row 1: free; from x = (0, 1, 0), y = 0 on side 1 of the
+    ping-pong pairs with step 2 at weight 1 (tau = sigma = 2), k = 2, an average pending.
+       x' = (2, 1, 0), xbar = (4, 1, 0), A xbar = (4, 1)
+       row 0: next = -8, low = up = -2: y' = -2                            row 1: free, min(+inf, 0) = 0: y' = 0
+       A^T y' = (-2, 0, -4); dx = (2, 0, 0), dy = (-2, 0): dx2 = dy2 = 4, interaction = -4, movement = 2 + 2 = 4, limit = 1 < 2:
+       REJECTED with margin 2.  k = 3: s1 = (1 - 1/4) 1 = 3/4, s2 = (1 + 1/16) 2: the new step is 3/4.
+       The pending average is consumed all the same: SUM_X + 2 x = (1, 4, 3), SUM_Y + 2 y = (4, 5); pending_avg = 0 afterwards."""
+    exact = exact or not er.LONGDOUBLE_IS_EXTENDED
+    S = ar.Structure(2, 3, [0, 2, 3], [0, 2, 1])
+    prob = arrays(A_VALUES=[1, 2, 1], C=[-1, 0, 0], LB=[0, 0, 0], UB=[INF, INF, 0], LO=[3, -INF], HI=[3, INF])
+    st = arrays(X=[0, 1, 0], Y=[0, 0], ATY=[0, 0, 0], SUM_X=[1, 2, 3], SUM_Y=[4, 5])
+    ctl = ctl_of(step_size=2.0, primal_weight=1.0, tau=2.0, sigma=2.0, sum_weights=10.0, k=2, cur=1, pending_avg=1, steps_taken=7, attempts=9,
+                 its_since_restart=3)
+    p, d, a, s, dec = stages(S, prob, ctl, st, SP_EXACT, exact)
+    np.testing.assert_array_equal(p["xn"], [2, 1, 0])
+    np.testing.assert_array_equal(p["xbar"], [4, 1, 0])
+    np.testing.assert_array_equal(p["sumx"], [1, 4, 3])
+    np.testing.assert_array_equal(d["y"], [-2, 0])
+    np.testing.assert_array_equal(d["sumy"], [4, 5])
+    assert d["bound"][1] == (17 * 2.0 + 8 * 2.0) * er.U  # (the free row: sigma |v| = 2 twice, no bound term)
+    np.testing.assert_array_equal(a["aty"], [-2, 0, -4])
+    assert (float(s["dx2"][0]), float(s["dy2"][0]), float(s["inter"][0])) == (4.0, 4.0, -4.0)
+    c = dec["ctl"]
+    assert not dec["accepted"] and (c["last_movement"], dec["limit"], dec["margin"]) == (4.0, 1.0, 2.0)
+    assert (c["step_size"], c["tau"], c["sigma"]) == (0.75, 0.75, 0.75)
+    assert (c["k"], c["attempts"], c["steps_taken"], c["its_since_restart"], c["cur"], c["pending_avg"], c["error"]) == (3, 10, 7, 3, 1, 0, 0)
+    assert c["sum_weights"] == 10.0
+    before = dict(st, ctl=ctl, X_OTHER=np.zeros(3), Y_OTHER=np.zeros(2), ATY_OTHER=np.zeros(3))
+    after = dict(st, ctl=c, X_OTHER=p["xn"], Y_OTHER=d["y"], ATY_OTHER=a["aty"], SUM_X=p["sumx"], SUM_Y=d["sumy"], XBAR=p["xbar"])
+    r = ar.check_attempt(S, prob, SP_EXACT, before, after, exact=exact)
+    assert not r["accepted"] and r["margin"] == 2.0 and r["pending_before"] == 1 and r["cur_before"] == 1
+    with pytest.raises(AssertionError, match="pending_avg"):  # (left set behind a rejection: the iterate would be averaged twice)
+        ar.check_attempt(S, prob, SP_EXACT, before, dict(after, ctl=dict(c, pending_avg=1)), exact=exact)
+    with pytest.raises(AssertionError, match="SUM_X"):
+        ar.check_attempt(S, prob, SP_EXACT, before, dict(after, SUM_X=st["SUM_X"]), exact=exact)
+    with pytest.raises(AssertionError, match="changed its own input"):
+        ar.check_attempt(S, prob, SP_EXACT, before, dict(after, X=p["xn"]), exact=exact)
+
+
+def test_scalar_branches_of_the_decision():
+    """movement 0: the step error, k and the step untouched, the buffers flip and the weight sum grows by the step;
+    interaction 0: accepted whatever the step, which grows by its full factor"""
+    ctl = ctl_of(step_size=0.5, primal_weight=2.0, tau=0.25, sigma=1.0, k=3, sum_weights=1.0)
+    d = ar.decision(ctl, 0.0, 0.0, 0.0, SP_EXACT)
+    assert d["accepted"] and d["ctl"] == dict(ctl, error=1, cur=1, pending_avg=1, sum_weights=1.5, steps_taken=1, its_since_restart=1, attempts=1)
+    d = ar.decision(ctl, 4.0, 0.0, 0.0, SP_EXACT)
+    assert d["accepted"] and d["limit"] == INF and d["margin"] == 0.0 and d["ctl"]["k"] == 4 and d["ctl"]["step_size"] == (1.0 + 1.0 / 25.0) * 0.5
+    assert ar.decision(ctl, float("nan"), 1.0, 1.0, SP_EXACT)["ctl"]["error"] == 1
+
+
+def small_mixed_lp(seed=3):
+    """300 x 200 with every kind of row and column bound, rows of 0 .. 12 entries"""
+    p, x, y = sc.tiny_lp("dual-only", seed=seed, m=300, n=200, density=0.03)
+    rng = np.random.default_rng(seed + 100)
+    kind_r, kind_c = rng.integers(0, 5, size=300), rng.integers(0, 4, size=200)
+    b = p["lo"]
+    p["lo"] = np.choose(kind_r, [np.full(300, -INF), b, b, np.full(300, -INF), b - 1.0])
+    p["hi"] = np.choose(kind_r, [b, np.full(300, INF), b, np.full(300, INF), b + 1.0])
+    p["lb"] = np.choose(kind_c, [np.full(200, -INF), np.zeros(200), np.zeros(200), np.full(200, -INF)])
+    p["ub"] = np.choose(kind_c, [np.full(200, INF), np.full(200, INF), np.full(200, 2.0), np.full(200, 2.0)])
+    p["c"] = rng.standard_normal(200)
+    return p, x, rng.standard_normal(300)
+
+
+@pytest.mark.parametrize("which", ["synthetic", "mixed"])
+def test_fixed_steps_match_the_oracle_bit_for_bit(which):
+    """x and y behind orc_pdhg_fixed_steps: the element-wise expressions of the reference around row sums taken left to right in
+    float64 (rowsums_f64: the oracle's order) give the oracle's bits; the extended sums stay within their own bounds of them"""
+    if which == "synthetic":
+        p = synthetic.generate(400, 300, 6, seed=3)
+        rng = np.random.default_rng(2)
+        x0, y0 = np.abs(rng.standard_normal(p["n"])), rng.standard_normal(p["m"])
+    else:
+        p, x0, y0 = small_mixed_lp()
+    m, n = p["m"], p["n"]
+    S = ar.Structure(m, n, p["offsets"], p["indices"])
+    to, ti, tv = orcbind.transpose(m, n, p["offsets"], p["indices"], p["values"])
+    np.testing.assert_array_equal(tv, np.asarray(p["values"])[S.order])  # (the reference's own transposition)
+    np.testing.assert_array_equal(to, S.t_off)
+    prob = arrays(A_VALUES=p["values"], C=p["c"], LB=p["lb"], UB=p["ub"], LO=p["lo"], HI=p["hi"])
+    step, w = 0.05, 1.3
+    ctl = ctl_of(step_size=step, primal_weight=w, tau=step / w, sigma=step * w)
+    P, off, idx, val = orcbind._p, np.ascontiguousarray(p["offsets"], np.int32), np.ascontiguousarray(p["indices"], np.int32), np.ascontiguousarray(p["values"])
+    x, y = x0.copy(), y0.copy()
+    aty = ar.rowsums_f64(tv, y, to, ti)
+    for it in range(1, 4):
+        xo, yo = x0.copy(), y0.copy()
+        orcbind.lib().orc_pdhg_fixed_steps(m, n, P(off), P(idx), P(val), P(to), P(ti), P(tv), P(prob["C"]), P(prob["LO"]), P(prob["HI"]), P(prob["LB"]),
+                                           P(prob["UB"]), step / w, step * w, it, P(xo), P(yo))
+        st = dict(X=x, Y=y, ATY=aty, SUM_X=np.zeros(n), SUM_Y=np.zeros(m))
+        pr = ar.primal(prob, ctl, st)
+        yn = ar.dual_f64(prob, ctl, st, ar.rowsums_f64(val, pr["xbar"], off, idx))
+        assert ar.bits_equal(pr["xn"], xo) and ar.bits_equal(yn, yo), it
+        d = ar.dual(S, prob, ctl, st, pr["xbar"])
+        assert er.worst_ratio(ar.abs_err(d, yo), d["bound"]) <= 1.0
+        x, y, aty = pr["xn"], yn, ar.rowsums_f64(tv, yn, to, ti)
+        a = ar.aty_product(S, prob, y)
+        assert er.worst_ratio(ar.abs_err(a, aty), a["bound"]) <= 1.0
+    assert np.abs(y - y0).max() > 1e-3 and np.abs(x - x0).max() > 1e-3
+
+
+def test_forty_iterations_follow_the_oracle():
+    """the reference replays the first 40 iterations of the oracle's solve with its OWN (extended) sums: the same accepted and
+    attempted counts, the same final step size (the sums differ in their last bits: rel 1e-9, as test_solve_gpu compares the device).
+    The preset's min_iteration_restart = 10 makes each of the first ten iterations a major one, with restarts and new primal weights
+    the attempt's restatement knows nothing of: it is 0 here, so that the 40 iterations are 40 steps of the loop and nothing else."""
+    p = synthetic.generate(800, 400, 5, seed=2)  # (two of the 40 steps take a second attempt)
+    h = orcbind.hyper_preset(1)
+    h[orcbind.H["ORC_H_MIN_ITERATION_RESTART"]] = 0
+    o = orcbind.solve(p, hyper=h, tol=0.0, iteration_limit=40)
+    assert o["status"] == "IterationLimit" and int(o["steps_taken"]) == 40 and o["num_restarts"] == 0
+    dr, dc = orcbind.compute_scaling(p["m"], p["n"], p["offsets"], p["indices"], p["values"], h)
+    S = ar.Structure(p["m"], p["n"], p["offsets"], p["indices"])
+    prob = dict(A_VALUES=p["values"] * dr[S.rows] * dc[S.idx], C=p["c"] * dc, LB=p["lb"] / dc, UB=p["ub"] / dc, LO=p["lo"] * dr, HI=p["hi"] * dr)
+    step, w = o["initial_step_size"], o["initial_primal_weight"]
+    assert step == 1.0 / np.abs(prob["A_VALUES"]).max()
+    ctl = ctl_of(step_size=step, primal_weight=w, tau=step / w, sigma=step * w)
+    x = np.minimum(np.maximum(np.zeros(p["n"]), prob["LB"]), prob["UB"])
+    st = dict(X=x, Y=np.zeros(p["m"]), ATY=np.zeros(p["n"]), SUM_X=np.zeros(p["n"]), SUM_Y=np.zeros(p["m"]))
+    sp, margins = step_params(1), []
+    while ctl["steps_taken"] < 40 and ctl["attempts"] < 400:
+        pr, d, a, s, dec = stages(S, prob, ctl, st, sp, None)
+        margins.append(dec["margin"])
+        if dec["accepted"]:
+            st = dict(X=pr["xn"], Y=d["y"], ATY=a["aty"], SUM_X=pr["sumx"], SUM_Y=d["sumy"])
+        else:
+            st = dict(st, SUM_X=pr["sumx"], SUM_Y=d["sumy"])
+        ctl = dec["ctl"]
+    assert min(abs(mg - 1.0) for mg in margins) >= 1e-9, "a decision too close to a tie to be compared: take another seed"
+    assert (ctl["steps_taken"], ctl["attempts"]) == (int(o["steps_taken"]), int(o["attempted_steps"]))
+    assert ctl["attempts"] > ctl["steps_taken"], "no rejection among them: the comparison would not see the rejection rule"
+    assert ctl["step_size"] == pytest.approx(o["final_step_size"], rel=1e-9)
+    assert ctl["primal_weight"] == o["final_primal_weight"]
+
+
+# ---- the GPU test's scenario on the float64 stand-in ------------------------------------------------------------------------------
+@pytest.fixture(scope="module", params=LPS, ids=LP_IDS)
+def lp(request):
+    p, x, y = edge_lp(*request.param)
+    return p, x, y, scaling_of(p)
+
+
+def test_scenario_on_the_stand_in(lp, request):
+    """every bound holds for plain float64 sums, and the scenario has the properties the GPU test asserts on the device"""
+    p, x0, y0, (dr, dc) = lp
+    dev, S, prob = sc.stand_in(p, x0, y0, dr, dc, step_params(1))
+    worst = sc.run_scenario(dev, S, prob, dev.sp, dr, dc, request.node.callspec.id)
+    print(worst.line(request.node.callspec.id))
+    assert max(worst.values()) <= 1.0 and min(worst[k] for k in ("y", "aty", "dy2", "dx2", "inter", "dist")) > 0.0, worst
+
+
+def test_uniform_bounds_variants_on_the_stand_in():
+    p, x0, y0 = edge_lp(4500, False, SEEDS[0])
+    dr, dc = scaling_of(p)
+    for name, q in sc.uniform_bounds_variants(p).items():
+        dev, S, prob = sc.stand_in(q, x0, y0, dr, dc, step_params(1))
+        worst = sc.Worst()
+        for i in range(3):
+            sc.assert_decided(sc.one_attempt(dev, S, prob, dev.sp, "%s %d" % (name, i), worst)[0], name)
+        print(worst.line("uniform-" + name))
+
+
+@pytest.mark.parametrize("kind", ["fixed-point", "dual-only"])
+def test_scalar_branch_lps_on_the_stand_in(kind):
+    p, x0, y0 = sc.tiny_lp(kind)
+    ones_m, ones_n = np.ones(p["m"]), np.ones(p["n"])
+    dev, S, prob = sc.stand_in(p, x0, y0, ones_m, ones_n, step_params(1))
+    r, before, after = sc.one_attempt(dev, S, prob, dev.sp, kind)
+    sc.assert_scalar_branch(kind, r, before, after, dev.sp)

@@ -107,12 +107,18 @@ def _iterate(dev, xname, yname, dr, dc):
     return dev.download(xname, len(dc)) * dc, dev.download(yname, len(dr)) * dr
 
 
-def _evaluations(name, reuse, monkeypatch):
+def variant_lp(name):
+    """(p, x0, y0, empty rows, empty columns) of id `name`: shared among the ids and the test files, read-only"""
+    return _lp(VARIANTS[name][2], VARIANTS[name][3], *VARIANTS[name][4:])
+
+
+def open_variant(name, p, monkeypatch, **tune):
+    """a context for LP p in the layout and geometry of id `name` (further CUOPT_AMD_TUNE keys in `tune`), and the assertions that
+    it IS that layout, that geometry and, where the id says so, the dense-segment prologue"""
     layout, knobs, long_col, dense = VARIANTS[name][:4]
-    p, x0, y0, empty_rows, empty_cols = _lp(long_col, dense, *VARIANTS[name][4:])
     m, n = p["m"], p["n"]
     monkeypatch.setenv("CUOPT_AMD_SPMV_LAYOUT", layout)
-    set_tune(monkeypatch, eval_reuse_aty=reuse, dense=1 if dense else 0, **knobs)
+    set_tune(monkeypatch, dense=1 if dense else 0, **knobs, **tune)
     dev = capi.Device(p)
     lay = dev.layout()
     print("LAYOUT %s %s" % (name, lay))
@@ -127,6 +133,14 @@ def _evaluations(name, reuse, monkeypatch):
         assert wide == bool(knobs.get("pb_wide")) and (wide or min(lay["A"]["workgroups"], lay["At"]["workgroups"]) >= -(-min(m, n) // 1024)), lay
     info = dev.dense_info()
     assert info["on"] == dense and (not dense or (info["segments"] >= 2 and info["entries"] > 4096 + 256)), info
+    return dev
+
+
+def _evaluations(name, reuse, monkeypatch):
+    layout, knobs, long_col, dense = VARIANTS[name][:4]
+    p, x0, y0, empty_rows, empty_cols = variant_lp(name)
+    m, n = p["m"], p["n"]
+    dev = open_variant(name, p, monkeypatch, eval_reuse_aty=reuse)
     worst = {}
 
     def vectors(slot, ref, phase):
