@@ -187,6 +187,25 @@ struct HalpernDualEpilogue {
   const double* __restrict__ hi;
   double sigma;
   HalpernWeights hw;
+  // the row's operands (as in DualEpilogue: a layout may request them before its row sums are ready)
+  struct Ops {
+    double y, lo, hi, y0;
+  };
+  __device__ __forceinline__ Ops load(int i) const { return Ops{y[i], lo[i], hi[i], y0[i]}; }
+  __device__ __forceinline__ void apply(int i, double v, const Ops& o, double (&acc)[1])
+  {
+    const double yi  = o.y;
+    double next      = yi - (sigma * v);
+    const double low = next + sigma * o.lo;
+    const double up  = next + sigma * o.hi;
+    next             = dmax(low, dmin(up, 0.0));
+    yp[i]            = next;
+    const double dy  = next - yi;
+    acc[0] += dy * dy;
+    yn[i] = hw.combine(next, yi, o.y0);
+  }
+  // (row() keeps its own wording -- y0[i] read behind the store to yp[i] -- so that the layouts that call it compile to the
+  // instructions they had: written as apply(load()) it moved 30 to 170 instructions in each of their Halpern kernels)
   __device__ __forceinline__ void row(int i, double v, double (&acc)[1])
   {
     const double yi  = y[i];
@@ -220,6 +239,23 @@ struct HalpernStepEpilogue {
   const double* __restrict__ aty0;
   double* __restrict__ xp;
   HalpernWeights hw;
+  // the row's operands (xn[j] is x', read here and overwritten in apply by the same lane)
+  struct Ops {
+    double x, xn, aty, x0, aty0;
+  };
+  __device__ __forceinline__ Ops load(int j) const { return Ops{x[j], xn[j], aty[j], x0[j], aty0[j]}; }
+  __device__ __forceinline__ void apply(int j, double v, const Ops& o, double (&acc)[2])
+  {
+    const double xj = o.x, xt = o.xn, a = o.aty;
+    const double dx = xt - xj;
+    const double t  = v - a;
+    acc[0] += t * dx;
+    acc[1] += dx * dx;
+    if (xp) xp[j] = xt;
+    xn[j]   = hw.combine(xt, xj, o.x0);
+    atyn[j] = hw.combine(v, a, o.aty0);
+  }
+  // (row() in its own wording, as in HalpernDualEpilogue: x0[j] and aty0[j] read where they are used)
   __device__ __forceinline__ void row(int j, double v, double (&acc)[2])
   {
     const double xj = x[j], xt = xn[j], a = aty[j];

@@ -1,6 +1,8 @@
 // The panel layout's SpMV skeleton (device code).  Included by kernels_panel.hip only; the layout's view struct and constants, which the
 // host side needs too, stay in pdlp_kernels.hpp.
 #pragma once
+#include <type_traits>
+
 #include "pdlp_kernels.hpp"
 
 namespace pdlp {
@@ -140,7 +142,31 @@ __device__ __forceinline__ double panel_dense_col(const PanelView& P, const Pane
   }
   return add;
 }
-// the fused epilogue over a panel's rows, natural order, from the row sums in LDS
+// the fused epilogue over a panel's rows, natural order, from the row sums in LDS: a lane's rows first, first + 512, ... through row(),
+// then the workgroup's partials
+template <class Epi>
+__device__ __forceinline__ void panel_epilogue_rows(const PanelView& P, Epi& epi, double (&acc)[Epi::NQ > 0 ? Epi::NQ : 1], const double* psum,
+                                                    int first, int r0, int nr, const PanelDenseSegs* D, const double* psum2)
+{
+  for (int r = first; r < nr; r += kPanelThreads)
+    if (__double_as_longlong(psum[r]) != kPanelNotMine) {
+      double v = psum2 ? psum[r] + psum2[r] : psum[r];
+      if (P.dn_pan_ptr) v = v + panel_dense_col(P, D, r0 + r);
+      epi.row(r0 + r, dense_plus(P.dense_add, r0 + r, v), acc);
+    }
+}
+template <class Epi>
+__device__ __forceinline__ void panel_epilogue_partials(const PanelView& P, double* __restrict__ partials, double (&acc)[Epi::NQ > 0 ? Epi::NQ : 1],
+                                                        double* red, int w)
+{
+  if constexpr (Epi::NQ > 0) {
+    block_reduce<typename Epi::Op, Epi::NQ, kPanelWaves>(acc, red);
+    if (threadIdx.x == 0) {
+#pragma unroll
+      for (int q = 0; q < Epi::NQ; ++q) partials[(size_t)q * P.W + w] = acc[q];
+    }
+  }
+}
 template <class Epi>
 __device__ __forceinline__ void panel_epilogue(const PanelView& P, Epi& epi, double* __restrict__ partials, const double* psum, double* red,
                                                int w, int r0, int nr, const PanelDenseSegs* D,
@@ -149,17 +175,128 @@ __device__ __forceinline__ void panel_epilogue(const PanelView& P, Epi& epi, dou
   double acc[Epi::NQ > 0 ? Epi::NQ : 1];
 #pragma unroll
   for (int q = 0; q < (Epi::NQ > 0 ? Epi::NQ : 1); ++q) acc[q] = Epi::Op::identity();
-  for (int r = threadIdx.x; r < nr; r += kPanelThreads)
-    if (__double_as_longlong(psum[r]) != kPanelNotMine) {
+  panel_epilogue_rows(P, epi, acc, psum, threadIdx.x, r0, nr, D, psum2);
+  panel_epilogue_partials<Epi>(P, partials, acc, red, w);
+}
+
+// ---- the epilogue's operands, requested before the last row sums ------------------------------------------------------------------
+// An epilogue with an `Ops` type (pdlp_epilogues.hpp: the two products of an attempt and their Halpern twins) splits row() into
+// load() and apply().  The walkers below request the operands of a lane's first kPanelEpiDepth rows in ONE batch where their final
+// chunk would have requested a following chunk: the round trip to HBM runs under the final chunk's row sums instead of once per
+// row, one after the other, at the tail of the kernel.  Register budget: the final chunk is peeled off the chunk loop, so the
+// batch is never live across the loop and takes the registers the stream no longer needs (va / ja / gathered x / ext_next, about
+// 45 VGPRs in the row kernel; the largest batch, HalpernStepEpilogue's, is 4 x 5 doubles = 40) -- every panel kernel stays within the
+// 128 VGPRs that two workgroups per CU allow.  Epilogues without `Ops` (Store, Eval) keep row() and their loop as it was.
+constexpr int kPanelEpiDepth = 4;  // rows per lane requested early (C3: ~1 960 rows per panel = 4 per lane); later rows: row()
+template <class Epi, class = void>
+struct PanelEarlyOps {
+  static constexpr bool on = false;
+  struct type {};
+};
+template <class Epi>
+struct PanelEarlyOps<Epi, std::void_t<typename Epi::Ops>> {
+  static constexpr bool on = true;
+  using type = typename Epi::Ops;
+};
+// (lanes without a row at a slot clamp the index like PANEL_REQUEST; a slot on a "not mine" row is loaded and never used)
+template <class Epi>
+__device__ __forceinline__ void panel_epilogue_request(const Epi& epi, typename Epi::Ops (&pre)[kPanelEpiDepth], int r0, int nr)
+{
+#pragma unroll
+  for (int q = 0; q < kPanelEpiDepth; ++q) {
+    int r  = threadIdx.x + q * kPanelThreads;
+    r      = r < nr ? r : 0;
+    pre[q] = epi.load(r0 + r);
+  }
+}
+// panel_epilogue with the operands of the first kPanelEpiDepth slots already requested: the same rows per lane in the same ascending
+// order into `acc`, the same skip, addends, reduction and partials slot
+template <class Epi>
+__device__ __forceinline__ void panel_epilogue_early(const PanelView& P, Epi& epi, double* __restrict__ partials, const double* psum, double* red,
+                                                     int w, int r0, int nr, const PanelDenseSegs* D,
+                                                     const typename Epi::Ops (&pre)[kPanelEpiDepth], const double* psum2 = nullptr)
+{
+  double acc[Epi::NQ > 0 ? Epi::NQ : 1];
+#pragma unroll
+  for (int q = 0; q < (Epi::NQ > 0 ? Epi::NQ : 1); ++q) acc[q] = Epi::Op::identity();
+  // ONE wait for the whole batch, in front of the first store: left to the compiler, slot q + 1 waits for its operands behind the
+  // branches around slot q's stores, where it no longer knows how many stores are in flight and waits for all of them -- a store's
+  // round trip per slot.  (gfx9 encoding of s_waitcnt: vmcnt(0), expcnt and lgkmcnt untouched)
+  __builtin_amdgcn_s_waitcnt(0x0F70);
+#pragma unroll
+  for (int q = 0; q < kPanelEpiDepth; ++q) {
+    const int r = threadIdx.x + q * kPanelThreads;
+    if (r < nr && __double_as_longlong(psum[r]) != kPanelNotMine) {
       double v = psum2 ? psum[r] + psum2[r] : psum[r];
       if (P.dn_pan_ptr) v = v + panel_dense_col(P, D, r0 + r);
-      epi.row(r0 + r, dense_plus(P.dense_add, r0 + r, v), acc);
+      epi.apply(r0 + r, dense_plus(P.dense_add, r0 + r, v), pre[q], acc);
     }
-  if constexpr (Epi::NQ > 0) {
-    block_reduce<typename Epi::Op, Epi::NQ, kPanelWaves>(acc, red);
-    if (threadIdx.x == 0) {
+  }
+  panel_epilogue_rows(P, epi, acc, psum, threadIdx.x + kPanelEpiDepth * kPanelThreads, r0, nr, D, psum2);
+  panel_epilogue_partials<Epi>(P, partials, acc, red, w);
+}
+
+// the row sums of one staged chunk [lo, hi) of its tile: lane r % 512 adds row r's segment of prod[] to psum[r]
+__device__ __forceinline__ void panel_row_sums(const PanelView& P, const unsigned (&ext)[kPanelRowsPer], const double* prod, double* psum,
+                                               int nr, int lo, int hi)
+{
+  if (!P.any_long) {  // (uniform) the common case: no extra instruction in the loop
 #pragma unroll
-      for (int q = 0; q < Epi::NQ; ++q) partials[(size_t)q * P.W + w] = acc[q];
+    for (int q = 0; q < kPanelRowsPer; ++q) {
+      const int r = threadIdx.x + q * kPanelThreads;
+      if (r < nr) {
+        int a = (int)(ext[q] & 0xFFFFu), b = (int)(ext[q] >> 16);
+        a = a > lo ? a : lo;
+        b = b < hi ? b : hi;
+        if (a < b) {
+          double sum = psum[r];
+          for (int k = a; k < b; ++k) sum = sum + prod[k - lo];
+          psum[r] = sum;
+        }
+      }
+    }
+    return;
+  }
+  bool any_long = false;
+#pragma unroll
+  for (int q = 0; q < kPanelRowsPer; ++q) {
+    const int r = threadIdx.x + q * kPanelThreads;
+    if (r < nr) {
+      int a = (int)(ext[q] & 0xFFFFu), b = (int)(ext[q] >> 16);
+      a = a > lo ? a : lo;
+      b = b < hi ? b : hi;
+      if (b - a > kLongRow) {
+        any_long = true;  // handled below, by the whole wave
+      } else if (a < b) {  // left to right by the row's lane: bit-identical to a sequential CSR sum
+        double sum = psum[r];
+        for (int k = a; k < b; ++k) sum = sum + prod[k - lo];
+        psum[r] = sum;
+      }
+    }
+  }
+  // A segment longer than kLongRow would keep ONE lane busy for thousands of dependent LDS reads: its wave sums it
+  // together instead (64 strided chains + the fixed butterfly; compared with a tolerance like every long row).
+  // One ballot per chunk on the common path.
+  if (__ballot(any_long)) {
+#pragma unroll
+    for (int q = 0; q < kPanelRowsPer; ++q) {
+      const int r = threadIdx.x + q * kPanelThreads;
+      int a = 0, b = 0;
+      if (r < nr) {
+        a = (int)(ext[q] & 0xFFFFu), b = (int)(ext[q] >> 16);
+        a = a > lo ? a : lo;
+        b = b < hi ? b : hi;
+      }
+      unsigned long long todo = __ballot(b - a > kLongRow);
+      while (todo) {
+        const int l  = __builtin_ctzll(todo);
+        todo &= todo - 1;
+        const int la = __builtin_amdgcn_readlane(a, l), lb = __builtin_amdgcn_readlane(b, l);
+        double part  = 0.0;
+        for (int k = la + (int)(threadIdx.x & 63); k < lb; k += 64) part = part + prod[k - lo];
+        part = wave_reduce<SumOp>(part);
+        if ((int)(threadIdx.x & 63) == l) psum[r] = psum[r] + part;
+      }
     }
   }
 }
@@ -173,6 +310,10 @@ __device__ __forceinline__ void panel_epilogue(const PanelView& P, Epi& epi, dou
 //            that owns the row adds the wave's partial), the "not mine" marks are written after the first barrier to rows that have no
 //            segment in any tile; the epilogue reads behind the barrier after the loop.
 //   tile_s / base_s  written once before the first barrier, read-only afterwards.
+// Global memory, the epilogue operands requested early (panel_epilogue_request): nothing is read before its writer.  A row's operands
+// are written by that row's own lane only, and only in apply(), behind the request in program order (sumy[i], the Halpern x'[j]: read,
+// then written by the same lane); y / lo / hi / x / xn / aty and the anchors are read-only in these kernels; the next-iterate buffers
+// are only stored to.  A row with a workgroup of its own is written by that workgroup: its slot here is requested and never used.
 template <class Epi>
 __device__ __forceinline__ void panel_spmv_block(const PanelView& P, const double* __restrict__ vec,
                                                  Epi& epi, double* __restrict__ partials)
@@ -235,6 +376,9 @@ __device__ __forceinline__ void panel_spmv_block(const PanelView& P, const doubl
   PanelChunk nxt = advance(none);
   PANEL_REQUEST(nxt)
   PanelChunk cur = nxt;
+  constexpr bool kEarly = PanelEarlyOps<Epi>::on;
+  [[maybe_unused]] typename PanelEarlyOps<Epi>::type pre[kPanelEpiDepth];
+  [[maybe_unused]] int lo_last = 0, hi_last = 0;
   while (cur.valid) {
     __syncthreads();  // the previous chunk's row sums are done with prod
     PANEL_DISPATCH(PANEL_ROUNDS(cur), PANEL_CALL_PRODUCTS)
@@ -242,76 +386,32 @@ __device__ __forceinline__ void panel_spmv_block(const PanelView& P, const doubl
     for (int q = 0; q < kPanelRowsPer; ++q) ext[q] = ext_next[q];
     const int lo = cur.c0 - cur.t0, hi = cur.c1 - cur.t0;
     nxt = advance(cur);
+    if constexpr (kEarly)
+      if (!nxt.valid) {  // the final chunk leaves the loop here: what it requests instead of a chunk is live only below the loop
+        lo_last = lo, hi_last = hi;
+        break;
+      }
     PANEL_REQUEST(nxt)  // in flight during the row sums below
     __syncthreads();
-    if (!P.any_long) {  // (uniform) the common case: no extra instruction in the loop
-#pragma unroll
-      for (int q = 0; q < kPanelRowsPer; ++q) {
-        const int r = threadIdx.x + q * kPanelThreads;
-        if (r < nr) {
-          int a = (int)(ext[q] & 0xFFFFu), b = (int)(ext[q] >> 16);
-          a = a > lo ? a : lo;
-          b = b < hi ? b : hi;
-          if (a < b) {
-            double sum = psum[r];
-            for (int k = a; k < b; ++k) sum = sum + prod[k - lo];
-            psum[r] = sum;
-          }
-        }
-      }
-      cur = nxt;
-      continue;
-    }
-    bool any_long = false;
-#pragma unroll
-    for (int q = 0; q < kPanelRowsPer; ++q) {
-      const int r = threadIdx.x + q * kPanelThreads;
-      if (r < nr) {
-        int a = (int)(ext[q] & 0xFFFFu), b = (int)(ext[q] >> 16);
-        a = a > lo ? a : lo;
-        b = b < hi ? b : hi;
-        if (b - a > kLongRow) {
-          any_long = true;  // handled below, by the whole wave
-        } else if (a < b) {  // left to right by the row's lane: bit-identical to a sequential CSR sum
-          double sum = psum[r];
-          for (int k = a; k < b; ++k) sum = sum + prod[k - lo];
-          psum[r] = sum;
-        }
-      }
-    }
-    // A segment longer than kLongRow would keep ONE lane busy for thousands of dependent LDS reads: its wave sums it
-    // together instead (64 strided chains + the fixed butterfly; compared with a tolerance like every long row).
-    // One ballot per chunk on the common path.
-    if (__ballot(any_long)) {
-#pragma unroll
-      for (int q = 0; q < kPanelRowsPer; ++q) {
-        const int r = threadIdx.x + q * kPanelThreads;
-        int a = 0, b = 0;
-        if (r < nr) {
-          a = (int)(ext[q] & 0xFFFFu), b = (int)(ext[q] >> 16);
-          a = a > lo ? a : lo;
-          b = b < hi ? b : hi;
-        }
-        unsigned long long todo = __ballot(b - a > kLongRow);
-        while (todo) {
-          const int l  = __builtin_ctzll(todo);
-          todo &= todo - 1;
-          const int la = __builtin_amdgcn_readlane(a, l), lb = __builtin_amdgcn_readlane(b, l);
-          double part  = 0.0;
-          for (int k = la + (int)(threadIdx.x & 63); k < lb; k += 64) part = part + prod[k - lo];
-          part = wave_reduce<SumOp>(part);
-          if ((int)(threadIdx.x & 63) == l) psum[r] = psum[r] + part;
-        }
-      }
-    }
+    panel_row_sums(P, ext, prod, psum, nr, lo, hi);
     cur = nxt;
   }
 #undef PANEL_REQUEST
 #undef PANEL_CALL_PRODUCTS
 #undef PANEL_CALL_LOAD
 #undef PANEL_ROUNDS
-  __syncthreads();
-  panel_epilogue(P, epi, partials, psum, red, w, r0, nr, &dseg);
+  if constexpr (kEarly) {
+    panel_epilogue_request(epi, pre, r0, nr);  // (a panel without a chunk requests here as well)
+    if (cur.valid) {  // the final chunk's row sums, the request in flight
+      __syncthreads();
+      panel_row_sums(P, ext, prod, psum, nr, lo_last, hi_last);
+    }
+    __syncthreads();
+    panel_epilogue_early(P, epi, partials, psum, red, w, r0, nr, &dseg, pre);
+  } else {
+    __syncthreads();
+    panel_epilogue(P, epi, partials, psum, red, w, r0, nr, &dseg);
+  }
 }
 // ------------------------------------------------------------------------------------------------
 // Long-tail variant of the panels: row sums dealt by NONZERO, not by row.
@@ -405,6 +505,42 @@ __device__ __forceinline__ void seg_rounds(const double* __restrict__ vec, int s
     }
   }
 }
+// wave 0, behind a chunk's barrier: joins the chunk's edge-run records (R rounds) and emits the joined sums to psum2
+__device__ __forceinline__ void panel_seg_join(const SegRecord* rec /* the chunk's parity */, double* psum2, int R, int lane)
+{
+  // join the edge runs in logical order: lane l <-> wave-round (round l / 8, wave l % 8), two pieces each (the run from the
+  // left edge, the run to the right edge; one piece when a single run fills the wave-round)
+  const int u = lane >> 3, q = lane & 7;
+  const bool on = u < R;
+  SegRecord g{0.0, 0.0, 0, -1};
+  if (on) g = rec[q * kPanelPer + u];
+  const bool single = g.rkey < 0;
+  const int my_first = g.lkey, my_last = single ? g.lkey : g.rkey;
+  const double open  = on ? (single ? g.lsum : g.rsum) : 0.0;  // the run still open at this lane's right edge
+  int prev_last      = __builtin_amdgcn_update_dpp(0, my_last, 0x138, 0xf, 0xf, false);
+  if (lane == 0) prev_last = my_first;
+  const bool flag = on && (!single || my_first != prev_last);  // a run ends inside this lane's pieces or at its left edge
+  const unsigned long long fm = __ballot(flag);
+  const unsigned long long at_or_below = fm & ((2ull << lane) - 1ull);
+  const int seg0  = at_or_below ? 63 - __builtin_clzll(at_or_below) : 0;
+  const double S  = seg_scan(open, lane, seg0);
+  double carry_in = seg_dpp<0x138, 0xf>(S);
+  if (lane == 0) carry_in = 0.0;
+  if (on) {
+    int key    = prev_last;
+    double sum = carry_in;
+    if (my_first != key) {
+      seg_emit(psum2, key, sum);
+      key = my_first, sum = 0.0;
+    }
+    sum = sum + g.lsum;
+    if (!single) {
+      seg_emit(psum2, key, sum);
+      key = g.rkey, sum = g.rsum;
+    }
+    if (lane == R * kPanelWaves - 1) seg_emit(psum2, key, sum);  // the chunk's last wave-round closes what is still open
+  }
+}
 // LDS hazards of panel_seg_block (round-6 audit):
 //   rec[2][]  the edge-run records, double-buffered by chunk parity.  rec[p] is written by every wave during the rounds of chunk i
 //             (parity p), read by wave 0's join after the chunk's barrier B(i), and next written during the rounds of chunk i + 2,
@@ -414,6 +550,7 @@ __device__ __forceinline__ void seg_rounds(const double* __restrict__ vec, int s
 //             the order of a row's additions is fixed.
 //   psum2[]   emitted to by wave 0 alone (the joined edge runs), in program order.
 //   the epilogue reads psum + psum2 behind the barrier after the loop.
+// Global memory, the epilogue operands requested early: as in panel_spmv_block (nothing is read before its writer).
 template <class Epi>
 __device__ __forceinline__ void panel_seg_block(const PanelView& P, const double* __restrict__ vec, Epi& epi, double* __restrict__ partials)
 {
@@ -466,54 +603,39 @@ __device__ __forceinline__ void panel_seg_block(const PanelView& P, const double
   if (nxt.valid) { PANEL_DISPATCH(SEG_ROUNDS(nxt), SEG_CALL_LOAD) }
   PanelChunk cur = nxt;
   int parity = 0;
+  constexpr bool kEarly = PanelEarlyOps<Epi>::on;
+  [[maybe_unused]] typename PanelEarlyOps<Epi>::type pre[kPanelEpiDepth];
+  [[maybe_unused]] int R_last = 0;
   while (cur.valid) {
     const int R = SEG_ROUNDS(cur);
     PANEL_DISPATCH(R, SEG_CALL_ROUNDS)   // gathers, products, the runs inside the wave-rounds, the edge records
     nxt = advance(cur);
+    if constexpr (kEarly)
+      if (!nxt.valid) {  // the final chunk leaves the loop here (see panel_spmv_block)
+        R_last = R;
+        break;
+      }
     if (nxt.valid) { PANEL_DISPATCH(SEG_ROUNDS(nxt), SEG_CALL_LOAD) }  // the next chunk's stream, in flight over the barrier and the join
     __syncthreads();  // the chunk's records are complete; every emission of the chunk before is done
-    if (wave == 0) {
-      // join the edge runs in logical order: lane l <-> wave-round (round l / 8, wave l % 8), two pieces each (the run from the
-      // left edge, the run to the right edge; one piece when a single run fills the wave-round)
-      const int u = lane >> 3, q = lane & 7;
-      const bool on = u < R;
-      SegRecord g{0.0, 0.0, 0, -1};
-      if (on) g = rec[parity][q * kPanelPer + u];
-      const bool single = g.rkey < 0;
-      const int my_first = g.lkey, my_last = single ? g.lkey : g.rkey;
-      const double open  = on ? (single ? g.lsum : g.rsum) : 0.0;  // the run still open at this lane's right edge
-      int prev_last      = __builtin_amdgcn_update_dpp(0, my_last, 0x138, 0xf, 0xf, false);
-      if (lane == 0) prev_last = my_first;
-      const bool flag = on && (!single || my_first != prev_last);  // a run ends inside this lane's pieces or at its left edge
-      const unsigned long long fm = __ballot(flag);
-      const unsigned long long at_or_below = fm & ((2ull << lane) - 1ull);
-      const int seg0  = at_or_below ? 63 - __builtin_clzll(at_or_below) : 0;
-      const double S  = seg_scan(open, lane, seg0);
-      double carry_in = seg_dpp<0x138, 0xf>(S);
-      if (lane == 0) carry_in = 0.0;
-      if (on) {
-        int key    = prev_last;
-        double sum = carry_in;
-        if (my_first != key) {
-          seg_emit(psum2, key, sum);
-          key = my_first, sum = 0.0;
-        }
-        sum = sum + g.lsum;
-        if (!single) {
-          seg_emit(psum2, key, sum);
-          key = g.rkey, sum = g.rsum;
-        }
-        if (lane == R * kPanelWaves - 1) seg_emit(psum2, key, sum);  // the chunk's last wave-round closes what is still open
-      }
-    }
+    if (wave == 0) panel_seg_join(rec[parity], psum2, R, lane);
     parity ^= 1;
     cur = nxt;
   }
 #undef SEG_CALL_ROUNDS
 #undef SEG_CALL_LOAD
 #undef SEG_ROUNDS
-  __syncthreads();
-  panel_epilogue(P, epi, partials, psum, red, w, r0, nr, &dseg, psum2);
+  if constexpr (kEarly) {
+    panel_epilogue_request(epi, pre, r0, nr);
+    if (cur.valid) {  // the final chunk's barrier and join, the request in flight
+      __syncthreads();
+      if (wave == 0) panel_seg_join(rec[parity], psum2, R_last, lane);
+    }
+    __syncthreads();
+    panel_epilogue_early(P, epi, partials, psum, red, w, r0, nr, &dseg, pre, psum2);
+  } else {
+    __syncthreads();
+    panel_epilogue(P, epi, partials, psum, red, w, r0, nr, &dseg, psum2);
+  }
 }
 #undef PANEL_DISPATCH
 template <bool SEG, class Epi>
