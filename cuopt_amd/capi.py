@@ -111,7 +111,7 @@ class SolverSettings(C.Structure):
                 ("log_to_console", c_int), ("log_file", c_char_p), ("unbounded_from_feasible_iterates", c_int),
                 ("accept_enabled", c_int), ("accept_tolerance", c_double * 6),
                 ("relative_primal_tolerance_factor", c_double), ("relative_dual_tolerance_factor", c_double),
-                ("batch_lanes", c_int), ("halpern_resident", c_int)]
+                ("batch_lanes", c_int), ("halpern_resident", c_int), ("halpern_batch", c_int)]
 
 
 class Result(C.Structure):
@@ -326,6 +326,8 @@ _proto("cuoptamd_batch_get_solutions", c_int, c_void_p, c_void_p, c_void_p, c_vo
 _proto("cuoptamd_batch_branch", c_int, c_void_p, c_void_p, c_void_p, c_void_p)
 _proto("cuoptamd_batch_solution_views", c_int, c_void_p, c_void_p, c_void_p, c_void_p)
 _proto("cuoptamd_batch_device", c_void_p, c_void_p)
+_proto("cuoptamd_batch_stats", c_int, c_void_p, c_void_p)
+_proto("cuoptamd_batch_solve_last_path", C.c_char_p)
 _proto("pdlpdev_small_batch_create", c_int, P(c_void_p), P(c_void_p), c_int)  # (the device layer's K-workgroup batch of resident LPs)
 _proto("pdlpdev_small_batch_destroy", None, c_void_p)
 _proto("pdlpdev_create_share_stream", None, c_void_p)
@@ -877,6 +879,15 @@ class SharedMatrixBatch:
             raise CuOptError(rc, lib.cuoptamd_last_error().decode())
         return list(zip(xs, ys, zs))
 
+    def stats(self):
+        """cuoptamd_batch_stats of a small-LP batch: dict halpern / tiers (resident tiers in use) and, counted for a batch in reflected
+        Halpern mode, loop_launches / eval_launches (behind the loop) / periods (runs) / restart_rounds / resets / syncs"""
+        out = np.zeros(8, np.int64)
+        rc = lib.cuoptamd_batch_stats(self.handle, _ptr(out))
+        if rc != 0:
+            raise CuOptError(rc, lib.cuoptamd_last_error().decode())
+        return dict(zip(("halpern", "tiers", "loop_launches", "eval_launches", "periods", "restart_rounds", "resets", "syncs"), out.tolist()))
+
     def time_kernels(self, reps=20):
         """average dispatch time (ms) of the four kernels of a batched attempt: dict primal / a_dual / at_step / decisions"""
         out = np.zeros(4)
@@ -901,7 +912,8 @@ SmallBatch = SharedMatrixBatch  # (the same cuoptamd_batch object; the name the 
 
 
 def batch_solve(problems, mode=1, max_threads=0, device=0, **setting_overrides):
-    """cuoptamd_batch_solve: independent LPs solved concurrently on one GPU -> list of result dicts"""
+    """cuoptamd_batch_solve: independent LPs solved concurrently on one GPU -> list of result dicts (batch_solve_last_path() says
+    which way the call took: mode=4 with halpern_resident=1, halpern_batch=1 puts LPs of resident size into K workgroups of one launch)"""
     k = len(problems)
     lps, keep = (LP * k)(), []
     for i, p in enumerate(problems):
@@ -927,6 +939,11 @@ def batch_solve(problems, mode=1, max_threads=0, device=0, **setting_overrides):
         d.update(x=xs[i], y=ys[i], reduced_cost=zs[i])
         out.append(d)
     return out
+
+
+def batch_solve_last_path():
+    """cuoptamd_batch_solve_last_path: "small", "small_halpern", "shared_matrix" or "independent" ("" before the first batch_solve of this thread)"""
+    return lib.cuoptamd_batch_solve_last_path().decode()
 
 
 def csr_transpose(m, n, offsets, indices, values):

@@ -481,6 +481,15 @@ struct pdlpdev_small_batch {
   SmallSolutionArgs* sol = nullptr;
   double* staging = nullptr;  // 3 n + m doubles per LP (new bounds + initial iterate in, solutions out), LP l at stage_off[l]
   std::vector<size_t> stage_off;
+  // A batch of LPs in reflected Halpern mode (pdlpdev_small_batch_create_halpern): the loop, its evaluation and the restart are
+  // kernels_resident_halpern.hip's, their records sit in the same pinned block; blk holds 2 * at_blocks_cap entries (a reset
+  // enqueues A^T y of the starting point AND the restart that sets the anchor before its one synchronisation).
+  bool halpern = false;
+  HalpernResidentArgs* hrun = nullptr;
+  HalpernRestartArgs* hrestart = nullptr;
+  // (Halpern batches) launches of the loop kernel / of the evaluation behind it, calls of pdlpdev_small_batch_run, restart rounds,
+  // resets, and the synchronisations: one per run, restart round, reset and separate pdlpdev_small_batch_major_eval
+  int64_t stat_loop_launches = 0, stat_eval_launches = 0, stat_periods = 0, stat_restart_rounds = 0, stat_resets = 0, stat_syncs = 0;
 };
 
 template <int T, int Q, int U>
@@ -496,25 +505,28 @@ static int launch_resident_batch(pdlpdev_small_batch* b, int tier, const int* li
   return 0;
 }
 
-extern "C" {
-
-int pdlpdev_small_batch_create(pdlpdev_small_batch** out, pdlpdev_ctx** ctx, int K)
+// pdlpdev_small_batch_create (halpern == false: the averaging iteration's batch) / pdlpdev_small_batch_create_halpern
+static int small_batch_create(pdlpdev_small_batch** out, pdlpdev_ctx** ctx, int K, bool halpern)
 {
-  if (!out || !ctx || K < 1) return fail(-1, "pdlpdev_small_batch_create: null argument");
+  const char* const who = halpern ? "pdlpdev_small_batch_create_halpern" : "pdlpdev_small_batch_create";
+  if (!out || !ctx || K < 1) return fail(-1, "%s: null argument", who);
   *out = nullptr;
   for (int l = 0; l < K; ++l) {
     const pdlpdev_ctx* c = ctx[l];
-    if (!c) return fail(-1, "pdlpdev_small_batch_create: null context");
+    if (!c) return fail(-1, "%s: null context", who);
     if (!c->small_resident || c->comm || c->At.layout() != pdlpdev_ctx::MatrixSide::kStream || c->dense.on)
-      return fail(-7, "pdlpdev_small_batch_create: LP %d is not on the resident small-LP path", l);
-    if (c->halpern)  // (the batch's loop, evaluation and restart are the averaging iteration's)
+      return fail(-7, "%s: LP %d is not on the resident small-LP path", who, l);
+    if (c->halpern && !halpern)  // (the batch's loop, evaluation and restart are the averaging iteration's)
       return fail(-7, "pdlpdev_small_batch_create: LP %d is in reflected Halpern mode, which has no K-workgroup batch (solve them one after the other)", l);
-    if (c->device != ctx[0]->device) return fail(-7, "pdlpdev_small_batch_create: the LPs sit on different devices");
+    if (halpern && c->halpern != ctx[0]->halpern)
+      return fail(-7, "%s: LP 0 and LP %d differ: a batch of averaging and reflected Halpern members is not available", who, l);
+    if (halpern && !c->halpern) return fail(-7, "%s: LP %d is not in reflected Halpern mode", who, l);
+    if (c->device != ctx[0]->device) return fail(-7, "%s: the LPs sit on different devices", who);
     for (int q = 0; q < l; ++q)
-      if (ctx[q] == c) return fail(-1, "pdlpdev_small_batch_create: LP %d and LP %d are the same context", q, l);
+      if (ctx[q] == c) return fail(-1, "%s: LP %d and LP %d are the same context", who, q, l);
   }
   std::unique_ptr<pdlpdev_small_batch> b(new pdlpdev_small_batch());
-  b->device = ctx[0]->device, b->K = K;
+  b->device = ctx[0]->device, b->K = K, b->halpern = halpern;
   b->ctx.assign(ctx, ctx + K);
   HIP_TRY(hipSetDevice(b->device));
   int blocks = 0;
@@ -527,9 +539,10 @@ int pdlpdev_small_batch_create(pdlpdev_small_batch** out, pdlpdev_ctx** ctx, int
   auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
   const size_t o_run = 0, o_list3 = o_run + up(sizeof(ResidentArgs) * K), o_major = o_list3 + up(sizeof(int) * 3 * K),
                o_list = o_major + up(sizeof(MajorSmallArgs) * K), o_restart = o_list + up(sizeof(int) * K),
-               o_blk = o_restart + up(sizeof(RestartBatchArgs) * K), o_at = o_blk + up(sizeof(int2) * (size_t)blocks),
+               o_blk = o_restart + up(sizeof(RestartBatchArgs) * K), o_at = o_blk + up(sizeof(int2) * (size_t)blocks * (halpern ? 2 : 1)),
                o_ops = o_at + up(sizeof(StreamAtCurArgs) * K), o_reset = o_ops + up(sizeof(CtlOp) * K), o_sol = o_reset + up(sizeof(SmallResetArgs) * K),
-               o_stage = o_sol + up(sizeof(SmallSolutionArgs) * K);
+               o_hrun = o_sol + up(sizeof(SmallSolutionArgs) * K), o_hrestart = o_hrun + (halpern ? up(sizeof(HalpernResidentArgs) * K) : 0),
+               o_stage = o_hrestart + (halpern ? up(sizeof(HalpernRestartArgs) * K) : 0);
   size_t total = o_stage;
   for (int l = 0; l < K; ++l) {
     b->stage_off.push_back((total - o_stage) / sizeof(double));
@@ -541,11 +554,153 @@ int pdlpdev_small_batch_create(pdlpdev_small_batch** out, pdlpdev_ctx** ctx, int
   b->list = (int*)(base + o_list), b->restart = (RestartBatchArgs*)(base + o_restart), b->blk = (int2*)(base + o_blk);
   b->at = (StreamAtCurArgs*)(base + o_at), b->ops = (CtlOp*)(base + o_ops);
   b->reset = (SmallResetArgs*)(base + o_reset), b->sol = (SmallSolutionArgs*)(base + o_sol), b->staging = (double*)(base + o_stage);
+  if (halpern) b->hrun = (HalpernResidentArgs*)(base + o_hrun), b->hrestart = (HalpernRestartArgs*)(base + o_hrestart);
   HIP_TRY(hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
   TRY(major_lds_attribute(b->device));
   for (int l = 0; l < K; ++l) HIP_TRY(hipStreamSynchronize(ctx[l]->stream));  // whatever the set-ups left in flight
   for (int l = 0; l < K; ++l) ctx[l]->batches_alive += 1;
   *out = b.release();
+  return 0;
+}
+
+// ---- a batch of LPs in reflected Halpern mode: the branches of pdlpdev_small_batch_run / _major_eval / _reset and the batched restart ----
+// pdlpdev_small_batch_run: per tier in use ONE launch of k_pdhg_resident_halpern_batch, behind them ONE launch of the guarded evaluation
+// of T(z^k) (k_major_small_halpern_batch) for the LPs whose steps end in a major iteration, ONE synchronisation.  evaluated[l] as
+// resident_halpern_period says it for one LP: the target reached, no step error, the evaluation ran.
+static int halpern_batch_run(pdlpdev_small_batch* b, const int32_t* targets, pdlpdev_ctl* ctl, const pdlpdev_small_eval* eval_after, double* out_current,
+                             double* out_average, int32_t* evaluated)
+{
+  const int K = b->K;
+  std::vector<char> todo(K, 0);
+  for (int l = 0; l < K; ++l) {
+    if (evaluated) evaluated[l] = 0;
+    if (targets[l] > 0) {
+      pdlpdev_ctx* c = b->ctx[l];
+      b->hrun[l]     = HalpernResidentArgs{halpern_view(c), c->ctl, c->ctl_h, c->hal, c->hal_h, targets[l], 0};
+      todo[l]        = 1;
+      loop_state_touched(c);
+    }
+  }
+  b->stat_periods += 1;
+  for (int guard = 0; guard < 1000; ++guard) {
+    int count[3] = {0, 0, 0};
+    for (int l = 0; l < K; ++l)
+      if (todo[l]) b->run_list[b->tier[l] * K + count[b->tier[l]]++] = l;
+    if (count[0] + count[1] + count[2] == 0) break;
+    for (int tier = 0; tier < 3; ++tier)
+      if (count[tier]) {
+        TRY(halpern_batch_launch_loop(b->stream, b->device, tier, b->hrun, b->run_list + tier * K, count[tier]));
+        b->stat_loop_launches += 1;
+      }
+    int nev = 0;
+    if (guard == 0 && eval_after) {
+      for (int l = 0; l < K; ++l)
+        if (todo[l] && eval_after[l].mode >= 0) {
+          const int want_linf = eval_after[l].eps_p >= 0.0 && eval_after[l].eps_d >= 0.0;
+          b->major[l] = major_args(b->ctx[l], 3, eval_after[l].rule_finite, want_linf, eval_after[l].eps_p, eval_after[l].eps_d);
+          b->major[l].guard_target = targets[l];
+          b->list[nev++]           = l;
+        }
+      if (nev) {
+        TRY(halpern_batch_launch_eval(b->stream, b->device, b->major_lds, b->major, b->list, nev));
+        b->stat_eval_launches += 1;
+      }
+    }
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    b->stat_syncs += 1;
+    for (int q = 0; q < nev; ++q) {
+      const int l           = b->list[q];
+      const pdlpdev_ctx* c = b->ctx[l];
+      if (c->ctl_h->error != 0 || c->ctl_h->steps_taken < targets[l] || c->scal_h[63] != 1.0) continue;
+      const bool want_linf = eval_after[l].eps_p >= 0.0 && eval_after[l].eps_d >= 0.0;
+      read_eval(c->scal_h + 32, want_linf, out_current + (size_t)l * PDLPDEV_EV_COUNT);
+      read_eval(c->scal_h + 32, want_linf, out_average + (size_t)l * PDLPDEV_EV_COUNT);
+      if (evaluated) evaluated[l] = 1;
+    }
+    for (int l = 0; l < K; ++l)
+      if (todo[l] && (b->ctx[l]->ctl_h->error != 0 || b->ctx[l]->ctl_h->steps_taken >= targets[l])) todo[l] = 0;
+  }
+  for (int l = 0; l < K; ++l)
+    if (targets[l] > 0) {
+      b->ctx[l]->ctl_h_current = true;  // (as resident_halpern_run leaves it: the kernel wrote the pinned mirror)
+      if (ctl) ctl[l] = *b->ctx[l]->ctl_h;
+    }
+  return 0;
+}
+// the restart of the LPs in b->list[0 .. count) (theta[l] < 0: the anchor and the counters only; clear: k_halpern_clear's values first),
+// enqueued only: k_restart_batch with the current iterate as the candidate and scaled distances, blocks from b->blk + blk_first, then the
+// finishing kernel.  The caller synchronises.
+static int halpern_batch_enqueue_restart(pdlpdev_small_batch* b, int count, const double* theta, int clear, int blk_first)
+{
+  int blocks = blk_first;
+  for (int q = 0; q < count; ++q) {
+    const int l    = b->list[q];
+    pdlpdev_ctx* c = b->ctx[l];
+    const int g    = std::min(grid_for(std::max(c->n, c->m)), kGenericBlocks);
+    b->restart[l]  = RestartBatchArgs{RestartView{c->n, c->m, PDLPDEV_CURRENT, 0, c->dc, c->dr, c->ctl, c->x[0], c->x[1], c->y[0], c->y[1], c->avgx, c->avgy, c->lrx,
+                                                 c->lry, c->sumx, c->sumy, c->part_g},
+                                     g, 0, c->scal_h};
+    b->hrestart[l] = HalpernRestartArgs{c->n, g, clear, 0, theta[l], c->part_g, c->aty[0], c->aty[1], c->lraty, c->scal, c->scal_h, c->ctl, c->ctl_h, c->hal, c->hal_h};
+    for (int i = 0; i < g; ++i) b->blk[blocks++] = make_int2(l, i);
+  }
+  k_restart_batch<<<blocks - blk_first, kBlock, 0, b->stream>>>(b->restart, b->blk + blk_first);
+  HIP_TRY(hipGetLastError());
+  return halpern_batch_launch_restart_finish(b->stream, b->hrestart, b->list, count);
+}
+// pdlpdev_small_batch_reset's tail for a Halpern batch (the LPs of b->list, behind k_small_reset_batch): what pdlpdev_reset and the
+// solver's start of a run do in this mode -- the Halpern block cleared, A^T y of the starting point, the restart that only sets the anchor
+static int halpern_batch_reset_tail(pdlpdev_small_batch* b, int count)
+{
+  int blocks = 0;
+  std::vector<double> theta(b->K, -1.0);
+  for (int q = 0; q < count; ++q) {
+    pdlpdev_ctx* c   = b->ctx[b->list[q]];
+    b->at[b->list[q]] = StreamAtCurArgs{c->At.nb, c->At.rb, c->At.hot.off, c->At.hot.idx, c->At.hot.val, c->ctl, c->y[0], c->y[1], c->aty[0], c->aty[1]};
+    for (int i = 0; i < c->At.nb; ++i) b->blk[blocks++] = make_int2(b->list[q], i);
+    loop_state_touched(c);
+  }
+  TRY(launch_stream_at_cur_batch(b->stream, b->at, b->blk, blocks));
+  return halpern_batch_enqueue_restart(b, count, theta.data(), 1, b->at_blocks_cap);
+}
+
+extern "C" {
+
+int pdlpdev_small_batch_create(pdlpdev_small_batch** out, pdlpdev_ctx** ctx, int K) { return small_batch_create(out, ctx, K, false); }
+int pdlpdev_small_batch_create_halpern(pdlpdev_small_batch** out, pdlpdev_ctx** ctx, int K) { return small_batch_create(out, ctx, K, true); }
+
+int pdlpdev_small_batch_halpern_restart(pdlpdev_small_batch* b, const int32_t* restart, const double* theta, double* dist, pdlpdev_ctl* ctl, pdlpdev_halpern* hal)
+{
+  if (!b || !b->halpern) return fail(-1, "pdlpdev_small_batch_halpern_restart: not a batch of LPs in reflected Halpern mode");
+  HIP_TRY(hipSetDevice(b->device));
+  int count = 0;
+  for (int l = 0; l < b->K; ++l)
+    if (restart[l]) b->list[count++] = l;
+  if (!count) return 0;
+  TRY(halpern_batch_enqueue_restart(b, count, theta, 0, 0));
+  HIP_TRY(hipStreamSynchronize(b->stream));
+  b->stat_restart_rounds += 1, b->stat_syncs += 1;
+  for (int l = 0; l < b->K; ++l)
+    if (restart[l]) {
+      const pdlpdev_ctx* c = b->ctx[l];
+      if (dist) dist[2 * l] = c->scal_h[0], dist[2 * l + 1] = c->scal_h[1];
+      if (ctl) ctl[l] = *c->ctl_h;
+      if (hal) hal[l] = *c->hal_h;
+    }
+  return 0;
+}
+int pdlpdev_small_batch_get_halpern(pdlpdev_small_batch* b, pdlpdev_halpern* hal)
+{
+  if (!b || !b->halpern) return fail(-1, "pdlpdev_small_batch_get_halpern: not a batch of LPs in reflected Halpern mode");
+  for (int l = 0; l < b->K; ++l) hal[l] = *b->ctx[l]->hal_h;
+  return 0;
+}
+int pdlpdev_small_batch_stats(pdlpdev_small_batch* b, int64_t out[8])
+{
+  if (!b) return fail(-1, "pdlpdev_small_batch_stats: null batch");
+  int tiers = 0;
+  for (int t = 0; t < 3; ++t) tiers += std::count(b->tier.begin(), b->tier.end(), t) > 0;
+  out[0] = b->halpern, out[1] = tiers, out[2] = b->stat_loop_launches, out[3] = b->stat_eval_launches, out[4] = b->stat_periods;
+  out[5] = b->stat_restart_rounds, out[6] = b->stat_resets, out[7] = b->stat_syncs;
   return 0;
 }
 
@@ -568,6 +723,7 @@ int pdlpdev_small_batch_run(pdlpdev_small_batch* b, const int32_t* targets, pdlp
 {
   roctx::Range range("pdlp: PDHG attempts (small-LP batch)");
   HIP_TRY(hipSetDevice(b->device));
+  if (b->halpern) return halpern_batch_run(b, targets, ctl, eval_after, out_current, out_average, evaluated);
   const int K = b->K;
   std::vector<char> todo(K, 0);
   for (int l = 0; l < K; ++l) {
@@ -631,13 +787,19 @@ int pdlpdev_small_batch_major_eval(pdlpdev_small_batch* b, const pdlpdev_small_e
       b->list[count++]    = l;
     }
   if (!count) return 0;
-  k_major_small_batch<<<count, kMajorThreads, b->major_lds, b->stream>>>(b->major, b->list);
+  if (b->halpern) {  // the evaluation of T(z^k) in the average slots (mode 3), whatever mode was asked for: both outputs receive it
+    for (int q = 0; q < count; ++q) b->major[b->list[q]].mode = 3;
+    TRY(halpern_batch_launch_eval(b->stream, b->device, b->major_lds, b->major, b->list, count));
+    b->stat_syncs += 1;
+  } else {
+    k_major_small_batch<<<count, kMajorThreads, b->major_lds, b->stream>>>(b->major, b->list);
+  }
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(b->stream));
   for (int l = 0; l < b->K; ++l)
     if (req[l].mode >= 0) {
       const bool want_linf = req[l].eps_p >= 0.0 && req[l].eps_d >= 0.0;
-      read_eval(b->ctx[l]->scal_h, want_linf, out_current + (size_t)l * PDLPDEV_EV_COUNT);
+      read_eval(b->ctx[l]->scal_h + (b->halpern ? 32 : 0), want_linf, out_current + (size_t)l * PDLPDEV_EV_COUNT);
       read_eval(b->ctx[l]->scal_h + 32, want_linf, out_average + (size_t)l * PDLPDEV_EV_COUNT);
     }
   return 0;
@@ -647,6 +809,7 @@ int pdlpdev_small_batch_major_eval(pdlpdev_small_batch* b, const pdlpdev_small_e
 int pdlpdev_small_batch_restart(pdlpdev_small_batch* b, const int32_t* which, const int32_t* unscaled_distances, double* dist2)
 {
   HIP_TRY(hipSetDevice(b->device));
+  if (b->halpern) return fail(-7, "pdlpdev_small_batch_restart: the averaging iteration's restart; a batch in reflected Halpern mode takes pdlpdev_small_batch_halpern_restart");
   int count = 0, blocks = 0;
   for (int l = 0; l < b->K; ++l)
     if (which[l] >= 0) {
@@ -731,6 +894,10 @@ int pdlpdev_small_batch_reset(pdlpdev_small_batch* b, const int32_t* take, const
   if (!count) return 0;
   k_small_reset_batch<<<count, 512, 0, b->stream>>>(b->reset, b->list);
   HIP_TRY(hipGetLastError());
+  if (b->halpern) {
+    TRY(halpern_batch_reset_tail(b, count));
+    b->stat_resets += 1, b->stat_syncs += 1;
+  }
   HIP_TRY(hipStreamSynchronize(b->stream));
   if (ctl)
     for (int l = 0; l < b->K; ++l)

@@ -6,14 +6,7 @@
 #include "pdlp_layouts.hpp"
 #include "resident_common.hpp"
 
-struct HalpernSmallView {
-  int m, n, nnz;
-  const int32_t *a_off, *a_idx, *at_off, *at_idx;
-  const double *a_val, *at_val, *c, *lb, *ub, *lo, *hi;
-  double *x0, *x1, *y0, *y1, *aty0, *aty1;
-  const double *ax, *ay, *aaty;  // the anchor z^0 and its A^T y (lrx, lry, lraty)
-  double *tx, *ty;               // T(z^k) of the last step of a run (the average slots)
-};
+// (HalpernSmallView, HalpernResidentArgs: resident_common.hpp -- the batch object in kernels_resident.hip holds the records)
 // resident_body's layout, lanes and barriers (B1 ... B5, B5 inside block_sum_fast) with the Halpern epilogues in the two row phases:
 //   * registers per owned element: x, x', A^T y, y, y' and the anchor x^0, y^0, A^T y^0 (loaded once; no running sums: no average);
 //   * LDS exactly as in resident_body (xbar_s, yn_s, the five constant vectors, prod): nothing is added;
@@ -189,6 +182,32 @@ k_pdhg_resident_halpern(HalpernSmallView V, pdlpdev_ctl* __restrict__ ctl, pdlpd
   extern __shared__ double lds[];
   resident_halpern_body<T, Q, U>(V, ctl, ctl_host, hal, hal_host, target_steps, max_steps, lds);
 }
+// p, which points to global memory, as a pointer the compiler knows that of (the empty statement keeps the two casts from cancelling
+// and names a scalar register: the value is uniform)
+template <class P>
+__device__ __forceinline__ P* as_global(P* p)
+{
+  __attribute__((address_space(1))) P* g = (__attribute__((address_space(1))) P*)p;
+  asm("" : "+s"(g));
+  return (P*)g;
+}
+// K LPs, one workgroup each, ONE launch: workgroup b runs the Halpern loop of LP list[b] exactly as k_pdhg_resident_halpern would -- the
+// same body, so every LP's iterates, scalars and counters are bit for bit those of its own launch (k_pdhg_resident_batch's arrangement).
+template <int T, int Q, int U>
+__global__ void __launch_bounds__(T) k_pdhg_resident_halpern_batch(const HalpernResidentArgs* __restrict__ args, const int* __restrict__ list, int max_steps)
+{
+  extern __shared__ double lds[];
+  const HalpernResidentArgs& A = args[list[blockIdx.x]];
+  // A pointer read from memory is a generic one to the compiler, a kernel argument is known to point to global memory.  as_global
+  // says so for the record's pointers: the two blocks are then read with scalar loads and the vectors with global ones, as in
+  // k_pdhg_resident_halpern (145 / 193 / 195 VGPRs; with generic pointers both blocks sit in vector registers: 168 / 219 / 223).
+  const HalpernSmallView& S = A.V;
+  const HalpernSmallView V{S.m, S.n, S.nnz, as_global(S.a_off), as_global(S.a_idx), as_global(S.at_off), as_global(S.at_idx), as_global(S.a_val),
+                           as_global(S.at_val), as_global(S.c), as_global(S.lb), as_global(S.ub), as_global(S.lo), as_global(S.hi), as_global(S.x0),
+                           as_global(S.x1), as_global(S.y0), as_global(S.y1), as_global(S.aty0), as_global(S.aty1), as_global(S.ax), as_global(S.ay),
+                           as_global(S.aaty), as_global(S.tx), as_global(S.ty)};
+  resident_halpern_body<T, Q, U>(V, as_global(A.ctl), as_global(A.ctl_host), as_global(A.hal), as_global(A.hal_host), A.target_steps, max_steps, lds);
+}
 
 // MajorSmallArgs::mode == 3, served by a kernel of its own: no average is formed and nothing is flushed; the average slots are
 // evaluated as the loop left them (T(z^k) of the period's last step), results in sc[32..41) as k_major_small leaves the average's.
@@ -198,9 +217,8 @@ k_pdhg_resident_halpern(HalpernSmallView V, pdlpdev_ctl* __restrict__ ctl, pdlpd
 // per-point helper called by both bodies (1206 lines of llvm-objdump -d of kernels_resident's gfx950 code object differ) -- and
 // the existing kernels are to keep the instructions they had.  guard_target as in
 // k_major_small_batch; sc[63] says whether the evaluation ran.
-__global__ void __launch_bounds__(kMajorThreads) k_major_small_halpern(MajorSmallArgs A)
+__device__ __forceinline__ void major_small_halpern_body(const MajorSmallArgs& A, double* prod /* nnz doubles of LDS */)
 {
-  extern __shared__ double prod[];
   __shared__ double red[4 * kMajorThreads / 64];
   const int t = threadIdx.x;
   if (A.guard_target >= 0 && !(A.ctl->error != 0 || A.ctl->steps_taken >= A.guard_target)) {  // (uniform)
@@ -240,8 +258,54 @@ __global__ void __launch_bounds__(kMajorThreads) k_major_small_halpern(MajorSmal
   }
   if (t == 0) A.sc[63] = 1.0;
 }
+__global__ void __launch_bounds__(kMajorThreads) k_major_small_halpern(MajorSmallArgs A)
+{
+  extern __shared__ double prod[];
+  major_small_halpern_body(A, prod);
+}
+// the same for the LPs of a batch: workgroup b evaluates LP list[b] (its own guard_target, its own sc[63])
+__global__ void __launch_bounds__(kMajorThreads) k_major_small_halpern_batch(const MajorSmallArgs* __restrict__ args, const int* __restrict__ list)
+{
+  extern __shared__ double prod[];
+  major_small_halpern_body(args[list[blockIdx.x]], prod);
+}
 
-static HalpernSmallView halpern_view(const pdlpdev_ctx* ctx)
+// Behind k_restart_batch (candidate = the current iterate, scaled distances) for the LPs of a Halpern batch: what pdlpdev_halpern_restart
+// enqueues behind k_restart for one LP -- k_finalize's two sums (finalize_rows: the same tree), k_copy_current of A^T y into the anchor's,
+// k_halpern_restart_ctl's arithmetic with this LP's theta -- in one workgroup per LP; both blocks go to their pinned mirrors and the two
+// distances to the LP's pinned scalars.  clear != 0 (a reset): k_halpern_clear's values first.
+__global__ void __launch_bounds__(kBlock) k_halpern_restart_finish_batch(const HalpernRestartArgs* __restrict__ args, const int* __restrict__ list)
+{
+  __shared__ double red[8];
+  const HalpernRestartArgs& A = args[list[blockIdx.x]];
+  const int cur = A.ctl->cur;  // (read by every thread in front of finalize_rows' barriers; thread 0 rewrites the block behind them)
+  finalize_rows(A.part, A.g, 2, 0u, A.dist2, red);
+  const double* __restrict__ v = cur ? A.aty1 : A.aty0;
+  for (int i = threadIdx.x; i < A.n; i += kBlock) A.lraty[i] = v[i];
+  if (threadIdx.x == 0) {
+    pdlpdev_ctl* ctl     = A.ctl;
+    pdlpdev_halpern* hal = A.hal;
+    if (A.clear) {  // k_halpern_clear
+      hal->r = hal->r_first = hal->r2 = 0.0;
+      hal->r2_min = __builtin_huge_val();
+      hal->k = 0, hal->reserved = 0;
+    }
+    const double dx = sqrt(A.dist2[0]), dy = sqrt(A.dist2[1]);  // k_halpern_restart_ctl
+    A.dist2[0] = dx, A.dist2[1] = dy;
+    A.dist_host[0] = dx, A.dist_host[1] = dy;
+    if (A.theta >= 0.0 && dx > 1.0e-10 && dy > 1.0e-10) {
+      const double w     = exp(A.theta * log(dy / dx) + (1.0 - A.theta) * log(ctl->primal_weight));
+      ctl->primal_weight = w;
+      ctl->tau           = ctl->step_size / w;
+      ctl->sigma         = ctl->step_size * w;
+    }
+    ctl->its_since_restart = 0;
+    hal->k                 = 0;
+    *A.ctl_host = *ctl, *A.hal_host = *hal;  // the pinned mirrors save the read-back copies
+  }
+}
+
+HalpernSmallView halpern_view(const pdlpdev_ctx* ctx)
 {
   return HalpernSmallView{ctx->m, ctx->n, (int)ctx->nnz, ctx->A.full.off, ctx->A.full.idx, ctx->At.full.off, ctx->At.full.idx, ctx->A.full.val, ctx->At.full.val,
                           ctx->c, ctx->lb, ctx->ub, ctx->lo, ctx->hi, ctx->x[0], ctx->x[1], ctx->y[0], ctx->y[1], ctx->aty[0],
@@ -322,4 +386,43 @@ int resident_halpern_period(pdlpdev_ctx* ctx, int32_t target_steps, int rc_rule_
   }
   if (ctx->ctl_h->error != 0) return 0;  // (the caller's major iteration evaluates the present way and reports the error)
   return resident_halpern_run(ctx, target_steps);  // a launch that hit its cap: the rest of the period, no evaluation
+}
+
+// ---- K LPs in K workgroups: the launches of a Halpern small-LP batch (the batch object and its host code: kernels_resident.hip) ----------
+template <int T, int Q, int U>
+static int launch_resident_halpern_batch(hipStream_t s, int device, int tier, const HalpernResidentArgs* args, const int* list, int count)
+{
+  static PerDeviceOnce once;  // per instantiation
+  TRY(once.run(device, [&]() -> int {
+    HIP_TRY(hipFuncSetAttribute((const void*)k_pdhg_resident_halpern_batch<T, Q, U>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)resident_lds_bytes(tier)));
+    return 0;
+  }));
+  k_pdhg_resident_halpern_batch<T, Q, U><<<count, T, resident_lds_bytes(tier), s>>>(args, list, 1 << 14);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+int halpern_batch_launch_loop(hipStream_t s, int device, int tier, const HalpernResidentArgs* args, const int* list, int count)
+{
+  if (tier == 0) return launch_resident_halpern_batch<256, 2, 8>(s, device, tier, args, list, count);
+  if (tier == 1) return launch_resident_halpern_batch<512, 2, 16>(s, device, tier, args, list, count);
+  if (tier == 2) return launch_resident_halpern_batch<512, 4, 8>(s, device, tier, args, list, count);
+  return fail(-1, "resident Halpern batch: no tier %d", tier);
+}
+int halpern_batch_launch_eval(hipStream_t s, int device, size_t lds, const MajorSmallArgs* args, const int* list, int count)
+{
+  static PerDeviceOnce once;
+  TRY(once.run(device, [&]() -> int {
+    HIP_TRY(hipFuncSetAttribute((const void*)k_major_small_halpern_batch, hipFuncAttributeMaxDynamicSharedMemorySize, 8192 * 8));
+    return 0;
+  }));
+  k_major_small_halpern_batch<<<count, kMajorThreads, lds, s>>>(args, list);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+int halpern_batch_launch_restart_finish(hipStream_t s, const HalpernRestartArgs* args, const int* list, int count)
+{
+  k_halpern_restart_finish_batch<<<count, kBlock, 0, s>>>(args, list);
+  HIP_TRY(hipGetLastError());
+  return 0;
 }

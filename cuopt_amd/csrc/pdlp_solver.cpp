@@ -664,21 +664,14 @@ const char* halpern_refused_setting(const cuoptamd_settings* st)
   return halpern_meaningless_setting(nullptr, st);
 }
 
-int halpern_major_iteration(cuoptamd_solver* s, bool* terminated)
+// The head: everything of the major iteration that needs no device call of its own once T(z^k) is evaluated (ev_t) -- the verdict, the
+// acceptance set, the limits, the three restart tests.  *restart: the caller restarts the iteration on the device
+// (pdlpdev_halpern_restart for one LP, pdlpdev_small_batch_halpern_restart for the LPs of a batch) and calls halpern_restart_done.
+int halpern_major_head(cuoptamd_solver* s, const double* ev_t, bool* terminated, bool* restart_out)
 {
-  HostRange range("pdlp: major iteration (Halpern: termination + restart logic)");
-  pdlpdev_ctx* dev        = s->dev;
   const cuoptamd_hyper& H = s->H;
   *terminated             = false;
-  const pdlpdev_small_eval rq = major_eval_request(s);
-  double ev[PDLPDEV_EV_COUNT], ev_t[PDLPDEV_EV_COUNT];
-  const pdlpdev_small_eval& fq = s->fused_rq;
-  if (s->fused_eval_ready && fq.rule_finite == rq.rule_finite && fq.eps_p == rq.eps_p && fq.eps_d == rq.eps_d) {
-    std::copy(s->fused_ev_avg, s->fused_ev_avg + PDLPDEV_EV_COUNT, ev_t);
-  } else {
-    DEV(pdlpdev_major_eval(dev, 0, rq.rule_finite, rq.eps_p, rq.eps_d, ev, ev_t));
-  }
-  s->fused_eval_ready = false;
+  *restart_out            = false;
   s->result.num_major_iterations += 1;
   s->conv_average = to_convergence(s, ev_t);
   s->conv_current = s->conv_average;
@@ -715,13 +708,36 @@ int halpern_major_iteration(cuoptamd_solver* s, bool* terminated)
   else if (r <= H.necessary_reduction_for_restart * r_first && s->halpern_r_prev >= 0.0 && r > s->halpern_r_prev) restart = true;
   else if ((double)s->hal.k >= H.artificial_restart_threshold * (double)s->total_iterations) restart = true;
   s->halpern_r_prev = r;
-  if (restart) {
-    double dist[2];
-    DEV(pdlpdev_halpern_restart(dev, H.primal_weight_update_smoothing, dist, &s->ctl));
-    DEV(pdlpdev_get_halpern(dev, &s->hal));
-    s->result.num_restarts += 1;
-    s->halpern_r_prev = -1.0;
+  *restart_out      = restart;
+  return 0;
+}
+// behind the device's restart (s->ctl and s->hal hold what it left)
+void halpern_restart_done(cuoptamd_solver* s)
+{
+  s->result.num_restarts += 1;
+  s->halpern_r_prev = -1.0;
+}
+int halpern_major_iteration(cuoptamd_solver* s, bool* terminated)
+{
+  HostRange range("pdlp: major iteration (Halpern: termination + restart logic)");
+  pdlpdev_ctx* dev = s->dev;
+  *terminated      = false;
+  const pdlpdev_small_eval rq = major_eval_request(s);
+  double ev[PDLPDEV_EV_COUNT], ev_t[PDLPDEV_EV_COUNT];
+  const pdlpdev_small_eval& fq = s->fused_rq;
+  if (s->fused_eval_ready && fq.rule_finite == rq.rule_finite && fq.eps_p == rq.eps_p && fq.eps_d == rq.eps_d) {
+    std::copy(s->fused_ev_avg, s->fused_ev_avg + PDLPDEV_EV_COUNT, ev_t);
+  } else {
+    DEV(pdlpdev_major_eval(dev, 0, rq.rule_finite, rq.eps_p, rq.eps_d, ev, ev_t));
   }
+  s->fused_eval_ready = false;
+  bool restart = false;
+  int rc       = halpern_major_head(s, ev_t, terminated, &restart);
+  if (rc != 0 || *terminated || !restart) return rc;
+  double dist[2];
+  DEV(pdlpdev_halpern_restart(dev, s->H.primal_weight_update_smoothing, dist, &s->ctl));
+  DEV(pdlpdev_get_halpern(dev, &s->hal));
+  halpern_restart_done(s);
   return 0;
 }
 
@@ -821,6 +837,7 @@ void cuoptamd_default_settings(cuoptamd_settings* s)
   s->relative_primal_tolerance_factor = s->relative_dual_tolerance_factor = -1.0;
   s->batch_lanes                      = 0;
   s->halpern_resident                 = 0;
+  s->halpern_batch                    = 0;
 }
 
 // Plain parallel counting sort by column (small matrices, and the fallback of the blocked one below).  Thread t owns a
@@ -1525,6 +1542,7 @@ struct cuoptamd_batch {
   std::vector<cuoptamd_solver*> s;
   pdlpdev_batch* dev = nullptr;          // K <= 16 LPs over ONE matrix in lockstep (kernels_batch.hip), or ...
   pdlpdev_small_batch* small = nullptr;  // ... K resident small LPs, one workgroup each (kernels_resident.hip)
+  bool halpern = false;                  // (a small batch of solvers in reflected Halpern mode: pdlpdev_small_batch_create_halpern)
 };
 
 int cuoptamd_solver_clone(cuoptamd_solver* parent, const double* lb, const double* ub, const double* lo, const double* hi,
@@ -1558,10 +1576,31 @@ int cuoptamd_batch_create(cuoptamd_solver** solvers, int K, cuoptamd_batch** out
 {
   if (!solvers || !out || K < 1) return fail(-1, "cuoptamd_batch_create: null argument");
   std::vector<pdlpdev_ctx*> ctx(K);
+  int halpern = 0, opted = 0, first_halpern = -1;
   for (int l = 0; l < K; ++l) {
     if (!solvers[l] || !solvers[l]->dev) return fail(-1, "cuoptamd_batch_create: null solver");
-    if (halpern_mode(solvers[l])) return fail(-7, "cuoptamd_batch_create: LP %d runs the %s, which has no lockstep batch (solve them one after the other)", l, kHalpernName);
+    if (halpern_mode(solvers[l])) {
+      halpern += 1, opted += solvers[l]->S.halpern_batch != 0;
+      if (first_halpern < 0) first_halpern = l;
+    }
     ctx[l] = solvers[l]->dev;
+  }
+  if (halpern > 0) {
+    // Halpern solvers: K workgroups of the resident loop iff every member is one, resident, with cuoptamd_settings::halpern_batch set
+    if (halpern == K && opted == K) {
+      pdlpdev_small_batch* small = nullptr;
+      int rc                     = pdlpdev_small_batch_create_halpern(&small, ctx.data(), K);
+      if (rc != 0) return fail(rc, "cuoptamd_batch_create: %s: %s", kHalpernName, pdlpdev_last_error());
+      cuoptamd_batch* b = new cuoptamd_batch();
+      b->K = K, b->small = small, b->halpern = true;
+      b->s.assign(solvers, solvers + K);
+      *out = b;
+      return 0;
+    }
+    if (halpern < K && opted > 0)
+      return fail(-7, "cuoptamd_batch_create: LP %d runs the %s and others the averaging iteration: a batch of both is not available", first_halpern, kHalpernName);
+    return fail(-7, "cuoptamd_batch_create: LP %d runs the %s, which has no lockstep batch (solve them one after the other, or create every "
+                    "member on the resident path with halpern_batch set: K LPs in K workgroups)", first_halpern, kHalpernName);
   }
   // small LPs first: any number of them, any matrices, a workgroup each
   pdlpdev_small_batch* small = nullptr;
@@ -1681,6 +1720,95 @@ static int small_batch_advance(cuoptamd_batch* b, const std::vector<int32_t>& bu
   }
 }
 
+// The same for K resident LPs in reflected Halpern mode (cuoptamd_settings::halpern_batch).  A round: the evaluation of T(z^k) for the
+// major iterations that are due -- one launch, unless it ran behind the steps with the same request --, the heads per LP on the host,
+// ONE batched restart for the LPs that restart, the targets, ONE pdlpdev_small_batch_run with the evaluation enqueued behind the steps.
+// A period of the whole batch is a launch per resident tier in use, one evaluation launch and one synchronisation; each LP goes through
+// exactly the sequence cuoptamd_solver_advance takes it through (halpern_major_iteration, pdlpdev_run_period).
+static int halpern_small_batch_advance(cuoptamd_batch* b, const std::vector<int32_t>& budget_end, std::vector<char>& done)
+{
+  const int K = b->K;
+  std::vector<pdlpdev_small_eval> req(K), ahead(K);
+  std::vector<double> ev((size_t)K * PDLPDEV_EV_COUNT), ev_t((size_t)K * PDLPDEV_EV_COUNT), theta(K);
+  std::vector<int32_t> restart(K), target(K), clear(K), aty(K), evaluated(K, 0);
+  std::vector<char> due(K);
+  std::vector<pdlpdev_ctl> ctl(K);
+  std::vector<pdlpdev_halpern> hal(K);
+  auto same_request = [](const pdlpdev_small_eval& a, const pdlpdev_small_eval& c) {  // (the mode plays no part: T(z^k) is what is evaluated)
+    return a.rule_finite == c.rule_finite && a.eps_p == c.eps_p && a.eps_d == c.eps_d;
+  };
+  for (;;) {
+    bool any = false, launch = false;
+    for (int l = 0; l < K; ++l) {
+      req[l].mode = -1, due[l] = 0;
+      if (done[l] || !major_due(b->s[l])) continue;
+      due[l] = 1, any = true;
+      const pdlpdev_small_eval rq = major_eval_request(b->s[l]);
+      if (evaluated[l] && same_request(rq, ahead[l])) continue;  // ev_t of LP l is in place
+      req[l] = rq, req[l].mode = 0, launch = true;
+    }
+    std::fill(evaluated.begin(), evaluated.end(), 0);
+    if (any) {
+      HostRange range("pdlp: major iterations of a small-LP batch (Halpern)");
+      int rc = launch ? pdlpdev_small_batch_major_eval(b->small, req.data(), ev.data(), ev_t.data()) : 0;
+      if (rc != 0) return fail(rc, "pdlpdev_small_batch_major_eval: %s", pdlpdev_last_error());
+      bool any_restart = false;
+      for (int l = 0; l < K; ++l) {
+        restart[l] = 0, theta[l] = -1.0;
+        if (!due[l]) continue;
+        bool terminated = false, again = false;
+        rc = halpern_major_head(b->s[l], &ev_t[(size_t)l * PDLPDEV_EV_COUNT], &terminated, &again);
+        if (rc != 0) return rc;
+        major_was_done(b->s[l], terminated);
+        if (terminated) done[l] = 1;
+        else if (again) restart[l] = 1, theta[l] = b->s[l]->H.primal_weight_update_smoothing, any_restart = true;
+      }
+      if (any_restart) {
+        rc = pdlpdev_small_batch_halpern_restart(b->small, restart.data(), theta.data(), nullptr, ctl.data(), hal.data());
+        if (rc != 0) return fail(rc, "pdlpdev_small_batch_halpern_restart: %s", pdlpdev_last_error());
+        for (int l = 0; l < K; ++l)
+          if (restart[l]) {
+            b->s[l]->ctl = ctl[l], b->s[l]->hal = hal[l];
+            halpern_restart_done(b->s[l]);
+          }
+      }
+    }
+    // ---- budgets and targets; what the steps need first (a cleared step error; A^T y of the iterate exists since the start of the run)
+    any = false;
+    bool any_prepare = false;
+    for (int l = 0; l < K; ++l) {
+      target[l] = 0, clear[l] = 0, aty[l] = 0, ahead[l].mode = -1;
+      if (done[l]) continue;
+      cuoptamd_solver* s = b->s[l];
+      if (!next_target(s, budget_end[l], &target[l])) {
+        done[l] = 1, target[l] = 0;
+        continue;
+      }
+      any = true;
+      if (s->step_error) s->step_error = false, clear[l] = 1, any_prepare = true;
+      if (s->need_aty) s->need_aty = false, aty[l] = 1, any_prepare = true;
+      // the major iteration these steps end in: its evaluation is enqueued behind them (cuoptamd_solver_advance's period path)
+      const cuoptamd_hyper& H = s->H;
+      const int32_t it_after = target[l] + s->iteration_offset;
+      if (!H.artificial_restart_in_main_loop && ((it_after % H.major_iteration == 0 && it_after > 0) || it_after <= H.min_iteration_restart)) {
+        ahead[l]      = major_eval_request_at(s, it_after, s->ctl.its_since_restart + (target[l] - s->ctl.steps_taken));
+        ahead[l].mode = 0;
+      }
+    }
+    if (any_prepare) {
+      int rc = pdlpdev_small_batch_prepare(b->small, clear.data(), nullptr, aty.data());
+      if (rc != 0) return fail(rc, "pdlpdev_small_batch_prepare: %s", pdlpdev_last_error());
+    }
+    if (!any) return 0;
+    int rc = pdlpdev_small_batch_run(b->small, target.data(), ctl.data(), ahead.data(), ev.data(), ev_t.data(), evaluated.data());
+    if (rc != 0) return fail(rc, "pdlpdev_small_batch_run: %s", pdlpdev_last_error());
+    for (int l = 0; l < K; ++l)
+      if (target[l] > 0) {
+        b->s[l]->ctl = ctl[l];
+        advance_after_attempts(b->s[l]);  // (the Halpern scalars: from the pinned mirror the loop kernel wrote, no read-back)
+      }
+  }
+}
 
 // every LP of the batch up to max_new_iterations further iterations (or to its verdict); results[l] as cuoptamd_solver_advance's.
 // An LP that finishes rests while the others go on; each LP's trajectory is the one its own cuoptamd_solver_advance would take.
@@ -1707,7 +1835,7 @@ int cuoptamd_batch_advance(cuoptamd_batch* b, int32_t max_new_iterations, cuopta
     }
     return rc;
   };
-  if (b->small) return leave(small_batch_advance(b, budget_end, done));
+  if (b->small) return leave(b->halpern ? halpern_small_batch_advance(b, budget_end, done) : small_batch_advance(b, budget_end, done));
   std::vector<pdlpdev_ctl> ctl(K);
   for (;;) {
     bool any = false;
@@ -1769,6 +1897,10 @@ static int batch_reset_impl(cuoptamd_batch* b, const double* const* lb, const do
     if (s->S.relative_primal_tolerance_factor >= 0.0) s->norm_b = s->S.relative_primal_tolerance_factor;
     if (s->S.relative_dual_tolerance_factor >= 0.0) s->norm_c = s->S.relative_dual_tolerance_factor;
     s->ctl = ctl[l];
+    if (b->halpern) {  // (start_run in this mode: A^T y of the starting point exists, the anchor is set, the scalars are cleared)
+      s->need_aty = false;
+      DEV(pdlpdev_get_halpern(s->dev, &s->hal));
+    }
     s->result.initial_step_size = step[l], s->result.initial_primal_weight = weight[l];
     s->result.norm_b = s->norm_b, s->result.norm_c = s->norm_c;
     s->result.step_size = step[l], s->result.primal_weight = weight[l];
@@ -1828,6 +1960,14 @@ int cuoptamd_batch_solution_views(cuoptamd_batch* b, const double** x, const dou
   for (int l = 0; l < b->K; ++l) which[l] = (b->s[l]->empty_problem || !b->s[l]->dev) ? -1 : b->s[l]->returned_which;
   int rc_ = pdlpdev_small_batch_solution_views(b->small, which.data(), x, y, rc);
   if (rc_ != 0) return fail(rc_, "pdlpdev_small_batch_solution_views: %s", pdlpdev_last_error());
+  return 0;
+}
+
+int cuoptamd_batch_stats(cuoptamd_batch* b, int64_t out[8])
+{
+  if (!b || !out) return fail(-1, "cuoptamd_batch_stats: null argument");
+  if (!b->small) return fail(-7, "cuoptamd_batch_stats: a batch of resident small LPs only");
+  DEV(pdlpdev_small_batch_stats(b->small, out));
   return 0;
 }
 
@@ -2137,6 +2277,7 @@ int cuoptamd_warm_start_remap(const cuoptamd_warm_start* in, const int32_t* var_
 // cuoptamd_batch_solve's path for LPs over one matrix and objective.  kNotShared: they are not (or the layouts are not the batch's):
 // nothing was done, the caller solves them independently.
 static constexpr int kNotShared = 12345;
+static thread_local const char* t_batch_solve_path = "";  // cuoptamd_batch_solve_last_path
 static int shared_matrix_batch_solve(int32_t count, const cuoptamd_lp* lps, const cuoptamd_hyper* hyper, const cuoptamd_settings* settings, int device,
                                      cuoptamd_result* results, double** x, double** y, double** rc)
 {
@@ -2219,7 +2360,9 @@ static int shared_matrix_batch_solve(int32_t count, const cuoptamd_lp* lps, cons
 static int small_lp_batch_solve(int32_t count, const cuoptamd_lp* lps, const cuoptamd_hyper* hyper, const cuoptamd_settings* settings, int device,
                                 int max_threads, cuoptamd_result* results, double** x, double** y, double** rc)
 {
-  if (hyper->algorithm == 1 && settings->halpern_resident) return kNotShared;  // (no K-workgroup batch in that mode: each LP runs its own resident loop)
+  // (reflected Halpern mode on the resident path: the K-workgroup batch is an option, cuoptamd_settings::halpern_batch; without it each
+  //  LP runs its own resident loop)
+  if (hyper->algorithm == 1 && settings->halpern_resident && !settings->halpern_batch) return kNotShared;
   for (int i = 0; i < count; ++i) {
     const cuoptamd_lp& L = lps[i];
     if (L.m <= 0 || L.n <= 0 || !L.offsets || !pdlpdev_resident_size(L.m, L.n, L.offsets[L.m])) return kNotShared;
@@ -2275,17 +2418,25 @@ int cuoptamd_batch_solve(int32_t count, const cuoptamd_lp* lps, const cuoptamd_h
 {
   if (count < 0 || (count > 0 && (!lps || !hyper || !settings || !results)))
     return fail(-1, "cuoptamd_batch_solve: null argument");
+  t_batch_solve_path = "";
   // small LPs (the size of MIP relaxations): all of them at once, a workgroup each (round 6)
   if (count >= 2 && cuopt_amd::tune_int("small_batch", 1) != 0) {
     int rc_ = small_lp_batch_solve(count, lps, hyper, settings, device, max_threads, results, x, y, rc);
-    if (rc_ != kNotShared) return rc_;
+    if (rc_ != kNotShared) {
+      t_batch_solve_path = hyper->algorithm == 1 ? "small_halpern" : "small";
+      return rc_;
+    }
   }
   // LPs that share matrix and objective (the MIP heuristics' re-solves: the same A and c under other bounds) go through ONE set-up and
   // advance in lockstep, sixteen, eight or four at a time (cuoptamd_batch_*): each gets, bit for bit, the answer of its own solve
   if (count >= 4 && cuopt_amd::tune_int("shared_batch", 1) != 0) {
     int rc_ = shared_matrix_batch_solve(count, lps, hyper, settings, device, results, x, y, rc);
-    if (rc_ != kNotShared) return rc_;
+    if (rc_ != kNotShared) {
+      t_batch_solve_path = "shared_matrix";
+      return rc_;
+    }
   }
+  t_batch_solve_path = "independent";
   const int nt = std::max(1, std::min<int>(count, max_threads > 0 ? max_threads : cuopt_amd::host_threads()));
   std::vector<int> codes(count, 0);
   std::vector<std::string> messages(count);
@@ -2307,6 +2458,8 @@ int cuoptamd_batch_solve(int32_t count, const cuoptamd_lp* lps, const cuoptamd_h
     if (codes[i] != 0) return fail(codes[i], "LP %d of the batch: %s", i, messages[i].c_str());
   return 0;
 }
+
+const char* cuoptamd_batch_solve_last_path(void) { return t_batch_solve_path; }
 
 pdlpdev_ctx* cuoptamd_solver_device(cuoptamd_solver* s) { return s ? s->dev : nullptr; }
 

@@ -64,3 +64,36 @@ inline MajorSmallArgs major_args(const pdlpdev_ctx* ctx, int average_mode, int r
                         ctx->ax_u[PDLPDEV_CURRENT], ctx->ax_u[PDLPDEV_AVERAGE], ctx->aty_u[PDLPDEV_CURRENT],
                         ctx->aty_u[PDLPDEV_AVERAGE], ctx->rc[0], ctx->rc[1], ctx->scal_h};
 }
+
+// ---- the reflected-Halpern loop (kernels_resident_halpern.hip); the records of a Halpern small-LP batch sit in the batch object's
+// pinned block (kernels_resident.hip), which launches that unit's kernels through the three functions below
+struct HalpernSmallView {
+  int m, n, nnz;
+  const int32_t *a_off, *a_idx, *at_off, *at_idx;
+  const double *a_val, *at_val, *c, *lb, *ub, *lo, *hi;
+  double *x0, *x1, *y0, *y1, *aty0, *aty1;
+  const double *ax, *ay, *aaty;  // the anchor z^0 and its A^T y (lrx, lry, lraty)
+  double *tx, *ty;               // T(z^k) of the last step of a run (the average slots)
+};
+// one LP of k_pdhg_resident_halpern_batch (ResidentArgs' counterpart)
+struct HalpernResidentArgs {
+  HalpernSmallView V;
+  pdlpdev_ctl *ctl, *ctl_host;
+  pdlpdev_halpern *hal, *hal_host;
+  int target_steps, pad;
+};
+// one LP of k_halpern_restart_finish_batch
+struct HalpernRestartArgs {
+  int n, g, clear, pad;
+  double theta;  // < 0: the anchor and the counters only
+  const double* part;  // k_restart_batch's partials
+  const double *aty0, *aty1;
+  double* lraty;
+  double *dist2, *dist_host;  // the LP's scalar block on the device / its pinned one: the two distances (not squared) at [0], [1]
+  pdlpdev_ctl *ctl, *ctl_host;
+  pdlpdev_halpern *hal, *hal_host;
+};
+HalpernSmallView halpern_view(const pdlpdev_ctx* ctx);
+int halpern_batch_launch_loop(hipStream_t s, int device, int tier, const HalpernResidentArgs* args, const int* list, int count);
+int halpern_batch_launch_eval(hipStream_t s, int device, size_t lds, const MajorSmallArgs* args, const int* list, int count);
+int halpern_batch_launch_restart_finish(hipStream_t s, const HalpernRestartArgs* args, const int* list, int count);

@@ -12,6 +12,10 @@
  *                            nnz <= 4096 ... 8192) runs a whole period of steps inside one workgroup with the LP on chip
  *                            (cuoptamd_settings::halpern_resident).  Larger LPs, and every LP under CUOPT_AMD_SMALL=0, take the
  *                            multi-launch kernels; ignored by the other solver modes.  cuOptAmdGetSolveInfo says what ran.
+ *   CUOPT_AMD_HALPERN_BATCH  1 / 0 (default 0): with CUOPT_AMD_HALPERN_RESIDENT, the solvers of this call may be members of a
+ *                            K-workgroup batch (cuoptamd_settings::halpern_batch): where several LPs are solved at once
+ *                            (cuoptamd_batch_solve, cuoptamd_batch_create) K of them run in K workgroups of one launch, each
+ *                            bit for bit as on its own.  A single solve is not changed by it; ignored by the other solver modes.
  * Extra value of CUOPT_PDLP_SOLVER_MODE (constants.h stops at CUOPT_PDLP_SOLVER_MODE_FAST1 = 3):
  *   CUOPT_AMD_PDLP_SOLVER_MODE_HALPERN1 = 4: the restarted reflected Halpern iteration with a constant step size
  *                            (cuoptamd_hyper_preset(4), docs/design/04d_halpern_mode.md).  One GPU; infeasibility detection,
@@ -27,6 +31,7 @@
 #define CUOPT_AMD_NUM_GPUS "amd_num_gpus"
 #define CUOPT_AMD_SIMPLEX_GRADE "amd_simplex_grade"
 #define CUOPT_AMD_HALPERN_RESIDENT "amd_halpern_resident"
+#define CUOPT_AMD_HALPERN_BATCH "amd_halpern_batch"
 #define CUOPT_AMD_PDLP_SOLVER_MODE_HALPERN1 4
 
 #ifdef __cplusplus

@@ -386,6 +386,26 @@ int pdlpdev_small_batch_reset(pdlpdev_small_batch* batch, const int32_t* take, c
 int pdlpdev_small_batch_solution_views(pdlpdev_small_batch* batch, const int32_t* which, const double** x_view, const double** y_view, const double** rc_view);
 /* pdlpdev_get_solution(which[l], x[l], y[l], rc[l]) for every LP with which[l] >= 0 in one launch (arrays and entries may be NULL) */
 int pdlpdev_small_batch_get_solutions(pdlpdev_small_batch* batch, const int32_t* which, double* const* x, double* const* y, double* const* rc);
+/* ---- K small LPs in reflected Halpern mode in K workgroups (docs/design/04d_halpern_mode.md, "K LPs in K workgroups").  Every context
+ * resident and in Halpern mode (pdlpdev_set_halpern); -7 otherwise, and for a mix of averaging and Halpern contexts.  The same object:
+ *   _run        per tier in use one launch of the resident Halpern loop, the guarded evaluation of T(z^k) behind them (eval_after[l].mode
+ *               >= 0; the mode itself is not looked at), one synchronisation; evaluated[l] = 1: out_current and out_average both hold it
+ *   _major_eval the evaluation of T(z^k) (both outputs), whatever mode is asked for
+ *   _reset      additionally what pdlpdev_reset and the start of a run do in this mode: the Halpern block cleared, A^T y of the starting
+ *               point, the restart that sets the anchor only -- ctl[l] is the control block after it (pdlpdev_small_batch_get_halpern
+ *               for the other block)
+ *   _prepare, _get_solutions, _solution_views as they are; _restart (the averaging iteration's) answers -7.
+ * Each LP gets, bit for bit, what pdlpdev_run_period / pdlpdev_major_eval / pdlpdev_halpern_restart give it on its own. */
+int pdlpdev_small_batch_create_halpern(pdlpdev_small_batch** out, pdlpdev_ctx** ctx, int K);
+/* pdlpdev_halpern_restart(theta[l]) for every LP with restart[l] != 0 in two launches and one synchronisation; dist[2 l], dist[2 l + 1]
+ * (not squared), ctl[l], hal[l] receive what that call returns and pdlpdev_get_halpern reads afterwards (any of the three may be NULL) */
+int pdlpdev_small_batch_halpern_restart(pdlpdev_small_batch* batch, const int32_t* restart, const double* theta, double* dist, pdlpdev_ctl* ctl,
+                                        pdlpdev_halpern* hal);
+/* hal[l], l < K: the Halpern scalars of every LP as the last _run / _halpern_restart / _reset left them in their pinned mirrors */
+int pdlpdev_small_batch_get_halpern(pdlpdev_small_batch* batch, pdlpdev_halpern* hal);
+/* out = {Halpern batch (0 / 1), resident tiers in use, then for a Halpern batch: launches of the loop kernel, launches of the evaluation
+ * behind it, _run calls, restart rounds, resets, synchronisations (= runs + restart rounds + resets + separate _major_eval calls)} */
+int pdlpdev_small_batch_stats(pdlpdev_small_batch* batch, int64_t out[8]);
 /* re-arm the loop after the step-size error flag was raised (take_step resets valid_step_size_,
  * pdlp.cu:1190) */
 int pdlpdev_clear_error(pdlpdev_ctx* ctx);

@@ -145,6 +145,13 @@ typedef struct cuoptamd_settings {
    * no clones: cuoptamd_solver_clone answers -7 for it, as for every resident solver (the multi-launch mode 4 can be cloned);
    * cuoptamd_batch_solve then solves the LPs independently, each in its own resident loop. */
   int32_t halpern_resident;
+  /* Reflected Halpern mode on the resident path (algorithm == 1, halpern_resident != 0, an LP of resident size) only: non-zero lets
+   * the solver be a member of a K-workgroup batch -- cuoptamd_batch_create accepts solvers that ALL have it set and run on the
+   * resident path (any number, any matrices; -7 for a mix with other solvers), and cuoptamd_batch_solve takes that batch.  One launch
+   * per resident tier in use, the evaluation of T(z^k) behind it and one synchronisation per period of the whole batch; every member
+   * gets, bit for bit, what cuoptamd_solver_advance gives it on its own.  0 (default): refused / solved one after the other, as
+   * before.  Ignored when algorithm == 0. */
+  int32_t halpern_batch;
 } cuoptamd_settings;
 
 /* additional_termination_information_t (pdlp/solver_solution.hpp:63-103) + run statistics */
@@ -233,7 +240,8 @@ const char* cuoptamd_last_error(void);
 /* presets, mode numbering as CUOPT_PDLP_SOLVER_MODE_* (0 Stable1, 1 Stable2, 2 Methodical1, 3 Fast1) and, beyond the reference's,
  * 4 = Halpern1 (CUOPT_AMD_PDLP_SOLVER_MODE_HALPERN1, cuopt_c_ext.h): Stable2's scaling and initial primal weight, algorithm = 1.  A
  * Halpern solver runs on one GPU and refuses, with a message that names the mode: sharded creation, warm-start snapshots,
- * detect_infeasibility, save_best_primal_so_far, first_primal_feasible; cuoptamd_batch_create answers -7 for it. */
+ * detect_infeasibility, save_best_primal_so_far, first_primal_feasible; cuoptamd_batch_create answers -7 for it unless every member
+ * is a resident Halpern solver with cuoptamd_settings::halpern_batch set. */
 void cuoptamd_hyper_preset(int mode, cuoptamd_hyper* h);
 void cuoptamd_default_settings(cuoptamd_settings* s);
 
@@ -294,6 +302,9 @@ int cuoptamd_batch_get_solutions(cuoptamd_batch* batch, double* const* x, double
 int cuoptamd_batch_branch(cuoptamd_batch* batch, const int32_t* var, const double* lb, const double* ub);
 int cuoptamd_batch_solution_views(cuoptamd_batch* batch, const double** x, const double** y, const double** rc);
 void cuoptamd_batch_destroy(cuoptamd_batch* batch);
+/* counters of a small-LP batch (pdlpdev_small_batch_stats): {Halpern batch (0 / 1), resident tiers in use, loop launches, evaluation
+ * launches behind the loop, runs (periods), restart rounds, resets, synchronisations}; -7: not a small-LP batch */
+int cuoptamd_batch_stats(cuoptamd_batch* batch, int64_t out[8]);
 /* the device-layer batch behind it (pdlpdev_batch_time_kernels) */
 struct pdlpdev_batch* cuoptamd_batch_device(cuoptamd_batch* batch);
 
@@ -324,6 +335,11 @@ int cuoptamd_solver_get_solution(cuoptamd_solver* s, double* x, double* y, doubl
 int cuoptamd_batch_solve(int32_t count, const cuoptamd_lp* lps, const cuoptamd_hyper* hyper,
                          const cuoptamd_settings* settings, int device, int max_threads,
                          cuoptamd_result* results, double** x, double** y, double** rc);
+/* which way the last cuoptamd_batch_solve of this thread took (a static string; "" before the first call): "small" -- the K-workgroup
+ * batch of resident LPs --, "small_halpern" -- the same in reflected Halpern mode (cuoptamd_settings::halpern_batch) --,
+ * "shared_matrix" -- one set-up, clones, lockstep batches --, "independent" -- a solver per LP on worker threads.  The answers do
+ * not tell the ways apart: every one gives each LP the result of its own solve. */
+const char* cuoptamd_batch_solve_last_path(void);
 
 /* the device context (for kernel timing and buffer downloads in benches/tests) */
 pdlpdev_ctx* cuoptamd_solver_device(cuoptamd_solver* s);
