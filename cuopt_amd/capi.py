@@ -335,6 +335,8 @@ _proto("pdlpdev_debug_ipc_export", c_int, c_int, c_int, c_void_p, P(c_void_p))
 _proto("pdlpdev_debug_ipc_store", c_int, c_int, c_void_p, c_int, c_double)
 _proto("pdlpdev_debug_ipc_wait", c_int, c_int, c_void_p, c_int, c_double)
 _proto("pdlpdev_resident_size", c_int, c_int, c_int, C.c_int64)
+if hasattr(lib, "pdlpdev_resident_tier"):  # (an older build given through CUOPT_AMD_LIB does not export it)
+    _proto("pdlpdev_resident_tier", c_int, c_int, c_int, C.c_int64)
 _proto("pdlpdev_batch_time_kernels", c_int, c_void_p, c_int, c_void_p)
 _proto("pdlpdev_synthetic_lp", c_int, c_int, c_int, c_int, c_int, C.c_uint64, *([c_void_p] * 8))
 
@@ -1041,6 +1043,11 @@ def device_exclusive_scan(values, device=0):
     return out
 
 
+def resident_tier(m, n, nnz):
+    """pdlpdev_resident_tier: 0, 1, 2 = the instantiation of the one-workgroup loop an LP of this size runs in; -1 = not resident"""
+    return int(lib.pdlpdev_resident_tier(int(m), int(n), int(nnz)))
+
+
 class Device:
     """pdlpdev_ctx: direct access to the HIP kernels (kernel-level parity tests, timing)."""
 
@@ -1096,7 +1103,10 @@ class Device:
         return c
 
     def attempts(self, count=1):
-        """pdlpdev_debug_attempts: `count` attempts as run() enqueues them and NO make-up round -> the control block behind them"""
+        """pdlpdev_debug_attempts: `count` (1 .. 64) attempts as run() enqueues them and NO make-up round -> the control block behind them.
+        On a resident context (not in Halpern mode): one launch of the one-workgroup loop capped at `count` attempts.  There a REJECTED
+        attempt writes nothing but the control block (the trial iterate never leaves the registers: the _OTHER buffers are stale) and
+        XBAR is never written.  CuOptError -7: a sharded context, Halpern mode."""
         c = Ctl()
         self._ck(lib.pdlpdev_debug_attempts(self.handle, int(count), C.byref(c)))
         return c

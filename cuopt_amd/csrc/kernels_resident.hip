@@ -202,7 +202,7 @@ int resident_tier(int m, int n, int64_t nnz)
 }
 template <int T, int Q, int U>
 static int launch_resident(hipStream_t s, int tier, const SmallView& V, pdlpdev_ctl* ctl, pdlpdev_ctl* ctl_host,
-                           const pdlpdev_step_params& sp, int target_steps)
+                           const pdlpdev_step_params& sp, int target_steps, int max_attempts)
 {
   static PerDeviceOnce once;  // per instantiation
   int device = 0;
@@ -212,7 +212,7 @@ static int launch_resident(hipStream_t s, int tier, const SmallView& V, pdlpdev_
                                 (int)resident_lds_bytes(tier)));
     return 0;
   }));
-  k_pdhg_resident<T, Q, U><<<1, T, resident_lds_bytes(tier), s>>>(V, ctl, ctl_host, sp, target_steps, 1 << 14);
+  k_pdhg_resident<T, Q, U><<<1, T, resident_lds_bytes(tier), s>>>(V, ctl, ctl_host, sp, target_steps, max_attempts);
   HIP_TRY(hipGetLastError());
   return 0;
 }
@@ -312,6 +312,14 @@ static int major_lds_attribute(int device)
     return 0;
   });
 }
+// the tier's instantiation of the loop kernel, enqueued
+static int launch_resident_tier(pdlpdev_ctx* ctx, int tier, const SmallView& V, int32_t target_steps, int max_attempts)
+{
+  if (tier == 0) TRY((launch_resident<256, 2, 8>(ctx->stream, tier, V, ctx->ctl, ctx->ctl_h, ctx->sp, target_steps, max_attempts)));
+  if (tier == 1) TRY((launch_resident<512, 2, 16>(ctx->stream, tier, V, ctx->ctl, ctx->ctl_h, ctx->sp, target_steps, max_attempts)));
+  if (tier == 2) TRY((launch_resident<512, 4, 8>(ctx->stream, tier, V, ctx->ctl, ctx->ctl_h, ctx->sp, target_steps, max_attempts)));
+  return 0;
+}
 // one launch runs attempts until the target is reached (rejected attempts included); the cap only bounds a pathological rejection
 // streak, in which case the loop relaunches.  The kernel takes the target as an argument and leaves the control block in pinned host
 // memory: one launch + one synchronize per call.
@@ -320,12 +328,19 @@ int resident_run(pdlpdev_ctx* ctx, int32_t target_steps)
   const SmallView V = small_view(ctx);
   const int tier    = resident_tier(ctx->m, ctx->n, ctx->nnz);
   for (int guard = 0; guard < 1000; ++guard) {
-    if (tier == 0) TRY((launch_resident<256, 2, 8>(ctx->stream, tier, V, ctx->ctl, ctx->ctl_h, ctx->sp, target_steps)));
-    if (tier == 1) TRY((launch_resident<512, 2, 16>(ctx->stream, tier, V, ctx->ctl, ctx->ctl_h, ctx->sp, target_steps)));
-    if (tier == 2) TRY((launch_resident<512, 4, 8>(ctx->stream, tier, V, ctx->ctl, ctx->ctl_h, ctx->sp, target_steps)));
+    TRY(launch_resident_tier(ctx, tier, V, target_steps, 1 << 14));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     if (ctx->ctl_h->error != 0 || ctx->ctl_h->steps_taken >= target_steps) break;
   }
+  return 0;
+}
+// pdlpdev_debug_attempts' resident branch: ONE launch that makes at most `count` attempts towards steps_taken + count (ctl_h is current
+// on entry: the caller read it back), one synchronisation, no relaunch -- a rejected attempt is not made up for.  The kernel leaves the
+// control block in the pinned mirror.
+int resident_attempts(pdlpdev_ctx* ctx, int count)
+{
+  TRY(launch_resident_tier(ctx, resident_tier(ctx->m, ctx->n, ctx->nnz), small_view(ctx), ctx->ctl_h->steps_taken + count, count));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
   return 0;
 }
 int resident_major_eval(pdlpdev_ctx* ctx, int average_mode, int rc_rule_finite_bounds, int want_linf, double eps_rel_primal, double eps_rel_dual)

@@ -29,6 +29,7 @@ void pdlpdev_create_batch_lanes(int lanes) { g_create_batch_lanes = lanes; }
 static thread_local pdlpdev_ctx* g_create_stream_donor = nullptr;
 void pdlpdev_create_share_stream(pdlpdev_ctx* donor) { g_create_stream_donor = donor; }
 int pdlpdev_resident_size(int32_t m, int32_t n, int64_t nnz) { return resident_tier(m, n, nnz) >= 0 ? 1 : 0; }
+int pdlpdev_resident_tier(int32_t m, int32_t n, int64_t nnz) { return resident_tier(m, n, nnz); }
 
 int pdlpdev_device_count(void)
 {

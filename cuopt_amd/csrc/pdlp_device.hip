@@ -1183,13 +1183,21 @@ int pdlpdev_run(pdlpdev_ctx* ctx, int32_t target_steps, pdlpdev_ctl* ctl)
 
 // Parity hook: `count` attempts as pdlpdev_run enqueues them (same kernels, graph replay or plain launches), one read-back, after_round's
 // bookkeeping -- and NO make-up round, so a rejected attempt is there to be looked at: the trial iterate in the other side of the
-// ping-pong pairs, the decision's inputs in the control block.
+// ping-pong pairs, the decision's inputs in the control block.  On the resident small-LP path: one launch of the one-workgroup loop
+// capped at `count` attempts (resident_attempts); a rejected trial iterate stays in that kernel's registers.
 int pdlpdev_debug_attempts(pdlpdev_ctx* ctx, int count, pdlpdev_ctl* ctl)
 {
   HIP_TRY(hipSetDevice(ctx->device));
-  if (ctx->small_resident || ctx->comm || ctx->halpern)
-    return fail(-7, "pdlpdev_debug_attempts: the multi-launch averaging attempt only (not the resident small-LP path, a sharded context or Halpern mode)");
+  const bool resident = ctx->small_resident && !ctx->comm && !ctx->halpern;
+  if (!resident && (ctx->small_resident || ctx->comm || ctx->halpern))
+    return fail(-7, "pdlpdev_debug_attempts: the averaging attempt only, multi-launch or resident (not a sharded context or Halpern mode)");
   if (count < 1 || count > 64) return fail(-1, "pdlpdev_debug_attempts: count must be 1 .. 64");
+  if (resident) {
+    TRY(fetch_ctl(ctx, nullptr));
+    TRY(resident_attempts(ctx, count));
+    if (ctl) *ctl = *ctx->ctl_h;
+    return 0;
+  }
   TRY(fetch_ctl(ctx, nullptr));
   const int before = ctx->ctl_h->steps_taken, attempts_before = ctx->ctl_h->attempts;
   TRY(set_target(ctx, before + count));

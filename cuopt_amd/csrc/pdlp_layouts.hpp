@@ -127,6 +127,7 @@ void strip_transpose(const DenseHost& Din, DenseHost* D, int32_t n, const int32_
 // ---- the resident small-LP path (kernels_resident.hip) ----------------------------------------------------------------------------
 int resident_tier(int m, int n, int64_t nnz);
 int resident_run(pdlpdev_ctx* ctx, int32_t target_steps);  // attempts inside one workgroup until the target (pdlpdev_run's small branch)
+int resident_attempts(pdlpdev_ctx* ctx, int count);  // at most `count` attempts in ONE launch, no relaunch (pdlpdev_debug_attempts' small branch)
 int resident_major_eval(pdlpdev_ctx* ctx, int average_mode, int rc_rule_finite_bounds, int want_linf, double eps_rel_primal, double eps_rel_dual);
 // ... in reflected Halpern mode (kernels_resident_halpern.hip): pdlpdev_run's, pdlpdev_major_eval's and pdlpdev_run_period's branches;
 // the evaluation is T(z^k)'s alone and lands in scal_h[32..41)

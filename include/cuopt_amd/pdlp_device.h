@@ -177,6 +177,9 @@ void pdlpdev_create_batch_lanes(int lanes);
 void pdlpdev_create_share_stream(pdlpdev_ctx* donor);
 /* 1: an LP of this size takes the resident small-LP path (one workgroup, pdlpdev_small_batch eligible) unless CUOPT_AMD_SMALL=0 */
 int pdlpdev_resident_size(int32_t m, int32_t n, int64_t nnz);
+/* which of the three instantiations of the one-workgroup loop an LP of this size runs in: 0 (256 lanes, 2 rows / columns and 8
+ * nonzeros per lane), 1 (512, 2, 16), 2 (512, 4, 8), the smallest that holds it; -1: too large for the resident path */
+int pdlpdev_resident_tier(int32_t m, int32_t n, int64_t nnz);
 int pdlpdev_create_overlapped(pdlpdev_ctx** out, int device, int32_t m, int32_t n, const int32_t* a_offsets,
                               const int32_t* a_indices, const double* a_values, const int32_t* at_offsets,
                               const int32_t* at_indices, const double* at_values,
@@ -527,7 +530,13 @@ int pdlpdev_time_kernel(pdlpdev_ctx* ctx, int kernel_id, int reps, double* avg_m
  * *ctl (may be NULL) and the host's bookkeeping of a round is done -- but NO make-up round follows a rejection.  After a rejected
  * attempt the iterate is untouched, the trial iterate (x', y', A^T y') sits in the _OTHER buffers and last_interaction / last_movement /
  * last_dx2 / last_dy2 are the decision's inputs (tests/attempt_reference.py checks every one of them).  With the step error up nothing
- * is enqueued.  -7: the resident small-LP path, a sharded context, Halpern mode. */
+ * is enqueued.
+ * On the resident small-LP path (not in Halpern mode) the hook is ONE launch of the one-workgroup loop with the target steps_taken + count
+ * and at most `count` attempts, one synchronisation and no relaunch.  What it leaves behind differs: a REJECTED attempt writes nothing
+ * but the control block -- the trial iterate never leaves the kernel's registers, so the _OTHER buffers are stale -- and XBAR is never
+ * written.  The current side (X, Y, ATY), SUM_X / SUM_Y and the control block are as above; with the step error up the launch makes
+ * no attempt.
+ * -1: count outside 1 .. 64.  -7: a sharded context, Halpern mode (the resident Halpern loop included). */
 int pdlpdev_debug_attempts(pdlpdev_ctx* ctx, int count, pdlpdev_ctl* ctl);
 /* device-side generation of the iterate is not needed; but benches need a sync point */
 int pdlpdev_synchronize(pdlpdev_ctx* ctx);

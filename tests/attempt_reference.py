@@ -44,7 +44,20 @@ section 4.2):
   the restart's squared distances likewise: within (N + 16) u of the sum of the squared terms d_i = (anchor_i - candidate_i) [D_i].
 
 The reference's own error is at most N 2^-64 of the same magnitude sums (1/2048 of a bound).  The bounds are derived, not measured:
-a layout that exceeds one is a finding."""
+a layout that exceeds one is a finding.
+
+THE RESIDENT SMALL-LP PATH (check_attempt(resident=True); resident_body, cuopt_amd/csrc/kernels_resident.hip).  There every row and
+column is added up by its owning lane left to right in float64 from products rounded once (lds_row_sum), so MORE is bit for bit:
+    x', SUM_X, SUM_Y as above
+    y'      = dual_f64(prob, ctl, st, rowsums_f64(A, xbar)), xbar the reference's own (bit-exact from x')
+    A^T y'  = rowsums_f64(A^T, y'), A^T in the stable transposition of A (Structure.order) with the values the device holds for it
+              (prob["AT_VALUES"]: scaling multiplies A by D_r then D_c and A^T by D_c then D_r, so an entry of the two may differ in
+              its last bit; without that key A_VALUES in that order); an empty column is exactly 0
+The three sums go through block_sum_fast's fixed tree, which is not left to right: they keep the bounds above, and are taken from the
+reference's own trial vectors (which the device's equal bit for bit).  The decision and everything behind it is unchanged.  What can be
+looked at differs: an ACCEPTED attempt leaves its trial iterate as the new current side; a REJECTED one writes nothing but the
+control block and the running sums (the trial iterate never leaves the registers: the other side is stale and not read), so X, Y and
+ATY must be the bits in front of the attempt, SUM_X / SUM_Y too unless an average was pending.  XBAR is never written there."""
 import math
 
 import numpy as np
@@ -260,11 +273,44 @@ def restart(which, unscaled, cand_x, cand_y, anchor_x, anchor_y, dc, dr, exact=N
 
 
 # ---- one whole attempt checked against the state in front of it --------------------------------------------------------------------
-def check_attempt(S, prob, sp, before, after, tag="", exact=None):
+def _check_decision(tag, cb, ca, flipped, sp):
+    """(5) the decision, from the device's own three sums"""
+    dec = decision(cb, ca["last_dy2"], ca["last_interaction"], ca["last_dx2"], sp)
+    want = dec["ctl"]
+    assert ca["last_movement"] == want["last_movement"], (tag, "movement", ca["last_movement"], want["last_movement"])
+    for k in ("k", "attempts", "steps_taken", "its_since_restart", "cur", "pending_avg", "error"):
+        assert ca[k] == want[k], (tag, k, ca[k], want[k], dec["margin"])
+    assert flipped == dec["accepted"], (tag, "accepted", dec["margin"])
+    assert abs(ca["step_size"] - want["step_size"]) <= STEP_REL * abs(want["step_size"]), (tag, "step_size", ca["step_size"], want["step_size"])
+    assert ca["primal_weight"] == cb["primal_weight"], (tag, "primal_weight")
+    if want["error"] == 0:  # (the error path leaves step, tau and sigma alone)
+        assert ca["tau"] == ca["step_size"] / cb["primal_weight"] and ca["sigma"] == ca["step_size"] * cb["primal_weight"], (tag, "tau / sigma")
+    else:
+        assert (ca["step_size"], ca["tau"], ca["sigma"]) == (cb["step_size"], cb["tau"], cb["sigma"]), (tag, "step on the error path")
+    assert ca["sum_weights"] == (cb["sum_weights"] + ca["step_size"] if dec["accepted"] else cb["sum_weights"]), (tag, "sum_weights")
+    return dec, want
+
+
+def _check_sums(tag, s, ca, ratios):
+    """(4) the three sums against (value, bound) of step_sums()"""
+    ratios.update(dy2=scalar_ratio(s["dy2"], ca["last_dy2"], s["_exact"]), dx2=scalar_ratio(s["dx2"], ca["last_dx2"], s["_exact"]),
+                  inter=scalar_ratio(s["inter"], ca["last_interaction"], s["_exact"]))
+    for k in ("dy2", "dx2", "inter"):
+        assert ratios[k] <= 1.0, (tag, k + " outside its bound", ratios[k], float(s[k][0]), ca["last_" + ("interaction" if k == "inter" else k)])
+
+
+def _first(a, b):
+    return int(np.argmax(np.asarray(a).view(np.int64) != np.asarray(b).view(np.int64)))
+
+
+def check_attempt(S, prob, sp, before, after, tag="", exact=None, resident=False):
     """Every rule of the module's docstring for ONE attempt.  before / after: dict(ctl=control block, X, Y, ATY, X_OTHER, Y_OTHER,
     ATY_OTHER, SUM_X, SUM_Y[, XBAR in `after`]) as downloaded in front of and behind it (X: the CURRENT side at that moment).
+    resident: the rules of the resident small-LP path (neither the _OTHER buffers nor XBAR are read).
     Raises AssertionError naming the stage; returns dict(accepted, error, margin, limit, pending_before, cur_before, ratios:
     y, aty, dy2, dx2, inter)."""
+    if resident:
+        return _check_resident_attempt(S, prob, sp, before, after, tag, exact)
     cb, ca = ctl_dict(before["ctl"]), ctl_dict(after["ctl"])
     assert cb["error"] == 0 and cb["steps_taken"] < ca["target_steps"], (tag, "the attempt was a no-op by its guard", cb, ca)
     flipped = ca["cur"] != cb["cur"]
@@ -290,24 +336,44 @@ def check_attempt(S, prob, sp, before, after, tag="", exact=None):
     assert ra <= 1.0, (tag, "A^T y' outside its bound", ra, int(np.argmax(abs_err(a, trial["ATY"]) / np.maximum(a["bound"], 1e-300))))
     assert (trial["ATY"][S.len_c == 0] == 0.0).all(), (tag, "A^T y' of the empty columns")
     # (4) the three sums, from the device's own vectors
-    s = step_sums(before, trial["X"], trial["Y"], trial["ATY"], exact)
-    ratios = dict(y=ry, aty=ra, dy2=scalar_ratio(s["dy2"], ca["last_dy2"], s["_exact"]), dx2=scalar_ratio(s["dx2"], ca["last_dx2"], s["_exact"]),
-                  inter=scalar_ratio(s["inter"], ca["last_interaction"], s["_exact"]))
-    for k in ("dy2", "dx2", "inter"):
-        assert ratios[k] <= 1.0, (tag, k + " outside its bound", ratios[k], float(s[k][0]), ca["last_" + ("interaction" if k == "inter" else k)])
+    ratios = dict(y=ry, aty=ra)
+    _check_sums(tag, step_sums(before, trial["X"], trial["Y"], trial["ATY"], exact), ca, ratios)
     # (5) the decision, from the device's own three sums
-    dec = decision(cb, ca["last_dy2"], ca["last_interaction"], ca["last_dx2"], sp)
-    want = dec["ctl"]
-    assert ca["last_movement"] == want["last_movement"], (tag, "movement", ca["last_movement"], want["last_movement"])
-    for k in ("k", "attempts", "steps_taken", "its_since_restart", "cur", "pending_avg", "error"):
-        assert ca[k] == want[k], (tag, k, ca[k], want[k], dec["margin"])
-    assert flipped == dec["accepted"], (tag, "accepted", dec["margin"])
-    assert abs(ca["step_size"] - want["step_size"]) <= STEP_REL * abs(want["step_size"]), (tag, "step_size", ca["step_size"], want["step_size"])
-    assert ca["primal_weight"] == cb["primal_weight"], (tag, "primal_weight")
-    if want["error"] == 0:  # (the error path leaves step, tau and sigma alone)
-        assert ca["tau"] == ca["step_size"] / cb["primal_weight"] and ca["sigma"] == ca["step_size"] * cb["primal_weight"], (tag, "tau / sigma")
+    dec, want = _check_decision(tag, cb, ca, flipped, sp)
+    return dict(accepted=dec["accepted"], error=want["error"], margin=dec["margin"], limit=dec["limit"], pending_before=cb["pending_avg"],
+                cur_before=cb["cur"], ratios=ratios)
+
+
+def resident_trial(S, prob, ctl, st):
+    """the trial iterate of the resident path in float64, every row and column left to right: dict(xn, xbar, sumx, y, sumy, aty)"""
+    p = primal(prob, ctl, st)
+    y = dual_f64(prob, ctl, st, rowsums_f64(prob["A_VALUES"], p["xbar"], S.off, S.idx))
+    sumy = st["SUM_Y"] + np.float64(ctl["step_size"]) * st["Y"] if ctl["pending_avg"] else st["SUM_Y"].copy()
+    at_values = prob["AT_VALUES"] if "AT_VALUES" in prob else prob["A_VALUES"][S.order]
+    return dict(p, y=y, sumy=sumy, aty=rowsums_f64(at_values, y, S.t_off, S.t_rows))
+
+
+def _check_resident_attempt(S, prob, sp, before, after, tag, exact):
+    cb, ca = ctl_dict(before["ctl"]), ctl_dict(after["ctl"])
+    assert cb["error"] == 0 and cb["steps_taken"] < ca["target_steps"], (tag, "the attempt was a no-op by its guard", cb, ca)
+    flipped = ca["cur"] != cb["cur"]
+    t = resident_trial(S, prob, cb, before)
+    assert np.isfinite(t["y"]).all() and np.isfinite(t["aty"]).all(), (tag, "the reference's own trial iterate")
+    # (1) - (3): the running sums always; the trial iterate where it is the new current side, the untouched iterate where it is not
+    assert bits_equal(after["SUM_X"], t["sumx"]), (tag, "SUM_X", cb["pending_avg"], _first(after["SUM_X"], t["sumx"]))
+    assert bits_equal(after["SUM_Y"], t["sumy"]), (tag, "SUM_Y", cb["pending_avg"], _first(after["SUM_Y"], t["sumy"]))
+    if flipped:
+        assert bits_equal(after["X"], t["xn"]), (tag, "x'", _first(after["X"], t["xn"]))
+        assert bits_equal(after["Y"], t["y"]), (tag, "y'", _first(after["Y"], t["y"]))
+        assert bits_equal(after["ATY"], t["aty"]), (tag, "A^T y'", _first(after["ATY"], t["aty"]))
+        assert (after["ATY"][S.len_c == 0] == 0.0).all(), (tag, "A^T y' of the empty columns")
     else:
-        assert (ca["step_size"], ca["tau"], ca["sigma"]) == (cb["step_size"], cb["tau"], cb["sigma"]), (tag, "step on the error path")
-    assert ca["sum_weights"] == (cb["sum_weights"] + ca["step_size"] if dec["accepted"] else cb["sum_weights"]), (tag, "sum_weights")
+        for k in ("X", "Y", "ATY"):
+            assert bits_equal(after[k], before[k]), (tag, "the rejected attempt changed", k, _first(after[k], before[k]))
+    # (4) the three sums, from the reference's own trial vectors
+    ratios = dict(y=0.0, aty=0.0)
+    _check_sums(tag, step_sums(before, t["xn"], t["y"], t["aty"], exact), ca, ratios)
+    # (5) the decision, from the device's own three sums
+    dec, want = _check_decision(tag, cb, ca, flipped, sp)
     return dict(accepted=dec["accepted"], error=want["error"], margin=dec["margin"], limit=dec["limit"], pending_before=cb["pending_avg"],
                 cur_before=cb["cur"], ratios=ratios)

@@ -3,7 +3,8 @@ float64 stand-in, checked stage by stage with tests/attempt_reference.py.  numpy
 
 `dev` is anything with ctl() -> control block, get(buffer name) -> array, attempt() (ONE attempt, no make-up round), flush(),
 make_average(mode), restart(which, unscaled) -> the two squared distances, set_step(step, weight), compute_aty(), put(buffer name,
-array)."""
+array) -- and, for the resident small-LP path's further cases (edge_attempts, check_composition: tests/test_resident_attempts_gpu.py),
+attempts(count) (at most `count` attempts towards steps_taken + count in one go) and run(target) (attempts until `target` steps)."""
 import numpy as np
 
 import attempt_reference as ar
@@ -40,12 +41,13 @@ class Worst(dict):
         return "WORST %s " % name + " ".join("%s=%.3g" % (k, self[k]) for k in RATIOS)
 
 
-def one_attempt(dev, S, prob, sp, tag, worst=None, record=None):
-    """one attempt through the hook, checked fully against the state in front of it -> (result, before, after)"""
+def one_attempt(dev, S, prob, sp, tag, worst=None, record=None, resident=False):
+    """one attempt through the hook, checked fully against the state in front of it -> (result, before, after); resident: by the rules
+    of the resident small-LP path, on which XBAR is never written"""
     before = snapshot(dev)
     dev.attempt()
-    after = snapshot(dev, xbar=True)
-    r = ar.check_attempt(S, prob, sp, before, after, tag)
+    after = snapshot(dev, xbar=not resident)
+    r = ar.check_attempt(S, prob, sp, before, after, tag, resident=resident)
     if worst is not None:
         worst.take(r["ratios"])
     if record is not None:
@@ -57,11 +59,11 @@ def assert_decided(r, tag):
     assert r["error"] == 0 and abs(r["margin"] - 1.0) >= MIN_MARGIN_GAP, (tag, "a near tie: take another seed", r["margin"])
 
 
-def natural_attempts(dev, S, prob, sp, tag, worst, record=None, count=NATURAL_ATTEMPTS):
+def natural_attempts(dev, S, prob, sp, tag, worst, record=None, count=NATURAL_ATTEMPTS, resident=False):
     """step 2: `count` single attempts, each checked; both cur parities accepted from, both pending_avg states seen"""
     seen = []
     for i in range(count):
-        r = one_attempt(dev, S, prob, sp, "%s attempt %d" % (tag, i), worst, record)[0]
+        r = one_attempt(dev, S, prob, sp, "%s attempt %d" % (tag, i), worst, record, resident)[0]
         assert_decided(r, "%s attempt %d" % (tag, i))
         seen.append(r)
     assert {r["cur_before"] for r in seen if r["accepted"]} == {0, 1}, (tag, "accepted from both sides of the ping-pong pairs", seen)
@@ -101,7 +103,7 @@ def check_restart(dev, which, unscaled, dr, dc, tag, worst):
     return after
 
 
-def force_rejection(dev, S, prob, sp, held, name):
+def force_rejection(dev, S, prob, sp, held, name, recoverable=False):
     """set_step(64 step, w) alone does not force a rejection with step / limit >= 2 on any LP: the limit of a consistent state grows
     with the step (for dy = -2 sigma A dx the limit is |dx|^2 / (4 step |A dx|^2) + step), so step / limit tends to 1 from either side
     -- 1.005, 1.022, 1.014, 0.994 (accepted!) and 1.003 on the five LPs here, at most 1.8 over a grid of steps and weights.  What
@@ -109,7 +111,15 @@ def force_rejection(dev, S, prob, sp, held, name):
     holds: Y + beta z through the upload hook, z = +-(A dx) on the equality rows (where the projection is the identity, so that dy and
     the movement stay what they were) and 0 elsewhere, dx the primal move this attempt is going to make (k_primal never reads y).  The
     interaction moves by beta (A dx).z, and beta is sized with the reference so that step / limit becomes FORCED_TARGET.  The attempt
-    kernels are functions of the buffers they are handed; the reference is handed the same ones.  -> the Y to put back afterwards"""
+    kernels are functions of the buffers they are handed; the reference is handed the same ones.  -> the Y to put back afterwards
+
+    recoverable: for a whole RUN behind the displacement, in the middle of which nobody can put Y back.  While Y sits off the A^T y
+    the device holds, the interaction keeps the term beta z.(A dx), which shrinks only like the step while the movement shrinks like its
+    square: with z = A dx, step / limit tends to a constant far above 1 as the rejections shorten the step (10 ... 1e5 on the resident
+    tests' LPs) and nothing is accepted until the movement underflows.  So z is taken orthogonal, on the equality rows, to A d, d the
+    direction every SHORT primal move has (-(c - A^T y) on the columns that do not push into a bound they sit on): the term is there at
+    the long step, which is rejected at step / limit = 4 all the same, and gone once the step is short, where an attempt is accepted
+    and forms A^T y afresh."""
     dev.set_step(FORCED_FACTOR * held["ctl"]["step_size"], held["ctl"]["primal_weight"])
     st = snapshot(dev)
     c = st["ctl"]
@@ -122,6 +132,11 @@ def force_rejection(dev, S, prob, sp, held, name):
     inter0, movement = float(s["inter"][0]), dec["ctl"]["last_movement"]
     adx = _segment_sums(prob["A_VALUES"] * (p["xn"] - st["X"])[S.idx], S.off, np.zeros(S.m))
     z = np.where(np.isfinite(prob["LO"]) & (prob["LO"] == prob["HI"]), adx, 0.0)
+    if recoverable:
+        gradient = prob["C"] - st["ATY"]
+        short = np.where(((st["X"] <= prob["LB"]) & (gradient > 0.0)) | ((st["X"] >= prob["UB"]) & (gradient < 0.0)), 0.0, -gradient)
+        ad = np.where(z != 0.0, _segment_sums(prob["A_VALUES"] * short[S.idx], S.off, np.zeros(S.m)), 0.0)
+        z = z - (float(np.sum(z * ad)) / float(np.sum(ad * ad))) * ad
     gain = float(np.sum(z * adx))
     assert gain > 0.0 and movement > 0.0, (name, "no equality row moves", gain, movement)
     beta = (FORCED_TARGET * movement / c["step_size"] - abs(inter0)) / gain
@@ -130,22 +145,22 @@ def force_rejection(dev, S, prob, sp, held, name):
     return st["Y"]
 
 
-def run_scenario(dev, S, prob, sp, dr, dc, name):
+def run_scenario(dev, S, prob, sp, dr, dc, name, resident=False):
     """steps 2 .. 5 on a context prepared by step 1 -> Worst"""
     worst = Worst()
-    natural_attempts(dev, S, prob, sp, name, worst)
+    natural_attempts(dev, S, prob, sp, name, worst, resident=resident)
     # 3. a forced rejection: no average pending, a step 64 times too long and the dual iterate moved off its A^T y (force_rejection)
     held = check_flush(dev, name + " flush")
     y_kept = force_rejection(dev, S, prob, sp, held, name)
     held = snapshot(dev)
-    r, before, after = one_attempt(dev, S, prob, sp, name + " forced rejection", worst)
+    r, before, after = one_attempt(dev, S, prob, sp, name + " forced rejection", worst, resident=resident)
     assert not r["accepted"] and r["margin"] >= FORCED_MARGIN, (name, "the forced rejection", r)
     assert (after["ctl"]["cur"], after["ctl"]["steps_taken"], after["ctl"]["pending_avg"]) == (held["ctl"]["cur"], held["ctl"]["steps_taken"], 0), after["ctl"]
     for k in ("X", "Y", "ATY", "SUM_X", "SUM_Y"):
         assert ar.bits_equal(after[k], held[k]), (name, "the rejected attempt changed", k)
     dev.put("Y", y_kept)
     for i in range(6):  # (the step behind a rejection at margin 4 is still several times the one the iteration had reached)
-        r, before, after = one_attempt(dev, S, prob, sp, "%s behind the rejection %d" % (name, i), worst)
+        r, before, after = one_attempt(dev, S, prob, sp, "%s behind the rejection %d" % (name, i), worst, resident=resident)
         assert_decided(r, "%s behind the rejection %d" % (name, i))
         assert r["pending_before"] == 0 and ar.bits_equal(after["SUM_X"], held["SUM_X"]) and ar.bits_equal(after["SUM_Y"], held["SUM_Y"]), (name, "sums behind the rejection")
         if r["accepted"]:  # (an accepted step is what steps 4 and 5 average and restart from)
@@ -167,9 +182,104 @@ def run_scenario(dev, S, prob, sp, dr, dc, name):
     a = ar.aty_product(S, prob, st["Y"])
     assert ar.worst_ratio(ar.abs_err(a, st["ATY"]), a["bound"]) <= 1.0, (name, "A^T y behind the restart")
     for i in range(2):
-        assert_decided(one_attempt(dev, S, prob, sp, "%s restarted attempt %d" % (name, i), worst)[0], name + " restarted")
+        assert_decided(one_attempt(dev, S, prob, sp, "%s restarted attempt %d" % (name, i), worst, resident=resident)[0], name + " restarted")
     check_restart(dev, ar.CURRENT, 1, dr, dc, name + " restart to the current iterate", worst)
     return worst
+
+
+# ---- the resident small-LP path's further cases ------------------------------------------------------------------------------------------
+CURRENT_SIDE = ("X", "Y", "ATY", "SUM_X", "SUM_Y")
+LAUNCH_ATTEMPTS = 12  # attempts of the one launch that is compared with as many single ones
+RUN_STEPS = 4         # accepted steps of the run behind the forced rejection
+STARTS = ("fresh", "pending", "cur1")  # cur = 0 and nothing pending; two steps on: an average pending; one step and a flush on: cur = 1
+EVAL_COMBOS = [(mode, rule, eps) for mode in (0, 1, 2) for rule in (True, False) for eps in (1e-4, -1.0)]
+
+
+def edge_attempts(dev, S, prob, sp, name, worst, resident=True):
+    """NATURAL_ATTEMPTS single attempts, each checked.  On the LPs of one row or one column only what is defined is asserted: an attempt
+    that ends in the step error (no movement) is checked like any other, the attempts behind it must leave the control block's
+    (error, attempts, steps_taken) and the iterate alone, and no property of the sequence is asked for."""
+    if not name.startswith("minimal"):
+        return natural_attempts(dev, S, prob, sp, name, worst, resident=resident)
+    seen = []
+    for i in range(NATURAL_ATTEMPTS):
+        if seen and seen[-1]["error"]:
+            before = snapshot(dev)
+            dev.attempt()
+            after = snapshot(dev)
+            assert all(after["ctl"][k] == before["ctl"][k] for k in ("error", "attempts", "steps_taken", "cur", "pending_avg", "step_size")), (name, i, after["ctl"])
+            assert all(ar.bits_equal(after[k], before[k]) for k in CURRENT_SIDE), (name, i, "an attempt behind the step error wrote")
+            continue
+        r = one_attempt(dev, S, prob, sp, "%s attempt %d" % (name, i), worst, resident=resident)[0]
+        if not r["error"]:
+            assert abs(r["margin"] - 1.0) >= MIN_MARGIN_GAP, (name, i, "a near tie: take another seed", r["margin"])
+        seen.append(r)
+    return seen
+
+
+def start_state(dev, start):
+    """the prepared context moved to one of STARTS"""
+    if start == "pending":
+        dev.run(2)
+    elif start == "cur1":
+        dev.run(1)
+        dev.flush()
+    c = dev.ctl()
+    want = dict(fresh=(0, 0, 0), pending=(0, 1, 2), cur1=(1, 0, 1))[start]
+    assert (c["cur"], c["pending_avg"], c["steps_taken"]) == want and c["error"] == 0, (start, c)
+
+
+def _same(a, b, tag, skip=()):
+    for k in a["ctl"]:
+        assert k in skip or a["ctl"][k] == b["ctl"][k], (tag, "control block", k, a["ctl"][k], b["ctl"][k])
+    for k in CURRENT_SIDE:
+        assert ar.bits_equal(a[k], b[k]), (tag, k, int(np.argmax(a[k] != b[k])))
+
+
+def check_composition(make, sp, name, start):
+    """A launch is the composition of its attempts.  make() -> (dev, S, prob) prepared afresh, the same state every time.
+    (a) attempts(LAUNCH_ATTEMPTS) in one go leaves the current side and the control block bit for bit what as many attempts(1) leave
+        (target_steps apart: it is what each call was asked for, steps_taken + count at ITS start);
+    (b) behind the scenario's forced rejection (set_step(64 step) and the moved Y in front of both), run(steps_taken + RUN_STEPS) leaves
+        them what attempts(1) repeated until that many steps leaves -- target_steps included -- and the run held a rejection.
+        (force_rejection(recoverable=True): a displacement of Y that a run gets past by itself.)
+    -> (attempts, accepted steps) of (a) and of (b)"""
+    tag = "%s from %s" % (name, start)
+    ends = []
+    for single in (False, True):
+        dev = make()[0]
+        start_state(dev, start)
+        first = dev.ctl()
+        if single:
+            for _ in range(LAUNCH_ATTEMPTS):
+                dev.attempts(1)
+        else:
+            dev.attempts(LAUNCH_ATTEMPTS)
+        ends.append(snapshot(dev))
+    _same(ends[0], ends[1], tag + ": one launch against single attempts", skip=("target_steps",))
+    c = ends[0]["ctl"]
+    counts_a = (c["attempts"] - first["attempts"], c["steps_taken"] - first["steps_taken"])
+    assert counts_a[0] == LAUNCH_ATTEMPTS and c["error"] == 0, (tag, c)
+    ends = []
+    for single in (False, True):
+        dev, S, prob = make()
+        start_state(dev, start)
+        force_rejection(dev, S, prob, sp, snapshot(dev), tag, recoverable=True)
+        first = dev.ctl()
+        target = first["steps_taken"] + RUN_STEPS
+        if single:
+            for _ in range(64 * RUN_STEPS):
+                if dev.ctl()["steps_taken"] >= target:
+                    break
+                dev.attempts(1)
+        else:
+            dev.run(target)
+        ends.append(snapshot(dev))
+    _same(ends[0], ends[1], tag + ": run against single attempts")
+    c = ends[0]["ctl"]
+    counts_b = (c["attempts"] - first["attempts"], c["steps_taken"] - first["steps_taken"])
+    assert c["error"] == 0 and counts_b[1] == RUN_STEPS and counts_b[0] > counts_b[1], (tag, "the run held no rejection", counts_b)
+    return counts_a, counts_b
 
 
 # ---- a plain float64 restatement standing in for the device ------------------------------------------------------------------------
@@ -177,8 +287,8 @@ class HostStandIn:
     """The same interface on the host: float64 throughout, numpy's own summation order.  It stands in for the device where the
     reference and the scenario are tested without one; it is no second reference."""
 
-    def __init__(self, S, prob, sp, x, y):
-        self.S, self.prob, self.sp = S, prob, sp
+    def __init__(self, S, prob, sp, x, y, resident=False):
+        self.S, self.prob, self.sp, self.resident = S, prob, sp, resident  # resident: rows and columns left to right, as the one-workgroup loop
         self.c = dict(step_size=0.0, primal_weight=1.0, tau=0.0, sigma=0.0, sum_weights=0.0, last_interaction=0.0, last_movement=0.0, last_dx2=0.0,
                       last_dy2=0.0, k=0, cur=0, pending_avg=0, steps_taken=0, attempts=0, target_steps=0, error=0, its_since_restart=0)
         n, m = S.n, S.m
@@ -209,15 +319,29 @@ class HostStandIn:
 
     def _at(self, y):
         S = self.S
+        if self.resident:
+            return ar.rowsums_f64(self.prob["A_VALUES"][S.order], y, S.t_off, S.t_rows)
         return _segment_sums(self.prob["A_VALUES"][S.order] * y[S.t_rows], S.t_off, np.zeros(S.n))
 
     def compute_aty(self):
         self.aty[self.c["cur"]] = self._at(self.y[self.c["cur"]])
 
     def attempt(self):
+        self.attempts(1)
+
+    def attempts(self, count):
+        self.c["target_steps"] = self.c["steps_taken"] + count
+        for _ in range(count):
+            self._attempt()
+
+    def run(self, target):
+        self.c["target_steps"] = target
+        while self.c["error"] == 0 and self.c["steps_taken"] < target:
+            self._attempt()
+
+    def _attempt(self):
         c, P, S, v = self.c, self.prob, self.S, self.v
-        c["target_steps"] = c["steps_taken"] + 1
-        if c["error"]:
+        if c["error"] or c["steps_taken"] >= c["target_steps"]:
             return
         cur = c["cur"]
         x, y, aty = self.x[cur], self.y[cur], self.aty[cur]
@@ -225,7 +349,10 @@ class HostStandIn:
         nxt = np.where(nxt < P["UB"], nxt, P["UB"])
         nxt = np.where(nxt > P["LB"], nxt, P["LB"])
         v["XBAR"] = nxt - x + nxt
-        ax = _segment_sums(P["A_VALUES"] * v["XBAR"][S.idx], S.off, np.zeros(S.m))
+        if self.resident:
+            ax = ar.rowsums_f64(P["A_VALUES"], v["XBAR"], S.off, S.idx)
+        else:
+            ax = _segment_sums(P["A_VALUES"] * v["XBAR"][S.idx], S.off, np.zeros(S.m))
         ny = y - c["sigma"] * ax
         with np.errstate(invalid="ignore"):
             low, up = ny + c["sigma"] * P["LO"], ny + c["sigma"] * P["HI"]
@@ -235,8 +362,9 @@ class HostStandIn:
             v["SUM_X"], v["SUM_Y"] = v["SUM_X"] + c["step_size"] * x, v["SUM_Y"] + c["step_size"] * y
         naty = self._at(ny)
         dx, dy = nxt - x, ny - y
-        self.x[cur ^ 1], self.y[cur ^ 1], self.aty[cur ^ 1] = nxt, ny, naty
         self.c = ar.decision(c, float(np.sum(dy * dy)), float(np.sum((naty - aty) * dx)), float(np.sum(dx * dx)), self.sp)["ctl"]
+        if not self.resident or self.c["cur"] != cur:  # (the resident loop's rejected trial iterate never leaves its registers)
+            self.x[cur ^ 1], self.y[cur ^ 1], self.aty[cur ^ 1] = nxt, ny, naty
 
     def flush(self):
         c, v, cur = self.c, self.v, self.c["cur"]
@@ -267,14 +395,14 @@ class HostStandIn:
         return np.array(dist)
 
 
-def stand_in(p, x0, y0, dr, dc, sp):
+def stand_in(p, x0, y0, dr, dc, sp, resident=False):
     """step 1 on the host: the LP scaled with (dr, dc) as pdlpdev_scale_problem scales it, the start scaled and projected, the step
     1 / max|A| at weight 1, A^T y formed -> (HostStandIn, Structure, the scaled problem)"""
     S = ar.Structure(p["m"], p["n"], p["offsets"], p["indices"])
     prob = dict(A_VALUES=np.asarray(p["values"], float) * dr[S.rows] * dc[S.idx], C=p["c"] * dc, LB=p["lb"] / dc, UB=p["ub"] / dc, LO=p["lo"] * dr,
                 HI=p["hi"] * dr)
     x = np.asarray(x0, float) / dc
-    dev = HostStandIn(S, prob, sp, np.minimum(np.maximum(x, prob["LB"]), prob["UB"]), np.asarray(y0, float) / dr)
+    dev = HostStandIn(S, prob, sp, np.minimum(np.maximum(x, prob["LB"]), prob["UB"]), np.asarray(y0, float) / dr, resident)
     dev.dr, dev.dc = dr, dc
     dev.set_step(1.0 / np.abs(prob["A_VALUES"]).max(), 1.0)
     dev.compute_aty()

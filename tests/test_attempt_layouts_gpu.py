@@ -160,11 +160,19 @@ def test_scalar_branches(kind, layout, monkeypatch):
 
 
 def test_hook_is_refused_where_no_multi_launch_attempt_runs(monkeypatch):
-    """-7 on the resident small-LP path and in Halpern mode"""
+    """-7 in Halpern mode, on the resident small-LP path (whose averaging loop the hook does serve: tests/test_resident_attempts_gpu.py)
+    and off it; -1 for a count outside 1 .. 64 on a resident context"""
     p, x0, y0 = sc.tiny_lp("dual-only")
     monkeypatch.setenv("CUOPT_AMD_SMALL", "1")
     raw = capi.Device(p)
     assert raw.layout()["resident"]
+    for count in (0, 65):
+        with pytest.raises(capi.CuOptError) as e:
+            raw.attempts(count)
+        assert e.value.code == -1
+    raw.call("scaling_compute", 1, 10, 1, 1.0)
+    raw.call("scale_problem")
+    raw.set_halpern(True)
     with pytest.raises(capi.CuOptError) as e:
         raw.attempts(1)
     assert e.value.code == -7

@@ -10,6 +10,7 @@ import attempt_reference as ar
 import attempt_scenario as sc
 import eval_reference as er
 from cuopt_amd import synthetic
+import resident_lps as rl
 from eval_lps import SEEDS, WIDE_N, edge_lp
 from oracle import orcbind
 
@@ -272,3 +273,131 @@ def test_scalar_branch_lps_on_the_stand_in(kind):
     dev, S, prob = sc.stand_in(p, x0, y0, ones_m, ones_n, step_params(1))
     r, before, after = sc.one_attempt(dev, S, prob, dev.sp, kind)
     sc.assert_scalar_branch(kind, r, before, after, dev.sp)
+
+
+# ---- the resident small-LP tests' LPs and cases on the stand-in ----------------------------------------------------------------------
+EVALUATED = list(rl.SCENARIO) + list(rl.FULL)
+
+
+@pytest.fixture(scope="module", params=list(rl.ALL))
+def resident_lp(request):
+    p, x, y = rl.lp(request.param)
+    return request.param, p, x, y, scaling_of(p)
+
+
+def resident_stand_in(lp):
+    name, p, x0, y0, (dr, dc) = lp
+    return sc.stand_in(p, x0, y0, dr, dc, step_params(1), resident=True)
+
+
+def test_resident_lps_hold_what_they_promise(resident_lp):
+    from cuopt_amd import capi
+    name, p, x, y, _ = resident_lp
+    m, n, nnz = p["m"], p["n"], len(p["values"])
+    want_m, want_n, entries, tier = rl.ALL[name][:4]
+    assert (m, n) == (want_m, want_n) and (entries is None or nnz == entries) and capi.resident_tier(m, n, nnz) == tier
+    rlen, clen = np.diff(p["offsets"]), np.bincount(p["indices"], minlength=n)
+    assert all((np.diff(p["indices"][a:b]) > 0).all() for a, b in zip(p["offsets"][:-1], p["offsets"][1:]))  # ascending, no duplicate
+    if name in rl.SCENARIO or name in rl.FULL:
+        assert set(rl.ROW_LENGTHS + rl.LONG_ROWS) <= set(rlen.tolist()) and clen.max() == clen[p["long_col"]] == rl.LONG_COL
+        assert (rlen == 0).sum() >= rl.EMPTY and (clen[p["empty_cols"]] == 0).all() and len(p["empty_cols"]) >= rl.EMPTY
+        zero_cost = (p["c"][p["empty_cols"]] == 0).sum()
+        assert zero_cost == (rl.EMPTY if name in rl.FULL else rl.EMPTY // 2)
+    if name in rl.FULL:  # every lane, every slot
+        T, Q, U = ((256, 2, 8), (512, 2, 16), (512, 4, 8))[tier]
+        assert m == n == Q * T and (nnz == U * T or (tier == 2 and nnz == 4096))
+    if name == "t1-full":
+        assert 8 * nnz == 65536  # k_major_small's dynamic LDS at the most it asks the runtime for
+    if name == "t1":
+        assert nnz > 4096
+    if name == "past-n":
+        assert capi.resident_tier(m, n - 1, nnz) == 0 and nnz <= 2048
+    if name == "past-nnz":
+        assert capi.resident_tier(m, n, nnz - 1) == 0
+    if name == "rows-only":
+        assert capi.resident_tier(m - 1, n, nnz) < 2 and n < 64
+    if name == "cols-only":
+        assert capi.resident_tier(m, n - 1, nnz) < 2 and m < 64
+    if name == "spanning":
+        assert rlen[rl.SPANNING_ROW] == n and clen[rl.SPANNING_COL] == m
+    if min(m, n) >= 5:
+        lo, hi, lb, ub = (p[k] for k in ("lo", "hi", "lb", "ub"))
+        row_kinds = [np.isinf(lo) & np.isfinite(hi), np.isfinite(lo) & np.isinf(hi), lo == hi, np.isinf(lo) & np.isinf(hi), np.isfinite(lo) & np.isfinite(hi) & (lo < hi)]
+        col_kinds = [np.isinf(lb) & np.isinf(ub), np.isinf(lb) & (ub == 5.0), (lb == 0.0) & np.isinf(ub), (lb == 1.5) & (ub == 1.5), (lb == 0.0) & (ub == 5.0)]
+        assert all(m // 5 <= k.sum() <= -(-m // 5) for k in row_kinds) and all(n // 5 <= k.sum() <= -(-n // 5) for k in col_kinds)
+        assert (x[col_kinds[3]] == 1.5).all()
+
+
+def test_resident_attempts_on_the_stand_in(resident_lp, request):
+    """the scenario (t0, t1, t2) or the eight natural attempts (every other LP) by the resident rules: y' and A^T y' bit for bit, the
+    three sums and the restart's distances inside their bounds, and the properties the GPU test asserts on the device"""
+    name, p, x0, y0, (dr, dc) = resident_lp
+    dev, S, prob = resident_stand_in(resident_lp)
+    if name in rl.SCENARIO:
+        worst = sc.run_scenario(dev, S, prob, dev.sp, dr, dc, name, resident=True)
+        assert min(worst[k] for k in ("dy2", "dx2", "inter", "dist")) > 0.0, worst
+    else:
+        worst = sc.Worst()
+        seen = sc.edge_attempts(dev, S, prob, dev.sp, name, worst)
+        assert not name.startswith("minimal") or len(seen) >= 1
+    print(worst.line("stand-in " + name))
+    assert max(worst.values()) <= 1.0 and worst["y"] == worst["aty"] == 0.0, worst
+
+
+def test_the_resident_rules_name_a_stage():
+    """check_attempt(resident=True) accepts the stand-in's own attempt and names the stage when one bit is off"""
+    lp = ("t0",) + rl.lp("t0") + (scaling_of(rl.lp("t0")[0]),)
+    dev, S, prob = resident_stand_in(lp)
+    for _ in range(3):  # (the third has an average pending)
+        before = sc.snapshot(dev)
+        dev.attempt()
+        after = sc.snapshot(dev)
+    assert before["ctl"]["pending_avg"] == 1 and after["ctl"]["cur"] != before["ctl"]["cur"]
+    ar.check_attempt(S, prob, dev.sp, before, after, resident=True)
+    for key, stage in (("X", "x'"), ("Y", "y'"), ("ATY", "A^T y'"), ("SUM_X", "SUM_X"), ("SUM_Y", "SUM_Y")):
+        off = after[key].copy()
+        j = int(np.argmax(off != 0.0))
+        off[j] = np.nextafter(off[j], np.inf)
+        with pytest.raises(AssertionError, match=stage.replace("^", r"\^")):
+            ar.check_attempt(S, prob, dev.sp, before, dict(after, **{key: off}), resident=True)
+    with pytest.raises(AssertionError, match="dy2"):
+        ar.check_attempt(S, prob, dev.sp, before, dict(after, ctl=dict(after["ctl"], last_dy2=after["ctl"]["last_dy2"] * (1 + 2.0 ** -40))), resident=True)
+    rejected = dict(before, ctl=dict(after["ctl"], cur=before["ctl"]["cur"]), SUM_X=after["SUM_X"], SUM_Y=after["SUM_Y"])
+    with pytest.raises(AssertionError, match="accepted|steps_taken|cur"):  # (the sums say accepted: a kept iterate is no answer)
+        ar.check_attempt(S, prob, dev.sp, before, rejected, resident=True)
+
+
+@pytest.mark.parametrize("start", sc.STARTS)
+@pytest.mark.parametrize("name", EVALUATED)
+def test_composition_case_on_the_stand_in(name, start):
+    """the starts, the forced rejection in front of the run and the rejection inside it exist on these LPs (the equality itself is
+    trivial on the host)"""
+    p, x0, y0 = rl.lp(name)
+    dr, dc = scaling_of(p)
+    sp = step_params(1)
+    a, b = sc.check_composition(lambda: sc.stand_in(p, x0, y0, dr, dc, sp, resident=True), sp, name, start)
+    print("COMPOSITION stand-in %s from %s: %d attempts / %d steps, run %d / %d" % (name, start, *a, *b))
+
+
+@pytest.mark.parametrize("name", EVALUATED)
+def test_evaluated_iterates_hold_hardly_a_tie(name):
+    """the condition of the GPU test's evaluation case, on the reference alone: at the iterates k_major_small evaluates (behind 3
+    steps, then one more accepted step per combination) at most 0.5 % of the columns sit on a reduced-cost tie"""
+    p, x0, y0 = rl.lp(name)
+    dr, dc = scaling_of(p)
+    dev, S, prob = sc.stand_in(p, x0, y0, dr, dc, step_params(1), resident=True)
+    dev.run(3)
+    worst = 0.0
+    for mode, rule, eps in sc.EVAL_COMBOS:
+        c = dev.ctl()
+        assert c["pending_avg"] == 1 and c["error"] == 0
+        dev.flush()
+        dev.make_average(mode)
+        for xs, ys in ((dev.get("X"), dev.get("Y")), (dev.get("AVG_X"), dev.get("AVG_Y"))):
+            ref = er.evaluate(p, xs * dc, ys * dr, rule_finite=rule, eps_p=eps, eps_d=eps)
+            worst = max(worst, float(ref["near_tie"].mean()))
+            assert ref["near_tie"].mean() <= 0.005, (name, mode, rule, eps)
+            assert ref["g_is_zero"].any()
+        dev.run(c["steps_taken"] + 1)
+    assert dev.ctl()["cur"] == 1 and dev.ctl()["steps_taken"] == 3 + len(sc.EVAL_COMBOS)
+    print("TIES %s worst share %.4f" % (name, worst))
