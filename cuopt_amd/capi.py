@@ -111,7 +111,7 @@ class SolverSettings(C.Structure):
                 ("log_to_console", c_int), ("log_file", c_char_p), ("unbounded_from_feasible_iterates", c_int),
                 ("accept_enabled", c_int), ("accept_tolerance", c_double * 6),
                 ("relative_primal_tolerance_factor", c_double), ("relative_dual_tolerance_factor", c_double),
-                ("batch_lanes", c_int), ("halpern_resident", c_int), ("halpern_batch", c_int)]
+                ("batch_lanes", c_int), ("halpern_resident", c_int), ("halpern_batch", c_int), ("halpern_lockstep", c_int)]
 
 
 class Result(C.Structure):
@@ -798,7 +798,9 @@ class SharedMatrixBatch:
     """cuoptamd_batch: K = 2, 4, 8 or 16 Solvers over ONE matrix (a parent and its clones) advance in lockstep, the matrix streamed once
     per attempt for all of them -- or (round 6) ANY number of Solvers on the resident small-LP path, whatever their matrices, one
     workgroup each in one launch per phase; every LP's trajectory is bit-identical to its own Solver.advance.  CuOptError(-7) when
-    the solvers are eligible for neither (the caller then advances them one by one)."""
+    the solvers are eligible for neither (the caller then advances them one by one).  Solvers in reflected Halpern mode (mode=4) on
+    the multi-launch path form the lockstep batch only when EVERY member was created with halpern_lockstep=1 (their own K-wide product
+    kernels; a jagged side is refused); without it, or mixed with averaging solvers or with members that lack it: CuOptError(-7)."""
 
     def __init__(self, solvers):
         self.solvers = list(solvers)
@@ -915,7 +917,9 @@ SmallBatch = SharedMatrixBatch  # (the same cuoptamd_batch object; the name the 
 
 def batch_solve(problems, mode=1, max_threads=0, device=0, **setting_overrides):
     """cuoptamd_batch_solve: independent LPs solved concurrently on one GPU -> list of result dicts (batch_solve_last_path() says
-    which way the call took: mode=4 with halpern_resident=1, halpern_batch=1 puts LPs of resident size into K workgroups of one launch)"""
+    which way the call took: mode=4 with halpern_resident=1, halpern_batch=1 puts LPs of resident size into K workgroups of one launch;
+    mode=4 with halpern_lockstep=1 advances LPs that share matrix and objective as lockstep batches of 16 / 8 / 4, the rest one after the
+    other through the clones)"""
     k = len(problems)
     lps, keep = (LP * k)(), []
     for i, p in enumerate(problems):
@@ -944,7 +948,8 @@ def batch_solve(problems, mode=1, max_threads=0, device=0, **setting_overrides):
 
 
 def batch_solve_last_path():
-    """cuoptamd_batch_solve_last_path: "small", "small_halpern", "shared_matrix" or "independent" ("" before the first batch_solve of this thread)"""
+    """cuoptamd_batch_solve_last_path: "small", "small_halpern", "shared_matrix", "shared_matrix_halpern" (at least one group
+    ran as a Halpern lockstep batch: halpern_lockstep=1) or "independent" ("" before the first batch_solve of this thread)"""
     return lib.cuoptamd_batch_solve_last_path().decode()
 
 

@@ -66,6 +66,7 @@ struct Settings {
   // the CUOPT_AMD_TUNE environment string, default on)
   int32_t num_gpus = 0, simplex_grade = -1;
   int32_t halpern_resident = 0;  // reflected Halpern mode: LPs of resident size run inside one workgroup (cuoptamd_settings::halpern_resident)
+  int32_t halpern_lockstep = 0;  // mode 4 on the multi-launch path: LPs over one matrix in lockstep batches (cuoptamd_settings::halpern_lockstep)
   int32_t halpern_batch = 0;     // ... and K of them in K workgroups of one launch where a batch is solved (cuoptamd_settings::halpern_batch)
   int32_t dual_simplex = -1;  // the dual simplex engine: -1 = CUOPT_AMD_DUAL_SIMPLEX (default on), 0 off, 1 on
   bool infeasibility_detection = false, strict_infeasibility = false, per_constraint_residual = false,
@@ -108,7 +109,8 @@ struct Settings {
             {"amd_simplex_grade", &simplex_grade, -1, 1},
             {"amd_dual_simplex", &dual_simplex, -1, 1},
             {CUOPT_AMD_HALPERN_RESIDENT, &halpern_resident, 0, 1},
-            {CUOPT_AMD_HALPERN_BATCH, &halpern_batch, 0, 1}};
+            {CUOPT_AMD_HALPERN_BATCH, &halpern_batch, 0, 1},
+            {CUOPT_AMD_HALPERN_LOCKSTEP, &halpern_lockstep, 0, 1}};
     bools = {{CUOPT_INFEASIBILITY_DETECTION, &infeasibility_detection},
              {CUOPT_STRICT_INFEASIBILITY, &strict_infeasibility},
              {CUOPT_PER_CONSTRAINT_RESIDUAL, &per_constraint_residual},
@@ -788,6 +790,7 @@ cuopt_int_t cuOptSolve(cuOptOptimizationProblem problem, cuOptSolverSettings set
     st.log_to_console              = s->log_to_console;
     st.halpern_resident            = s->halpern_resident;
     st.halpern_batch               = s->halpern_batch;
+    st.halpern_lockstep            = s->halpern_lockstep;
     st.log_file                    = s->log_file.empty() ? nullptr : s->log_file.c_str();
     auto say = [&](const std::string& line) {
       if (s->log_to_console) std::fputs(line.c_str(), stdout), std::fflush(stdout);

@@ -1,0 +1,52 @@
+// The decision of a Halpern step for ONE LP by one workgroup of kHalpernDecisionThreads threads: the body of k_halpern_decision
+// (pdlp_device.hip) and of k_halpern_decision_batch (kernels_batch_halpern.hip, workgroup <-> LP), so that the two cannot drift apart.
+// The partials are added in k_step_decision's order, the fixed-point error of the step is formed in PDHG's metric
+//   r_k^2 = (w / eta) ||dx||^2 + 2 dy.(A dx) + ||dy||^2 / (eta w),   dy.(A dx) = dx.(A^T y' - A^T y^k) = StepEpilogue's first sum,
+// the counters advance and the buffers flip.  A NaN or an overflow raises the step error like an invalid movement does.
+#pragma once
+#include "pdlp_kernels.hpp"
+
+constexpr int kHalpernDecisionThreads = 1024;  // (= kDecisionThreads of pdlp_device.hip: one wide workgroup, every partial one independent load)
+
+__device__ __forceinline__ void halpern_decision_workgroup(pdlpdev_ctl* __restrict__ ctl, pdlpdev_halpern* __restrict__ hal, const double* __restrict__ part_dy,
+                                                           int nb_dy, const double* __restrict__ part_t, int nb_t)
+{
+  __shared__ double red[3 * 16];
+  pdlpdev_ctl lc = *ctl;
+  if (!(lc.error == 0 && lc.steps_taken < lc.target_steps)) return;
+  const int t   = threadIdx.x;
+  double acc[3] = {0.0, 0.0, 0.0};
+#pragma unroll 4
+  for (int i = t; i < nb_dy; i += kHalpernDecisionThreads) acc[0] += part_dy[i];
+#pragma unroll 4
+  for (int i = t; i < nb_t; i += kHalpernDecisionThreads) {
+    acc[1] += part_t[i];
+    acc[2] += part_t[nb_t + i];
+  }
+  block_sum_fast<3, kHalpernDecisionThreads / 64>(acc, red);
+  if (t != 0) return;
+  pdlpdev_halpern lh = *hal;
+  const double dy2 = acc[0], interaction = acc[1], dx2 = acc[2];
+  const double eta = lc.step_size, w = lc.primal_weight;
+  const double r2  = (w / eta) * dx2 + 2.0 * interaction + dy2 / (eta * w);
+  lc.last_interaction = interaction;
+  lc.last_movement    = r2;
+  lc.last_dx2         = dx2;
+  lc.last_dy2         = dy2;
+  lc.attempts += 1;
+  if (!(r2 == r2) || !(r2 < 1.0e100)) {
+    lc.error = 1;
+  } else {
+    const double r = sqrt(dmax(r2, 0.0));
+    lh.r = r, lh.r2 = r2;
+    if (lh.k == 0) lh.r_first = r;
+    lh.r2_min = dmin(lh.r2_min, r2);
+    lh.k += 1;
+    *hal = lh;
+  }
+  lc.k += 1;
+  lc.cur ^= 1;
+  lc.steps_taken += 1;
+  lc.its_since_restart += 1;
+  *ctl = lc;
+}

@@ -31,6 +31,7 @@
 #include <cstring>
 #include <hip/hip_runtime.h>
 
+#include "batch_common.hpp"
 #include "pdlp_ctx.hpp"
 
 #define LAUNCH_CHECK() HIP_TRY(hipGetLastError())
@@ -42,31 +43,7 @@ __global__ void k_set_error(pdlpdev_ctl* ctl);
 
 namespace {
 
-constexpr int kBT = kPanelThreads;  // threads per workgroup = the panel kernels' (the partial sums reproduce their tree)
-static_assert(kBT == 512, "8 waves of 64 lanes: the reduction below mirrors block_reduce<.., kPanelWaves>");
-constexpr int kBatchMax = 16;       // LPs per batch
-
-struct BatchLp {  // what the batched kernels need of one LP, in device memory
-  pdlpdev_ctl* ctl;
-  double *y0, *y1, *sumy;
-  const double *lo, *hi;
-  double *x0, *x1, *aty0, *aty1, *sumx;
-  const double *c, *lb, *ub;
-  pdlpdev_ctx::UniformBounds ubd;
-  double *part_a, *part_at;
-};
-static_assert(sizeof(BatchLp) == 16 * sizeof(void*) + 2 * sizeof(int) + 2 * sizeof(double), "no padding: batch_refresh_table compares entries with memcmp");
-
-// wave <-> LP in the element-wise phases: K <= 8: 8 / K waves share an LP (wave w: LP w % K, every (8 / K)-th piece of 64 rows from
-// piece w / K on); K = 16: a wave serves two LPs one after the other (w and w + 8)
-template <int K>
-struct WaveLps {
-  static constexpr int PASSES = K > 8 ? K / 8 : 1;  // LPs per wave
-  static constexpr int NSUB   = K > 8 ? 1 : 8 / K;  // waves per LP
-  static __device__ __forceinline__ int lp(int wave, int pass) { return K > 8 ? wave + 8 * pass : wave % K; }
-  static __device__ __forceinline__ int sub(int wave) { return K > 8 ? 0 : wave / K; }
-};
-
+// (kBT, kBatchMax, BatchLp, WaveLps: batch_common.hpp)
 // ---- (1) the primal step of K LPs (k_primal's expressions, LP by LP) with xbar written INTERLEAVED ------------------------------
 // wave <-> LP, lane <-> column: every per-LP stream is read and written in 512-byte pieces; the tile of xbar goes through LDS (one
 // padded row per column) and leaves as whole entries of the interleaved vector.
@@ -125,163 +102,7 @@ __global__ void __launch_bounds__(kBT) kb_primal(const BatchLp* __restrict__ lp,
 // through LDS): every per-LP stream is read and written in 512-byte pieces, and lane t of an LP's wave holds exactly the panel
 // kernels' "thread t" accumulators (rows t, t + 512, ... of the panel in ascending order), so the wave tree and the wave-by-wave
 // sum of block_reduce apply unchanged.
-template <int K>
-struct BatchGeometry {
-  static constexpr int KL    = K / 2;              // lanes per entry
-  static constexpr int G     = kBT / KL;           // groups per workgroup
-  static constexpr int CHUNK = K > 8 ? 256 : 512;  // matrix entries staged per pass (64 KB of products in two buffers)
-  static constexpr int PER   = CHUNK / G;          // entries per lane and chunk
-  static constexpr int RU    = kBT / G;            // rows per lane and block of 512 rows
-};
-template <int K>
-struct alignas(16) BatchShared {
-  using Geo = BatchGeometry<K>;
-  union {
-    struct {
-      double prod[2][Geo::CHUNK][K];
-      int scol[2][Geo::CHUNK];
-      double sval[2][Geo::CHUNK];
-    } p;
-    double sums[kBT][K + 1];  // the epilogue's view of a block: row sums / new iterates, one padded row per matrix row
-  } u;
-  double red[2][K][8];
-};
-static_assert(sizeof(BatchShared<8>) <= 80 * 1024 && sizeof(BatchShared<16>) <= 80 * 1024, "two workgroups per CU");
-
-// row sums of the block [b0, b0 + 512) of panel rows [r0, r0 + nr): lane (g, h) -- group g of K / 2 lanes, lane h of it = the LPs 2h and
-// 2h + 1 -- ends with s[u][0..1] = the sums of row b0 + g + G * u for its two LPs
-// LDS hazards of batch_block_sums (round-6 audit; the stage round 5's contention run had caught one barrier short):
-//   prod[2][], scol[2][], sval[2][]  double-buffered by chunk parity.  Trip c (ends in barrier E(c)): reads scol / sval[(c + 1) & 1]
-//   (chunk c + 1's entries, written in trip c - 1), reads prod[(c - 1) & 1] (chunk c - 1's products, written in trip c - 1), writes
-//   prod[c & 1] (last read by the row sums of chunk c - 2 in trip c - 1, before E(c - 1)) and scol / sval[c & 1] with chunk c + 2's
-//   entries (last read by trip c - 1's requests for chunk c, before E(c - 1)).  Every write is separated from the last read of its slot
-//   by E(c - 1), every read from the write it depends on by E(c - 1) as well; the barrier in front of trip 0 covers the two staged chunks.
-template <int K>
-__device__ __forceinline__ void batch_block_sums(BatchShared<K>& S, int r0, int nr, int b0, const int32_t* __restrict__ off, const int32_t* __restrict__ idx,
-                                                 const double* __restrict__ val, const double* __restrict__ vK, double (&s)[BatchGeometry<K>::RU][2])
-{
-  using Geo = BatchGeometry<K>;
-  constexpr int KL = Geo::KL, G = Geo::G, PER = Geo::PER, RU = Geo::RU, CH = Geo::CHUNK;
-  const int tid = threadIdx.x, h = tid % KL, g = tid / KL;
-  int k0[RU], k1[RU];
-#pragma unroll
-  for (int u = 0; u < RU; ++u) {
-    const int r = b0 + g + G * u;
-    const int i = r0 + (r < nr ? r : 0);
-    k0[u] = off[i];
-    k1[u] = r < nr ? off[i + 1] : k0[u];
-    s[u][0] = 0.0, s[u][1] = 0.0;
-  }
-  const int eb0 = off[r0 + b0], eb1 = off[r0 + (b0 + kBT < nr ? b0 + kBT : nr)];
-  const int nch = (eb1 - eb0 + CH - 1) / CH;
-  const bool stager = CH == kBT || tid < CH;  // (chunks of 256: the first four waves fetch and stage)
-  // chunks 0 and 1 staged (past the block's last entry: column 0 with value 0 -- gathered, multiplied, never added);
-  // chunk 0's gathers on their way
-#pragma unroll
-  for (int c = 0; c < 2; ++c) {
-    const int e   = eb0 + c * CH + tid;
-    const bool in = stager && e < eb1;
-    const int cl  = idx[in ? e : eb0];
-    const double vl = val[in ? e : eb0];
-    if (stager) S.u.p.scol[c][tid] = in ? cl : 0, S.u.p.sval[c][tid] = in ? vl : 0.0;
-  }
-  __syncthreads();
-  auto rowsum = [&](int cc) {
-    const int c0 = eb0 + cc * CH, c1 = c0 + CH < eb1 ? c0 + CH : eb1, pb = cc & 1;
-#pragma unroll
-    for (int u = 0; u < RU; ++u) {
-      const int a = k0[u] > c0 ? k0[u] : c0, e = k1[u] < c1 ? k1[u] : c1;
-      for (int k = a; k < e; ++k) {
-        const double2 p = *(const double2*)&S.u.p.prod[pb][k - c0][2 * h];
-        s[u][0] = s[u][0] + p.x, s[u][1] = s[u][1] + p.y;
-      }
-    }
-  };
-  double2 pv[PER], pvn[PER];
-  double sv[PER], svn[PER];
-  auto request = [&](int cc, double2 (&p)[PER], double (&v)[PER]) {  // chunk cc: its entries' values, its gathers
-#pragma unroll
-    for (int i = 0; i < PER; ++i) {
-      v[i] = S.u.p.sval[cc & 1][g + G * i];
-      p[i] = *(const double2*)(vK + ((unsigned)S.u.p.scol[cc & 1][g + G * i] * (unsigned)K + 2u * h));
-    }
-  };
-  // the entries of chunk c + 2 wait in registers for one trip before they go to LDS: every wait below is for loads issued a whole
-  // trip earlier (the vector memory counter completes in order: a load consumed in the trip that issued it would drag the trip's
-  // gathers along)
-  auto fetch = [&](int cc, int& col, double& v) {
-    const int e   = eb0 + cc * CH + tid;
-    const bool in = stager && e < eb1;
-    const int cl  = idx[in ? e : eb0];
-    const double vl = val[in ? e : eb0];
-    col = in ? cl : 0, v = in ? vl : 0.0;
-  };
-  int colA = 0, colB = 0;
-  double valA = 0.0, valB = 0.0;
-  // one trip: chunk c's products (its gathers were issued a trip ago into `cur`), chunk c + 1's gathers into `nxt`, chunk c + 2's
-  // entries from their registers to LDS, chunk c + 3's entries requested.  (Two register sets that swap roles, the loop unrolled by
-  // two: a copy "cur = nxt" at the end of a trip would wait for the gathers it has just issued.)
-  auto trip = [&](int c, double2 (&cur)[PER], double (&curv)[PER], double2 (&nxt)[PER], double (&nxtv)[PER], int& col_st, double& val_st, int& col_ld,
-                  double& val_ld) {
-    request(c + 1, nxt, nxtv);  // (past the last chunk: staged zeros -- column 0, value 0; no branch around the loads: the counter
-    fetch(c + 3, col_ld, val_ld);  //  bookkeeping of the compiler stays exact only in straight-line code)
-    rowsum(c - 1);                // (c = 0: an empty range)
-#pragma unroll
-    for (int i = 0; i < PER; ++i) *(double2*)&S.u.p.prod[c & 1][g + G * i][2 * h] = double2{curv[i] * cur[i].x, curv[i] * cur[i].y};
-    if (stager) S.u.p.scol[c & 1][tid] = col_st, S.u.p.sval[c & 1][tid] = val_st;  // (chunk c + 2 takes chunk c's place: read one barrier ago)
-    __syncthreads();
-  };
-  request(0, pv, sv);
-  fetch(2, colA, valA);
-  __syncthreads();  // (trip 0 puts chunk 2 where chunk 0's entries are: every lane has read them first)
-  for (int c = 0; c < nch; c += 2) {
-    trip(c, pv, sv, pvn, svn, colA, valA, colB, valB);
-    if (c + 1 < nch) trip(c + 1, pvn, svn, pv, sv, colB, valB, colA, valA);
-  }
-  if (nch > 0) rowsum(nch - 1);
-}
-
-// the row sums of a block cross over: lane (g, h) -> sums[row][LP] (padded rows), for the epilogue's wave <-> LP, lane <-> row
-template <int K>
-__device__ __forceinline__ void batch_cross_over(BatchShared<K>& S, const double (&s)[BatchGeometry<K>::RU][2])
-{
-  using Geo = BatchGeometry<K>;
-  const int h = threadIdx.x % Geo::KL, g = threadIdx.x / Geo::KL;
-  __syncthreads();  // (the last chunk's products are read)
-#pragma unroll
-  for (int u = 0; u < Geo::RU; ++u) S.u.sums[g + Geo::G * u][2 * h] = s[u][0], S.u.sums[g + Geo::G * u][2 * h + 1] = s[u][1];
-  __syncthreads();
-}
-
-// block_reduce<SumOp, NQ, VW> of the single-LP kernels for every LP: acc[pass][q][v] = the sums of virtual threads lane + 64 v of LP
-// (wave, pass).  VW = 8: the panel kernels' 512 threads; VW = 4: the CSR stream kernels' 256 (row t of a block belongs to thread t mod 256).
-template <int K, int NQ, int VW>
-__device__ __forceinline__ void batch_block_partials(BatchShared<K>& S, const double (&acc)[WaveLps<K>::PASSES][NQ][8], const BatchLp* __restrict__ lp, bool a_side,
-                                                     int W, int w)
-{
-  using WL = WaveLps<K>;
-  static_assert(WL::NSUB <= VW, "a wave owns whole virtual waves");
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, sub = WL::sub(wave);
-#pragma unroll
-  for (int pass = 0; pass < WL::PASSES; ++pass)
-#pragma unroll
-    for (int q = 0; q < NQ; ++q)
-#pragma unroll
-      for (int v = 0; v < VW; ++v)
-        if (v % WL::NSUB == sub) {  // (rows lane + 64 j, j = sub mod NSUB, are this wave's: virtual waves j mod VW)
-          const double r = wave_reduce<SumOp>(acc[pass][q][v]);
-          if (lane == 0) S.red[q][WL::lp(wave, pass)][v] = r;
-        }
-  __syncthreads();
-  if (threadIdx.x < K * NQ) {
-    const int q = threadIdx.x / K, ll = threadIdx.x % K;
-    if (loop_active(lp[ll].ctl)) {
-      double total = S.red[q][ll][0];
-      for (int vw = 1; vw < VW; ++vw) total = total + S.red[q][ll][vw];
-      (a_side ? lp[ll].part_a : lp[ll].part_at)[(size_t)q * W + w] = total;
-    }
-  }
-}
+// (BatchGeometry, BatchShared, batch_block_sums, batch_cross_over, batch_block_partials: batch_common.hpp)
 
 // rows of A for K LPs: y' = proj(y - sigma A xbar), ||dy||^2 partials, the deferred dual averaging (DualEpilogue, pdlp_epilogues.hpp);
 // y' also goes, interleaved, to the vector the column side gathers from
@@ -633,6 +454,10 @@ struct pdlpdev_batch {
     size_t lds = 0;
   } a_side, t_side;
   std::vector<BatchLp> lp_host;  // what lp_dev holds
+  // every member in reflected Halpern mode (kernels_batch_halpern.hip): the second per-LP table, kept current as the first is
+  bool halpern = false;
+  BatchHalpernLp* hl_dev = nullptr;
+  std::vector<BatchHalpernLp> hl_host;
   std::map<int, hipGraphExec_t> graphs;
 };
 
@@ -640,6 +465,8 @@ static BatchLp batch_lp_of(const pdlpdev_ctx* c)
 {
   return BatchLp{c->ctl, c->y[0], c->y[1], c->sumy, c->lo, c->hi, c->x[0], c->x[1], c->aty[0], c->aty[1], c->sumx, c->c, c->lb, c->ub, c->ubd, c->A.part, c->At.part};
 }
+
+static BatchHalpernLp batch_halpern_lp_of(const pdlpdev_ctx* c) { return BatchHalpernLp{c->hal, c->avgx, c->avgy, c->lrx, c->lry, c->lraty}; }
 
 // A reset that gives a member row bounds of its own moves its lo / hi (pdlpdev_reset: copy on change): the table the kernels read
 // follows (the kernels -- and the captured graphs -- take the table's address, not its contents).
@@ -650,13 +477,19 @@ static int batch_refresh_table(pdlpdev_batch* b)
     const BatchLp now = batch_lp_of(b->ctx[l]);
     if (memcmp(&now, &b->lp_host[l], sizeof(BatchLp)) != 0) b->lp_host[l] = now, changed = true;
   }
+  bool hl_changed = false;
+  for (int l = 0; b->halpern && l < b->K; ++l) {
+    const BatchHalpernLp now = batch_halpern_lp_of(b->ctx[l]);
+    if (memcmp(&now, &b->hl_host[l], sizeof(BatchHalpernLp)) != 0) b->hl_host[l] = now, hl_changed = true;
+  }
+  if (hl_changed) HIP_TRY(hipMemcpyAsync(b->hl_dev, b->hl_host.data(), b->K * sizeof(BatchHalpernLp), hipMemcpyHostToDevice, b->stream));
   bool sp_changed = false;  // (the step-size exponents travel by value in the decision kernel's arguments)
   for (int l = 0; l < b->K; ++l)
     if (memcmp(&b->dargs_host[l].sp, &b->ctx[l]->sp, sizeof(pdlpdev_step_params)) != 0) b->dargs_host[l].sp = b->ctx[l]->sp, sp_changed = true;
   if (changed) HIP_TRY(hipMemcpyAsync(b->lp_dev, b->lp_host.data(), b->K * sizeof(BatchLp), hipMemcpyHostToDevice, b->stream));
   if (sp_changed)  // (the attempt graphs carry the POINTER to this table, not its contents: no re-capture)
     HIP_TRY(hipMemcpyAsync(b->dargs_dev, b->dargs_host.data(), b->K * sizeof(pdlpdev_decision_args), hipMemcpyHostToDevice, b->stream));
-  if (changed || sp_changed) HIP_TRY(hipStreamSynchronize(b->stream));
+  if (changed || sp_changed || hl_changed) HIP_TRY(hipStreamSynchronize(b->stream));
   return 0;
 }
 
@@ -664,6 +497,8 @@ static int batch_fetch_ctl(pdlpdev_batch* b)
 {
   for (int l = 0; l < b->K; ++l)
     HIP_TRY(hipMemcpyAsync(b->ctx[l]->ctl_h, b->ctx[l]->ctl, sizeof(pdlpdev_ctl), hipMemcpyDeviceToHost, b->stream));
+  for (int l = 0; b->halpern && l < b->K; ++l)  // (the Halpern scalars come back with the control block: pdlpdev_get_halpern reads hal_h)
+    HIP_TRY(hipMemcpyAsync(b->ctx[l]->hal_h, b->ctx[l]->hal, sizeof(pdlpdev_halpern), hipMemcpyDeviceToHost, b->stream));
   HIP_TRY(hipStreamSynchronize(b->stream));
   return 0;
 }
@@ -689,6 +524,12 @@ static int batch_enqueue_attempt(pdlpdev_batch* b, hipEvent_t* ev = nullptr)
   // per side: the CSR-walking products (panels / CSR stream), or the jagged layout's
   const pdlpdev_batch::Side &A = b->a_side, &T = b->t_side;
   auto jgrid = [](const pdlpdev_batch::Side& S) { return dim3((S.jv.nblk + 7) & ~7); };
+  if (b->halpern) {  // kb_primal as it is (pending_avg stays 0), then the Halpern products and the K decisions (never jagged, never timed here)
+    kb_primal<K><<<pgrid, kBT, 0, s>>>(b->lp_dev, n, b->xK);
+    LAUNCH_CHECK();
+    const BatchProductSide ps{aw, arow0, ap, c0->A.hot.off, c0->A.hot.idx, c0->A.hot.val}, pt{tw, trow0, tp, c0->At.hot.off, c0->At.hot.idx, c0->At.hot.val};
+    return batch_halpern_enqueue_tail(K, s, ps, pt, b->lp_dev, b->hl_dev, b->xK, b->yK);
+  }
   if (ev) {
     JagView ajv = A.jv, tjv = T.jv;
     int aP = A.P, tP = T.P;
@@ -848,8 +689,15 @@ int pdlpdev_batch_create(pdlpdev_batch** out, pdlpdev_ctx** ctx, int K)
         c->At.jag.v.row0 != c0->At.jag.v.row0 || c->A.jag.v.val != c0->A.jag.v.val || c->At.jag.v.val != c0->At.jag.v.val || c->stream != c0->stream)
       return fail(-1, "pdlpdev_batch_create: the contexts do not share one matrix (pdlpdev_clone_shared)");
   }
-  for (int l = 0; l < K; ++l)
-    if (ctx[l]->halpern) return fail(-7, "pdlpdev_batch_create: not eligible (LP %d is in reflected Halpern mode: the lockstep kernels carry the averaging iteration only)", l);
+  // all K in reflected Halpern mode (kernels_batch_halpern.hip) or none; the caller opts in (cuoptamd_settings::halpern_lockstep)
+  int nhalpern = 0;
+  for (int l = 0; l < K; ++l) nhalpern += ctx[l]->halpern ? 1 : 0;
+  if (nhalpern != 0 && nhalpern != K)
+    return fail(-7, "pdlpdev_batch_create: not eligible (the batch mixes %d contexts in reflected Halpern mode with %d in the averaging iteration: a lockstep "
+                    "attempt runs one of the two)", nhalpern, K - nhalpern);
+  const bool halpern = nhalpern == K;
+  for (int l = 0; halpern && l < K; ++l)
+    if (!ctx[l]->hal || !ctx[l]->hal_h || !ctx[l]->lraty) return fail(-1, "pdlpdev_batch_create: LP %d is in reflected Halpern mode without its anchor (pdlpdev_set_halpern)", l);
   if ((int64_t)std::max(c0->m, c0->n) * K >= ((int64_t)1 << 32))
     return fail(-7, "pdlpdev_batch_create: not eligible (the interleaved vectors are addressed with 32-bit element offsets: max(m, n) * K < 2^32)");
   // per side: the row-sum variant of the panels, the CSR stream layout or the jagged layout -- the three whose rows are summed by one lane
@@ -863,6 +711,9 @@ int pdlpdev_batch_create(pdlpdev_batch** out, pdlpdev_ctx** ctx, int K)
     const pdlpdev_ctx::Jag& Jg = M.jag;
     const bool jag = Jg.on, pb = M.pb.on;
     const int nlong = M.nlong;
+    if (jag && halpern)
+      return fail(-7, "pdlpdev_batch_create: not eligible (the %s side is in the jagged layout: the reflected Halpern mode has lockstep products for the "
+                      "row-sum panels and the CSR stream layout only)", M.name);
     if (jag && c0->batch_lanes < K)
       return fail(-7, "pdlpdev_batch_create: not eligible (the %s side is in the jagged layout: lockstep batches of %d LPs on it need a parent created "
                       "with batch_lanes >= %d, cuoptamd_settings::batch_lanes; this one has %d)", M.name, K, K, c0->batch_lanes);
@@ -923,6 +774,7 @@ int pdlpdev_batch_create(pdlpdev_batch** out, pdlpdev_ctx** ctx, int K)
   *out      = b;
   b->K = K, b->device = c0->device, b->stream = c0->stream;
   b->a_side = side[0], b->t_side = side[1];
+  b->halpern = halpern;
   std::vector<BatchLp>& h = b->lp_host;
   h.resize(K);
   std::vector<pdlpdev_decision_args>& dargs = b->dargs_host;
@@ -931,6 +783,7 @@ int pdlpdev_batch_create(pdlpdev_batch** out, pdlpdev_ctx** ctx, int K)
     pdlpdev_ctx* c = ctx[l];
     b->ctx[l]      = c;
     h[l]     = batch_lp_of(c);
+    if (halpern) b->hl_host.push_back(batch_halpern_lp_of(c));
     dargs[l] = pdlpdev_decision_args{c->ctl, c->A.part, side[0].W, c->At.part, side[1].W, c->sp};
     c->batches_alive += 1;
   }
@@ -941,6 +794,10 @@ int pdlpdev_batch_create(pdlpdev_batch** out, pdlpdev_ctx** ctx, int K)
   // everything on the batch's OWN stream (a non-blocking one: work of the null stream -- hipMemset, hipMemcpy -- is not ordered
   // with it, and a memset that the queue scheduler lets wait can land attempts later, in the middle of a product's vectors)
   HIP_TRY(hipMemcpyAsync(b->lp_dev, h.data(), K * sizeof(BatchLp), hipMemcpyHostToDevice, b->stream));
+  if (halpern) {
+    HIP_TRY(hipMalloc((void**)&b->hl_dev, K * sizeof(BatchHalpernLp)));
+    HIP_TRY(hipMemcpyAsync(b->hl_dev, b->hl_host.data(), K * sizeof(BatchHalpernLp), hipMemcpyHostToDevice, b->stream));
+  }
   HIP_TRY(hipMemcpyAsync(b->dargs_dev, dargs.data(), K * sizeof(pdlpdev_decision_args), hipMemcpyHostToDevice, b->stream));
   HIP_TRY(hipMemsetAsync(b->xK, 0, ((size_t)c0->n * K + 64) * sizeof(double), b->stream));
   HIP_TRY(hipMemsetAsync(b->yK, 0, ((size_t)c0->m * K + 64) * sizeof(double), b->stream));
@@ -957,6 +814,7 @@ void pdlpdev_batch_destroy(pdlpdev_batch* b)
   if (b->stream) (void)hipStreamSynchronize(b->stream);
   for (auto& kv : b->graphs) (void)hipGraphExecDestroy(kv.second);
   if (b->lp_dev) (void)hipFree(b->lp_dev);
+  if (b->hl_dev) (void)hipFree(b->hl_dev);
   if (b->dargs_dev) (void)hipFree(b->dargs_dev);
   if (b->xK) (void)hipFree(b->xK);
   if (b->yK) (void)hipFree(b->yK);
@@ -1002,7 +860,8 @@ int pdlpdev_batch_run(pdlpdev_batch* b, const int32_t* targets, pdlpdev_ctl* ctl
       remaining -= chunk;
     }
     TRY(batch_fetch_ctl(b));
-    for (int l = 0; l < K; ++l) {  // (64 rejections in a row leave nothing of a step size: the single loop's rule, per LP)
+    // (64 rejections in a row leave nothing of a step size: the single loop's rule, per LP; a Halpern step is never rejected)
+    for (int l = 0; !b->halpern && l < K; ++l) {
       if (asked[l] == 0) continue;
       pdlpdev_ctx* c = b->ctx[l];
       c->rejected_in_a_row = c->ctl_h->steps_taken == before[l] ? c->rejected_in_a_row + asked[l] : 0;
@@ -1012,7 +871,7 @@ int pdlpdev_batch_run(pdlpdev_batch* b, const int32_t* targets, pdlpdev_ctl* ctl
         LAUNCH_CHECK();
       }
     }
-    TRY(batch_fetch_ctl(b));
+    if (!b->halpern) TRY(batch_fetch_ctl(b));  // (k_set_error may have run; in Halpern mode nothing moved since the fetch above)
     if (++guard > 100000) return fail(-6, "pdlpdev_batch_run: no progress");
   }
   if (ctl)
@@ -1027,6 +886,8 @@ int pdlpdev_batch_run(pdlpdev_batch* b, const int32_t* targets, pdlpdev_ctl* ctl
 int pdlpdev_batch_time_kernels(pdlpdev_batch* b, int reps, double avg_ms[4])
 {
   if (!b || !avg_ms) return fail(-1, "pdlpdev_batch_time_kernels: null argument");
+  if (b->halpern)
+    return fail(-7, "pdlpdev_batch_time_kernels: not for a batch in reflected Halpern mode (it forces the averaging traffic; take the kernel times from a kernel trace)");
   HIP_TRY(hipSetDevice(b->device));
   TRY(batch_refresh_table(b));
   hipStream_t s = b->stream;

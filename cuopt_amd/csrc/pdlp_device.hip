@@ -1,6 +1,7 @@
 #include "pdlp_ctx.hpp"
 #include "pdlp_layouts.hpp"
 #include "pdlp_setup.hpp"
+#include "halpern_decision.hpp"
 
 
 // ================================================================================================
@@ -184,6 +185,7 @@ k_step_stats(int n, int nbg, const pdlpdev_ctl* __restrict__ ctl, const double* 
 }
 
 constexpr int kDecisionThreads = 1024;  // one wide workgroup: every partial is one independent load
+static_assert(kDecisionThreads == kHalpernDecisionThreads, "k_halpern_decision runs halpern_decision_workgroup");
 // Latency is all that matters here (one workgroup on the critical path of every attempt): the control block is
 // read once into registers (uniform -> scalar loads) and written back once, the two pow() of the step-size rule
 // are evaluated by the last wave while the others fetch partials, the sums use DPP lane permutes.
@@ -238,44 +240,7 @@ __global__ void __launch_bounds__(kDecisionThreads)
 k_halpern_decision(pdlpdev_ctl* __restrict__ ctl, pdlpdev_halpern* __restrict__ hal, const double* __restrict__ part_dy, int nb_dy,
                    const double* __restrict__ part_t, int nb_t)
 {
-  __shared__ double red[3 * 16];
-  pdlpdev_ctl lc = *ctl;
-  if (!(lc.error == 0 && lc.steps_taken < lc.target_steps)) return;
-  const int t   = threadIdx.x;
-  double acc[3] = {0.0, 0.0, 0.0};
-#pragma unroll 4
-  for (int i = t; i < nb_dy; i += kDecisionThreads) acc[0] += part_dy[i];
-#pragma unroll 4
-  for (int i = t; i < nb_t; i += kDecisionThreads) {
-    acc[1] += part_t[i];
-    acc[2] += part_t[nb_t + i];
-  }
-  block_sum_fast<3, kDecisionThreads / 64>(acc, red);
-  if (t != 0) return;
-  pdlpdev_halpern lh = *hal;
-  const double dy2 = acc[0], interaction = acc[1], dx2 = acc[2];
-  const double eta = lc.step_size, w = lc.primal_weight;
-  const double r2  = (w / eta) * dx2 + 2.0 * interaction + dy2 / (eta * w);
-  lc.last_interaction = interaction;
-  lc.last_movement    = r2;
-  lc.last_dx2         = dx2;
-  lc.last_dy2         = dy2;
-  lc.attempts += 1;
-  if (!(r2 == r2) || !(r2 < 1.0e100)) {
-    lc.error = 1;
-  } else {
-    const double r = sqrt(dmax(r2, 0.0));
-    lh.r = r, lh.r2 = r2;
-    if (lh.k == 0) lh.r_first = r;
-    lh.r2_min = dmin(lh.r2_min, r2);
-    lh.k += 1;
-    *hal = lh;
-  }
-  lc.k += 1;
-  lc.cur ^= 1;
-  lc.steps_taken += 1;
-  lc.its_since_restart += 1;
-  *ctl = lc;
+  halpern_decision_workgroup(ctl, hal, part_dy, nb_dy, part_t, nb_t);  // (halpern_decision.hpp: shared with the lockstep batch's K decisions)
 }
 __global__ void k_halpern_clear(pdlpdev_halpern* hal)
 {

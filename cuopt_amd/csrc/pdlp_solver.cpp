@@ -838,6 +838,7 @@ void cuoptamd_default_settings(cuoptamd_settings* s)
   s->batch_lanes                      = 0;
   s->halpern_resident                 = 0;
   s->halpern_batch                    = 0;
+  s->halpern_lockstep                 = 0;
 }
 
 // Plain parallel counting sort by column (small matrices, and the fallback of the blocked one below).  Thread t owns a
@@ -1542,7 +1543,8 @@ struct cuoptamd_batch {
   std::vector<cuoptamd_solver*> s;
   pdlpdev_batch* dev = nullptr;          // K <= 16 LPs over ONE matrix in lockstep (kernels_batch.hip), or ...
   pdlpdev_small_batch* small = nullptr;  // ... K resident small LPs, one workgroup each (kernels_resident.hip)
-  bool halpern = false;                  // (a small batch of solvers in reflected Halpern mode: pdlpdev_small_batch_create_halpern)
+  bool halpern = false;                  // every member in reflected Halpern mode: with `small`, K workgroups of the resident loop
+                                         // (pdlpdev_small_batch_create_halpern); with `dev`, the Halpern lockstep batch (halpern_lockstep)
 };
 
 int cuoptamd_solver_clone(cuoptamd_solver* parent, const double* lb, const double* ub, const double* lo, const double* hi,
@@ -1576,14 +1578,39 @@ int cuoptamd_batch_create(cuoptamd_solver** solvers, int K, cuoptamd_batch** out
 {
   if (!solvers || !out || K < 1) return fail(-1, "cuoptamd_batch_create: null argument");
   std::vector<pdlpdev_ctx*> ctx(K);
-  int halpern = 0, opted = 0, first_halpern = -1;
+  int halpern = 0, opted = 0, first_halpern = -1, lockstep = 0, resident = 0;
   for (int l = 0; l < K; ++l) {
     if (!solvers[l] || !solvers[l]->dev) return fail(-1, "cuoptamd_batch_create: null solver");
     if (halpern_mode(solvers[l])) {
       halpern += 1, opted += solvers[l]->S.halpern_batch != 0;
       if (first_halpern < 0) first_halpern = l;
+      int32_t lay[8] = {0};
+      const bool res = pdlpdev_layout_info(solvers[l]->dev, lay) == 0 && lay[0] == 2;  // (the resident one-workgroup loop)
+      resident += res;
+      lockstep += solvers[l]->S.halpern_lockstep != 0 && !res;
     }
     ctx[l] = solvers[l]->dev;
+  }
+  if (halpern > 0 && lockstep > 0 && resident == 0) {
+    // Halpern solvers on the multi-launch path with cuoptamd_settings::halpern_lockstep set: the shared-matrix lockstep batch
+    // (kernels_batch_halpern.hip) iff every member is one
+    if (halpern < K)
+      return fail(-7, "cuoptamd_batch_create: LP %d runs the %s and others the averaging iteration: a batch of both is not available", first_halpern, kHalpernName);
+    if (lockstep < K)
+      return fail(-7, "cuoptamd_batch_create: %d of the %d solvers in %s have halpern_lockstep set and the others not: a lockstep batch needs it "
+                      "on every member", lockstep, K, kHalpernName);
+    if (K > 16) return fail(-7, "cuoptamd_batch_create: a lockstep batch holds 2, 4, 8 or 16 LPs");
+    pdlpdev_batch* dev = nullptr;
+    int rc             = pdlpdev_batch_create(&dev, ctx.data(), K);
+    if (rc != 0) {
+      if (dev) pdlpdev_batch_destroy(dev);
+      return fail(rc, "%s", pdlpdev_last_error());
+    }
+    cuoptamd_batch* b = new cuoptamd_batch();
+    b->K = K, b->dev = dev, b->halpern = true;
+    b->s.assign(solvers, solvers + K);
+    *out = b;
+    return 0;
   }
   if (halpern > 0) {
     // Halpern solvers: K workgroups of the resident loop iff every member is one, resident, with cuoptamd_settings::halpern_batch set
@@ -1600,7 +1627,8 @@ int cuoptamd_batch_create(cuoptamd_solver** solvers, int K, cuoptamd_batch** out
     if (halpern < K && opted > 0)
       return fail(-7, "cuoptamd_batch_create: LP %d runs the %s and others the averaging iteration: a batch of both is not available", first_halpern, kHalpernName);
     return fail(-7, "cuoptamd_batch_create: LP %d runs the %s, which has no lockstep batch (solve them one after the other, or create every "
-                    "member on the resident path with halpern_batch set: K LPs in K workgroups)", first_halpern, kHalpernName);
+                    "member on the resident path with halpern_batch set: K LPs in K workgroups; or, for LPs over one matrix on the multi-launch "
+                    "path, with halpern_lockstep set: the lockstep batch)", first_halpern, kHalpernName);
   }
   // small LPs first: any number of them, any matrices, a workgroup each
   pdlpdev_small_batch* small = nullptr;
@@ -2278,9 +2306,11 @@ int cuoptamd_warm_start_remap(const cuoptamd_warm_start* in, const int32_t* var_
 // nothing was done, the caller solves them independently.
 static constexpr int kNotShared = 12345;
 static thread_local const char* t_batch_solve_path = "";  // cuoptamd_batch_solve_last_path
+// *halpern_lockstep: at least one group advanced as a lockstep batch in reflected Halpern mode (cuoptamd_settings::halpern_lockstep)
 static int shared_matrix_batch_solve(int32_t count, const cuoptamd_lp* lps, const cuoptamd_hyper* hyper, const cuoptamd_settings* settings, int device,
-                                     cuoptamd_result* results, double** x, double** y, double** rc)
+                                     cuoptamd_result* results, double** x, double** y, double** rc, bool* halpern_lockstep)
 {
+  *halpern_lockstep = false;
   const cuoptamd_lp& L0 = lps[0];
   if (L0.m <= 0 || L0.n <= 0 || !L0.offsets || !L0.lb || !L0.ub || !L0.lo || !L0.hi) return kNotShared;
   const size_t nnz = (size_t)L0.offsets[L0.m];
@@ -2336,6 +2366,7 @@ static int shared_matrix_batch_solve(int32_t count, const cuoptamd_lp* lps, cons
       else if (rc_ != 0) return rc_;
     }
     if (b) {
+      if (b->halpern) *halpern_lockstep = true;
       int rc_ = cuoptamd_batch_advance(b, std::numeric_limits<int32_t>::max(), &results[done]);
       cuoptamd_batch_destroy(b);
       if (rc_ != 0) return rc_;
@@ -2430,9 +2461,10 @@ int cuoptamd_batch_solve(int32_t count, const cuoptamd_lp* lps, const cuoptamd_h
   // LPs that share matrix and objective (the MIP heuristics' re-solves: the same A and c under other bounds) go through ONE set-up and
   // advance in lockstep, sixteen, eight or four at a time (cuoptamd_batch_*): each gets, bit for bit, the answer of its own solve
   if (count >= 4 && cuopt_amd::tune_int("shared_batch", 1) != 0) {
-    int rc_ = shared_matrix_batch_solve(count, lps, hyper, settings, device, results, x, y, rc);
+    bool halpern_lockstep = false;
+    int rc_ = shared_matrix_batch_solve(count, lps, hyper, settings, device, results, x, y, rc, &halpern_lockstep);
     if (rc_ != kNotShared) {
-      t_batch_solve_path = "shared_matrix";
+      t_batch_solve_path = halpern_lockstep ? "shared_matrix_halpern" : "shared_matrix";
       return rc_;
     }
   }

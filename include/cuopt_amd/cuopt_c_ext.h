@@ -16,6 +16,10 @@
  *                            K-workgroup batch (cuoptamd_settings::halpern_batch): where several LPs are solved at once
  *                            (cuoptamd_batch_solve, cuoptamd_batch_create) K of them run in K workgroups of one launch, each
  *                            bit for bit as on its own.  A single solve is not changed by it; ignored by the other solver modes.
+ *   CUOPT_AMD_HALPERN_LOCKSTEP  1 / 0 (default 0): under CUOPT_AMD_PDLP_SOLVER_MODE_HALPERN1 on the multi-launch path, LPs that share
+ *                            matrix and objective advance as shared-matrix lockstep batches of 16 / 8 / 4
+ *                            (cuoptamd_settings::halpern_lockstep; cuoptamd_batch_solve, cuoptamd_batch_create), each bit for bit
+ *                            as on its own.  A single cuOptSolve is not changed by it; ignored by the other solver modes.
  * Extra value of CUOPT_PDLP_SOLVER_MODE (constants.h stops at CUOPT_PDLP_SOLVER_MODE_FAST1 = 3):
  *   CUOPT_AMD_PDLP_SOLVER_MODE_HALPERN1 = 4: the restarted reflected Halpern iteration with a constant step size
  *                            (cuoptamd_hyper_preset(4), docs/design/04d_halpern_mode.md).  One GPU; infeasibility detection,
@@ -32,6 +36,7 @@
 #define CUOPT_AMD_SIMPLEX_GRADE "amd_simplex_grade"
 #define CUOPT_AMD_HALPERN_RESIDENT "amd_halpern_resident"
 #define CUOPT_AMD_HALPERN_BATCH "amd_halpern_batch"
+#define CUOPT_AMD_HALPERN_LOCKSTEP "amd_halpern_lockstep"
 #define CUOPT_AMD_PDLP_SOLVER_MODE_HALPERN1 4
 
 #ifdef __cplusplus

@@ -152,6 +152,15 @@ typedef struct cuoptamd_settings {
    * gets, bit for bit, what cuoptamd_solver_advance gives it on its own.  0 (default): refused / solved one after the other, as
    * before.  Ignored when algorithm == 0. */
   int32_t halpern_batch;
+  /* Reflected Halpern mode on the multi-launch path (algorithm == 1, not the resident loop) only: non-zero lets the solver be a member
+   * of a shared-matrix LOCKSTEP batch -- cuoptamd_batch_create accepts 2, 4, 8 or 16 such solvers over one matrix (a parent and its
+   * clones) that ALL have it set, under the eligibility rules of the averaging lockstep batch (both matrices in the row-sum panels or
+   * the CSR stream layout, no row beyond 128 entries; a jagged side is refused, with or without batch_lanes); -7, by name, for a mix of
+   * members with and without it and for a mix of the two iterations.  The K LPs advance through four launches per step, the matrix
+   * is streamed once for all of them; every member gets, bit for bit, what cuoptamd_solver_advance gives it on its own.
+   * cuoptamd_batch_solve then groups LPs that share matrix and objective by 16 / 8 / 4 ("shared_matrix_halpern").  0 (default):
+   * refused / solved one after the other, as before.  Ignored when algorithm == 0, and by a single solve. */
+  int32_t halpern_lockstep;
 } cuoptamd_settings;
 
 /* additional_termination_information_t (pdlp/solver_solution.hpp:63-103) + run statistics */
@@ -241,7 +250,8 @@ const char* cuoptamd_last_error(void);
  * 4 = Halpern1 (CUOPT_AMD_PDLP_SOLVER_MODE_HALPERN1, cuopt_c_ext.h): Stable2's scaling and initial primal weight, algorithm = 1.  A
  * Halpern solver runs on one GPU and refuses, with a message that names the mode: sharded creation, warm-start snapshots,
  * detect_infeasibility, save_best_primal_so_far, first_primal_feasible; cuoptamd_batch_create answers -7 for it unless every member
- * is a resident Halpern solver with cuoptamd_settings::halpern_batch set. */
+ * is a resident Halpern solver with cuoptamd_settings::halpern_batch set (K workgroups of one launch), or every member is a
+ * multi-launch Halpern solver over one matrix with cuoptamd_settings::halpern_lockstep set (the lockstep batch). */
 void cuoptamd_hyper_preset(int mode, cuoptamd_hyper* h);
 void cuoptamd_default_settings(cuoptamd_settings* s);
 
@@ -337,7 +347,9 @@ int cuoptamd_batch_solve(int32_t count, const cuoptamd_lp* lps, const cuoptamd_h
                          cuoptamd_result* results, double** x, double** y, double** rc);
 /* which way the last cuoptamd_batch_solve of this thread took (a static string; "" before the first call): "small" -- the K-workgroup
  * batch of resident LPs --, "small_halpern" -- the same in reflected Halpern mode (cuoptamd_settings::halpern_batch) --,
- * "shared_matrix" -- one set-up, clones, lockstep batches --, "independent" -- a solver per LP on worker threads.  The answers do
+ * "shared_matrix" -- one set-up, clones, lockstep batches (reflected Halpern mode without halpern_lockstep: the clones one after the
+ * other) --, "shared_matrix_halpern" -- the same with at least one group advanced by the Halpern lockstep batch
+ * (cuoptamd_settings::halpern_lockstep) --, "independent" -- a solver per LP on worker threads.  The answers do
  * not tell the ways apart: every one gives each LP the result of its own solve. */
 const char* cuoptamd_batch_solve_last_path(void);
 
