@@ -114,6 +114,18 @@ class SolverSettings(C.Structure):
                 ("batch_lanes", c_int), ("halpern_resident", c_int), ("halpern_batch", c_int), ("halpern_lockstep", c_int)]
 
 
+class SolverSettingsWithRays(SolverSettings):
+    """cuoptamd_settings as the library has it now: SolverSettings (the fields up to halpern_lockstep, whose order and end the
+    interface tests pin) plus what was appended behind them.  ctypes lays a subclass's fields out behind its base's, which is where
+    the C struct has them (the assertion below holds the two against each other); every function that takes a SolverSettings pointer
+    takes this one, and default_settings() makes one."""
+    _fields_ = [("halpern_infeasibility", c_int)]
+
+
+# (no padding at the base's end for the appended field to fall into: the C compiler would put it there, ctypes behind it)
+assert SolverSettingsWithRays.halpern_infeasibility.offset == SolverSettings.halpern_lockstep.offset + C.sizeof(c_int)
+
+
 class Result(C.Structure):
     _fields_ = [("status", c_int), ("steps_taken", c_int), ("attempted_steps", c_int),
                 ("returned_average", c_int), ("num_restarts", c_int), ("num_major_iterations", c_int),
@@ -346,6 +358,11 @@ if hasattr(lib, "pdlpdev_set_halpern"):  # (an older build given through CUOPT_A
     _proto("pdlpdev_spectral_norm", c_int, c_void_p, c_double, c_int, P(c_double), P(c_int))
     _proto("pdlpdev_halpern_restart", c_int, c_void_p, c_double, c_void_p, P(Ctl))
     _proto("pdlpdev_get_halpern", c_int, c_void_p, P(Halpern))
+if hasattr(lib, "cuoptamd_solver_get_ray"):  # (... or no infeasibility detection in that mode)
+    _proto("cuoptamd_solver_get_ray", c_int, c_void_p, c_void_p, c_void_p)
+    _proto("pdlpdev_set_halpern_rays", c_int, c_void_p, c_int)
+    _proto("pdlpdev_halpern_eval_infeasibility", c_int, c_void_p, c_int, c_void_p)
+    _proto("pdlpdev_halpern_get_ray", c_int, c_void_p, c_void_p, c_void_p)
 PDLP_SOLVER_MODE_HALPERN1 = 4  # CUOPT_AMD_PDLP_SOLVER_MODE_HALPERN1 (cuopt_c_ext.h)
 
 # ids of pdlp_device.h
@@ -595,7 +612,7 @@ def hyper_preset(mode=1):
 
 
 def default_settings(**over):
-    s = SolverSettings()
+    s = SolverSettingsWithRays()
     lib.cuoptamd_default_settings(C.byref(s))
     tol = over.pop("tol", None)
     if tol is not None:
@@ -741,6 +758,16 @@ class Solver:
         if rc != 0:
             raise CuOptError(rc, lib.cuoptamd_last_error().decode())
         return x, y, z
+
+    def ray(self):
+        """mode 4 with halpern_infeasibility=1: (dx, dy), the unscaled displacement T(z^k) - z^k of the last ray evaluation -- the
+        certificate (dy: Farkas for PrimalInfeasible; dx: the unbounded direction for DualInfeasible).  CuOptError -7 when the option
+        is off or nothing was evaluated at the present step count."""
+        dx, dy = np.zeros(self.n), np.zeros(self.m)
+        rc = lib.cuoptamd_solver_get_ray(self.handle, _ptr(dx), _ptr(dy))
+        if rc != 0:
+            raise CuOptError(rc, lib.cuoptamd_last_error().decode())
+        return dx, dy
 
     @property
     def device(self):
@@ -1137,6 +1164,21 @@ class Device:
         h = Halpern()
         self._ck(lib.pdlpdev_get_halpern(self.handle, C.byref(h)))
         return dict(r=h.r, r_first=h.r_first, r2=h.r2, r2_min=h.r2_min, k=h.k)
+
+    def set_halpern_rays(self, on=True):
+        self._ck(lib.pdlpdev_set_halpern_rays(self.handle, int(bool(on))))
+
+    def halpern_eval_infeasibility(self, rule_finite=True):
+        """the infeasibility information with the displacement T(z^k) - z^k of the last step as the ray estimate"""
+        out = np.zeros(4)
+        self._ck(lib.pdlpdev_halpern_eval_infeasibility(self.handle, int(rule_finite), _ptr(out)))
+        return dict(zip(["max_primal_ray_infeasibility", "primal_ray_linear_objective",
+                         "max_dual_ray_infeasibility", "dual_ray_linear_objective"], out.tolist()))
+
+    def halpern_ray(self, n, m):
+        dx, dy = np.zeros(int(n)), np.zeros(int(m))
+        self._ck(lib.pdlpdev_halpern_get_ray(self.handle, _ptr(dx), _ptr(dy)))
+        return dx, dy
 
     def download(self, name, count):
         out = np.zeros(int(count))

@@ -74,6 +74,18 @@ __device__ __forceinline__ void resident_halpern_body(const HalpernSmallView& V,
     const double tau = lc.tau, sigma = lc.sigma;
     const HalpernWeights hw(&lh);
     const int par = step & 1;
+    if (lc.steps_taken + 1 >= lc.target_steps) {
+      // the LAST step of the launch: z^k goes where the multi-launch kernels leave it -- the side `cur` selects now, which this step's
+      // flip makes the other one.  The ray pass of the evaluation behind the launch forms T(z^k) - z^k from there (uniform branch).
+      double* xk = lc.cur ? V.x1 : V.x0;
+      double* yk = lc.cur ? V.y1 : V.y0;
+#pragma unroll
+      for (int q = 0; q < Q; ++q) {
+        const int e = t + q * T;
+        if (e < V.n) xk[e] = x[q];
+        if (e < V.m) yk[e] = y[q];
+      }
+    }
     // primal projection (utils.cuh:80-95): x' and the extrapolated point
 #pragma unroll
     for (int q = 0; q < Q; ++q) {
@@ -254,6 +266,44 @@ __device__ __forceinline__ void major_small_halpern_body(const MajorSmallArgs& A
       block_reduce<MaxOp, 1, kMajorThreads / 64>(mx, red);
       if (t == 0) sc[8] = mx[0];
       __syncthreads();
+    }
+  }
+  if (A.want_ray) {
+    // Infeasibility detection: the infeasibility information with the displacement of the last step in the iterate's place
+    // (k_halpern_ray_rows / _cols of pdlp_eval.hip as epilogues).  T(z^k) is what the two passes above evaluated; z^k is in the side
+    // of the ping-pong pairs `cur` does not select.  The scaled displacement goes to linf_n / linf_m for the products to gather
+    // (written here, read behind small_rows' barrier by the same workgroup); prod is free behind the barriers above.
+    __shared__ double rred[6 * kMajorThreads / 64];
+    const int cur    = A.ctl->cur;
+    const double* xk = cur ? A.x0 : A.x1;
+    const double* yk = cur ? A.y0 : A.y1;
+    for (int j = t; j < A.n; j += kMajorThreads) A.linf_n[j] = A.avgx[j] - xk[j];
+    for (int i = t; i < A.m; i += kMajorThreads) A.linf_m[i] = A.avgy[i] - yk[i];
+    __syncthreads();
+    {
+      RayRowsEpilogue e{A.avgy, yk, A.dr, A.lo_u, A.hi_u};
+      double acc[3] = {0.0, 0.0, 0.0};
+      small_rows(A.m, A.a_off, A.a_idx, A.a_val, A.linf_n, prod, e, acc);
+      double mx[2] = {acc[0], acc[1]}, sm[1] = {acc[2]};
+      block_reduce<MaxOp, 2, kMajorThreads / 64>(mx, rred);
+      __syncthreads();
+      block_reduce<SumOp, 1, kMajorThreads / 64>(sm, rred + 2 * (kMajorThreads / 64));
+      if (t == 0) A.sc[kRayRows] = mx[0], A.sc[kRayRows + 1] = mx[1], A.sc[kRayRows + 2] = sm[0];
+      __syncthreads();
+    }
+    {
+      RayColsEpilogue e{A.avgx, xk, A.dc, A.c_u, A.lb_u, A.ub_u, A.rule_finite};
+      double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+      small_rows(A.n, A.at_off, A.at_idx, A.at_val, A.linf_m, prod, e, acc);
+      double mx[4] = {acc[0], acc[1], acc[2], acc[3]}, sm[2] = {acc[4], acc[5]};
+      block_reduce<MaxOp, 4, kMajorThreads / 64>(mx, rred);
+      __syncthreads();
+      block_reduce<SumOp, 2, kMajorThreads / 64>(sm, rred + 4 * (kMajorThreads / 64));
+      if (t == 0) {
+        for (int q = 0; q < 4; ++q) A.sc[kRayCols + q] = mx[q];
+        A.sc[kRayCols + 4] = sm[0], A.sc[kRayCols + 5] = sm[1];
+        A.sc[kRayMark] = (double)A.ctl->steps_taken, A.sc[kRayMark + 1] = A.rule_finite != 0 ? 1.0 : 0.0;
+      }
     }
   }
   if (t == 0) A.sc[63] = 1.0;

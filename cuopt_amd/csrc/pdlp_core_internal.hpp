@@ -17,6 +17,11 @@ void read_major_eval(pdlpdev_ctx* ctx, double* out_current, double* out_average)
 // Halpern mode: the evaluation of T(z^k) (the average slots) alone, results in scal[32 ..), same guard (pdlp_eval.hip)
 int enqueue_halpern_eval(pdlpdev_ctx* ctx, int rc_rule_finite_bounds, double eps_rel_primal, double eps_rel_dual, int guard);
 void launch_restart_current(pdlpdev_ctx* ctx, int g);  // k_restart(CURRENT, scaled distances) -> part_g
+// Halpern mode with pdlpdev_set_halpern_rays: the ray pass behind an evaluation of T(z^k), nothing read back -- raw statistics of the
+// displacement T(z^k) - z^k in scal[kRayRows ..), scal[kRayCols ..), step count and rule in scal[kRayMark ..) (pdlp_eval.hip)
+int enqueue_halpern_ray(pdlpdev_ctx* ctx, int rc_rule_finite_bounds);
+// compute_remaining_stats_kernel on the raw statistics of rows (3) and columns (6) -> the four figures
+void compute_remaining_stats(const double* r, const double* c, double out[4]);
 }
 
 __global__ void __launch_bounds__(kBlock)

@@ -449,6 +449,7 @@ struct pdlpdev_ctx {
   bool halpern = false;
   double* lraty = nullptr;                                  // A^T y of the anchor
   pdlpdev_halpern *hal = nullptr, *hal_h = nullptr;         // device block + pinned mirror (read back with the control block)
+  bool halpern_rays = false;  // pdlpdev_set_halpern_rays: every evaluation of T(z^k) is followed by the ray pass on T(z^k) - z^k
   // multi-GPU
   rccl::comm_t comm = nullptr;  // non-null also marks "sharded mode" when the soft communicator is used
   softcomm::Comm* soft = nullptr;
@@ -596,6 +597,11 @@ constexpr int kGenericBlocks = 1024;
 constexpr int kScalars       = 64;
 constexpr int kCtlSlot       = 48;  // scal[kCtlSlot ..): the control block as pdlpdev_run_period's last kernel copied it (one read-back for both)
 static_assert(kCtlSlot * sizeof(double) + sizeof(pdlpdev_ctl) <= kScalars * sizeof(double), "the control block fits behind the scalars");
+// Halpern mode, the ray pass on T(z^k) - z^k (pdlpdev_halpern_eval_infeasibility): the slots of pdlpdev_eval_infeasibility, which the mode
+// leaves free, on the device (multi-launch path) and in the pinned block the one-workgroup evaluation writes (resident path) alike
+constexpr int kRayRows = 16;  // max homogeneous primal residual, ||dy||_inf, sum B(dy, lo, hi)
+constexpr int kRayCols = 24;  // max homogeneous dual residual, ||rc||_inf, ||dx||_inf, max bound violation, sum B(rc, lb, ub), c . dx
+constexpr int kRayMark = 30;  // the accepted-step count the pass ran at, and its reduced-cost rule (0 / 1)
 // the iterate or the control block changed behind the loop's back
 inline void loop_state_touched(pdlpdev_ctx* c) { c->aty_valid = false, c->ctl_h_current = false; }
 

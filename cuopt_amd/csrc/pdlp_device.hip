@@ -1218,6 +1218,7 @@ int pdlpdev_run_period(pdlpdev_ctx* ctx, int32_t target_steps, const pdlpdev_sma
   if (spare > 0) TRY(enqueue_attempts(ctx, spare));
   if (ctx->halpern) {
     TRY(enqueue_halpern_eval(ctx, rq->rule_finite, rq->eps_p, rq->eps_d, 1));
+    if (ctx->halpern_rays) TRY(enqueue_halpern_ray(ctx, rq->rule_finite));  // (its scalars sit in front of kCtlSlot: the same read-back)
     HIP_TRY(hipMemcpyAsync(ctx->hal_h, ctx->hal, sizeof(pdlpdev_halpern), hipMemcpyDeviceToHost, ctx->stream));
   } else {
     TRY(enqueue_major_eval(ctx, rq->mode, rq->rule_finite, rq->eps_p, rq->eps_d, 1));

@@ -373,6 +373,66 @@ struct EvalDualEpilogue {
   __device__ __forceinline__ void row(int j, double v, double (&acc)[4]) { core.col(j, v, acc); }
 };
 
+// Infeasibility detection in reflected Halpern mode, the one-workgroup evaluation (kernels_resident_halpern.hip): the statistics of
+// k_halpern_ray_rows / k_halpern_ray_cols (pdlp_eval.hip) as epilogues of the two products formed from the scaled displacement
+// T(z^k) - z^k.  t: T(z^k) (the average slot), zk: z^k.  Maxima and sums share one accumulator array; the caller reduces them apart.
+struct RayRowsEpilogue {
+  static constexpr int NQ = 3;
+  const double* __restrict__ t;
+  const double* __restrict__ zk;
+  const double* __restrict__ dr;
+  const double* __restrict__ lo_u;
+  const double* __restrict__ hi_u;
+  // acc: 0 max homogeneous primal residual, 1 ||dy||_inf, 2 sum B(dy, lo, hi)
+  __device__ __forceinline__ void row(int i, double v, double (&acc)[3])
+  {
+    const double d  = dr[i];
+    const double lo = lo_u[i], hi = hi_u[i];
+    const double hl = dfinite(lo) ? 0.0 : lo, hu = dfinite(hi) ? 0.0 : hi;  // zero_if_is_finite
+    const double r  = fabs(violation(v / d, hl, hu));
+    const double yi = (t[i] - zk[i]) * d;
+    acc[0] = r > acc[0] ? r : acc[0];
+    acc[1] = fabs(yi) > acc[1] ? fabs(yi) : acc[1];
+    acc[2] += bound_value_product(yi, lo, hi);
+  }
+};
+struct RayColsEpilogue {
+  static constexpr int NQ = 6;
+  const double* __restrict__ t;
+  const double* __restrict__ zk;
+  const double* __restrict__ dc;
+  const double* __restrict__ c_u;
+  const double* __restrict__ lb_u;
+  const double* __restrict__ ub_u;
+  int rule_finite;
+  // acc: 0 max homogeneous dual residual, 1 ||rc||_inf, 2 ||dx||_inf, 3 max bound violation, 4 sum B(rc, lb, ub), 5 c . dx
+  __device__ __forceinline__ void row(int j, double v, double (&acc)[6])
+  {
+    const double d  = dc[j];
+    const double g  = -1.0 * (v / d);
+    const double xj = (t[j] - zk[j]) * d;
+    const double lb = lb_u[j], ub = ub_u[j];
+    const double bv = g > 0.0 ? lb : ub;
+    double rc;
+    if (g == 0.0)
+      rc = g;
+    else if (rule_finite)
+      rc = dfinite(bv) ? g : 0.0;
+    else
+      rc = fabs(xj - bv) <= fabs(xj) ? g : 0.0;
+    const double rd = fabs(g - rc);
+    double viol     = 0.0;
+    if (dfinite(lb)) viol = dmax(viol, -xj);
+    if (dfinite(ub)) viol = dmax(viol, xj);
+    acc[0] = rd > acc[0] ? rd : acc[0];
+    acc[1] = fabs(rc) > acc[1] ? fabs(rc) : acc[1];
+    acc[2] = fabs(xj) > acc[2] ? fabs(xj) : acc[2];
+    acc[3] = viol > acc[3] ? viol : acc[3];
+    acc[4] += bound_value_product(rc, lb, ub);
+    acc[5] += c_u[j] * xj;
+  }
+};
+
 // ---- dense row segments: index-free storage (pdlpdev_ctx::Dense) ---------------------------------------------------------
 struct DenseView {
   const int32_t* __restrict__ row;

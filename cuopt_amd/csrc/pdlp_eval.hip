@@ -140,6 +140,103 @@ k_infeas_cols(int n, int nbg, const pdlpdev_ctl* __restrict__ ctl, int which, co
 }
 
 
+// ---- infeasibility detection in reflected Halpern mode (docs/design/04d_halpern_mode.md, "Infeasibility detection"): the ray estimate is
+// the displacement of the last step, T(z^k) - z^k.  T(z^k) is in the average slots; z^k in the side of the ping-pong pairs that `cur`
+// does NOT select (the step kernels wrote z^{k+1} to the other side and never touched it).
+// the SCALED displacement (the products below are formed from it: on a diverging solve A^T y' and A^T y^k grow, their difference does not)
+__global__ void __launch_bounds__(kBlock)
+k_halpern_ray_diff(int n, int m, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ x0, const double* __restrict__ x1,
+                   const double* __restrict__ y0, const double* __restrict__ y1, const double* __restrict__ avgx,
+                   const double* __restrict__ avgy, double* __restrict__ dx, double* __restrict__ dy)
+{
+  const int cur = ctl->cur;
+  const double* __restrict__ xk = cur ? x0 : x1;
+  const double* __restrict__ yk = cur ? y0 : y1;
+  const int tot = n > m ? n : m;
+  for (int i = blockIdx.x * kBlock + threadIdx.x; i < tot; i += gridDim.x * kBlock) {
+    if (i < n) dx[i] = avgx[i] - xk[i];
+    if (i < m) dy[i] = avgy[i] - yk[i];
+  }
+}
+// k_infeas_rows' statistics with the unscaled ray: (A dx_u)_i = (A^ dx^)_i / D_r,i and dy_u,i = dy^_i D_r,i
+__global__ void __launch_bounds__(kBlock)
+k_halpern_ray_rows(int m, int nbg, const double* __restrict__ a_dx, const double* __restrict__ dy, const double* __restrict__ dr,
+                   const double* __restrict__ lo_u, const double* __restrict__ hi_u, double* __restrict__ part)
+{
+  __shared__ double red[12];
+  double mx[2] = {0.0, 0.0}, sm[1] = {0.0};
+  for (int i = blockIdx.x * kBlock + threadIdx.x; i < m; i += gridDim.x * kBlock) {
+    const double d  = dr[i];
+    const double lo = lo_u[i], hi = hi_u[i];
+    const double hl = dfinite(lo) ? 0.0 : lo, hu = dfinite(hi) ? 0.0 : hi;  // zero_if_is_finite
+    const double r  = fabs(violation(a_dx[i] / d, hl, hu));
+    const double yi = dy[i] * d;
+    mx[0] = r > mx[0] ? r : mx[0];
+    mx[1] = fabs(yi) > mx[1] ? fabs(yi) : mx[1];
+    sm[0] += bound_value_product(yi, lo, hi);
+  }
+  block_reduce<MaxOp, 2>(mx, red);
+  __syncthreads();
+  block_reduce<SumOp, 1>(sm, red + 8);
+  if (threadIdx.x == 0) {
+    part[blockIdx.x]           = mx[0];
+    part[nbg + blockIdx.x]     = mx[1];
+    part[2 * nbg + blockIdx.x] = sm[0];
+  }
+}
+// k_infeas_cols' statistics likewise: (A^T dy_u)_j = (A^T^ dy^)_j / D_c,j and dx_u,j = dx^_j D_c,j; both reduced-cost rules look at the
+// ray's own x.  mark (two doubles): the accepted-step count the pass belongs to and its rule, for the host to recognise the figures by.
+__global__ void __launch_bounds__(kBlock)
+k_halpern_ray_cols(int n, int nbg, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ at_dy, const double* __restrict__ dx,
+                   const double* __restrict__ dc, const double* __restrict__ c_u, const double* __restrict__ lb_u,
+                   const double* __restrict__ ub_u, int rule_finite, double* __restrict__ part, double* __restrict__ mark)
+{
+  __shared__ double red[28];
+  if (blockIdx.x == 0 && threadIdx.x == 0) mark[0] = (double)ctl->steps_taken, mark[1] = (double)rule_finite;
+  double mx[4] = {0.0, 0.0, 0.0, 0.0}, sm[2] = {0.0, 0.0};
+  for (int j = blockIdx.x * kBlock + threadIdx.x; j < n; j += gridDim.x * kBlock) {
+    const double d  = dc[j];
+    const double g  = -1.0 * (at_dy[j] / d);
+    const double xj = dx[j] * d;
+    const double lb = lb_u[j], ub = ub_u[j];
+    const double bv = g > 0.0 ? lb : ub;
+    double rc;
+    if (g == 0.0)
+      rc = g;
+    else if (rule_finite)
+      rc = dfinite(bv) ? g : 0.0;
+    else
+      rc = fabs(xj - bv) <= fabs(xj) ? g : 0.0;
+    const double rd = fabs(g - rc);
+    double viol     = 0.0;  // max_violation, utils.cuh:181-193
+    if (dfinite(lb)) viol = dmax(viol, -xj);
+    if (dfinite(ub)) viol = dmax(viol, xj);
+    mx[0] = rd > mx[0] ? rd : mx[0];
+    mx[1] = fabs(rc) > mx[1] ? fabs(rc) : mx[1];
+    mx[2] = fabs(xj) > mx[2] ? fabs(xj) : mx[2];
+    mx[3] = viol > mx[3] ? viol : mx[3];
+    sm[0] += bound_value_product(rc, lb, ub);
+    sm[1] += c_u[j] * xj;
+  }
+  block_reduce<MaxOp, 4>(mx, red);
+  __syncthreads();
+  block_reduce<SumOp, 2>(sm, red + 16);
+  if (threadIdx.x == 0) {
+    for (int q = 0; q < 4; ++q) part[(size_t)q * nbg + blockIdx.x] = mx[q];
+    part[(size_t)4 * nbg + blockIdx.x] = sm[0];
+    part[(size_t)5 * nbg + blockIdx.x] = sm[1];
+  }
+}
+// the unscaled displacement for the caller (pdlpdev_halpern_get_ray)
+__global__ void __launch_bounds__(kBlock)
+k_halpern_ray_unscaled(int n, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ v0, const double* __restrict__ v1,
+                       const double* __restrict__ t, const double* __restrict__ d, double* __restrict__ out)
+{
+  const int cur = ctl->cur;
+  const double* __restrict__ vk = cur ? v0 : v1;
+  for (int i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) out[i] = (t[i] - vk[i]) * d[i];
+}
+
 // ---- trust-region restart support (Methodical1) -------------------------------------------------------
 // Virtual element k of the joint vector z = (x, y) of the UNSCALED problem at point `which`:
 //   k <  n : center x_k, objective g_k = c_k - (A^T y)_k, bounds [lb, ub], weight wp
@@ -430,6 +527,7 @@ int pdlpdev_major_eval(pdlpdev_ctx* ctx, int average_mode, int rc_rule_finite_bo
       TRY(resident_halpern_eval(ctx, rc_rule_finite_bounds, want_linf ? 1 : 0, eps_rel_primal, eps_rel_dual));
     } else {
       TRY(enqueue_halpern_eval(ctx, rc_rule_finite_bounds, eps_rel_primal, eps_rel_dual, 0));
+      if (ctx->halpern_rays) TRY(enqueue_halpern_ray(ctx, rc_rule_finite_bounds));  // (scal[16..32): inside the read-back below)
       TRY(fetch_scalars(ctx, 41));
       ctx->stat_loop_syncs += 1;
     }
@@ -501,9 +599,13 @@ int pdlpdev_eval_infeasibility(pdlpdev_ctx* ctx, int which, int rc_rule_finite_b
   LAUNCH_CHECK();
   HIP_TRY(hipMemcpyAsync(ctx->scal_h + 16, ctx->scal + 16, 16 * sizeof(double), hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
-  const double* r = ctx->scal_h + 16;  // max hom. primal residual, ||y||_inf, sum B(y)
-  const double* c = ctx->scal_h + 24;  // max hom. dual residual, ||rc||_inf, ||x||_inf, max violation, sum B(rc), c.x
-  // compute_remaining_stats_kernel, infeasibility_information.cu:115-172
+  compute_remaining_stats(ctx->scal_h + 16, ctx->scal_h + 24, out);
+  return 0;
+}
+// r: max hom. primal residual, ||y||_inf, sum B(y);  c: max hom. dual residual, ||rc||_inf, ||x||_inf, max violation, sum B(rc), c.x
+// (compute_remaining_stats_kernel, infeasibility_information.cu:115-172)
+void compute_remaining_stats(const double* r, const double* c, double out[4])
+{
   double max_primal = r[0], primal_obj = c[2] == 0.0 ? 0.0 : c[5] * (1.0 / c[2]);
   double max_dual = c[0], dual_obj = r[2] + c[4];
   const double scaling = std::max(r[1], c[1]);
@@ -519,6 +621,84 @@ int pdlpdev_eval_infeasibility(pdlpdev_ctx* ctx, int which, int rc_rule_finite_b
     max_primal = 0.0, primal_obj = 0.0;
   }
   out[0] = max_primal, out[1] = primal_obj, out[2] = max_dual, out[3] = dual_obj;
+}
+
+// ---- infeasibility detection in Halpern mode: the ray pass ------------------------------------------------------------------------
+// Vectors that are free between runs: the scaled displacement goes to tmp_n / tmp_m (the l-infinity residuals of an evaluation are
+// reduced before this pass starts), the two products -- the layout's own plain ones, formed FROM the displacement -- to
+// ax_u / aty_u[PDLPDEV_CURRENT] (the mode evaluates the average slots only).  Raw statistics in scal[kRayRows ..), scal[kRayCols ..),
+// the step count and the rule in scal[kRayMark ..); nothing is read back.
+int enqueue_halpern_ray(pdlpdev_ctx* ctx, int rc_rule_finite_bounds)
+{
+  hipStream_t s = ctx->stream;
+  const int n = ctx->n, m = ctx->m;
+  double *dx = ctx->tmp_n, *dy = ctx->tmp_m, *a_dx = ctx->ax_u[PDLPDEV_CURRENT], *at_dy = ctx->aty_u[PDLPDEV_CURRENT];
+  k_halpern_ray_diff<<<grid_for(std::max(n, m)), kBlock, 0, s>>>(n, m, ctx->ctl, ctx->x[0], ctx->x[1], ctx->y[0], ctx->y[1], ctx->avgx, ctx->avgy, dx, dy);
+  launch_plain(ctx, 0, dx, a_dx);
+  launch_plain(ctx, 1, dy, at_dy);
+  const int gr = std::min(grid_for(m), kGenericBlocks), gc = std::min(grid_for(n), kGenericBlocks);
+  double* part_rows = ctx->part_g;             // 3 * gr
+  double* part_cols = ctx->part_g + 3 * 2048;  // 6 * gc  (part_g holds 8 * 2048)
+  k_halpern_ray_rows<<<gr, kBlock, 0, s>>>(m, gr, a_dx, dy, ctx->dr, ctx->lo_u, ctx->hi_u, part_rows);
+  k_finalize<<<1, kBlock, 0, s>>>(part_rows, gr, 3, 0x3u, ctx->scal + kRayRows);
+  k_halpern_ray_cols<<<gc, kBlock, 0, s>>>(n, gc, ctx->ctl, at_dy, dx, ctx->dc, ctx->c_u, ctx->lb_u, ctx->ub_u, rc_rule_finite_bounds != 0, part_cols, ctx->scal + kRayMark);
+  k_finalize<<<1, kBlock, 0, s>>>(part_cols, gc, 6, 0xFu, ctx->scal + kRayCols);
+  LAUNCH_CHECK();
+  return 0;
+}
+int pdlpdev_set_halpern_rays(pdlpdev_ctx* ctx, int on)
+{
+  HIP_TRY(hipSetDevice(ctx->device));
+  if (on && !ctx->halpern) return fail(-7, "pdlpdev_set_halpern_rays: the context is not in Halpern mode");
+  ctx->halpern_rays = on != 0;
+  // whatever an earlier solve left is no ray of this one: no step count equals a NaN
+  ctx->scal_h[kRayMark] = ctx->scal_h[kRayMark + 1] = __builtin_nan("");
+  HIP_TRY(hipMemsetAsync(ctx->scal + kRayMark, 0xFF, 2 * sizeof(double), ctx->stream));
+  return 0;
+}
+int pdlpdev_halpern_eval_infeasibility(pdlpdev_ctx* ctx, int rc_rule_finite_bounds, double out[4])
+{
+  HIP_TRY(hipSetDevice(ctx->device));
+  if (!ctx->halpern) return fail(-7, "pdlpdev_halpern_eval_infeasibility: the context is not in Halpern mode");
+  if (!ctx->ctl_h_current) {
+    TRY(fetch_ctl(ctx, nullptr));
+    ctx->stat_loop_syncs += 1;
+  }
+  const int steps = ctx->ctl_h->steps_taken;
+  if (steps < 1) return fail(-7, "pdlpdev_halpern_eval_infeasibility: no step has been taken: there is no displacement yet");
+  const double rule = rc_rule_finite_bounds != 0 ? 1.0 : 0.0;
+  const double* h   = ctx->scal_h;
+  // (an evaluation of T(z^k) with the rays switched on left the pass behind it, read back with its own synchronisation)
+  const bool fresh = ctx->halpern_rays && h[kRayMark] == (double)steps && h[kRayMark + 1] == rule;
+  if (!fresh) {
+    TRY(enqueue_halpern_ray(ctx, rc_rule_finite_bounds));
+    HIP_TRY(hipMemcpyAsync(ctx->scal_h + kRayRows, ctx->scal + kRayRows, (kRayMark + 2 - kRayRows) * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    ctx->stat_loop_syncs += 1;
+  }
+  compute_remaining_stats(h + kRayRows, h + kRayCols, out);
+  return 0;
+}
+int pdlpdev_halpern_get_ray(pdlpdev_ctx* ctx, double* dx, double* dy)
+{
+  HIP_TRY(hipSetDevice(ctx->device));
+  if (!ctx->halpern) return fail(-7, "pdlpdev_halpern_get_ray: the context is not in Halpern mode");
+  TRY(fetch_ctl(ctx, nullptr));
+  const int steps = ctx->ctl_h->steps_taken;
+  if (steps < 1 || !(ctx->scal_h[kRayMark] == (double)steps))
+    return fail(-7, "pdlpdev_halpern_get_ray: no ray was evaluated at the present step count (%d)", steps);
+  // both ends of the displacement are where the evaluation found them: nothing has stepped since
+  hipStream_t s = ctx->stream;
+  if (dx) {
+    k_halpern_ray_unscaled<<<grid_for(ctx->n), kBlock, 0, s>>>(ctx->n, ctx->ctl, ctx->x[0], ctx->x[1], ctx->avgx, ctx->dc, ctx->tmp_n);
+    HIP_TRY(hipMemcpyAsync(dx, ctx->tmp_n, (size_t)ctx->n * sizeof(double), hipMemcpyDeviceToHost, s));
+  }
+  if (dy) {
+    k_halpern_ray_unscaled<<<grid_for(ctx->m), kBlock, 0, s>>>(ctx->m, ctx->ctl, ctx->y[0], ctx->y[1], ctx->avgy, ctx->dr, ctx->tmp_m);
+    HIP_TRY(hipMemcpyAsync(dy, ctx->tmp_m, (size_t)ctx->m * sizeof(double), hipMemcpyDeviceToHost, s));
+  }
+  LAUNCH_CHECK();
+  HIP_TRY(hipStreamSynchronize(s));
   return 0;
 }
 

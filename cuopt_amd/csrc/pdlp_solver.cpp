@@ -667,13 +667,22 @@ const char* halpern_refused_setting(const cuoptamd_settings* st)
 // The head: everything of the major iteration that needs no device call of its own once T(z^k) is evaluated (ev_t) -- the verdict, the
 // acceptance set, the limits, the three restart tests.  *restart: the caller restarts the iteration on the device
 // (pdlpdev_halpern_restart for one LP, pdlpdev_small_batch_halpern_restart for the LPs of a batch) and calls halpern_restart_done.
-int halpern_major_head(cuoptamd_solver* s, const double* ev_t, bool* terminated, bool* restart_out)
+// ray: the four figures of the infeasibility information with the displacement T(z^k) - z^k of the period's last step in the
+// iterate's place (cuoptamd_settings::halpern_infeasibility; pdlpdev_halpern_eval_infeasibility), or null when the option is off.
+// They are looked at whether or not T(z^k) is primal feasible -- the iterates of an unbounded LP are, and the ray does not depend on
+// the point -- behind Optimal and the step error, in front of the limits.
+int halpern_major_head(cuoptamd_solver* s, const double* ev_t, const double* ray, bool* terminated, bool* restart_out)
 {
   const cuoptamd_hyper& H = s->H;
   *terminated             = false;
   *restart_out            = false;
   s->result.num_major_iterations += 1;
   s->conv_average = to_convergence(s, ev_t);
+  if (ray) {
+    std::copy(ray, ray + 4, s->conv_average.infeasibility);
+    s->result.max_primal_ray_infeasibility = ray[0], s->result.primal_ray_linear_objective = ray[1];  // (also while the solve goes on)
+    s->result.max_dual_ray_infeasibility = ray[2], s->result.dual_ray_linear_objective = ray[3];
+  }
   s->conv_current = s->conv_average;
   const int t     = verdict(s, s->conv_average);
   bool done = false;
@@ -685,6 +694,12 @@ int halpern_major_head(cuoptamd_solver* s, const double* ev_t, bool* terminated,
       s->result.returned_average = 0;
       *terminated                = true;
       return 0;
+    }
+    if (!done && ray) {  // termination_strategy.cu:228-249 on the displacement
+      if (ray[3] > 0.0 && ray[2] / ray[3] <= s->S.primal_infeasible_tolerance)
+        done = true, status = kPrimalInfeasible;
+      else if (ray[1] < 0.0 && ray[0] / -ray[1] <= s->S.dual_infeasible_tolerance)
+        done = true, status = kDualInfeasible;
     }
   }
   if (!done && s->S.accept_enabled && !s->have_accepted && s->total_iterations > 1 && accepted_by_looser(s, s->conv_average)) {
@@ -731,8 +746,12 @@ int halpern_major_iteration(cuoptamd_solver* s, bool* terminated)
     DEV(pdlpdev_major_eval(dev, 0, rq.rule_finite, rq.eps_p, rq.eps_d, ev, ev_t));
   }
   s->fused_eval_ready = false;
+  // (the ray pass ran behind the evaluation, whichever path that took: its figures are on the host already)
+  double ray[4];
+  const bool want_ray = s->S.halpern_infeasibility != 0 && !s->step_error;
+  if (want_ray) DEV(pdlpdev_halpern_eval_infeasibility(dev, rq.rule_finite, ray));
   bool restart = false;
-  int rc       = halpern_major_head(s, ev_t, terminated, &restart);
+  int rc       = halpern_major_head(s, ev_t, want_ray ? ray : nullptr, terminated, &restart);
   if (rc != 0 || *terminated || !restart) return rc;
   double dist[2];
   DEV(pdlpdev_halpern_restart(dev, s->H.primal_weight_update_smoothing, dist, &s->ctl));
@@ -839,6 +858,7 @@ void cuoptamd_default_settings(cuoptamd_settings* s)
   s->halpern_resident                 = 0;
   s->halpern_batch                    = 0;
   s->halpern_lockstep                 = 0;
+  s->halpern_infeasibility            = 0;
 }
 
 // Plain parallel counting sort by column (small matrices, and the fallback of the blocked one below).  Thread t owns a
@@ -996,7 +1016,11 @@ static int start_run(cuoptamd_solver* s, const double* init_x, const double* ini
   // set_relative_{primal,dual}_tolerance_factor (pdlp.cu:209-231): the caller's ||b|| / ||c|| for the termination rule
   if (settings->relative_primal_tolerance_factor >= 0.0) s->norm_b = settings->relative_primal_tolerance_factor;
   if (settings->relative_dual_tolerance_factor >= 0.0) s->norm_c = settings->relative_dual_tolerance_factor;
-  if (halpern_mode(s)) DEV(pdlpdev_set_halpern(s->dev, 1));  // (a fresh context or a clone; a context that is reset keeps the mode)
+  if (halpern_mode(s)) {
+    DEV(pdlpdev_set_halpern(s->dev, 1));  // (a fresh context or a clone; a context that is reset keeps the mode)
+    // cuoptamd_settings::halpern_infeasibility: every evaluation of T(z^k) brings the ray pass on T(z^k) - z^k with it
+    DEV(pdlpdev_set_halpern_rays(s->dev, settings->halpern_infeasibility != 0));
+  }
   double step = s->computed_step, weight = s->computed_weight;
   if (settings->initial_step_size >= 0.0) step = settings->initial_step_size;  // pdlp.cu:1014-1021
   if (settings->initial_primal_weight >= 0.0) weight = settings->initial_primal_weight;
@@ -1098,7 +1122,9 @@ int cuoptamd_solver_create(cuoptamd_solver** out, const cuoptamd_lp* lp, const c
   if (hyper->algorithm == 1) {
     // what the mode does not have is refused by name, not ignored
     if (world > 1 || comm_id != nullptr) return fail(-7, "%s: sharded solvers (world > 1, a communicator) are not supported", kHalpernName);
-    if (settings->detect_infeasibility) return fail(-7, "%s: detect_infeasibility is not supported (the rays of the averaging iteration are not formed)", kHalpernName);
+    if (settings->detect_infeasibility)
+      return fail(-7, "%s: detect_infeasibility is not supported (the rays of the averaging iteration are not formed; halpern_infeasibility "
+                      "switches on the mode's own detection, on the displacement of a step)", kHalpernName);
     if (settings->save_best_primal_so_far) return fail(-7, "%s: save_best_primal_so_far is not supported", kHalpernName);
     if (settings->first_primal_feasible) return fail(-7, "%s: first_primal_feasible is not supported", kHalpernName);
     if (const char* bad = halpern_meaningless_setting(hyper, settings)) return fail(-7, "%s: %s has no meaning in this mode and is not accepted", kHalpernName, bad);
@@ -1600,6 +1626,9 @@ int cuoptamd_batch_create(cuoptamd_solver** solvers, int K, cuoptamd_batch** out
       return fail(-7, "cuoptamd_batch_create: %d of the %d solvers in %s have halpern_lockstep set and the others not: a lockstep batch needs it "
                       "on every member", lockstep, K, kHalpernName);
     if (K > 16) return fail(-7, "cuoptamd_batch_create: a lockstep batch holds 2, 4, 8 or 16 LPs");
+    for (int l = 0; l < K; ++l)  // (the K-wide products have no ray pass: such LPs run one after the other)
+      if (solvers[l]->S.halpern_infeasibility)
+        return fail(-7, "cuoptamd_batch_create: LP %d has halpern_infeasibility set: the lockstep batch of the %s does not detect infeasibility", l, kHalpernName);
     pdlpdev_batch* dev = nullptr;
     int rc             = pdlpdev_batch_create(&dev, ctx.data(), K);
     if (rc != 0) {
@@ -1785,7 +1814,14 @@ static int halpern_small_batch_advance(cuoptamd_batch* b, const std::vector<int3
         restart[l] = 0, theta[l] = -1.0;
         if (!due[l]) continue;
         bool terminated = false, again = false;
-        rc = halpern_major_head(b->s[l], &ev_t[(size_t)l * PDLPDEV_EV_COUNT], &terminated, &again);
+        // (halpern_infeasibility: the evaluation kernel left the ray pass's statistics in this LP's pinned block -- no launch here)
+        double ray[4];
+        const bool want_ray = b->s[l]->S.halpern_infeasibility != 0 && !b->s[l]->step_error;
+        if (want_ray) {
+          rc = pdlpdev_halpern_eval_infeasibility(b->s[l]->dev, major_eval_request(b->s[l]).rule_finite, ray);
+          if (rc != 0) return fail(rc, "pdlpdev_halpern_eval_infeasibility: %s", pdlpdev_last_error());
+        }
+        rc = halpern_major_head(b->s[l], &ev_t[(size_t)l * PDLPDEV_EV_COUNT], want_ray ? ray : nullptr, &terminated, &again);
         if (rc != 0) return rc;
         major_was_done(b->s[l], terminated);
         if (terminated) done[l] = 1;
@@ -2018,6 +2054,22 @@ int cuoptamd_solver_get_solution(cuoptamd_solver* s, double* x, double* y, doubl
   if (x) cuoptamd_solver::to_caller_order(s->col_new2old, tx.data(), x, 0, (size_t)s->n);
   if (rc) cuoptamd_solver::to_caller_order(s->col_new2old, trc.data(), rc, 0, (size_t)s->n);
   if (y) cuoptamd_solver::to_caller_order(s->row_new2old, ty.data(), y, (size_t)s->row_begin, (size_t)s->row_end);
+  return 0;
+}
+
+int cuoptamd_solver_get_ray(cuoptamd_solver* s, double* dx, double* dy)
+{
+  if (!s) return fail(-1, "null solver");
+  if (!halpern_mode(s) || !s->S.halpern_infeasibility || s->empty_problem || !s->dev)
+    return fail(-7, "cuoptamd_solver_get_ray: needs the %s with halpern_infeasibility set", kHalpernName);
+  if (s->row_new2old.empty()) {
+    DEV(pdlpdev_halpern_get_ray(s->dev, dx, dy));
+    return 0;
+  }
+  std::vector<double> tx(dx ? (size_t)s->n : 0), ty(dy ? (size_t)s->m_global : 0);  // the device's order -> the caller's
+  DEV(pdlpdev_halpern_get_ray(s->dev, dx ? tx.data() : nullptr, dy ? ty.data() : nullptr));
+  if (dx) cuoptamd_solver::to_caller_order(s->col_new2old, tx.data(), dx, 0, (size_t)s->n);
+  if (dy) cuoptamd_solver::to_caller_order(s->row_new2old, ty.data(), dy, 0, (size_t)s->m_global);
   return 0;
 }
 

@@ -41,6 +41,12 @@ struct MajorSmallArgs {
   double* sc;  // current at sc[0..9), average at sc[32..41)  (pinned host memory: no read-back copy)
   int guard_target = -1;  // >= 0 (evaluation enqueued right behind the attempts of a small-LP batch): only if the attempts reached this
                           // accepted-step count or raised the step-size error -- i.e. only if a major iteration is what comes next
+  int want_ray = 0;       // mode 3 only (pdlpdev_set_halpern_rays): behind the two passes, the infeasibility information of the displacement
+                          // T(z^k) - z^k -- the average slots minus the side of (x0, x1) / (y0, y1) that ctl->cur does not select, where the
+                          // loop stored z^k before its last step.  linf_n / linf_m hold the scaled displacement (free behind the l-infinity
+                          // reductions).  Raw statistics into free slots of the pinned block below sc[63]: the three of the rows at
+                          // sc[kRayRows ..), the six of the columns at sc[kRayCols ..), the step count and the rule at sc[kRayMark ..)
+                          // (pdlp_ctx.hpp; sc[16 .. 32) is pdlpdev_eval_infeasibility's, which this mode never calls)
 };
 constexpr int kMajorThreads = 1024;
 // M vec for a matrix of <= 8192 nonzeros: all products in parallel into LDS, then every row is added up left to
@@ -57,12 +63,14 @@ __device__ __forceinline__ void small_rows(int rows, const int32_t* __restrict__
 }
 inline MajorSmallArgs major_args(const pdlpdev_ctx* ctx, int average_mode, int rc_rule_finite_bounds, int want_linf, double eps_rel_primal, double eps_rel_dual)
 {
-  return MajorSmallArgs{ctx->m, ctx->n, average_mode, rc_rule_finite_bounds, want_linf, eps_rel_primal, eps_rel_dual,
+  MajorSmallArgs A{ctx->m, ctx->n, average_mode, rc_rule_finite_bounds, want_linf, eps_rel_primal, eps_rel_dual,
                         ctx->A.full.off, ctx->A.full.idx, ctx->At.full.off, ctx->At.full.idx, ctx->A.full.val, ctx->At.full.val, ctx->ctl,
                         ctx->x[0], ctx->x[1], ctx->y[0], ctx->y[1], ctx->sumx, ctx->sumy, ctx->avgx, ctx->avgy,
                         ctx->dr, ctx->dc, ctx->c_u, ctx->lb_u, ctx->ub_u, ctx->lo_u, ctx->hi_u, ctx->tmp_m, ctx->tmp_n,
                         ctx->ax_u[PDLPDEV_CURRENT], ctx->ax_u[PDLPDEV_AVERAGE], ctx->aty_u[PDLPDEV_CURRENT],
                         ctx->aty_u[PDLPDEV_AVERAGE], ctx->rc[0], ctx->rc[1], ctx->scal_h};
+  A.want_ray = average_mode == 3 && ctx->halpern && ctx->halpern_rays;
+  return A;
 }
 
 // ---- the reflected-Halpern loop (kernels_resident_halpern.hip); the records of a Halpern small-LP batch sit in the batch object's

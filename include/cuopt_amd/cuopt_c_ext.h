@@ -20,9 +20,14 @@
  *                            matrix and objective advance as shared-matrix lockstep batches of 16 / 8 / 4
  *                            (cuoptamd_settings::halpern_lockstep; cuoptamd_batch_solve, cuoptamd_batch_create), each bit for bit
  *                            as on its own.  A single cuOptSolve is not changed by it; ignored by the other solver modes.
+ *   CUOPT_AMD_HALPERN_INFEASIBILITY  1 / 0 (default 0): under CUOPT_AMD_PDLP_SOLVER_MODE_HALPERN1, infeasibility detection on the
+ *                            displacement of a step (cuoptamd_settings::halpern_infeasibility): an infeasible LP ends as
+ *                            PrimalInfeasible, an unbounded one as DualInfeasible, at CUOPT_PRIMAL_INFEASIBLE_TOLERANCE /
+ *                            CUOPT_DUAL_INFEASIBLE_TOLERANCE, instead of at its iteration or time limit.  CUOPT_INFEASIBILITY_DETECTION
+ *                            (the averaging iteration's) stays a validation error under that mode; ignored by the other modes.
  * Extra value of CUOPT_PDLP_SOLVER_MODE (constants.h stops at CUOPT_PDLP_SOLVER_MODE_FAST1 = 3):
  *   CUOPT_AMD_PDLP_SOLVER_MODE_HALPERN1 = 4: the restarted reflected Halpern iteration with a constant step size
- *                            (cuoptamd_hyper_preset(4), docs/design/04d_halpern_mode.md).  One GPU; infeasibility detection,
+ *                            (cuoptamd_hyper_preset(4), docs/design/04d_halpern_mode.md).  One GPU; CUOPT_INFEASIBILITY_DETECTION,
  *                            save_best_primal_so_far and first_primal_feasible are refused with a validation error, and the
  *                            simplex-grade emulation leaves the infeasibility detection it would switch on off.
  */
@@ -37,6 +42,7 @@
 #define CUOPT_AMD_HALPERN_RESIDENT "amd_halpern_resident"
 #define CUOPT_AMD_HALPERN_BATCH "amd_halpern_batch"
 #define CUOPT_AMD_HALPERN_LOCKSTEP "amd_halpern_lockstep"
+#define CUOPT_AMD_HALPERN_INFEASIBILITY "amd_halpern_infeasibility"
 #define CUOPT_AMD_PDLP_SOLVER_MODE_HALPERN1 4
 
 #ifdef __cplusplus

@@ -445,6 +445,20 @@ int pdlpdev_halpern_restart(pdlpdev_ctx* ctx, double theta, double dist[2], pdlp
 /* the Halpern scalars as the last pdlpdev_run / pdlpdev_run_period / pdlpdev_halpern_restart / pdlpdev_get_ctl read them back together
  * with the control block */
 int pdlpdev_get_halpern(pdlpdev_ctx* ctx, pdlpdev_halpern* out);
+/* Infeasibility detection in Halpern mode ("Infeasibility detection" in the design note).  The ray estimate is the displacement of
+ * the last step, D = T(z^k) - z^k: T(z^k) sits in the average slots, z^k in the side of the ping-pong pairs the control block's
+ * `cur` does NOT select (a step writes z^{k+1} to the other side and never touches z^k).
+ * pdlpdev_set_halpern_rays(on != 0): every evaluation of T(z^k) from now on (pdlpdev_major_eval, pdlpdev_run_period, the evaluations
+ * of a Halpern small-LP batch) is followed by the ray pass in the same stream, read back with the evaluation's own synchronisation.
+ * pdlpdev_halpern_eval_infeasibility: out = the four figures of pdlpdev_eval_infeasibility with the unscaled displacement
+ * (D_c dx, D_r dy) in the iterate's place.  What an evaluation left for the present step count and the same rule is handed out
+ * without touching the device; otherwise the pass is enqueued now (one synchronisation).  -7 outside Halpern mode or before the
+ * first step.
+ * pdlpdev_halpern_get_ray: the unscaled displacement itself, dx (n), dy (m), either may be NULL; -7 unless a ray was evaluated at
+ * the present step count. */
+int pdlpdev_set_halpern_rays(pdlpdev_ctx* ctx, int on);
+int pdlpdev_halpern_eval_infeasibility(pdlpdev_ctx* ctx, int rc_rule_finite_bounds, double out[4]);
+int pdlpdev_halpern_get_ray(pdlpdev_ctx* ctx, double* dx, double* dy);
 
 /* ---- major iteration -------------------------------------------------------------------------- */
 /* adds a still-pending accepted iterate to the running sums */

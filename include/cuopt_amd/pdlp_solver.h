@@ -161,6 +161,17 @@ typedef struct cuoptamd_settings {
    * cuoptamd_batch_solve then groups LPs that share matrix and objective by 16 / 8 / 4 ("shared_matrix_halpern").  0 (default):
    * refused / solved one after the other, as before.  Ignored when algorithm == 0, and by a single solve. */
   int32_t halpern_lockstep;
+  /* Reflected Halpern mode (algorithm == 1) only: non-zero switches infeasibility detection on.  At every major iteration whose
+   * T(z^k) is not Optimal, the displacement of the period's last step, D = T(z^k) - z^k (unscaled: D_c dx, D_r dy), takes the
+   * iterate's place in the infeasibility information: PrimalInfeasible iff dual_ray_linear_objective > 0 and
+   * max_dual_ray_infeasibility / dual_ray_linear_objective <= primal_infeasible_tolerance, else DualInfeasible iff
+   * primal_ray_linear_objective < 0 and max_primal_ray_infeasibility / -primal_ray_linear_objective <= dual_infeasible_tolerance --
+   * whether or not T(z^k) is primal feasible.  The four *_ray_* fields of the result are filled, T(z^k) is what is returned, and
+   * cuoptamd_solver_get_ray hands out the displacement itself.  Serves the multi-launch path (every layout), the resident loop
+   * (halpern_resident) and the K-workgroup batch (halpern_batch); a lockstep batch (halpern_lockstep) refuses members that have it
+   * set, with -7.  0 (default): no certificate is looked for, as before (detect_infeasibility stays refused under algorithm == 1).
+   * Ignored when algorithm == 0. */
+  int32_t halpern_infeasibility;
 } cuoptamd_settings;
 
 /* additional_termination_information_t (pdlp/solver_solution.hpp:63-103) + run statistics */
@@ -337,6 +348,11 @@ int cuoptamd_warm_start_remap(const cuoptamd_warm_start* in, const int32_t* var_
 /* x (n), y (m_global), reduced cost (n) of the returned iterate, unscaled, in the internal min-form
  * sign convention of the reference (any pointer may be NULL). Valid after a terminating advance. */
 int cuoptamd_solver_get_solution(cuoptamd_solver* s, double* x, double* y, double* rc);
+/* Reflected Halpern mode with cuoptamd_settings::halpern_infeasibility: the certificate of the last ray evaluation -- the unscaled
+ * displacement dx (n) = D_c (x' - x^k), dy (m) = D_r (y' - y^k) of the period's last step, in the caller's order (either pointer may
+ * be NULL).  For PrimalInfeasible dy is the Farkas certificate, for DualInfeasible dx the unbounded direction.  -7 when the option is
+ * off or no ray has been evaluated at the solver's present step count. */
+int cuoptamd_solver_get_ray(cuoptamd_solver* s, double* dx, double* dy);
 
 /* Batch solve (call_batch_solve, LP/utilities/cython_solve.cu:264-296: independent LPs solved concurrently on
  * one GPU, one host thread + one stream each, at most `max_threads` at a time; <= 0: one per available core,
