@@ -318,6 +318,10 @@ _proto("pdlpdev_shard_transport", c_int, c_void_p)
 _proto("pdlpdev_shard_wire_bytes", c_int, c_void_p, c_void_p)
 _proto("pdlpdev_dense_info", c_int, c_void_p, c_void_p)
 _proto("pdlpdev_layout_info", c_int, c_void_p, c_void_p)
+_proto("pdlpdev_comm_abort", c_int, c_void_p)
+if hasattr(lib, "pdlpdev_shard_slice"):  # (an older build given through CUOPT_AMD_LIB has neither)
+    _proto("pdlpdev_shard_slice", c_int, c_void_p, P(c_int), P(c_int))
+    _proto("pdlpdev_owner_layout_info", c_int, c_void_p, c_void_p)
 # device-side set-up (round 5)
 _proto("pdlpdev_analyze", c_int, P(c_void_p), c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int)
 _proto("pdlpdev_analysis_info", c_int, c_void_p, c_void_p)
@@ -639,6 +643,12 @@ def softcomm_id(world):
     if rc != 0:
         raise CuOptError(rc, lib.pdlpdev_last_error().decode())
     return bytes(buf)
+
+
+def comm_abort(comm_id):
+    """pdlpdev_comm_abort: a rank of a sharded solve failed -- the other ranks' collectives on communicators made from `comm_id` return an
+    error instead of waiting for it"""
+    return lib.pdlpdev_comm_abort((C.c_uint8 * 128).from_buffer_copy(comm_id))
 
 
 SIMPLEX_STATUS = {1: "Optimal", 2: "PrimalInfeasible", 3: "Unbounded", 5: "IterationLimit", 6: "TimeLimit", 7: "NumericalError",
@@ -1138,7 +1148,9 @@ class Device:
         """pdlpdev_debug_attempts: `count` (1 .. 64) attempts as run() enqueues them and NO make-up round -> the control block behind them.
         On a resident context (not in Halpern mode): one launch of the one-workgroup loop capped at `count` attempts.  There a REJECTED
         attempt writes nothing but the control block (the trial iterate never leaves the registers: the _OTHER buffers are stale) and
-        XBAR is never written.  CuOptError -7: a sharded context, Halpern mode."""
+        XBAR is never written.  On a sharded context (every rank calls it with the same count): the round with its collectives, then
+        X, ATY and SUM_X of the current side replicated again under the sliced dataflows; X_OTHER, ATY_OTHER and XBAR stay valid on the
+        rank's slice (shard_slice()) only.  CuOptError -7: Halpern mode."""
         c = Ctl()
         self._ck(lib.pdlpdev_debug_attempts(self.handle, int(count), C.byref(c)))
         return c
@@ -1253,6 +1265,19 @@ class Device:
                     d["row_sums"] = "by_nonzero" if out[6 + k // 3] else "by_row"  # by_nonzero: the long-tail variant (every row at rtol)
             return d
         return dict(A=side(0), At=side(3), resident=bool(out[0] == 2))
+
+    def shard_slice(self):
+        """pdlpdev_shard_slice -> (first column, columns) on which this rank's primal side is complete inside the attempt loop: its
+        slice under the rsag / owner dataflows, (0, n) otherwise"""
+        a, b = c_int(), c_int()
+        self._ck(lib.pdlpdev_shard_slice(self.handle, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def owner_layout(self):
+        """owner-computes dataflow: the column block's layout as layout()'s sides give theirs"""
+        out = np.zeros(3, np.int32)
+        self._ck(lib.pdlpdev_owner_layout_info(self.handle, _ptr(out)))
+        return dict(layout={0: "stream", 1: "panel", 3: "jag", 4: "pb"}[int(out[0])], workgroups=int(out[1]), detail=int(out[2]))
 
     def wire_bytes(self):
         """sharded solve, owner-computes dataflow: bytes this rank receives per attempt for the two vector exchanges"""

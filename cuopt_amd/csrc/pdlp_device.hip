@@ -469,6 +469,19 @@ int pdlpdev_owner_slice(pdlpdev_ctx* ctx, int32_t* col_begin, int32_t* ncols)
   *ncols           = (int32_t)std::max<int64_t>(0, std::min<int64_t>(ctx->slice, (int64_t)ctx->n - cs));
   return 0;
 }
+int pdlpdev_shard_slice(pdlpdev_ctx* ctx, int32_t* col_begin, int32_t* ncols)
+{
+  const int64_t cs = ctx->rsag ? (int64_t)ctx->rank * ctx->slice : 0, len = ctx->rsag ? ctx->slice : ctx->n;
+  *col_begin       = (int32_t)std::min<int64_t>(cs, ctx->n);
+  *ncols           = (int32_t)std::max<int64_t>(0, std::min<int64_t>(len, (int64_t)ctx->n - cs));
+  return 0;
+}
+int pdlpdev_owner_layout_info(pdlpdev_ctx* ctx, int32_t out[3])
+{
+  if (!ctx->owner || !ctx->Oc.hot.off) return fail(-1, "pdlpdev_owner_layout_info: no column block (the owner-computes dataflow behind pdlpdev_owner_setup only)");
+  ctx->Oc.info(out);
+  return 0;
+}
 // The column block of the owner-computes dataflow: rows [col_begin, col_begin + ncols) of the GLOBAL A^T (column indices =
 // global row numbers of A, ascending: every column is then summed over the rows in the order one GPU uses), unscaled
 // values; row_bounds[world + 1] = the ranks' row blocks.  Call after pdlpdev_scale_problem: the values are scaled here with
@@ -1149,13 +1162,13 @@ int pdlpdev_run(pdlpdev_ctx* ctx, int32_t target_steps, pdlpdev_ctl* ctl)
 // Parity hook: `count` attempts as pdlpdev_run enqueues them (same kernels, graph replay or plain launches), one read-back, after_round's
 // bookkeeping -- and NO make-up round, so a rejected attempt is there to be looked at: the trial iterate in the other side of the
 // ping-pong pairs, the decision's inputs in the control block.  On the resident small-LP path: one launch of the one-workgroup loop
-// capped at `count` attempts (resident_attempts); a rejected trial iterate stays in that kernel's registers.
+// capped at `count` attempts (resident_attempts); a rejected trial iterate stays in that kernel's registers.  On a sharded context
+// every rank calls it with the same count; run_epilogue behind the round replicates the current side again (sliced dataflows).
 int pdlpdev_debug_attempts(pdlpdev_ctx* ctx, int count, pdlpdev_ctl* ctl)
 {
   HIP_TRY(hipSetDevice(ctx->device));
   const bool resident = ctx->small_resident && !ctx->comm && !ctx->halpern;
-  if (!resident && (ctx->small_resident || ctx->comm || ctx->halpern))
-    return fail(-7, "pdlpdev_debug_attempts: the averaging attempt only, multi-launch or resident (not a sharded context or Halpern mode)");
+  if (ctx->halpern) return fail(-7, "pdlpdev_debug_attempts: the averaging attempt only, multi-launch, sharded or resident (not Halpern mode)");
   if (count < 1 || count > 64) return fail(-1, "pdlpdev_debug_attempts: count must be 1 .. 64");
   if (resident) {
     TRY(fetch_ctl(ctx, nullptr));
@@ -1166,14 +1179,15 @@ int pdlpdev_debug_attempts(pdlpdev_ctx* ctx, int count, pdlpdev_ctl* ctl)
   TRY(fetch_ctl(ctx, nullptr));
   const int before = ctx->ctl_h->steps_taken, attempts_before = ctx->ctl_h->attempts;
   TRY(set_target(ctx, before + count));
-  if (ctx->ctl_h->error == 0) {
+  int rounds = 0;
+  if (ctx->ctl_h->error == 0) {  // (all-reduced scalars decide the error: every rank of a sharded context sees the same)
     TRY(enqueue_attempts(ctx, count));
     TRY(fetch_ctl(ctx, nullptr));
     ctx->stat_loop_syncs += 1;
     TRY(after_round(ctx, before, attempts_before, count, count));
+    rounds = 1;
   }
-  if (ctl) *ctl = *ctx->ctl_h;
-  return 0;
+  return run_epilogue(ctx, rounds, ctl);
 }
 
 // One major-iteration period with ONE synchronisation: the attempts up to `target_steps`, a few spare ones (empty launches unless an

@@ -1219,6 +1219,15 @@ int cuoptamd_solver_create(cuoptamd_solver** out, const cuoptamd_lp* lp, const c
   cuoptamd_partition_rows(m, L->offsets, world, bounds.data());
   s->row_begin = bounds[rank], s->row_end = bounds[rank + 1];
   const int32_t ml = s->row_end - s->row_begin;
+  // A row holding more than 1 / world of the nonzeros leaves a block without rows (cuoptamd_partition_rows), and nothing of the device
+  // layer is written for a context of zero rows.  Every rank computes the same bounds, so every rank refuses here, by name, and the
+  // refusal takes the way of any other set-up failure (the agreement in front of the communicator, below).
+  if (setup_rc == 0 && world > 1)
+    for (int g = 0; g < world; ++g)
+      if (bounds[g + 1] == bounds[g]) {
+        setup_rc = fail(-1, "cuoptamd_solver_create: empty row block: rank %d of %d would hold no rows (one row holds more than 1 / world of the nonzeros); use fewer ranks", g, world);
+        break;
+      }
   if (ag.an && setup_rc == 0) {
     // single GPU: the analysis' device arrays become the context's
     pdlpdev_create_hint(0);

@@ -550,7 +550,12 @@ int pdlpdev_time_kernel(pdlpdev_ctx* ctx, int kernel_id, int reps, double* avg_m
  * but the control block -- the trial iterate never leaves the kernel's registers, so the _OTHER buffers are stale -- and XBAR is never
  * written.  The current side (X, Y, ATY), SUM_X / SUM_Y and the control block are as above; with the step error up the launch makes
  * no attempt.
- * -1: count outside 1 .. 64.  -7: a sharded context, Halpern mode (the resident Halpern loop included). */
+ * On a SHARDED context (averaging modes; every rank calls the hook with the same `count`): the same round -- target, `count` attempts
+ * with their collectives, one read-back, the bookkeeping -- and then what pdlpdev_run does behind its rounds: under the sliced
+ * dataflows (rsag, owner) X, ATY and SUM_X of the current side are all-gathered, so that they are replicated again when the call
+ * returns.  The trial side of a rejected attempt (X_OTHER, ATY_OTHER) and XBAR stay valid on the owner's slice (XBAR under the halo
+ * exchange: on the ranges the rank's rows reference) only.  The step error is the same on all ranks, so all enqueue or none does.
+ * -1: count outside 1 .. 64.  -7: Halpern mode (the resident Halpern loop included). */
 int pdlpdev_debug_attempts(pdlpdev_ctx* ctx, int count, pdlpdev_ctl* ctl);
 /* device-side generation of the iterate is not needed; but benches need a sync point */
 int pdlpdev_synchronize(pdlpdev_ctx* ctx);
@@ -578,6 +583,12 @@ int pdlpdev_shard_transport(pdlpdev_ctx* ctx);
 int pdlpdev_shard_wire_bytes(pdlpdev_ctx* ctx, int64_t out[3]);
 /* owner-computes dataflow: the columns [*col_begin, *col_begin + *ncols) of A this rank owns ... */
 int pdlpdev_owner_slice(pdlpdev_ctx* ctx, int32_t* col_begin, int32_t* ncols);
+/* any context: the columns on which this rank's primal side is complete INSIDE the attempt loop -- its slice under the sliced
+ * dataflows (rsag, owner; an empty slice: col_begin = n, ncols = 0), all of them (0, n) under the replicated dataflow and without a
+ * communicator */
+int pdlpdev_shard_slice(pdlpdev_ctx* ctx, int32_t* col_begin, int32_t* ncols);
+/* owner-computes dataflow: the column block's layout, as one triple of pdlpdev_layout_info (layout, workgroups, detail) */
+int pdlpdev_owner_layout_info(pdlpdev_ctx* ctx, int32_t out[3]);
 /* ... and their nonzeros over ALL rows of A: rows [col_begin, col_begin + ncols) of the global A^T as CSR (indices = global
  * row numbers, ascending; UNSCALED values; offsets start at 0), row_bounds[world + 1] = the ranks' row blocks
  * (cuoptamd_partition_rows).  After pdlpdev_scale_problem, before the first pdlpdev_run. */

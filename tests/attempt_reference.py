@@ -57,7 +57,19 @@ The three sums go through block_sum_fast's fixed tree, which is not left to righ
 reference's own trial vectors (which the device's equal bit for bit).  The decision and everything behind it is unchanged.  What can be
 looked at differs: an ACCEPTED attempt leaves its trial iterate as the new current side; a REJECTED one writes nothing but the
 control block and the running sums (the trial iterate never leaves the registers: the other side is stale and not read), so X, Y and
-ATY must be the bits in front of the attempt, SUM_X / SUM_Y too unless an average was pending.  XBAR is never written there."""
+ATY must be the bits in front of the attempt, SUM_X / SUM_Y too unless an average was pending.  XBAR is never written there.
+
+THE SHARDED PATH (tests/test_sharded_attempts_gpu.py: W ranks' buffers assembled to the global vectors by tests/sharded_ranks.py, then
+check_attempt as it stands).  No bound above is widened, because none needs to be:
+    the ranks' partial products of a column, added in rank order (the all-reduce, the reduce-scatter), are one more summation tree
+    over the same L_j terms, and a rank without an entry in the column contributes an exact 0: (L_j + 16) u sum |a_ij y'_i| holds for
+    A^T y' under all three dataflows.  The owner-computes column block sums a whole column on one rank: a tree like any other.
+    dy2, dx2, the interaction and the restart's distances are sums of per-rank (per-slice) partials over the same m or n terms.
+    An entry of the column block, or of a rank's A^T, is scaled (a D_c) D_r where A_VALUES holds (a D_r) D_c: it may differ in its last
+    bit, which is one of the 16 spare roundings per term.
+    x', xbar, SUM_X, SUM_Y, the flush, the three averages, the restart's copies and everything derived from the device's own three
+    sums are element-wise or scalar work on values every rank holds alike: bit for bit, as on one GPU.
+A ratio above 1.0 there is a finding about the kernel concerned, not a reason to touch a bound."""
 import math
 
 import numpy as np

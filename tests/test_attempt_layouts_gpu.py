@@ -161,7 +161,9 @@ def test_scalar_branches(kind, layout, monkeypatch):
 
 def test_hook_is_refused_where_no_multi_launch_attempt_runs(monkeypatch):
     """-7 in Halpern mode, on the resident small-LP path (whose averaging loop the hook does serve: tests/test_resident_attempts_gpu.py)
-    and off it; -1 for a count outside 1 .. 64 on a resident context"""
+    and off it; -1 for a count outside 1 .. 64 on a resident context.  A context behind a communicator is NOT refused any more (the
+    sharded attempt is what tests/test_sharded_attempts_gpu.py looks at through the hook): one rank behind one serves an attempt, and
+    refuses the same counts."""
     p, x0, y0 = sc.tiny_lp("dual-only")
     monkeypatch.setenv("CUOPT_AMD_SMALL", "1")
     raw = capi.Device(p)
@@ -186,3 +188,12 @@ def test_hook_is_refused_where_no_multi_launch_attempt_runs(monkeypatch):
         raw.attempts(1)
     assert e.value.code == -7
     raw.close()
+    solver = capi.Solver(p, rank=0, world=1, comm_id=capi.softcomm_id(1))
+    assert capi.lib.pdlpdev_shard_dataflow(solver.device.handle) == 3
+    for count in (0, 65):
+        with pytest.raises(capi.CuOptError) as e:
+            solver.device.attempts(count)
+        assert e.value.code == -1
+    c = solver.device.attempts(1)
+    assert (c.error, c.attempts, c.target_steps) == (0, 1, 1)
+    solver.close()

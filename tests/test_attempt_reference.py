@@ -2,7 +2,9 @@
 oracle, and the scenario of tests/test_attempt_layouts_gpu.py (tests/attempt_scenario.py) on a plain float64 stand-in for the device,
 on every LP and seed the GPU test uses: the stand-in stays inside every derived bound, and the scenario has the properties the GPU
 test relies on (accepted steps from both sides of the ping-pong pairs, attempts with and without a pending average, a forced rejection
-with step / limit >= 2, no natural decision within 1e-6 of a tie)."""
+with step / limit >= 2, no natural decision within 1e-6 of a tie).  The last section runs the same scenario on W stand-in RANKS behind
+the assembly of tests/sharded_ranks.py, for the cases of tests/test_sharded_attempts_gpu.py: the assembly reads no stale entry (whatever
+a rank does not own is NaN there) and the LPs keep the scenario's properties in the sharded order of summation."""
 import numpy as np
 import pytest
 
@@ -11,6 +13,7 @@ import attempt_scenario as sc
 import eval_reference as er
 from cuopt_amd import synthetic
 import resident_lps as rl
+import sharded_ranks as sr
 from eval_lps import SEEDS, WIDE_N, edge_lp
 from oracle import orcbind
 
@@ -401,3 +404,96 @@ def test_evaluated_iterates_hold_hardly_a_tie(name):
         dev.run(c["steps_taken"] + 1)
     assert dev.ctl()["cur"] == 1 and dev.ctl()["steps_taken"] == 3 + len(sc.EVAL_COMBOS)
     print("TIES %s worst share %.4f" % (name, worst))
+
+
+# ---- the sharded GPU test's cases on W stand-in ranks (tests/sharded_ranks.py) --------------------------------------------------------
+FLOWS = ("allreduce", "rsag", "owner")
+# world -> (rows per block, slice, last slice) of the 6000 x 6000 LP with the 4500-entry column, as the GPU test's docstring quotes them
+BLOCKS = {2: ((2979, 3021), 3008, 2992), 3: ((1924, 1955, 2121), 2000, 2000), 4: ((1501, 1478, 1442, 1579), 1504, 1488)}
+# the LPs behind the ids of the layout cases at world 4 (test_eval_layouts_gpu.VARIANTS): panel-*, jag-8 | pb | dense-stream, dense-panel-longtail
+WORLD4 = [(0, "allreduce"), (0, "rsag"), (0, "owner"), (1, "allreduce"), (1, "owner"), (2, "allreduce"), (2, "owner")]
+
+
+@pytest.fixture(scope="module")
+def sharded_lps():
+    out = []
+    for spec in LPS[:3]:
+        p, x, y = edge_lp(*spec)
+        out.append((p, x, y, scaling_of(p)))
+    return out
+
+
+def test_row_blocks_and_slices_of_the_sharded_cases(sharded_lps):
+    from cuopt_amd import capi
+    p = sharded_lps[0][0]
+    for world, (rows, width, last) in BLOCKS.items():
+        assert tuple(np.diff(capi.partition_rows(p["m"], p["offsets"], world))) == rows
+        sl = sr.slices_of(p["n"], world, "owner")
+        assert all(s == (r * width, width) for r, s in enumerate(sl[:-1])) and sl[-1] == ((world - 1) * width, last), sl
+    rows = np.diff(capi.partition_rows(p["m"], p["offsets"], 8))
+    assert (rows.min(), rows.max()) == (649, 796) and sr.slices_of(p["n"], 8, "rsag")[-1] == (7 * 752, 736)
+    assert sr.slices_of(p["n"], 8, "allreduce") == [(0, 6000)] * 8
+    assert sr.slices_of(60, 8, "owner") == [(0, 16), (16, 16), (32, 16), (48, 12)] + [(60, 0)] * 4  # (the 40 x 60 LPs: four empty slices)
+
+
+def _sharded_scenario(lp, world, flow, name):
+    p, x0, y0, (dr, dc) = lp
+    dev, S, prob = sr.stand_in(p, x0, y0, dr, dc, step_params(1), world, flow)
+    worst = sc.run_scenario(dev, S, prob, dev.sp, dr, dc, name)
+    print(worst.line(name))
+    assert max(worst.values()) <= 1.0 and min(worst[k] for k in ("y", "aty", "dy2", "dx2", "inter", "dist")) > 0.0, worst
+
+
+@pytest.mark.parametrize("world", [2, 3, 8])
+@pytest.mark.parametrize("flow", FLOWS)
+def test_sharded_scenario_on_the_stand_in_ranks(sharded_lps, flow, world):
+    _sharded_scenario(sharded_lps[0], world, flow, "stand-in ranks %s world %d" % (flow, world))
+
+
+@pytest.mark.parametrize("which,flow", WORLD4, ids=["%s-%s" % (LP_IDS[w], f) for w, f in WORLD4])
+def test_sharded_scenario_of_the_layout_cases_on_the_stand_in_ranks(sharded_lps, which, flow):
+    _sharded_scenario(sharded_lps[which], 4, flow, "stand-in ranks %s %s world 4" % (LP_IDS[which], flow))
+
+
+def test_band_lp_of_the_transport_cases():
+    """the smallest band LP on which every rank takes the halo exchange at world 4 (the rule restated on the host; the GPU test asserts
+    wire_bytes()), and the scenario's properties on it under the owner-computes dataflow"""
+    m, band = sr.smallest_band(4)
+    assert (m, band) == sr.BAND_LP
+    p, x0, y0 = sr.band_lp(m, band)
+    use, worst, full = sr.halo_rule(p, 4)
+    assert use and not sr.halo_rule(sr.band_lp(m // 2, band)[0], 4)[0], (worst, full)
+    lo, hi = p["lo"], p["hi"]
+    assert (np.isfinite(lo) & (lo == hi)).sum() == m // 5 or abs((np.isfinite(lo) & (lo == hi)).sum() - m / 5) <= 1
+    print("BAND m=%d band=%d: a rank receives at most %d entries per attempt, the all-gathers bring %d" % (m, band, worst, full))
+    _sharded_scenario((p, x0, y0, scaling_of(p)), 4, "owner", "stand-in ranks band world 4")
+
+
+@pytest.mark.parametrize("flow", FLOWS)
+@pytest.mark.parametrize("kind", ["fixed-point", "dual-only"])
+def test_scalar_branch_lps_on_the_stand_in_ranks(kind, flow):
+    """40 x 60 at world 8: slices of 16 columns, so rank 3 holds 12 and ranks 4 .. 7 none"""
+    p, x0, y0 = sc.tiny_lp(kind)
+    dev, S, prob = sr.stand_in(p, x0, y0, np.ones(p["m"]), np.ones(p["n"]), step_params(1), 8, flow)
+    assert flow == "allreduce" or [s[1] for s in dev.slices] == [16, 16, 16, 12, 0, 0, 0, 0]
+    r, before, after = sc.one_attempt(dev, S, prob, dev.sp, "%s %s" % (kind, flow))
+    sc.assert_scalar_branch(kind, r, before, after, dev.sp)
+
+
+def test_the_assembly_sees_a_stale_entry(sharded_lps):
+    """what the stand-in ranks prove rests on this: a value taken from a rank that does not own it fails the check, at the stage"""
+    p, x0, y0, (dr, dc) = sharded_lps[0]
+    dev, S, prob = sr.stand_in(p, x0, y0, dr, dc, step_params(1), 4, "owner")
+    before = sc.snapshot(dev)
+    dev.attempt()
+    after = sc.snapshot(dev, xbar=True)
+    ar.check_attempt(S, prob, dev.sp, before, after, "owner")
+    ranks = dev.b.ranks
+    assert all(np.isnan(k.v["XBAR"][:k.c0]).all() and np.isnan(k.v["XBAR"][k.c0 + k.nc:]).all() for k in ranks[1:3])
+    dev.slices = [dev.slices[0], (dev.slices[1][0] + 1, dev.slices[1][1]), *dev.slices[2:]]  # (rank 1's slice taken one column late)
+    dev._cache.clear()
+    with pytest.raises(AssertionError, match="changed its own input|xbar"):
+        ar.check_attempt(S, prob, dev.sp, before, sc.snapshot(dev, xbar=True), "owner, a slice off by one")
+    swapped = dict(after, ctl=dict(after["ctl"], last_dx2=after["ctl"]["last_interaction"], last_interaction=after["ctl"]["last_dx2"]))
+    with pytest.raises(AssertionError):  # (two entries of the 3-scalar pack swapped)
+        ar.check_attempt(S, prob, dev.sp, before, swapped, "owner, swapped sums")

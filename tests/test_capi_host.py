@@ -169,6 +169,39 @@ def test_partition_rows_balances_nonzeros():
         assert per.max() - per.min() <= 2 * 50
 
 
+def heavy_row_lp():
+    """64 x 64, one row of 60 entries among rows of one: more than 1 / 4 of the nonzeros in one row"""
+    lens = np.ones(64, dtype=np.int64)
+    lens[20] = 60
+    off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)
+    idx = np.concatenate([np.arange(60) if l == 60 else [i] for i, l in enumerate(lens)]).astype(np.int32)
+    rng = np.random.default_rng(4)
+    return dict(m=64, n=64, offsets=off, indices=idx, values=rng.standard_normal(off[-1]), c=rng.standard_normal(64), lo=np.full(64, -INF),
+                hi=np.ones(64), lb=np.zeros(64), ub=np.full(64, 3.0))
+
+
+def test_partition_rows_leaves_a_block_empty_behind_a_heavy_row():
+    p = heavy_row_lp()
+    b = capi.partition_rows(p["m"], p["offsets"], 4)
+    assert b[0] == 0 and b[-1] == 64 and np.all(np.diff(b) >= 0) and (np.diff(b) == 0).any(), b
+    assert (np.diff(capi.partition_rows(p["m"], p["offsets"], 2)) > 0).all()
+
+
+def test_a_sharded_solver_refuses_an_empty_row_block_on_every_rank():
+    """nothing of the device layer is written for a context of zero rows: every rank computes the same bounds and refuses by name,
+    before it touches the device or the communicator (so no rank waits for another) -- and the same LP at world 2 is not refused here"""
+    p = heavy_row_lp()
+    cid = capi.softcomm_id(4)
+    for rank in range(4):
+        with pytest.raises(capi.CuOptError) as e:
+            capi.Solver(p, rank=rank, world=4, comm_id=cid)
+        assert e.value.code == -1 and "empty row block" in str(e.value) and "of 4" in str(e.value), str(e.value)
+    if capi.device_count() == 0:  # (at world 2 the set-up goes on to the device, and fails there for another reason)
+        with pytest.raises(capi.CuOptError) as e:
+            capi.Solver(p, rank=0, world=2, comm_id=capi.softcomm_id(2))
+        assert "empty row block" not in str(e.value)
+
+
 def test_csr_transpose_matches_scipy():
     import scipy.sparse as sp
     rng = np.random.default_rng(1)
