@@ -921,8 +921,9 @@ class SharedMatrixBatch:
         return list(zip(xs, ys, zs))
 
     def stats(self):
-        """cuoptamd_batch_stats of a small-LP batch: dict halpern / tiers (resident tiers in use) and, counted for a batch in reflected
-        Halpern mode, loop_launches / eval_launches (behind the loop) / periods (runs) / restart_rounds / resets / syncs"""
+        """cuoptamd_batch_stats of a small-LP batch: dict halpern / tiers (resident tiers in use) / loop_launches / eval_launches (behind the
+        loop) / periods (runs) and, counted for a batch in reflected Halpern mode, restart_rounds / resets; syncs (an averaging batch: those of
+        its runs only)"""
         out = np.zeros(8, np.int64)
         rc = lib.cuoptamd_batch_stats(self.handle, _ptr(out))
         if rc != 0:

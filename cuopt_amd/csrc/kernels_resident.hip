@@ -200,22 +200,6 @@ int resident_tier(int m, int n, int64_t nnz)
   }
   return -1;
 }
-template <int T, int Q, int U>
-static int launch_resident(hipStream_t s, int tier, const SmallView& V, pdlpdev_ctl* ctl, pdlpdev_ctl* ctl_host,
-                           const pdlpdev_step_params& sp, int target_steps, int max_attempts)
-{
-  static PerDeviceOnce once;  // per instantiation
-  int device = 0;
-  HIP_TRY(hipGetDevice(&device));
-  TRY(once.run(device, [&]() -> int {
-    HIP_TRY(hipFuncSetAttribute((const void*)k_pdhg_resident<T, Q, U>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)resident_lds_bytes(tier)));
-    return 0;
-  }));
-  k_pdhg_resident<T, Q, U><<<1, T, resident_lds_bytes(tier), s>>>(V, ctl, ctl_host, sp, target_steps, max_attempts);
-  HIP_TRY(hipGetLastError());
-  return 0;
-}
 
 
 // single-workgroup head of a major iteration (pdlpdev_major_eval) for LPs on the resident path: MajorSmallArgs, small_rows
@@ -305,20 +289,19 @@ static SmallView small_view(const pdlpdev_ctx* ctx)
 }
 static int major_lds_attribute(int device)
 {
-  static PerDeviceOnce once;
-  return once.run(device, [&]() -> int {
-    HIP_TRY(hipFuncSetAttribute((const void*)k_major_small, hipFuncAttributeMaxDynamicSharedMemorySize, 8192 * 8));
-    HIP_TRY(hipFuncSetAttribute((const void*)k_major_small_batch, hipFuncAttributeMaxDynamicSharedMemorySize, 8192 * 8));
-    return 0;
-  });
+  TRY(allow_dynamic_lds((const void*)k_major_small, device, 8192 * 8));
+  return allow_dynamic_lds((const void*)k_major_small_batch, device, 8192 * 8);
 }
-// the tier's instantiation of the loop kernel, enqueued
+// the tier's instantiation of the loop kernel, enqueued (a value that is no tier: nothing, as ever -- resident contexts have one)
 static int launch_resident_tier(pdlpdev_ctx* ctx, int tier, const SmallView& V, int32_t target_steps, int max_attempts)
 {
-  if (tier == 0) TRY((launch_resident<256, 2, 8>(ctx->stream, tier, V, ctx->ctl, ctx->ctl_h, ctx->sp, target_steps, max_attempts)));
-  if (tier == 1) TRY((launch_resident<512, 2, 16>(ctx->stream, tier, V, ctx->ctl, ctx->ctl_h, ctx->sp, target_steps, max_attempts)));
-  if (tier == 2) TRY((launch_resident<512, 4, 8>(ctx->stream, tier, V, ctx->ctl, ctx->ctl_h, ctx->sp, target_steps, max_attempts)));
-  return 0;
+  return for_resident_tier(
+    tier,
+    [&](auto I) {
+      constexpr ResidentTier r = kResidentTiers[decltype(I)::value];
+      return launch_resident_kernel(k_pdhg_resident<r.T, r.Q, r.U>, I, ctx->device, ctx->stream, 1, V, ctx->ctl, ctx->ctl_h, ctx->sp, target_steps, max_attempts);
+    },
+    [] { return 0; });
 }
 // one launch runs attempts until the target is reached (rejected attempts included); the cap only bounds a pathological rejection
 // streak, in which case the loop relaunches.  The kernel takes the target as an argument and leaves the control block in pinned host
@@ -502,22 +485,42 @@ struct pdlpdev_small_batch {
   bool halpern = false;
   HalpernResidentArgs* hrun = nullptr;
   HalpernRestartArgs* hrestart = nullptr;
-  // (Halpern batches) launches of the loop kernel / of the evaluation behind it, calls of pdlpdev_small_batch_run, restart rounds,
-  // resets, and the synchronisations: one per run, restart round, reset and separate pdlpdev_small_batch_major_eval
+  // launches of the loop kernel / of the evaluation behind it, calls of pdlpdev_small_batch_run, and the synchronisations: one per
+  // pass of a run in either mode; for a Halpern batch also restart rounds and resets, and one synchronisation per restart round, reset
+  // and separate pdlpdev_small_batch_major_eval
   int64_t stat_loop_launches = 0, stat_eval_launches = 0, stat_periods = 0, stat_restart_rounds = 0, stat_resets = 0, stat_syncs = 0;
 };
 
-template <int T, int Q, int U>
+// the tier's instantiation of the averaging loop kernel for the LPs of `list`, enqueued
 static int launch_resident_batch(pdlpdev_small_batch* b, int tier, const int* list, int count)
 {
-  static PerDeviceOnce once;
-  TRY(once.run(b->device, [&]() -> int {
-    HIP_TRY(hipFuncSetAttribute((const void*)k_pdhg_resident_batch<T, Q, U>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)resident_lds_bytes(tier)));
-    return 0;
-  }));
-  k_pdhg_resident_batch<T, Q, U><<<count, T, resident_lds_bytes(tier), b->stream>>>(b->run_args, list, 1 << 14);
+  return for_resident_tier(
+    tier,
+    [&](auto I) {
+      constexpr ResidentTier r = kResidentTiers[decltype(I)::value];
+      return launch_resident_kernel(k_pdhg_resident_batch<r.T, r.Q, r.U>, I, b->device, b->stream, count, b->run_args, list, 1 << 14);
+    },
+    [] { return 0; });
+}
+// the mode's evaluation kernel over b->major for the LPs of b->list[0 .. count), enqueued
+static int launch_major_batch(pdlpdev_small_batch* b, int count)
+{
+  if (b->halpern) return halpern_batch_launch_eval(b->stream, b->device, b->major_lds, b->major, b->list, count);
+  k_major_small_batch<<<count, kMajorThreads, b->major_lds, b->stream>>>(b->major, b->list);
   HIP_TRY(hipGetLastError());
   return 0;
+}
+// k_restart_batch's record of LP c (pdlpdev_restart(which, unscaled)'s view; distances to the LP's pinned scalars) and
+// k_spmv_at_cur's (pdlpdev_compute_aty)
+static RestartBatchArgs restart_batch_args(const pdlpdev_ctx* c, int which, int unscaled)
+{
+  return RestartBatchArgs{RestartView{c->n, c->m, which, unscaled, c->dc, c->dr, c->ctl, c->x[0], c->x[1], c->y[0], c->y[1], c->avgx, c->avgy, c->lrx, c->lry,
+                                      c->sumx, c->sumy, c->part_g},
+                          std::min(grid_for(std::max(c->n, c->m)), kGenericBlocks), 0, c->scal_h};
+}
+static StreamAtCurArgs stream_at_cur_args(const pdlpdev_ctx* c)
+{
+  return StreamAtCurArgs{c->At.nb, c->At.rb, c->At.hot.off, c->At.hot.idx, c->At.hot.val, c->ctl, c->y[0], c->y[1], c->aty[0], c->aty[1]};
 }
 
 // pdlpdev_small_batch_create (halpern == false: the averaging iteration's batch) / pdlpdev_small_batch_create_halpern
@@ -578,70 +581,8 @@ static int small_batch_create(pdlpdev_small_batch** out, pdlpdev_ctx** ctx, int 
   return 0;
 }
 
-// ---- a batch of LPs in reflected Halpern mode: the branches of pdlpdev_small_batch_run / _major_eval / _reset and the batched restart ----
-// pdlpdev_small_batch_run: per tier in use ONE launch of k_pdhg_resident_halpern_batch, behind them ONE launch of the guarded evaluation
-// of T(z^k) (k_major_small_halpern_batch) for the LPs whose steps end in a major iteration, ONE synchronisation.  evaluated[l] as
-// resident_halpern_period says it for one LP: the target reached, no step error, the evaluation ran.
-static int halpern_batch_run(pdlpdev_small_batch* b, const int32_t* targets, pdlpdev_ctl* ctl, const pdlpdev_small_eval* eval_after, double* out_current,
-                             double* out_average, int32_t* evaluated)
-{
-  const int K = b->K;
-  std::vector<char> todo(K, 0);
-  for (int l = 0; l < K; ++l) {
-    if (evaluated) evaluated[l] = 0;
-    if (targets[l] > 0) {
-      pdlpdev_ctx* c = b->ctx[l];
-      b->hrun[l]     = HalpernResidentArgs{halpern_view(c), c->ctl, c->ctl_h, c->hal, c->hal_h, targets[l], 0};
-      todo[l]        = 1;
-      loop_state_touched(c);
-    }
-  }
-  b->stat_periods += 1;
-  for (int guard = 0; guard < 1000; ++guard) {
-    int count[3] = {0, 0, 0};
-    for (int l = 0; l < K; ++l)
-      if (todo[l]) b->run_list[b->tier[l] * K + count[b->tier[l]]++] = l;
-    if (count[0] + count[1] + count[2] == 0) break;
-    for (int tier = 0; tier < 3; ++tier)
-      if (count[tier]) {
-        TRY(halpern_batch_launch_loop(b->stream, b->device, tier, b->hrun, b->run_list + tier * K, count[tier]));
-        b->stat_loop_launches += 1;
-      }
-    int nev = 0;
-    if (guard == 0 && eval_after) {
-      for (int l = 0; l < K; ++l)
-        if (todo[l] && eval_after[l].mode >= 0) {
-          const int want_linf = eval_after[l].eps_p >= 0.0 && eval_after[l].eps_d >= 0.0;
-          b->major[l] = major_args(b->ctx[l], 3, eval_after[l].rule_finite, want_linf, eval_after[l].eps_p, eval_after[l].eps_d);
-          b->major[l].guard_target = targets[l];
-          b->list[nev++]           = l;
-        }
-      if (nev) {
-        TRY(halpern_batch_launch_eval(b->stream, b->device, b->major_lds, b->major, b->list, nev));
-        b->stat_eval_launches += 1;
-      }
-    }
-    HIP_TRY(hipStreamSynchronize(b->stream));
-    b->stat_syncs += 1;
-    for (int q = 0; q < nev; ++q) {
-      const int l           = b->list[q];
-      const pdlpdev_ctx* c = b->ctx[l];
-      if (c->ctl_h->error != 0 || c->ctl_h->steps_taken < targets[l] || c->scal_h[63] != 1.0) continue;
-      const bool want_linf = eval_after[l].eps_p >= 0.0 && eval_after[l].eps_d >= 0.0;
-      read_eval(c->scal_h + 32, want_linf, out_current + (size_t)l * PDLPDEV_EV_COUNT);
-      read_eval(c->scal_h + 32, want_linf, out_average + (size_t)l * PDLPDEV_EV_COUNT);
-      if (evaluated) evaluated[l] = 1;
-    }
-    for (int l = 0; l < K; ++l)
-      if (todo[l] && (b->ctx[l]->ctl_h->error != 0 || b->ctx[l]->ctl_h->steps_taken >= targets[l])) todo[l] = 0;
-  }
-  for (int l = 0; l < K; ++l)
-    if (targets[l] > 0) {
-      b->ctx[l]->ctl_h_current = true;  // (as resident_halpern_run leaves it: the kernel wrote the pinned mirror)
-      if (ctl) ctl[l] = *b->ctx[l]->ctl_h;
-    }
-  return 0;
-}
+// ---- a batch of LPs in reflected Halpern mode: the batched restart and pdlpdev_small_batch_reset's tail (the run and the evaluation are
+// pdlpdev_small_batch_run's / _major_eval's own, with the mode's records and kernels) ----
 // the restart of the LPs in b->list[0 .. count) (theta[l] < 0: the anchor and the counters only; clear: k_halpern_clear's values first),
 // enqueued only: k_restart_batch with the current iterate as the candidate and scaled distances, blocks from b->blk + blk_first, then the
 // finishing kernel.  The caller synchronises.
@@ -651,10 +592,8 @@ static int halpern_batch_enqueue_restart(pdlpdev_small_batch* b, int count, cons
   for (int q = 0; q < count; ++q) {
     const int l    = b->list[q];
     pdlpdev_ctx* c = b->ctx[l];
-    const int g    = std::min(grid_for(std::max(c->n, c->m)), kGenericBlocks);
-    b->restart[l]  = RestartBatchArgs{RestartView{c->n, c->m, PDLPDEV_CURRENT, 0, c->dc, c->dr, c->ctl, c->x[0], c->x[1], c->y[0], c->y[1], c->avgx, c->avgy, c->lrx,
-                                                 c->lry, c->sumx, c->sumy, c->part_g},
-                                     g, 0, c->scal_h};
+    b->restart[l]  = restart_batch_args(c, PDLPDEV_CURRENT, 0);
+    const int g    = b->restart[l].g;
     b->hrestart[l] = HalpernRestartArgs{c->n, g, clear, 0, theta[l], c->part_g, c->aty[0], c->aty[1], c->lraty, c->scal, c->scal_h, c->ctl, c->ctl_h, c->hal, c->hal_h};
     for (int i = 0; i < g; ++i) b->blk[blocks++] = make_int2(l, i);
   }
@@ -670,7 +609,7 @@ static int halpern_batch_reset_tail(pdlpdev_small_batch* b, int count)
   std::vector<double> theta(b->K, -1.0);
   for (int q = 0; q < count; ++q) {
     pdlpdev_ctx* c   = b->ctx[b->list[q]];
-    b->at[b->list[q]] = StreamAtCurArgs{c->At.nb, c->At.rb, c->At.hot.off, c->At.hot.idx, c->At.hot.val, c->ctl, c->y[0], c->y[1], c->aty[0], c->aty[1]};
+    b->at[b->list[q]] = stream_at_cur_args(c);
     for (int i = 0; i < c->At.nb; ++i) b->blk[blocks++] = make_int2(b->list[q], i);
     loop_state_touched(c);
   }
@@ -733,59 +672,74 @@ void pdlpdev_small_batch_destroy(pdlpdev_small_batch* b)
 // eval_after (optional): the head of the major iteration that follows the attempts is enqueued right behind them for every LP with
 // eval_after[l].mode >= 0 -- one synchronisation for both; the evaluation runs only if LP l's attempts reached their target (or raised
 // the step-size error), evaluated[l] says whether it did, out_current / out_average then hold its results.
+// Per tier in use ONE launch of the mode's loop kernel, behind them ONE launch of the mode's guarded evaluation, ONE synchronisation.
+// A Halpern batch evaluates T(z^k) in the average slots (mode 3), whatever mode was asked for, takes a result as resident_halpern_period
+// does for one LP (the target reached, no step error, the evaluation ran), and both outputs receive it.
 int pdlpdev_small_batch_run(pdlpdev_small_batch* b, const int32_t* targets, pdlpdev_ctl* ctl, const pdlpdev_small_eval* eval_after, double* out_current,
                             double* out_average, int32_t* evaluated)
 {
   roctx::Range range("pdlp: PDHG attempts (small-LP batch)");
   HIP_TRY(hipSetDevice(b->device));
-  if (b->halpern) return halpern_batch_run(b, targets, ctl, eval_after, out_current, out_average, evaluated);
   const int K = b->K;
   std::vector<char> todo(K, 0);
   for (int l = 0; l < K; ++l) {
     if (evaluated) evaluated[l] = 0;
-    if (targets[l] > 0) {
-      pdlpdev_ctx* c = b->ctx[l];
+    if (targets[l] <= 0) continue;
+    pdlpdev_ctx* c = b->ctx[l];
+    todo[l]        = 1;
+    if (b->halpern) {
+      b->hrun[l] = HalpernResidentArgs{halpern_view(c), c->ctl, c->ctl_h, c->hal, c->hal_h, targets[l], 0};
+      loop_state_touched(c);
+    } else {
       b->run_args[l] = ResidentArgs{small_view(c), c->ctl, c->ctl_h, c->sp, targets[l], 0};
-      todo[l]        = 1;
     }
   }
+  b->stat_periods += 1;
   for (int guard = 0; guard < 1000; ++guard) {
     int count[3] = {0, 0, 0};
     for (int l = 0; l < K; ++l)
       if (todo[l]) b->run_list[b->tier[l] * K + count[b->tier[l]]++] = l;
     if (count[0] + count[1] + count[2] == 0) break;
-    if (count[0]) TRY((launch_resident_batch<256, 2, 8>(b, 0, b->run_list, count[0])));
-    if (count[1]) TRY((launch_resident_batch<512, 2, 16>(b, 1, b->run_list + K, count[1])));
-    if (count[2]) TRY((launch_resident_batch<512, 4, 8>(b, 2, b->run_list + 2 * K, count[2])));
+    for (int tier = 0; tier < 3; ++tier)
+      if (count[tier]) {
+        TRY(b->halpern ? halpern_batch_launch_loop(b->stream, b->device, tier, b->hrun, b->run_list + tier * K, count[tier])
+                       : launch_resident_batch(b, tier, b->run_list + tier * K, count[tier]));
+        b->stat_loop_launches += 1;
+      }
     int nev = 0;
     if (guard == 0 && eval_after) {
       for (int l = 0; l < K; ++l)
         if (todo[l] && eval_after[l].mode >= 0) {
           const int want_linf = eval_after[l].eps_p >= 0.0 && eval_after[l].eps_d >= 0.0;
-          b->major[l] = major_args(b->ctx[l], eval_after[l].mode, eval_after[l].rule_finite, want_linf, eval_after[l].eps_p, eval_after[l].eps_d);
+          b->major[l] = major_args(b->ctx[l], b->halpern ? 3 : eval_after[l].mode, eval_after[l].rule_finite, want_linf, eval_after[l].eps_p, eval_after[l].eps_d);
           b->major[l].guard_target = targets[l];
           b->list[nev++]           = l;
         }
       if (nev) {
-        k_major_small_batch<<<nev, kMajorThreads, b->major_lds, b->stream>>>(b->major, b->list);
-        HIP_TRY(hipGetLastError());
+        TRY(launch_major_batch(b, nev));
+        b->stat_eval_launches += 1;
       }
     }
     HIP_TRY(hipStreamSynchronize(b->stream));
+    b->stat_syncs += 1;
     for (int q = 0; q < nev; ++q) {
-      const int l = b->list[q];
-      if (b->ctx[l]->scal_h[63] != 1.0) continue;
+      const int l          = b->list[q];
+      const pdlpdev_ctx* c = b->ctx[l];
+      if (c->scal_h[63] != 1.0) continue;
+      if (b->halpern && (c->ctl_h->error != 0 || c->ctl_h->steps_taken < targets[l])) continue;
       const bool want_linf = eval_after[l].eps_p >= 0.0 && eval_after[l].eps_d >= 0.0;
-      read_eval(b->ctx[l]->scal_h, want_linf, out_current + (size_t)l * PDLPDEV_EV_COUNT);
-      read_eval(b->ctx[l]->scal_h + 32, want_linf, out_average + (size_t)l * PDLPDEV_EV_COUNT);
+      read_eval(c->scal_h + (b->halpern ? 32 : 0), want_linf, out_current + (size_t)l * PDLPDEV_EV_COUNT);
+      read_eval(c->scal_h + 32, want_linf, out_average + (size_t)l * PDLPDEV_EV_COUNT);
       if (evaluated) evaluated[l] = 1;
     }
     for (int l = 0; l < K; ++l)
       if (todo[l] && (b->ctx[l]->ctl_h->error != 0 || b->ctx[l]->ctl_h->steps_taken >= targets[l])) todo[l] = 0;
   }
-  if (ctl)
-    for (int l = 0; l < K; ++l)
-      if (targets[l] > 0) ctl[l] = *b->ctx[l]->ctl_h;
+  for (int l = 0; l < K; ++l)
+    if (targets[l] > 0) {
+      if (b->halpern) b->ctx[l]->ctl_h_current = true;  // (as resident_halpern_run leaves it: the kernel wrote the pinned mirror)
+      if (ctl) ctl[l] = *b->ctx[l]->ctl_h;
+    }
   return 0;
 }
 
@@ -804,12 +758,9 @@ int pdlpdev_small_batch_major_eval(pdlpdev_small_batch* b, const pdlpdev_small_e
   if (!count) return 0;
   if (b->halpern) {  // the evaluation of T(z^k) in the average slots (mode 3), whatever mode was asked for: both outputs receive it
     for (int q = 0; q < count; ++q) b->major[b->list[q]].mode = 3;
-    TRY(halpern_batch_launch_eval(b->stream, b->device, b->major_lds, b->major, b->list, count));
     b->stat_syncs += 1;
-  } else {
-    k_major_small_batch<<<count, kMajorThreads, b->major_lds, b->stream>>>(b->major, b->list);
   }
-  HIP_TRY(hipGetLastError());
+  TRY(launch_major_batch(b, count));
   HIP_TRY(hipStreamSynchronize(b->stream));
   for (int l = 0; l < b->K; ++l)
     if (req[l].mode >= 0) {
@@ -828,11 +779,8 @@ int pdlpdev_small_batch_restart(pdlpdev_small_batch* b, const int32_t* which, co
   int count = 0, blocks = 0;
   for (int l = 0; l < b->K; ++l)
     if (which[l] >= 0) {
-      pdlpdev_ctx* c = b->ctx[l];
-      const int g    = std::min(grid_for(std::max(c->n, c->m)), kGenericBlocks);
-      b->restart[l]  = RestartBatchArgs{RestartView{c->n, c->m, which[l], unscaled_distances ? unscaled_distances[l] : 0, c->dc, c->dr, c->ctl, c->x[0], c->x[1], c->y[0],
-                                                   c->y[1], c->avgx, c->avgy, c->lrx, c->lry, c->sumx, c->sumy, c->part_g},
-                                       g, 0, c->scal_h};
+      b->restart[l] = restart_batch_args(b->ctx[l], which[l], unscaled_distances ? unscaled_distances[l] : 0);
+      const int g   = b->restart[l].g;
       for (int q = 0; q < g; ++q) b->blk[blocks++] = make_int2(l, q);
       b->list[count++] = l;
     }
@@ -856,9 +804,8 @@ int pdlpdev_small_batch_prepare(pdlpdev_small_batch* b, const int32_t* clear_err
     const bool ce = clear_error && clear_error[l], sw = primal_weight && primal_weight[l] > 0.0;
     if (ce || sw) b->ops[nops++] = CtlOp{b->ctx[l]->ctl, ce ? 1 : 0, sw ? 1 : 0, sw ? primal_weight[l] : 0.0};
     if (compute_aty && compute_aty[l]) {
-      pdlpdev_ctx* c = b->ctx[l];
-      b->at[l]       = StreamAtCurArgs{c->At.nb, c->At.rb, c->At.hot.off, c->At.hot.idx, c->At.hot.val, c->ctl, c->y[0], c->y[1], c->aty[0], c->aty[1]};
-      for (int q = 0; q < c->At.nb; ++q) b->blk[blocks++] = make_int2(l, q);
+      b->at[l] = stream_at_cur_args(b->ctx[l]);
+      for (int q = 0; q < b->at[l].nb; ++q) b->blk[blocks++] = make_int2(l, q);
       ++nat;
     }
   }

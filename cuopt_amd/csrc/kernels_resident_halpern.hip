@@ -361,35 +361,21 @@ HalpernSmallView halpern_view(const pdlpdev_ctx* ctx)
                           ctx->c, ctx->lb, ctx->ub, ctx->lo, ctx->hi, ctx->x[0], ctx->x[1], ctx->y[0], ctx->y[1], ctx->aty[0],
                           ctx->aty[1], ctx->lrx, ctx->lry, ctx->lraty, ctx->avgx, ctx->avgy};
 }
-template <int T, int Q, int U>
-static int launch_resident_halpern(pdlpdev_ctx* ctx, int tier, const HalpernSmallView& V, int target_steps)
-{
-  static PerDeviceOnce once;  // per instantiation
-  TRY(once.run(ctx->device, [&]() -> int {
-    HIP_TRY(hipFuncSetAttribute((const void*)k_pdhg_resident_halpern<T, Q, U>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)resident_lds_bytes(tier)));
-    return 0;
-  }));
-  k_pdhg_resident_halpern<T, Q, U><<<1, T, resident_lds_bytes(tier), ctx->stream>>>(V, ctx->ctl, ctx->ctl_h, ctx->hal, ctx->hal_h, target_steps, 1 << 14);
-  HIP_TRY(hipGetLastError());
-  return 0;
-}
 static int enqueue_resident_halpern(pdlpdev_ctx* ctx, int32_t target_steps)
 {
   const HalpernSmallView V = halpern_view(ctx);
-  const int tier           = resident_tier(ctx->m, ctx->n, ctx->nnz);
-  if (tier == 0) return launch_resident_halpern<256, 2, 8>(ctx, tier, V, target_steps);
-  if (tier == 1) return launch_resident_halpern<512, 2, 16>(ctx, tier, V, target_steps);
-  if (tier == 2) return launch_resident_halpern<512, 4, 8>(ctx, tier, V, target_steps);
-  return fail(-1, "resident Halpern loop: the LP fits no tier");
+  return for_resident_tier(
+    resident_tier(ctx->m, ctx->n, ctx->nnz),
+    [&](auto I) {
+      constexpr ResidentTier r = kResidentTiers[decltype(I)::value];
+      return launch_resident_kernel(k_pdhg_resident_halpern<r.T, r.Q, r.U>, I, ctx->device, ctx->stream, 1, V, ctx->ctl, ctx->ctl_h, ctx->hal, ctx->hal_h,
+                                    target_steps, 1 << 14);
+    },
+    [] { return fail(-1, "resident Halpern loop: the LP fits no tier"); });
 }
 static int enqueue_resident_halpern_eval(pdlpdev_ctx* ctx, int rc_rule_finite_bounds, int want_linf, double eps_rel_primal, double eps_rel_dual, int guard_target)
 {
-  static PerDeviceOnce once;
-  TRY(once.run(ctx->device, [&]() -> int {
-    HIP_TRY(hipFuncSetAttribute((const void*)k_major_small_halpern, hipFuncAttributeMaxDynamicSharedMemorySize, 8192 * 8));
-    return 0;
-  }));
+  TRY(allow_dynamic_lds((const void*)k_major_small_halpern, ctx->device, 8192 * 8));
   MajorSmallArgs A = major_args(ctx, 3, rc_rule_finite_bounds, want_linf, eps_rel_primal, eps_rel_dual);
   A.guard_target   = guard_target;
   const size_t lds = sizeof(double) * (size_t)std::max<int64_t>(ctx->nnz, 1);
@@ -439,33 +425,19 @@ int resident_halpern_period(pdlpdev_ctx* ctx, int32_t target_steps, int rc_rule_
 }
 
 // ---- K LPs in K workgroups: the launches of a Halpern small-LP batch (the batch object and its host code: kernels_resident.hip) ----------
-template <int T, int Q, int U>
-static int launch_resident_halpern_batch(hipStream_t s, int device, int tier, const HalpernResidentArgs* args, const int* list, int count)
-{
-  static PerDeviceOnce once;  // per instantiation
-  TRY(once.run(device, [&]() -> int {
-    HIP_TRY(hipFuncSetAttribute((const void*)k_pdhg_resident_halpern_batch<T, Q, U>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)resident_lds_bytes(tier)));
-    return 0;
-  }));
-  k_pdhg_resident_halpern_batch<T, Q, U><<<count, T, resident_lds_bytes(tier), s>>>(args, list, 1 << 14);
-  HIP_TRY(hipGetLastError());
-  return 0;
-}
 int halpern_batch_launch_loop(hipStream_t s, int device, int tier, const HalpernResidentArgs* args, const int* list, int count)
 {
-  if (tier == 0) return launch_resident_halpern_batch<256, 2, 8>(s, device, tier, args, list, count);
-  if (tier == 1) return launch_resident_halpern_batch<512, 2, 16>(s, device, tier, args, list, count);
-  if (tier == 2) return launch_resident_halpern_batch<512, 4, 8>(s, device, tier, args, list, count);
-  return fail(-1, "resident Halpern batch: no tier %d", tier);
+  return for_resident_tier(
+    tier,
+    [&](auto I) {
+      constexpr ResidentTier r = kResidentTiers[decltype(I)::value];
+      return launch_resident_kernel(k_pdhg_resident_halpern_batch<r.T, r.Q, r.U>, I, device, s, count, args, list, 1 << 14);
+    },
+    [&] { return fail(-1, "resident Halpern batch: no tier %d", tier); });
 }
 int halpern_batch_launch_eval(hipStream_t s, int device, size_t lds, const MajorSmallArgs* args, const int* list, int count)
 {
-  static PerDeviceOnce once;
-  TRY(once.run(device, [&]() -> int {
-    HIP_TRY(hipFuncSetAttribute((const void*)k_major_small_halpern_batch, hipFuncAttributeMaxDynamicSharedMemorySize, 8192 * 8));
-    return 0;
-  }));
+  TRY(allow_dynamic_lds((const void*)k_major_small_halpern_batch, device, 8192 * 8));
   k_major_small_halpern_batch<<<count, kMajorThreads, lds, s>>>(args, list);
   HIP_TRY(hipGetLastError());
   return 0;

@@ -605,26 +605,27 @@ constexpr int kRayMark = 30;  // the accepted-step count the pass ran at, and it
 // the iterate or the control block changed behind the loop's back
 inline void loop_state_touched(pdlpdev_ctx* c) { c->aty_valid = false, c->ctl_h_current = false; }
 
+// A kernel that takes more dynamic LDS than the default limit allows: the attribute is per kernel and device, and set ONCE, under the
+// lock (batch solves create contexts from many threads), the first time the triple (kernel, device, size) comes by.  A kernel's
+// launches all ask for the same size today (jag by WAVES, pb by WIDE, phase P always 160 KiB, the resident loops by tier); the size is
+// part of the key so that one which ever asks for a second size gets it set.  The list is per translation unit: setting a kernel's
+// attribute twice is harmless.
+static int allow_dynamic_lds(const void* kernel, int device, size_t bytes)
+{
+  static std::mutex mu;
+  static std::vector<std::tuple<const void*, int, size_t>> done;
+  std::lock_guard<std::mutex> lock(mu);
+  const std::tuple<const void*, int, size_t> key(kernel, device, bytes);
+  if (std::find(done.begin(), done.end(), key) == done.end()) {
+    HIP_TRY(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    done.push_back(key);
+  }
+  return 0;
+}
+
 // Streams (an HSA queue each: ~2 ms to create), the pinned read-back block and the first arena chunk are handed from
 // a destroyed context to the next one created on the same device: back-to-back small solves (cuOptSolve in a loop,
 // MIP-style re-solves) otherwise spend more time in these three calls than in PDHG.  Never freed (a few per device).
-// hipFuncSetAttribute is per device and must happen before the first launch that asks for > 64 KiB of LDS:
-// one flag per (kernel instantiation, device), taken under a lock (batch solves create contexts from many threads)
-struct PerDeviceOnce {
-  std::mutex m;
-  bool done[64] = {};
-  template <class F>
-  int run(int device, F&& f)
-  {
-    std::lock_guard<std::mutex> lock(m);
-    if (device < 0 || device >= 64) return f();
-    if (done[device]) return 0;
-    const int rc = f();
-    if (rc == 0) done[device] = true;
-    return rc;
-  }
-};
-
 struct Recycled {
   int device;
   hipStream_t stream;

@@ -1,8 +1,7 @@
 // Launch helpers shared by the translation units of the core (pdlp_device.hip: set-up, the attempt, results; pdlp_eval.hip: the major
 // iteration): argument packing for hipExtLaunchKernel-style launches with the context's timing hooks, the per-layout launch wrappers
 // (the two geometries of the jagged kernels, the two launches of a gather-free product), and launch_product, which takes one product
-// of one matrix side to the kernels of the side's layout.  Static state (the "attribute already set" list) is per translation unit:
-// setting a kernel's attribute twice is harmless.
+// of one matrix side to the kernels of the side's layout.  (allow_dynamic_lds, the once-per-kernel LDS attribute: pdlp_ctx.hpp.)
 #pragma once
 #include <algorithm>
 #include <mutex>
@@ -32,21 +31,6 @@ static void launch_k(pdlpdev_ctx* c, void (*kernel)(KArgs...), dim3 grid, dim3 b
     return;
   }
   kernel<<<grid, block, lds, c->stream>>>(static_cast<KArgs>(args)...);
-}
-// A kernel that takes more dynamic LDS than the default limit allows: the attribute is per kernel and device, and set ONCE, under the
-// lock, the first time the triple (kernel, device, size) comes by.  A kernel's launches all ask for the same size today (jag by
-// WAVES, pb by WIDE, phase P always 160 KiB); the size is part of the key so that one which ever asks for a second size gets it set.
-static int allow_dynamic_lds(const void* kernel, int device, size_t bytes)
-{
-  static std::mutex mu;
-  static std::vector<std::tuple<const void*, int, size_t>> done;
-  std::lock_guard<std::mutex> lock(mu);
-  const std::tuple<const void*, int, size_t> key(kernel, device, bytes);
-  if (std::find(done.begin(), done.end(), key) == done.end()) {
-    HIP_TRY(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    done.push_back(key);
-  }
-  return 0;
 }
 // Launch of a jagged-layout kernel: 80 or 160 KiB of dynamic LDS
 template <typename... KArgs, typename... Args>

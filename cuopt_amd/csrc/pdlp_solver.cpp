@@ -362,6 +362,12 @@ pdlpdev_small_eval major_eval_request_at(const cuoptamd_solver* s, int32_t total
   return r;
 }
 pdlpdev_small_eval major_eval_request(const cuoptamd_solver* s) { return major_eval_request_at(s, s->total_iterations, s->ctl.its_since_restart); }
+// an evaluation that ran behind the attempts serves the major iteration that asks for the same (the Halpern mode evaluates T(z^k)
+// whatever average mode is named: compare_mode = false)
+bool same_eval_request(const pdlpdev_small_eval& a, const pdlpdev_small_eval& b, bool compare_mode)
+{
+  return (!compare_mode || a.mode == b.mode) && a.rule_finite == b.rule_finite && a.eps_p == b.eps_p && a.eps_d == b.eps_d;
+}
 // ... and, when the KKT rule decides to restart, for pdlpdev_restart(which, unscaled) -- whose distances then give the new primal
 // weight (major_restart_done).  The plan is what the head hands back to whoever talks to the device.
 struct MajorPlan {
@@ -379,8 +385,7 @@ int major_iteration(cuoptamd_solver* s, bool* terminated)
   pdlpdev_ctx* dev = s->dev;
   const pdlpdev_small_eval rq = major_eval_request(s);
   double ev[PDLPDEV_EV_COUNT], ev_avg[PDLPDEV_EV_COUNT];
-  const pdlpdev_small_eval& fq = s->fused_rq;
-  if (s->fused_eval_ready && fq.mode == rq.mode && fq.rule_finite == rq.rule_finite && fq.eps_p == rq.eps_p && fq.eps_d == rq.eps_d) {
+  if (s->fused_eval_ready && same_eval_request(s->fused_rq, rq, true)) {
     // pdlpdev_run_period evaluated behind the attempts, with the request this major iteration makes
     std::copy(s->fused_ev, s->fused_ev + PDLPDEV_EV_COUNT, ev);
     std::copy(s->fused_ev_avg, s->fused_ev_avg + PDLPDEV_EV_COUNT, ev_avg);
@@ -739,8 +744,7 @@ int halpern_major_iteration(cuoptamd_solver* s, bool* terminated)
   *terminated      = false;
   const pdlpdev_small_eval rq = major_eval_request(s);
   double ev[PDLPDEV_EV_COUNT], ev_t[PDLPDEV_EV_COUNT];
-  const pdlpdev_small_eval& fq = s->fused_rq;
-  if (s->fused_eval_ready && fq.rule_finite == rq.rule_finite && fq.eps_p == rq.eps_p && fq.eps_d == rq.eps_d) {
+  if (s->fused_eval_ready && same_eval_request(s->fused_rq, rq, false)) {
     std::copy(s->fused_ev_avg, s->fused_ev_avg + PDLPDEV_EV_COUNT, ev_t);
   } else {
     DEV(pdlpdev_major_eval(dev, 0, rq.rule_finite, rq.eps_p, rq.eps_d, ev, ev_t));
@@ -1433,12 +1437,14 @@ int cuoptamd_solver_reset(cuoptamd_solver* s, const double* lb, const double* ub
 // primal weight), the iteration budget, then what the attempts need (a cleared step error, A^T y of a fresh iterate).  *stop: the
 // solve is over or the budget is used up (s->result says which); otherwise *target = the accepted-step count (the device's) the
 // attempts run to.  cuoptamd_solver_advance runs one LP through it, cuoptamd_batch_advance K of them in lockstep.
+// the schedule alone: iteration `it` is one at which a major iteration is due
+static bool major_due_at(const cuoptamd_hyper& H, int32_t it) { return (it % H.major_iteration == 0 && it > 0) || it <= H.min_iteration_restart; }
 static bool major_due(const cuoptamd_solver* s)
 {
   const cuoptamd_hyper& H = s->H;
   const int32_t it = s->total_iterations;
   if (halpern_mode(s)) return ((it % H.major_iteration == 0 && it > 0) || s->step_error) && s->major_done_at != it;  // (T(z^k) exists after a step)
-  const bool major = (it % H.major_iteration == 0 && it > 0) || it <= H.min_iteration_restart;
+  const bool major = major_due_at(H, it);
   // should_do_artificial_restart (pdlp_restart_strategy.cu:939-961), Fast1 only
   const bool artificial = H.artificial_restart_in_main_loop && s->ctl.its_since_restart >= H.artificial_restart_threshold * it;
   return (major || artificial || s->step_error) && s->major_done_at != it;
@@ -1557,8 +1563,7 @@ int cuoptamd_solver_advance(cuoptamd_solver* s, int32_t max_new_iterations, cuop
     // the artificial restart of Fast1), its evaluation is enqueued behind the attempts and both come back with one synchronisation.
     const cuoptamd_hyper& H   = s->H;
     const int32_t total_after = s->iteration_offset + target;
-    const bool due_at_target  = (total_after % H.major_iteration == 0 && total_after > 0) || total_after <= H.min_iteration_restart;
-    if (period_path && s->world == 1 && !H.artificial_restart_in_main_loop && due_at_target) {
+    if (period_path && s->world == 1 && !H.artificial_restart_in_main_loop && major_due_at(H, total_after)) {
       s->fused_rq       = major_eval_request_at(s, total_after, s->ctl.its_since_restart + (target - s->ctl.steps_taken));
       int32_t evaluated = 0;
       rc = pdlpdev_run_period(s->dev, target, &s->fused_rq, &s->ctl, s->fused_ev, s->fused_ev_avg, &evaluated);
@@ -1626,11 +1631,16 @@ int cuoptamd_batch_create(cuoptamd_solver** solvers, int K, cuoptamd_batch** out
     }
     ctx[l] = solvers[l]->dev;
   }
+  auto mixed = [&] {
+    return fail(-7, "cuoptamd_batch_create: LP %d runs the %s and others the averaging iteration: a batch of both is not available", first_halpern, kHalpernName);
+  };
+  pdlpdev_batch* dev         = nullptr;
+  pdlpdev_small_batch* small = nullptr;
+  int rc                     = 0;
   if (halpern > 0 && lockstep > 0 && resident == 0) {
     // Halpern solvers on the multi-launch path with cuoptamd_settings::halpern_lockstep set: the shared-matrix lockstep batch
     // (kernels_batch_halpern.hip) iff every member is one
-    if (halpern < K)
-      return fail(-7, "cuoptamd_batch_create: LP %d runs the %s and others the averaging iteration: a batch of both is not available", first_halpern, kHalpernName);
+    if (halpern < K) return mixed();
     if (lockstep < K)
       return fail(-7, "cuoptamd_batch_create: %d of the %d solvers in %s have halpern_lockstep set and the others not: a lockstep batch needs it "
                       "on every member", lockstep, K, kHalpernName);
@@ -1638,50 +1648,30 @@ int cuoptamd_batch_create(cuoptamd_solver** solvers, int K, cuoptamd_batch** out
     for (int l = 0; l < K; ++l)  // (the K-wide products have no ray pass: such LPs run one after the other)
       if (solvers[l]->S.halpern_infeasibility)
         return fail(-7, "cuoptamd_batch_create: LP %d has halpern_infeasibility set: the lockstep batch of the %s does not detect infeasibility", l, kHalpernName);
-    pdlpdev_batch* dev = nullptr;
-    int rc             = pdlpdev_batch_create(&dev, ctx.data(), K);
-    if (rc != 0) {
-      if (dev) pdlpdev_batch_destroy(dev);
-      return fail(rc, "%s", pdlpdev_last_error());
-    }
-    cuoptamd_batch* b = new cuoptamd_batch();
-    b->K = K, b->dev = dev, b->halpern = true;
-    b->s.assign(solvers, solvers + K);
-    *out = b;
-    return 0;
-  }
-  if (halpern > 0) {
-    // Halpern solvers: K workgroups of the resident loop iff every member is one, resident, with cuoptamd_settings::halpern_batch set
-    if (halpern == K && opted == K) {
-      pdlpdev_small_batch* small = nullptr;
-      int rc                     = pdlpdev_small_batch_create_halpern(&small, ctx.data(), K);
-      if (rc != 0) return fail(rc, "cuoptamd_batch_create: %s: %s", kHalpernName, pdlpdev_last_error());
-      cuoptamd_batch* b = new cuoptamd_batch();
-      b->K = K, b->small = small, b->halpern = true;
-      b->s.assign(solvers, solvers + K);
-      *out = b;
-      return 0;
-    }
-    if (halpern < K && opted > 0)
-      return fail(-7, "cuoptamd_batch_create: LP %d runs the %s and others the averaging iteration: a batch of both is not available", first_halpern, kHalpernName);
-    return fail(-7, "cuoptamd_batch_create: LP %d runs the %s, which has no lockstep batch (solve them one after the other, or create every "
-                    "member on the resident path with halpern_batch set: K LPs in K workgroups; or, for LPs over one matrix on the multi-launch "
-                    "path, with halpern_lockstep set: the lockstep batch)", first_halpern, kHalpernName);
-  }
-  // small LPs first: any number of them, any matrices, a workgroup each
-  pdlpdev_small_batch* small = nullptr;
-  int rc                     = pdlpdev_small_batch_create(&small, ctx.data(), K);
-  pdlpdev_batch* dev         = nullptr;
-  if (rc == -7) {  // not the resident path: 2, 4, 8 or 16 LPs over one matrix in lockstep
-    if (K > 16) return fail(-7, "cuoptamd_batch_create: more than 16 LPs need the resident small-LP path (%s)", pdlpdev_last_error());
     rc = pdlpdev_batch_create(&dev, ctx.data(), K);
+  } else if (halpern > 0) {
+    // Halpern solvers: K workgroups of the resident loop iff every member is one, resident, with cuoptamd_settings::halpern_batch set
+    if (halpern < K && opted > 0) return mixed();
+    if (halpern < K || opted < K)
+      return fail(-7, "cuoptamd_batch_create: LP %d runs the %s, which has no lockstep batch (solve them one after the other, or create every "
+                      "member on the resident path with halpern_batch set: K LPs in K workgroups; or, for LPs over one matrix on the multi-launch "
+                      "path, with halpern_lockstep set: the lockstep batch)", first_halpern, kHalpernName);
+    rc = pdlpdev_small_batch_create_halpern(&small, ctx.data(), K);
+    if (rc != 0) return fail(rc, "cuoptamd_batch_create: %s: %s", kHalpernName, pdlpdev_last_error());
+  } else {
+    // small LPs first: any number of them, any matrices, a workgroup each
+    rc = pdlpdev_small_batch_create(&small, ctx.data(), K);
+    if (rc == -7) {  // not the resident path: 2, 4, 8 or 16 LPs over one matrix in lockstep
+      if (K > 16) return fail(-7, "cuoptamd_batch_create: more than 16 LPs need the resident small-LP path (%s)", pdlpdev_last_error());
+      rc = pdlpdev_batch_create(&dev, ctx.data(), K);
+    }
   }
   if (rc != 0) {
     if (dev) pdlpdev_batch_destroy(dev);
     return fail(rc, "%s", pdlpdev_last_error());
   }
   cuoptamd_batch* b = new cuoptamd_batch();
-  b->K = K, b->dev = dev, b->small = small;
+  b->K = K, b->dev = dev, b->small = small, b->halpern = halpern > 0;
   b->s.assign(solvers, solvers + K);
   *out = b;
   return 0;
@@ -1698,19 +1688,25 @@ void cuoptamd_batch_destroy(cuoptamd_batch* b)
 }
 
 // K resident small LPs: every phase of the loop that touches the device is ONE launch over the LPs that are in it
-// (pdlpdev_small_batch_*), the scalar logic in between runs per LP on the host exactly as in cuoptamd_solver_advance
+// (pdlpdev_small_batch_*), the scalar logic in between runs per LP on the host exactly as in cuoptamd_solver_advance.  A round: the
+// evaluation for the major iterations that are due -- one launch, unless it ran behind the attempts with the same request --, the heads
+// per LP on the host, ONE batched restart for the LPs that restart, the targets and what the attempts need first, ONE
+// pdlpdev_small_batch_run with the next evaluation enqueued behind the attempts.  A period of the whole batch is a launch per resident
+// tier in use, one evaluation launch and one synchronisation.  Both iterations go through it; a batch in reflected Halpern mode
+// (cuoptamd_settings::halpern_batch) differs where `halpern` is asked: each LP takes the sequence its own cuoptamd_solver_advance
+// takes (major_iteration / halpern_major_iteration, pdlpdev_run_period).
 static int small_batch_advance(cuoptamd_batch* b, const std::vector<int32_t>& budget_end, std::vector<char>& done)
 {
-  const int K = b->K;
+  const int K        = b->K;
+  const bool halpern = b->halpern;
   std::vector<pdlpdev_small_eval> req(K), ahead(K);
-  std::vector<double> ev((size_t)K * PDLPDEV_EV_COUNT), ev_avg((size_t)K * PDLPDEV_EV_COUNT), dist2(2 * (size_t)K), weight(K);
-  std::vector<int32_t> which(K), unscaled(K), target(K), clear(K), aty(K), evaluated(K, 0);
+  // (Halpern: ev_avg receives the evaluation of T(z^k), the only one the head reads)
+  std::vector<double> ev((size_t)K * PDLPDEV_EV_COUNT), ev_avg((size_t)K * PDLPDEV_EV_COUNT), dist2(2 * (size_t)K), weight(K), theta(K);
+  std::vector<int32_t> restart(K), which(K), unscaled(K), target(K), clear(K), aty(K), evaluated(K, 0);
   std::vector<char> due(K);
   std::vector<MajorPlan> plan(K);
   std::vector<pdlpdev_ctl> ctl(K);
-  auto same_request = [](const pdlpdev_small_eval& a, const pdlpdev_small_eval& c) {
-    return a.mode == c.mode && a.rule_finite == c.rule_finite && a.eps_p == c.eps_p && a.eps_d == c.eps_d;
-  };
+  std::vector<pdlpdev_halpern> hal(K);
   for (;;) {
     // ---- major iterations that are due: one evaluation launch (unless the evaluation already ran behind the attempts), the heads on
     // the host, one restart launch
@@ -1720,34 +1716,58 @@ static int small_batch_advance(cuoptamd_batch* b, const std::vector<int32_t>& bu
       if (done[l] || !major_due(b->s[l])) continue;
       due[l] = 1, any = true;
       const pdlpdev_small_eval rq = major_eval_request(b->s[l]);
-      if (evaluated[l] && same_request(rq, ahead[l])) continue;  // ev / ev_avg of LP l are in place
+      if (evaluated[l] && same_eval_request(rq, ahead[l], !halpern)) continue;  // ev / ev_avg of LP l are in place
       req[l] = rq, launch = true;
+      if (halpern) req[l].mode = 0;
     }
     std::fill(evaluated.begin(), evaluated.end(), 0);
     std::fill(weight.begin(), weight.end(), -1.0);
     if (any) {
-      HostRange range("pdlp: major iterations of a small-LP batch");
+      HostRange range(halpern ? "pdlp: major iterations of a small-LP batch (Halpern)" : "pdlp: major iterations of a small-LP batch");
       int rc = launch ? pdlpdev_small_batch_major_eval(b->small, req.data(), ev.data(), ev_avg.data()) : 0;
       if (rc != 0) return fail(rc, "pdlpdev_small_batch_major_eval: %s", pdlpdev_last_error());
       bool any_restart = false;
       for (int l = 0; l < K; ++l) {
-        which[l] = -1, unscaled[l] = 0;
+        restart[l] = 0, which[l] = -1, unscaled[l] = 0, theta[l] = -1.0;
         if (!due[l]) continue;
-        bool terminated = false;
-        rc = major_head(b->s[l], &ev[(size_t)l * PDLPDEV_EV_COUNT], &ev_avg[(size_t)l * PDLPDEV_EV_COUNT], &terminated, &plan[l]);
+        cuoptamd_solver* s  = b->s[l];
+        const double* e_avg = &ev_avg[(size_t)l * PDLPDEV_EV_COUNT];
+        bool terminated     = false, again = false;
+        if (halpern) {
+          // (halpern_infeasibility: the evaluation kernel left the ray pass's statistics in this LP's pinned block -- no launch here)
+          double ray[4];
+          const bool want_ray = s->S.halpern_infeasibility != 0 && !s->step_error;
+          if (want_ray) {
+            rc = pdlpdev_halpern_eval_infeasibility(s->dev, major_eval_request(s).rule_finite, ray);
+            if (rc != 0) return fail(rc, "pdlpdev_halpern_eval_infeasibility: %s", pdlpdev_last_error());
+          }
+          rc = halpern_major_head(s, e_avg, want_ray ? ray : nullptr, &terminated, &again);
+        } else {
+          rc    = major_head(s, &ev[(size_t)l * PDLPDEV_EV_COUNT], e_avg, &terminated, &plan[l]);
+          again = plan[l].restart;
+        }
         if (rc != 0) return rc;
-        major_was_done(b->s[l], terminated);
+        major_was_done(s, terminated);
         if (terminated) done[l] = 1;
-        else if (plan[l].restart) which[l] = plan[l].which, unscaled[l] = plan[l].unscaled, any_restart = true;
+        else if (again) restart[l] = 1, which[l] = plan[l].which, unscaled[l] = plan[l].unscaled, theta[l] = s->H.primal_weight_update_smoothing, any_restart = true;
       }
-      if (any_restart) {
+      if (any_restart && halpern) {
+        rc = pdlpdev_small_batch_halpern_restart(b->small, restart.data(), theta.data(), nullptr, ctl.data(), hal.data());
+        if (rc != 0) return fail(rc, "pdlpdev_small_batch_halpern_restart: %s", pdlpdev_last_error());
+        for (int l = 0; l < K; ++l)
+          if (restart[l]) {
+            b->s[l]->ctl = ctl[l], b->s[l]->hal = hal[l];
+            halpern_restart_done(b->s[l]);
+          }
+      } else if (any_restart) {
         rc = pdlpdev_small_batch_restart(b->small, which.data(), unscaled.data(), dist2.data());
         if (rc != 0) return fail(rc, "pdlpdev_small_batch_restart: %s", pdlpdev_last_error());
         for (int l = 0; l < K; ++l)
-          if (which[l] >= 0) weight[l] = major_restart_done(b->s[l], plan[l], &dist2[2 * (size_t)l]);
+          if (restart[l]) weight[l] = major_restart_done(b->s[l], plan[l], &dist2[2 * (size_t)l]);
       }
     }
-    // ---- budgets and targets; what the attempts need first (new weights, a cleared step error, A^T y of a fresh iterate)
+    // ---- budgets and targets; what the attempts need first (new weights -- the Halpern restart set its own --, a cleared step error,
+    // A^T y of a fresh iterate -- in Halpern mode it exists since the start of the run)
     any = false;
     bool any_prepare = false;
     for (int l = 0; l < K; ++l) {
@@ -1764,116 +1784,23 @@ static int small_batch_advance(cuoptamd_batch* b, const std::vector<int32_t>& bu
       if (s->need_aty) s->need_aty = false, aty[l] = 1, any_prepare = true;
       // the major iteration these attempts end in (when the target is a boundary of the schedule, the usual case): its evaluation is
       // enqueued right behind them.  The request is what major_eval_request will say once the attempts are done -- verified then.
-      const cuoptamd_hyper& H = s->H;
+      // (Halpern: as cuoptamd_solver_advance's period path asks, which leaves Fast1's artificial restarts out)
       const int32_t it_after = target[l] + s->iteration_offset;
-      if ((it_after % H.major_iteration == 0 && it_after > 0) || it_after <= H.min_iteration_restart) {
+      if (!major_due_at(s->H, it_after)) continue;
+      if (halpern && !s->H.artificial_restart_in_main_loop) {
+        ahead[l]      = major_eval_request_at(s, it_after, s->ctl.its_since_restart + (target[l] - s->ctl.steps_taken));
+        ahead[l].mode = 0;
+      } else if (!halpern) {
         ahead[l]      = major_eval_request(s);
         ahead[l].mode = (target[l] <= 1 && !s->warm_started) ? 0 : 2;
       }
     }
     if (any_prepare) {
-      int rc = pdlpdev_small_batch_prepare(b->small, clear.data(), weight.data(), aty.data());
+      int rc = pdlpdev_small_batch_prepare(b->small, clear.data(), halpern ? nullptr : weight.data(), aty.data());
       if (rc != 0) return fail(rc, "pdlpdev_small_batch_prepare: %s", pdlpdev_last_error());
     }
     if (!any) return 0;
     int rc = pdlpdev_small_batch_run(b->small, target.data(), ctl.data(), ahead.data(), ev.data(), ev_avg.data(), evaluated.data());
-    if (rc != 0) return fail(rc, "pdlpdev_small_batch_run: %s", pdlpdev_last_error());
-    for (int l = 0; l < K; ++l)
-      if (target[l] > 0) {
-        b->s[l]->ctl = ctl[l];
-        advance_after_attempts(b->s[l]);
-      }
-  }
-}
-
-// The same for K resident LPs in reflected Halpern mode (cuoptamd_settings::halpern_batch).  A round: the evaluation of T(z^k) for the
-// major iterations that are due -- one launch, unless it ran behind the steps with the same request --, the heads per LP on the host,
-// ONE batched restart for the LPs that restart, the targets, ONE pdlpdev_small_batch_run with the evaluation enqueued behind the steps.
-// A period of the whole batch is a launch per resident tier in use, one evaluation launch and one synchronisation; each LP goes through
-// exactly the sequence cuoptamd_solver_advance takes it through (halpern_major_iteration, pdlpdev_run_period).
-static int halpern_small_batch_advance(cuoptamd_batch* b, const std::vector<int32_t>& budget_end, std::vector<char>& done)
-{
-  const int K = b->K;
-  std::vector<pdlpdev_small_eval> req(K), ahead(K);
-  std::vector<double> ev((size_t)K * PDLPDEV_EV_COUNT), ev_t((size_t)K * PDLPDEV_EV_COUNT), theta(K);
-  std::vector<int32_t> restart(K), target(K), clear(K), aty(K), evaluated(K, 0);
-  std::vector<char> due(K);
-  std::vector<pdlpdev_ctl> ctl(K);
-  std::vector<pdlpdev_halpern> hal(K);
-  auto same_request = [](const pdlpdev_small_eval& a, const pdlpdev_small_eval& c) {  // (the mode plays no part: T(z^k) is what is evaluated)
-    return a.rule_finite == c.rule_finite && a.eps_p == c.eps_p && a.eps_d == c.eps_d;
-  };
-  for (;;) {
-    bool any = false, launch = false;
-    for (int l = 0; l < K; ++l) {
-      req[l].mode = -1, due[l] = 0;
-      if (done[l] || !major_due(b->s[l])) continue;
-      due[l] = 1, any = true;
-      const pdlpdev_small_eval rq = major_eval_request(b->s[l]);
-      if (evaluated[l] && same_request(rq, ahead[l])) continue;  // ev_t of LP l is in place
-      req[l] = rq, req[l].mode = 0, launch = true;
-    }
-    std::fill(evaluated.begin(), evaluated.end(), 0);
-    if (any) {
-      HostRange range("pdlp: major iterations of a small-LP batch (Halpern)");
-      int rc = launch ? pdlpdev_small_batch_major_eval(b->small, req.data(), ev.data(), ev_t.data()) : 0;
-      if (rc != 0) return fail(rc, "pdlpdev_small_batch_major_eval: %s", pdlpdev_last_error());
-      bool any_restart = false;
-      for (int l = 0; l < K; ++l) {
-        restart[l] = 0, theta[l] = -1.0;
-        if (!due[l]) continue;
-        bool terminated = false, again = false;
-        // (halpern_infeasibility: the evaluation kernel left the ray pass's statistics in this LP's pinned block -- no launch here)
-        double ray[4];
-        const bool want_ray = b->s[l]->S.halpern_infeasibility != 0 && !b->s[l]->step_error;
-        if (want_ray) {
-          rc = pdlpdev_halpern_eval_infeasibility(b->s[l]->dev, major_eval_request(b->s[l]).rule_finite, ray);
-          if (rc != 0) return fail(rc, "pdlpdev_halpern_eval_infeasibility: %s", pdlpdev_last_error());
-        }
-        rc = halpern_major_head(b->s[l], &ev_t[(size_t)l * PDLPDEV_EV_COUNT], want_ray ? ray : nullptr, &terminated, &again);
-        if (rc != 0) return rc;
-        major_was_done(b->s[l], terminated);
-        if (terminated) done[l] = 1;
-        else if (again) restart[l] = 1, theta[l] = b->s[l]->H.primal_weight_update_smoothing, any_restart = true;
-      }
-      if (any_restart) {
-        rc = pdlpdev_small_batch_halpern_restart(b->small, restart.data(), theta.data(), nullptr, ctl.data(), hal.data());
-        if (rc != 0) return fail(rc, "pdlpdev_small_batch_halpern_restart: %s", pdlpdev_last_error());
-        for (int l = 0; l < K; ++l)
-          if (restart[l]) {
-            b->s[l]->ctl = ctl[l], b->s[l]->hal = hal[l];
-            halpern_restart_done(b->s[l]);
-          }
-      }
-    }
-    // ---- budgets and targets; what the steps need first (a cleared step error; A^T y of the iterate exists since the start of the run)
-    any = false;
-    bool any_prepare = false;
-    for (int l = 0; l < K; ++l) {
-      target[l] = 0, clear[l] = 0, aty[l] = 0, ahead[l].mode = -1;
-      if (done[l]) continue;
-      cuoptamd_solver* s = b->s[l];
-      if (!next_target(s, budget_end[l], &target[l])) {
-        done[l] = 1, target[l] = 0;
-        continue;
-      }
-      any = true;
-      if (s->step_error) s->step_error = false, clear[l] = 1, any_prepare = true;
-      if (s->need_aty) s->need_aty = false, aty[l] = 1, any_prepare = true;
-      // the major iteration these steps end in: its evaluation is enqueued behind them (cuoptamd_solver_advance's period path)
-      const cuoptamd_hyper& H = s->H;
-      const int32_t it_after = target[l] + s->iteration_offset;
-      if (!H.artificial_restart_in_main_loop && ((it_after % H.major_iteration == 0 && it_after > 0) || it_after <= H.min_iteration_restart)) {
-        ahead[l]      = major_eval_request_at(s, it_after, s->ctl.its_since_restart + (target[l] - s->ctl.steps_taken));
-        ahead[l].mode = 0;
-      }
-    }
-    if (any_prepare) {
-      int rc = pdlpdev_small_batch_prepare(b->small, clear.data(), nullptr, aty.data());
-      if (rc != 0) return fail(rc, "pdlpdev_small_batch_prepare: %s", pdlpdev_last_error());
-    }
-    if (!any) return 0;
-    int rc = pdlpdev_small_batch_run(b->small, target.data(), ctl.data(), ahead.data(), ev.data(), ev_t.data(), evaluated.data());
     if (rc != 0) return fail(rc, "pdlpdev_small_batch_run: %s", pdlpdev_last_error());
     for (int l = 0; l < K; ++l)
       if (target[l] > 0) {
@@ -1908,7 +1835,7 @@ int cuoptamd_batch_advance(cuoptamd_batch* b, int32_t max_new_iterations, cuopta
     }
     return rc;
   };
-  if (b->small) return leave(b->halpern ? halpern_small_batch_advance(b, budget_end, done) : small_batch_advance(b, budget_end, done));
+  if (b->small) return leave(small_batch_advance(b, budget_end, done));
   std::vector<pdlpdev_ctl> ctl(K);
   for (;;) {
     bool any = false;

@@ -1,7 +1,10 @@
 // What the two translation units of the resident small-LP path share (kernels_resident.hip: the averaging loop, its evaluation and the
 // K-workgroup batch; kernels_resident_halpern.hip: the reflected-Halpern loop and its evaluation): the row sum every one-workgroup
-// kernel uses, the three tiers, and the argument record + row walker of the one-workgroup evaluation.
+// kernel uses, the three tiers and the one place that takes a tier to its kernel instantiation (for_resident_tier), and the argument
+// record + row walker of the one-workgroup evaluation.
 #pragma once
+#include <type_traits>
+
 #include "pdlp_ctx.hpp"
 #include "pdlp_layouts.hpp"
 
@@ -26,6 +29,28 @@ inline size_t resident_lds_bytes(int tier)
 {
   const ResidentTier& r = kResidentTiers[tier];
   return sizeof(double) * (size_t)r.T * (7 * r.Q + r.U);
+}
+// The one place that takes a tier to its entry of kResidentTiers at compile time: f(std::integral_constant<int, I>) for tier I --
+//   [&](auto I) { constexpr ResidentTier r = kResidentTiers[decltype(I)::value]; return launch_resident_kernel(kernel<r.T, r.Q, r.U>, I, ...); }
+// -- and none() for a value that is no tier.
+template <class F, class None>
+static int for_resident_tier(int tier, F&& f, None&& none)
+{
+  switch (tier) {
+    case 0: return f(std::integral_constant<int, 0>{});
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    default: return none();
+  }
+}
+// `blocks` workgroups of a tier's instantiation of a loop kernel, enqueued on `s`, the kernel's LDS attribute set first
+template <class... KArgs, class... Args>
+static int launch_resident_kernel(void (*kernel)(KArgs...), int tier, int device, hipStream_t s, int blocks, Args... args)
+{
+  TRY(allow_dynamic_lds((const void*)kernel, device, resident_lds_bytes(tier)));
+  kernel<<<blocks, kResidentTiers[tier].T, resident_lds_bytes(tier), s>>>(args...);
+  HIP_TRY(hipGetLastError());
+  return 0;
 }
 
 // single-workgroup head of a major iteration (pdlpdev_major_eval) for LPs on the resident path

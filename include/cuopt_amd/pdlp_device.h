@@ -406,8 +406,9 @@ int pdlpdev_small_batch_halpern_restart(pdlpdev_small_batch* batch, const int32_
                                         pdlpdev_halpern* hal);
 /* hal[l], l < K: the Halpern scalars of every LP as the last _run / _halpern_restart / _reset left them in their pinned mirrors */
 int pdlpdev_small_batch_get_halpern(pdlpdev_small_batch* batch, pdlpdev_halpern* hal);
-/* out = {Halpern batch (0 / 1), resident tiers in use, then for a Halpern batch: launches of the loop kernel, launches of the evaluation
- * behind it, _run calls, restart rounds, resets, synchronisations (= runs + restart rounds + resets + separate _major_eval calls)} */
+/* out = {Halpern batch (0 / 1), resident tiers in use, launches of the loop kernel, launches of the evaluation behind it, _run calls,
+ * then restart rounds and resets (counted for a Halpern batch), synchronisations (a Halpern batch: = runs + restart rounds + resets +
+ * separate _major_eval calls; an averaging batch: those of its runs)} */
 int pdlpdev_small_batch_stats(pdlpdev_small_batch* batch, int64_t out[8]);
 /* re-arm the loop after the step-size error flag was raised (take_step resets valid_step_size_,
  * pdlp.cu:1190) */

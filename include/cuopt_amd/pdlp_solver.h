@@ -324,7 +324,8 @@ int cuoptamd_batch_branch(cuoptamd_batch* batch, const int32_t* var, const doubl
 int cuoptamd_batch_solution_views(cuoptamd_batch* batch, const double** x, const double** y, const double** rc);
 void cuoptamd_batch_destroy(cuoptamd_batch* batch);
 /* counters of a small-LP batch (pdlpdev_small_batch_stats): {Halpern batch (0 / 1), resident tiers in use, loop launches, evaluation
- * launches behind the loop, runs (periods), restart rounds, resets, synchronisations}; -7: not a small-LP batch */
+ * launches behind the loop, runs (periods), restart rounds, resets, synchronisations}; restart rounds and resets are counted for a batch
+ * in reflected Halpern mode, and an averaging batch counts the synchronisations of its runs only; -7: not a small-LP batch */
 int cuoptamd_batch_stats(cuoptamd_batch* batch, int64_t out[8]);
 /* the device-layer batch behind it (pdlpdev_batch_time_kernels) */
 struct pdlpdev_batch* cuoptamd_batch_device(cuoptamd_batch* batch);

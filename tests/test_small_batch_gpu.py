@@ -129,6 +129,40 @@ def test_budgets_resume_where_they_stopped(golden_problems):
     batch.close()
 
 
+def test_budgets_that_end_on_a_period(golden_problems):
+    """pieces of 80 and 40 iterations end exactly where a major iteration is due: the evaluation enqueued behind the attempts is the one
+    the next call's major iteration uses (test_halpern_small_batch_gpu has the twin for the other iteration)"""
+    problems = family(golden_problems, 3)
+    chunks = (80, 40, 2 ** 31 - 1)
+    want = singles(problems, chunks=chunks, tol=1e-6, iteration_limit=LIMIT)
+    solvers = [capi.Solver(p, tol=1e-6, iteration_limit=LIMIT) for p in problems]
+    batch = capi.SmallBatch(solvers)
+    for c in chunks:
+        got = batch.advance(c)
+    for l, s in enumerate(solvers):
+        same(want[l][0], got[l])
+        for u, v in zip(want[l][1], s.solution()):
+            np.testing.assert_array_equal(u, v)
+    batch.close()
+
+
+def test_the_counters_of_an_averaging_batch(golden_problems):
+    """one LP per base problem (all three tiers), 400 iterations that no tolerance ends: every run of the batch is one launch per tier in
+    use (a relaunch needs 16384 attempts short of a target at most 40 steps away) and at most one evaluation launch behind them"""
+    solvers = [capi.Solver(p, tol=0.0) for p in family(golden_problems, 6)]
+    batch = capi.SmallBatch(solvers)
+    got = batch.advance(400)
+    assert [r["steps_taken"] for r in got] == [400] * 6
+    st = batch.stats()
+    print(st)
+    assert st["halpern"] == 0 and st["tiers"] == 3
+    assert st["loop_launches"] == st["tiers"] * st["periods"]
+    assert 1 <= st["eval_launches"] <= st["periods"]
+    batch.close()
+    for s in solvers:
+        s.close()
+
+
 def test_re_solves_through_one_batch(golden_problems):
     """config 5's pattern: the same solvers are reset to new bounds, warm-started from the previous primal / dual, and advanced again
     through the SAME batch object (relaxed_lp.cu:74-108)"""
