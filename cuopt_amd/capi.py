@@ -52,7 +52,7 @@ class Ctl(C.Structure):
                 ("last_movement", c_double), ("last_dx2", c_double), ("last_dy2", c_double),
                 ("k", c_int), ("cur", c_int), ("pending_avg", c_int), ("steps_taken", c_int),
                 ("attempts", c_int), ("target_steps", c_int), ("error", c_int),
-                ("its_since_restart", c_int)]
+                ("its_since_restart", c_int), ("zskip", c_int), ("zs_nonzeros", c_int)]
 
 
 class StepParams(C.Structure):
@@ -374,7 +374,7 @@ BUF = {n: i for i, n in enumerate(
     ["X", "Y", "X_OTHER", "Y_OTHER", "ATY", "ATY_OTHER", "XBAR", "SUM_X", "SUM_Y", "AVG_X", "AVG_Y",
      "DROW", "DCOL", "A_VALUES", "AT_VALUES", "C", "LB", "UB", "LO", "HI", "RC_CURRENT", "RC_AVERAGE",
      "LAST_RESTART_X", "LAST_RESTART_Y", "ATY_U_CURRENT", "ATY_U_AVERAGE", "LAST_RESTART_ATY",
-     "AX_U_CURRENT", "AX_U_AVERAGE"])}
+     "AX_U_CURRENT", "AX_U_AVERAGE", "PART_A", "PART_AT", "XBAR_MASK", "ZS_LAUNCHES"])}
 KERNEL = {n: i for i, n in enumerate(
     ["PRIMAL", "SPMV_A_DUAL", "SPMV_AT_STEP", "STEP_DECISION", "SPMV_A_PLAIN", "SPMV_AT_PLAIN"])}
 EV = {n: i for i, n in enumerate(

@@ -617,6 +617,7 @@ int pdlpdev_clone_shared(pdlpdev_ctx** out, pdlpdev_ctx* parent)
   c->scal_h = nullptr, c->ctl_h = nullptr;  // (the parent's pinned block until the clone has its own: a clone that fails below must not free it)
   // (likewise the parent's Halpern block and anchor: the mode is the clone's to switch on -- pdlpdev_set_halpern gives it its own)
   c->halpern = false, c->lraty = nullptr, c->hal = nullptr, c->hal_h = nullptr;
+  c->xmask = nullptr, c->zcount = nullptr, c->zs_mode = 0;  // (the parent's bitmap of ITS xbar: a clone run on its own gathers every entry)
   c->clones_alive = 0, c->batches_alive = 0, c->rows_private = false;
   c->bytes = 0, c->slab = nullptr, c->slab_cap = c->slab_used = 0, c->arena = nullptr, c->arena_used = 0, c->first_chunk = nullptr;
   c->bestx = c->besty = c->bestrc = nullptr;

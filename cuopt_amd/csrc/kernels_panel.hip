@@ -17,7 +17,13 @@ k_panel_a_dual(PanelView P, const pdlpdev_ctl* __restrict__ ctl, const double* _
 {
   if (!loop_active(ctl)) return;
   DualEpilogue e = DualEpilogue::make(ctl, y0, y1, lo, hi, sumy, ycopy, push);
-  panel_block<SEG>(P, xbar, e, part);
+  const bool masked = !SEG && P.zmask != nullptr && (P.zforce != 0 || ctl->zskip != 0);  // (the flag: part of the control block this kernel reads anyway)
+  // TEST INSTRUMENTATION (tests/test_zero_skip_gpu.py reads it as ZS_LAUNCHES and fails without it): the launches that took the masked
+  // path, one add without return per launch by one lane, into the word behind the bitmap's quads -- the only evidence from INSIDE the
+  // kernel that the branch ran (the host launch site is not passed under graph replay, and the flag is the device's)
+  if (masked && blockIdx.x == 0 && threadIdx.x == 0)
+    __hip_atomic_fetch_add(const_cast<unsigned long long*>(P.zmask) + 2 * ((size_t)(P.zcols + 127) / 128), 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  panel_block_zs<SEG>(P, xbar, e, part, masked);
   if (push) p2pdev::count_exchange(push);
 }
 

@@ -600,6 +600,16 @@ static int create_impl(pdlpdev_ctx** out, int device, int32_t m, int32_t n, cons
     TRY(pick_layout(ctx, &ctx->At, ctx->tmp_m, ctx->tmp_n));
     lap("layout autotune");
   }
+  // Zero skip: the bitmap of xbar's non-zeros (whole 16-byte quads) and the counts -- only for a context whose A product can ever read
+  // them (attempt_xmask, pdlp_device.hip: one GPU, A in the row-sum panels), and as the LAST allocation of the set-up, so that no
+  // other buffer of any context lies anywhere else than it would without them.
+  if (one_gpu && !ctx->small_resident && ctx->A.layout() == pdlpdev_ctx::MatrixSide::kPanel && !ctx->A.pan.v.seg && cuopt_amd::tune_int("zero_skip", 1) != 0) {
+    const size_t words = 2 * (((size_t)n + 127) / 128);
+    ctx->zs_mode = cuopt_amd::tune_int("zero_skip", 1) == 2 ? 2 : 1;
+    TRY(dev_alloc(ctx, &ctx->zcount, (size_t)grid_for(n)));
+    TRY(dev_alloc(ctx, &ctx->xmask, words + 2));  // (+ the quad of the masked launches' counter)
+    HIP_TRY(hipMemsetAsync(ctx->xmask, 0, (words + 2) * sizeof(unsigned long long), ctx->stream));
+  }
   HIP_TRY(hipStreamSynchronize(ctx->stream));
   scratch_free(ctx);  // (the layout constructions' temporaries: both sides are built)
   return 0;

@@ -433,6 +433,13 @@ struct pdlpdev_ctx {
   // iterate state
   double *x[2] = {nullptr, nullptr}, *y[2] = {nullptr, nullptr}, *aty[2] = {nullptr, nullptr};
   double *xbar = nullptr, *sumx = nullptr, *sumy = nullptr, *avgx = nullptr, *avgy = nullptr;
+  // Zero skip: one bit per column, set where xbar is not 0.0 (k_primal's ballots; ceil(n / 128) 16-byte quads, the unit the panels of A
+  // fetch).  CUOPT_AMD_TUNE=zero_skip=0, or an A that is not in the row-sum panels: not allocated, every entry of xbar is gathered as before; 1 (default), 2: in use wherever
+  // attempt_xmask (pdlp_device.hip) says it applies.  pdlpdev_clone_shared nulls it in the clone.  One more
+  // word behind the quads counts the launches of the A product that took the masked path (PDLPDEV_BUF_ZS_LAUNCHES: tests).
+  unsigned long long* xmask = nullptr;
+  int* zcount = nullptr;  // k_primal's per-workgroup counts of the set bits (grid_for(n) of them): the density guard's input
+  int zs_mode = 0;        // 1: the product skips when the control block's flag is up (pdlpdev_ctl::zskip); 2: always
   double *lrx = nullptr, *lry = nullptr, *rc[2] = {nullptr, nullptr};
   double *tmp_n = nullptr, *tmp_m = nullptr;
   double *ax_u[3] = {nullptr, nullptr, nullptr}, *aty_u[3] = {nullptr, nullptr, nullptr};  // unscaled A x / A^T y of pdlpdev_eval(which)

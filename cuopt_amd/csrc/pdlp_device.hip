@@ -120,12 +120,21 @@ __global__ void __launch_bounds__(kBlock) k_finalize(const double* __restrict__ 
 // ================================================================================================
 // (1) primal projection + extrapolation (primal_projection functor, utils.cuh:80-95) fused with the
 //     deferred averaging of the previously accepted iterate (weighted_average_solution.cu:73-108).
-__global__ void __launch_bounds__(kBlock)
-k_primal(int n, const pdlpdev_ctl* __restrict__ ctl, double* __restrict__ x0, double* __restrict__ x1,
+// primal_body<false> is k_primal as it was, argument list included; <true> (k_primal_zs) also writes the bitmap of xbar's non-zeros and
+// counts them.
+template <bool ZS>
+__device__ __forceinline__ void
+primal_body(int n, const pdlpdev_ctl* __restrict__ ctl, double* __restrict__ x0, double* __restrict__ x1,
          const double* __restrict__ aty0, const double* __restrict__ aty1,
          const double* __restrict__ c, const double* __restrict__ lb, const double* __restrict__ ub,
-         double* __restrict__ xbar, double* __restrict__ sumx, const p2pdev::Push* __restrict__ push, pdlpdev_ctx::UniformBounds ubd)
+         double* __restrict__ xbar, double* __restrict__ sumx, const p2pdev::Push* __restrict__ push, pdlpdev_ctx::UniformBounds ubd,
+         unsigned long long* __restrict__ xmask, int* __restrict__ zcount)
 {
+  // (xmask, may be null: one bit per column, set where xbar is not 0.0 -- what the panels of A need to skip the gathers of zeros.  A
+  //  wave's 64 columns are consecutive and start at a multiple of 64, so its ballot is one whole word of the bitmap; lanes beyond n
+  //  have left the loop and count as zeros.  -0.0 compares equal to 0.0: clear; NaN and infinities: set.
+  //  zcount, with xmask: the set bits per workgroup, an exact integer that k_step_decision_zs adds up for the density guard.)
+  [[maybe_unused]] int nz = 0;
   // (ubd: every lower / upper bound is the same 0 or infinity -- x >= 0 is the usual LP -- so the bound arrays, 16 of the kernel's
   //  72 bytes per column, are not read at all; scaling keeps 0 and infinity what they are)
   if (!loop_active(ctl)) return;
@@ -144,13 +153,46 @@ k_primal(int n, const pdlpdev_ctl* __restrict__ ctl, double* __restrict__ x0, do
     xn[j]                 = next;
     const double xb       = next - xj + next;
     xbar[j]               = xb;
+    if constexpr (ZS) {
+      const unsigned long long bits = __ballot(xb != 0.0);
+      if ((threadIdx.x & 63) == 0) xmask[j >> 6] = bits;
+      nz += __popcll(bits);
+    }
     if (push)  // sharded solve, direct peer transport: this rank's slice of xbar lands in every OTHER rank's block (its own copy is
                // the ordinary store above: write-through stores cost 17 us per attempt at C3 and buy nothing at home)
       for (int q = 0; q < push->world; ++q)
         if (push->wants(q, j)) p2pdev::put(push->slot(q) + j, xb);
     if (pend) sumx[j] = sumx[j] + weight * xj;
   }
+  if constexpr (ZS) {  // (lane 0 of a wave is in every iteration its wave makes, so its count is the wave's)
+    __shared__ int wave_nz[kBlock / 64];
+    if ((threadIdx.x & 63) == 0) wave_nz[threadIdx.x >> 6] = nz;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      int sum = 0;
+#pragma unroll
+      for (int w = 0; w < kBlock / 64; ++w) sum += wave_nz[w];
+      zcount[blockIdx.x] = sum;
+    }
+  }
   if (push) p2pdev::count_exchange(push);
+}
+__global__ void __launch_bounds__(kBlock)
+k_primal(int n, const pdlpdev_ctl* __restrict__ ctl, double* __restrict__ x0, double* __restrict__ x1,
+         const double* __restrict__ aty0, const double* __restrict__ aty1,
+         const double* __restrict__ c, const double* __restrict__ lb, const double* __restrict__ ub,
+         double* __restrict__ xbar, double* __restrict__ sumx, const p2pdev::Push* __restrict__ push, pdlpdev_ctx::UniformBounds ubd)
+{
+  primal_body<false>(n, ctl, x0, x1, aty0, aty1, c, lb, ub, xbar, sumx, push, ubd, nullptr, nullptr);
+}
+__global__ void __launch_bounds__(kBlock)
+k_primal_zs(int n, const pdlpdev_ctl* __restrict__ ctl, double* __restrict__ x0, double* __restrict__ x1,
+            const double* __restrict__ aty0, const double* __restrict__ aty1,
+            const double* __restrict__ c, const double* __restrict__ lb, const double* __restrict__ ub,
+            double* __restrict__ xbar, double* __restrict__ sumx, pdlpdev_ctx::UniformBounds ubd,
+            unsigned long long* __restrict__ xmask, int* __restrict__ zcount)
+{
+  primal_body<true>(n, ctl, x0, x1, aty0, aty1, c, lb, ub, xbar, sumx, nullptr, ubd, xmask, zcount);
 }
 
 
@@ -189,11 +231,17 @@ static_assert(kDecisionThreads == kHalpernDecisionThreads, "k_halpern_decision r
 // Latency is all that matters here (one workgroup on the critical path of every attempt): the control block is
 // read once into registers (uniform -> scalar loads) and written back once, the two pow() of the step-size rule
 // are evaluated by the last wave while the others fetch partials, the sums use DPP lane permutes.
+// ZS (k_step_decision_zs): the density guard of the zero skip rides along -- the non-zeros of xbar that k_primal's workgroups counted
+// are added up as a fourth sum (integers below 2^31 as doubles: exact in any order) and set the flag the NEXT attempt's A product
+// reads: up at 25 % zeros or more, down at 13 % or fewer (measured break-even on the 1e6 x 1e6 LP: docs/design/09_next.md item
+// 9), unchanged in between; zmode 2 keeps it up.  The flag never changes a result, only which code path forms it.
+template <bool ZS = false>
 __device__ __forceinline__ void step_decision_workgroup(pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ part_dy, int nb_dy,
                                                         const double* __restrict__ part_t, int nb_t, const double* __restrict__ dy2_reduced,
-                                                        const pdlpdev_step_params& sp)
+                                                        const pdlpdev_step_params& sp, const int* __restrict__ zcount = nullptr, int nb_z = 0,
+                                                        int zn = 0, int zmode = 0)
 {
-  __shared__ double red[3 * 16];
+  __shared__ double red[(ZS ? 4 : 3) * 16];
   __shared__ double pw[2];
   pdlpdev_ctl lc = *ctl;
   if (!(lc.error == 0 && lc.steps_taken < lc.target_steps)) return;
@@ -202,7 +250,7 @@ __device__ __forceinline__ void step_decision_workgroup(pdlpdev_ctl* __restrict_
     const double knext = (double)(lc.k + 1) + 1.0;
     pw[t - (kDecisionThreads - 2)] = pow(knext, t == kDecisionThreads - 2 ? -sp.reduction_exponent : -sp.growth_exponent);
   }
-  double acc[3] = {0.0, 0.0, 0.0};
+  double acc[ZS ? 4 : 3] = {0.0, 0.0, 0.0};
   if (dy2_reduced == nullptr) {
 #pragma unroll 4
     for (int i = t; i < nb_dy; i += kDecisionThreads) acc[0] += part_dy[i];
@@ -212,10 +260,25 @@ __device__ __forceinline__ void step_decision_workgroup(pdlpdev_ctl* __restrict_
     acc[1] += part_t[i];
     acc[2] += part_t[nb_t + i];
   }
-  block_sum_fast<3, kDecisionThreads / 64>(acc, red);
+  if constexpr (ZS) {
+    acc[3] = 0.0;
+#pragma unroll 2
+    for (int i = t; i < nb_z; i += kDecisionThreads) acc[3] += (double)zcount[i];
+  }
+  block_sum_fast<ZS ? 4 : 3, kDecisionThreads / 64>(acc, red);
   if (t != 0) return;
   apply_step_decision(&lc, dy2_reduced ? dy2_reduced[0] : acc[0], acc[1], acc[2], sp, pw);
-  *ctl = lc;
+  if constexpr (ZS) {
+    const long long nonzeros = (long long)acc[3];
+    lc.zs_nonzeros           = (int32_t)nonzeros;
+    if (zmode == 2 || nonzeros * 4 <= 3ll * zn) lc.zskip = 1;
+    else if (nonzeros * 100 >= 87ll * zn) lc.zskip = 0;
+    *ctl = lc;
+  } else {
+    // (the decision without the guard neither reads nor writes the guard's two fields at the block's end: the loads and stores of this
+    //  latency-bound kernel are the ones it had before the block grew)
+    __builtin_memcpy(ctl, &lc, offsetof(pdlpdev_ctl, zskip));
+  }
 }
 __global__ void __launch_bounds__(kDecisionThreads)
 k_step_decision(pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ part_dy, int nb_dy,
@@ -223,6 +286,13 @@ k_step_decision(pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ part_d
                 pdlpdev_step_params sp)
 {
   step_decision_workgroup(ctl, part_dy, nb_dy, part_t, nb_t, dy2_reduced, sp);
+}
+// (single GPU, averaging modes, with the bitmap of xbar in use: attempt_xmask)
+__global__ void __launch_bounds__(kDecisionThreads)
+k_step_decision_zs(pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ part_dy, int nb_dy,
+                   const double* __restrict__ part_t, int nb_t, pdlpdev_step_params sp, const int* __restrict__ zcount, int nb_z, int zn, int zmode)
+{
+  step_decision_workgroup<true>(ctl, part_dy, nb_dy, part_t, nb_t, nullptr, sp, zcount, nb_z, zn, zmode);
 }
 // the decisions of the K LPs of a shared-matrix batch (kernels_batch.hip): workgroup <-> LP, each exactly k_step_decision
 __global__ void __launch_bounds__(kDecisionThreads)
@@ -861,8 +931,28 @@ int pdlpdev_compute_aty(pdlpdev_ctx* ctx)
 // the products of an attempt and the plain ones, each in its side's layout (launch_product)
 static inline HalpernArgs halpern_args(const pdlpdev_ctx* ctx) { return HalpernArgs{ctx->hal, ctx->avgx, ctx->avgy, ctx->lrx, ctx->lry, ctx->lraty}; }
 // (Halpern mode: the twins' kernels; its A^T product gathers y' from its own buffer, which the kernels take inside HalpernArgs)
+// Zero skip (CUOPT_AMD_TUNE=zero_skip, pdlp_ctx.hpp): the bitmap of xbar's non-zeros that k_primal writes and k_panel_a_dual<false> reads in
+// the attempts of a single-GPU context in the averaging modes whose A is in the row-sum panels (of any slab width: the layout is
+// the one it would be without the bitmap); null everywhere else (sharded dataflows hand k_primal slices, Halpern mode has its own products).  Both launches of an
+// attempt ask here, so the bits a product reads are always those of the xbar it gathers.
+static unsigned long long* attempt_xmask(const pdlpdev_ctx* ctx)
+{
+  const pdlpdev_ctx::Panels& pn = ctx->A.pan;
+  if (!ctx->xmask || ctx->comm || ctx->owner || ctx->rsag || ctx->halpern) return nullptr;
+  if (ctx->A.layout() != pdlpdev_ctx::MatrixSide::kPanel || pn.v.seg) return nullptr;
+  return ctx->xmask;
+}
+// the primal step of a single-GPU attempt: with the bitmap where the A product reads it, else the kernel as it always was
+static void launch_primal(pdlpdev_ctx* ctx)
+{
+  const int n = ctx->n;
+  if (unsigned long long* xmask = attempt_xmask(ctx))
+    return launch_k(ctx, k_primal_zs, grid_for(n), kBlock, 0, n, ctx->ctl, ctx->x[0], ctx->x[1], ctx->aty[0], ctx->aty[1], ctx->c, ctx->lb, ctx->ub, ctx->xbar, ctx->sumx, ctx->ubd, xmask, ctx->zcount);
+  launch_k(ctx, k_primal, grid_for(n), kBlock, 0, n, ctx->ctl, ctx->x[0], ctx->x[1], ctx->aty[0], ctx->aty[1], ctx->c, ctx->lb, ctx->ub, ctx->xbar, ctx->sumx, (const p2pdev::Push*)nullptr, ctx->ubd);
+}
 static void launch_a_dual(pdlpdev_ctx* ctx, double* ycopy = nullptr, const p2pdev::Push* push = nullptr)
 {
+  ctx->A.pan.v.zmask = attempt_xmask(ctx), ctx->A.pan.v.zcols = ctx->n, ctx->A.pan.v.zforce = ctx->zs_mode == 2;  // (the view travels by value with every launch)
   const Gathered g = Gathered::fixed(ctx->xbar, true);
   const auto pre  = std::make_tuple(ctx->ctl);
   const auto vecs = std::make_tuple(ctx->xbar);
@@ -892,6 +982,9 @@ void launch_plain(pdlpdev_ctx* ctx, int transpose, const double* vec, double* ou
 static void launch_decision(pdlpdev_ctx* ctx)
 {
   if (ctx->halpern) return launch_k(ctx, k_halpern_decision, 1, kDecisionThreads, 0, ctx->ctl, ctx->hal, ctx->A.part, ctx->A.partials(), ctx->At.part, ctx->At.partials());
+  if (attempt_xmask(ctx))
+    return launch_k(ctx, k_step_decision_zs, 1, kDecisionThreads, 0, ctx->ctl, ctx->A.part, ctx->A.partials(), ctx->At.part, ctx->At.partials(), ctx->sp, ctx->zcount,
+                    grid_for(ctx->n), ctx->n, ctx->zs_mode);
   launch_k(ctx, k_step_decision, 1, kDecisionThreads, 0, ctx->ctl, ctx->A.part, ctx->A.partials(), ctx->At.part, ctx->At.partials(), nullptr, ctx->sp);
 }
 
@@ -989,7 +1082,7 @@ static int enqueue_attempt(pdlpdev_ctx* ctx)
     LAUNCH_CHECK();
     return 0;
   }
-  launch_k(ctx, k_primal, grid_for(n), kBlock, 0, n, ctx->ctl, ctx->x[0], ctx->x[1], ctx->aty[0], ctx->aty[1], ctx->c, ctx->lb, ctx->ub, ctx->xbar, ctx->sumx, (const p2pdev::Push*)nullptr, ctx->ubd);
+  launch_primal(ctx);
   launch_a_dual(ctx);
   if (!ctx->comm) {
     launch_at_step(ctx);
@@ -1408,6 +1501,16 @@ static int64_t locate_buffer(pdlpdev_ctx* ctx, int id, double** ptr)
       break;
     case PDLPDEV_BUF_AX_U_CURRENT: src = ctx->ax_u[PDLPDEV_CURRENT], count = m; break;
     case PDLPDEV_BUF_AX_U_AVERAGE: src = ctx->ax_u[PDLPDEV_AVERAGE], count = m; break;
+    case PDLPDEV_BUF_PART_A: src = ctx->A.part, count = ctx->A.partials(); break;
+    case PDLPDEV_BUF_PART_AT: src = ctx->At.part, count = 2 * (int64_t)ctx->At.partials(); break;
+    case PDLPDEV_BUF_ZS_LAUNCHES:
+      if (!ctx->xmask) { fail(-1, "buffer %d: this context has no bitmap of xbar (CUOPT_AMD_TUNE=zero_skip=0, or A is not in the row-sum panels)", id); return -1; }
+      src = reinterpret_cast<double*>(ctx->xmask + 2 * (((size_t)n + 127) / 128)), count = 1;
+      break;
+    case PDLPDEV_BUF_XBAR_MASK:  // (64-bit words, the size of the doubles the hook copies; all zero where no attempt writes it)
+      if (!ctx->xmask) { fail(-1, "buffer %d: this context has no bitmap of xbar (CUOPT_AMD_TUNE=zero_skip=0, or A is not in the row-sum panels)", id); return -1; }
+      src = reinterpret_cast<double*>(ctx->xmask), count = (n + 63) / 64;
+      break;
     default: fail(-1, "unknown buffer %d", id); return -1;
   }
   *ptr = src;
@@ -1434,6 +1537,10 @@ int64_t pdlpdev_upload(pdlpdev_ctx* ctx, int id, const void* host, int64_t eleme
   if (count < 0) return count;
   if (id == PDLPDEV_BUF_A_VALUES || id == PDLPDEV_BUF_AT_VALUES) {
     fail(-1, "matrix values cannot be overwritten");
+    return -1;
+  }
+  if (id == PDLPDEV_BUF_XBAR_MASK || id == PDLPDEV_BUF_ZS_LAUNCHES || id == PDLPDEV_BUF_PART_A || id == PDLPDEV_BUF_PART_AT) {
+    fail(-1, "the bitmap of xbar and the reduction partials are written by the attempt's kernels alone");
     return -1;
   }
   count = std::min(count, elements);
@@ -1592,7 +1699,7 @@ int pdlpdev_time_kernel(pdlpdev_ctx* ctx, int kernel_id, int reps, double* avg_m
   auto one = [&]() {
     switch (kernel_id) {
       case PDLPDEV_K_PRIMAL:
-        launch_k(ctx, k_primal, grid_for(ctx->n), kBlock, 0, ctx->n, ctx->ctl, ctx->x[0], ctx->x[1], ctx->aty[0], ctx->aty[1], ctx->c, ctx->lb, ctx->ub, ctx->xbar, ctx->sumx, (const p2pdev::Push*)nullptr, ctx->ubd);
+        launch_primal(ctx);
         break;
       case PDLPDEV_K_SPMV_A_DUAL: launch_a_dual(ctx); break;
       case PDLPDEV_K_SPMV_AT_STEP: launch_at_step(ctx); break;

@@ -224,7 +224,16 @@ struct PanelView {
   const int32_t* __restrict__ dn_seg_len   = nullptr;
   const int32_t* __restrict__ dn_seg_ptr   = nullptr;
   const double* __restrict__ dn_val        = nullptr;
+  // Zero skip (k_panel_a_dual<false> only; every other kernel ignores the field): one bit per column of the gathered vector, set where
+  // its entry is not 0.0 (k_primal's ballots).  Null: every entry is gathered.  Set by the launch site for the attempts whose
+  // k_primal wrote the bits; `zcols` = the vector's length.  The kernel takes the masked path when the control block's flag is up
+  // (pdlpdev_ctl::zskip, the density guard) or zforce is set.
+  const unsigned long long* __restrict__ zmask = nullptr;
+  int zcols = 0, zforce = 0;  // zforce: skip whatever the control block's flag says (zero_skip=2)
 };
+// the slab's words of the bitmap live in LDS, in 16-byte quads (128 columns) from the quad that holds the slab's first column; columns
+// of a wider slab that lie behind the window are gathered unconditionally (panel_products_zs)
+constexpr int kZsQuads        = 1152;                    // 18 KiB: what two workgroups per CU leave next to prod / psum
 constexpr int kPanelOwnRow = 4096;
 constexpr int kPanelDenseSegs = 32;  // dense segments per panel of the column side that the epilogue handles itself (more: k_dense_cols)
 constexpr long long kPanelNotMine = 0x7FF8C0DEC0DEC0DELL;  // a NaN no arithmetic produces: "this row is summed elsewhere"

@@ -41,6 +41,60 @@ __device__ __forceinline__ void panel_products(const double* __restrict__ vec, d
     if (u < R - 1 || i < len) prod[i] = va[u] * x[u];
   }
 }
+// Zero skip: the gathered vector's entry is fetched only where its bit of the slab's bitmap (LDS, 32-bit words from word `zbase`) is
+// set; a clear bit stands for an entry that is exactly 0.0, whose product is stored as +0.0 -- a row sum that starts at +0.0 holds the
+// same bits with that addend as with a * (+-0.0).  The bits are read first, then the R gathers go out in one batch as above.
+// The LDS window holds kZsQuads * 128 columns from the slab's first quad; a slab wider than that (the default 174 762 columns) has its
+// last columns outside the window, and those are gathered whatever they hold -- so the slabs keep the width they had.
+template <int R>
+__device__ __forceinline__ void panel_products_zs(const double* __restrict__ vec, double* prod, const double (&va)[kPanelPer],
+                                                  const int (&ja)[kPanelPer], int len, const unsigned* zbits, int zbase)
+{
+  unsigned w[R];
+#pragma unroll
+  for (int u = 0; u < R; ++u) {
+    const int wi = (ja[u] >> 5) - zbase;
+    w[u]         = wi < kZsQuads * 4 ? zbits[wi] : ~0u;
+  }
+  double x[R];
+#pragma unroll
+  for (int u = 0; u < R; ++u) {
+    x[u] = 0.0;
+    if ((w[u] >> (ja[u] & 31)) & 1u) x[u] = vec[ja[u]];
+  }
+#pragma unroll
+  for (int u = 0; u < R; ++u) {
+    const int i = threadIdx.x + u * kPanelThreads;
+    if (u < R - 1 || i < len) prod[i] = va[u] * x[u];
+  }
+}
+// the bitmap of slab s: the 16-byte quads (128 columns each) from the one that holds the slab's first column to the one that holds its
+// last, kZsPer per lane through registers (requested behind one barrier, stored in front of the next: see the hazard comment)
+constexpr int kZsPer = (kZsQuads + kPanelThreads - 1) / kPanelThreads;
+__device__ __forceinline__ int panel_zs_first_quad(const PanelView& P, int s) { return (int)(((long long)s * P.slab_w) >> 7); }  // (s < S: at most the vector's length)
+__device__ __forceinline__ void panel_zs_load(const PanelView& P, int s, uint4 (&st)[kZsPer])
+{
+  const long long c1 = (long long)(s + 1) * P.slab_w;
+  const int last     = (int)(c1 < P.zcols ? c1 : P.zcols) - 1;  // the slab's last column
+  const int q0       = panel_zs_first_quad(P, s);
+  int nq             = (last >> 7) - q0 + 1;
+  nq                 = nq < kZsQuads ? nq : kZsQuads;
+  const uint4* __restrict__ src = reinterpret_cast<const uint4*>(P.zmask) + q0;
+#pragma unroll
+  for (int k = 0; k < kZsPer; ++k) {
+    const int q = threadIdx.x + k * kPanelThreads;
+    st[k]       = uint4{0u, 0u, 0u, 0u};
+    if (q < nq) st[k] = src[q];
+  }
+}
+__device__ __forceinline__ void panel_zs_store(uint4* zq, const uint4 (&st)[kZsPer])
+{
+#pragma unroll
+  for (int k = 0; k < kZsPer; ++k) {
+    const int q = threadIdx.x + k * kPanelThreads;
+    if (q < kZsQuads) zq[q] = st[k];
+  }
+}
 #define PANEL_DISPATCH(rounds, CALL) \
   switch (rounds) {                   \
     case 1: CALL(1); break;           \
@@ -310,15 +364,28 @@ __device__ __forceinline__ void panel_row_sums(const PanelView& P, const unsigne
 //            that owns the row adds the wave's partial), the "not mine" marks are written after the first barrier to rows that have no
 //            segment in any tile; the epilogue reads behind the barrier after the loop.
 //   tile_s / base_s  written once before the first barrier, read-only afterwards.
+//   zq[]    (ZS only) the bitmap of the CURRENT chunk's slab.  Read by panel_products_zs of chunk i between T(i) and M(i).  When chunk
+//            i + 1 opens another slab, that slab's bits are requested from global memory behind M(i) -- every read of the old bits
+//            ends before its thread arrives at M(i) -- held in registers over the row sums of chunk i and stored in front of T(i + 1),
+//            the barrier that makes them visible to the first panel_products_zs of the new slab.  The first slab's bits are stored in
+//            front of T(0).  The bits themselves were written by k_primal of the same attempt, a kernel boundary away.
 // Global memory, the epilogue operands requested early (panel_epilogue_request): nothing is read before its writer.  A row's operands
 // are written by that row's own lane only, and only in apply(), behind the request in program order (sumy[i], the Halpern x'[j]: read,
 // then written by the same lane); y / lo / hi / x / xn / aty and the anchors are read-only in these kernels; the next-iterate buffers
 // are only stored to.  A row with a workgroup of its own is written by that workgroup: its slot here is requested and never used.
-template <class Epi>
+// ZS: the instantiation can skip the gathers of zero entries (panel_products_zs); it does so when `zmask` is not null (uniform).
+// Without ZS nothing of it is compiled.
+template <class Epi, bool ZS = false>
 __device__ __forceinline__ void panel_spmv_block(const PanelView& P, const double* __restrict__ vec,
-                                                 Epi& epi, double* __restrict__ partials)
+                                                 Epi& epi, double* __restrict__ partials, const unsigned long long* zmask = nullptr)
 {
   static_assert(kPanelPer == 8, "PANEL_DISPATCH enumerates 1..8 rounds");
+  [[maybe_unused]] uint4* zq = nullptr;
+  if constexpr (ZS) {
+    __shared__ uint4 zq_s[kZsQuads];
+    zq = zq_s;
+  }
+  const bool zon = ZS && zmask != nullptr;
   __shared__ double prod[kPanelChunk];
   __shared__ double psum[kPanelMaxRows];
   __shared__ double red[kPanelWaves * (Epi::NQ > 0 ? Epi::NQ : 1)];
@@ -362,6 +429,7 @@ __device__ __forceinline__ void panel_spmv_block(const PanelView& P, const doubl
 #define PANEL_ROUNDS(c) (((c).c1 - (c).c0 + kPanelThreads - 1) / kPanelThreads)
 #define PANEL_CALL_LOAD(R) panel_load<R>(P, va, ja, nxt.c0, nxt.c1)
 #define PANEL_CALL_PRODUCTS(R) panel_products<R>(vec, prod, va, ja, cur.c1 - cur.c0)
+#define PANEL_CALL_PRODUCTS_ZS(R) panel_products_zs<R>(vec, prod, va, ja, cur.c1 - cur.c0, reinterpret_cast<const unsigned*>(zq), panel_zs_first_quad(P, cur.s) << 2)
 #define PANEL_REQUEST(c)                                                         \
   if ((c).valid) {                                                               \
     PANEL_DISPATCH(PANEL_ROUNDS(c), PANEL_CALL_LOAD)                             \
@@ -376,12 +444,18 @@ __device__ __forceinline__ void panel_spmv_block(const PanelView& P, const doubl
   PanelChunk nxt = advance(none);
   PANEL_REQUEST(nxt)
   PanelChunk cur = nxt;
+  if (zon && cur.valid) {  // the first slab's bits (zon is a constant false without ZS: nothing of the bitmap is compiled there)
+    uint4 st[kZsPer];
+    panel_zs_load(P, cur.s, st);
+    panel_zs_store(zq, st);
+  }
   constexpr bool kEarly = PanelEarlyOps<Epi>::on;
   [[maybe_unused]] typename PanelEarlyOps<Epi>::type pre[kPanelEpiDepth];
   [[maybe_unused]] int lo_last = 0, hi_last = 0;
   while (cur.valid) {
     __syncthreads();  // the previous chunk's row sums are done with prod
-    PANEL_DISPATCH(PANEL_ROUNDS(cur), PANEL_CALL_PRODUCTS)
+    if (zon) { PANEL_DISPATCH(PANEL_ROUNDS(cur), PANEL_CALL_PRODUCTS_ZS) }
+    else { PANEL_DISPATCH(PANEL_ROUNDS(cur), PANEL_CALL_PRODUCTS) }
 #pragma unroll
     for (int q = 0; q < kPanelRowsPer; ++q) ext[q] = ext_next[q];
     const int lo = cur.c0 - cur.t0, hi = cur.c1 - cur.t0;
@@ -393,10 +467,18 @@ __device__ __forceinline__ void panel_spmv_block(const PanelView& P, const doubl
       }
     PANEL_REQUEST(nxt)  // in flight during the row sums below
     __syncthreads();
-    panel_row_sums(P, ext, prod, psum, nr, lo, hi);
+    if (zon && nxt.valid && nxt.s != cur.s) {  // (uniform) the next chunk opens another slab: its bits travel under the row sums
+      uint4 st[kZsPer];
+      panel_zs_load(P, nxt.s, st);
+      panel_row_sums(P, ext, prod, psum, nr, lo, hi);
+      panel_zs_store(zq, st);
+    } else {
+      panel_row_sums(P, ext, prod, psum, nr, lo, hi);
+    }
     cur = nxt;
   }
 #undef PANEL_REQUEST
+#undef PANEL_CALL_PRODUCTS_ZS
 #undef PANEL_CALL_PRODUCTS
 #undef PANEL_CALL_LOAD
 #undef PANEL_ROUNDS
@@ -643,6 +725,13 @@ __device__ __forceinline__ void panel_block(const PanelView& P, const double* __
 {
   if constexpr (SEG) panel_seg_block(P, vec, epi, partials);
   else panel_spmv_block(P, vec, epi, partials);
+}
+// the product whose gathered vector comes with a bitmap of its non-zeros (P.zmask, null: none): the row-sum variant can skip the zeros
+template <bool SEG, class Epi>
+__device__ __forceinline__ void panel_block_zs(const PanelView& P, const double* __restrict__ vec, Epi& epi, double* __restrict__ partials, bool on)
+{
+  if constexpr (SEG) panel_seg_block(P, vec, epi, partials);
+  else panel_spmv_block<Epi, true>(P, vec, epi, partials, on ? P.zmask : nullptr);
 }
 
 }  // namespace pdlp

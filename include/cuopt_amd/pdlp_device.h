@@ -56,6 +56,9 @@ typedef struct pdlpdev_ctl {
   int32_t target_steps; /* kernels are no-ops once steps_taken >= target_steps    */
   int32_t error;        /* 1: movement <= 0 or >= 1e100 (valid_step_size = -1)    */
   int32_t its_since_restart;
+  int32_t zskip;        /* zero skip (CUOPT_AMD_TUNE=zero_skip=1): 1 = the NEXT attempt's A product skips the zero entries of
+                           xbar; decided by k_step_decision from zs_nonzeros with hysteresis.  Never changes a result.     */
+  int32_t zs_nonzeros;  /* non-zero entries of xbar in the last attempt (k_primal's ballots, an exact count)               */
 } pdlpdev_ctl;
 
 /* Scalars of the restarted reflected-Halpern mode (pdlpdev_set_halpern), a block of their own next to the control block: the
@@ -126,6 +129,11 @@ enum {
   PDLPDEV_BUF_LAST_RESTART_ATY, /* Halpern mode: A^T y of the anchor (scaled)               n */
   PDLPDEV_BUF_AX_U_CURRENT, /* A x of the unscaled problem from the last eval(CURRENT)    m */
   PDLPDEV_BUF_AX_U_AVERAGE, /*                                                            m */
+  PDLPDEV_BUF_PART_A,       /* the A product's per-workgroup partials of ||dy||^2 as the last attempt left them (download only) */
+  PDLPDEV_BUF_PART_AT,      /* the A^T product's: interaction, then ||dx||^2, one per workgroup each (download only)            */
+  PDLPDEV_BUF_XBAR_MASK,    /* zero skip: bit j of the 64-bit words = (xbar_j != 0), as the last primal step wrote it; download only,
+                               ceil(n / 64) elements; -1 with CUOPT_AMD_TUNE=zero_skip=0 */
+  PDLPDEV_BUF_ZS_LAUNCHES,  /* zero skip: one 64-bit count of the launches of the A product that took the masked path (download only) */
   PDLPDEV_BUF_COUNT
 };
 
