@@ -381,6 +381,7 @@ EV = {n: i for i, n in enumerate(
     ["CX", "DUAL_SUM", "PRES2", "DRES2", "X2", "Y2", "LINF_PRES_REL", "LINF_DRES_REL"])}
 CURRENT, AVERAGE = 0, 1
 LAST_RESTART = 2  # PDLPDEV_LAST_RESTART: pdlpdev_eval / pdlpdev_trust_region_bounds only
+BEST = 3  # PDLPDEV_BEST: pdlpdev_get_solution only (the snapshot pdlpdev_save_best took)
 
 
 class CuOptError(RuntimeError):
@@ -1192,6 +1193,13 @@ class Device:
         dx, dy = np.zeros(int(n)), np.zeros(int(m))
         self._ck(lib.pdlpdev_halpern_get_ray(self.handle, _ptr(dx), _ptr(dy)))
         return dx, dy
+
+    def solution(self, which, n, m):
+        """pdlpdev_get_solution: (x, y, reduced costs) of iterate `which` (CURRENT, AVERAGE or BEST), unscaled, in the device's order;
+        the reduced costs are what the last evaluation of that iterate left"""
+        x, y, z = np.zeros(int(n)), np.zeros(int(m)), np.zeros(int(n))
+        self._ck(lib.pdlpdev_get_solution(self.handle, int(which), _ptr(x), _ptr(y), _ptr(z)))
+        return x, y, z
 
     def download(self, name, count):
         out = np.zeros(int(count))

@@ -120,6 +120,10 @@ struct cuoptamd_solver {
   cuoptamd_result best_result{};
   bool have_accepted = false;  // settings.accept_tolerance: first iterate that met the looser set (snapshot = best buffers)
   cuoptamd_result accepted_result{};
+  // a head took a snapshot (pdlpdev_save_best: copies enqueued on the context's stream, not waited for).  Whoever goes on with the
+  // iterate on ANOTHER stream -- the small-LP batch -- waits for them first and clears the flag; on the context's own stream the
+  // order is the stream's.
+  bool snapshot_pending = false;
   std::string log_path;
   pdlpdev_ctl ctl{};
   Convergence conv_current, conv_average;
@@ -429,6 +433,7 @@ double major_restart_done(cuoptamd_solver* s, const MajorPlan& plan, const doubl
 int keep_accepted_point(cuoptamd_solver* s, int which)
 {
   DEV(pdlpdev_save_best(s->dev, which));
+  s->snapshot_pending = true;
   fill_result(s, kOptimal, which);
   if (s->H.algorithm == 1) s->result.returned_average = 0;  // (the Halpern mode's "average" slots hold T(z^k): no average)
   s->accepted_result = s->result;
@@ -537,6 +542,7 @@ int major_head(cuoptamd_solver* s, const double* ev, const double* ev_avg, bool*
       const int bw = (&cand == &qc) ? PDLPDEV_CURRENT : PDLPDEV_AVERAGE;
       s->best_quality = over;
       DEV(pdlpdev_save_best(dev, bw));
+      s->snapshot_pending = true;
       fill_result(s, kTimeLimit, bw);
       s->best_result = s->result;
       s->have_best   = true;
@@ -1387,6 +1393,7 @@ static void reset_host_state(cuoptamd_solver* s)
   s->best_quality.objective = s->maximize ? -std::numeric_limits<double>::infinity() : std::numeric_limits<double>::infinity();
   s->have_best = false, s->best_result = blank;
   s->have_accepted = false, s->accepted_result = blank;
+  s->snapshot_pending = false;
   s->conv_current = Convergence{}, s->conv_average = Convergence{};
   s->returned_which = PDLPDEV_CURRENT, s->finished = false, s->warm_started = false, s->started = false;
   s->result = blank;
@@ -1747,6 +1754,14 @@ static int small_batch_advance(cuoptamd_batch* b, const std::vector<int32_t>& bu
           again = plan[l].restart;
         }
         if (rc != 0) return rc;
+        if (s->snapshot_pending) {
+          // the head kept this iterate (save_best_primal_so_far, the acceptance set): its copies run on the context's stream, and the
+          // restart, the preparation and the attempts below rewrite their sources on the batch's -- which also reads the kept point
+          // later (cuoptamd_batch_branch, cuoptamd_batch_get_solutions).  Only an LP that kept a point waits.
+          s->snapshot_pending = false;
+          rc = pdlpdev_synchronize(s->dev);
+          if (rc != 0) return fail(rc, "pdlpdev_synchronize: %s", pdlpdev_last_error());
+        }
         major_was_done(s, terminated);
         if (terminated) done[l] = 1;
         else if (again) restart[l] = 1, which[l] = plan[l].which, unscaled[l] = plan[l].unscaled, theta[l] = s->H.primal_weight_update_smoothing, any_restart = true;
