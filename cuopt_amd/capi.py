@@ -332,6 +332,8 @@ _proto("pdlpdev_analysis_destroy", None, c_void_p)
 _proto("pdlpdev_debug_sort_pairs", c_int, c_int, C.c_int64, c_void_p, c_void_p, c_int, c_void_p, c_void_p)
 _proto("pdlpdev_debug_scan", c_int, c_int, C.c_int64, c_void_p, c_void_p)
 _proto("pdlpdev_debug_layout_checksums", c_int, c_void_p, c_void_p)
+if hasattr(lib, "pdlpdev_debug_panel_words"):  # (an older build given through CUOPT_AMD_LIB does not export it)
+    _proto("pdlpdev_debug_panel_words", c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p)
 # shared-matrix batch (round 5)
 _proto("cuoptamd_solver_clone", c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, P(c_void_p))
 _proto("cuoptamd_batch_create", c_int, c_void_p, c_int, P(c_void_p))
@@ -1299,6 +1301,15 @@ class Device:
         out = np.zeros(16, np.uint64)
         self._ck(lib.pdlpdev_debug_layout_checksums(self.handle, _ptr(out)))
         return out
+
+    def panel_words(self, side):
+        """the stored words of one side's panels ("A" / "At"): dict(panels, slabs, sorted, slab_w, tile_ptr [panels * slabs + 1], col
+        [entries]); with column-sorted chunks a word is slot << 20 | (column - slab * slab_w), else the column"""
+        which, info = dict(A=0, At=1)[side], np.zeros(5, np.int64)
+        self._ck(lib.pdlpdev_debug_panel_words(self.handle, which, _ptr(info), None, None))
+        tile_ptr, col = np.zeros(int(info[0] * info[1]) + 1, np.int32), np.zeros(int(info[2]), np.int32)
+        self._ck(lib.pdlpdev_debug_panel_words(self.handle, which, _ptr(info), _ptr(tile_ptr), _ptr(col)))
+        return dict(panels=int(info[0]), slabs=int(info[1]), sorted=bool(info[3]), slab_w=int(info[4]), tile_ptr=tile_ptr, col=col)
 
     def dense_info(self):
         out = np.zeros(3, np.int64)

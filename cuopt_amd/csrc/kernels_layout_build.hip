@@ -91,6 +91,42 @@ __global__ void __launch_bounds__(512) k_panel_place(const int32_t* __restrict__
   }
 }
 
+// Column-sorted chunks (PanelView::sorted): workgroup <-> tile, chunk by chunk as the row kernel's advance() cuts them.  The chunk's keys
+// (column inside the slab) << 12 | slot -- slot = the position k_panel_place gave the entry -- are sorted in LDS by a bitonic network
+// (padded with all-ones to a power of two; the keys are unique, so the order is the host's std::sort order); the permutation moves with
+// them through LDS, and the stored word is slot << kSegColBits | column.
+__global__ void __launch_bounds__(512) k_panel_sort(int S, int32_t slab_w, const int32_t* __restrict__ tile_ptr, int32_t* __restrict__ perm,
+                                                    int32_t* __restrict__ col)
+{
+  __shared__ uint32_t key[kPanelChunk];
+  __shared__ int32_t pm[kPanelChunk];
+  const int32_t t1 = tile_ptr[blockIdx.x + 1], base = (int32_t)(blockIdx.x % (unsigned)S) * slab_w;
+  for (int32_t c0 = tile_ptr[blockIdx.x]; c0 < t1; c0 += kPanelChunk) {
+    const int len = t1 - c0 < kPanelChunk ? t1 - c0 : kPanelChunk;
+    int n = 2;
+    while (n < len) n <<= 1;  // (<= kPanelChunk, a power of two)
+    for (int i = threadIdx.x; i < n; i += 512) {
+      key[i] = i < len ? ((uint32_t)(col[c0 + i] - base) << 12) | (uint32_t)i : 0xFFFFFFFFu;
+      if (i < len) pm[i] = perm[c0 + i];
+    }
+    __syncthreads();
+    for (int k = 2; k <= n; k <<= 1)
+      for (int j = k >> 1; j > 0; j >>= 1) {
+        for (int t = threadIdx.x; t < (n >> 1); t += 512) {
+          const int lo = ((t & ~(j - 1)) << 1) | (t & (j - 1)), hi = lo | j;
+          const uint32_t a = key[lo], b = key[hi];
+          if ((a > b) == ((lo & k) == 0)) key[lo] = b, key[hi] = a;
+        }
+        __syncthreads();
+      }
+    for (int i = threadIdx.x; i < len; i += 512) {
+      const uint32_t slot = key[i] & 0xFFFu;
+      col[c0 + i]  = (int32_t)((slot << kSegColBits) | (key[i] >> 12));
+      perm[c0 + i] = pm[slot];
+    }
+    __syncthreads();  // (the next chunk overwrites key / pm)
+  }
+}
 
 }  // namespace
 
@@ -174,11 +210,15 @@ int build_panels_device(pdlpdev_ctx* c, pdlpdev_ctx::Panels* dst, int32_t rows, 
     if (h.seg) k_panel_place<true><<<W, 512, lds, c->stream>>>(row0, d_off, d_idx, S, h.slab_w, own_from, tile_ptr, rp_base, rowptr, dst->perm, col);
     else k_panel_place<false><<<W, 512, lds, c->stream>>>(row0, d_off, d_idx, S, h.slab_w, own_from, tile_ptr, rp_base, rowptr, dst->perm, col);
     HIP_TRY(hipGetLastError());
+    if (h.sorted) {
+      k_panel_sort<<<W * S, 512, 0, c->stream>>>(S, h.slab_w, tile_ptr, dst->perm, col);
+      HIP_TRY(hipGetLastError());
+    }
   }
   HIP_TRY(hipStreamSynchronize(c->stream));  // (the host vectors die here)
   plap("place");
   dst->v = PanelView{h.W, h.S, h.any_long ? 1 : 0, row0, tile_ptr, rowptr, rp_base, col, dst->val};
-  dst->v.seg = h.seg ? 1 : 0, dst->v.slab_w = h.slab_w;
+  dst->v.seg = h.seg ? 1 : 0, dst->v.slab_w = h.slab_w, dst->v.sorted = h.sorted ? 1 : 0;
   dst->nent  = (int64_t)h.nnz;
   if (!h.own_row.empty()) {
     int32_t *own_row = nullptr, *own_ptr = nullptr;

@@ -267,6 +267,8 @@ bool panel_plan(PanelHost* out, int32_t rows, int32_t cols, const int32_t* off, 
     const long long want = cuopt_amd::tune_int("panel_seg", -1);
     P.seg = want == 1 || (want != 0 && long_nnz * 50 > nnz);
     if (slab_w > (1 << kSegColBits)) P.seg = false;
+    // the row-sum panels store every chunk in column order (PanelView::sorted; CUOPT_AMD_TUNE=panel_sort=0: in (row, CSR) order as before)
+    P.sorted = !P.seg && slab_w <= (1 << kSegColBits) && cuopt_amd::tune_int("panel_sort", 1) != 0;
   }
   // Rows beyond kPanelOwnRow nonzeros get a workgroup each behind the panels (a lane, or a wave, would walk them for ever).  The
   // long-tail variant deals every row by nonzero, so a row leaves the panels only when it is longer than a whole panel should be
@@ -403,6 +405,22 @@ PanelHost build_panels(int32_t rows, int32_t cols, const int32_t* off, const int
     }
     for (int s2 = 0; s2 < S; ++s2)
       P.rowptr[(size_t)(P.rp_base[(size_t)w * S + s2] + nr)] = (uint16_t)(cursor[s2] - P.tile_ptr[(size_t)w * S + s2]);
+    if (!P.sorted) return;
+    // every chunk (the kernel's advance(): kPanelChunk-entry pieces of a tile) in ascending order of (column inside the slab, slot);
+    // slot = the entry's position inside the chunk in the order placed above.  The keys are unique: any sort gives this order.
+    std::vector<uint32_t> key;
+    std::vector<int32_t> pm;
+    for (int s2 = 0; s2 < S; ++s2)
+      for (int32_t c0 = P.tile_ptr[(size_t)w * S + s2], t1 = P.tile_ptr[(size_t)w * S + s2 + 1]; c0 < t1; c0 += kPanelChunk) {
+        const int32_t len = std::min<int32_t>(kPanelChunk, t1 - c0);
+        key.resize((size_t)len), pm.assign(&P.perm[c0], &P.perm[c0] + len);
+        for (int32_t i = 0; i < len; ++i) key[i] = ((uint32_t)(P.col[c0 + i] - s2 * slab_w) << 12) | (uint32_t)i;
+        std::sort(key.begin(), key.end());
+        for (int32_t i = 0; i < len; ++i) {
+          const uint32_t slot = key[i] & 0xFFFu;
+          P.col[c0 + i] = (int32_t)((slot << kSegColBits) | (key[i] >> 12)), P.perm[c0 + i] = pm[slot];
+        }
+      }
   }, nnz);
   P.ok = true;
   return P;
@@ -426,7 +444,7 @@ int upload_panels(pdlpdev_ctx* c, pdlpdev_ctx::Panels* dst, const PanelHost& h, 
   TRY(dev_alloc(c, &dst->val, h.nnz));
   HIP_TRY(hipStreamSynchronize(c->stream));  // the host vectors die with the caller's PanelHost
   dst->v  = PanelView{h.W, h.S, h.any_long ? 1 : 0, row0, tile_ptr, rowptr, rp_base, col, dst->val};
-  dst->v.seg = h.seg ? 1 : 0, dst->v.slab_w = h.slab_w;
+  dst->v.seg = h.seg ? 1 : 0, dst->v.slab_w = h.slab_w, dst->v.sorted = h.sorted ? 1 : 0;
   dst->nent = (int64_t)h.nnz;
   if (!h.own_row.empty()) {  // W becomes the number of workgroups / partials: the panels, then a workgroup per own row
     int32_t *own_row = nullptr, *own_ptr = nullptr;

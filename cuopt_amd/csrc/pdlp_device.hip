@@ -1802,6 +1802,18 @@ static uint64_t checksum_device(pdlpdev_ctx* ctx, const void* dev, size_t bytes)
   (void)ctx;
   return f;
 }
+int pdlpdev_debug_panel_words(pdlpdev_ctx* ctx, int side, int64_t info[5], int32_t* tile_ptr, int32_t* col)
+{
+  HIP_TRY(hipSetDevice(ctx->device));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  const pdlpdev_ctx::Panels& P = side ? ctx->At.pan : ctx->A.pan;
+  if (!P.on) return fail(-1, "side %d is not in panels", side);
+  const int NP = P.v.NP ? P.v.NP : P.v.W;
+  info[0] = NP, info[1] = P.v.S, info[2] = P.nent, info[3] = P.v.sorted, info[4] = P.v.slab_w;
+  if (tile_ptr) HIP_TRY(hipMemcpy(tile_ptr, P.v.tile_ptr, ((size_t)NP * P.v.S + 1) * 4, hipMemcpyDeviceToHost));
+  if (col) HIP_TRY(hipMemcpy(col, P.v.col, (size_t)P.nent * 4, hipMemcpyDeviceToHost));
+  return 0;
+}
 int pdlpdev_debug_layout_checksums(pdlpdev_ctx* ctx, uint64_t out[16])
 {
   HIP_TRY(hipSetDevice(ctx->device));

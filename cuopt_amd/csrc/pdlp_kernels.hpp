@@ -200,6 +200,12 @@ struct PanelView {
   // Long-tail variant (panel_seg_block below): `col` holds (row within the panel) << kSegColBits | (column - slab * slab_w), the entries of a
   // chunk are stored lane-major (lane t's consecutive entries one per round), and there are no row pointers
   int seg = 0, slab_w = 0;
+  // Row-sum panels with column-sorted chunks (`sorted`; build_panels): inside every chunk -- the <= kPanelChunk-entry pieces of a tile as
+  // the kernel's advance() cuts them -- the entries are stored in ascending order of (column inside the slab, slot), and `col` holds
+  // slot << kSegColBits | (column - slab * slab_w), where `slot` is the entry's position inside the chunk in (row, CSR) order: the
+  // place in the LDS stage its product is written to, so the row sums add what they always added in the order they always did.  The 64
+  // gathers of a wave instruction are then neighbouring columns, which the texture path merges when they share a 128-byte line.
+  int sorted = 0;
   // Rows of more than kPanelOwnRow nonzeros are not in the panels: each gets a workgroup of its own BEHIND the panels in the same
   // grid (W = NP panels + the own rows; a 20 000-entry row inside a panel is one wave adding up 3 000-entry segments while seven
   // waves wait, and that panel sets the kernel time).  They are read from the CSR arrays the layout was built on.
@@ -243,6 +249,7 @@ constexpr int kPanelPer     = kPanelChunk / kPanelThreads;                      
 constexpr int kPanelRowsPer = (kPanelMaxRows + kPanelThreads - 1) / kPanelThreads;  // rows per lane
 constexpr int kSegColBits = 20;                     // slab width < 2^20 columns (1.33 MiB slabs: 174 763)
 constexpr unsigned kSegColMask = (1u << kSegColBits) - 1u;
+static_assert(kPanelChunk <= 1 << 12, "a sorted chunk's slot takes the 12 bits beside the column");
 
 // ------------------------------------------------------------------------------------------------
 // Sorted jagged rows ("jag"): the SpMV for STRUCTURED matrices, whose rows re-use a limited set of columns.

@@ -7,6 +7,7 @@
 struct PanelHost {
   bool ok = false, any_long = false;
   bool seg = false;                        // long-tail variant: packed (row, column) entries, no row pointers (panel_seg_block)
+  bool sorted = false;                     // row-sum panels: chunks stored in column order, every entry with its slot (PanelView::sorted)
   int32_t slab_w = 0;
   int W = 0, S = 0;                        // W: panels only
   std::vector<int32_t> own_row, own_ptr;   // rows of more than kPanelOwnRow nonzeros (a workgroup each, behind the panels); per panel

@@ -28,17 +28,29 @@ __device__ __forceinline__ void panel_load(const PanelView& P, double (&va)[kPan
     ja[u] = __builtin_nontemporal_load(P.col + k);
   }
 }
+// Column-sorted chunks (P.sorted, uniform): the stored word is slot << kSegColBits | (column - slab_base); the entry at position i of the
+// chunk is gathered by lane i % 512 as ever, and its product goes to prod[slot], where the (row, CSR) order would have put it.
+__device__ __forceinline__ void panel_decode(int word, int i, bool sorted, int slab_base, int& col, int& slot)
+{
+  col  = sorted ? slab_base + (int)((unsigned)word & kSegColMask) : word;
+  slot = sorted ? (int)((unsigned)word >> kSegColBits) : i;
+}
 template <int R>
 __device__ __forceinline__ void panel_products(const double* __restrict__ vec, double* prod, const double (&va)[kPanelPer],
-                                               const int (&ja)[kPanelPer], int len)
+                                               const int (&ja)[kPanelPer], int len, bool sorted, int slab_base)
 {
   double x[R];
+  int slot[R];
 #pragma unroll
-  for (int u = 0; u < R; ++u) x[u] = vec[ja[u]];
+  for (int u = 0; u < R; ++u) {
+    int c;
+    panel_decode(ja[u], threadIdx.x + u * kPanelThreads, sorted, slab_base, c, slot[u]);
+    x[u] = vec[c];
+  }
 #pragma unroll
   for (int u = 0; u < R; ++u) {
     const int i = threadIdx.x + u * kPanelThreads;
-    if (u < R - 1 || i < len) prod[i] = va[u] * x[u];
+    if (u < R - 1 || i < len) prod[slot[u]] = va[u] * x[u];
   }
 }
 // Zero skip: the gathered vector's entry is fetched only where its bit of the slab's bitmap (LDS, 32-bit words from word `zbase`) is
@@ -48,24 +60,27 @@ __device__ __forceinline__ void panel_products(const double* __restrict__ vec, d
 // last columns outside the window, and those are gathered whatever they hold -- so the slabs keep the width they had.
 template <int R>
 __device__ __forceinline__ void panel_products_zs(const double* __restrict__ vec, double* prod, const double (&va)[kPanelPer],
-                                                  const int (&ja)[kPanelPer], int len, const unsigned* zbits, int zbase)
+                                                  const int (&ja)[kPanelPer], int len, const unsigned* zbits, int zbase, bool sorted,
+                                                  int slab_base)
 {
   unsigned w[R];
+  int c[R], slot[R];  // (the bitmap is indexed by the absolute column, whichever way it is stored)
 #pragma unroll
   for (int u = 0; u < R; ++u) {
-    const int wi = (ja[u] >> 5) - zbase;
+    panel_decode(ja[u], threadIdx.x + u * kPanelThreads, sorted, slab_base, c[u], slot[u]);
+    const int wi = (c[u] >> 5) - zbase;
     w[u]         = wi < kZsQuads * 4 ? zbits[wi] : ~0u;
   }
   double x[R];
 #pragma unroll
   for (int u = 0; u < R; ++u) {
     x[u] = 0.0;
-    if ((w[u] >> (ja[u] & 31)) & 1u) x[u] = vec[ja[u]];
+    if ((w[u] >> (c[u] & 31)) & 1u) x[u] = vec[c[u]];
   }
 #pragma unroll
   for (int u = 0; u < R; ++u) {
     const int i = threadIdx.x + u * kPanelThreads;
-    if (u < R - 1 || i < len) prod[i] = va[u] * x[u];
+    if (u < R - 1 || i < len) prod[slot[u]] = va[u] * x[u];
   }
 }
 // the bitmap of slab s: the 16-byte quads (128 columns each) from the one that holds the slab's first column to the one that holds its
@@ -359,7 +374,9 @@ __device__ __forceinline__ void panel_row_sums(const PanelView& P, const unsigne
 //   prod[]  (ONE buffer; the chunk "one stage ahead" lives in REGISTERS: va / ja / ext_next)
 //            written by panel_products of chunk i between barrier T(i) [loop top] and barrier M(i) [after the next chunk's requests];
 //            read by the row sums of chunk i after M(i); next written by chunk i + 1 after T(i + 1) -- every row sum of chunk i ends
-//            before its thread arrives at T(i + 1).
+//            before its thread arrives at T(i + 1).  With column-sorted chunks (P.sorted) a lane writes prod[slot] for the slot its entry
+//            carries instead of prod[its own position]: the slots of a chunk are a permutation of 0 .. len - 1, so no two lanes meet
+//            at an element, every element below len is written, and the barriers are the same.
 //   psum[]  zeroed before the first barrier; row r is read and written by lane r % 512 ONLY (also in the long-segment path: the lane
 //            that owns the row adds the wave's partial), the "not mine" marks are written after the first barrier to rows that have no
 //            segment in any tile; the epilogue reads behind the barrier after the loop.
@@ -428,8 +445,8 @@ __device__ __forceinline__ void panel_spmv_block(const PanelView& P, const doubl
   // (macros, not lambdas: the register arrays must stay visible to scalar replacement)
 #define PANEL_ROUNDS(c) (((c).c1 - (c).c0 + kPanelThreads - 1) / kPanelThreads)
 #define PANEL_CALL_LOAD(R) panel_load<R>(P, va, ja, nxt.c0, nxt.c1)
-#define PANEL_CALL_PRODUCTS(R) panel_products<R>(vec, prod, va, ja, cur.c1 - cur.c0)
-#define PANEL_CALL_PRODUCTS_ZS(R) panel_products_zs<R>(vec, prod, va, ja, cur.c1 - cur.c0, reinterpret_cast<const unsigned*>(zq), panel_zs_first_quad(P, cur.s) << 2)
+#define PANEL_CALL_PRODUCTS(R) panel_products<R>(vec, prod, va, ja, cur.c1 - cur.c0, P.sorted != 0, cur.s * P.slab_w)
+#define PANEL_CALL_PRODUCTS_ZS(R) panel_products_zs<R>(vec, prod, va, ja, cur.c1 - cur.c0, reinterpret_cast<const unsigned*>(zq), panel_zs_first_quad(P, cur.s) << 2, P.sorted != 0, cur.s * P.slab_w)
 #define PANEL_REQUEST(c)                                                         \
   if ((c).valid) {                                                               \
     PANEL_DISPATCH(PANEL_ROUNDS(c), PANEL_CALL_LOAD)                             \

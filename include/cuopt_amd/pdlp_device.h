@@ -256,6 +256,9 @@ int pdlpdev_debug_ipc_export(int device, int count, uint8_t handle[64], void** b
 int pdlpdev_debug_ipc_store(int device, const uint8_t handle[64], int count, double seed);
 int pdlpdev_debug_ipc_wait(int device, void* base, int count, double seed);
 int pdlpdev_debug_layout_checksums(pdlpdev_ctx* ctx, uint64_t out[16]);
+/* The stored words of one side's panels (side 0: A, 1: A^T): info = {panels, slabs, entries, column-sorted chunks 0/1, slab width}; with
+   tile_ptr (panels * slabs + 1) and col (entries) not NULL the two arrays are copied out.  -1: the side is not in panels. */
+int pdlpdev_debug_panel_words(pdlpdev_ctx* ctx, int side, int64_t info[5], int32_t* tile_ptr, int32_t* col);
 /* The wide-bin geometry of the gather-free layout walked on the CPU (no GPU needed): out = M x summed exactly as phase P and phase R order
    the work; info = {padded entries, bins, panels, highest level, serial rows}.  1: the geometry cannot hold the matrix, 2: inconsistent arrays. */
 int pdlpdev_debug_pb_wide_host(int32_t rows, int32_t cols, const int32_t* off, const int32_t* idx, const double* val, const double* x, double* out,
