@@ -376,7 +376,8 @@ BUF = {n: i for i, n in enumerate(
     ["X", "Y", "X_OTHER", "Y_OTHER", "ATY", "ATY_OTHER", "XBAR", "SUM_X", "SUM_Y", "AVG_X", "AVG_Y",
      "DROW", "DCOL", "A_VALUES", "AT_VALUES", "C", "LB", "UB", "LO", "HI", "RC_CURRENT", "RC_AVERAGE",
      "LAST_RESTART_X", "LAST_RESTART_Y", "ATY_U_CURRENT", "ATY_U_AVERAGE", "LAST_RESTART_ATY",
-     "AX_U_CURRENT", "AX_U_AVERAGE", "PART_A", "PART_AT", "XBAR_MASK", "ZS_LAUNCHES"])}
+     "AX_U_CURRENT", "AX_U_AVERAGE", "PART_A", "PART_AT", "XBAR_MASK", "ZS_LAUNCHES",
+     "AX_U_LAST_RESTART", "ATY_U_LAST_RESTART"])}
 KERNEL = {n: i for i, n in enumerate(
     ["PRIMAL", "SPMV_A_DUAL", "SPMV_AT_STEP", "STEP_DECISION", "SPMV_A_PLAIN", "SPMV_AT_PLAIN"])}
 EV = {n: i for i, n in enumerate(

@@ -1511,6 +1511,8 @@ static int64_t locate_buffer(pdlpdev_ctx* ctx, int id, double** ptr)
       if (!ctx->xmask) { fail(-1, "buffer %d: this context has no bitmap of xbar (CUOPT_AMD_TUNE=zero_skip=0, or A is not in the row-sum panels)", id); return -1; }
       src = reinterpret_cast<double*>(ctx->xmask), count = (n + 63) / 64;
       break;
+    case PDLPDEV_BUF_AX_U_LAST_RESTART: src = ctx->ax_u[PDLPDEV_LAST_RESTART], count = m; break;
+    case PDLPDEV_BUF_ATY_U_LAST_RESTART: src = ctx->aty_u[PDLPDEV_LAST_RESTART], count = n; break;
     default: fail(-1, "unknown buffer %d", id); return -1;
   }
   *ptr = src;
@@ -1541,6 +1543,10 @@ int64_t pdlpdev_upload(pdlpdev_ctx* ctx, int id, const void* host, int64_t eleme
   }
   if (id == PDLPDEV_BUF_XBAR_MASK || id == PDLPDEV_BUF_ZS_LAUNCHES || id == PDLPDEV_BUF_PART_A || id == PDLPDEV_BUF_PART_AT) {
     fail(-1, "the bitmap of xbar and the reduction partials are written by the attempt's kernels alone");
+    return -1;
+  }
+  if (id == PDLPDEV_BUF_AX_U_LAST_RESTART || id == PDLPDEV_BUF_ATY_U_LAST_RESTART) {
+    fail(-1, "the products at the last-restart anchors are written by the evaluation and the trust region alone");
     return -1;
   }
   count = std::min(count, elements);

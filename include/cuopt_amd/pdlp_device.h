@@ -134,6 +134,8 @@ enum {
   PDLPDEV_BUF_XBAR_MASK,    /* zero skip: bit j of the 64-bit words = (xbar_j != 0), as the last primal step wrote it; download only,
                                ceil(n / 64) elements; -1 with CUOPT_AMD_TUNE=zero_skip=0 */
   PDLPDEV_BUF_ZS_LAUNCHES,  /* zero skip: one 64-bit count of the launches of the A product that took the masked path (download only) */
+  PDLPDEV_BUF_AX_U_LAST_RESTART,  /* A x of the unscaled problem at the anchors, from the last eval / trust region at LAST_RESTART  m (download only) */
+  PDLPDEV_BUF_ATY_U_LAST_RESTART, /* A^T y likewise                                                                                 n (download only) */
   PDLPDEV_BUF_COUNT
 };
 

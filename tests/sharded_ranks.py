@@ -16,6 +16,7 @@ What Assembled assembles, and what it asserts on the way:
                    owners and not compared across ranks
     put("Y", a)    every rank its rows; an n-sized buffer whole to every rank
     restart        the two squared distances are the same on every rank
+    eval_infeasibility, trust_region_bounds   the four / six figures are the same bits on every rank (tests/test_restart_inputs_gpu.py)
 A snapshot of the scenario asks for nine buffers: the first of them fetches all nine and the control block from every rank in ONE
 command, the rest is served from that until the next command that changes something.
 
@@ -35,7 +36,7 @@ import attempt_reference as ar
 from eval_reference import _segment_sums
 
 INF = np.inf
-M_SIZED = ("Y", "Y_OTHER", "SUM_Y", "AVG_Y", "LO", "HI", "DROW", "LAST_RESTART_Y", "AX_U_CURRENT", "AX_U_AVERAGE")
+M_SIZED = ("Y", "Y_OTHER", "SUM_Y", "AVG_Y", "LO", "HI", "DROW", "LAST_RESTART_Y", "AX_U_CURRENT", "AX_U_AVERAGE", "AX_U_LAST_RESTART")
 SLICE_ONLY = ("X_OTHER", "ATY_OTHER", "XBAR")   # sliced dataflows: valid on the owner's slice only
 SNAPSHOT = ar.STATE + ("XBAR",)                 # fetched together, once per rank
 FLOWS = {"allreduce": 1, "rsag": 2, "owner": 3}  # pdlpdev_shard_dataflow
@@ -141,11 +142,22 @@ class Assembled:
     def eval_infeasibility(self, which, rule_finite=True):
         out = self._do("eval_infeasibility", int(which), bool(rule_finite))
         for r, e in enumerate(out):
-            assert e == out[0], ("eval_infeasibility: rank %d against rank 0" % r, e, out[0])
+            assert e == out[0] and all(bits_of(e[k]) == bits_of(out[0][k]) for k in e), ("eval_infeasibility: rank %d against rank 0" % r, e, out[0])
+        return out[0]
+
+    def trust_region_bounds(self, which, *args, **kw):
+        """pdlpdev_trust_region_bounds on every rank -> the six figures, the same bits on all ranks"""
+        out = self._do("trust_region_bounds", int(which), args, kw)
+        for r, e in enumerate(out):
+            assert all(bits_of(e[k]) == bits_of(out[0][k]) for k in out[0]), ("trust_region_bounds: rank %d against rank 0" % r, e, out[0])
         return out[0]
 
     def close(self):
         self.b.close()
+
+
+def bits_of(v):
+    return np.asarray(v, dtype=np.float64).view(np.int64)
 
 
 # ---- W worker threads, each with one rank's solver ---------------------------------------------------------------------------------------
@@ -211,6 +223,9 @@ class RankOnDevice:
 
     def eval_infeasibility(self, which, rule_finite):
         return self.dev.eval_infeasibility(which, rule_finite=rule_finite)
+
+    def trust_region_bounds(self, which, args, kw):
+        return self.dev.trust_region_bounds(which, *args, **kw)
 
     def close(self):
         self.solver.close()
