@@ -126,6 +126,29 @@ class SolverSettingsWithRays(SolverSettings):
 assert SolverSettingsWithRays.halpern_infeasibility.offset == SolverSettings.halpern_lockstep.offset + C.sizeof(c_int)
 
 
+class SolverSettingsWithLockstepRays(SolverSettingsWithRays):
+    """... and the field appended behind halpern_infeasibility: int32_t halpern_lockstep_rays.  The C compiler puts it straight behind
+    halpern_infeasibility, into what ctypes counts as the tail padding of SolverSettingsWithRays (whose size is rounded up to the
+    doubles' alignment); a ctypes field of a subclass would start behind that padding, four bytes late.  So the field is a view of
+    those four bytes -- inside the structure's own buffer -- and not an entry of _fields_; the two classes above keep the ends their
+    tests pin.  The struct every call passes now, and what default_settings() makes."""
+    _fields_ = []
+    _LOCKSTEP_RAYS_OFFSET = SolverSettingsWithRays.halpern_infeasibility.offset + C.sizeof(c_int)
+
+    @property
+    def halpern_lockstep_rays(self):
+        return c_int.from_buffer(self, self._LOCKSTEP_RAYS_OFFSET).value
+
+    @halpern_lockstep_rays.setter
+    def halpern_lockstep_rays(self, value):
+        c_int.from_buffer(self, self._LOCKSTEP_RAYS_OFFSET).value = int(value)
+
+
+# (the same assertion as above, for a field the C compiler places without padding: it lies inside the structure ctypes allocates)
+assert SolverSettingsWithLockstepRays._LOCKSTEP_RAYS_OFFSET == SolverSettingsWithRays.halpern_infeasibility.offset + C.sizeof(c_int)
+assert SolverSettingsWithLockstepRays._LOCKSTEP_RAYS_OFFSET + C.sizeof(c_int) <= C.sizeof(SolverSettingsWithLockstepRays) == C.sizeof(SolverSettingsWithRays)
+
+
 class Result(C.Structure):
     _fields_ = [("status", c_int), ("steps_taken", c_int), ("attempted_steps", c_int),
                 ("returned_average", c_int), ("num_restarts", c_int), ("num_major_iterations", c_int),
@@ -356,6 +379,10 @@ _proto("pdlpdev_resident_size", c_int, c_int, c_int, C.c_int64)
 if hasattr(lib, "pdlpdev_resident_tier"):  # (an older build given through CUOPT_AMD_LIB does not export it)
     _proto("pdlpdev_resident_tier", c_int, c_int, c_int, C.c_int64)
 _proto("pdlpdev_batch_time_kernels", c_int, c_void_p, c_int, c_void_p)
+if hasattr(lib, "pdlpdev_batch_spmv"):  # (an older build given through CUOPT_AMD_LIB does not export them)
+    _proto("pdlpdev_batch_spmv", c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p)
+    _proto("pdlpdev_batch_ray_stats", c_int, c_void_p, c_void_p)
+    _proto("pdlpdev_batch_halpern_rays", c_int, c_void_p, c_void_p)
 _proto("pdlpdev_synthetic_lp", c_int, c_int, c_int, c_int, c_int, C.c_uint64, *([c_void_p] * 8))
 
 if hasattr(lib, "pdlpdev_set_halpern"):  # (an older build given through CUOPT_AMD_LIB has no Halpern mode)
@@ -620,7 +647,7 @@ def hyper_preset(mode=1):
 
 
 def default_settings(**over):
-    s = SolverSettingsWithRays()
+    s = SolverSettingsWithLockstepRays()
     lib.cuoptamd_default_settings(C.byref(s))
     tol = over.pop("tol", None)
     if tol is not None:
@@ -841,7 +868,9 @@ class SharedMatrixBatch:
     workgroup each in one launch per phase; every LP's trajectory is bit-identical to its own Solver.advance.  CuOptError(-7) when
     the solvers are eligible for neither (the caller then advances them one by one).  Solvers in reflected Halpern mode (mode=4) on
     the multi-launch path form the lockstep batch only when EVERY member was created with halpern_lockstep=1 (their own K-wide product
-    kernels; a jagged side is refused); without it, or mixed with averaging solvers or with members that lack it: CuOptError(-7)."""
+    kernels; a jagged side is refused); without it, or mixed with averaging solvers or with members that lack it: CuOptError(-7).
+    Members with halpern_infeasibility=1 are taken only when EVERY member has halpern_lockstep_rays=1 (their ray passes then run as one
+    K-wide pass, ray_stats() counts them); otherwise CuOptError(-7), by name."""
 
     def __init__(self, solvers):
         self.solvers = list(solvers)
@@ -942,6 +971,35 @@ class SharedMatrixBatch:
             raise CuOptError(rc, lib.pdlpdev_last_error().decode())
         return dict(zip(("primal", "a_dual", "at_step", "decisions"), out.tolist()))
 
+    def spmv(self, vectors, transpose=False, on=None):
+        """pdlpdev_batch_spmv: the K-wide plain product of the lockstep batch (kb_plain) -- out[l] = A vectors[l] (A^T with
+        transpose=True) for the members with on[l] != 0 (default: all), each bit for bit what the parent's device.spmv gives;
+        returns the K output arrays (an unserved member's keeps the NaN it was made with)"""
+        k = len(self.solvers)
+        s0 = self.solvers[0]
+        cols, rows = (s0.m, s0.n) if transpose else (s0.n, s0.m)
+        ins = [_f64(v) for v in vectors]
+        if len(ins) != k or any(v.shape != (cols,) for v in ins):
+            raise ValueError("spmv: one vector of %d entries per member" % cols)
+        outs = [np.full(rows, np.nan) for _ in range(k)]
+        flags = _i32(np.ones(k, np.int32) if on is None else on)
+        if flags.shape != (k,):
+            raise ValueError("spmv: one flag per member")
+        arr = lambda vs: (c_void_p * k)(*[v.ctypes.data for v in vs])
+        rc = lib.pdlpdev_batch_spmv(c_void_p(lib.cuoptamd_batch_device(self.handle)), int(bool(transpose)), arr(ins), arr(outs), _ptr(flags))
+        if rc != 0:
+            raise CuOptError(rc, lib.pdlpdev_last_error().decode())
+        return outs
+
+    def ray_stats(self):
+        """pdlpdev_batch_ray_stats of a lockstep batch in reflected Halpern mode: dict wide_passes (K-wide ray passes enqueued) /
+        members_served (member passes those served) / single_passes (single ray passes the members' contexts enqueued while in the batch)"""
+        out = np.zeros(4, np.int64)
+        rc = lib.pdlpdev_batch_ray_stats(c_void_p(lib.cuoptamd_batch_device(self.handle)), _ptr(out))
+        if rc != 0:
+            raise CuOptError(rc, lib.pdlpdev_last_error().decode())
+        return dict(zip(("wide_passes", "members_served", "single_passes"), out.tolist()[:3]))
+
     def close(self):
         if self.handle:
             lib.cuoptamd_batch_destroy(self.handle)
@@ -961,7 +1019,7 @@ def batch_solve(problems, mode=1, max_threads=0, device=0, **setting_overrides):
     """cuoptamd_batch_solve: independent LPs solved concurrently on one GPU -> list of result dicts (batch_solve_last_path() says
     which way the call took: mode=4 with halpern_resident=1, halpern_batch=1 puts LPs of resident size into K workgroups of one launch;
     mode=4 with halpern_lockstep=1 advances LPs that share matrix and objective as lockstep batches of 16 / 8 / 4, the rest one after the
-    other through the clones)"""
+    other through the clones; with halpern_infeasibility=1 the lockstep batches need halpern_lockstep_rays=1 as well)"""
     k = len(problems)
     lps, keep = (LP * k)(), []
     for i, p in enumerate(problems):

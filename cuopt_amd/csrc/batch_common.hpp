@@ -214,3 +214,30 @@ struct BatchProductSide {
 // lp_table / halpern_table: the device tables of K BatchLp / BatchHalpernLp (untyped here: the two structs are internal to each unit)
 int batch_halpern_enqueue_tail(int K, hipStream_t s, const BatchProductSide& A, const BatchProductSide& T, const void* lp_table, const void* halpern_table,
                                double* xK, double* yK);
+
+// kernels_batch_halpern_ray.hip: the K-wide ray pass of a batch in reflected Halpern mode and the K-wide plain product it is made of.
+// What the pass needs of one LP, in device memory, kept current as the two tables above are (every vector is the member's own: a
+// clone shares none of them with its parent).  Which LPs a pass serves and their reduced-cost rules travel by value in the launch
+// arguments (bit l of on_mask / rule_mask): the table changes with a reset only, and a pass uploads nothing.
+struct BatchRayLp {
+  const pdlpdev_ctl* ctl;
+  const double *avgx, *avgy;             // T(z^k)
+  const double *x0, *x1, *y0, *y1;       // z^k: the side `cur` does NOT select
+  double *tmp_n, *tmp_m;                 // the scaled displacement (k_halpern_ray_diff's slots)
+  double *ax, *aty;                      // ax_u / aty_u[PDLPDEV_CURRENT]: the two products formed from it
+  const double *lo_u, *hi_u, *lb_u, *ub_u;
+  double *part_g, *scal;
+};
+static_assert(sizeof(BatchRayLp) == 17 * sizeof(void*), "no padding: batch_refresh_table compares entries with memcmp");
+// what the K LPs share (the parent's): dimensions, the scaling vectors, the unscaled objective
+struct BatchRayShared {
+  int n, m;
+  const double *dr, *dc, *c_u;
+};
+// the pass for the LPs of on_mask behind whatever runs on s: kb_ray_diff, kb_plain on either side, the two statistics kernels
+// (grid y <-> LP), one finalize (workgroup <-> LP) -- six launches, two streams of the matrix
+int batch_halpern_enqueue_rays(int K, hipStream_t s, const BatchProductSide& A, const BatchProductSide& T, const void* ray_table, const BatchRayShared& sh,
+                               unsigned on_mask, unsigned rule_mask, double* xK, double* yK);
+// vK[i * K + l] = (transpose ? tmp_m : tmp_n of LP l)[i] (0 for an LP outside on_mask), then ONE kb_plain<K> on that side: row sums to
+// the LP's aty / ax for the LPs of on_mask, nobody else's output is touched (pdlpdev_batch_spmv)
+int batch_enqueue_plain(int K, hipStream_t s, const BatchProductSide& side, int transpose, int len, const void* ray_table, unsigned on_mask, double* vK);

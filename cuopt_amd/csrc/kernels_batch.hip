@@ -458,6 +458,11 @@ struct pdlpdev_batch {
   bool halpern = false;
   BatchHalpernLp* hl_dev = nullptr;
   std::vector<BatchHalpernLp> hl_host;
+  // ... and the third, of the K-wide ray pass (kernels_batch_halpern_ray.hip; pdlpdev_batch_halpern_rays)
+  BatchRayLp* ray_dev = nullptr;
+  std::vector<BatchRayLp> ray_host;
+  int64_t ray_wide = 0, ray_served = 0;  // K-wide passes enqueued, member passes they served
+  int64_t ray_single0[kBatchMax] = {0};  // the members' own counts of single passes when they joined
   std::map<int, hipGraphExec_t> graphs;
 };
 
@@ -467,6 +472,12 @@ static BatchLp batch_lp_of(const pdlpdev_ctx* c)
 }
 
 static BatchHalpernLp batch_halpern_lp_of(const pdlpdev_ctx* c) { return BatchHalpernLp{c->hal, c->avgx, c->avgy, c->lrx, c->lry, c->lraty}; }
+
+static BatchRayLp batch_ray_lp_of(const pdlpdev_ctx* c)
+{
+  return BatchRayLp{c->ctl, c->avgx, c->avgy, c->x[0], c->x[1], c->y[0], c->y[1], c->tmp_n, c->tmp_m, c->ax_u[PDLPDEV_CURRENT], c->aty_u[PDLPDEV_CURRENT],
+                    c->lo_u, c->hi_u, c->lb_u, c->ub_u, c->part_g, c->scal};
+}
 
 // A reset that gives a member row bounds of its own moves its lo / hi (pdlpdev_reset: copy on change): the table the kernels read
 // follows (the kernels -- and the captured graphs -- take the table's address, not its contents).
@@ -483,6 +494,15 @@ static int batch_refresh_table(pdlpdev_batch* b)
     if (memcmp(&now, &b->hl_host[l], sizeof(BatchHalpernLp)) != 0) b->hl_host[l] = now, hl_changed = true;
   }
   if (hl_changed) HIP_TRY(hipMemcpyAsync(b->hl_dev, b->hl_host.data(), b->K * sizeof(BatchHalpernLp), hipMemcpyHostToDevice, b->stream));
+  bool ray_changed = false;  // (the ray pass's table: a reset may move a member's unscaled row bounds as well)
+  for (int l = 0; b->halpern && l < b->K; ++l) {
+    const BatchRayLp now = batch_ray_lp_of(b->ctx[l]);
+    if (memcmp(&now, &b->ray_host[l], sizeof(BatchRayLp)) != 0) b->ray_host[l] = now, ray_changed = true;
+  }
+  if (ray_changed) {
+    HIP_TRY(hipMemcpyAsync(b->ray_dev, b->ray_host.data(), b->K * sizeof(BatchRayLp), hipMemcpyHostToDevice, b->stream));
+    hl_changed = true;  // (waited for below, as the other tables are)
+  }
   bool sp_changed = false;  // (the step-size exponents travel by value in the decision kernel's arguments)
   for (int l = 0; l < b->K; ++l)
     if (memcmp(&b->dargs_host[l].sp, &b->ctx[l]->sp, sizeof(pdlpdev_step_params)) != 0) b->dargs_host[l].sp = b->ctx[l]->sp, sp_changed = true;
@@ -784,7 +804,8 @@ int pdlpdev_batch_create(pdlpdev_batch** out, pdlpdev_ctx** ctx, int K)
     pdlpdev_ctx* c = ctx[l];
     b->ctx[l]      = c;
     h[l]     = batch_lp_of(c);
-    if (halpern) b->hl_host.push_back(batch_halpern_lp_of(c));
+    if (halpern) b->hl_host.push_back(batch_halpern_lp_of(c)), b->ray_host.push_back(batch_ray_lp_of(c));
+    b->ray_single0[l] = c->stat_single_rays;
     dargs[l] = pdlpdev_decision_args{c->ctl, c->A.part, side[0].W, c->At.part, side[1].W, c->sp};
     c->batches_alive += 1;
   }
@@ -798,6 +819,8 @@ int pdlpdev_batch_create(pdlpdev_batch** out, pdlpdev_ctx** ctx, int K)
   if (halpern) {
     HIP_TRY(hipMalloc((void**)&b->hl_dev, K * sizeof(BatchHalpernLp)));
     HIP_TRY(hipMemcpyAsync(b->hl_dev, b->hl_host.data(), K * sizeof(BatchHalpernLp), hipMemcpyHostToDevice, b->stream));
+    HIP_TRY(hipMalloc((void**)&b->ray_dev, K * sizeof(BatchRayLp)));
+    HIP_TRY(hipMemcpyAsync(b->ray_dev, b->ray_host.data(), K * sizeof(BatchRayLp), hipMemcpyHostToDevice, b->stream));
   }
   HIP_TRY(hipMemcpyAsync(b->dargs_dev, dargs.data(), K * sizeof(pdlpdev_decision_args), hipMemcpyHostToDevice, b->stream));
   HIP_TRY(hipMemsetAsync(b->xK, 0, ((size_t)c0->n * K + 64) * sizeof(double), b->stream));
@@ -816,6 +839,7 @@ void pdlpdev_batch_destroy(pdlpdev_batch* b)
   for (auto& kv : b->graphs) (void)hipGraphExecDestroy(kv.second);
   if (b->lp_dev) (void)hipFree(b->lp_dev);
   if (b->hl_dev) (void)hipFree(b->hl_dev);
+  if (b->ray_dev) (void)hipFree(b->ray_dev);
   if (b->dargs_dev) (void)hipFree(b->dargs_dev);
   if (b->xK) (void)hipFree(b->xK);
   if (b->yK) (void)hipFree(b->yK);
@@ -875,8 +899,102 @@ int pdlpdev_batch_run(pdlpdev_batch* b, const int32_t* targets, pdlpdev_ctl* ctl
     if (!b->halpern) TRY(batch_fetch_ctl(b));  // (k_set_error may have run; in Halpern mode nothing moved since the fetch above)
     if (++guard > 100000) return fail(-6, "pdlpdev_batch_run: no progress");
   }
+  // (the pinned control blocks are what the device holds until something moves a member again: pdlpdev_batch_halpern_rays reads them)
+  for (int l = 0; l < K; ++l) b->ctx[l]->batch_ctl_fresh = true;
   if (ctl)
     for (int l = 0; l < K; ++l) ctl[l] = *b->ctx[l]->ctl_h;
+  return 0;
+}
+
+static BatchProductSide batch_product_side(const pdlpdev_batch::Side& S, const pdlpdev_ctx::MatrixSide& M)
+{
+  return BatchProductSide{S.W, S.row0, S.panel, M.hot.off, M.hot.idx, M.hot.val};
+}
+
+// The ray pass (enqueue_halpern_ray) for the members with rule[l] >= 0 (the reduced-cost rule, 0 / 1; -1: not in the pass) as ONE K-wide
+// pass on the batch's stream behind whatever ran: kernels_batch_halpern_ray.hip.  Nothing is read back and nothing is waited for: the
+// member contexts' evaluations run on this same stream (pdlpdev_batch_create refuses contexts on another one), so they are ordered
+// behind the pass without an event, and their read-back of scal[0..41) brings the figures along.  A member is served only if its
+// control block -- as pdlpdev_batch_run's last read-back left it, nothing having moved the member since -- says error == 0 and at
+// least one step; a served context notes the step count and the rule, and its pdlpdev_major_eval then leaves the single pass out.
+int pdlpdev_batch_halpern_rays(pdlpdev_batch* b, const int32_t* rule)
+{
+  if (!b || !rule) return fail(-1, "pdlpdev_batch_halpern_rays: null argument");
+  if (!b->halpern) return fail(-7, "pdlpdev_batch_halpern_rays: the batch is not in reflected Halpern mode (the averaging iteration has no ray pass)");
+  HIP_TRY(hipSetDevice(b->device));
+  TRY(batch_refresh_table(b));
+  unsigned on_mask = 0, rule_mask = 0;
+  int served = 0;
+  for (int l = 0; l < b->K; ++l) {
+    pdlpdev_ctx* c = b->ctx[l];
+    if (rule[l] < 0 || !c->batch_ctl_fresh || c->ctl_h->error != 0 || c->ctl_h->steps_taken < 1) continue;
+    on_mask |= 1u << l, rule_mask |= (rule[l] != 0 ? 1u : 0u) << l;
+    served += 1;
+  }
+  if (on_mask == 0) return 0;
+  roctx::Range range("pdlp: K-wide Halpern ray pass");
+  pdlpdev_ctx* c0 = b->ctx[0];
+  const BatchRayShared sh{c0->n, c0->m, c0->dr, c0->dc, c0->c_u};
+  TRY(batch_halpern_enqueue_rays(b->K, b->stream, batch_product_side(b->a_side, c0->A), batch_product_side(b->t_side, c0->At), b->ray_dev, sh, on_mask, rule_mask,
+                                 b->xK, b->yK));
+  for (int l = 0; l < b->K; ++l)
+    if ((on_mask >> l) & 1u) {
+      pdlpdev_ctx* c     = b->ctx[l];
+      c->ctl_h_current   = true;  // (batch_ctl_fresh: the read-back behind the attempts is what the device holds)
+      c->batch_ray_steps = c->ctl_h->steps_taken, c->batch_ray_rule = (int)((rule_mask >> l) & 1u);
+    }
+  b->ray_wide += 1, b->ray_served += served;
+  return 0;
+}
+
+// {K-wide passes enqueued, member passes they served, single passes the members' contexts enqueued since they joined the batch, 0}
+int pdlpdev_batch_ray_stats(pdlpdev_batch* b, int64_t out[4])
+{
+  if (!b || !out) return fail(-1, "pdlpdev_batch_ray_stats: null argument");
+  out[0] = b->ray_wide, out[1] = b->ray_served, out[2] = 0, out[3] = 0;
+  for (int l = 0; l < b->K; ++l) out[2] += b->ctx[l]->stat_single_rays - b->ray_single0[l];
+  return 0;
+}
+
+// The K-wide plain product as a parity hook, the batch twin of pdlpdev_spmv: out[l] = A in[l] (transpose: A^T in[l]) for the members
+// with on[l] != 0 (on == NULL: all) through ONE kb_plain<K>; the other members' outputs are not touched.  The vectors pass through the
+// members' tmp_n / tmp_m (where pdlpdev_spmv puts them) and the batch's interleaved vector of that side, all free between runs.
+int pdlpdev_batch_spmv(pdlpdev_batch* b, int transpose, const double* const* in, double* const* out, const int32_t* on)
+{
+  if (!b || !in || !out) return fail(-1, "pdlpdev_batch_spmv: null argument");
+  const pdlpdev_batch::Side& S = transpose ? b->t_side : b->a_side;
+  if (S.jag) return fail(-7, "pdlpdev_batch_spmv: the %s side is in the jagged layout (the K-wide plain product walks the CSR arrays)", transpose ? "A^T" : "A");
+  HIP_TRY(hipSetDevice(b->device));
+  pdlpdev_ctx* c0 = b->ctx[0];
+  hipStream_t s   = b->stream;
+  const int K = b->K, rows = transpose ? c0->n : c0->m, cols = transpose ? c0->m : c0->n;
+  unsigned on_mask = 0;
+  for (int l = 0; l < K; ++l)
+    if (!on || on[l]) {
+      if (!in[l] || !out[l]) return fail(-1, "pdlpdev_batch_spmv: member %d is in the product without a vector", l);
+      on_mask |= 1u << l;
+    }
+  if (on_mask == 0) return 0;
+  struct Table {  // (the outputs are the members' tmp vectors, not the ray pass's: a table of its own, released on every way out)
+    BatchRayLp* p = nullptr;
+    ~Table() { if (p) (void)hipFree(p); }
+  } table;
+  std::vector<BatchRayLp> host(K);
+  for (int l = 0; l < K; ++l) {
+    host[l]    = batch_ray_lp_of(b->ctx[l]);
+    host[l].ax = b->ctx[l]->tmp_m, host[l].aty = b->ctx[l]->tmp_n;
+  }
+  HIP_TRY(hipMalloc((void**)&table.p, K * sizeof(BatchRayLp)));
+  HIP_TRY(hipMemcpyAsync(table.p, host.data(), K * sizeof(BatchRayLp), hipMemcpyHostToDevice, s));
+  for (int l = 0; l < K; ++l)
+    if ((on_mask >> l) & 1u)
+      HIP_TRY(hipMemcpyAsync(transpose ? b->ctx[l]->tmp_m : b->ctx[l]->tmp_n, in[l], (size_t)cols * sizeof(double), hipMemcpyHostToDevice, s));
+  HIP_TRY(hipStreamSynchronize(s));  // (the table and the vectors have left the caller's memory)
+  TRY(batch_enqueue_plain(K, s, batch_product_side(S, transpose ? c0->At : c0->A), transpose, cols, table.p, on_mask, transpose ? b->yK : b->xK));
+  for (int l = 0; l < K; ++l)
+    if ((on_mask >> l) & 1u)
+      HIP_TRY(hipMemcpyAsync(out[l], transpose ? b->ctx[l]->tmp_n : b->ctx[l]->tmp_m, (size_t)rows * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
   return 0;
 }
 

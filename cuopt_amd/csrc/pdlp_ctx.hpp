@@ -526,6 +526,13 @@ struct pdlpdev_ctx {
   //                  side from there instead of running the product again (CUOPT_AMD_TUNE=eval_reuse_aty=0: never).
   //   ctl_h_current  the pinned copy of the control block is what the device holds: the read-back behind k_set_target is skipped.
   bool aty_valid = false, ctl_h_current = false;
+  // A member of a lockstep batch (kernels_batch.hip); loop_state_touched drops both:
+  //   batch_ctl_fresh   pdlpdev_batch_run's last read-back of the control block is what the device holds
+  //   batch_ray_steps   >= 0: the K-wide ray pass (pdlpdev_batch_halpern_rays) served this context at that accepted-step count, with the
+  //                     reduced-cost rule batch_ray_rule: the evaluation of T(z^k) at that count leaves the single pass out
+  bool batch_ctl_fresh = false;
+  int batch_ray_steps = -1, batch_ray_rule = -1;
+  int64_t stat_single_rays = 0;  // single ray passes enqueued (enqueue_halpern_ray)
   int eval_reuse_aty = 1;   // CUOPT_AMD_TUNE=eval_reuse_aty
   int spare_attempts = 0;   // pdlpdev_run_period: empty-unless-needed attempts behind a period's, from the rejections the period before saw
   // pdlpdev_loop_stats: evaluations of the current iterate that reused A^T y / ran the product, synchronisations inside
@@ -610,7 +617,7 @@ constexpr int kRayRows = 16;  // max homogeneous primal residual, ||dy||_inf, su
 constexpr int kRayCols = 24;  // max homogeneous dual residual, ||rc||_inf, ||dx||_inf, max bound violation, sum B(rc, lb, ub), c . dx
 constexpr int kRayMark = 30;  // the accepted-step count the pass ran at, and its reduced-cost rule (0 / 1)
 // the iterate or the control block changed behind the loop's back
-inline void loop_state_touched(pdlpdev_ctx* c) { c->aty_valid = false, c->ctl_h_current = false; }
+inline void loop_state_touched(pdlpdev_ctx* c) { c->aty_valid = false, c->ctl_h_current = false, c->batch_ctl_fresh = false, c->batch_ray_steps = -1; }
 
 // A kernel that takes more dynamic LDS than the default limit allows: the attribute is per kernel and device, and set ONCE, under the
 // lock (batch solves create contexts from many threads), the first time the triple (kernel, device, size) comes by.  A kernel's

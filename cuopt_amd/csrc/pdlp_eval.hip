@@ -6,6 +6,7 @@
 #include "pdlp_setup.hpp"
 #include "pdlp_launch.hpp"
 #include "pdlp_core_internal.hpp"
+#include "halpern_ray_stats.hpp"
 
 // ================================================================================================
 // kernels: major iteration
@@ -158,74 +159,20 @@ k_halpern_ray_diff(int n, int m, const pdlpdev_ctl* __restrict__ ctl, const doub
     if (i < m) dy[i] = avgy[i] - yk[i];
   }
 }
-// k_infeas_rows' statistics with the unscaled ray: (A dx_u)_i = (A^ dx^)_i / D_r,i and dy_u,i = dy^_i D_r,i
+// k_infeas_rows' / k_infeas_cols' statistics with the unscaled ray: the bodies are halpern_ray_stats.hpp's (shared with the K-wide pass of
+// the lockstep batch, kernels_batch_halpern_ray.hip)
 __global__ void __launch_bounds__(kBlock)
 k_halpern_ray_rows(int m, int nbg, const double* __restrict__ a_dx, const double* __restrict__ dy, const double* __restrict__ dr,
                    const double* __restrict__ lo_u, const double* __restrict__ hi_u, double* __restrict__ part)
 {
-  __shared__ double red[12];
-  double mx[2] = {0.0, 0.0}, sm[1] = {0.0};
-  for (int i = blockIdx.x * kBlock + threadIdx.x; i < m; i += gridDim.x * kBlock) {
-    const double d  = dr[i];
-    const double lo = lo_u[i], hi = hi_u[i];
-    const double hl = dfinite(lo) ? 0.0 : lo, hu = dfinite(hi) ? 0.0 : hi;  // zero_if_is_finite
-    const double r  = fabs(violation(a_dx[i] / d, hl, hu));
-    const double yi = dy[i] * d;
-    mx[0] = r > mx[0] ? r : mx[0];
-    mx[1] = fabs(yi) > mx[1] ? fabs(yi) : mx[1];
-    sm[0] += bound_value_product(yi, lo, hi);
-  }
-  block_reduce<MaxOp, 2>(mx, red);
-  __syncthreads();
-  block_reduce<SumOp, 1>(sm, red + 8);
-  if (threadIdx.x == 0) {
-    part[blockIdx.x]           = mx[0];
-    part[nbg + blockIdx.x]     = mx[1];
-    part[2 * nbg + blockIdx.x] = sm[0];
-  }
+  halpern_ray_rows_block(m, nbg, a_dx, dy, dr, lo_u, hi_u, part);
 }
-// k_infeas_cols' statistics likewise: (A^T dy_u)_j = (A^T^ dy^)_j / D_c,j and dx_u,j = dx^_j D_c,j; both reduced-cost rules look at the
-// ray's own x.  mark (two doubles): the accepted-step count the pass belongs to and its rule, for the host to recognise the figures by.
 __global__ void __launch_bounds__(kBlock)
 k_halpern_ray_cols(int n, int nbg, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ at_dy, const double* __restrict__ dx,
                    const double* __restrict__ dc, const double* __restrict__ c_u, const double* __restrict__ lb_u,
                    const double* __restrict__ ub_u, int rule_finite, double* __restrict__ part, double* __restrict__ mark)
 {
-  __shared__ double red[28];
-  if (blockIdx.x == 0 && threadIdx.x == 0) mark[0] = (double)ctl->steps_taken, mark[1] = (double)rule_finite;
-  double mx[4] = {0.0, 0.0, 0.0, 0.0}, sm[2] = {0.0, 0.0};
-  for (int j = blockIdx.x * kBlock + threadIdx.x; j < n; j += gridDim.x * kBlock) {
-    const double d  = dc[j];
-    const double g  = -1.0 * (at_dy[j] / d);
-    const double xj = dx[j] * d;
-    const double lb = lb_u[j], ub = ub_u[j];
-    const double bv = g > 0.0 ? lb : ub;
-    double rc;
-    if (g == 0.0)
-      rc = g;
-    else if (rule_finite)
-      rc = dfinite(bv) ? g : 0.0;
-    else
-      rc = fabs(xj - bv) <= fabs(xj) ? g : 0.0;
-    const double rd = fabs(g - rc);
-    double viol     = 0.0;  // max_violation, utils.cuh:181-193
-    if (dfinite(lb)) viol = dmax(viol, -xj);
-    if (dfinite(ub)) viol = dmax(viol, xj);
-    mx[0] = rd > mx[0] ? rd : mx[0];
-    mx[1] = fabs(rc) > mx[1] ? fabs(rc) : mx[1];
-    mx[2] = fabs(xj) > mx[2] ? fabs(xj) : mx[2];
-    mx[3] = viol > mx[3] ? viol : mx[3];
-    sm[0] += bound_value_product(rc, lb, ub);
-    sm[1] += c_u[j] * xj;
-  }
-  block_reduce<MaxOp, 4>(mx, red);
-  __syncthreads();
-  block_reduce<SumOp, 2>(sm, red + 16);
-  if (threadIdx.x == 0) {
-    for (int q = 0; q < 4; ++q) part[(size_t)q * nbg + blockIdx.x] = mx[q];
-    part[(size_t)4 * nbg + blockIdx.x] = sm[0];
-    part[(size_t)5 * nbg + blockIdx.x] = sm[1];
-  }
+  halpern_ray_cols_block(n, nbg, ctl, at_dy, dx, dc, c_u, lb_u, ub_u, rule_finite, part, mark);
 }
 // the unscaled displacement for the caller (pdlpdev_halpern_get_ray)
 __global__ void __launch_bounds__(kBlock)
@@ -527,7 +474,10 @@ int pdlpdev_major_eval(pdlpdev_ctx* ctx, int average_mode, int rc_rule_finite_bo
       TRY(resident_halpern_eval(ctx, rc_rule_finite_bounds, want_linf ? 1 : 0, eps_rel_primal, eps_rel_dual));
     } else {
       TRY(enqueue_halpern_eval(ctx, rc_rule_finite_bounds, eps_rel_primal, eps_rel_dual, 0));
-      if (ctx->halpern_rays) TRY(enqueue_halpern_ray(ctx, rc_rule_finite_bounds));  // (scal[16..32): inside the read-back below)
+      // (scal[16..32): inside the read-back below.  A member of a lockstep batch that the K-wide pass served at this step count with
+      // this rule has its figures there already -- pdlpdev_batch_halpern_rays, on this same stream: ordered in front of the read-back)
+      const bool served = ctx->batch_ray_steps >= 0 && ctx->batch_ray_steps == ctx->ctl_h->steps_taken && ctx->batch_ray_rule == (rc_rule_finite_bounds != 0 ? 1 : 0);
+      if (ctx->halpern_rays && !served) TRY(enqueue_halpern_ray(ctx, rc_rule_finite_bounds));
       TRY(fetch_scalars(ctx, 41));
       ctx->stat_loop_syncs += 1;
     }
@@ -633,6 +583,7 @@ int enqueue_halpern_ray(pdlpdev_ctx* ctx, int rc_rule_finite_bounds)
   hipStream_t s = ctx->stream;
   const int n = ctx->n, m = ctx->m;
   double *dx = ctx->tmp_n, *dy = ctx->tmp_m, *a_dx = ctx->ax_u[PDLPDEV_CURRENT], *at_dy = ctx->aty_u[PDLPDEV_CURRENT];
+  ctx->stat_single_rays += 1;
   k_halpern_ray_diff<<<grid_for(std::max(n, m)), kBlock, 0, s>>>(n, m, ctx->ctl, ctx->x[0], ctx->x[1], ctx->y[0], ctx->y[1], ctx->avgx, ctx->avgy, dx, dy);
   launch_plain(ctx, 0, dx, a_dx);
   launch_plain(ctx, 1, dy, at_dy);

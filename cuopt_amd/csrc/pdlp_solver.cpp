@@ -869,6 +869,7 @@ void cuoptamd_default_settings(cuoptamd_settings* s)
   s->halpern_batch                    = 0;
   s->halpern_lockstep                 = 0;
   s->halpern_infeasibility            = 0;
+  s->halpern_lockstep_rays            = 0;
 }
 
 // Plain parallel counting sort by column (small matrices, and the fallback of the blocked one below).  Thread t owns a
@@ -1652,7 +1653,14 @@ int cuoptamd_batch_create(cuoptamd_solver** solvers, int K, cuoptamd_batch** out
       return fail(-7, "cuoptamd_batch_create: %d of the %d solvers in %s have halpern_lockstep set and the others not: a lockstep batch needs it "
                       "on every member", lockstep, K, kHalpernName);
     if (K > 16) return fail(-7, "cuoptamd_batch_create: a lockstep batch holds 2, 4, 8 or 16 LPs");
-    for (int l = 0; l < K; ++l)  // (the K-wide products have no ray pass: such LPs run one after the other)
+    // halpern_lockstep_rays on every member: the batch takes members with halpern_infeasibility (cuoptamd_batch_advance runs their ray
+    // passes K-wide, pdlpdev_batch_halpern_rays); on none: such members are refused, as before -- those LPs run one after the other
+    int rays = 0;
+    for (int l = 0; l < K; ++l) rays += solvers[l]->S.halpern_lockstep_rays != 0;
+    if (rays != 0 && rays < K)
+      return fail(-7, "cuoptamd_batch_create: %d of the %d solvers in %s have halpern_lockstep_rays set and the others not: a lockstep batch needs it "
+                      "on every member", rays, K, kHalpernName);
+    for (int l = 0; rays == 0 && l < K; ++l)
       if (solvers[l]->S.halpern_infeasibility)
         return fail(-7, "cuoptamd_batch_create: LP %d has halpern_infeasibility set: the lockstep batch of the %s does not detect infeasibility", l, kHalpernName);
     rc = pdlpdev_batch_create(&dev, ctx.data(), K);
@@ -1871,6 +1879,24 @@ int cuoptamd_batch_advance(cuoptamd_batch* b, int32_t max_new_iterations, cuopta
         b->s[l]->ctl = ctl[l];
         advance_after_attempts(b->s[l]);
       }
+    // Halpern lockstep batch with halpern_lockstep_rays: the ray passes of the members whose major iteration is due at the step count
+    // they have just reached go out as ONE K-wide pass behind the attempts.  Nothing is waited for here: each member's own evaluation
+    // (halpern_major_iteration, the next trip's advance_to_attempts) runs behind it on the same stream and reads the figures back.
+    if (b->halpern && b->s[0]->S.halpern_lockstep_rays) {
+      int32_t rule[16];
+      bool any_ray = false;
+      for (int l = 0; l < K; ++l) {
+        cuoptamd_solver* s = b->s[l];
+        rule[l]            = -1;
+        if (target[l] <= 0 || !s->S.halpern_infeasibility || ctl[l].error != 0 || ctl[l].steps_taken != target[l]) continue;
+        if (!major_due_at(s->H, s->iteration_offset + target[l])) continue;
+        rule[l] = major_eval_request(s).rule_finite ? 1 : 0, any_ray = true;
+      }
+      if (any_ray) {
+        rc = pdlpdev_batch_halpern_rays(b->dev, rule);
+        if (rc != 0) return leave(fail(rc, "pdlpdev_batch_halpern_rays: %s", pdlpdev_last_error()));
+      }
+    }
   }
 }
 
@@ -2341,6 +2367,13 @@ static int shared_matrix_batch_solve(int32_t count, const cuoptamd_lp* lps, cons
     // created with them.
     int32_t lay[8] = {0};
     if (parent->dev && pdlpdev_layout_info(parent->dev, lay) == 0 && (lay[0] == 3 || lay[3] == 3)) lockstep = false;
+    // Reflected Halpern mode with halpern_infeasibility and halpern_lockstep_rays: a side in the row-sum panels keeps the LPs one after
+    // the other as well.  The routing rule (docs/design/07_measurement.md, "Halpern mode": at K = 4 the lockstep median must beat the
+    // sequential median by more than the two spreads combined) is stated on the wall time of this call to 1e-8, and the panels miss
+    // it: four variants of c3 take 9.09 s in lockstep against 8.21 s one after the other -- the batch runs K-wide until its longest
+    // member ends (17 560 steps against 10 240 ... 13 160), at 1.23x the sequential rate.  The CSR stream layout passes (c2: 0.286 s
+    // against 0.438 s).  cuoptamd_batch_create itself takes such members on either layout: the caller who knows its LPs decides.
+    if (hyper->algorithm == 1 && settings->halpern_infeasibility && settings->halpern_lockstep_rays && (lay[0] == 1 || lay[3] == 1)) lockstep = false;
   }
   // the solver of slot q takes LP i: the parent as created (i = 0), a new clone, or an existing solver reset to LP i's bounds
   auto take = [&](int q, int i) -> int {

@@ -48,6 +48,7 @@ CUOPT_AMD_HALPERN_RESIDENT = "amd_halpern_resident"  # 0 / 1: PDLPSolverMode.Hal
 CUOPT_AMD_HALPERN_BATCH = "amd_halpern_batch"  # 0 / 1: ... and the LPs of a BatchSolve in K workgroups of one launch
 CUOPT_AMD_HALPERN_LOCKSTEP = "amd_halpern_lockstep"  # 0 / 1: Halpern1 LPs of a BatchSolve over one matrix in lockstep batches of 16 / 8 / 4
 CUOPT_AMD_HALPERN_INFEASIBILITY = "amd_halpern_infeasibility"  # 0 / 1: Halpern1 detects infeasible / unbounded LPs (the displacement of a step)
+CUOPT_AMD_HALPERN_LOCKSTEP_RAYS = "amd_halpern_lockstep_rays"  # 0 / 1: ... and lockstep batches take such LPs (one K-wide ray pass for all members)
 
 
 class SolverMethod(IntEnum):  # solver_settings.py:44-60
@@ -307,7 +308,7 @@ class SolverSettings:  # solver_settings.py:99-330
         CUOPT_PER_CONSTRAINT_RESIDUAL: False, CUOPT_SAVE_BEST_PRIMAL_SO_FAR: False, CUOPT_FIRST_PRIMAL_FEASIBLE: False,
         CUOPT_LOG_FILE: "", CUOPT_LOG_TO_CONSOLE: False, CUOPT_CROSSOVER: False, CUOPT_SOLUTION_FILE: "",
         CUOPT_USER_PROBLEM_FILE: "", CUOPT_AMD_HALPERN_RESIDENT: 0, CUOPT_AMD_HALPERN_BATCH: 0,
-        CUOPT_AMD_HALPERN_LOCKSTEP: 0, CUOPT_AMD_HALPERN_INFEASIBILITY: 0,
+        CUOPT_AMD_HALPERN_LOCKSTEP: 0, CUOPT_AMD_HALPERN_INFEASIBILITY: 0, CUOPT_AMD_HALPERN_LOCKSTEP_RAYS: 0,
     }
 
     def __init__(self):
@@ -479,6 +480,7 @@ def Solve(data_model, solver_settings=None, log_file=""):
     over["halpern_batch"] = int(st[CUOPT_AMD_HALPERN_BATCH])
     over["halpern_lockstep"] = int(st[CUOPT_AMD_HALPERN_LOCKSTEP])
     over["halpern_infeasibility"] = int(st[CUOPT_AMD_HALPERN_INFEASIBILITY])
+    over["halpern_lockstep_rays"] = int(st[CUOPT_AMD_HALPERN_LOCKSTEP_RAYS])
     if st[CUOPT_LOG_FILE]:
         over["log_file"] = st[CUOPT_LOG_FILE].encode()
     t0 = time.perf_counter()
@@ -511,6 +513,7 @@ def BatchSolve(data_model_list, solver_settings=None, log_file=""):
     over["halpern_batch"] = int(st[CUOPT_AMD_HALPERN_BATCH])
     over["halpern_lockstep"] = int(st[CUOPT_AMD_HALPERN_LOCKSTEP])
     over["halpern_infeasibility"] = int(st[CUOPT_AMD_HALPERN_INFEASIBILITY])
+    over["halpern_lockstep_rays"] = int(st[CUOPT_AMD_HALPERN_LOCKSTEP_RAYS])
     t0 = time.perf_counter()
     out = capi.batch_solve([dm._problem_dict() for dm in data_model_list], mode=int(st[CUOPT_PDLP_SOLVER_MODE]), **over)
     sols = [Solution(ProblemCategory.LP, _named(dm, r["x"]), r["setup_seconds"] + r["loop_seconds"], r["x"], r["y"],

@@ -25,6 +25,11 @@
  *                            PrimalInfeasible, an unbounded one as DualInfeasible, at CUOPT_PRIMAL_INFEASIBLE_TOLERANCE /
  *                            CUOPT_DUAL_INFEASIBLE_TOLERANCE, instead of at its iteration or time limit.  CUOPT_INFEASIBILITY_DETECTION
  *                            (the averaging iteration's) stays a validation error under that mode; ignored by the other modes.
+ *   CUOPT_AMD_HALPERN_LOCKSTEP_RAYS  1 / 0 (default 0): with CUOPT_AMD_HALPERN_LOCKSTEP and CUOPT_AMD_HALPERN_INFEASIBILITY, the
+ *                            lockstep batches take LPs that detect infeasibility (cuoptamd_settings::halpern_lockstep_rays): the
+ *                            ray passes of a batch's members run as one K-wide pass, each member bit for bit as on its own; without
+ *                            it such LPs are solved one after the other, as before.  A single cuOptSolve is not changed by it
+ *                            (cuOptAmdGetSolveInfo reports "halpern_lockstep_rays"); ignored by the other solver modes.
  * Extra value of CUOPT_PDLP_SOLVER_MODE (constants.h stops at CUOPT_PDLP_SOLVER_MODE_FAST1 = 3):
  *   CUOPT_AMD_PDLP_SOLVER_MODE_HALPERN1 = 4: the restarted reflected Halpern iteration with a constant step size
  *                            (cuoptamd_hyper_preset(4), docs/design/04d_halpern_mode.md).  One GPU; CUOPT_INFEASIBILITY_DETECTION,
@@ -43,6 +48,7 @@
 #define CUOPT_AMD_HALPERN_BATCH "amd_halpern_batch"
 #define CUOPT_AMD_HALPERN_LOCKSTEP "amd_halpern_lockstep"
 #define CUOPT_AMD_HALPERN_INFEASIBILITY "amd_halpern_infeasibility"
+#define CUOPT_AMD_HALPERN_LOCKSTEP_RAYS "amd_halpern_lockstep_rays"
 #define CUOPT_AMD_PDLP_SOLVER_MODE_HALPERN1 4
 
 #ifdef __cplusplus

@@ -360,6 +360,21 @@ void pdlpdev_batch_destroy(pdlpdev_batch* batch);
 /* average dispatch durations (ms) of the four kernels of a batched attempt {primal, A / dual, A^T / step, decisions}: whole attempts in
  * the loop's order, every LP forced active, the dispatches' own timestamps; state is put back (bench.py's roofline of the batch line) */
 int pdlpdev_batch_time_kernels(pdlpdev_batch* batch, int reps, double avg_ms[4]);
+/* A batch in reflected Halpern mode: the ray pass of pdlpdev_set_halpern_rays (the displacement T(z^k) - z^k of the last step, the two
+ * plain products formed from it, the nine raw statistics, the mark) for the members with rule[l] >= 0 -- rule[l]: the reduced-cost
+ * rule, 0 / 1; -1: LP l is not in the pass -- as ONE K-wide pass: six launches and two streams of the matrix whatever K, enqueued on
+ * the batch's stream behind whatever ran, nothing read back.  A member is served only if the control block pdlpdev_batch_run read
+ * back last says error == 0 and at least one step and nothing has moved the member since; pdlpdev_major_eval of a served context at
+ * that step count with that rule then leaves its own pass out, its read-back brings the figures, and
+ * pdlpdev_halpern_eval_infeasibility finds them fresh: bit for bit the single pass's.  -7: the batch runs the averaging iteration.
+ * pdlpdev_batch_ray_stats: {K-wide passes enqueued, member passes they served, single passes the members' contexts enqueued since they
+ * joined the batch, 0 (reserved)}. */
+int pdlpdev_batch_halpern_rays(pdlpdev_batch* batch, const int32_t* rule);
+int pdlpdev_batch_ray_stats(pdlpdev_batch* batch, int64_t out[4]);
+/* The K-wide plain product as a parity hook, the batch twin of pdlpdev_spmv: out[l] = A in[l] (transpose != 0: A^T in[l]) for the
+ * members with on[l] != 0 (on == NULL: all) through ONE product kernel, each output bit for bit pdlpdev_spmv's of the parent context;
+ * the outputs of the other members are not touched.  -7: that side of the batch is in the jagged layout. */
+int pdlpdev_batch_spmv(pdlpdev_batch* batch, int transpose, const double* const* in, double* const* out, const int32_t* on);
 /* ---- K SMALL LPs in K workgroups (round 6; BASELINE config 5 at branch-and-bound scale: the reference's batch entry,
  * cpp/src/linear_programming/utilities/cython_solve.cu:264-296, is a thread pool of independent solves, and the MIP heuristics fire
  * thousands of relaxations, cpp/src/mip/relaxed_lp/relaxed_lp.cu:53-127).  An LP on the resident small-LP path runs its whole loop in

@@ -169,9 +169,20 @@ typedef struct cuoptamd_settings {
    * whether or not T(z^k) is primal feasible.  The four *_ray_* fields of the result are filled, T(z^k) is what is returned, and
    * cuoptamd_solver_get_ray hands out the displacement itself.  Serves the multi-launch path (every layout), the resident loop
    * (halpern_resident) and the K-workgroup batch (halpern_batch); a lockstep batch (halpern_lockstep) refuses members that have it
-   * set, with -7.  0 (default): no certificate is looked for, as before (detect_infeasibility stays refused under algorithm == 1).
+   * set, with -7, unless every member also sets halpern_lockstep_rays (below).  0 (default): no certificate is looked for, as before (detect_infeasibility stays refused under algorithm == 1).
    * Ignored when algorithm == 0. */
   int32_t halpern_infeasibility;
+  /* Reflected Halpern mode in a lockstep batch (halpern_lockstep) only: non-zero lets the batch take members that have
+   * halpern_infeasibility set.  cuoptamd_batch_create then accepts such members iff EVERY member has this field set (-7, by name, for
+   * a mix of members with and without it; members with and without halpern_infeasibility may be mixed), and cuoptamd_batch_advance
+   * runs the ray pass for all members whose major iteration is due as ONE K-wide pass behind the attempts (pdlpdev_batch_halpern_rays:
+   * two K-wide plain products in place of 2K single ones); the figures reach the host with each member's own evaluation read-back,
+   * every member gets, bit for bit, what its own solver with halpern_infeasibility gives it, cuoptamd_solver_get_ray works on a member,
+   * and a member that ends PrimalInfeasible / DualInfeasible rests while the others go on.  cuoptamd_batch_solve groups such LPs by
+   * 16 / 8 / 4 ("shared_matrix_halpern") when both matrices are in the CSR stream layout; a side in the row-sum panels keeps them one
+   * after the other ("shared_matrix"): the measured routing rule of docs/design/07_measurement.md, "Halpern mode".  0 (default): the refusal above stands, as before.  Ignored when algorithm == 0, and by a
+   * single solve. */
+  int32_t halpern_lockstep_rays;
 } cuoptamd_settings;
 
 /* additional_termination_information_t (pdlp/solver_solution.hpp:63-103) + run statistics */
