@@ -303,6 +303,11 @@ _proto("pdlpdev_scaling_compute", c_int, c_void_p, c_int, c_int, c_int, c_double
 _proto("pdlpdev_scale_problem", c_int, c_void_p)
 _proto("pdlpdev_init_norms", c_int, c_void_p, c_void_p)
 _proto("pdlpdev_problem_norms", c_int, c_void_p, P(c_double), P(c_double))
+_proto("pdlpdev_weight_norms", c_int, c_void_p, c_int, c_void_p)
+_proto("pdlpdev_initial_solution_stats", c_int, c_void_p, c_void_p, c_void_p, c_void_p)
+_proto("pdlpdev_reset", c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p)
+if hasattr(lib, "pdlpdev_scaling_stats"):  # (an older build given through CUOPT_AMD_LIB does not count the scaling's launches)
+    _proto("pdlpdev_scaling_stats", c_int, c_void_p, c_void_p)
 _proto("pdlpdev_set_step_params", c_int, c_void_p, P(StepParams))
 _proto("pdlpdev_set_step", c_int, c_void_p, c_double, c_double)
 _proto("pdlpdev_set_k", c_int, c_void_p, c_int)
@@ -1317,6 +1322,41 @@ class Device:
         out = np.zeros(3)
         self._ck(lib.pdlpdev_init_norms(self.handle, _ptr(out)))
         return out
+
+    def weight_norms(self, unscaled=False):
+        """pdlpdev_weight_norms -> (sum c_j^2, sum combine_bounds(lo_i, hi_i)^2) of the scaled (unscaled: the caller's) problem"""
+        out = np.zeros(2)
+        self._ck(lib.pdlpdev_weight_norms(self.handle, int(bool(unscaled)), _ptr(out)))
+        return float(out[0]), float(out[1])
+
+    def problem_norms(self):
+        """pdlpdev_problem_norms -> (||c||, ||combine_bounds(lo, hi)||) of the caller's problem"""
+        c, b = c_double(), c_double()
+        self._ck(lib.pdlpdev_problem_norms(self.handle, C.byref(c), C.byref(b)))
+        return c.value, b.value
+
+    def initial_solution_stats(self, x0=None, y0=None):
+        """pdlpdev_initial_solution_stats -> [x0 . A^T y0, ||x0||^2, ||y0||^2, max|x0|, max|y0|]: of the scaled iterate in the current
+        buffers, or (both given) of the caller's vectors as they come against the scaled matrix"""
+        out = np.zeros(5)
+        x0, y0 = (None if v is None else _f64(v) for v in (x0, y0))
+        self._ck(lib.pdlpdev_initial_solution_stats(self.handle, _ptr(out), _ptr(x0), _ptr(y0)))
+        return out
+
+    def reset(self, lb=None, ub=None, lo=None, hi=None):
+        """pdlpdev_reset: iterate and loop state back to their values right after scale_problem; a bound vector given (unscaled)
+        replaces that bound, None keeps it"""
+        lb, ub, lo, hi = (None if v is None else _f64(v) for v in (lb, ub, lo, hi))
+        self._ck(lib.pdlpdev_reset(self.handle, _ptr(lb), _ptr(ub), _ptr(lo), _ptr(hi)))
+        self._ck(lib.pdlpdev_synchronize(self.handle))  # (the copies are asynchronous and the arrays are this call's own)
+
+    def scaling_stats(self):
+        """pdlpdev_scaling_stats: kernel launches of scaling_compute / scale_problem per site -> {"A" / "At": {"max" / "sum" / "scale":
+        {"blocks" / "lanes" / "long": count}}}"""
+        out = np.zeros(18, dtype=np.int64)
+        self._ck(lib.pdlpdev_scaling_stats(self.handle, out.ctypes.data_as(C.c_void_p)))
+        return {side: {what: dict(zip(("blocks", "lanes", "long"), (int(v) for v in out[9 * t + 3 * w:9 * t + 3 * w + 3])))
+                       for w, what in enumerate(("max", "sum", "scale"))} for t, side in enumerate(("A", "At"))}
 
     def layout(self):
         out = np.zeros(8, np.int32)

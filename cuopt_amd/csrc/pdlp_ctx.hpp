@@ -538,6 +538,8 @@ struct pdlpdev_ctx {
   // pdlpdev_loop_stats: evaluations of the current iterate that reused A^T y / ran the product, synchronisations inside
   // pdlpdev_run and pdlpdev_run_period (pdlpdev_major_eval's own included), attempts enqueued that found the target reached
   int64_t stat_eval_reused = 0, stat_eval_product = 0, stat_loop_syncs = 0, stat_empty_attempts = 0;
+  // pdlpdev_scaling_stats: launches per site of the scaling, [side][norms of a max pass x 3 shapes, of a sum pass x 3, value scaling x 3]
+  int64_t stat_scaling[2][9] = {};
   // graphs
   int use_graph = 1;
   int batch_lanes = 0;  // jagged layouts built for lockstep batches of up to this many LPs (cuoptamd_settings::batch_lanes)

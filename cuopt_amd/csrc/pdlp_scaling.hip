@@ -179,9 +179,10 @@ static void row_norms(pdlpdev_ctx* ctx, const pdlpdev_ctx::MatrixSide& M, double
 {
   const pdlpdev_ctx::Csr& F = M.full;
   hipStream_t s = ctx->stream;
-  if (stream_blocks_usable(M)) k_row_norm_blocks<TRANSPOSED, POW><<<M.nb, kBlock, 0, s>>>(M.nb, M.rb, F.off, F.idx, F.val, ctx->dr, ctx->dc, e, out);
-  else k_row_norm<TRANSPOSED, POW><<<grid_for(M.rows), kBlock, 0, s>>>(M.rows, F.off, F.idx, F.val, ctx->dr, ctx->dc, e, out);
-  if (M.nlong) k_row_norm_long<TRANSPOSED, POW><<<M.nlong, kBlock, 0, s>>>(M.longs, F.off, F.idx, F.val, ctx->dr, ctx->dc, e, out);
+  int64_t* count = ctx->stat_scaling[TRANSPOSED ? 1 : 0] + (POW ? 3 : 0);  // pdlpdev_scaling_stats
+  if (stream_blocks_usable(M)) ++count[0], k_row_norm_blocks<TRANSPOSED, POW><<<M.nb, kBlock, 0, s>>>(M.nb, M.rb, F.off, F.idx, F.val, ctx->dr, ctx->dc, e, out);
+  else ++count[1], k_row_norm<TRANSPOSED, POW><<<grid_for(M.rows), kBlock, 0, s>>>(M.rows, F.off, F.idx, F.val, ctx->dr, ctx->dc, e, out);
+  if (M.nlong) ++count[2], k_row_norm_long<TRANSPOSED, POW><<<M.nlong, kBlock, 0, s>>>(M.longs, F.off, F.idx, F.val, ctx->dr, ctx->dc, e, out);
 }
 
 extern "C" {
@@ -228,9 +229,10 @@ int pdlpdev_scale_problem(pdlpdev_ctx* ctx)
   int t = 0;
   for (const pdlpdev_ctx::MatrixSide* M : {&ctx->A, &ctx->At}) {  // (val * d_self[row]) * d_other[column], each side by its own rows
     const pdlpdev_ctx::Csr& F = M->full;
-    if (stream_blocks_usable(*M)) k_scale_matrix_blocks<<<M->nb, kBlock, 0, s>>>(M->nb, M->rb, F.off, F.idx, F.val, d[t], d[1 - t]);
-    else k_scale_matrix<<<grid_for(M->rows), kBlock, 0, s>>>(M->rows, F.off, F.idx, F.val, d[t], d[1 - t]);
-    if (M->nlong) k_scale_matrix_long<<<M->nlong, kBlock, 0, s>>>(M->longs, F.off, F.idx, F.val, d[t], d[1 - t]);
+    int64_t* count = ctx->stat_scaling[t] + 6;  // pdlpdev_scaling_stats
+    if (stream_blocks_usable(*M)) ++count[0], k_scale_matrix_blocks<<<M->nb, kBlock, 0, s>>>(M->nb, M->rb, F.off, F.idx, F.val, d[t], d[1 - t]);
+    else ++count[1], k_scale_matrix<<<grid_for(M->rows), kBlock, 0, s>>>(M->rows, F.off, F.idx, F.val, d[t], d[1 - t]);
+    if (M->nlong) ++count[2], k_scale_matrix_long<<<M->nlong, kBlock, 0, s>>>(M->longs, F.off, F.idx, F.val, d[t], d[1 - t]);
     ++t;
   }
   k_scale_vectors<<<grid_for(std::max(ctx->m, ctx->n)), kBlock, 0, s>>>(ctx->n, ctx->m, ctx->c, ctx->lb, ctx->ub, ctx->dc, ctx->lo, ctx->hi, ctx->dr);
@@ -238,6 +240,13 @@ int pdlpdev_scale_problem(pdlpdev_ctx* ctx)
   ctx->scaled = true;
   TRY(sync_panel_values(ctx));
   HIP_TRY(hipStreamSynchronize(s));
+  return 0;
+}
+
+int pdlpdev_scaling_stats(pdlpdev_ctx* ctx, int64_t out[18])
+{
+  for (int t = 0; t < 2; ++t)
+    for (int k = 0; k < 9; ++k) out[9 * t + k] = ctx->stat_scaling[t][k];
   return 0;
 }
 

@@ -519,6 +519,10 @@ int pdlpdev_run_period(pdlpdev_ctx* ctx, int32_t target_steps, const pdlpdev_sma
  * product, host synchronisations inside pdlpdev_run / pdlpdev_run_period / pdlpdev_major_eval, attempts enqueued that found their
  * target reached (empty launches)}.  Single-GPU, non-resident contexts. */
 int pdlpdev_loop_stats(pdlpdev_ctx* ctx, int64_t out[4]);
+/* Read-only counters since create: kernel launches of pdlpdev_scaling_compute and pdlpdev_scale_problem per launch site.  out[9 * side +
+ * k], side 0 = A, 1 = A^T; k = 0..2: the norm kernels of a max (Ruiz) pass in the shapes {row blocks, a lane per row, long rows}, 3..5:
+ * the same of a sum (Pock-Chambolle) pass, 6..8: the value-scaling kernels {row blocks, a lane per row, long rows}. */
+int pdlpdev_scaling_stats(pdlpdev_ctx* ctx, int64_t out[18]);
 /* Infeasibility information of the iterate evaluated by the LAST pdlpdev_eval(which) call (its A x and
  * A^T y are reused; the iterate itself is the ray estimate, infeasibility_information.cu:176-223):
  * out = {max_primal_ray_infeasibility, primal_ray_linear_objective, max_dual_ray_infeasibility,
