@@ -617,11 +617,11 @@ static int batch_graph(pdlpdev_batch* b, int attempts, hipGraphExec_t* out)
 
 extern "C" {
 
-// A context for ANOTHER LP over the same matrix and objective: matrices, layouts, scaling vectors and c are the parent's (which must
-// outlive the clone; resets of either side are fine: row bounds are shared until a reset changes them); the iterate, variable bounds, sums,
-// control block and partial buffers are the
-// clone's own.  The clone starts with the parent's (scaled) bounds: pdlpdev_reset(clone, lb, ub, lo, hi) gives it its own, bit for
-// bit the state of a freshly created context of that LP (tests/test_persistent_resolve_gpu.py pins reset against a fresh solver).
+// A context for ANOTHER LP over the same matrix and objective.  The clone takes the parent's CtxProblem whole -- matrices, layouts, scaling
+// vectors, c and the stream are the parent's arrays, which must outlive it -- and starts every other field from its initialiser: what it takes
+// from the parent beyond that is carried over below, line by line.  Bounds: own copies of the variable bounds, the parent's row bounds until a
+// reset brings others (resets of either side are fine).  pdlpdev_reset(clone, lb, ub, lo, hi) gives it its own bounds and start, bit for bit the
+// state of a freshly created context of that LP (tests/test_persistent_resolve_gpu.py pins reset against a fresh solver).
 int pdlpdev_clone_shared(pdlpdev_ctx** out, pdlpdev_ctx* parent)
 {
   if (!out || !parent) return fail(-1, "pdlpdev_clone_shared: null argument");
@@ -629,68 +629,34 @@ int pdlpdev_clone_shared(pdlpdev_ctx** out, pdlpdev_ctx* parent)
   if (parent->comm || parent->small_resident || parent->dense.on) return fail(-7, "pdlpdev_clone_shared: not for sharded, resident or dense-segment contexts");
   HIP_TRY(hipSetDevice(parent->device));
   HIP_TRY(hipStreamSynchronize(parent->stream));
-  pdlpdev_ctx* c = new pdlpdev_ctx(*parent);  // (pointers to the shared arrays, geometry, parameters: by value)
+  pdlpdev_ctx* c = new pdlpdev_ctx();
   *out           = c;
-  c->allocs.clear(), c->graphs.clear(), c->scratch.clear();
-  c->shared_with_parent = true;
-  c->parent = nullptr;  // (set once the clone is complete: a failed clone is destroyed without touching the parent's count)
-  c->scal_h = nullptr, c->ctl_h = nullptr;  // (the parent's pinned block until the clone has its own: a clone that fails below must not free it)
-  // (likewise the parent's Halpern block and anchor: the mode is the clone's to switch on -- pdlpdev_set_halpern gives it its own)
-  c->halpern = false, c->lraty = nullptr, c->hal = nullptr, c->hal_h = nullptr;
-  c->xmask = nullptr, c->zcount = nullptr, c->zs_mode = 0;  // (the parent's bitmap of ITS xbar: a clone run on its own gathers every entry)
-  c->clones_alive = 0, c->batches_alive = 0, c->rows_private = false;
-  c->bytes = 0, c->slab = nullptr, c->slab_cap = c->slab_used = 0, c->arena = nullptr, c->arena_used = 0, c->first_chunk = nullptr;
-  c->bestx = c->besty = c->bestrc = nullptr;
-  c->prof_armed = false, c->prof_used = 0, c->rejected_in_a_row = 0;
-  for (hipEvent_t& e : c->prof_ev) e = nullptr;
+  static_cast<CtxProblem&>(*c) = *parent;  // (pointers to the shared arrays, geometry, switches: by value)
+  c->shared_with_parent = true;  // (c->parent is set once the row bounds are aliased: a clone that fails before is destroyed without touching the parent's count)
+  c->ubd       = parent->ubd;        // the bounds below are the parent's: so is what is known about their uniformity
+  c->sp        = parent->sp;         // the step rule's exponents and smoothing (pdlpdev_set_step_params)
+  c->use_graph = parent->use_graph;  // pdlpdev_set_graph_mode
   HIP_TRY(hipHostMalloc((void**)&c->scal_h, kScalars * sizeof(double) + sizeof(pdlpdev_ctl)));
   c->ctl_h = (pdlpdev_ctl*)(c->scal_h + kScalars);
   HIP_TRY(hipMalloc((void**)&c->arena, kArenaChunk));
   HIP_TRY(hipMemsetAsync(c->arena, 0, kArenaChunk, c->stream));
   c->first_chunk = c->arena;
-  const int m = c->m, n = c->n;
-  {
-    const size_t bytes = (24 * ((size_t)n + kSlicePad + 32) + 15 * ((size_t)m + 32)) * sizeof(double);
-    if ((int64_t)m + n >= 262144 && hipMalloc((void**)&c->slab, bytes) == hipSuccess) {
-      c->allocs.push_back(c->slab);
-      c->slab_cap = bytes;
-      HIP_TRY(hipMemsetAsync(c->slab, 0, bytes, c->stream));
-    } else {
-      c->slab = nullptr;
-      (void)hipGetLastError();
-    }
-  }
-  auto own_copy = [&](double** p, size_t count) -> int {  // an own buffer holding what the parent's holds
-    const double* src = *p;
+  TRY(lp_alloc_slab(c));
+  auto own_copy = [&](double** p, const double* src, size_t count) -> int {  // an own buffer holding what the parent's holds
     TRY(dev_alloc(c, p, count));
     HIP_TRY(hipMemcpyAsync(*p, src, count * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
     return 0;
   };
-  TRY(own_copy(&c->lb, n)); TRY(own_copy(&c->lb_u, n)); TRY(own_copy(&c->ub, n)); TRY(own_copy(&c->ub_u, n));
-  // (lo, hi and their unscaled twins stay the parent's until a reset brings other row bounds: pdlpdev_reset makes the copies then)
-  c->rows_aliased = true, c->parent = parent, c->clones_alive = 0;
+  const size_t n = (size_t)c->n;
+  TRY(own_copy(&c->lb, parent->lb, n)); TRY(own_copy(&c->lb_u, parent->lb_u, n)); TRY(own_copy(&c->ub, parent->ub, n)); TRY(own_copy(&c->ub_u, parent->ub_u, n));
+  // lo, hi and their unscaled twins are the parent's until a reset brings other row bounds: pdlpdev_reset makes the copies then
+  c->lo = parent->lo, c->hi = parent->hi, c->lo_u = parent->lo_u, c->hi_u = parent->hi_u;
+  c->rows_aliased = true, c->parent = parent;
   parent->clones_alive += 1;
   parent->rows_private = false;  // (this clone aliases the parent's CURRENT row bounds)
-  for (int i = 0; i < 2; ++i) {
-    TRY(dev_alloc(c, &c->x[i], (size_t)n + kSlicePad)); TRY(dev_alloc(c, &c->y[i], m));
-    TRY(dev_alloc(c, &c->aty[i], (size_t)n + kSlicePad)); TRY(dev_alloc(c, &c->rc[i], n));
-  }
-  TRY(dev_alloc(c, &c->xbar, (size_t)n + kSlicePad)); TRY(dev_alloc(c, &c->sumx, (size_t)n + kSlicePad)); TRY(dev_alloc(c, &c->sumy, m));
-  TRY(dev_alloc(c, &c->avgx, n)); TRY(dev_alloc(c, &c->avgy, m));
-  TRY(dev_alloc(c, &c->lrx, n)); TRY(dev_alloc(c, &c->lry, m));
-  TRY(dev_alloc(c, &c->tmp_n, n)); TRY(dev_alloc(c, &c->tmp_m, m));
-  for (int i = 0; i < 3; ++i) {
-    TRY(dev_alloc(c, &c->ax_u[i], m));
-    TRY(dev_alloc(c, &c->aty_u[i], n));
-  }
-  TRY(dev_alloc(c, &c->rc_scratch, n));
-  TRY(dev_alloc(c, &c->A.part, (size_t)8 * c->A.max_partials()));
-  TRY(dev_alloc(c, &c->At.part, (size_t)8 * c->At.max_partials()));
-  TRY(dev_alloc(c, &c->part_g, (size_t)8 * 2048));
-  TRY(dev_alloc(c, &c->scal, kScalars));
-  TRY(dev_alloc(c, &c->ctl, 1));
-  TRY(dev_alloc(c, &c->ar_buf, (size_t)n + kSlicePad));
-  HIP_TRY(hipMemcpyAsync(c->ctl, parent->ctl, sizeof(pdlpdev_ctl), hipMemcpyDeviceToDevice, c->stream));
+  TRY(lp_alloc_iterate(c));
+  TRY(lp_alloc_partials(c));
+  HIP_TRY(hipMemcpyAsync(c->ctl, parent->ctl, sizeof(pdlpdev_ctl), hipMemcpyDeviceToDevice, c->stream));  // step size, primal weight, counters: the parent's
   HIP_TRY(hipStreamSynchronize(c->stream));
   return 0;
 }

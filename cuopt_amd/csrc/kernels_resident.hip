@@ -489,6 +489,14 @@ struct pdlpdev_small_batch {
   // pass of a run in either mode; for a Halpern batch also restart rounds and resets, and one synchronisation per restart round, reset
   // and separate pdlpdev_small_batch_major_eval
   int64_t stat_loop_launches = 0, stat_eval_launches = 0, stat_periods = 0, stat_restart_rounds = 0, stat_resets = 0, stat_syncs = 0;
+  pdlpdev_small_batch() = default;
+  pdlpdev_small_batch(const pdlpdev_small_batch&) = delete;
+  pdlpdev_small_batch& operator=(const pdlpdev_small_batch&) = delete;
+  ~pdlpdev_small_batch()  // (also on a failed creation's way out: the stream and the pinned block go with the struct)
+  {
+    if (stream) (void)hipStreamDestroy(stream);
+    if (pinned) (void)hipHostFree(pinned);
+  }
 };
 
 // the tier's instantiation of the averaging loop kernel for the LPs of `list`, enqueued
@@ -663,8 +671,7 @@ void pdlpdev_small_batch_destroy(pdlpdev_small_batch* b)
   if (!b) return;
   for (pdlpdev_ctx* c : b->ctx) c->batches_alive -= 1;
   (void)hipSetDevice(b->device);
-  if (b->stream) (void)hipStreamSynchronize(b->stream), (void)hipStreamDestroy(b->stream);
-  if (b->pinned) (void)hipHostFree(b->pinned);
+  if (b->stream) (void)hipStreamSynchronize(b->stream);
   delete b;
 }
 

@@ -424,18 +424,7 @@ static int create_impl(pdlpdev_ctx** out, int device, int32_t m, int32_t n, cons
   lap("row blocks A");
   ctx->A.nb = (int)rba.size() / 2 - 1;
   TRY(upload_i32(ctx, &ctx->A.rb, rba.data(), rba.size()));
-  if ((int64_t)m + n >= 262144) {
-    // the vectors below (24 of n (+ pad), 15 of m entries) out of one zero-filled allocation
-    const size_t bytes = (24 * ((size_t)n + kSlicePad + 32) + 15 * ((size_t)m + 32)) * sizeof(double);
-    if (hipMalloc((void**)&ctx->slab, bytes) == hipSuccess) {
-      ctx->allocs.push_back(ctx->slab);
-      ctx->slab_cap = bytes, ctx->slab_used = 0;
-      HIP_TRY(hipMemsetAsync(ctx->slab, 0, bytes, ctx->stream));
-    } else {
-      ctx->slab = nullptr;
-      (void)hipGetLastError();
-    }
-  }
+  TRY(lp_alloc_slab(ctx));  // (a large LP: the vectors below out of one zero-filled allocation)
   // every problem vector crosses PCIe once: the unscaled copy is made on the device, and a bound vector that is one value
   // throughout (all lower bounds 0, all upper bounds +inf: most LPs) is not uploaded at all
   lap("slab");
@@ -462,21 +451,7 @@ static int create_impl(pdlpdev_ctx** out, int device, int32_t m, int32_t n, cons
   TRY(upload_pair(&ctx->hi, &ctx->hi_u, hi, (size_t)m, false, 0.0));
   lap("vector uploads");
   TRY(dev_alloc(ctx, &ctx->dr, m)); TRY(dev_alloc(ctx, &ctx->dc, n));
-  // x, A^T y, xbar, sum_x carry kSlicePad spare entries: the sliced-primal dataflow of a sharded solve all-gathers them in
-  // equal slices of a multiple of 16 entries per rank (slice * world may exceed n by up to 16 * 16 - 1)
-  for (int i = 0; i < 2; ++i) {
-    TRY(dev_alloc(ctx, &ctx->x[i], (size_t)n + kSlicePad)); TRY(dev_alloc(ctx, &ctx->y[i], m));
-    TRY(dev_alloc(ctx, &ctx->aty[i], (size_t)n + kSlicePad)); TRY(dev_alloc(ctx, &ctx->rc[i], n));
-  }
-  TRY(dev_alloc(ctx, &ctx->xbar, (size_t)n + kSlicePad)); TRY(dev_alloc(ctx, &ctx->sumx, (size_t)n + kSlicePad)); TRY(dev_alloc(ctx, &ctx->sumy, m));
-  TRY(dev_alloc(ctx, &ctx->avgx, n)); TRY(dev_alloc(ctx, &ctx->avgy, m));
-  TRY(dev_alloc(ctx, &ctx->lrx, n)); TRY(dev_alloc(ctx, &ctx->lry, m));
-  TRY(dev_alloc(ctx, &ctx->tmp_n, n)); TRY(dev_alloc(ctx, &ctx->tmp_m, m));
-  for (int i = 0; i < 3; ++i) {
-    TRY(dev_alloc(ctx, &ctx->ax_u[i], m));
-    TRY(dev_alloc(ctx, &ctx->aty_u[i], n));
-  }
-  TRY(dev_alloc(ctx, &ctx->rc_scratch, n));
+  TRY(lp_alloc_iterate(ctx));
   const size_t slab_rest = ctx->slab_cap - ctx->slab_used;  // (kept for the n-sized buffers allocated after the layouts)
   ctx->slab_cap = ctx->slab_used;
   LayoutPolicy P;
@@ -581,12 +556,8 @@ static int create_impl(pdlpdev_ctx** out, int device, int32_t m, int32_t n, cons
     // kernels add the segments themselves (own-row workgroups / the column epilogue): no launch in front
     s->pan.v.dense_add = s->jag.v.dense_add = s->pb.v.dense_add = s->dense_add;
     if (s->pan.v.dn_own_seg || s->pan.v.dn_pan_ptr) s->pan.v.dense_add = nullptr;
-    TRY(dev_alloc(ctx, &s->part, (size_t)8 * s->max_partials()));
   }
-  TRY(dev_alloc(ctx, &ctx->part_g, (size_t)8 * 2048));
-  TRY(dev_alloc(ctx, &ctx->scal, kScalars));
-  TRY(dev_alloc(ctx, &ctx->ctl, 1));
-  TRY(dev_alloc(ctx, &ctx->ar_buf, (size_t)n + kSlicePad));
+  TRY(lp_alloc_partials(ctx));
   lap("partial buffers");
   k_fill<<<grid_for(m), kBlock, 0, ctx->stream>>>(m, ctx->dr, 1.0);
   k_fill<<<grid_for(n), kBlock, 0, ctx->stream>>>(n, ctx->dc, 1.0);

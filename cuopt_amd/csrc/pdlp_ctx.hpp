@@ -290,7 +290,15 @@ static __global__ void __launch_bounds__(256) k_pull_ranges(pdlpdev_ctl* __restr
 // context
 // ================================================================================================
 constexpr size_t kSlicePad = 512;  // spare entries of the vectors that are exchanged in equal slices (sliced-primal dataflow)
-struct pdlpdev_ctx {
+struct pdlpdev_ctx;
+// The context is three plain structs side by side (pdlpdev_ctx below inherits all of them: ctx->x reaches every field).
+//
+// CtxProblem: the problem as the device holds it, immutable once pdlpdev_scale_problem has run -- device, stream, dimensions, both
+// matrices with their layouts, the objective, the scaling vectors, the tuning switches, the sharded dataflow.  Written by the set-up
+// (pdlp_create.hip, pdlpdev_scale_problem, pdlpdev_owner_setup) only; pdlpdev_clone_shared copies this part, and nothing else, into a
+// clone, which then ALIASES every array in it.  One exception: MatrixSide::part is per LP (each side's epilogue partials); it lives in
+// the side because every launch site reads it from there, and lp_alloc_partials re-points it at the clone's own buffer.
+struct CtxProblem {
   int device = 0;
   hipStream_t stream = nullptr;
   int32_t m = 0, n = 0;
@@ -394,75 +402,17 @@ struct pdlpdev_ctx {
     double* val = nullptr;                   // nent: the segments' values, row after row
     int32_t* tile_slot = nullptr;               // per 256-column tile: its index in tile_ptr, -1 where no segment overlaps it
   } dense;
-  // problem vectors: scaled working copies and the unscaled originals
-  double *c = nullptr, *lb = nullptr, *ub = nullptr, *lo = nullptr, *hi = nullptr;
-  // all lower (upper) bounds are the same 0 or infinity: k_primal takes the constant instead of streaming the array
-  struct UniformBounds {
-    int lb_same = 0, ub_same = 0;
-    double lb = 0.0, ub = 0.0;
-  } ubd;
-  void note_uniform_bounds(const double* lb_host, const double* ub_host)  // (null: that side is unchanged)
-  {
-    auto same = [&](const double* v, int* flag, double* value) {
-      if (!v) return;
-      *flag = 0;
-      if (n <= 0) return;
-      const double v0 = v[0];
-      if (!(v0 == 0.0 || std::isinf(v0))) return;
-      // (16 MB of bounds at n = 1e6: the scan runs on the host pool's threads)
-      constexpr int kParts = 16;
-      bool differs[kParts] = {false};
-      cuopt_amd::parallel_tasks(kParts, [&](int t) {
-        const int32_t a = (int32_t)((int64_t)n * t / kParts), b = (int32_t)((int64_t)n * (t + 1) / kParts);
-        for (int32_t j = a; j < b; ++j)
-          if (v[j] != v0) {
-            differs[t] = true;
-            return;
-          }
-      }, (int64_t)n * 4);
-      for (bool d : differs)
-        if (d) return;
-      *flag = 1, *value = v0;
-    };
-    same(lb_host, &ubd.lb_same, &ubd.lb);
-    same(ub_host, &ubd.ub_same, &ubd.ub);
-  }
-  double *c_u = nullptr, *lb_u = nullptr, *ub_u = nullptr, *lo_u = nullptr, *hi_u = nullptr;
+  double *c = nullptr, *c_u = nullptr;  // the objective: scaled working copy and the unscaled original
   double *dr = nullptr, *dc = nullptr;
   bool scaled = false;
-  // iterate state
-  double *x[2] = {nullptr, nullptr}, *y[2] = {nullptr, nullptr}, *aty[2] = {nullptr, nullptr};
-  double *xbar = nullptr, *sumx = nullptr, *sumy = nullptr, *avgx = nullptr, *avgy = nullptr;
-  // Zero skip: one bit per column, set where xbar is not 0.0 (k_primal's ballots; ceil(n / 128) 16-byte quads, the unit the panels of A
-  // fetch).  CUOPT_AMD_TUNE=zero_skip=0, or an A that is not in the row-sum panels: not allocated, every entry of xbar is gathered as before; 1 (default), 2: in use wherever
-  // attempt_xmask (pdlp_device.hip) says it applies.  pdlpdev_clone_shared nulls it in the clone.  One more
-  // word behind the quads counts the launches of the A product that took the masked path (PDLPDEV_BUF_ZS_LAUNCHES: tests).
-  unsigned long long* xmask = nullptr;
-  int* zcount = nullptr;  // k_primal's per-workgroup counts of the set bits (grid_for(n) of them): the density guard's input
-  int zs_mode = 0;        // 1: the product skips when the control block's flag is up (pdlpdev_ctl::zskip); 2: always
-  double *lrx = nullptr, *lry = nullptr, *rc[2] = {nullptr, nullptr};
-  double *tmp_n = nullptr, *tmp_m = nullptr;
-  double *ax_u[3] = {nullptr, nullptr, nullptr}, *aty_u[3] = {nullptr, nullptr, nullptr};  // unscaled A x / A^T y of pdlpdev_eval(which)
-  double* rc_scratch = nullptr;  // reduced costs of eval(LAST_RESTART): never returned
-  double *bestx = nullptr, *besty = nullptr, *bestrc = nullptr;  // save_best_primal_so_far snapshot (scaled x, y)
-  // reductions (each side's own partials: MatrixSide::part)
-  double *part_g = nullptr;                      // generic grid-stride partials
-  double *scal = nullptr;                        // device scalars (outputs of finalize kernels)
-  double *scal_h = nullptr;                      // pinned mirror
-  pdlpdev_ctl *ctl = nullptr, *ctl_h = nullptr;  // device control block + pinned mirror
-  pdlpdev_step_params sp = {0.3, 0.6, 0.5, 0.5};
-  // restarted reflected-Halpern mode (pdlpdev_set_halpern): z^k lives in the iterate buffers, T(z^k) of a run's last step in avgx / avgy
-  // (avgy is also the vector the A^T product gathers), the anchor in lrx / lry / lraty; the mode's scalars in a block of their own
-  bool halpern = false;
-  double* lraty = nullptr;                                  // A^T y of the anchor
-  pdlpdev_halpern *hal = nullptr, *hal_h = nullptr;         // device block + pinned mirror (read back with the control block)
-  bool halpern_rays = false;  // pdlpdev_set_halpern_rays: every evaluation of T(z^k) is followed by the ray pass on T(z^k) - z^k
-  // multi-GPU
+  int eval_reuse_aty = 1;   // CUOPT_AMD_TUNE=eval_reuse_aty
+  int batch_lanes = 0;  // jagged layouts built for lockstep batches of up to this many LPs (cuoptamd_settings::batch_lanes)
+  bool small_resident = false;  // whole attempt batches inside one workgroup (k_pdhg_small)
+  // multi-GPU (a sharded context is never cloned: the dataflow's own buffers stay with what describes it)
   rccl::comm_t comm = nullptr;  // non-null also marks "sharded mode" when the soft communicator is used
   softcomm::Comm* soft = nullptr;
   std::string comm_key;  // RCCL: this solver's entry of the communicator cache
   int rank = 0, world = 1;
-  double* ar_buf = nullptr;  // n + pad doubles: A^T y partial + packed scalars
   // "sliced primal" dataflow of a sharded solve (CUOPT_AMD_SHARD_DATAFLOW=rsag): inside the attempt loop a rank updates only
   // its slice [rank * slice, rank * slice + slice) of the primal-side vectors; reduce-scatter(A^T y' partials) -> slice of
   // A^T y', all-gather(xbar slices) -> the gathered vector of the next A xbar.  Outside the loop everything is replicated.
@@ -510,6 +460,45 @@ struct pdlpdev_ctx {
     p2pdev::Push* push_dev = nullptr;  // device: the three exchanges' descriptors (xbar, y', scalars) for the producing kernels
     p2pdev::Push push_host[p2pdev::kKinds];  // their host copies (the halo set-up narrows the ranges afterwards)
   } p2p;
+};
+
+// CtxLp: ONE LP over that problem -- its bounds, iterate, sums, averages, anchor, control block with the pinned mirror, partial buffers,
+// zero-skip bitmap and best-point snapshot on the device, and what the host knows about them without asking (validity flags, counters,
+// profiling events).  Written by everything that moves the LP (pdlpdev_reset, the loop, the evaluations).  A clone starts from the
+// member initialisers below; pdlpdev_clone_shared carries over, by name, the few values it takes from its parent, and
+// lp_alloc_iterate / lp_alloc_partials give it its buffers.
+struct CtxLp {
+  // bounds: scaled working copies and the unscaled originals
+  double *lb = nullptr, *ub = nullptr, *lo = nullptr, *hi = nullptr;  // (what is known about lb / ub: pdlpdev_ctx::ubd)
+  double *lb_u = nullptr, *ub_u = nullptr, *lo_u = nullptr, *hi_u = nullptr;
+  // iterate state
+  double *x[2] = {nullptr, nullptr}, *y[2] = {nullptr, nullptr}, *aty[2] = {nullptr, nullptr};
+  double *xbar = nullptr, *sumx = nullptr, *sumy = nullptr, *avgx = nullptr, *avgy = nullptr;
+  // Zero skip: one bit per column, set where xbar is not 0.0 (k_primal's ballots; ceil(n / 128) 16-byte quads, the unit the panels of A
+  // fetch).  CUOPT_AMD_TUNE=zero_skip=0, or an A that is not in the row-sum panels: not allocated, every entry of xbar is gathered as before; 1 (default), 2: in use wherever
+  // attempt_xmask (pdlp_device.hip) says it applies.  A clone has none (like every CtxLp field it starts from the initialiser: the parent's bitmap is of ITS xbar), and gathers every entry.  One more
+  // word behind the quads counts the launches of the A product that took the masked path (PDLPDEV_BUF_ZS_LAUNCHES: tests).
+  unsigned long long* xmask = nullptr;
+  int* zcount = nullptr;  // k_primal's per-workgroup counts of the set bits (grid_for(n) of them): the density guard's input
+  int zs_mode = 0;        // 1: the product skips when the control block's flag is up (pdlpdev_ctl::zskip); 2: always
+  double *lrx = nullptr, *lry = nullptr, *rc[2] = {nullptr, nullptr};
+  double *tmp_n = nullptr, *tmp_m = nullptr;
+  double *ax_u[3] = {nullptr, nullptr, nullptr}, *aty_u[3] = {nullptr, nullptr, nullptr};  // unscaled A x / A^T y of pdlpdev_eval(which)
+  double* rc_scratch = nullptr;  // reduced costs of eval(LAST_RESTART): never returned
+  double *bestx = nullptr, *besty = nullptr, *bestrc = nullptr;  // save_best_primal_so_far snapshot (scaled x, y)
+  // reductions (each side's own partials: MatrixSide::part)
+  double *part_g = nullptr;                      // generic grid-stride partials
+  double *scal = nullptr;                        // device scalars (outputs of finalize kernels)
+  double *scal_h = nullptr;                      // pinned mirror
+  pdlpdev_ctl *ctl = nullptr, *ctl_h = nullptr;  // device control block + pinned mirror
+  pdlpdev_step_params sp = {0.3, 0.6, 0.5, 0.5};
+  // restarted reflected-Halpern mode (pdlpdev_set_halpern): z^k lives in the iterate buffers, T(z^k) of a run's last step in avgx / avgy
+  // (avgy is also the vector the A^T product gathers), the anchor in lrx / lry / lraty; the mode's scalars in a block of their own
+  bool halpern = false;
+  double* lraty = nullptr;                                  // A^T y of the anchor
+  pdlpdev_halpern *hal = nullptr, *hal_h = nullptr;         // device block + pinned mirror (read back with the control block)
+  bool halpern_rays = false;  // pdlpdev_set_halpern_rays: every evaluation of T(z^k) is followed by the ray pass on T(z^k) - z^k
+  double* ar_buf = nullptr;  // n + pad doubles: A^T y partial + packed scalars
   // pdlpdev_time_kernel: the next launch through launch_k carries these events (kernel start / stop timestamps of the
   // dispatch itself, what rocprofv3 --kernel-trace reports)
   // (a call site may consist of several launches -- dense segments, phase P, phase R: each gets its own pair, the durations add up)
@@ -533,18 +522,21 @@ struct pdlpdev_ctx {
   bool batch_ctl_fresh = false;
   int batch_ray_steps = -1, batch_ray_rule = -1;
   int64_t stat_single_rays = 0;  // single ray passes enqueued (enqueue_halpern_ray)
-  int eval_reuse_aty = 1;   // CUOPT_AMD_TUNE=eval_reuse_aty
   int spare_attempts = 0;   // pdlpdev_run_period: empty-unless-needed attempts behind a period's, from the rejections the period before saw
   // pdlpdev_loop_stats: evaluations of the current iterate that reused A^T y / ran the product, synchronisations inside
   // pdlpdev_run and pdlpdev_run_period (pdlpdev_major_eval's own included), attempts enqueued that found the target reached
   int64_t stat_eval_reused = 0, stat_eval_product = 0, stat_loop_syncs = 0, stat_empty_attempts = 0;
   // pdlpdev_scaling_stats: launches per site of the scaling, [side][norms of a max pass x 3 shapes, of a sum pass x 3, value scaling x 3]
   int64_t stat_scaling[2][9] = {};
-  // graphs
-  int use_graph = 1;
-  int batch_lanes = 0;  // jagged layouts built for lockstep batches of up to this many LPs (cuoptamd_settings::batch_lanes)
+  int use_graph = 1;  // attempts are replayed from captured graphs (CtxOwned::graphs)
   bool comm_warm = false;          // one attempt went out eagerly over this communicator (before the first capture)
   bool graph_comm_failed = false;  // capturing the RCCL collectives into an attempt graph failed once: plain launches from then on
+};
+
+// CtxOwned: what this context has to give back -- allocations, slab, arena, graphs, the set-up's scratch -- and its links to the
+// contexts that alias its arrays (parent, clones, batches).  Written by dev_alloc, the graph cache, clone / batch creation and
+// pdlpdev_destroy; never copied from one context to another.
+struct CtxOwned {
   // one allocation for the ~40 problem / iterate vectors of a large LP (each hipMalloc + memset pair costs ~0.1 ms: 3 ms of a 25 ms
   // set-up at 1e6 x 1e6); dev_alloc draws from it while it lasts
   char* slab = nullptr;
@@ -553,7 +545,6 @@ struct pdlpdev_ctx {
   char* first_chunk = nullptr;  // recycled with the stream, not in `allocs`
   bool stream_borrowed = false; // pdlpdev_create_share_stream: the stream is another context's
   size_t arena_used = 0;
-  bool small_resident = false;  // whole attempt batches inside one workgroup (k_pdhg_small)
   bool shared_with_parent = false;  // pdlpdev_clone_shared: matrices, layouts, scaling vectors, c and the stream are another context's
   pdlpdev_ctx* parent = nullptr;    // ... that one
   bool rows_aliased = false;        // ... and so are the row bounds (lo, hi and their unscaled twins) until a reset brings other ones:
@@ -569,11 +560,47 @@ struct pdlpdev_ctx {
   // hipMalloc of a few GB right after a hipFree of the same size took 1.9 s at 1e9 nonzeros (the first one of the process: 2 ms) --
   // and go back to the runtime when the context has been created (scratch_free, pdlp_create.hip).
   struct Scratch {
-    void* p;
-    size_t bytes;
-    bool busy;
+    void* p = nullptr;
+    size_t bytes = 0;
+    bool busy = false;
   };
   std::vector<Scratch> scratch;
+};
+
+struct pdlpdev_ctx : CtxProblem, CtxLp, CtxOwned {
+  // all lower (upper) bounds are the same 0 or infinity: k_primal takes the constant instead of streaming the array.  Per LP like
+  // CtxLp's fields (a clone carries its parent's over with the bounds); declared here because the type is a kernel argument: as a
+  // member of this struct it keeps the name the kernels' symbols are mangled with.
+  struct UniformBounds {
+    int lb_same = 0, ub_same = 0;
+    double lb = 0.0, ub = 0.0;
+  } ubd;
+  void note_uniform_bounds(const double* lb_host, const double* ub_host)  // (null: that side is unchanged)
+  {
+    auto same = [&](const double* v, int* flag, double* value) {
+      if (!v) return;
+      *flag = 0;
+      if (n <= 0) return;
+      const double v0 = v[0];
+      if (!(v0 == 0.0 || std::isinf(v0))) return;
+      // (16 MB of bounds at n = 1e6: the scan runs on the host pool's threads)
+      constexpr int kParts = 16;
+      bool differs[kParts] = {false};
+      cuopt_amd::parallel_tasks(kParts, [&](int t) {
+        const int32_t a = (int32_t)((int64_t)n * t / kParts), b = (int32_t)((int64_t)n * (t + 1) / kParts);
+        for (int32_t j = a; j < b; ++j)
+          if (v[j] != v0) {
+            differs[t] = true;
+            return;
+          }
+      }, (int64_t)n * 4);
+      for (bool d : differs)
+        if (d) return;
+      *flag = 1, *value = v0;
+    };
+    same(lb_host, &ubd.lb_same, &ubd.lb);
+    same(ub_host, &ubd.ub_same, &ubd.ub);
+  }
 };
 inline int scratch_take(pdlpdev_ctx* c, void** p, size_t bytes)
 {
@@ -712,6 +739,56 @@ inline int dev_alloc(pdlpdev_ctx* c, T** p, size_t count)
     int rc_ = (expr);      \
     if (rc_ != 0) return rc_; \
   } while (0)
+
+// ---- the device vectors of ONE LP (CtxLp), for pdlpdev_create and pdlpdev_clone_shared alike.  The order of the dev_alloc calls is part of
+// the contract: buffer addresses are what the attempt kernels' speed depends on, and the zero-skip buffers come last of all (pdlp_create.hip).
+// the slab that the problem / iterate vectors of a large LP are carved from (24 of n (+ pad), 15 of m entries), zero-filled
+inline int lp_alloc_slab(pdlpdev_ctx* c)
+{
+  if ((int64_t)c->m + c->n < 262144) return 0;
+  const size_t bytes = (24 * ((size_t)c->n + kSlicePad + 32) + 15 * ((size_t)c->m + 32)) * sizeof(double);
+  if (hipMalloc((void**)&c->slab, bytes) == hipSuccess) {
+    c->allocs.push_back(c->slab);
+    c->slab_cap = bytes, c->slab_used = 0;
+    HIP_TRY(hipMemsetAsync(c->slab, 0, bytes, c->stream));
+  } else {
+    c->slab = nullptr;
+    (void)hipGetLastError();
+  }
+  return 0;
+}
+// the iterate and its companions.  x, A^T y, xbar, sum_x carry kSlicePad spare entries: the sliced-primal dataflow of a sharded solve
+// all-gathers them in equal slices of a multiple of 16 entries per rank (slice * world may exceed n by up to 16 * 16 - 1)
+inline int lp_alloc_iterate(pdlpdev_ctx* c)
+{
+  const size_t m = (size_t)c->m, n = (size_t)c->n;
+  for (int i = 0; i < 2; ++i) {
+    TRY(dev_alloc(c, &c->x[i], n + kSlicePad)); TRY(dev_alloc(c, &c->y[i], m));
+    TRY(dev_alloc(c, &c->aty[i], n + kSlicePad)); TRY(dev_alloc(c, &c->rc[i], n));
+  }
+  TRY(dev_alloc(c, &c->xbar, n + kSlicePad)); TRY(dev_alloc(c, &c->sumx, n + kSlicePad)); TRY(dev_alloc(c, &c->sumy, m));
+  TRY(dev_alloc(c, &c->avgx, n)); TRY(dev_alloc(c, &c->avgy, m));
+  TRY(dev_alloc(c, &c->lrx, n)); TRY(dev_alloc(c, &c->lry, m));
+  TRY(dev_alloc(c, &c->tmp_n, n)); TRY(dev_alloc(c, &c->tmp_m, m));
+  for (int i = 0; i < 3; ++i) {
+    TRY(dev_alloc(c, &c->ax_u[i], m));
+    TRY(dev_alloc(c, &c->aty_u[i], n));
+  }
+  TRY(dev_alloc(c, &c->rc_scratch, n));
+  return 0;
+}
+// what needs the layouts in place: each side's epilogue partials (MatrixSide::part, the one per-LP field of CtxProblem: pointed at
+// this LP's own buffer here), the generic partials, the scalars and the control block
+inline int lp_alloc_partials(pdlpdev_ctx* c)
+{
+  TRY(dev_alloc(c, &c->A.part, (size_t)8 * c->A.max_partials()));
+  TRY(dev_alloc(c, &c->At.part, (size_t)8 * c->At.max_partials()));
+  TRY(dev_alloc(c, &c->part_g, (size_t)8 * 2048));
+  TRY(dev_alloc(c, &c->scal, kScalars));
+  TRY(dev_alloc(c, &c->ctl, 1));
+  TRY(dev_alloc(c, &c->ar_buf, (size_t)c->n + kSlicePad));
+  return 0;
+}
 
 // the stream kernels remap blockIdx so that each XCD owns a contiguous range of row blocks
 // (xcd_remap); the grid is padded to a multiple of 8 so the remap is a bijection.

@@ -77,19 +77,11 @@ struct Convergence {
 
 }  // namespace
 
-struct cuoptamd_solver {
-  pdlpdev_ctx* dev = nullptr;
-  // the set-up's analysis object, minus its workspace, when its release was put off to the solver's end (cuoptamd_solver_create)
-  pdlpdev_analysis* spent_analysis = nullptr;
-  cuoptamd_hyper H{};
-  cuoptamd_settings S{};
-  int32_t m_global = 0, n = 0, row_begin = 0, row_end = 0;
-  int rank = 0, world = 1;
-  bool empty_problem = false;  // n_constraints == 0 -> NumericalError (LP/solve.cu:355-359)
-  double objective_scale = 1.0, objective_offset = 0.0;
-  double norm_b = 0.0, norm_c = 0.0;
-  double computed_step = 0.0, computed_weight = 0.0;  // compute_initial_step_size / _primal_weight, before overrides
-  // loop state
+// The host's loop state of one solve: what cuoptamd_solver_reset and cuoptamd_batch_reset put back by assigning a default-constructed
+// value (reset_host_state), and what a clone does not take from its parent.  ctl, fused_rq, fused_ev* and solve_start are written before
+// they are read in every run: ctl by the tail of start_run (or by batch_reset_impl), the fused_* triple in front of the call that raises
+// fused_eval_ready, solve_start by advance_begin when `started` is down.
+struct SolverLoop {
   int32_t total_iterations = 0;  // total_pdlp_iterations_ (keeps counting across warm starts)
   int32_t iteration_offset = 0;  // total_pdlp_iterations_ - internal_solver_iterations_
   int32_t attempt_offset   = 0;
@@ -100,23 +92,22 @@ struct cuoptamd_solver {
   double fused_ev[PDLPDEV_EV_COUNT] = {}, fused_ev_avg[PDLPDEV_EV_COUNT] = {};
   bool step_error = false, need_aty = true, last_restart_was_average = false;
   double last_candidate_kkt = 0.0, last_restart_kkt = 0.0;
-  // reflected Halpern mode (H.algorithm == 1): the fixed-point error at the previous restart check since the last restart (< 0: none),
-  // the device's Halpern scalars as the last attempts left them, and what the power iteration found
+  // reflected Halpern mode (H.algorithm == 1): the fixed-point error at the previous restart check since the last restart (< 0: none)
+  // and the device's Halpern scalars as the last attempts left them
   double halpern_r_prev = -1.0;
   pdlpdev_halpern hal{};
-  double sigma_max = 0.0;
-  int32_t power_products = 0;
   // the reference leaves gap_reduction_ratio_last_trial_ uninitialised (pdlp_restart_strategy.cu:160);
   // 1.0 is the published algorithm's start value (same choice as the oracle)
   double gap_reduction_ratio_last_trial = 1.0;
-  // save_best_primal_so_far: primal_quality_adapter_t of the stored point (convergence_information.hpp:110-124)
+  // save_best_primal_so_far: primal_quality_adapter_t of the stored point (convergence_information.hpp:110-124); its objective starts
+  // at the worst value of the solver's sense (reset_host_state, pdlp.cu:183-185)
   struct Quality {
     bool feasible = false;
     double residual = std::numeric_limits<double>::infinity();
     double objective = 0.0;
     bool operator==(const Quality& o) const { return feasible == o.feasible && residual == o.residual && objective == o.objective; }
   } best_quality;
-  bool have_best = false, maximize = false;
+  bool have_best = false;
   cuoptamd_result best_result{};
   bool have_accepted = false;  // settings.accept_tolerance: first iterate that met the looser set (snapshot = best buffers)
   cuoptamd_result accepted_result{};
@@ -124,7 +115,6 @@ struct cuoptamd_solver {
   // iterate on ANOTHER stream -- the small-LP batch -- waits for them first and clears the flag; on the context's own stream the
   // order is the stream's.
   bool snapshot_pending = false;
-  std::string log_path;
   pdlpdev_ctl ctl{};
   Convergence conv_current, conv_average;
   int returned_which = PDLPDEV_CURRENT;
@@ -132,6 +122,25 @@ struct cuoptamd_solver {
   cuoptamd_result result{};
   clock_type::time_point solve_start;
   bool started = false;
+};
+
+// What a solver knows about its PROBLEM: parameters, settings, geometry, what the set-up computed once (norms, the start values, the
+// power iteration's result, the reordering).  Written by cuoptamd_solver_create and, for the settings-dependent part, by
+// cuoptamd_solver_reset; cuoptamd_solver_clone copies exactly this part from the parent.
+struct SolverProblem {
+  cuoptamd_hyper H{};
+  cuoptamd_settings S{};
+  int32_t m_global = 0, n = 0, row_begin = 0, row_end = 0;
+  int rank = 0, world = 1;
+  bool empty_problem = false;  // n_constraints == 0 -> NumericalError (LP/solve.cu:355-359)
+  bool maximize = false;
+  double objective_scale = 1.0, objective_offset = 0.0;
+  double norm_b = 0.0, norm_c = 0.0;
+  double computed_step = 0.0, computed_weight = 0.0;  // compute_initial_step_size / _primal_weight, before overrides
+  // reflected Halpern mode: what the power iteration found
+  double sigma_max = 0.0;
+  int32_t power_products = 0;
+  std::string log_path;
   // Set-up reordering (pdlpdev_analyze): the device works on P A Q -- row i of its matrix is row row_new2old[i] of the caller's,
   // column j is column col_new2old[j].  Everything that crosses this interface (bounds, initial iterates, solutions, warm-start
   // snapshots) is in the CALLER's order; empty maps = the matrix as given.
@@ -153,6 +162,12 @@ struct cuoptamd_solver {
   {
     for (size_t i = first; i < last; ++i) user[new2old[i]] = dev[i];
   }
+};
+
+struct cuoptamd_solver : SolverProblem, SolverLoop {
+  pdlpdev_ctx* dev = nullptr;
+  // the set-up's analysis object, minus its workspace, when its release was put off to the solver's end (cuoptamd_solver_create)
+  pdlpdev_analysis* spent_analysis = nullptr;
 };
 
 namespace {
@@ -1384,20 +1399,8 @@ void cuoptamd_solver_destroy(cuoptamd_solver* s)
 // loop state as freshly constructed (cuoptamd_solver_reset, cuoptamd_batch_reset)
 static void reset_host_state(cuoptamd_solver* s)
 {
-  const cuoptamd_result blank{};
-  s->total_iterations = 0, s->iteration_offset = 0, s->attempt_offset = 0, s->major_done_at = -1;
-  s->fused_eval_ready = false;
-  s->step_error = false, s->need_aty = true, s->last_restart_was_average = false;
-  s->last_candidate_kkt = 0.0, s->last_restart_kkt = 0.0, s->gap_reduction_ratio_last_trial = 1.0;
-  s->halpern_r_prev = -1.0, s->hal = pdlpdev_halpern{};
-  s->best_quality = cuoptamd_solver::Quality{};
-  s->best_quality.objective = s->maximize ? -std::numeric_limits<double>::infinity() : std::numeric_limits<double>::infinity();
-  s->have_best = false, s->best_result = blank;
-  s->have_accepted = false, s->accepted_result = blank;
-  s->snapshot_pending = false;
-  s->conv_current = Convergence{}, s->conv_average = Convergence{};
-  s->returned_which = PDLPDEV_CURRENT, s->finished = false, s->warm_started = false, s->started = false;
-  s->result = blank;
+  static_cast<SolverLoop&>(*s) = SolverLoop{};
+  s->best_quality.objective = s->maximize ? -std::numeric_limits<double>::infinity() : std::numeric_limits<double>::infinity();  // pdlp.cu:183-185
 }
 
 int cuoptamd_solver_reset(cuoptamd_solver* s, const double* lb, const double* ub, const double* lo, const double* hi,
@@ -1609,9 +1612,9 @@ int cuoptamd_solver_clone(cuoptamd_solver* parent, const double* lb, const doubl
     return fail(rc, "pdlpdev_clone_shared: %s", pdlpdev_last_error());
   }
   const double t_dev = seconds_since(t0);
-  cuoptamd_solver* s = new cuoptamd_solver(*parent);
-  s->spent_analysis = nullptr;  // (the parent's to release)
-  s->dev             = dev;
+  cuoptamd_solver* s = new cuoptamd_solver();
+  static_cast<SolverProblem&>(*s) = *parent;  // (the loop state is the reset's below; the analysis object stays the parent's to release)
+  s->dev = dev;
   rc = cuoptamd_solver_reset(s, lb, ub, lo, hi, settings, nullptr, nullptr);
   if (timing) fprintf(stderr, "[cuopt_amd setup] clone: device context %.2f ms, reset to its bounds %.2f ms\n", 1e3 * t_dev, 1e3 * (seconds_since(t0) - t_dev));
   if (rc != 0) {

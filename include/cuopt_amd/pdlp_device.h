@@ -344,7 +344,9 @@ int pdlpdev_get_ctl(pdlpdev_ctx* ctx, pdlpdev_ctl* ctl);
  * pdlpdev_clone_shared: a context for another LP over the parent's matrices, layouts, scaling vectors and c (shared, read-only: the
  * parent must outlive its clones and must not be re-scaled while they exist; pdlpdev_reset of either side is fine -- row bounds are
  * shared until a reset changes them, the changing side then gets arrays of its own); iterates, variable bounds, sums, control block are the
- * clone's own.  It starts with the parent's bounds: pdlpdev_reset(clone, lb, ub, lo, hi) gives it its own.  Single GPU only.
+ * clone's own.  It starts with the parent's bounds, step parameters, graph mode and a copy of its control block, and with nothing else of
+ * the parent's LP: not its mode (pdlpdev_set_halpern), not what the host knew about its loop, not its counters -- pdlpdev_loop_stats and
+ * pdlpdev_scaling_stats of a clone start at 0.  pdlpdev_reset(clone, lb, ub, lo, hi) gives it its own bounds and start.  Single GPU only.
  * pdlpdev_batch_create: K = 2, 4, 8 or 16 such contexts (ctx[0] may be the parent).  The two products of an attempt then serve all K LPs
  * from ONE pass over the matrix: the K gathered vectors are interleaved, a row belongs to a group of K lanes, one 64-byte request
  * fetches a column's entry of eight LPs.  Each LP's trajectory is BIT-IDENTICAL to the one pdlpdev_run gives it (same row sums, same

@@ -118,6 +118,65 @@ def test_clone_alone_is_a_fresh_solver_and_row_bounds_travel(monkeypatch):
     batch.close(), child.close(), parent.close()
 
 
+# the smallest LP that stays off the resident one-workgroup path (m, n just above 2048), for the tests of what a clone starts from
+def assert_off_resident(parent):
+    lay = parent.device.layout()
+    assert not lay["resident"] and lay["A"]["layout"] == "panel" and lay["At"]["layout"] == "panel", lay
+
+
+CLONE_SETTINGS = {
+    "averaging": dict(tol=1e-5, iteration_limit=LIMIT, save_best_primal_so_far=1),
+    "halpern": dict(mode=4, tol=1e-4, iteration_limit=LIMIT, halpern_lockstep=1, halpern_infeasibility=1),
+}
+
+
+@pytest.mark.parametrize("setting", sorted(CLONE_SETTINGS))
+def test_a_clone_of_a_parent_that_has_run_is_a_fresh_solver(setting, monkeypatch):
+    """the parent is cloned 130 iterations into its solve (mid-way between two major iterations: its pinned control block is current,
+    it has spare attempts from rejections, non-zero counters and -- per setting -- a best-point snapshot or the Halpern block, anchor
+    and ray pass live): nothing of that reaches the clone, and the clone's creation leaves the parent's solve where it was"""
+    monkeypatch.setenv("CUOPT_AMD_SPMV_LAYOUT", "panel")
+    kw = CLONE_SETTINGS[setting]
+    p = synthetic.generate(2600, 2200, 6, seed=41)
+    (lb0, ub0), (lb1, ub1) = variants(p, 2, seed=11)
+    alone = capi.Solver(dict(p, lb=lb0, ub=ub0), **kw)
+    alone.advance(130)
+    want_parent = (alone.advance(), alone.solution())
+    alone.close()
+    fresh = capi.Solver(dict(p, lb=lb1, ub=ub1), **kw)
+    want_child = (fresh.advance(), fresh.solution())
+    fresh.close()
+    parent = capi.Solver(dict(p, lb=lb0, ub=ub0), **kw)
+    assert_off_resident(parent)
+    mid = parent.advance(130)
+    assert mid["steps_taken"] == 130 and mid["status_name"] != "Optimal", mid
+    child = parent.clone(lb=lb1, ub=ub1)
+    same(child.advance(), want_child[0], child.solution(), want_child[1], "%s: clone of a parent 130 iterations into its solve" % setting)
+    same(parent.advance(), want_parent[0], parent.solution(), want_parent[1], "%s: parent, continued behind its clone" % setting)
+    child.close(), parent.close()
+
+
+def test_a_clones_counters_do_not_come_from_its_parent(monkeypatch):
+    """pdlpdev_loop_stats right after clone(): the same for a clone of an untouched parent and for a clone of a parent 130 iterations
+    into its solve (a clone's counters start at 0; what they show is its own reset)"""
+    monkeypatch.setenv("CUOPT_AMD_SPMV_LAYOUT", "panel")
+    kw = CLONE_SETTINGS["averaging"]
+    p = synthetic.generate(2600, 2200, 6, seed=41)
+    (lb0, ub0), (lb1, ub1) = variants(p, 2, seed=11)
+    stats = []
+    for iterations in (0, 130):
+        parent = capi.Solver(dict(p, lb=lb0, ub=ub0), **kw)
+        assert_off_resident(parent)
+        before = parent.device.loop_stats()
+        if iterations:
+            parent.advance(iterations)
+            assert parent.device.loop_stats() != before  # (the premise: the advanced parent's counters have moved)
+        child = parent.clone(lb=lb1, ub=ub1)
+        stats.append(child.device.loop_stats())
+        child.close(), parent.close()
+    assert stats[0] == stats[1], stats
+
+
 def test_not_eligible_layouts_are_refused(monkeypatch):
     monkeypatch.setenv("CUOPT_AMD_SPMV_LAYOUT", "jag")
     p = synthetic.generate(20000, 20000, 10, seed=2, band=500)
