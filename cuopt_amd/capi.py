@@ -388,6 +388,9 @@ if hasattr(lib, "pdlpdev_batch_spmv"):  # (an older build given through CUOPT_AM
     _proto("pdlpdev_batch_spmv", c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p)
     _proto("pdlpdev_batch_ray_stats", c_int, c_void_p, c_void_p)
     _proto("pdlpdev_batch_halpern_rays", c_int, c_void_p, c_void_p)
+if hasattr(lib, "pdlpdev_debug_batch_attempts"):
+    _proto("pdlpdev_debug_batch_attempts", c_int, c_void_p, c_int, c_void_p, c_void_p)
+    _proto("pdlpdev_debug_batch_view", c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p)
 _proto("pdlpdev_synthetic_lp", c_int, c_int, c_int, c_int, c_int, C.c_uint64, *([c_void_p] * 8))
 
 if hasattr(lib, "pdlpdev_set_halpern"):  # (an older build given through CUOPT_AMD_LIB has no Halpern mode)
@@ -995,6 +998,36 @@ class SharedMatrixBatch:
         if rc != 0:
             raise CuOptError(rc, lib.pdlpdev_last_error().decode())
         return outs
+
+    def debug_attempts(self, count=1, on=None):
+        """pdlpdev_debug_batch_attempts: exactly `count` (1 .. 64) lockstep attempts for the members with on[l] != 0 (default: all), the
+        others rest; one read-back and NO make-up round -> the K control blocks.  CuOptError -7: a batch in reflected Halpern mode."""
+        k = len(self.solvers)
+        flags = _i32(np.ones(k, np.int32) if on is None else on)
+        if flags.shape != (k,):
+            raise ValueError("debug_attempts: one flag per member")
+        ctls = (Ctl * k)()
+        rc = lib.pdlpdev_debug_batch_attempts(c_void_p(lib.cuoptamd_batch_device(self.handle)), int(count), _ptr(flags), ctls)
+        if rc != 0:
+            raise CuOptError(rc, lib.pdlpdev_last_error().decode())
+        return list(ctls)
+
+    def view(self, side):
+        """pdlpdev_debug_batch_view of side 0 (A) or 1 (A^T): dict K / W / layout (panel, stream, jag) / rows / row0 (the W + 1 block
+        boundaries of the product's partial sums) / vK (the interleaved vector the side gathers from, as an array of shape (length, K):
+        side 0 xK over the n columns, side 1 yK over the m rows)"""
+        dev = c_void_p(lib.cuoptamd_batch_device(self.handle))
+        info = np.zeros(4, np.int32)
+        rc = lib.pdlpdev_debug_batch_view(dev, int(side), _ptr(info), None, None)
+        if rc != 0:
+            raise CuOptError(rc, lib.pdlpdev_last_error().decode())
+        k, w = int(info[0]), int(info[1])
+        s0 = self.solvers[0]
+        row0, vk = np.zeros(w + 1, np.int32), np.zeros((s0.m if side else s0.n) * k)
+        rc = lib.pdlpdev_debug_batch_view(dev, int(side), _ptr(info), _ptr(row0), _ptr(vk))
+        if rc != 0:
+            raise CuOptError(rc, lib.pdlpdev_last_error().decode())
+        return dict(K=k, W=w, layout=("panel", "stream", "jag")[int(info[2])], rows=int(info[3]), row0=row0, vK=vk.reshape(-1, k))
 
     def ray_stats(self):
         """pdlpdev_batch_ray_stats of a lockstep batch in reflected Halpern mode: dict wide_passes (K-wide ray passes enqueued) /

@@ -872,6 +872,79 @@ int pdlpdev_batch_run(pdlpdev_batch* b, const int32_t* targets, pdlpdev_ctl* ctl
   return 0;
 }
 
+// Parity hook, the batch twin of pdlpdev_debug_attempts: EXACTLY `count` (1 .. 64) lockstep attempts as one round of pdlpdev_batch_run
+// enqueues them (the same power-of-two chunks, graph replay or plain launches), one read-back, that round's rejected_in_a_row
+// bookkeeping -- and NO make-up round, so a rejected member's trial iterate is there to be looked at next to the accepted members'.
+// Members with on[l] != 0 (on == NULL: all) and no error aim at steps_taken + count; the others REST: a target a resting member still
+// holds beyond its steps_taken (a rejection in an earlier round of this hook) is taken back to steps_taken, nothing else of it is
+// touched.  ctl[l] receives LP l's control block.  -7: a batch in reflected Halpern mode.
+int pdlpdev_debug_batch_attempts(pdlpdev_batch* b, int count, const int32_t* on, pdlpdev_ctl* ctl)
+{
+  if (!b) return fail(-1, "pdlpdev_debug_batch_attempts: null argument");
+  if (b->halpern) return fail(-7, "pdlpdev_debug_batch_attempts: the averaging attempt only (not a batch in reflected Halpern mode)");
+  if (count < 1 || count > 64) return fail(-1, "pdlpdev_debug_batch_attempts: count must be 1 .. 64");
+  HIP_TRY(hipSetDevice(b->device));
+  TRY(batch_refresh_table(b));
+  const int K = b->K;
+  for (int l = 0; l < K; ++l) loop_state_touched(b->ctx[l]);
+  TRY(batch_fetch_ctl(b));
+  int before[kBatchMax];
+  bool asked[kBatchMax];
+  for (int l = 0; l < K; ++l) {
+    const pdlpdev_ctl& c = *b->ctx[l]->ctl_h;
+    before[l] = c.steps_taken;
+    asked[l]  = (!on || on[l] != 0) && c.error == 0;
+    if (asked[l]) k_set_target<<<1, 1, 0, b->stream>>>(b->ctx[l]->ctl, before[l] + count);
+    else if (c.target_steps > c.steps_taken) k_set_target<<<1, 1, 0, b->stream>>>(b->ctx[l]->ctl, c.steps_taken);
+  }
+  LAUNCH_CHECK();
+  const bool use_graph = b->ctx[0]->use_graph != 0;
+  for (int remaining = count; remaining > 0;) {
+    int chunk = 1;
+    while (chunk * 2 <= remaining && chunk < 64) chunk *= 2;
+    if (use_graph) {
+      hipGraphExec_t g;
+      TRY(batch_graph(b, chunk, &g));
+      HIP_TRY(hipGraphLaunch(g, b->stream));
+    } else {
+      for (int i = 0; i < chunk; ++i) TRY(batch_enqueue(b));
+    }
+    remaining -= chunk;
+  }
+  TRY(batch_fetch_ctl(b));
+  for (int l = 0; l < K; ++l) {
+    if (!asked[l]) continue;
+    pdlpdev_ctx* c = b->ctx[l];
+    c->rejected_in_a_row = c->ctl_h->steps_taken == before[l] ? c->rejected_in_a_row + count : 0;
+    if (c->ctl_h->error == 0 && c->rejected_in_a_row >= 64) {
+      c->rejected_in_a_row = 0;
+      k_set_error<<<1, 1, 0, b->stream>>>(c->ctl);
+      LAUNCH_CHECK();
+    }
+  }
+  TRY(batch_fetch_ctl(b));
+  for (int l = 0; l < K; ++l) b->ctx[l]->batch_ctl_fresh = true;
+  if (ctl)
+    for (int l = 0; l < K; ++l) ctl[l] = *b->ctx[l]->ctl_h;
+  return 0;
+}
+
+// Parity hook: what the products of one side (0: A, 1: A^T) work on.  info = {K, W, layout (0 panels, 1 CSR stream, 2 jagged), rows of
+// that side}; row0 (if not NULL) receives the W + 1 block boundaries whose partial sums the product reproduces; vK (if not NULL) a copy
+// of the interleaved vector that side GATHERS from: side 0 xK (n * K doubles), side 1 yK (m * K doubles).
+int pdlpdev_debug_batch_view(pdlpdev_batch* b, int side, int32_t info[4], int32_t* row0, double* vK)
+{
+  if (!b || !info || (side != 0 && side != 1)) return fail(-1, "pdlpdev_debug_batch_view: null argument, or a side other than 0 / 1");
+  HIP_TRY(hipSetDevice(b->device));
+  const pdlpdev_batch::Side& S = side ? b->t_side : b->a_side;
+  const pdlpdev_ctx* c0        = b->ctx[0];
+  info[0] = b->K, info[1] = S.W, info[2] = S.jag ? 2 : S.panel ? 0 : 1, info[3] = side ? c0->n : c0->m;
+  HIP_TRY(hipStreamSynchronize(b->stream));
+  if (row0) HIP_TRY(hipMemcpy(row0, S.jag ? S.jv.row0 : S.row0, ((size_t)S.W + 1) * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (vK) HIP_TRY(hipMemcpy(vK, side ? b->yK : b->xK, (size_t)(side ? c0->m : c0->n) * b->K * sizeof(double), hipMemcpyDeviceToHost));
+  return 0;
+}
+
 static BatchProductSide batch_product_side(const pdlpdev_batch::Side& S, const pdlpdev_ctx::MatrixSide& M)
 {
   return BatchProductSide{S.W, S.row0, S.panel, M.hot.off, M.hot.idx, M.hot.val};

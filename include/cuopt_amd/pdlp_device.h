@@ -377,6 +377,16 @@ int pdlpdev_batch_ray_stats(pdlpdev_batch* batch, int64_t out[4]);
  * members with on[l] != 0 (on == NULL: all) through ONE product kernel, each output bit for bit pdlpdev_spmv's of the parent context;
  * the outputs of the other members are not touched.  -7: that side of the batch is in the jagged layout. */
 int pdlpdev_batch_spmv(pdlpdev_batch* batch, int transpose, const double* const* in, double* const* out, const int32_t* on);
+/* Parity hooks of the averaging lockstep attempt (tests/test_batch_attempts_gpu.py).
+ * pdlpdev_debug_batch_attempts, the batch twin of pdlpdev_debug_attempts: exactly `count` (1 .. 64) lockstep attempts as one round of
+ * pdlpdev_batch_run enqueues them, one read-back, that round's bookkeeping and NO make-up round.  Members with on[l] != 0 (on == NULL:
+ * all) and no error aim at steps_taken + count; the others rest (a target still beyond a resting member's steps_taken is taken back to
+ * it, nothing else of the member is touched).  ctl[l] receives LP l's control block.  -1: count outside 1 .. 64; -7: Halpern mode.
+ * pdlpdev_debug_batch_view: info = {K, W, layout (0 panels, 1 CSR stream, 2 jagged), rows} of side 0 (A) or 1 (A^T); row0 (or NULL):
+ * the W + 1 block boundaries the product's partial sums follow; vK (or NULL): the interleaved vector the side gathers from -- side 0:
+ * xK, n * K doubles, xK[j K + l] = xbar_l[j]; side 1: yK, m * K doubles, yK[i K + l] = y'_l[i]. */
+int pdlpdev_debug_batch_attempts(pdlpdev_batch* batch, int count, const int32_t* on, pdlpdev_ctl* ctl);
+int pdlpdev_debug_batch_view(pdlpdev_batch* batch, int side, int32_t info[4], int32_t* row0, double* vK);
 /* ---- K SMALL LPs in K workgroups (round 6; BASELINE config 5 at branch-and-bound scale: the reference's batch entry,
  * cpp/src/linear_programming/utilities/cython_solve.cu:264-296, is a thread pool of independent solves, and the MIP heuristics fire
  * thousands of relaxations, cpp/src/mip/relaxed_lp/relaxed_lp.cu:53-127).  An LP on the resident small-LP path runs its whole loop in
