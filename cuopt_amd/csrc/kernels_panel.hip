@@ -445,6 +445,7 @@ int upload_panels(pdlpdev_ctx* c, pdlpdev_ctx::Panels* dst, const PanelHost& h, 
   HIP_TRY(hipStreamSynchronize(c->stream));  // the host vectors die with the caller's PanelHost
   dst->v  = PanelView{h.W, h.S, h.any_long ? 1 : 0, row0, tile_ptr, rowptr, rp_base, col, dst->val};
   dst->v.seg = h.seg ? 1 : 0, dst->v.slab_w = h.slab_w, dst->v.sorted = h.sorted ? 1 : 0;
+  dst->v.req_order = !h.seg && cuopt_amd::tune_int("panel_req_order", 1) != 0 ? 1 : 0;  // (PanelView::req_order)
   dst->nent = (int64_t)h.nnz;
   if (!h.own_row.empty()) {  // W becomes the number of workgroups / partials: the panels, then a workgroup per own row
     int32_t *own_row = nullptr, *own_ptr = nullptr;

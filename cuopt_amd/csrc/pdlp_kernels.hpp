@@ -206,6 +206,11 @@ struct PanelView {
   // place in the LDS stage its product is written to, so the row sums add what they always added in the order they always did.  The 64
   // gathers of a wave instruction are then neighbouring columns, which the texture path merges when they share a 128-byte line.
   int sorted = 0;
+  // Row-sum panels: a chunk's request (spmv_panel.hpp, PANEL_REQUEST) issues the row extents, for the ceil(rows / 512) slots the panel
+  // has, IN FRONT of the stream loads, and every case of the dispatch defines all the stream registers -- so nothing between the request
+  // and the end of the current chunk's row sums waits for it.  0 (CUOPT_AMD_TUNE=panel_req_order=0): the stream first, kPanelRowsPer
+  // extent loads behind it, as before.  Same loads of the same entries either way: the results are the same bits.
+  int req_order = 0;
   // Rows of more than kPanelOwnRow nonzeros are not in the panels: each gets a workgroup of its own BEHIND the panels in the same
   // grid (W = NP panels + the own rows; a 20 000-entry row inside a panel is one wave adding up 3 000-entry segments while seven
   // waves wait, and that panel sets the kernel time).  They are read from the CSR arrays the layout was built on.

@@ -12,7 +12,8 @@ namespace pdlp {
 // only the last round has idle lanes: they re-read the chunk's last nonzero and never store).  The value / column
 // loads and the packed 16-bit row extents of chunk i+1 are requested before the row sums of chunk i, so one of the two
 // dependent memory round trips of a chunk (matrix stream -> gather) always overlaps LDS work of the same workgroup.
-// Stages are straight-line code selected by a switch on R (exact load accounting, no wasted gathers).
+// Stages are straight-line code selected by a switch on R (exact load accounting, no wasted gathers); the request of the next chunk
+// is, by default, a chain of rounds behind its extent loads instead (panel_load_rounds, PanelView::req_order).
 struct PanelChunk {
   int s, c0, c1, t0;  // tile (slab) index, nonzero range of the chunk, start of its tile
   bool valid;
@@ -27,6 +28,36 @@ __device__ __forceinline__ void panel_load(const PanelView& P, double (&va)[kPan
     va[u] = __builtin_nontemporal_load(P.val + k);
     ja[u] = __builtin_nontemporal_load(P.col + k);
   }
+}
+// The same loads for the request that goes out behind the extent loads (PanelView::req_order), without the switch on the number of
+// rounds.  The compiler lays the cases of that switch one behind the other, and a case that computes anything -- an address, the
+// clamped index, a move out of the spare registers it loaded into -- waits for whatever a case in front of it MIGHT have loaded into
+// the registers it computes in: a wait three loads into a request and, where the cases meet, a wait for half the request in front of
+// the extent loads.  Here every lane's byte offsets (clamped to the chunk's last entry, so only the last round re-reads it) are final
+// before the first load, and round u is loaded where the chunk has a round u: a chain of uniform branches around nothing but loads
+// from the chunk's base (scalar registers) plus one offset register each.  A round the chunk does not have is SET (to an entry nothing
+// reads): carried through instead, the registers of the request and of the chunk in front of it become two sets with moves between.
+__device__ __forceinline__ void panel_load_rounds(const PanelView& P, double (&va)[kPanelPer], int (&ja)[kPanelPer], int c0, int c1, int rounds)
+{
+  unsigned ov[kPanelPer], oc[kPanelPer];
+  const int last = c1 - c0 - 1;
+#pragma unroll
+  for (int u = 0; u < kPanelPer; ++u) {
+    int i = (int)threadIdx.x + u * kPanelThreads;
+    i     = i < last ? i : last;
+    ov[u] = (unsigned)i * 8u, oc[u] = (unsigned)i * 4u;
+    asm volatile("" : "+v"(ov[u]), "+v"(oc[u]));  // (final here: nothing of an address is computed between the loads)
+  }
+  const char* vb = reinterpret_cast<const char*>(P.val + c0);
+  const char* cb = reinterpret_cast<const char*>(P.col + c0);
+#pragma unroll
+  for (int u = 0; u < kPanelPer; ++u)
+    if (u == 0 || u < rounds) {  // (a chunk has a round 0)
+      va[u] = __builtin_nontemporal_load(reinterpret_cast<const double*>(vb + ov[u]));
+      ja[u] = __builtin_nontemporal_load(reinterpret_cast<const int*>(cb + oc[u]));
+    } else {
+      va[u] = 0.0, ja[u] = 0;
+    }
 }
 // Column-sorted chunks (P.sorted, uniform): the stored word is slot << kSegColBits | (column - slab_base); the entry at position i of the
 // chunk is gathered by lane i % 512 as ever, and its product goes to prod[slot], where the (row, CSR) order would have put it.
@@ -306,12 +337,19 @@ __device__ __forceinline__ void panel_epilogue_early(const PanelView& P, Epi& ep
 }
 
 // the row sums of one staged chunk [lo, hi) of its tile: lane r % 512 adds row r's segment of prod[] to psum[r]
+// (`slots`, uniform: the slots that hold a row of the panel, ceil(nr / 512), or kPanelRowsPer where the bound is not in use)
+// A TUNING CONSTANT, not the exact bound: the first kPanelRowsLow slots are requested and walked in every panel (a panel of 300 rows
+// still issues four extent loads, three of them of row 0), the others only in a panel of more rows than those slots hold -- ONE
+// uniform branch instead of one per slot, which cost scalar-register spills in the chunk loop.  4 = what C3's ~1 960-row panels need.
+constexpr int kPanelRowsLow = 4;
+static_assert(kPanelRowsLow < kPanelRowsPer, "");
 __device__ __forceinline__ void panel_row_sums(const PanelView& P, const unsigned (&ext)[kPanelRowsPer], const double* prod, double* psum,
-                                               int nr, int lo, int hi)
+                                               int nr, int lo, int hi, int slots)
 {
   if (!P.any_long) {  // (uniform) the common case: no extra instruction in the loop
 #pragma unroll
     for (int q = 0; q < kPanelRowsPer; ++q) {
+      if (q == kPanelRowsLow && slots <= kPanelRowsLow) break;  // (one uniform branch)
       const int r = threadIdx.x + q * kPanelThreads;
       if (r < nr) {
         int a = (int)(ext[q] & 0xFFFFu), b = (int)(ext[q] >> 16);
@@ -423,26 +461,34 @@ __device__ __forceinline__ void panel_spmv_block(const PanelView& P, const doubl
   __syncthreads();
   if (P.own_ptr)  // rows that have a workgroup of their own: no segment of theirs is in the tiles, the epilogue below skips them
     for (int q = P.own_ptr[w] + (int)threadIdx.x; q < P.own_ptr[w + 1]; q += kPanelThreads) psum[P.own_row[q] - r0] = __longlong_as_double(kPanelNotMine);
+  // (the tile boundaries are the same in every lane; read through the first lane the compiler knows it too: the chunk's bookkeeping
+  // stays in scalar registers, the chunk loop and the switches on the number of rounds are scalar branches -- left as LDS values
+  // they count as different from lane to lane, and the cases of a switch are then laid one behind the other under execution masks,
+  // each waiting for the loads a case in front of it MIGHT have issued)
+  auto tile = [&](int i) -> int { return __builtin_amdgcn_readfirstlane(tile_s[i]); };
   auto advance = [&](PanelChunk c) -> PanelChunk {
-    if (c.valid && c.c1 < tile_s[c.s + 1]) {  // next chunk of the same tile
+    if (c.valid && c.c1 < tile(c.s + 1)) {  // next chunk of the same tile
       c.c0 = c.c1;
-      c.c1 = c.c0 + kPanelChunk < tile_s[c.s + 1] ? c.c0 + kPanelChunk : tile_s[c.s + 1];
+      c.c1 = c.c0 + kPanelChunk < tile(c.s + 1) ? c.c0 + kPanelChunk : tile(c.s + 1);
       return c;
     }
     int s = c.s + 1;
-    while (s < P.S && tile_s[s + 1] == tile_s[s]) ++s;  // empty tiles contribute nothing
+    while (s < P.S && tile(s + 1) == tile(s)) ++s;  // empty tiles contribute nothing
     c.valid = s < P.S;
     c.s     = s;
     if (c.valid) {
-      c.t0 = c.c0 = tile_s[s];
-      c.c1 = c.c0 + kPanelChunk < tile_s[s + 1] ? c.c0 + kPanelChunk : tile_s[s + 1];
+      c.t0 = c.c0 = tile(s);
+      c.c1 = c.c0 + kPanelChunk < tile(s + 1) ? c.c0 + kPanelChunk : tile(s + 1);
     }
     return c;
   };
   double va[kPanelPer];
   int ja[kPanelPer];
-  unsigned ext_next[kPanelRowsPer], ext[kPanelRowsPer];  // (begin | end << 16) of the lane's rows in the chunk's tile
-  // (macros, not lambdas: the register arrays must stay visible to scalar replacement)
+  // (begin | end << 16) of the lane's rows in the chunk's tile.  The extent-first request leaves the slots a panel does not have
+  // unwritten; they are neither copied to `ext` (the copy below has the request's bound) nor read by a row sum (r < nr fails there).
+  // Setting them once instead keeps three more values alive round the chunk loop: measured 0.8 % of the headline rate.
+  unsigned ext_next[kPanelRowsPer], ext[kPanelRowsPer];
+  // (macros for what touches the register arrays lane by lane: they must stay visible to scalar replacement)
 #define PANEL_ROUNDS(c) (((c).c1 - (c).c0 + kPanelThreads - 1) / kPanelThreads)
 #define PANEL_CALL_LOAD(R) panel_load<R>(P, va, ja, nxt.c0, nxt.c1)
 #define PANEL_CALL_PRODUCTS(R) panel_products<R>(vec, prod, va, ja, cur.c1 - cur.c0, P.sorted != 0, cur.s * P.slab_w)
@@ -457,43 +503,79 @@ __device__ __forceinline__ void panel_spmv_block(const PanelView& P, const doubl
       ext_next[q] = (unsigned)rp_[r_] | ((unsigned)rp_[r_ + 1] << 16);           \
     }                                                                            \
   }
+  // The same request in the other order (PanelView::req_order): the extents first -- of the first kPanelRowsLow slots always, of the
+  // others only where the panel has more rows than those hold (C3: ~1 960 rows, 4 slots of 7) -- then the stream.
+#define PANEL_EXTENT(q)                                                          \
+  {                                                                              \
+    int r_      = threadIdx.x + (q) * kPanelThreads;                             \
+    r_          = r_ < nr ? r_ : 0;                                              \
+    ext_next[q] = (unsigned)rp_[r_] | ((unsigned)rp_[r_ + 1] << 16);             \
+  }
+#define PANEL_REQUEST_EXT_FIRST(c)                                                                         \
+  if ((c).valid) {                                                                                         \
+    const uint16_t* __restrict__ rp_ = P.rowptr + base_s[(c).s];                                           \
+    _Pragma("unroll") for (int q = 0; q < kPanelRowsLow; ++q) PANEL_EXTENT(q)                              \
+    if (slots > kPanelRowsLow) {                                                                           \
+      _Pragma("unroll") for (int q = kPanelRowsLow; q < kPanelRowsPer; ++q) PANEL_EXTENT(q)                \
+    }                                                                                                      \
+    panel_load_rounds(P, va, ja, (c).c0, (c).c1, PANEL_ROUNDS(c));                                         \
+  }
+  const bool ext_first = P.req_order != 0;                                                     // (uniform)
+  const int slots      = ext_first ? (nr + kPanelThreads - 1) / kPanelThreads : kPanelRowsPer;  // (nr <= kPanelMaxRows)
   PanelChunk none{-1, 0, 0, 0, false};
   PanelChunk nxt = advance(none);
-  PANEL_REQUEST(nxt)
   PanelChunk cur = nxt;
-  if (zon && cur.valid) {  // the first slab's bits (zon is a constant false without ZS: nothing of the bitmap is compiled there)
-    uint4 st[kZsPer];
-    panel_zs_load(P, cur.s, st);
-    panel_zs_store(zq, st);
-  }
   constexpr bool kEarly = PanelEarlyOps<Epi>::on;
   [[maybe_unused]] typename PanelEarlyOps<Epi>::type pre[kPanelEpiDepth];
   [[maybe_unused]] int lo_last = 0, hi_last = 0;
-  while (cur.valid) {
-    __syncthreads();  // the previous chunk's row sums are done with prod
-    if (zon) { PANEL_DISPATCH(PANEL_ROUNDS(cur), PANEL_CALL_PRODUCTS_ZS) }
-    else { PANEL_DISPATCH(PANEL_ROUNDS(cur), PANEL_CALL_PRODUCTS) }
-#pragma unroll
-    for (int q = 0; q < kPanelRowsPer; ++q) ext[q] = ext_next[q];
-    const int lo = cur.c0 - cur.t0, hi = cur.c1 - cur.t0;
-    nxt = advance(cur);
-    if constexpr (kEarly)
-      if (!nxt.valid) {  // the final chunk leaves the loop here: what it requests instead of a chunk is live only below the loop
-        lo_last = lo, hi_last = hi;
-        break;
-      }
-    PANEL_REQUEST(nxt)  // in flight during the row sums below
-    __syncthreads();
-    if (zon && nxt.valid && nxt.s != cur.s) {  // (uniform) the next chunk opens another slab: its bits travel under the row sums
+  // The first request and the chunk loop stand ONCE PER ORDER of the request (a generic lambda, inlined twice, the order a constant in
+  // each copy).  Where two orders meet inside a loop, the compiler counts what EITHER may have in flight into whichever registers:
+  // row sums shared behind such a meeting point wait for the request in the registers the other order loads into, and the two
+  // orders' register sets are moved into each other once per chunk.  Once the order has settled, the other copy can go.
+  auto walk = [&](auto first) __attribute__((always_inline)) {
+    constexpr bool kFirst = decltype(first)::value;
+    if constexpr (kFirst) { PANEL_REQUEST_EXT_FIRST(nxt) }
+    else { PANEL_REQUEST(nxt) }
+    if (zon && cur.valid) {  // the first slab's bits (zon is a constant false without ZS: nothing of the bitmap is compiled there)
       uint4 st[kZsPer];
-      panel_zs_load(P, nxt.s, st);
-      panel_row_sums(P, ext, prod, psum, nr, lo, hi);
+      panel_zs_load(P, cur.s, st);
       panel_zs_store(zq, st);
-    } else {
-      panel_row_sums(P, ext, prod, psum, nr, lo, hi);
     }
-    cur = nxt;
-  }
+    while (cur.valid) {
+      __syncthreads();  // the previous chunk's row sums are done with prod
+      if (zon) { PANEL_DISPATCH(PANEL_ROUNDS(cur), PANEL_CALL_PRODUCTS_ZS) }
+      else { PANEL_DISPATCH(PANEL_ROUNDS(cur), PANEL_CALL_PRODUCTS) }
+#pragma unroll
+      for (int q = 0; q < kPanelRowsLow; ++q) ext[q] = ext_next[q];
+      if (!kFirst || slots > kPanelRowsLow) {  // (the slots the request wrote: all of them in the other order)
+#pragma unroll
+        for (int q = kPanelRowsLow; q < kPanelRowsPer; ++q) ext[q] = ext_next[q];
+      }
+      const int lo = cur.c0 - cur.t0, hi = cur.c1 - cur.t0;
+      nxt = advance(cur);
+      if constexpr (kEarly)
+        if (!nxt.valid) {  // the final chunk leaves the loop here: what it requests instead of a chunk is live only below the loop
+          lo_last = lo, hi_last = hi;
+          break;
+        }
+      if constexpr (kFirst) { PANEL_REQUEST_EXT_FIRST(nxt) }  // in flight during the row sums below
+      else { PANEL_REQUEST(nxt) }
+      __syncthreads();
+      if (zon && nxt.valid && nxt.s != cur.s) {  // (uniform) the next chunk opens another slab: its bits travel under the row sums
+        uint4 st[kZsPer];
+        panel_zs_load(P, nxt.s, st);
+        panel_row_sums(P, ext, prod, psum, nr, lo, hi, slots);
+        panel_zs_store(zq, st);
+      } else {
+        panel_row_sums(P, ext, prod, psum, nr, lo, hi, slots);
+      }
+      cur = nxt;
+    }
+  };
+  if (ext_first) walk(std::true_type{});
+  else walk(std::false_type{});
+#undef PANEL_REQUEST_EXT_FIRST
+#undef PANEL_EXTENT
 #undef PANEL_REQUEST
 #undef PANEL_CALL_PRODUCTS_ZS
 #undef PANEL_CALL_PRODUCTS
@@ -503,7 +585,7 @@ __device__ __forceinline__ void panel_spmv_block(const PanelView& P, const doubl
     panel_epilogue_request(epi, pre, r0, nr);  // (a panel without a chunk requests here as well)
     if (cur.valid) {  // the final chunk's row sums, the request in flight
       __syncthreads();
-      panel_row_sums(P, ext, prod, psum, nr, lo_last, hi_last);
+      panel_row_sums(P, ext, prod, psum, nr, lo_last, hi_last, slots);
     }
     __syncthreads();
     panel_epilogue_early(P, epi, partials, psum, red, w, r0, nr, &dseg, pre);

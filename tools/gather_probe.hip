@@ -15,6 +15,7 @@
 //     1e7 random indices: one 8-byte gather per nonzero inside windows of W bytes of an fp64 vector, against TWO 4-byte gathers (hi
 //     and lo planes, windows of W / 2 bytes each: the same columns in half the bytes per plane).
 //   hipcc -O3 --offload-arch=gfx950 tools/gather_probe.hip -o /tmp/gather_probe && /tmp/gather_probe planes
+// (3), `l2`, and (3d), `wide` (round 22: the streamed gather with 16-byte value and 8-byte index loads), are described at their kernels.
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstring>
@@ -132,11 +133,90 @@ __global__ void __launch_bounds__(256) k_stream_gather(const int* __restrict__ i
   if (acc == 123.456) out[0] = acc;
 }
 
+// (3d) the same with the stream fetched WIDE (round 22): the entries of two consecutive rounds of a lane are neighbours in memory (physical
+//      position v * 512 + 2 * lane + (round & 1) inside the workgroup's U * 256 entries), so a lane fetches a pair of rounds with one
+//      16-byte value load and one 8-byte index load.  `shift` = 1 starts every workgroup's piece at an odd entry: the 16-byte loads are
+//      then 8-byte aligned only and the 8-byte loads 4-byte aligned only, which is what a chunk that starts at an arbitrary entry gets.
+//      The indices are random and the values zero, so the order of the entries changes nothing but the access pattern.
+typedef double wide_val __attribute__((ext_vector_type(2), aligned(8)));
+typedef int wide_idx __attribute__((ext_vector_type(2), aligned(4)));
+template <int U>
+__global__ void __launch_bounds__(256) k_stream_gather_wide(const int* __restrict__ idx, const double* __restrict__ val, long long per_xcd, const double* __restrict__ v,
+                                                            int window_lines, int shift, double* __restrict__ out)
+{
+  static_assert(U % 2 == 0, "rounds come in pairs");
+  const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3, nb = gridDim.x >> 3;
+  const double* w = v + (size_t)xcd * window_lines * 16;
+  const int* ix = idx + (size_t)xcd * per_xcd;
+  const double* vl = val + (size_t)xcd * per_xcd;
+  double acc = 0.0;
+  for (long long kb = (long long)j * 256 * U + shift; kb + U * 256 <= per_xcd; kb += (long long)nb * 256 * U) {  // (the last entry touched: kb + U * 256 - 1)
+    wide_idx c[U / 2];
+    wide_val a[U / 2];
+    double x[U];
+#pragma unroll
+    for (int p = 0; p < U / 2; ++p) {
+      const long long k = kb + p * 512 + 2 * threadIdx.x;
+      c[p] = __builtin_nontemporal_load(reinterpret_cast<const wide_idx*>(ix + k));
+      a[p] = __builtin_nontemporal_load(reinterpret_cast<const wide_val*>(vl + k));
+    }
+#pragma unroll
+    for (int p = 0; p < U / 2; ++p) x[2 * p] = w[c[p].x], x[2 * p + 1] = w[c[p].y];
+#pragma unroll
+    for (int p = 0; p < U / 2; ++p) acc += a[p].x * x[2 * p], acc += a[p].y * x[2 * p + 1];
+  }
+  if (acc == 123.456) out[0] = acc;
+}
+
 static float time_ms(hipStream_t s, hipEvent_t e0, hipEvent_t e1) { float ms = 0; (void)hipEventSynchronize(e1); (void)hipEventElapsedTime(&ms, e0, e1); (void)s; return ms; }
 
 int main(int argc, char** argv)
 {
   const bool calibrate = argc > 1 && !std::strcmp(argv[1], "calibrate");
+  if (argc > 1 && !std::strcmp(argv[1], "wide")) {
+    // (3d) narrow against wide stream loads, the data and grids of (3c): five timed repetitions each, mean (min .. max) in us
+    hipStream_t s; OK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+    hipEvent_t e0, e1; OK(hipEventCreate(&e0)); OK(hipEventCreate(&e1));
+    double* out; OK(hipMalloc((void**)&out, 64));
+    const long long per = 1250000;
+    const int wl = 10922;  // lines of a 1.33 MiB window
+    std::vector<int> h((size_t)per * 8);
+    unsigned long long st = 88172645463325252ull;
+    for (auto& e : h) { st ^= st << 13, st ^= st >> 7, st ^= st << 17; e = (int)((st >> 20) % (unsigned long long)(wl * 16)); }
+    int* di; double *dv, *dw;
+    OK(hipMalloc((void**)&di, h.size() * 4)); OK(hipMalloc((void**)&dv, h.size() * 8)); OK(hipMalloc((void**)&dw, (size_t)wl * 128 * 8));
+    OK(hipMemcpy(di, h.data(), h.size() * 4, hipMemcpyHostToDevice)); OK(hipMemset(dv, 0, h.size() * 8)); OK(hipMemset(dw, 0, (size_t)wl * 128 * 8));
+    std::printf("gathers fed from memory (1e7 indices + values streamed, 1.33 MiB window per XCD): us per pass, mean (min .. max) of 5\n");
+    std::printf("narrow: 4-byte index + 8-byte value loads per lane and round; wide: 8-byte index + 16-byte value loads per lane and pair of rounds,\n");
+    std::printf("        aligned (every piece starts at an even entry) and shifted (at an odd entry: 16-byte loads 8-byte aligned only)\n");
+    for (int grid : {1024, 2048, 4096, 8192}) {
+      for (int U : {2, 4, 8}) {
+        std::printf("  grid %5d U=%d:", grid, U);
+        for (int variant = 0; variant < 3; ++variant) {  // narrow, wide aligned, wide shifted
+          float t = 0, lo = 1e30f, hi = 0;
+          for (int rep = -2; rep < 5; ++rep) {
+            OK(hipEventRecord(e0, s));
+            if (variant == 0) {
+              if (U == 2) k_stream_gather<2><<<grid, 256, 0, s>>>(di, dv, per, dw, wl, out);
+              else if (U == 4) k_stream_gather<4><<<grid, 256, 0, s>>>(di, dv, per, dw, wl, out);
+              else k_stream_gather<8><<<grid, 256, 0, s>>>(di, dv, per, dw, wl, out);
+            } else {
+              const int shift = variant - 1;
+              if (U == 2) k_stream_gather_wide<2><<<grid, 256, 0, s>>>(di, dv, per, dw, wl, shift, out);
+              else if (U == 4) k_stream_gather_wide<4><<<grid, 256, 0, s>>>(di, dv, per, dw, wl, shift, out);
+              else k_stream_gather_wide<8><<<grid, 256, 0, s>>>(di, dv, per, dw, wl, shift, out);
+            }
+            OK(hipEventRecord(e1, s));
+            const float a = time_ms(s, e0, e1);
+            if (rep >= 0) t += a, lo = a < lo ? a : lo, hi = a > hi ? a : hi;
+          }
+          std::printf("  %s %6.1f (%5.1f .. %5.1f)", variant == 0 ? "narrow" : variant == 1 ? "wide" : "wide shifted", t / 5 * 1e3, lo * 1e3, hi * 1e3);
+        }
+        std::printf("\n");
+      }
+    }
+    return 0;
+  }
   if (argc > 1 && !std::strcmp(argv[1], "l2")) {
     hipStream_t s; OK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
     hipEvent_t e0, e1; OK(hipEventCreate(&e0)); OK(hipEventCreate(&e1));
