@@ -149,6 +149,17 @@ assert SolverSettingsWithLockstepRays._LOCKSTEP_RAYS_OFFSET == SolverSettingsWit
 assert SolverSettingsWithLockstepRays._LOCKSTEP_RAYS_OFFSET + C.sizeof(c_int) <= C.sizeof(SolverSettingsWithLockstepRays) == C.sizeof(SolverSettingsWithRays)
 
 
+class SolverSettingsWithSharded(SolverSettingsWithLockstepRays):
+    """... and the field appended behind halpern_lockstep_rays: int32_t halpern_sharded.  halpern_lockstep_rays filled the four bytes
+    of tail padding, so a subclass's field now starts exactly where the C compiler puts the new member: a regular _fields_ entry.
+    The struct every call passes now, and what default_settings() makes; the classes above keep the ends their tests pin."""
+    _fields_ = [("halpern_sharded", c_int)]
+
+
+assert SolverSettingsWithSharded.halpern_sharded.offset == SolverSettingsWithLockstepRays._LOCKSTEP_RAYS_OFFSET + C.sizeof(c_int)
+assert SolverSettingsWithSharded.halpern_sharded.offset + C.sizeof(c_int) <= C.sizeof(SolverSettingsWithSharded)
+
+
 class Result(C.Structure):
     _fields_ = [("status", c_int), ("steps_taken", c_int), ("attempted_steps", c_int),
                 ("returned_average", c_int), ("num_restarts", c_int), ("num_major_iterations", c_int),
@@ -655,7 +666,7 @@ def hyper_preset(mode=1):
 
 
 def default_settings(**over):
-    s = SolverSettingsWithLockstepRays()
+    s = SolverSettingsWithSharded()
     lib.cuoptamd_default_settings(C.byref(s))
     tol = over.pop("tol", None)
     if tol is not None:

@@ -70,6 +70,7 @@ struct Settings {
   int32_t halpern_batch = 0;     // ... and K of them in K workgroups of one launch where a batch is solved (cuoptamd_settings::halpern_batch)
   int32_t halpern_infeasibility = 0;  // mode 4: infeasibility detection on the displacement of a step (cuoptamd_settings::halpern_infeasibility)
   int32_t halpern_lockstep_rays = 0;  // ... and lockstep batches take LPs that have it set (cuoptamd_settings::halpern_lockstep_rays)
+  int32_t halpern_sharded = 0;  // mode 4 with amd_num_gpus > 1: sharded solves on the owner-computes dataflow (cuoptamd_settings::halpern_sharded)
   int32_t dual_simplex = -1;  // the dual simplex engine: -1 = CUOPT_AMD_DUAL_SIMPLEX (default on), 0 off, 1 on
   bool infeasibility_detection = false, strict_infeasibility = false, per_constraint_residual = false,
        save_best_primal_so_far = false, first_primal_feasible = false, log_to_console = true,
@@ -114,7 +115,8 @@ struct Settings {
             {CUOPT_AMD_HALPERN_BATCH, &halpern_batch, 0, 1},
             {CUOPT_AMD_HALPERN_LOCKSTEP, &halpern_lockstep, 0, 1},
             {CUOPT_AMD_HALPERN_INFEASIBILITY, &halpern_infeasibility, 0, 1},
-            {CUOPT_AMD_HALPERN_LOCKSTEP_RAYS, &halpern_lockstep_rays, 0, 1}};
+            {CUOPT_AMD_HALPERN_LOCKSTEP_RAYS, &halpern_lockstep_rays, 0, 1},
+            {CUOPT_AMD_HALPERN_SHARDED, &halpern_sharded, 0, 1}};
     bools = {{CUOPT_INFEASIBILITY_DETECTION, &infeasibility_detection},
              {CUOPT_STRICT_INFEASIBILITY, &strict_infeasibility},
              {CUOPT_PER_CONSTRAINT_RESIDUAL, &per_constraint_residual},
@@ -797,6 +799,7 @@ cuopt_int_t cuOptSolve(cuOptOptimizationProblem problem, cuOptSolverSettings set
     st.halpern_lockstep            = s->halpern_lockstep;
     st.halpern_infeasibility       = s->halpern_infeasibility;
     st.halpern_lockstep_rays       = s->halpern_lockstep_rays;
+    st.halpern_sharded             = s->halpern_sharded;
     st.log_file                    = s->log_file.empty() ? nullptr : s->log_file.c_str();
     auto say = [&](const std::string& line) {
       if (s->log_to_console) std::fputs(line.c_str(), stdout), std::fflush(stdout);
@@ -978,14 +981,15 @@ cuopt_int_t cuOptSolve(cuOptOptimizationProblem problem, cuOptSolverSettings set
                     "{\"engine\": \"%s\", \"requested_method\": \"%s\", \"crossover_requested\": %s, \"simplex_grade_emulation\": %s, "
                     "\"dual_simplex_consulted\": %s, \"dual_simplex_status\": %d, \"crossover\": \"%s\", "
                     "\"answered_by\": \"%s\", \"gpus\": %d, \"iterations\": %d, \"simplex_grade_attempt_iterations\": %d, "
-                    "\"pdlp_algorithm\": \"%s\", \"halpern_resident\": %d, \"halpern_infeasibility\": %d, \"halpern_lockstep_rays\": %d}",
+                    "\"pdlp_algorithm\": \"%s\", \"halpern_resident\": %d, \"halpern_infeasibility\": %d, \"halpern_lockstep_rays\": %d, \"halpern_sharded\": %d}",
                     engine_answered ? "dual_simplex" : "pdlp", method_name, s->crossover ? "true" : "false", simplex_grade ? "true" : "false",
                     engine_ran ? "true" : "false", (int)sx.status, crossover_by, answered.c_str(), gpus,
                     res.steps_taken + (answered == "requested_tolerances_after_simplex_grade_budget" ? first_attempt_steps : 0),
                     answered == "requested_tolerances_after_simplex_grade_budget" ? first_attempt_steps : 0,
                     hyper.algorithm == 1 ? "reflected_halpern" : "pdhg_average", halpern_resident_ran,
                     hyper.algorithm == 1 && st.halpern_infeasibility ? 1 : 0,
-                    hyper.algorithm == 1 && st.halpern_infeasibility && st.halpern_lockstep_rays ? 1 : 0);
+                    hyper.algorithm == 1 && st.halpern_infeasibility && st.halpern_lockstep_rays ? 1 : 0,
+                    hyper.algorithm == 1 && st.halpern_sharded && gpus > 1 ? 1 : 0);
       sol->solve_info = info;
       if (other_method || s->crossover) say("cuopt_amd: " + sol->solve_info + "\n");
     }

@@ -8,25 +8,13 @@
 
 constexpr int kHalpernDecisionThreads = 1024;  // (= kDecisionThreads of pdlp_device.hip: one wide workgroup, every partial one independent load)
 
-__device__ __forceinline__ void halpern_decision_workgroup(pdlpdev_ctl* __restrict__ ctl, pdlpdev_halpern* __restrict__ hal, const double* __restrict__ part_dy,
-                                                           int nb_dy, const double* __restrict__ part_t, int nb_t)
+// The decision itself from three FINISHED sums, by one thread: lc is the thread's copy of the control block, which it stores.  One
+// body for the one-LP and the batch decisions (below) and for a sharded solve's, whose sums come out of an all-reduce
+// (k_halpern_decision_sums) or out of the peers' landing blocks (k_halpern_decision_p2p), pdlp_device.hip.
+__device__ __forceinline__ void halpern_decision_from_sums(pdlpdev_ctl* __restrict__ ctl, pdlpdev_halpern* __restrict__ hal, pdlpdev_ctl& lc, double dy2,
+                                                           double interaction, double dx2)
 {
-  __shared__ double red[3 * 16];
-  pdlpdev_ctl lc = *ctl;
-  if (!(lc.error == 0 && lc.steps_taken < lc.target_steps)) return;
-  const int t   = threadIdx.x;
-  double acc[3] = {0.0, 0.0, 0.0};
-#pragma unroll 4
-  for (int i = t; i < nb_dy; i += kHalpernDecisionThreads) acc[0] += part_dy[i];
-#pragma unroll 4
-  for (int i = t; i < nb_t; i += kHalpernDecisionThreads) {
-    acc[1] += part_t[i];
-    acc[2] += part_t[nb_t + i];
-  }
-  block_sum_fast<3, kHalpernDecisionThreads / 64>(acc, red);
-  if (t != 0) return;
   pdlpdev_halpern lh = *hal;
-  const double dy2 = acc[0], interaction = acc[1], dx2 = acc[2];
   const double eta = lc.step_size, w = lc.primal_weight;
   const double r2  = (w / eta) * dx2 + 2.0 * interaction + dy2 / (eta * w);
   lc.last_interaction = interaction;
@@ -49,4 +37,24 @@ __device__ __forceinline__ void halpern_decision_workgroup(pdlpdev_ctl* __restri
   lc.steps_taken += 1;
   lc.its_since_restart += 1;
   *ctl = lc;
+}
+
+__device__ __forceinline__ void halpern_decision_workgroup(pdlpdev_ctl* __restrict__ ctl, pdlpdev_halpern* __restrict__ hal, const double* __restrict__ part_dy,
+                                                           int nb_dy, const double* __restrict__ part_t, int nb_t)
+{
+  __shared__ double red[3 * 16];
+  pdlpdev_ctl lc = *ctl;
+  if (!(lc.error == 0 && lc.steps_taken < lc.target_steps)) return;
+  const int t   = threadIdx.x;
+  double acc[3] = {0.0, 0.0, 0.0};
+#pragma unroll 4
+  for (int i = t; i < nb_dy; i += kHalpernDecisionThreads) acc[0] += part_dy[i];
+#pragma unroll 4
+  for (int i = t; i < nb_t; i += kHalpernDecisionThreads) {
+    acc[1] += part_t[i];
+    acc[2] += part_t[nb_t + i];
+  }
+  block_sum_fast<3, kHalpernDecisionThreads / 64>(acc, red);
+  if (t != 0) return;
+  halpern_decision_from_sums(ctl, hal, lc, acc[0], acc[1], acc[2]);
 }

@@ -55,6 +55,20 @@ k_jag_at_halpern(JagView J, const pdlpdev_ctl* __restrict__ ctl, double* __restr
   jag_block<decltype(e), WAVES>(J, h.ty /* y' */, e, part);
 }
 
+// ... and the A product of a sharded Halpern step (HalpernShardedDualEpilogue: y' also into the gathered dual / the peers' blocks)
+template <int WAVES>
+__global__ void __launch_bounds__(WAVES * 64)
+k_jag_a_halpern_sharded(JagView J, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ xbar,
+                        double* __restrict__ y0, double* __restrict__ y1, const double* __restrict__ lo,
+                        const double* __restrict__ hi, HalpernArgs h, double* __restrict__ part, double* __restrict__ ycopy,
+                        const p2pdev::Push* __restrict__ push)
+{
+  if (!loop_active(ctl)) return;
+  HalpernShardedDualEpilogue e = HalpernShardedDualEpilogue::make(ctl, y0, y1, lo, hi, h, ycopy, push);
+  jag_block<decltype(e), WAVES>(J, xbar, e, part);
+  if (push) p2pdev::count_exchange(push);
+}
+
 template <int WAVES>
 __global__ void __launch_bounds__(WAVES * 64)
 k_jag_at_cur(JagView J, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ y0,
@@ -107,6 +121,7 @@ k_jag_eval_dual(JagView J, const pdlpdev_ctl* __restrict__ ctl, int which,
 }
 
 // explicit instantiations (the launch sites live in another translation unit), from the lists of pdlp_kernel_decls.hpp
+INSTANTIATE_JAG(A_HALPERN_SHARDED_KERNELS)
 INSTANTIATE_JAG(A_HALPERN_KERNELS)
 INSTANTIATE_JAG(AT_HALPERN_KERNELS)
 INSTANTIATE_JAG(A_DUAL_KERNELS)

@@ -61,6 +61,20 @@ k_panel_at_halpern(PanelView P, const pdlpdev_ctl* __restrict__ ctl, double* __r
   panel_block<SEG>(P, h.ty /* y' */, e, part);
 }
 
+// ... and the A product of a sharded Halpern step (HalpernShardedDualEpilogue: y' also into the gathered dual / the peers' blocks)
+template <bool SEG>
+__global__ void __launch_bounds__(kPanelThreads)
+k_panel_a_halpern_sharded(PanelView P, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ xbar,
+                          double* __restrict__ y0, double* __restrict__ y1, const double* __restrict__ lo,
+                          const double* __restrict__ hi, HalpernArgs h, double* __restrict__ part, double* __restrict__ ycopy,
+                          const p2pdev::Push* __restrict__ push)
+{
+  if (!loop_active(ctl)) return;
+  HalpernShardedDualEpilogue e = HalpernShardedDualEpilogue::make(ctl, y0, y1, lo, hi, h, ycopy, push);
+  panel_block<SEG>(P, xbar, e, part);
+  if (push) p2pdev::count_exchange(push);
+}
+
 // panel twin of k_spmv_at_cur (A^T y of the iterate / of the trial iterate, optionally into `out_override`)
 template <bool SEG>
 __global__ void __launch_bounds__(kPanelThreads)
@@ -163,6 +177,7 @@ k_panel_eval_dual_from_aty(PanelView P, const pdlpdev_ctl* __restrict__ ctl, con
 }
 
 // explicit instantiations (the launch sites live in another translation unit), from the lists of pdlp_kernel_decls.hpp
+INSTANTIATE_PANEL(A_HALPERN_SHARDED_KERNELS)
 INSTANTIATE_PANEL(A_HALPERN_KERNELS)
 INSTANTIATE_PANEL(AT_HALPERN_KERNELS)
 INSTANTIATE_PANEL(A_DUAL_KERNELS)

@@ -68,6 +68,21 @@ k_pb_at_halpern(PbView V, const pdlpdev_ctl* __restrict__ ctl, double* __restric
   else pb_rows_block(V, e, part, pb_lds);
 }
 
+// ... and the A product of a sharded Halpern step (HalpernShardedDualEpilogue: y' also into the gathered dual / the peers' blocks)
+template <bool WIDE>
+__global__ void __launch_bounds__(WIDE ? kPbwThreads : kPbThreads)
+k_pb_a_halpern_sharded(PbView V, const pdlpdev_ctl* __restrict__ ctl, double* __restrict__ y0, double* __restrict__ y1, const double* __restrict__ lo,
+                       const double* __restrict__ hi, HalpernArgs h, double* __restrict__ part, double* __restrict__ ycopy,
+                       const p2pdev::Push* __restrict__ push)
+{
+  extern __shared__ __attribute__((aligned(16))) double pb_lds[];
+  if (!loop_active(ctl)) return;
+  HalpernShardedDualEpilogue e = HalpernShardedDualEpilogue::make(ctl, y0, y1, lo, hi, h, ycopy, push);
+  if constexpr (WIDE) pbw_rows_block(V, e, part, pb_lds);
+  else pb_rows_block(V, e, part, pb_lds);
+  if (push) p2pdev::count_exchange(push);
+}
+
 template <bool WIDE>
 __global__ void __launch_bounds__(WIDE ? kPbwThreads : kPbThreads)
 k_pb_at_cur(PbView V, const pdlpdev_ctl* __restrict__ ctl, double* __restrict__ aty0, double* __restrict__ aty1,
@@ -120,6 +135,7 @@ k_pb_eval_dual(PbView V, const pdlpdev_ctl* __restrict__ ctl, int which, const d
 }
 
 // explicit instantiations (the launch sites live in another translation unit), from the lists of pdlp_kernel_decls.hpp
+INSTANTIATE_PB(A_HALPERN_SHARDED_KERNELS)
 INSTANTIATE_PB(A_HALPERN_KERNELS)
 INSTANTIATE_PB(AT_HALPERN_KERNELS)
 PB_PRODUCTS_KERNEL(KERNEL_PAIR_INSTANTIATE)

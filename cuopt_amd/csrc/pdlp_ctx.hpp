@@ -498,7 +498,11 @@ struct CtxLp {
   double* lraty = nullptr;                                  // A^T y of the anchor
   pdlpdev_halpern *hal = nullptr, *hal_h = nullptr;         // device block + pinned mirror (read back with the control block)
   bool halpern_rays = false;  // pdlpdev_set_halpern_rays: every evaluation of T(z^k) is followed by the ray pass on T(z^k) - z^k
-  double* ar_buf = nullptr;  // n + pad doubles: A^T y partial + packed scalars
+  // n + pad doubles: A^T y partial + packed scalars between attempts (pdlpdev_compute_aty, the evaluation, pdlpdev_spectral_norm).  A
+  // sharded context in Halpern mode (owner-computes dataflow) ALSO keeps x' of a run's last step there, on the rank's slice, from the
+  // column block's product of that step until run_epilogue has all-gathered it and copied it into avgx (which has no spare entries for
+  // equal slices): nothing else may write ar_buf between enqueue_attempts and run_epilogue of one pdlpdev_run.
+  double* ar_buf = nullptr;
   // pdlpdev_time_kernel: the next launch through launch_k carries these events (kernel start / stop timestamps of the
   // dispatch itself, what rocprofv3 --kernel-trace reports)
   // (a call site may consist of several launches -- dense segments, phase P, phase R: each gets its own pair, the durations add up)

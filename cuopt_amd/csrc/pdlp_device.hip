@@ -344,16 +344,17 @@ __global__ void __launch_bounds__(kBlock) k_div_by_scalar(int n, double* __restr
   for (int i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) out[i] = v[i] / d;
 }
 
-// direct peer transport of a sharded solve: wait for every rank's three step-size sums (landed in this rank's block), add them
-// up in rank order -- the same bits on every rank -- and take the decision
-// (one workgroup, so the whole scalar exchange lives in this kernel: its own three sums from the partials of the two SpMV kernels,
-// write-through stores into every rank's block, the flag, the wait for the others -- no ticket, no kernel boundary in between)
-__global__ void __launch_bounds__(kBlock)
-k_step_decision_p2p(pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ part_dy, int nb_dy, const double* __restrict__ part_t, int nb_t,
-                    const double* __restrict__ landed, const unsigned long long* __restrict__ flags, int world,
-                    const unsigned long long* __restrict__ epoch, int* __restrict__ fault, pdlpdev_step_params sp, const p2pdev::Push* __restrict__ push)
+// The scalar exchange of the direct peer transport, by ONE workgroup of kBlock threads (the body of k_step_decision_p2p and of
+// k_halpern_decision_p2p, so that the flag / wait protocol exists once): this rank's three sums from the partials of the two SpMV
+// kernels, write-through stores into every rank's block, the flag, the bounded wait for the others, the landed sums added in rank
+// order -- the same bits on every rank.  true: thread 0 (and only it) goes on with `sum`; false: every other thread, and every
+// thread when the wait ran out (then the fault flag and the step error are up).
+__device__ __forceinline__ bool p2p_exchange_step_sums(pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ part_dy, int nb_dy,
+                                                       const double* __restrict__ part_t, int nb_t, const double* __restrict__ landed,
+                                                       const unsigned long long* __restrict__ flags, int world,
+                                                       const unsigned long long* __restrict__ epoch, int* __restrict__ fault,
+                                                       const p2pdev::Push* __restrict__ push, double (&sum)[3])
 {
-  if (!loop_active(ctl)) return;
   {
     __shared__ double red[3 * 8];
     double acc[3] = {0.0, 0.0, 0.0};
@@ -376,15 +377,51 @@ k_step_decision_p2p(pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ pa
   }
   if (!p2pdev::wait_flags(flags, world, 2, epoch)) {
     if (threadIdx.x == 0) *fault = 1, ctl->error = 1;
-    return;
+    return false;
   }
-  if (threadIdx.x != 0) return;
-  double sum[3] = {0.0, 0.0, 0.0};
+  if (threadIdx.x != 0) return false;
+  sum[0] = sum[1] = sum[2] = 0.0;
   for (int q = 0; q < world; ++q)
     for (int k = 0; k < 3; ++k) sum[k] += __hip_atomic_load(landed + 4 * q + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  return true;
+}
+
+// direct peer transport of a sharded solve: wait for every rank's three step-size sums (landed in this rank's block), add them
+// up in rank order -- the same bits on every rank -- and take the decision
+// (one workgroup, so the whole scalar exchange lives in this kernel: its own three sums from the partials of the two SpMV kernels,
+// write-through stores into every rank's block, the flag, the wait for the others -- no ticket, no kernel boundary in between)
+__global__ void __launch_bounds__(kBlock)
+k_step_decision_p2p(pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ part_dy, int nb_dy, const double* __restrict__ part_t, int nb_t,
+                    const double* __restrict__ landed, const unsigned long long* __restrict__ flags, int world,
+                    const unsigned long long* __restrict__ epoch, int* __restrict__ fault, pdlpdev_step_params sp, const p2pdev::Push* __restrict__ push)
+{
+  if (!loop_active(ctl)) return;
+  double sum[3];
+  if (!p2p_exchange_step_sums(ctl, part_dy, nb_dy, part_t, nb_t, landed, flags, world, epoch, fault, push, sum)) return;
   pdlpdev_ctl lc = *ctl;
   apply_step_decision(&lc, sum[0], sum[1], sum[2], sp);
   *ctl = lc;
+}
+// ---- the decision of a sharded Halpern step (cuoptamd_settings::halpern_sharded; owner-computes dataflow) ----
+// collective transport: the three sums arrive all-reduced (k_pack_step_sums -> allreduce(3)): the same bits on every rank, so every
+// rank takes the same decision -- the step error of a NaN or an overflow included -- through the one body of halpern_decision.hpp
+__global__ void k_halpern_decision_sums(pdlpdev_ctl* __restrict__ ctl, pdlpdev_halpern* __restrict__ hal, const double* __restrict__ sums)
+{
+  pdlpdev_ctl lc = *ctl;
+  if (!(lc.error == 0 && lc.steps_taken < lc.target_steps)) return;
+  halpern_decision_from_sums(ctl, hal, lc, sums[0], sums[1], sums[2]);
+}
+// direct peer transport: the twin of k_step_decision_p2p -- the same scalar exchange (p2p_exchange_step_sums), the Halpern decision
+__global__ void __launch_bounds__(kBlock)
+k_halpern_decision_p2p(pdlpdev_ctl* __restrict__ ctl, pdlpdev_halpern* __restrict__ hal, const double* __restrict__ part_dy, int nb_dy,
+                       const double* __restrict__ part_t, int nb_t, const double* __restrict__ landed, const unsigned long long* __restrict__ flags,
+                       int world, const unsigned long long* __restrict__ epoch, int* __restrict__ fault, const p2pdev::Push* __restrict__ push)
+{
+  if (!loop_active(ctl)) return;
+  double sum[3];
+  if (!p2p_exchange_step_sums(ctl, part_dy, nb_dy, part_t, nb_t, landed, flags, world, epoch, fault, push, sum)) return;
+  pdlpdev_ctl lc = *ctl;
+  halpern_decision_from_sums(ctl, hal, lc, sum[0], sum[1], sum[2]);
 }
 
 __global__ void __launch_bounds__(kBlock)
@@ -956,7 +993,9 @@ static void launch_a_dual(pdlpdev_ctx* ctx, double* ycopy = nullptr, const p2pde
   const Gathered g = Gathered::fixed(ctx->xbar, true);
   const auto pre  = std::make_tuple(ctx->ctl);
   const auto vecs = std::make_tuple(ctx->xbar);
-  if (ctx->halpern) (void)launch_product(ctx, ctx->A, products::a_halpern, g, pre, vecs, std::make_tuple(ctx->y[0], ctx->y[1], ctx->lo, ctx->hi, halpern_args(ctx), ctx->A.part));
+  if (ctx->halpern && ycopy)  // (a rank of a sharded Halpern solve: y' also into the gathered dual and, with `push`, the peers' blocks)
+    (void)launch_product(ctx, ctx->A, products::a_halpern_sharded, g, pre, vecs, std::make_tuple(ctx->y[0], ctx->y[1], ctx->lo, ctx->hi, halpern_args(ctx), ctx->A.part, ycopy, push));
+  else if (ctx->halpern) (void)launch_product(ctx, ctx->A, products::a_halpern, g, pre, vecs, std::make_tuple(ctx->y[0], ctx->y[1], ctx->lo, ctx->hi, halpern_args(ctx), ctx->A.part));
   else (void)launch_product(ctx, ctx->A, products::a_dual, g, pre, vecs, std::make_tuple(ctx->y[0], ctx->y[1], ctx->lo, ctx->hi, ctx->sumy, ctx->A.part, ycopy, push));
 }
 static void launch_at_step(pdlpdev_ctx* ctx)
@@ -994,6 +1033,15 @@ static void launch_oc_step(pdlpdev_ctx* ctx)
   const size_t cs = (size_t)ctx->rank * ctx->slice;
   double *x0 = ctx->x[0] + cs, *x1 = ctx->x[1] + cs, *t0 = ctx->aty[0] + cs, *t1 = ctx->aty[1] + cs;
   const double* yg = ctx->ygather;  // the trial dual of every rank, whichever ping-pong buffer it lives in
+  if (ctx->halpern) {
+    // the Halpern twin gathers y' of every rank from the gathered dual; T(z^k)'s primal half (x' of a run's last step), the anchor and its A^T y are offset
+    // by the slice like the x / A^T y pairs.  Complete column sums on the owner: A^T y^{k+1} of a column is the linear combination
+    // of the bits an unsharded step combines.
+    const HalpernArgs h{ctx->hal, ctx->ar_buf + cs /* run_epilogue takes it to the average slot */, const_cast<double*>(yg), ctx->lrx + cs, ctx->lry, ctx->lraty + cs};
+    (void)launch_product(ctx, ctx->Oc, products::at_halpern, Gathered::fixed(yg, true), std::make_tuple(ctx->ctl), std::make_tuple(),
+                         std::make_tuple(x0, x1, t0, t1, h, ctx->Oc.part));
+    return;
+  }
   (void)launch_product(ctx, ctx->Oc, products::at_step, Gathered::trial(yg, yg, true), std::make_tuple(ctx->ctl), std::make_tuple(yg, yg),
                        std::make_tuple(x0, x1, t0, t1, ctx->Oc.part));
 }
@@ -1002,9 +1050,9 @@ static void launch_oc_step(pdlpdev_ctx* ctx)
 static int enqueue_attempt(pdlpdev_ctx* ctx)
 {
   const int n = ctx->n;
-  // (a context in Halpern mode is never sharded: the single-GPU sequence at the end of this function, whose three launch helpers pick
-  //  the Halpern kernels -- k_primal is the same, pending_avg stays 0)
-  if (ctx->halpern && ctx->comm) return fail(-7, "reflected Halpern mode: not available behind a communicator");
+  // (Halpern mode: the single-GPU sequence at the end of this function or, behind a communicator, the owner-computes sequence; the
+  //  launch helpers pick the Halpern kernels -- k_primal is the same, pending_avg stays 0.  pdlpdev_set_halpern admits no other dataflow.)
+  if (ctx->halpern && ctx->comm && !ctx->owner) return fail(-7, "reflected Halpern mode: behind a communicator the owner-computes dataflow only");
   if (ctx->owner) {
     if (!ctx->Oc.hot.off) return fail(-1, "owner-computes dataflow: pdlpdev_owner_setup was not called");
     const size_t cs = (size_t)ctx->rank * ctx->slice;
@@ -1040,6 +1088,10 @@ static int enqueue_attempt(pdlpdev_ctx* ctx)
       if (ctx->halo.on) pull_ranges(1, ctx->ygather, P.off_y);
       else pull(1, ctx->ygather, P.off_y, ctx->ypad);
       launch_oc_step(ctx);
+      if (ctx->halpern)
+        launch_k(ctx, k_halpern_decision_p2p, 1, kBlock, 0, ctx->ctl, ctx->hal, ctx->A.part, ctx->A.partials(), ctx->Oc.part, ctx->Oc.partials(),
+                 reinterpret_cast<const double*>(P.base + P.off_s), flags, W, P.epoch, P.fault, P.push_dev + 2);
+      else
       launch_k(ctx, k_step_decision_p2p, 1, kBlock, 0, ctx->ctl, ctx->A.part, ctx->A.partials(), ctx->Oc.part, ctx->Oc.partials(),
                reinterpret_cast<const double*>(P.base + P.off_s), flags, W, P.epoch, P.fault, ctx->sp, P.push_dev + 2);
       LAUNCH_CHECK();
@@ -1055,7 +1107,8 @@ static int enqueue_attempt(pdlpdev_ctx* ctx)
     launch_k(ctx, k_pack_step_sums, 1, kBlock, 0, ctx->A.part, ctx->A.partials(), ctx->Oc.part, ctx->Oc.partials(), ctx->rs_scal);
     LAUNCH_CHECK();
     TRY(allreduce(ctx, ctx->rs_scal, 3, rccl::kSum));
-    launch_k(ctx, k_step_decision, 1, kDecisionThreads, 0, ctx->ctl, nullptr, 0, ctx->rs_scal + 1, 1, ctx->rs_scal, ctx->sp);
+    if (ctx->halpern) launch_k(ctx, k_halpern_decision_sums, 1, 1, 0, ctx->ctl, ctx->hal, ctx->rs_scal);
+    else launch_k(ctx, k_step_decision, 1, kDecisionThreads, 0, ctx->ctl, nullptr, 0, ctx->rs_scal + 1, 1, ctx->rs_scal, ctx->sp);
     LAUNCH_CHECK();
     return 0;
   }
@@ -1218,7 +1271,15 @@ static int run_epilogue(pdlpdev_ctx* ctx, int rounds, pdlpdev_ctl* ctl)
     const int cur = ctx->ctl_h->cur;
     TRY(all_gather(ctx, ctx->x[cur], (size_t)ctx->slice));
     TRY(all_gather(ctx, ctx->aty[cur], (size_t)ctx->slice));
-    TRY(all_gather(ctx, ctx->sumx, (size_t)ctx->slice));
+    if (ctx->halpern) {
+      // (owner dataflow: the mode has no running sum.  x' of the run's last step -- the primal half of T(z^k), which the evaluation reads
+      //  from the average slot -- is valid on the owners' slices only; it travels through ar_buf, which has the spare entries equal
+      //  slices need and is free between attempts, and lands in the average slot, which has none: launch_oc_step)
+      TRY(all_gather(ctx, ctx->ar_buf, (size_t)ctx->slice));
+      HIP_TRY(hipMemcpyAsync(ctx->avgx, ctx->ar_buf, (size_t)ctx->n * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+    } else {
+      TRY(all_gather(ctx, ctx->sumx, (size_t)ctx->slice));
+    }
   }
   if (ctl) *ctl = *ctx->ctl_h;
   return 0;
@@ -1502,7 +1563,11 @@ static int64_t locate_buffer(pdlpdev_ctx* ctx, int id, double** ptr)
     case PDLPDEV_BUF_AX_U_CURRENT: src = ctx->ax_u[PDLPDEV_CURRENT], count = m; break;
     case PDLPDEV_BUF_AX_U_AVERAGE: src = ctx->ax_u[PDLPDEV_AVERAGE], count = m; break;
     case PDLPDEV_BUF_PART_A: src = ctx->A.part, count = ctx->A.partials(); break;
-    case PDLPDEV_BUF_PART_AT: src = ctx->At.part, count = 2 * (int64_t)ctx->At.partials(); break;
+    case PDLPDEV_BUF_PART_AT:  // (a sharded Halpern step's A^T product runs on the owner-computes column block, whose partials these are;
+                               //  every other context answers as it always did)
+      if (ctx->halpern && ctx->owner && ctx->Oc.part) src = ctx->Oc.part, count = 2 * (int64_t)ctx->Oc.partials();
+      else src = ctx->At.part, count = 2 * (int64_t)ctx->At.partials();
+      break;
     case PDLPDEV_BUF_ZS_LAUNCHES:
       if (!ctx->xmask) { fail(-1, "buffer %d: this context has no bitmap of xbar (CUOPT_AMD_TUNE=zero_skip=0, or A is not in the row-sum panels)", id); return -1; }
       src = reinterpret_cast<double*>(ctx->xmask + 2 * (((size_t)n + 127) / 128)), count = 1;
@@ -1586,7 +1651,12 @@ int pdlpdev_set_halpern(pdlpdev_ctx* ctx, int on)
   HIP_TRY(hipSetDevice(ctx->device));
   if ((on != 0) == ctx->halpern) return 0;
   if (on) {
-    if (ctx->comm) return fail(-7, "reflected Halpern mode: not available for a sharded solver");
+    // behind a communicator: the owner-computes dataflow only (the step's twins run on its column block; the solver's
+    // cuoptamd_settings::halpern_sharded is the public gate above this layer).  The anchors lrx / lry / lraty: replicated / this
+    // rank's rows / replicated.
+    if (ctx->comm && !ctx->owner)
+      return fail(-7, "reflected Halpern mode: a sharded solver runs it on the owner-computes dataflow only, not on CUOPT_AMD_SHARD_DATAFLOW=%s",
+                  ctx->rsag ? "rsag" : "allreduce");
     // (a context on the resident small-LP path runs the mode inside one workgroup: kernels_resident_halpern.hip)
     if (!ctx->scaled) return fail(-1, "pdlpdev_set_halpern: call after pdlpdev_scale_problem");
     if (!ctx->lraty) TRY(dev_alloc(ctx, &ctx->lraty, (size_t)ctx->n));
@@ -1611,18 +1681,24 @@ int pdlpdev_get_halpern(pdlpdev_ctx* ctx, pdlpdev_halpern* out)
 int pdlpdev_spectral_norm(pdlpdev_ctx* ctx, double rel_tol, int32_t max_products, double* sigma_max, int32_t* products)
 {
   HIP_TRY(hipSetDevice(ctx->device));
-  if (ctx->comm) return fail(-7, "pdlpdev_spectral_norm: single GPU only");
   // (a resident context keeps its stream-layout arrays: launch_plain runs the layout's plain products on it, as pdlpdev_compute_aty does)
+  // A sharded context: A v on this rank's rows, the partial A^T (A v) into ar_buf, one all-reduce as in pdlpdev_compute_aty, the norm
+  // and the next v from the replicated result -- every rank holds the same bits and returns the same sigma_max.  xbar is not borrowed.
   hipStream_t s = ctx->stream;
   const int n   = ctx->n;
-  double* v = ctx->tmp_n;  // the normalised iterate; A v -> tmp_m; A^T A v -> xbar
+  double* v = ctx->tmp_n;  // the normalised iterate; A v -> tmp_m; A^T A v -> xbar (sharded: ar_buf)
+  double* const atav = ctx->comm ? ctx->ar_buf : ctx->xbar;
   k_fill<<<grid_for(n), kBlock, 0, s>>>(n, v, 1.0 / sqrt((double)n));
   double est = 0.0;
   int done   = 0;
   while (done < max_products) {
     launch_plain(ctx, 0, v, ctx->tmp_m);
-    launch_plain(ctx, 1, ctx->tmp_m, ctx->xbar);
-    TRY(reduce_vec(ctx, 1, n, ctx->xbar, nullptr, 0));
+    launch_plain(ctx, 1, ctx->tmp_m, atav);
+    if (ctx->comm) {
+      LAUNCH_CHECK();
+      TRY(allreduce(ctx, atav, (size_t)n, rccl::kSum));
+    }
+    TRY(reduce_vec(ctx, 1, n, atav, nullptr, 0));
     TRY(fetch_scalars(ctx, 1));
     done += 1;
     const double s2 = sqrt(ctx->scal_h[0]);  // ||A^T A v||, v of unit length: the estimate of sigma_max^2 (from below)
@@ -1630,13 +1706,13 @@ int pdlpdev_spectral_norm(pdlpdev_ctx* ctx, double rel_tol, int32_t max_products
       est = 0.0;
       break;
     }
-    k_div_by_scalar<<<grid_for(n), kBlock, 0, s>>>(n, v, ctx->xbar, s2);  // v <- A^T A v / s2
+    k_div_by_scalar<<<grid_for(n), kBlock, 0, s>>>(n, v, atav, s2);  // v <- A^T A v / s2
     LAUNCH_CHECK();
     const bool settled = fabs(s2 - est) <= rel_tol * s2;
     est                = s2;
     if (settled) break;
   }
-  HIP_TRY(hipMemsetAsync(ctx->xbar, 0, (size_t)n * sizeof(double), s));
+  if (!ctx->comm) HIP_TRY(hipMemsetAsync(ctx->xbar, 0, (size_t)n * sizeof(double), s));
   if (sigma_max) *sigma_max = sqrt(est);
   if (products) *products = done;
   return 0;
@@ -1651,6 +1727,10 @@ int pdlpdev_halpern_restart(pdlpdev_ctx* ctx, double theta, double dist[2], pdlp
   launch_restart_current(ctx, g);
   k_finalize<<<1, kBlock, 0, s>>>(ctx->part_g, g, 2, 0u, ctx->scal);
   k_copy_current<<<grid_for(ctx->n), kBlock, 0, s>>>(ctx->n, ctx->ctl, ctx->aty[0], ctx->aty[1], ctx->lraty);
+  if (ctx->comm) {  // (the dual distance is a sum over the row blocks, as in pdlpdev_restart: every rank forms the same weight)
+    LAUNCH_CHECK();
+    TRY(allreduce(ctx, ctx->scal + 1, 1, rccl::kSum));
+  }
   k_halpern_restart_ctl<<<1, 1, 0, s>>>(ctx->ctl, ctx->hal, ctx->scal, theta);
   LAUNCH_CHECK();
   HIP_TRY(hipMemcpyAsync(ctx->scal_h, ctx->scal, 2 * sizeof(double), hipMemcpyDeviceToHost, s));

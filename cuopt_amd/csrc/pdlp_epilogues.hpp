@@ -225,6 +225,51 @@ struct HalpernDualEpilogue {
     return HalpernDualEpilogue{cur ? y1 : y0, cur ? y0 : y1, h.ty, h.y0, lo, hi, ctl->sigma, HalpernWeights(h.hal)};
   }
 };
+// (2hs) the same on a rank of a sharded solve, owner-computes dataflow (cuoptamd_settings::halpern_sharded): y' of the rank's rows also
+//       goes to this rank's slot of the gathered dual (copy), which the column block's A^T product gathers, and -- direct peer
+//       transport -- into every other rank's landing block (push), as DualEpilogue's copy / push do.  One more coalesced 8-byte
+//       stream per row; no LDS.  An epilogue of its own: HalpernDualEpilogue and the kernels built on it keep their instructions.
+struct HalpernShardedDualEpilogue {
+  static constexpr int NQ = 1;
+  using Op = SumOp;
+  const double* __restrict__ y;
+  double* __restrict__ yn;
+  double* __restrict__ yp;
+  const double* __restrict__ y0;
+  const double* __restrict__ lo;
+  const double* __restrict__ hi;
+  double sigma;
+  HalpernWeights hw;
+  double* __restrict__ copy;
+  const p2pdev::Push* __restrict__ push;
+  struct Ops {
+    double y, lo, hi, y0;
+  };
+  __device__ __forceinline__ Ops load(int i) const { return Ops{y[i], lo[i], hi[i], y0[i]}; }
+  __device__ __forceinline__ void apply(int i, double v, const Ops& o, double (&acc)[1])
+  {
+    const double yi  = o.y;
+    double next      = yi - (sigma * v);
+    const double low = next + sigma * o.lo;
+    const double up  = next + sigma * o.hi;
+    next             = dmax(low, dmin(up, 0.0));
+    yp[i]            = next;
+    copy[i]          = next;
+    if (push)
+      for (int q = 0; q < push->world; ++q)
+        if (push->wants(q, i)) p2pdev::put(push->slot(q) + i, next);
+    const double dy = next - yi;
+    acc[0] += dy * dy;
+    yn[i] = hw.combine(next, yi, o.y0);
+  }
+  __device__ __forceinline__ void row(int i, double v, double (&acc)[1]) { apply(i, v, load(i), acc); }
+  static __device__ __forceinline__ HalpernShardedDualEpilogue make(const pdlpdev_ctl* ctl, double* y0, double* y1, const double* lo, const double* hi,
+                                                                    const HalpernArgs& h, double* ycopy, const p2pdev::Push* push)
+  {
+    const int cur = ctl->cur;
+    return HalpernShardedDualEpilogue{cur ? y1 : y0, cur ? y0 : y1, h.ty, h.y0, lo, hi, ctl->sigma, HalpernWeights(h.hal), ycopy, push};
+  }
+};
 // (3h) rows of A^T: v = A^T y' with StepEpilogue's two sums (dx . (A^T y' - A^T y^k) = dy . A dx, ||dx||^2), then x^{k+1} over x'
 //      (read and written by the same lane) and A^T y^{k+1} by the same linear combination; xp (null except on the last step of a
 //      run): x', the primal half of T(z^k), survives there

@@ -135,3 +135,15 @@ DECLARE_KERNELS(A_HALPERN_KERNELS)
   ROW(at_halpern, const pdlpdev_ctl* __restrict__ ctl, double* __restrict__ x0, double* __restrict__ x1, double* __restrict__ aty0, double* __restrict__ aty1, HalpernArgs h, double* __restrict__ part) \
   PB(at_halpern, const pdlpdev_ctl* __restrict__ ctl, double* __restrict__ x0, double* __restrict__ x1, double* __restrict__ aty0, double* __restrict__ aty1, HalpernArgs h, double* __restrict__ part)
 DECLARE_KERNELS(AT_HALPERN_KERNELS)
+// ... and the A product of a sharded Halpern step (HalpernShardedDualEpilogue: y' also into the gathered dual / the peers' blocks)
+__global__ void __launch_bounds__(kBlock)
+k_spmv_a_halpern_sharded(int nb, const int32_t* __restrict__ rb, const int32_t* __restrict__ off,
+                         const int32_t* __restrict__ idx, const double* __restrict__ val,
+                         const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ xbar,
+                         double* __restrict__ y0, double* __restrict__ y1, const double* __restrict__ lo,
+                         const double* __restrict__ hi, HalpernArgs h, double* __restrict__ part, double* __restrict__ ycopy,
+                         const p2pdev::Push* __restrict__ push, const double* __restrict__ dadd);
+#define A_HALPERN_SHARDED_KERNELS(ROW, PB) \
+  ROW(a_halpern_sharded, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ xbar, double* __restrict__ y0, double* __restrict__ y1, const double* __restrict__ lo, const double* __restrict__ hi, HalpernArgs h, double* __restrict__ part, double* __restrict__ ycopy, const p2pdev::Push* __restrict__ push) \
+  PB(a_halpern_sharded, const pdlpdev_ctl* __restrict__ ctl, double* __restrict__ y0, double* __restrict__ y1, const double* __restrict__ lo, const double* __restrict__ hi, HalpernArgs h, double* __restrict__ part, double* __restrict__ ycopy, const p2pdev::Push* __restrict__ push)
+DECLARE_KERNELS(A_HALPERN_SHARDED_KERNELS)

@@ -85,6 +85,7 @@ inline const auto eval_primal = PRODUCT_KERNELS(k_eval_primal, eval_primal);
 inline const auto eval_dual   = PRODUCT_KERNELS(k_eval_dual, eval_dual);
 inline const auto a_halpern   = PRODUCT_KERNELS(k_spmv_a_halpern, a_halpern);
 inline const auto at_halpern  = PRODUCT_KERNELS(k_spmv_at_halpern, at_halpern);
+inline const auto a_halpern_sharded = PRODUCT_KERNELS(k_spmv_a_halpern_sharded, a_halpern_sharded);
 }  // namespace products
 
 // the vector a product gathers, as the device picks it (GatherMode, pdlp_epilogues.hpp): one vector as it is, or the trial / the

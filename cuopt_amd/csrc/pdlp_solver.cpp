@@ -132,6 +132,7 @@ struct SolverProblem {
   cuoptamd_settings S{};
   int32_t m_global = 0, n = 0, row_begin = 0, row_end = 0;
   int rank = 0, world = 1;
+  bool behind_comm = false;  // created with a communicator id (any world >= 1): a rank of a sharded solve
   bool empty_problem = false;  // n_constraints == 0 -> NumericalError (LP/solve.cu:355-359)
   bool maximize = false;
   double objective_scale = 1.0, objective_offset = 0.0;
@@ -682,6 +683,15 @@ const char* halpern_meaningless_setting(const cuoptamd_hyper* h, const cuoptamd_
   if (h && h->update_primal_weight_on_initial_solution) return "update_primal_weight_on_initial_solution";
   return nullptr;
 }
+// what a SHARDED solver of the mode (cuoptamd_settings::halpern_sharded) does not have, by name: the ray pass forms two plain products of
+// a displacement and is not sharded; the resident loop and its K-workgroup batch hold a whole LP in one workgroup
+const char* halpern_sharded_refused_setting(const cuoptamd_settings* st)
+{
+  if (st->halpern_infeasibility) return "halpern_infeasibility";
+  if (st->halpern_resident) return "halpern_resident";
+  if (st->halpern_batch) return "halpern_batch";
+  return nullptr;
+}
 const char* halpern_refused_setting(const cuoptamd_settings* st)
 {
   if (st->detect_infeasibility) return "detect_infeasibility";
@@ -885,6 +895,7 @@ void cuoptamd_default_settings(cuoptamd_settings* s)
   s->halpern_lockstep                 = 0;
   s->halpern_infeasibility            = 0;
   s->halpern_lockstep_rays            = 0;
+  s->halpern_sharded                  = 0;
 }
 
 // Plain parallel counting sort by column (small matrices, and the fallback of the blocked one below).  Thread t owns a
@@ -1147,7 +1158,15 @@ int cuoptamd_solver_create(cuoptamd_solver** out, const cuoptamd_lp* lp, const c
   if (hyper->algorithm != 0 && hyper->algorithm != 1) return fail(-1, "cuoptamd_solver_create: algorithm must be 0 (PDHG with averages) or 1 (reflected Halpern)");
   if (hyper->algorithm == 1) {
     // what the mode does not have is refused by name, not ignored
-    if (world > 1 || comm_id != nullptr) return fail(-7, "%s: sharded solvers (world > 1, a communicator) are not supported", kHalpernName);
+    if (world > 1 || comm_id != nullptr) {
+      if (!settings->halpern_sharded) return fail(-7, "%s: sharded solvers (world > 1, a communicator) are not supported", kHalpernName);
+      // cuoptamd_settings::halpern_sharded: the owner-computes dataflow only, and without what is refused together with it
+      if (const char* bad = halpern_sharded_refused_setting(settings))
+        return fail(-7, "%s: %s is not supported together with halpern_sharded (a sharded solver)", kHalpernName, bad);
+      const char* flow = std::getenv("CUOPT_AMD_SHARD_DATAFLOW");
+      if (flow && *flow && std::string(flow) != "owner")
+        return fail(-7, "%s: halpern_sharded runs on the owner-computes dataflow only, not on CUOPT_AMD_SHARD_DATAFLOW=%s", kHalpernName, flow);
+    }
     if (settings->detect_infeasibility)
       return fail(-7, "%s: detect_infeasibility is not supported (the rays of the averaging iteration are not formed; halpern_infeasibility "
                       "switches on the mode's own detection, on the displacement of a step)", kHalpernName);
@@ -1163,6 +1182,7 @@ int cuoptamd_solver_create(cuoptamd_solver** out, const cuoptamd_lp* lp, const c
   if (settings->log_file && settings->log_file[0]) s->log_path = settings->log_file;
   s->S.log_file = nullptr;  // the caller's string is not kept
   s->m_global = lp->m, s->n = lp->n, s->rank = rank, s->world = world;
+  s->behind_comm = comm_id != nullptr;
   s->objective_offset = lp->objective_offset;
   const int32_t m = lp->m, n = lp->n;
   if (m == 0) {  // run_pdlp_solver: no constraints -> NumericalError (LP/solve.cu:355-359)
@@ -1410,6 +1430,11 @@ int cuoptamd_solver_reset(cuoptamd_solver* s, const double* lb, const double* ub
   const auto t0 = clock_type::now();
   if (settings && halpern_mode(s))  // (refused before anything of the solver changes: it stays usable with its present settings)
     if (const char* bad = halpern_refused_setting(settings)) return fail(-7, "cuoptamd_solver_reset: %s: %s is not supported", kHalpernName, bad);
+  if (settings && halpern_mode(s) && (s->world > 1 || s->behind_comm)) {  // (a sharded solver of the mode: likewise before anything changes)
+    if (!settings->halpern_sharded) return fail(-7, "cuoptamd_solver_reset: %s: a sharded solver needs halpern_sharded to stay set", kHalpernName);
+    if (const char* bad = halpern_sharded_refused_setting(settings))
+      return fail(-7, "cuoptamd_solver_reset: %s: %s is not supported together with halpern_sharded (a sharded solver)", kHalpernName, bad);
+  }
   if (settings) {
     s->S = *settings;
     if (settings->log_file && settings->log_file[0]) s->log_path = settings->log_file;
@@ -1603,6 +1628,8 @@ int cuoptamd_solver_clone(cuoptamd_solver* parent, const double* lb, const doubl
 {
   if (!parent || !out) return fail(-1, "cuoptamd_solver_clone: null argument");
   if (parent->empty_problem || !parent->dev || parent->world != 1) return fail(-7, "cuoptamd_solver_clone: not for empty or sharded solvers");
+  if (halpern_mode(parent) && parent->behind_comm)
+    return fail(-7, "cuoptamd_solver_clone: %s: a solver created with halpern_sharded behind a communicator has no clones", kHalpernName);
   const bool timing = std::getenv("CUOPT_AMD_TIMING") != nullptr;
   const auto t0     = clock_type::now();
   pdlpdev_ctx* dev = nullptr;
@@ -1632,6 +1659,8 @@ int cuoptamd_batch_create(cuoptamd_solver** solvers, int K, cuoptamd_batch** out
   int halpern = 0, opted = 0, first_halpern = -1, lockstep = 0, resident = 0;
   for (int l = 0; l < K; ++l) {
     if (!solvers[l] || !solvers[l]->dev) return fail(-1, "cuoptamd_batch_create: null solver");
+    if (halpern_mode(solvers[l]) && (solvers[l]->world > 1 || solvers[l]->behind_comm))
+      return fail(-7, "cuoptamd_batch_create: LP %d runs the %s sharded (halpern_sharded): a sharded solver is no member of a batch", l, kHalpernName);
     if (halpern_mode(solvers[l])) {
       halpern += 1, opted += solvers[l]->S.halpern_batch != 0;
       if (first_halpern < 0) first_halpern = l;
@@ -2058,7 +2087,10 @@ int cuoptamd_solve_sharded(const cuoptamd_lp* lp, const cuoptamd_hyper* hyper, c
 {
   if (!lp || !hyper || !settings || !result) return fail(-1, "cuoptamd_solve_sharded: null argument");
   if (gpus < 1 || gpus > 16) return fail(-1, "cuoptamd_solve_sharded: 1..16 row blocks");
-  if (hyper->algorithm == 1) return fail(-7, "cuoptamd_solve_sharded: the %s runs on one GPU only", kHalpernName);
+  if (hyper->algorithm == 1 && !settings->halpern_sharded) return fail(-7, "cuoptamd_solve_sharded: the %s runs on one GPU only", kHalpernName);
+  if (hyper->algorithm == 1)  // (what every rank's creation would refuse, refused once and before the device count is looked at)
+    if (const char* bad = halpern_sharded_refused_setting(settings))
+      return fail(-7, "cuoptamd_solve_sharded: %s: %s is not supported together with halpern_sharded (a sharded solver)", kHalpernName, bad);
   if (!soft_communicator && pdlpdev_device_count() < gpus)
     return fail(-5, "cuoptamd_solve_sharded: %d GPUs requested, %d visible (there is no CPU fallback)", gpus,
                 pdlpdev_device_count());
@@ -2133,6 +2165,8 @@ int cuoptamd_solve_sharded(const cuoptamd_lp* lp, const cuoptamd_hyper* hyper, c
 int cuoptamd_solver_get_warm_start(cuoptamd_solver* s, cuoptamd_warm_start* ws)
 {
   if (!s || !ws || !s->dev) return fail(-1, "cuoptamd_solver_get_warm_start: null argument");
+  if (halpern_mode(s) && (s->world > 1 || s->behind_comm))
+    return fail(-7, "cuoptamd_solver_get_warm_start: the %s has no warm-start snapshot, with halpern_sharded as without", kHalpernName);
   if (halpern_mode(s)) return fail(-7, "cuoptamd_solver_get_warm_start: the %s has no warm-start snapshot (its state is not the averaging iteration's)", kHalpernName);
   // Sharded solver: the primal-side vectors are replicated, of the dual-side (m-sized) vectors this rank owns rows
   // [row_begin, row_end): they land at their global positions, the other rows are zeroed -- the snapshots of all ranks

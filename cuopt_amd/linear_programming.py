@@ -49,6 +49,7 @@ CUOPT_AMD_HALPERN_BATCH = "amd_halpern_batch"  # 0 / 1: ... and the LPs of a Bat
 CUOPT_AMD_HALPERN_LOCKSTEP = "amd_halpern_lockstep"  # 0 / 1: Halpern1 LPs of a BatchSolve over one matrix in lockstep batches of 16 / 8 / 4
 CUOPT_AMD_HALPERN_INFEASIBILITY = "amd_halpern_infeasibility"  # 0 / 1: Halpern1 detects infeasible / unbounded LPs (the displacement of a step)
 CUOPT_AMD_HALPERN_LOCKSTEP_RAYS = "amd_halpern_lockstep_rays"  # 0 / 1: ... and lockstep batches take such LPs (one K-wide ray pass for all members)
+CUOPT_AMD_HALPERN_SHARDED = "amd_halpern_sharded"  # 0 / 1: Halpern1 solves sharded over several GPUs (row blocks, owner-computes dataflow)
 
 
 class SolverMethod(IntEnum):  # solver_settings.py:44-60
@@ -309,6 +310,7 @@ class SolverSettings:  # solver_settings.py:99-330
         CUOPT_LOG_FILE: "", CUOPT_LOG_TO_CONSOLE: False, CUOPT_CROSSOVER: False, CUOPT_SOLUTION_FILE: "",
         CUOPT_USER_PROBLEM_FILE: "", CUOPT_AMD_HALPERN_RESIDENT: 0, CUOPT_AMD_HALPERN_BATCH: 0,
         CUOPT_AMD_HALPERN_LOCKSTEP: 0, CUOPT_AMD_HALPERN_INFEASIBILITY: 0, CUOPT_AMD_HALPERN_LOCKSTEP_RAYS: 0,
+        CUOPT_AMD_HALPERN_SHARDED: 0,
     }
 
     def __init__(self):
@@ -481,6 +483,7 @@ def Solve(data_model, solver_settings=None, log_file=""):
     over["halpern_lockstep"] = int(st[CUOPT_AMD_HALPERN_LOCKSTEP])
     over["halpern_infeasibility"] = int(st[CUOPT_AMD_HALPERN_INFEASIBILITY])
     over["halpern_lockstep_rays"] = int(st[CUOPT_AMD_HALPERN_LOCKSTEP_RAYS])
+    over["halpern_sharded"] = int(st[CUOPT_AMD_HALPERN_SHARDED])
     if st[CUOPT_LOG_FILE]:
         over["log_file"] = st[CUOPT_LOG_FILE].encode()
     t0 = time.perf_counter()
@@ -514,6 +517,7 @@ def BatchSolve(data_model_list, solver_settings=None, log_file=""):
     over["halpern_lockstep"] = int(st[CUOPT_AMD_HALPERN_LOCKSTEP])
     over["halpern_infeasibility"] = int(st[CUOPT_AMD_HALPERN_INFEASIBILITY])
     over["halpern_lockstep_rays"] = int(st[CUOPT_AMD_HALPERN_LOCKSTEP_RAYS])
+    over["halpern_sharded"] = int(st[CUOPT_AMD_HALPERN_SHARDED])
     t0 = time.perf_counter()
     out = capi.batch_solve([dm._problem_dict() for dm in data_model_list], mode=int(st[CUOPT_PDLP_SOLVER_MODE]), **over)
     sols = [Solution(ProblemCategory.LP, _named(dm, r["x"]), r["setup_seconds"] + r["loop_seconds"], r["x"], r["y"],

@@ -30,9 +30,14 @@
  *                            ray passes of a batch's members run as one K-wide pass, each member bit for bit as on its own; without
  *                            it such LPs are solved one after the other, as before.  A single cuOptSolve is not changed by it
  *                            (cuOptAmdGetSolveInfo reports "halpern_lockstep_rays"); ignored by the other solver modes.
+ *   CUOPT_AMD_HALPERN_SHARDED  1 / 0 (default 0): under CUOPT_AMD_PDLP_SOLVER_MODE_HALPERN1 with CUOPT_AMD_NUM_GPUS > 1, the solve is
+ *                            sharded by row blocks on the owner-computes dataflow (cuoptamd_settings::halpern_sharded), over
+ *                            collectives or the direct peer stores; without it such a request stays a validation error.
+ *                            CUOPT_AMD_HALPERN_INFEASIBILITY, _RESIDENT and _BATCH are validation errors together with it
+ *                            (cuOptAmdGetSolveInfo reports "halpern_sharded"); ignored by the other solver modes.
  * Extra value of CUOPT_PDLP_SOLVER_MODE (constants.h stops at CUOPT_PDLP_SOLVER_MODE_FAST1 = 3):
  *   CUOPT_AMD_PDLP_SOLVER_MODE_HALPERN1 = 4: the restarted reflected Halpern iteration with a constant step size
- *                            (cuoptamd_hyper_preset(4), docs/design/04d_halpern_mode.md).  One GPU; CUOPT_INFEASIBILITY_DETECTION,
+ *                            (cuoptamd_hyper_preset(4), docs/design/04d_halpern_mode.md).  One GPU unless CUOPT_AMD_HALPERN_SHARDED is set (below); CUOPT_INFEASIBILITY_DETECTION,
  *                            save_best_primal_so_far and first_primal_feasible are refused with a validation error, and the
  *                            simplex-grade emulation leaves the infeasibility detection it would switch on off.
  */
@@ -49,6 +54,7 @@
 #define CUOPT_AMD_HALPERN_LOCKSTEP "amd_halpern_lockstep"
 #define CUOPT_AMD_HALPERN_INFEASIBILITY "amd_halpern_infeasibility"
 #define CUOPT_AMD_HALPERN_LOCKSTEP_RAYS "amd_halpern_lockstep_rays"
+#define CUOPT_AMD_HALPERN_SHARDED "amd_halpern_sharded"
 #define CUOPT_AMD_PDLP_SOLVER_MODE_HALPERN1 4
 
 #ifdef __cplusplus

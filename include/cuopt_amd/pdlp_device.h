@@ -130,7 +130,8 @@ enum {
   PDLPDEV_BUF_AX_U_CURRENT, /* A x of the unscaled problem from the last eval(CURRENT)    m */
   PDLPDEV_BUF_AX_U_AVERAGE, /*                                                            m */
   PDLPDEV_BUF_PART_A,       /* the A product's per-workgroup partials of ||dy||^2 as the last attempt left them (download only) */
-  PDLPDEV_BUF_PART_AT,      /* the A^T product's: interaction, then ||dx||^2, one per workgroup each (download only)            */
+  PDLPDEV_BUF_PART_AT,      /* the A^T product's: interaction, then ||dx||^2, one per workgroup each (download only); a sharded
+                             * context in Halpern mode: the owner-computes column block's, which is where its step forms them  */
   PDLPDEV_BUF_XBAR_MASK,    /* zero skip: bit j of the 64-bit words = (xbar_j != 0), as the last primal step wrote it; download only,
                                ceil(n / 64) elements; -1 with CUOPT_AMD_TUNE=zero_skip=0 */
   PDLPDEV_BUF_ZS_LAUNCHES,  /* zero skip: one 64-bit count of the launches of the A product that took the masked path (download only) */

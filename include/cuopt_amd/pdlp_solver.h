@@ -183,6 +183,14 @@ typedef struct cuoptamd_settings {
    * after the other ("shared_matrix"): the measured routing rule of docs/design/07_measurement.md, "Halpern mode".  0 (default): the refusal above stands, as before.  Ignored when algorithm == 0, and by a
    * single solve. */
   int32_t halpern_lockstep_rays;
+  /* Reflected Halpern mode (algorithm == 1) only: non-zero lets cuoptamd_solver_create build a SHARDED solver (world >= 1 with a
+   * communicator id) and cuoptamd_solve_sharded accept the mode: row blocks of A per rank, the owner-computes dataflow (the default
+   * CUOPT_AMD_SHARD_DATAFLOW; allreduce and rsag are refused with -7, by name), over the collective transport (RCCL or the in-process
+   * communicator, all-gathers or the halo exchange) or the direct peer stores (CUOPT_AMD_SHARD_TRANSPORT=p2p).  Every rank runs the
+   * same major iterations on identical scalars.  Refused together with it, with -7 and by name: halpern_infeasibility,
+   * halpern_resident, halpern_batch, membership of a lockstep batch and clones of a sharded solver, warm-start snapshots.  0
+   * (default): a sharded solver in this mode is refused, as before.  Ignored when algorithm == 0. */
+  int32_t halpern_sharded;
 } cuoptamd_settings;
 
 /* additional_termination_information_t (pdlp/solver_solution.hpp:63-103) + run statistics */
@@ -270,7 +278,8 @@ const char* cuoptamd_last_error(void);
 
 /* presets, mode numbering as CUOPT_PDLP_SOLVER_MODE_* (0 Stable1, 1 Stable2, 2 Methodical1, 3 Fast1) and, beyond the reference's,
  * 4 = Halpern1 (CUOPT_AMD_PDLP_SOLVER_MODE_HALPERN1, cuopt_c_ext.h): Stable2's scaling and initial primal weight, algorithm = 1.  A
- * Halpern solver runs on one GPU and refuses, with a message that names the mode: sharded creation, warm-start snapshots,
+ * Halpern solver refuses, with a message that names the mode: sharded creation unless cuoptamd_settings::halpern_sharded is set
+ * (then: the owner-computes dataflow, and none of halpern_infeasibility / _resident / _batch, clones or batches), warm-start snapshots,
  * detect_infeasibility, save_best_primal_so_far, first_primal_feasible; cuoptamd_batch_create answers -7 for it unless every member
  * is a resident Halpern solver with cuoptamd_settings::halpern_batch set (K workgroups of one launch), or every member is a
  * multi-launch Halpern solver over one matrix with cuoptamd_settings::halpern_lockstep set (the lockstep batch). */
