@@ -98,6 +98,29 @@ class Halpern(C.Structure):
                 ("k", c_int), ("reserved", c_int)]
 
 
+class HalpernMajorParams(C.Structure):
+    """pdlpdev_halpern_major_params: what k_halpern_major_decide needs besides the blocks on the device"""
+    _fields_ = [("absolute_gap_tolerance", c_double), ("relative_gap_tolerance", c_double),
+                ("absolute_primal_tolerance", c_double), ("relative_primal_tolerance", c_double),
+                ("absolute_dual_tolerance", c_double), ("relative_dual_tolerance", c_double),
+                ("norm_b", c_double), ("norm_c", c_double), ("objective_scale", c_double), ("objective_offset", c_double),
+                ("sufficient_reduction", c_double), ("necessary_reduction", c_double), ("artificial_threshold", c_double),
+                ("per_constraint_residual", c_int), ("want_linf", c_int), ("iteration_limit", c_int), ("iteration_offset", c_int)]
+
+
+class HalpernMajorRecord(C.Structure):
+    """pdlpdev_halpern_major_record: one decision of a burst"""
+    _fields_ = [("ev", c_double * 8), ("r", c_double), ("r_first", c_double), ("primal_weight", c_double), ("dist", c_double * 2),
+                ("new_weight", c_double), ("steps_taken", c_int), ("k", c_int), ("verdict", c_int), ("restart", c_int)]
+
+    def as_dict(self):
+        return dict(ev=list(self.ev), r=self.r, r_first=self.r_first, primal_weight=self.primal_weight, dist=list(self.dist),
+                    new_weight=self.new_weight, steps_taken=self.steps_taken, k=self.k, verdict=self.verdict, restart=self.restart)
+
+
+MAJOR_GO_ON, MAJOR_OPTIMAL, MAJOR_ITERATION_LIMIT, MAJOR_STEP_ERROR, MAJOR_FELL_SHORT = 0, 1, 4, -1, -2  # verdicts of a record
+
+
 class SolverSettings(C.Structure):
     _fields_ = [("absolute_gap_tolerance", c_double), ("relative_gap_tolerance", c_double),
                 ("absolute_primal_tolerance", c_double), ("relative_primal_tolerance", c_double),
@@ -158,6 +181,27 @@ class SolverSettingsWithSharded(SolverSettingsWithLockstepRays):
 
 assert SolverSettingsWithSharded.halpern_sharded.offset == SolverSettingsWithLockstepRays._LOCKSTEP_RAYS_OFFSET + C.sizeof(c_int)
 assert SolverSettingsWithSharded.halpern_sharded.offset + C.sizeof(c_int) <= C.sizeof(SolverSettingsWithSharded)
+
+
+class SolverSettingsWithDeviceMajor(SolverSettingsWithSharded):
+    """... and the field appended behind halpern_sharded: int32_t halpern_device_major (0: the host decides every major iteration;
+    P = 1 .. 16: the device decides, P periods per host synchronisation).  halpern_sharded ends four bytes short of the doubles'
+    alignment, so the C compiler puts the new member into what ctypes counts as the tail padding of SolverSettingsWithSharded: like
+    halpern_lockstep_rays it is a view of those four bytes and not an entry of _fields_.  The struct every call passes now, and what
+    default_settings() makes; the classes above keep the ends their tests pin."""
+    _fields_ = []
+    _DEVICE_MAJOR_OFFSET = SolverSettingsWithSharded.halpern_sharded.offset + C.sizeof(c_int)
+
+    @property
+    def halpern_device_major(self):
+        return c_int.from_buffer(self, self._DEVICE_MAJOR_OFFSET).value
+
+    @halpern_device_major.setter
+    def halpern_device_major(self, value):
+        c_int.from_buffer(self, self._DEVICE_MAJOR_OFFSET).value = int(value)
+
+
+assert SolverSettingsWithDeviceMajor._DEVICE_MAJOR_OFFSET + C.sizeof(c_int) <= C.sizeof(SolverSettingsWithDeviceMajor) == C.sizeof(SolverSettingsWithSharded)
 
 
 class Result(C.Structure):
@@ -415,6 +459,11 @@ if hasattr(lib, "cuoptamd_solver_get_ray"):  # (... or no infeasibility detectio
     _proto("pdlpdev_set_halpern_rays", c_int, c_void_p, c_int)
     _proto("pdlpdev_halpern_eval_infeasibility", c_int, c_void_p, c_int, c_void_p)
     _proto("pdlpdev_halpern_get_ray", c_int, c_void_p, c_void_p, c_void_p)
+if hasattr(lib, "pdlpdev_run_halpern_burst"):  # (... or no device-decided major iterations: cuoptamd_settings::halpern_device_major)
+    _proto("cuoptamd_solver_halpern_device_major", c_int, c_void_p)
+    _proto("pdlpdev_halpern_burst_stats", c_int, c_void_p, c_void_p)
+    _proto("pdlpdev_debug_halpern_major_decide", c_int, c_int, c_void_p, c_void_p, P(Halpern), c_double, c_int, c_int, P(HalpernMajorParams),
+           P(HalpernMajorRecord), P(c_double), P(c_int), P(c_int))
 PDLP_SOLVER_MODE_HALPERN1 = 4  # CUOPT_AMD_PDLP_SOLVER_MODE_HALPERN1 (cuopt_c_ext.h)
 
 # ids of pdlp_device.h
@@ -666,7 +715,7 @@ def hyper_preset(mode=1):
 
 
 def default_settings(**over):
-    s = SolverSettingsWithSharded()
+    s = SolverSettingsWithDeviceMajor()
     lib.cuoptamd_default_settings(C.byref(s))
     tol = over.pop("tol", None)
     if tol is not None:
@@ -832,6 +881,11 @@ class Solver:
     @property
     def device(self):
         return Device(handle=c_void_p(lib.cuoptamd_solver_device(self.handle)), owner=False)
+
+    def halpern_device_major(self):
+        """cuoptamd_solver_halpern_device_major: the P of cuoptamd_settings::halpern_device_major this solver runs with (its major
+        iterations are decided on the device, P periods per host synchronisation), 0 when the host decides them"""
+        return int(lib.cuoptamd_solver_halpern_device_major(self.handle))
 
     def row_range(self):
         a, b = c_int(), c_int()
@@ -1289,6 +1343,12 @@ class Device:
         self._ck(lib.pdlpdev_get_halpern(self.handle, C.byref(h)))
         return dict(r=h.r, r_first=h.r_first, r2=h.r2, r2_min=h.r2_min, k=h.k)
 
+    def halpern_burst_stats(self):
+        """pdlpdev_halpern_burst_stats: bursts, periods enqueued, records written, periods enqueued behind a stop (empty launches)"""
+        out = np.zeros(4, dtype=np.int64)
+        self._ck(lib.pdlpdev_halpern_burst_stats(self.handle, out.ctypes.data_as(C.c_void_p)))
+        return dict(zip(["bursts", "periods", "records", "empty_periods"], (int(v) for v in out)))
+
     def set_halpern_rays(self, on=True):
         self._ck(lib.pdlpdev_set_halpern_rays(self.handle, int(bool(on))))
 
@@ -1474,3 +1534,21 @@ class Device:
             self.close()
         except Exception:
             pass
+
+
+def debug_halpern_major_decide(ev, ctl, hal, r_prev, params, target=None, stopped=0, record=None, device=0):
+    """pdlpdev_debug_halpern_major_decide: k_halpern_major_decide once, on the caller's figures -- ev: the eight evaluation figures
+    (PDLPDEV_EV_* order), ctl: a Ctl, hal: a Halpern, r_prev: the fixed-point error at the previous check (< 0: none), params: a
+    HalpernMajorParams, target: the period's accepted-step count (default: ctl.steps_taken), stopped: the burst's flag, record: the
+    record as it stands (in/out).  -> (record, r_prev, stopped, restart) as the kernel left them."""
+    e = _f64(ev)
+    if e.shape != (8,):
+        raise ValueError("debug_halpern_major_decide: eight evaluation figures")
+    rec = HalpernMajorRecord() if record is None else record
+    rp, st, rs = c_double(float(r_prev)), c_int(int(stopped)), c_int(0)
+    rc = lib.pdlpdev_debug_halpern_major_decide(int(device), _ptr(e), C.byref(ctl), C.byref(hal), float(r_prev), int(stopped),
+                                                int(ctl.steps_taken if target is None else target), C.byref(params), C.byref(rec),
+                                                C.byref(rp), C.byref(st), C.byref(rs))
+    if rc != 0:
+        raise CuOptError(rc, lib.pdlpdev_last_error().decode())
+    return rec, rp.value, st.value, rs.value

@@ -71,6 +71,7 @@ struct Settings {
   int32_t halpern_infeasibility = 0;  // mode 4: infeasibility detection on the displacement of a step (cuoptamd_settings::halpern_infeasibility)
   int32_t halpern_lockstep_rays = 0;  // ... and lockstep batches take LPs that have it set (cuoptamd_settings::halpern_lockstep_rays)
   int32_t halpern_sharded = 0;  // mode 4 with amd_num_gpus > 1: sharded solves on the owner-computes dataflow (cuoptamd_settings::halpern_sharded)
+  int32_t halpern_device_major = 0;  // mode 4: P periods per host synchronisation, decided on the device (cuoptamd_settings::halpern_device_major)
   int32_t dual_simplex = -1;  // the dual simplex engine: -1 = CUOPT_AMD_DUAL_SIMPLEX (default on), 0 off, 1 on
   bool infeasibility_detection = false, strict_infeasibility = false, per_constraint_residual = false,
        save_best_primal_so_far = false, first_primal_feasible = false, log_to_console = true,
@@ -116,7 +117,8 @@ struct Settings {
             {CUOPT_AMD_HALPERN_LOCKSTEP, &halpern_lockstep, 0, 1},
             {CUOPT_AMD_HALPERN_INFEASIBILITY, &halpern_infeasibility, 0, 1},
             {CUOPT_AMD_HALPERN_LOCKSTEP_RAYS, &halpern_lockstep_rays, 0, 1},
-            {CUOPT_AMD_HALPERN_SHARDED, &halpern_sharded, 0, 1}};
+            {CUOPT_AMD_HALPERN_SHARDED, &halpern_sharded, 0, 1},
+            {CUOPT_AMD_HALPERN_DEVICE_MAJOR, &halpern_device_major, 0, 16}};
     bools = {{CUOPT_INFEASIBILITY_DETECTION, &infeasibility_detection},
              {CUOPT_STRICT_INFEASIBILITY, &strict_infeasibility},
              {CUOPT_PER_CONSTRAINT_RESIDUAL, &per_constraint_residual},
@@ -800,6 +802,7 @@ cuopt_int_t cuOptSolve(cuOptOptimizationProblem problem, cuOptSolverSettings set
     st.halpern_infeasibility       = s->halpern_infeasibility;
     st.halpern_lockstep_rays       = s->halpern_lockstep_rays;
     st.halpern_sharded             = s->halpern_sharded;
+    st.halpern_device_major        = s->halpern_device_major;
     st.log_file                    = s->log_file.empty() ? nullptr : s->log_file.c_str();
     auto say = [&](const std::string& line) {
       if (s->log_to_console) std::fputs(line.c_str(), stdout), std::fflush(stdout);
@@ -826,6 +829,7 @@ cuopt_int_t cuOptSolve(cuOptOptimizationProblem problem, cuOptSolverSettings set
       }
       if (tightened) {
         st.accept_enabled  = 1;
+        st.halpern_device_major = 0;  // (the acceptance set is kept by the host's head: the device-decided bursts are dropped, the info says so)
         st.iteration_limit = std::min(st.iteration_limit, kSimplexGradeBudget);
       }
     }
@@ -834,6 +838,7 @@ cuopt_int_t cuOptSolve(cuOptOptimizationProblem problem, cuOptSolverSettings set
     int32_t first_attempt_steps = 0, first_attempt_attempts = 0;  // work of a simplex-grade attempt that a second solve followed
     bool second_leg = false;  // ... inside a Concurrent race (the simplex kept running)
     int halpern_resident_ran = 0;  // the solver that answered ran the Halpern mode on the resident small-LP path
+    int halpern_device_major_ran = 0;  // ... with its major iterations decided on the device, P periods per synchronisation (0: by the host)
     std::string answered = simplex_grade && tightened ? "simplex_grade_1e-8" : "requested_tolerances";
     sol->x.assign(p->n, 0.0), sol->y.assign(p->m, 0.0), sol->rc.assign(p->n, 0.0);
     auto take_simplex = [&]() {  // the dual simplex's verdict as the solve's result
@@ -871,6 +876,7 @@ cuopt_int_t cuOptSolve(cuOptOptimizationProblem problem, cuOptSolverSettings set
       {
         int32_t lay[8] = {0};
         if (hyper.algorithm == 1 && pdlpdev_layout_info(cuoptamd_solver_device(solver), lay) == 0) halpern_resident_ran = lay[0] == 2;
+        halpern_device_major_ran = cuoptamd_solver_halpern_device_major(solver);
       }
       if (racing) {
         // Concurrent: the simplex on a host thread, PDLP here in batches of a few major iterations; the first verdict wins
@@ -905,6 +911,7 @@ cuopt_int_t cuOptSolve(cuOptOptimizationProblem problem, cuOptSolverSettings set
           answered   = "requested_tolerances_after_simplex_grade_budget";
           rc         = cuoptamd_solver_reset(solver, nullptr, nullptr, nullptr, nullptr, &st_rest, nullptr, nullptr);
           if (rc != 0) break;
+          halpern_device_major_ran = cuoptamd_solver_halpern_device_major(solver);
         }
         const bool pdlp_done = rc == 0 && res.status != CUOPT_TERIMINATION_STATUS_NO_TERMINATION;
         // whenever the loop ends without a finished, conclusive simplex -- PDLP has its verdict, hit a limit, or FAILED -- the simplex
@@ -938,6 +945,7 @@ cuopt_int_t cuOptSolve(cuOptOptimizationProblem problem, cuOptSolverSettings set
         if (st_rest.iteration_limit > 0 && st_rest.time_limit > 0.0) {
           answered = "requested_tolerances_after_simplex_grade_budget";
           rc = cuoptamd_solver_reset(solver, nullptr, nullptr, nullptr, nullptr, &st_rest, nullptr, nullptr);
+          if (rc == 0) halpern_device_major_ran = cuoptamd_solver_halpern_device_major(solver);
           if (rc == 0) rc = cuoptamd_solver_advance(solver, INT_MAX, &res);
         } else {
           answered = "limit_reached_during_simplex_grade_attempt";
@@ -981,7 +989,8 @@ cuopt_int_t cuOptSolve(cuOptOptimizationProblem problem, cuOptSolverSettings set
                     "{\"engine\": \"%s\", \"requested_method\": \"%s\", \"crossover_requested\": %s, \"simplex_grade_emulation\": %s, "
                     "\"dual_simplex_consulted\": %s, \"dual_simplex_status\": %d, \"crossover\": \"%s\", "
                     "\"answered_by\": \"%s\", \"gpus\": %d, \"iterations\": %d, \"simplex_grade_attempt_iterations\": %d, "
-                    "\"pdlp_algorithm\": \"%s\", \"halpern_resident\": %d, \"halpern_infeasibility\": %d, \"halpern_lockstep_rays\": %d, \"halpern_sharded\": %d}",
+                    "\"pdlp_algorithm\": \"%s\", \"halpern_resident\": %d, \"halpern_infeasibility\": %d, \"halpern_lockstep_rays\": %d, \"halpern_sharded\": %d, "
+                    "\"halpern_device_major\": %d}",
                     engine_answered ? "dual_simplex" : "pdlp", method_name, s->crossover ? "true" : "false", simplex_grade ? "true" : "false",
                     engine_ran ? "true" : "false", (int)sx.status, crossover_by, answered.c_str(), gpus,
                     res.steps_taken + (answered == "requested_tolerances_after_simplex_grade_budget" ? first_attempt_steps : 0),
@@ -989,7 +998,7 @@ cuopt_int_t cuOptSolve(cuOptOptimizationProblem problem, cuOptSolverSettings set
                     hyper.algorithm == 1 ? "reflected_halpern" : "pdhg_average", halpern_resident_ran,
                     hyper.algorithm == 1 && st.halpern_infeasibility ? 1 : 0,
                     hyper.algorithm == 1 && st.halpern_infeasibility && st.halpern_lockstep_rays ? 1 : 0,
-                    hyper.algorithm == 1 && st.halpern_sharded && gpus > 1 ? 1 : 0);
+                    hyper.algorithm == 1 && st.halpern_sharded && gpus > 1 ? 1 : 0, engine_answered ? 0 : halpern_device_major_ran);
       sol->solve_info = info;
       if (other_method || s->crossover) say("cuopt_amd: " + sol->solve_info + "\n");
     }

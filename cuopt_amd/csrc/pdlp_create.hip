@@ -605,6 +605,7 @@ void pdlpdev_destroy(pdlpdev_ctx* ctx)
   if (ctx->comm && !ctx->soft) comm_cache::release(ctx->comm_key);
   for (void* p : ctx->allocs) (void)hipFree(p);
   if (ctx->hal_h) (void)hipHostFree(ctx->hal_h);
+  if (ctx->hmaj_ring) (void)hipHostFree(ctx->hmaj_ring);
   const bool whole = ctx->stream && ctx->scal_h && ctx->first_chunk && !ctx->shared_with_parent && !ctx->stream_borrowed;
   if (!(whole && give_recycled(Recycled{ctx->device, ctx->stream, ctx->scal_h, ctx->first_chunk}))) {
     if (ctx->first_chunk) (void)hipFree(ctx->first_chunk);

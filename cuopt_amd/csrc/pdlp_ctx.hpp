@@ -498,6 +498,11 @@ struct CtxLp {
   double* lraty = nullptr;                                  // A^T y of the anchor
   pdlpdev_halpern *hal = nullptr, *hal_h = nullptr;         // device block + pinned mirror (read back with the control block)
   bool halpern_rays = false;  // pdlpdev_set_halpern_rays: every evaluation of T(z^k) is followed by the ray pass on T(z^k) - z^k
+  // pdlpdev_set_halpern_device_major (cuoptamd_settings::halpern_device_major): the burst's own device block (halpern_major.hpp) and its
+  // ring of 16 records in pinned host memory -- allocated only when the option is set; a clone starts without them like every CtxLp field
+  struct pdlpdev_halpern_major_state* hmaj = nullptr;
+  pdlpdev_halpern_major_record* hmaj_ring = nullptr;
+  int64_t stat_bursts = 0, stat_burst_periods = 0, stat_burst_records = 0, stat_burst_empty = 0;  // pdlpdev_halpern_burst_stats
   // n + pad doubles: A^T y partial + packed scalars between attempts (pdlpdev_compute_aty, the evaluation, pdlpdev_spectral_norm).  A
   // sharded context in Halpern mode (owner-computes dataflow) ALSO keeps x' of a run's last step there, on the rank's slice, from the
   // column block's product of that step until run_epilogue has all-gathered it and copied it into avgx (which has no spare entries for

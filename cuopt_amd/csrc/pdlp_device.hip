@@ -526,6 +526,7 @@ k_unscale(int n, const double* __restrict__ v, const double* __restrict__ d, dou
 // timestamps (hipExtLaunchKernel) without putting event records between the kernels of an attempt.
 #include "pdlp_launch.hpp"
 #include "pdlp_core_internal.hpp"
+#include "halpern_major.hpp"
 
 // panel values <- current CSR values (after upload and again after scale_problem)
 int sync_panel_values(pdlpdev_ctx* c)
@@ -1417,6 +1418,112 @@ int pdlpdev_run_period(pdlpdev_ctx* ctx, int32_t target_steps, const pdlpdev_sma
     TRY(run_rounds(ctx, target_steps, &rounds));
   }
   return run_epilogue(ctx, rounds, ctl);
+}
+
+// ---- bursts of device-decided major iterations (cuoptamd_settings::halpern_device_major; kernels: kernels_halpern_major.hip) ----------
+int pdlpdev_set_halpern_device_major(pdlpdev_ctx* ctx, int on)
+{
+  HIP_TRY(hipSetDevice(ctx->device));
+  if (!on) return 0;
+  if (!ctx->halpern || ctx->comm) return fail(-7, "pdlpdev_set_halpern_device_major: reflected Halpern mode on one GPU only");
+  if (!ctx->hmaj) TRY(dev_alloc(ctx, &ctx->hmaj, 1));
+  if (!ctx->hmaj_ring) HIP_TRY(hipHostMalloc((void**)&ctx->hmaj_ring, 16 * sizeof(pdlpdev_halpern_major_record)));
+  return 0;
+}
+static bool burst_panels(const pdlpdev_ctx* ctx)  // (pdlpdev_run_period's layouts: the guarded evaluation exists for them)
+{
+  const bool both_panels   = ctx->A.layout() == pdlpdev_ctx::MatrixSide::kPanel && ctx->At.layout() == pdlpdev_ctx::MatrixSide::kPanel;
+  const bool dense_unfused = ctx->dense.on && !(ctx->At.fuses_dense() && ctx->A.fuses_dense());
+  return !ctx->small_resident && both_panels && !dense_unfused;
+}
+int pdlpdev_halpern_burst_eligible(pdlpdev_ctx* ctx, const pdlpdev_small_eval* rq)
+{
+  if (!ctx->halpern || ctx->comm || ctx->halpern_rays) return 0;
+  if (ctx->small_resident) return 1;
+  return burst_panels(ctx) && !(rq->eps_p >= 0.0 && rq->eps_d >= 0.0) ? 1 : 0;
+}
+int pdlpdev_halpern_burst_stats(pdlpdev_ctx* ctx, int64_t out[4])
+{
+  out[0] = ctx->stat_bursts, out[1] = ctx->stat_burst_periods, out[2] = ctx->stat_burst_records, out[3] = ctx->stat_burst_empty;
+  return 0;
+}
+// Per period, in stream order: the steps to the period's target (multi-launch: the guarded twin of k_set_target, then the attempt graphs
+// as pdlpdev_run_period replays them; resident: the loop kernel's body behind the guard), the guarded evaluation of T(z^k) that
+// pdlpdev_run_period enqueues, k_halpern_major_decide, the guarded restart.  One synchronisation behind the last period.
+int pdlpdev_run_halpern_burst(pdlpdev_ctx* ctx, int32_t first_target, int32_t period, int32_t count, const pdlpdev_small_eval* rq,
+                              const pdlpdev_halpern_major_params* params, double theta, double r_prev,
+                              pdlpdev_halpern_major_record* records, int32_t* written, double* r_prev_out, pdlpdev_ctl* ctl)
+{
+  roctx::Range range("pdlp: Halpern burst (steps + evaluation + decision + restart, P periods)");
+  *written = 0;
+  HIP_TRY(hipSetDevice(ctx->device));
+  if (count < 1 || count > 16 || period < 1) return fail(-1, "pdlpdev_run_halpern_burst: 1 .. 16 periods of at least one step");
+  if (!ctx->hmaj || !ctx->hmaj_ring) return fail(-7, "pdlpdev_run_halpern_burst: call pdlpdev_set_halpern_device_major first");
+  if (!pdlpdev_halpern_burst_eligible(ctx, rq)) return fail(-7, "pdlpdev_run_halpern_burst: the context has no burst (the resident Halpern loop, or panels on both sides without an l-infinity request)");
+  const bool resident = ctx->small_resident;
+  if (!ctx->ctl_h_current) {  // (something moved the control block behind the loop's back -- a cleared step error: read it, as set_target does)
+    TRY(fetch_ctl(ctx, nullptr));
+    ctx->stat_loop_syncs += 1;
+  }
+  const int before = ctx->ctl_h->steps_taken, attempts_before = ctx->ctl_h->attempts;
+  if (ctx->ctl_h->error != 0 || before >= first_target || first_target - before > period || (resident && period > (1 << 14)))
+    return fail(-7, "pdlpdev_run_halpern_burst: the first period must start inside (step error down, target ahead, at most one period away)");
+  const bool want_linf = rq->eps_p >= 0.0 && rq->eps_d >= 0.0;
+  pdlpdev_halpern_major_params p = *params;
+  p.want_linf = want_linf ? 1 : 0;
+  for (int j = 0; j < count; ++j) ctx->hmaj_ring[j].steps_taken = -1;  // ("not written": a decision leaves its step count here)
+  TRY(halpern_major_launch_arm(ctx, r_prev));
+  int enqueued = 0;
+  for (int j = 0; j < count; ++j) {
+    const int32_t target = first_target + j * period;
+    if (resident) {
+      // (the one-workgroup evaluation writes the pinned block: scal_h is what the decision reads, and the host afterwards)
+      TRY(halpern_major_launch_resident_period(ctx, target, rq->rule_finite, want_linf ? 1 : 0, rq->eps_p, rq->eps_d));
+      TRY(halpern_major_launch_decide(ctx, ctx->scal_h + 32, p, target, ctx->hmaj_ring + j));
+    } else {
+      const int asked = j == 0 ? first_target - before : period;
+      TRY(halpern_major_launch_set_target(ctx, target));
+      TRY(enqueue_attempts(ctx, asked));
+      enqueued += asked;
+      TRY(enqueue_halpern_eval(ctx, rq->rule_finite, rq->eps_p, rq->eps_d, 1));
+      TRY(halpern_major_launch_decide(ctx, ctx->scal + 32, p, target, ctx->hmaj_ring + j));
+    }
+    TRY(halpern_major_launch_restart(ctx, theta, ctx->hmaj_ring + j, resident ? 1 : 0));
+  }
+  if (!resident) {
+    HIP_TRY(hipMemcpyAsync(ctx->hal_h, ctx->hal, sizeof(pdlpdev_halpern), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(ctx->ctl_h, ctx->ctl, sizeof(pdlpdev_ctl), hipMemcpyDeviceToHost, ctx->stream));
+  }
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  ctx->stat_loop_syncs += 1;
+  ctx->ctl_h_current = true;
+  ctx->stat_bursts += 1, ctx->stat_burst_periods += count;
+  int n_written = 0;
+  bool stop_seen = false;
+  for (int j = 0; j < count; ++j) {
+    const pdlpdev_halpern_major_record& r = ctx->hmaj_ring[j];
+    if (r.steps_taken < 0) {
+      stop_seen = true;  // (a period behind the stop: its launches were empty)
+      ctx->stat_burst_empty += 1;
+      continue;
+    }
+    if (stop_seen || n_written != j) return fail(-6, "pdlpdev_run_halpern_burst: a record was written behind the period that stopped the burst");
+    records[n_written++] = r;
+    if (r.verdict != PDLPDEV_MAJOR_GO_ON) stop_seen = true;
+    else r_prev = r.restart ? -1.0 : r.r;  // (what the decision left in the burst's block)
+  }
+  ctx->stat_burst_records += n_written;
+  *written = n_written;
+  if (r_prev_out) *r_prev_out = r_prev;
+  if (!resident) {
+    const pdlpdev_ctl& c = *ctx->ctl_h;
+    ctx->stat_empty_attempts += enqueued - (c.attempts - attempts_before);
+    if (c.steps_taken > before && c.error == 0) ctx->aty_valid = true;  // (after_round's bookkeeping: k_*_at_halpern stored A^T y of z^{k+1})
+    if (c.error != 0) ctx->aty_valid = false;
+    ctx->rejected_in_a_row = 0;  // (a Halpern step never fails)
+  }
+  if (ctl) *ctl = *ctx->ctl_h;
+  return 0;
 }
 
 int pdlpdev_loop_stats(pdlpdev_ctx* ctx, int64_t out[4])

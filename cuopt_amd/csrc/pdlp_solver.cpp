@@ -135,6 +135,8 @@ struct SolverProblem {
   bool behind_comm = false;  // created with a communicator id (any world >= 1): a rank of a sharded solve
   bool empty_problem = false;  // n_constraints == 0 -> NumericalError (LP/solve.cu:355-359)
   bool maximize = false;
+  // cuoptamd_settings::halpern_device_major as it runs: P periods per burst, decided on the device; 0: the host decides (start_run)
+  int device_major = 0;
   double objective_scale = 1.0, objective_offset = 0.0;
   double norm_b = 0.0, norm_c = 0.0;
   double computed_step = 0.0, computed_weight = 0.0;  // compute_initial_step_size / _primal_weight, before overrides
@@ -692,6 +694,29 @@ const char* halpern_sharded_refused_setting(const cuoptamd_settings* st)
   if (st->halpern_batch) return "halpern_batch";
   return nullptr;
 }
+// cuoptamd_settings::halpern_device_major: what is refused together with it, by name.  The ray pass, the acceptance set's snapshot and the
+// batches' own loops are the host's; a sharded solver's ranks decide together.
+const char kDeviceMajorName[] = "halpern_device_major";
+const char* halpern_device_major_refused_setting(const cuoptamd_settings* st)
+{
+  if (st->halpern_infeasibility) return "halpern_infeasibility";
+  if (st->accept_enabled) return "accept_tolerance (an enabled acceptance set)";
+  if (st->halpern_sharded) return "halpern_sharded";
+  if (st->halpern_batch) return "halpern_batch";
+  if (st->halpern_lockstep) return "halpern_lockstep";
+  return nullptr;
+}
+// 0: fine.  -1: the value is outside 0 .. 16.  -7: the option is set together with something it is refused with (who: the caller's name)
+int halpern_device_major_check(const char* who, const cuoptamd_settings* st, bool sharded)
+{
+  if (st->halpern_device_major < 0 || st->halpern_device_major > 16)
+    return fail(-1, "%s: %s: %s must lie in 0 .. 16 (periods per host synchronisation), not %d", who, kHalpernName, kDeviceMajorName, (int)st->halpern_device_major);
+  if (st->halpern_device_major == 0) return 0;
+  if (sharded) return fail(-7, "%s: %s: %s is not supported on a sharded solver (world > 1, a communicator)", who, kHalpernName, kDeviceMajorName);
+  if (const char* bad = halpern_device_major_refused_setting(st))
+    return fail(-7, "%s: %s: %s is not supported together with %s", who, kHalpernName, bad, kDeviceMajorName);
+  return 0;
+}
 const char* halpern_refused_setting(const cuoptamd_settings* st)
 {
   if (st->detect_infeasibility) return "detect_infeasibility";
@@ -896,6 +921,7 @@ void cuoptamd_default_settings(cuoptamd_settings* s)
   s->halpern_infeasibility            = 0;
   s->halpern_lockstep_rays            = 0;
   s->halpern_sharded                  = 0;
+  s->halpern_device_major             = 0;
 }
 
 // Plain parallel counting sort by column (small matrices, and the fallback of the blocked one below).  Thread t owns a
@@ -1058,6 +1084,16 @@ static int start_run(cuoptamd_solver* s, const double* init_x, const double* ini
     // cuoptamd_settings::halpern_infeasibility: every evaluation of T(z^k) brings the ray pass on T(z^k) - z^k with it
     DEV(pdlpdev_set_halpern_rays(s->dev, settings->halpern_infeasibility != 0));
   }
+  // cuoptamd_settings::halpern_device_major: bursts where the device layer has them (the resident Halpern loop, panels on both sides
+  // without an l-infinity request); every other context silently keeps the host-decided path
+  s->device_major = 0;
+  if (halpern_mode(s) && settings->halpern_device_major > 0 && s->world == 1 && !s->behind_comm) {
+    const pdlpdev_small_eval rq = major_eval_request(s);
+    if (pdlpdev_halpern_burst_eligible(s->dev, &rq)) {
+      DEV(pdlpdev_set_halpern_device_major(s->dev, 1));
+      s->device_major = settings->halpern_device_major;
+    }
+  }
   double step = s->computed_step, weight = s->computed_weight;
   if (settings->initial_step_size >= 0.0) step = settings->initial_step_size;  // pdlp.cu:1014-1021
   if (settings->initial_primal_weight >= 0.0) weight = settings->initial_primal_weight;
@@ -1158,6 +1194,7 @@ int cuoptamd_solver_create(cuoptamd_solver** out, const cuoptamd_lp* lp, const c
   if (hyper->algorithm != 0 && hyper->algorithm != 1) return fail(-1, "cuoptamd_solver_create: algorithm must be 0 (PDHG with averages) or 1 (reflected Halpern)");
   if (hyper->algorithm == 1) {
     // what the mode does not have is refused by name, not ignored
+    if (int rc = halpern_device_major_check("cuoptamd_solver_create", settings, world > 1 || comm_id != nullptr)) return rc;
     if (world > 1 || comm_id != nullptr) {
       if (!settings->halpern_sharded) return fail(-7, "%s: sharded solvers (world > 1, a communicator) are not supported", kHalpernName);
       // cuoptamd_settings::halpern_sharded: the owner-computes dataflow only, and without what is refused together with it
@@ -1430,6 +1467,8 @@ int cuoptamd_solver_reset(cuoptamd_solver* s, const double* lb, const double* ub
   const auto t0 = clock_type::now();
   if (settings && halpern_mode(s))  // (refused before anything of the solver changes: it stays usable with its present settings)
     if (const char* bad = halpern_refused_setting(settings)) return fail(-7, "cuoptamd_solver_reset: %s: %s is not supported", kHalpernName, bad);
+  if (settings && halpern_mode(s))
+    if (int rc = halpern_device_major_check("cuoptamd_solver_reset", settings, s->world > 1 || s->behind_comm)) return rc;
   if (settings && halpern_mode(s) && (s->world > 1 || s->behind_comm)) {  // (a sharded solver of the mode: likewise before anything changes)
     if (!settings->halpern_sharded) return fail(-7, "cuoptamd_solver_reset: %s: a sharded solver needs halpern_sharded to stay set", kHalpernName);
     if (const char* bad = halpern_sharded_refused_setting(settings))
@@ -1565,6 +1604,77 @@ static void advance_begin(cuoptamd_solver* s, clock_type::time_point t0)
              s->power_products, s->result.initial_step_size, s->result.initial_primal_weight);
   log_line(s, "   Iter    Primal Obj.      Dual Obj.    Gap        Primal Res.  Dual Res.   Time\n");  // pdlp.cu:1077-1080
 }
+// cuoptamd_settings::halpern_device_major: a BURST in place of the period the loop was about to run (docs/design/04d_halpern_mode.md,
+// "Verdict and restart on the device").  `target`: the accepted-step count (the device's) next_target gave.  Taken only when that is a
+// whole period's end -- a budget that ends inside a period goes the host-decided way -- and then for as many whole periods as fit the
+// budget, at most P.  One synchronisation; afterwards the records are replayed in order: what halpern_major_head and
+// halpern_restart_done do to the host's state, with the device's verdict as the decision.  *taken: the burst ran (s->ctl, s->hal and
+// total_iterations are what it left); *terminated: a record ended the solve, or the time limit did between two bursts.
+static int advance_halpern_burst(cuoptamd_solver* s, int32_t budget_end, int32_t target, bool* taken, bool* terminated)
+{
+  *taken = *terminated = false;
+  const cuoptamd_hyper& H   = s->H;
+  const int32_t period      = H.major_iteration;
+  const int32_t total_after = s->iteration_offset + target;
+  if (s->device_major <= 0 || s->world != 1 || total_after % period != 0 || s->total_iterations + 1 <= H.min_iteration_restart) return 0;
+  const int32_t count = (int32_t)std::min<int64_t>(s->device_major, 1 + ((int64_t)budget_end - total_after) / period);
+  if (count < 1) return 0;
+  const pdlpdev_small_eval rq = major_eval_request_at(s, total_after, s->ctl.its_since_restart + (target - s->ctl.steps_taken));
+  const cuoptamd_settings& t  = s->S;
+  pdlpdev_halpern_major_params p{};
+  p.absolute_gap_tolerance = t.absolute_gap_tolerance, p.relative_gap_tolerance = t.relative_gap_tolerance;
+  p.absolute_primal_tolerance = t.absolute_primal_tolerance, p.relative_primal_tolerance = t.relative_primal_tolerance;
+  p.absolute_dual_tolerance = t.absolute_dual_tolerance, p.relative_dual_tolerance = t.relative_dual_tolerance;
+  p.norm_b = s->norm_b, p.norm_c = s->norm_c;
+  p.objective_scale = s->objective_scale, p.objective_offset = s->objective_offset;
+  p.sufficient_reduction = H.sufficient_reduction_for_restart, p.necessary_reduction = H.necessary_reduction_for_restart;
+  p.artificial_threshold = H.artificial_restart_threshold;
+  p.per_constraint_residual = t.per_constraint_residual;
+  p.iteration_limit = t.iteration_limit, p.iteration_offset = s->iteration_offset;
+  pdlpdev_halpern_major_record rec[16];
+  int32_t written = 0;
+  double r_prev   = s->halpern_r_prev;
+  int rc = pdlpdev_run_halpern_burst(s->dev, target, period, count, &rq, &p, H.primal_weight_update_smoothing, s->halpern_r_prev, rec, &written, &r_prev,
+                                     &s->ctl);
+  if (rc != 0) return fail(rc, "pdlpdev_run_halpern_burst: %s", pdlpdev_last_error());
+  *taken = true;
+  (void)pdlpdev_get_halpern(s->dev, &s->hal);
+  HostRange range("pdlp: major iterations of a burst (records replayed)");
+  for (int32_t i = 0; i < written && !*terminated; ++i) {
+    const pdlpdev_halpern_major_record& r = rec[i];
+    if (r.verdict == PDLPDEV_MAJOR_STEP_ERROR || r.verdict == PDLPDEV_MAJOR_FELL_SHORT) break;  // (the host-decided path takes over below)
+    s->total_iterations = s->iteration_offset + r.steps_taken;
+    s->result.num_major_iterations += 1;
+    s->conv_average = to_convergence(s, r.ev);
+    s->conv_current = s->conv_average;
+    if (s->total_iterations % 1000 == 0) log_iteration(s, s->conv_average);  // (the time is the burst's)
+    if (r.verdict != PDLPDEV_MAJOR_GO_ON) {
+      finish_solve(s, r.verdict, PDLPDEV_AVERAGE);
+      major_was_done(s, true);
+      *terminated = true;
+      break;
+    }
+    s->halpern_r_prev = r.r;
+    if (r.restart) halpern_restart_done(s);
+    s->major_done_at = s->total_iterations;
+  }
+  s->total_iterations = s->iteration_offset + s->ctl.steps_taken;
+  if (s->ctl.error) s->step_error = true;
+  if (!*terminated && !s->step_error && s->major_done_at == s->total_iterations) {
+    s->halpern_r_prev = r_prev;  // (the burst's block: the same value the replay arrived at)
+    bool done  = false;
+    int status = kNumericalError;
+    rc         = check_limits(s, &done, &status);  // the time limit, between bursts
+    if (rc) return rc;
+    if (done) {
+      finish_solve(s, status, PDLPDEV_AVERAGE);
+      major_was_done(s, true);
+      *terminated = true;
+    }
+  }
+  return 0;
+}
+
 static int32_t advance_budget_end(const cuoptamd_solver* s, int32_t max_new_iterations)
 {
   const int64_t budget_end64 = (int64_t)s->total_iterations + std::max<int64_t>(max_new_iterations, 0);
@@ -1599,6 +1709,12 @@ int cuoptamd_solver_advance(cuoptamd_solver* s, int32_t max_new_iterations, cuop
     // the artificial restart of Fast1), its evaluation is enqueued behind the attempts and both come back with one synchronisation.
     const cuoptamd_hyper& H   = s->H;
     const int32_t total_after = s->iteration_offset + target;
+    if (halpern_mode(s) && s->device_major > 0) {  // (cuoptamd_settings::halpern_device_major: P periods, decided on the device, one wait)
+      bool taken = false, terminated = false;
+      rc = advance_halpern_burst(s, budget_end, target, &taken, &terminated);
+      if (rc != 0 || terminated) return leave(rc);
+      if (taken) continue;
+    }
     if (period_path && s->world == 1 && !H.artificial_restart_in_main_loop && major_due_at(H, total_after)) {
       s->fused_rq       = major_eval_request_at(s, total_after, s->ctl.its_since_restart + (target - s->ctl.steps_taken));
       int32_t evaluated = 0;
@@ -1661,6 +1777,8 @@ int cuoptamd_batch_create(cuoptamd_solver** solvers, int K, cuoptamd_batch** out
     if (!solvers[l] || !solvers[l]->dev) return fail(-1, "cuoptamd_batch_create: null solver");
     if (halpern_mode(solvers[l]) && (solvers[l]->world > 1 || solvers[l]->behind_comm))
       return fail(-7, "cuoptamd_batch_create: LP %d runs the %s sharded (halpern_sharded): a sharded solver is no member of a batch", l, kHalpernName);
+    if (halpern_mode(solvers[l]) && solvers[l]->S.halpern_device_major != 0)
+      return fail(-7, "cuoptamd_batch_create: LP %d has %s set: a solver whose major iterations the device decides is no member of a batch", l, kDeviceMajorName);
     if (halpern_mode(solvers[l])) {
       halpern += 1, opted += solvers[l]->S.halpern_batch != 0;
       if (first_halpern < 0) first_halpern = l;
@@ -1725,6 +1843,7 @@ int cuoptamd_batch_create(cuoptamd_solver** solvers, int K, cuoptamd_batch** out
 }
 
 pdlpdev_batch* cuoptamd_batch_device(cuoptamd_batch* b) { return b ? b->dev : nullptr; }
+int cuoptamd_solver_halpern_device_major(cuoptamd_solver* s) { return s && halpern_mode(s) ? s->device_major : 0; }
 
 void cuoptamd_batch_destroy(cuoptamd_batch* b)
 {
@@ -2087,6 +2206,8 @@ int cuoptamd_solve_sharded(const cuoptamd_lp* lp, const cuoptamd_hyper* hyper, c
 {
   if (!lp || !hyper || !settings || !result) return fail(-1, "cuoptamd_solve_sharded: null argument");
   if (gpus < 1 || gpus > 16) return fail(-1, "cuoptamd_solve_sharded: 1..16 row blocks");
+  if (hyper->algorithm == 1)
+    if (int rc = halpern_device_major_check("cuoptamd_solve_sharded", settings, true)) return rc;
   if (hyper->algorithm == 1 && !settings->halpern_sharded) return fail(-7, "cuoptamd_solve_sharded: the %s runs on one GPU only", kHalpernName);
   if (hyper->algorithm == 1)  // (what every rank's creation would refuse, refused once and before the device count is looked at)
     if (const char* bad = halpern_sharded_refused_setting(settings))

@@ -50,6 +50,7 @@ CUOPT_AMD_HALPERN_LOCKSTEP = "amd_halpern_lockstep"  # 0 / 1: Halpern1 LPs of a 
 CUOPT_AMD_HALPERN_INFEASIBILITY = "amd_halpern_infeasibility"  # 0 / 1: Halpern1 detects infeasible / unbounded LPs (the displacement of a step)
 CUOPT_AMD_HALPERN_LOCKSTEP_RAYS = "amd_halpern_lockstep_rays"  # 0 / 1: ... and lockstep batches take such LPs (one K-wide ray pass for all members)
 CUOPT_AMD_HALPERN_SHARDED = "amd_halpern_sharded"  # 0 / 1: Halpern1 solves sharded over several GPUs (row blocks, owner-computes dataflow)
+CUOPT_AMD_HALPERN_DEVICE_MAJOR = "amd_halpern_device_major"  # 0 .. 16: Halpern1 decides verdict and restart on the device, P periods per host synchronisation
 
 
 class SolverMethod(IntEnum):  # solver_settings.py:44-60
@@ -310,7 +311,7 @@ class SolverSettings:  # solver_settings.py:99-330
         CUOPT_LOG_FILE: "", CUOPT_LOG_TO_CONSOLE: False, CUOPT_CROSSOVER: False, CUOPT_SOLUTION_FILE: "",
         CUOPT_USER_PROBLEM_FILE: "", CUOPT_AMD_HALPERN_RESIDENT: 0, CUOPT_AMD_HALPERN_BATCH: 0,
         CUOPT_AMD_HALPERN_LOCKSTEP: 0, CUOPT_AMD_HALPERN_INFEASIBILITY: 0, CUOPT_AMD_HALPERN_LOCKSTEP_RAYS: 0,
-        CUOPT_AMD_HALPERN_SHARDED: 0,
+        CUOPT_AMD_HALPERN_SHARDED: 0, CUOPT_AMD_HALPERN_DEVICE_MAJOR: 0,
     }
 
     def __init__(self):
@@ -484,6 +485,7 @@ def Solve(data_model, solver_settings=None, log_file=""):
     over["halpern_infeasibility"] = int(st[CUOPT_AMD_HALPERN_INFEASIBILITY])
     over["halpern_lockstep_rays"] = int(st[CUOPT_AMD_HALPERN_LOCKSTEP_RAYS])
     over["halpern_sharded"] = int(st[CUOPT_AMD_HALPERN_SHARDED])
+    over["halpern_device_major"] = int(st[CUOPT_AMD_HALPERN_DEVICE_MAJOR])
     if st[CUOPT_LOG_FILE]:
         over["log_file"] = st[CUOPT_LOG_FILE].encode()
     t0 = time.perf_counter()

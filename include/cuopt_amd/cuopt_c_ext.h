@@ -35,6 +35,14 @@
  *                            collectives or the direct peer stores; without it such a request stays a validation error.
  *                            CUOPT_AMD_HALPERN_INFEASIBILITY, _RESIDENT and _BATCH are validation errors together with it
  *                            (cuOptAmdGetSolveInfo reports "halpern_sharded"); ignored by the other solver modes.
+ *   CUOPT_AMD_HALPERN_DEVICE_MAJOR  0 (default) .. 16: under CUOPT_AMD_PDLP_SOLVER_MODE_HALPERN1 on one GPU, P > 0 lets the device decide
+ *                            verdict and restart of a major iteration itself and enqueues up to P periods per host
+ *                            synchronisation (cuoptamd_settings::halpern_device_major); the answer is, bit for bit, the one of P = 0.
+ *                            A time limit can be overrun by up to P periods.  CUOPT_AMD_HALPERN_INFEASIBILITY, _SHARDED, _BATCH and
+ *                            _LOCKSTEP are validation errors together with it; where the simplex-grade emulation has switched the
+ *                            acceptance set on, the parameter is dropped.  cuOptAmdGetSolveInfo reports "halpern_device_major": the
+ *                            P that ran, 0 where the host decided (a layout without the burst, a dropped parameter); ignored by
+ *                            the other solver modes.
  * Extra value of CUOPT_PDLP_SOLVER_MODE (constants.h stops at CUOPT_PDLP_SOLVER_MODE_FAST1 = 3):
  *   CUOPT_AMD_PDLP_SOLVER_MODE_HALPERN1 = 4: the restarted reflected Halpern iteration with a constant step size
  *                            (cuoptamd_hyper_preset(4), docs/design/04d_halpern_mode.md).  One GPU unless CUOPT_AMD_HALPERN_SHARDED is set (below); CUOPT_INFEASIBILITY_DETECTION,
@@ -55,6 +63,7 @@
 #define CUOPT_AMD_HALPERN_INFEASIBILITY "amd_halpern_infeasibility"
 #define CUOPT_AMD_HALPERN_LOCKSTEP_RAYS "amd_halpern_lockstep_rays"
 #define CUOPT_AMD_HALPERN_SHARDED "amd_halpern_sharded"
+#define CUOPT_AMD_HALPERN_DEVICE_MAJOR "amd_halpern_device_major"
 #define CUOPT_AMD_PDLP_SOLVER_MODE_HALPERN1 4
 
 #ifdef __cplusplus

@@ -528,6 +528,70 @@ int pdlpdev_major_eval(pdlpdev_ctx* ctx, int average_mode, int rc_rule_finite_bo
  * iteration is due at target_steps and what it will request. */
 int pdlpdev_run_period(pdlpdev_ctx* ctx, int32_t target_steps, const pdlpdev_small_eval* rq, pdlpdev_ctl* ctl,
                        double out_current[PDLPDEV_EV_COUNT], double out_average[PDLPDEV_EV_COUNT], int32_t* evaluated);
+/* ---- verdict and restart of a Halpern major iteration on the device (cuoptamd_settings::halpern_device_major; the design note's
+ * "Verdict and restart on the device") ------------------------------------------------------------------------------------------
+ * What the decision needs besides the blocks that are on the device: the termination rule's constants and the restart tests'. */
+typedef struct pdlpdev_halpern_major_params {
+  double absolute_gap_tolerance, relative_gap_tolerance;
+  double absolute_primal_tolerance, relative_primal_tolerance;
+  double absolute_dual_tolerance, relative_dual_tolerance;
+  double norm_b, norm_c;                    /* the norms of the termination rule (or the caller's factors)                     */
+  double objective_scale, objective_offset; /* applied to both objectives unless they are 1 and 0                              */
+  double sufficient_reduction, necessary_reduction, artificial_threshold; /* the three restart tests                           */
+  int32_t per_constraint_residual;          /* the verdict's per-constraint form (the l-infinity figures against the absolutes) */
+  int32_t want_linf;                        /* the evaluation formed the two l-infinity figures (else they are reported as 0)   */
+  int32_t iteration_limit;                  /* against the context's accepted steps (internal_solver_iterations_)               */
+  int32_t iteration_offset;                 /* total iterations = iteration_offset + accepted steps                             */
+} pdlpdev_halpern_major_params;
+/* verdicts of a record */
+enum {
+  PDLPDEV_MAJOR_GO_ON = 0,
+  PDLPDEV_MAJOR_OPTIMAL = 1,          /* == CUOPT_TERIMINATION_STATUS_OPTIMAL          */
+  PDLPDEV_MAJOR_ITERATION_LIMIT = 4,  /* == CUOPT_TERIMINATION_STATUS_ITERATION_LIMIT  */
+  PDLPDEV_MAJOR_STEP_ERROR = -1,      /* the control block's error flag is up: nothing was decided, the host's path takes over */
+  PDLPDEV_MAJOR_FELL_SHORT = -2       /* the steps did not reach the period's target: likewise                                 */
+};
+/* One decision, as k_halpern_major_decide leaves it in pinned host memory.  ev: the evaluation of T(z^k) as pdlpdev_major_eval hands
+ * it out; r, r_first, k: the Halpern scalars the restart tests saw; primal_weight: in front of the restart; dist, new_weight: written
+ * by the restart (restart != 0), the two distances to the old anchor (not squared) and the weight behind it. */
+typedef struct pdlpdev_halpern_major_record {
+  double ev[PDLPDEV_EV_COUNT];
+  double r, r_first;
+  double primal_weight;
+  double dist[2];
+  double new_weight;
+  int32_t steps_taken; /* accepted steps at the decision */
+  int32_t k;
+  int32_t verdict;
+  int32_t restart;
+} pdlpdev_halpern_major_record;
+/* on != 0: allocates the burst's device block and its ring of 16 records in pinned host memory (once; they are the context's own, a
+ * clone gets none from its parent).  -7 outside Halpern mode and behind a communicator. */
+int pdlpdev_set_halpern_device_major(pdlpdev_ctx* ctx, int on);
+/* 1: pdlpdev_run_halpern_burst serves this context with this evaluation request -- the resident Halpern loop, or a multi-launch
+ * context that pdlpdev_run_period serves (panels on both sides, no l-infinity request); 0: it does not (the caller keeps its loop) */
+int pdlpdev_halpern_burst_eligible(pdlpdev_ctx* ctx, const pdlpdev_small_eval* rq);
+/* A burst: `count` (1 .. 16) whole periods -- period j runs the steps to first_target + j * period accepted steps, the guarded
+ * evaluation of T(z^k) with the request rq, k_halpern_major_decide, and the restart (theta: the primal weight's smoothing) guarded by
+ * the decision -- enqueued with no wait in between, then ONE synchronisation.  No kernel waits for another: stream order only.  A
+ * decision other than "go on" stops the burst: every kernel behind it does nothing (on the multi-launch path the guarded evaluation
+ * behind a stop that is no step error finds its target reached and forms the same figures from the same vectors again; nothing that
+ * can be read back changes).  r_prev: the fixed-point error at the previous check since the last restart (< 0: none).  records[0 ..
+ * *written) receive the decisions in order, *r_prev_out what r_prev has become, *ctl the control block (pdlpdev_get_halpern the
+ * other one).  The caller must KNOW that no major iteration is due in front of first_target and hold the control block
+ * (pdlpdev_run / pdlpdev_run_period / pdlpdev_halpern_restart returned it last).  -7: not eligible or not armed. */
+int pdlpdev_run_halpern_burst(pdlpdev_ctx* ctx, int32_t first_target, int32_t period, int32_t count, const pdlpdev_small_eval* rq,
+                              const pdlpdev_halpern_major_params* params, double theta, double r_prev,
+                              pdlpdev_halpern_major_record* records, int32_t* written, double* r_prev_out, pdlpdev_ctl* ctl);
+/* out = {bursts, periods enqueued, records written, periods enqueued behind a stop (their launches were empty)} since create */
+int pdlpdev_halpern_burst_stats(pdlpdev_ctx* ctx, int64_t out[4]);
+/* Parity hook, in the style of pdlpdev_debug_attempts: k_halpern_major_decide ONCE, on blocks of its own on `device`, with the
+ * evaluation figures ev, the control block, the Halpern scalars, the previous r, the "stopped" flag, the period's target and the
+ * parameters the caller supplies.  *record is in/out (a stopped burst must leave it alone); *r_prev_out, *stopped_out, *restart_out:
+ * the burst's block afterwards.  Solves nothing. */
+int pdlpdev_debug_halpern_major_decide(int device, const double ev[PDLPDEV_EV_COUNT], const pdlpdev_ctl* ctl, const pdlpdev_halpern* hal,
+                                       double r_prev, int32_t stopped, int32_t target, const pdlpdev_halpern_major_params* params,
+                                       pdlpdev_halpern_major_record* record, double* r_prev_out, int32_t* stopped_out, int32_t* restart_out);
 /* Read-only counters since create: out = {evaluations of the current iterate that read A^T y from the loop's buffer, ... that ran the
  * product, host synchronisations inside pdlpdev_run / pdlpdev_run_period / pdlpdev_major_eval, attempts enqueued that found their
  * target reached (empty launches)}.  Single-GPU, non-resident contexts. */

@@ -191,6 +191,23 @@ typedef struct cuoptamd_settings {
    * halpern_resident, halpern_batch, membership of a lockstep batch and clones of a sharded solver, warm-start snapshots.  0
    * (default): a sharded solver in this mode is refused, as before.  Ignored when algorithm == 0. */
   int32_t halpern_sharded;
+  /* Reflected Halpern mode (algorithm == 1) only: P = 1 .. 16 moves verdict and restart of a major iteration to the device and lets
+   * cuoptamd_solver_advance enqueue BURSTS of up to P whole periods -- per period the steps to the period's target, the guarded
+   * evaluation of T(z^k), one decision workgroup (the termination rule and the three restart tests on the scalars that are on the
+   * device already), the guarded restart -- with no wait in between and ONE synchronisation per burst; the host then replays the
+   * records the decisions left in pinned memory (counters, log lines, the result).  The device's verdict is the decision.  Every
+   * figure, iterate and counter of the solve is, bit for bit, the one of P = 0; behind the period that stops a burst nothing that can
+   * be read back changes.  Serves, with world == 1, the resident loop (halpern_resident and an LP of resident size) and the
+   * multi-launch contexts the fused period path serves (both matrices in the panels, no per_constraint_residual); every other
+   * context (stream, jagged, gather-free layouts; panels with per_constraint_residual) silently keeps the host-decided path
+   * (cuoptamd_solver_halpern_device_major says which runs; cuOptAmdGetSolveInfo reports "halpern_device_major").  The time limit is looked at between bursts only: a
+   * solve can overrun it by up to P periods, and the times in the iteration log are the burst's.  A step error, a budget that ends
+   * inside a period and a period that is due at once go through the host-decided path.  Refused together with it, with -7 and by
+   * name, at creation and at reset (a refused reset leaves the solver as it was): halpern_infeasibility, an enabled acceptance set
+   * (accept_tolerance), halpern_sharded or any world > 1, halpern_batch, halpern_lockstep; cuoptamd_batch_create refuses a member that
+   * has it set.  A value outside 0 .. 16 answers -1.  0 (default): the host decides after every period, as before.  Ignored when
+   * algorithm == 0. */
+  int32_t halpern_device_major;
 } cuoptamd_settings;
 
 /* additional_termination_information_t (pdlp/solver_solution.hpp:63-103) + run statistics */
@@ -392,6 +409,9 @@ const char* cuoptamd_batch_solve_last_path(void);
 
 /* the device context (for kernel timing and buffer downloads in benches/tests) */
 pdlpdev_ctx* cuoptamd_solver_device(cuoptamd_solver* s);
+/* cuoptamd_settings::halpern_device_major as this solver runs it: P when its major iterations are decided on the device in bursts of
+ * up to P periods, 0 when the host decides them (the option is off, the averaging iteration, a context without the burst) */
+int cuoptamd_solver_halpern_device_major(cuoptamd_solver* s);
 /* rows [row_begin, row_end) of A held by this rank (of the matrix in the DEVICE's order when the set-up reordered it) */
 int cuoptamd_solver_row_range(cuoptamd_solver* s, int32_t* row_begin, int32_t* row_end);
 /* Set-up reordering (pdlp_device.h "device-side set-up"): info = pdlpdev_analysis_info's ten numbers (info[0] = 1: the device works

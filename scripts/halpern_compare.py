@@ -2,6 +2,7 @@
 """Measurements of the restarted reflected-Halpern mode (solver mode 4) against Stable2 -> profiles/r09_halpern.jsonl.
 
   python scripts/halpern_compare.py [--out FILE] [--only cost|convergence|small] [--workloads c3,c2,...] [--parent-lib libcuopt.so]
+                                    [--device-major 0,1,4,8]
 
 * cost of a step: ms per step in mode 4 against ms per ATTEMPT of Stable2 (solves to a fixed iteration count from a warmed
   solver: wall time over attempted steps, five alternating runs each), plus the per-kernel durations of both modes from
@@ -13,7 +14,10 @@
   resident one-workgroup loop (halpern_resident = 1), mode 4 on the multi-launch path (--parent-lib: on that build, which is how the
   commit before the setting is measured), Stable2 -- five alternating rounds, one child process per variant and round; a record
   per LP and tolerance with all runs, their median and their spread (min, max), plus steps/s of the three loops over 4000
-  steps of 50v-10 at tol = 0, likewise.
+  steps of 50v-10 at tol = 0, likewise.  --device-major 0,1,4,8 adds, per P of the list, the resident loop with
+  cuoptamd_settings::halpern_device_major = P (verdict and restart decided on the device, P periods per synchronisation; P = 0 runs
+  on --parent-lib when one is given: the commit before the setting), with the synchronisations of the loop (pdlpdev_loop_stats)
+  and the burst counters (pdlpdev_halpern_burst_stats: periods enqueued behind a stop are empty launches) in every record.
 Every record is one JSON line: {"kind": "cost" | "kernels" | "convergence" | "small" | "small_rate", ...}; --out is written anew by every run.
 
 Each leg is a child process of its own under a time limit sized to the leg.  The first leg that fails, is killed by a signal or
@@ -79,10 +83,12 @@ def convergence_leg(name, mode, tol, limit):
 SMALL = ["afiro", "mip-50v-10-free-bound-relaxation", "mip-neos5-free-bound-relaxation", "mip-sudoku-relaxation"]
 
 
-def small_leg(names, mode, resident, limit):
+def small_leg(names, mode, resident, limit, device_major=0):
     """every LP of `names` at 1e-4 and 1e-8 in one process (a warm-up solve of the first LP in front), then the loop's rate on 50v-10"""
     from cuopt_amd import capi
     kw = dict(halpern_resident=1) if resident else {}
+    if device_major:
+        kw["halpern_device_major"] = device_major
     out = {}
     for i, name in enumerate([names[0]] + names):
         p = problem(name)
@@ -90,7 +96,9 @@ def small_leg(names, mode, resident, limit):
             s = capi.Solver(p, mode=mode, tol=tol, iteration_limit=limit, **kw)
             r = s.advance()
             out["%s@%g" % (name, tol)] = dict(status=r["status_name"], iterations=r["steps_taken"], restarts=r["num_restarts"], loop_seconds=r["loop_seconds"],
-                                               resident=bool(s.device.layout()["resident"]))
+                                               resident=bool(s.device.layout()["resident"]), majors=r["num_major_iterations"],
+                                               loop_syncs=s.device.loop_stats()["loop_syncs"],
+                                               burst=s.device.halpern_burst_stats() if device_major else None)
             s.close()
     s = capi.Solver(problem(SMALL[1]), mode=mode, tol=0.0, **kw)
     s.advance(400)
@@ -110,7 +118,7 @@ def summary(values):
 def child(args):
     leg = json.loads(args.child)
     if leg["kind"] == "small":
-        print(json.dumps(small_leg(leg["workloads"], leg["mode"], leg["resident"], leg["limit"])))
+        print(json.dumps(small_leg(leg["workloads"], leg["mode"], leg["resident"], leg["limit"], leg.get("device_major", 0))))
     elif leg["kind"] == "cost":
         print(json.dumps(cost_leg(leg["workload"], leg["mode"], leg["steps"], leg["runs"])))
     else:
@@ -148,6 +156,7 @@ def main():
     ap.add_argument("--parent-lib", default=None)
     ap.add_argument("--steps", type=int, default=6000)
     ap.add_argument("--limit", type=int, default=200000)
+    ap.add_argument("--device-major", default=None, help="comma-separated P of halpern_device_major for --only small, e.g. 0,1,4,8")
     ap.add_argument("--child", default=None)
     args = ap.parse_args()
     if args.child:
@@ -173,18 +182,21 @@ def main():
             emit(dict(kind="kernels", workload=w, stable2_ms=a["kernels_ms"], halpern_ms=b["kernels_ms"]))
     if args.only == "small":
         names = args.workloads.split(",") if args.workloads else SMALL
-        variants = (("halpern_resident", 4, True, None), ("halpern_multi_launch", 4, False, args.parent_lib), ("stable2", 1, False, None))
+        variants = (("halpern_resident", 4, True, None, 0), ("halpern_multi_launch", 4, False, args.parent_lib, 0), ("stable2", 1, False, None, 0))
+        if args.device_major:  # the resident loop alone, per P (P = 0: the host-decided loop, on the parent's build when one is given)
+            variants = tuple(("halpern_resident_P%d" % P, 4, True, args.parent_lib if P == 0 else None, P) for P in (int(v) for v in args.device_major.split(",")))
         runs = {v[0]: [] for v in variants}
         for _ in range(5):  # alternating: the variants see the same machine state
-            for key, mode, resident, lib in variants:
-                runs[key].append(run_child(dict(kind="small", workloads=names, mode=mode, resident=resident, limit=args.limit), lib=lib))
+            for key, mode, resident, lib, major in variants:
+                runs[key].append(run_child(dict(kind="small", workloads=names, mode=mode, resident=resident, limit=args.limit, device_major=major), lib=lib))
         for w in names:
             for tol in (1e-4, 1e-8):
                 rec = dict(kind="small", workload=w, tol=tol, multi_launch_library="parent" if args.parent_lib else "this build")
                 for key in runs:
                     legs = [r["%s@%g" % (w, tol)] for r in runs[key]]
                     rec[key] = dict(status=legs[0]["status"], iterations=legs[0]["iterations"], restarts=legs[0]["restarts"], resident=legs[0]["resident"],
-                                    same_iterations_in_every_run=len({l["iterations"] for l in legs}) == 1, loop_seconds=summary([l["loop_seconds"] for l in legs]))
+                                    same_iterations_in_every_run=len({l["iterations"] for l in legs}) == 1, loop_seconds=summary([l["loop_seconds"] for l in legs]),
+                                    majors=legs[0].get("majors"), loop_syncs=legs[0].get("loop_syncs"), burst=legs[0].get("burst"))
                 emit(rec)
         emit(dict(kind="small_rate", workload=SMALL[1], steps=4000, steps_per_second={key: summary([r["rate"] for r in runs[key]]) for key in runs}))
     if args.only in (None, "convergence"):
