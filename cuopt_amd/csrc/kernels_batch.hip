@@ -615,6 +615,23 @@ static int batch_graph(pdlpdev_batch* b, int attempts, hipGraphExec_t* out)
   return 0;
 }
 
+// `count` lockstep attempts on the batch's stream, in the single loop's power-of-two chunks: graph replays or plain launches
+static int batch_enqueue_attempts(pdlpdev_batch* b, int count)
+{
+  const bool use_graph = b->ctx[0]->use_graph != 0;
+  for (int remaining = count, chunk; remaining > 0; remaining -= chunk) {
+    chunk = attempt_chunk(remaining);
+    if (use_graph) {
+      hipGraphExec_t g;
+      TRY(batch_graph(b, chunk, &g));
+      HIP_TRY(hipGraphLaunch(g, b->stream));
+    } else {
+      for (int i = 0; i < chunk; ++i) TRY(batch_enqueue(b));
+    }
+  }
+  return 0;
+}
+
 extern "C" {
 
 // A context for ANOTHER LP over the same matrix and objective.  The clone takes the parent's CtxProblem whole -- matrices, layouts, scaling
@@ -837,30 +854,13 @@ int pdlpdev_batch_run(pdlpdev_batch* b, const int32_t* targets, pdlpdev_ctl* ctl
       remaining = std::max(remaining, asked[l]);
     }
     if (remaining == 0) break;
-    const bool use_graph = b->ctx[0]->use_graph != 0;
-    while (remaining > 0) {
-      int chunk = 1;
-      while (chunk * 2 <= remaining && chunk < 64) chunk *= 2;
-      if (use_graph) {
-        hipGraphExec_t g;
-        TRY(batch_graph(b, chunk, &g));
-        HIP_TRY(hipGraphLaunch(g, b->stream));
-      } else {
-        for (int i = 0; i < chunk; ++i) TRY(batch_enqueue(b));
-      }
-      remaining -= chunk;
-    }
+    TRY(batch_enqueue_attempts(b, remaining));
     TRY(batch_fetch_ctl(b));
-    // (64 rejections in a row leave nothing of a step size: the single loop's rule, per LP; a Halpern step is never rejected)
+    // (the single loop's rule, per LP: too_many_rejections; a Halpern step is never rejected)
     for (int l = 0; !b->halpern && l < K; ++l) {
-      if (asked[l] == 0) continue;
-      pdlpdev_ctx* c = b->ctx[l];
-      c->rejected_in_a_row = c->ctl_h->steps_taken == before[l] ? c->rejected_in_a_row + asked[l] : 0;
-      if (c->ctl_h->error == 0 && c->rejected_in_a_row >= 64) {
-        c->rejected_in_a_row = 0;
-        k_set_error<<<1, 1, 0, b->stream>>>(c->ctl);
-        LAUNCH_CHECK();
-      }
+      if (asked[l] == 0 || !too_many_rejections(b->ctx[l], before[l], asked[l])) continue;
+      k_set_error<<<1, 1, 0, b->stream>>>(b->ctx[l]->ctl);
+      LAUNCH_CHECK();
     }
     if (!b->halpern) TRY(batch_fetch_ctl(b));  // (k_set_error may have run; in Halpern mode nothing moved since the fetch above)
     if (++guard > 100000) return fail(-6, "pdlpdev_batch_run: no progress");
@@ -898,29 +898,12 @@ int pdlpdev_debug_batch_attempts(pdlpdev_batch* b, int count, const int32_t* on,
     else if (c.target_steps > c.steps_taken) k_set_target<<<1, 1, 0, b->stream>>>(b->ctx[l]->ctl, c.steps_taken);
   }
   LAUNCH_CHECK();
-  const bool use_graph = b->ctx[0]->use_graph != 0;
-  for (int remaining = count; remaining > 0;) {
-    int chunk = 1;
-    while (chunk * 2 <= remaining && chunk < 64) chunk *= 2;
-    if (use_graph) {
-      hipGraphExec_t g;
-      TRY(batch_graph(b, chunk, &g));
-      HIP_TRY(hipGraphLaunch(g, b->stream));
-    } else {
-      for (int i = 0; i < chunk; ++i) TRY(batch_enqueue(b));
-    }
-    remaining -= chunk;
-  }
+  TRY(batch_enqueue_attempts(b, count));
   TRY(batch_fetch_ctl(b));
   for (int l = 0; l < K; ++l) {
-    if (!asked[l]) continue;
-    pdlpdev_ctx* c = b->ctx[l];
-    c->rejected_in_a_row = c->ctl_h->steps_taken == before[l] ? c->rejected_in_a_row + count : 0;
-    if (c->ctl_h->error == 0 && c->rejected_in_a_row >= 64) {
-      c->rejected_in_a_row = 0;
-      k_set_error<<<1, 1, 0, b->stream>>>(c->ctl);
-      LAUNCH_CHECK();
-    }
+    if (!asked[l] || !too_many_rejections(b->ctx[l], before[l], count)) continue;
+    k_set_error<<<1, 1, 0, b->stream>>>(b->ctx[l]->ctl);
+    LAUNCH_CHECK();
   }
   TRY(batch_fetch_ctl(b));
   for (int l = 0; l < K; ++l) b->ctx[l]->batch_ctl_fresh = true;

@@ -717,7 +717,7 @@ int pdlpdev_small_batch_run(pdlpdev_small_batch* b, const int32_t* targets, pdlp
     if (guard == 0 && eval_after) {
       for (int l = 0; l < K; ++l)
         if (todo[l] && eval_after[l].mode >= 0) {
-          const int want_linf = eval_after[l].eps_p >= 0.0 && eval_after[l].eps_d >= 0.0;
+          const int want_linf = wants_linf(eval_after[l].eps_p, eval_after[l].eps_d);
           b->major[l] = major_args(b->ctx[l], b->halpern ? 3 : eval_after[l].mode, eval_after[l].rule_finite, want_linf, eval_after[l].eps_p, eval_after[l].eps_d);
           b->major[l].guard_target = targets[l];
           b->list[nev++]           = l;
@@ -734,7 +734,7 @@ int pdlpdev_small_batch_run(pdlpdev_small_batch* b, const int32_t* targets, pdlp
       const pdlpdev_ctx* c = b->ctx[l];
       if (c->scal_h[63] != 1.0) continue;
       if (b->halpern && (c->ctl_h->error != 0 || c->ctl_h->steps_taken < targets[l])) continue;
-      const bool want_linf = eval_after[l].eps_p >= 0.0 && eval_after[l].eps_d >= 0.0;
+      const bool want_linf = wants_linf(eval_after[l].eps_p, eval_after[l].eps_d);
       read_eval(c->scal_h + (b->halpern ? 32 : 0), want_linf, out_current + (size_t)l * PDLPDEV_EV_COUNT);
       read_eval(c->scal_h + 32, want_linf, out_average + (size_t)l * PDLPDEV_EV_COUNT);
       if (evaluated) evaluated[l] = 1;
@@ -758,7 +758,7 @@ int pdlpdev_small_batch_major_eval(pdlpdev_small_batch* b, const pdlpdev_small_e
   int count = 0;
   for (int l = 0; l < b->K; ++l)
     if (req[l].mode >= 0) {
-      const int want_linf = req[l].eps_p >= 0.0 && req[l].eps_d >= 0.0;
+      const int want_linf = wants_linf(req[l].eps_p, req[l].eps_d);
       b->major[l]         = major_args(b->ctx[l], req[l].mode, req[l].rule_finite, want_linf, req[l].eps_p, req[l].eps_d);
       b->list[count++]    = l;
     }
@@ -771,7 +771,7 @@ int pdlpdev_small_batch_major_eval(pdlpdev_small_batch* b, const pdlpdev_small_e
   HIP_TRY(hipStreamSynchronize(b->stream));
   for (int l = 0; l < b->K; ++l)
     if (req[l].mode >= 0) {
-      const bool want_linf = req[l].eps_p >= 0.0 && req[l].eps_d >= 0.0;
+      const bool want_linf = wants_linf(req[l].eps_p, req[l].eps_d);
       read_eval(b->ctx[l]->scal_h + (b->halpern ? 32 : 0), want_linf, out_current + (size_t)l * PDLPDEV_EV_COUNT);
       read_eval(b->ctx[l]->scal_h + 32, want_linf, out_average + (size_t)l * PDLPDEV_EV_COUNT);
     }

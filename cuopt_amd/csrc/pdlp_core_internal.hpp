@@ -1,5 +1,6 @@
 // What the core's translation units (pdlp_device.hip, pdlp_eval.hip) share beyond the public device ABI: read-backs, the plain products'
-// launch sites, and the element-wise kernels both of them enqueue.  Defined in pdlp_device.hip.
+// launch sites, and the element-wise kernels both of them enqueue.  Defined in pdlp_device.hip.  (Shared with the lockstep batch as well,
+// inline in pdlp_ctx.hpp: attempt_chunk, too_many_rejections, has_guarded_eval, wants_linf.)
 #pragma once
 #include "pdlp_ctx.hpp"
 
@@ -8,6 +9,7 @@
 extern "C" {
 int fetch_scalars(pdlpdev_ctx* ctx, int count);         // scal[0..count) -> scal_h, synchronised
 int fetch_ctl(pdlpdev_ctx* ctx, pdlpdev_ctl* out);      // the control block -> ctl_h (and *out)
+int fetch_ctl_counted(pdlpdev_ctx* ctx, pdlpdev_ctl* out);  // ... as one of the loop's synchronisations (stat_loop_syncs)
 void launch_plain(pdlpdev_ctx* ctx, int transpose, const double* vec, double* out);   // out = A vec / A^T vec in the side's layout
 void launch_at_cur(pdlpdev_ctx* ctx, double* out_override, int use_next);             // A^T y of the current (next) iterate
 // the kernels of pdlpdev_major_eval, nothing read back (pdlp_eval.hip).  guard != 0: for pdlpdev_run_period -- every kernel is empty unless

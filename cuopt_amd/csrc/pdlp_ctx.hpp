@@ -656,6 +656,33 @@ constexpr int kRayCols = 24;  // max homogeneous dual residual, ||rc||_inf, ||dx
 constexpr int kRayMark = 30;  // the accepted-step count the pass ran at, and its reduced-cost rule (0 / 1)
 // the iterate or the control block changed behind the loop's back
 inline void loop_state_touched(pdlpdev_ctx* c) { c->aty_valid = false, c->ctl_h_current = false, c->batch_ctl_fresh = false, c->batch_ray_steps = -1; }
+// Shared by the single loop (pdlp_device.hip) and the lockstep batch (kernels_batch.hip).  The attempts of a round go out in chunks, one
+// graph per chunk size: the largest power of two <= min(remaining, 64)
+inline int attempt_chunk(int remaining)
+{
+  int chunk = 1;
+  while (chunk * 2 <= remaining && chunk < 64) chunk *= 2;
+  return chunk;
+}
+// The rejection rule, on the fresh ctl_h behind a round that started at `before` accepted steps and made `counted` attempts that count.
+// Every rejection shrinks the step size; 64 in a row leave nothing of it: the caller raises the step error (true: k_set_error on its own
+// stream), like the reference's invalid step size, instead of re-enqueueing forever.  Counted across rounds AND calls.
+inline bool too_many_rejections(pdlpdev_ctx* c, int before, int counted)
+{
+  c->rejected_in_a_row = c->ctl_h->steps_taken == before ? c->rejected_in_a_row + counted : 0;
+  if (c->ctl_h->error != 0 || c->rejected_in_a_row < 64) return false;
+  c->rejected_in_a_row = 0;
+  return true;
+}
+// guarded evaluation kernels exist for this context: only the panel kernels know the guard flag, an unfused dense segment's do not
+inline bool has_guarded_eval(const pdlpdev_ctx* c)
+{
+  const bool both_panels   = c->A.layout() == pdlpdev_ctx::MatrixSide::kPanel && c->At.layout() == pdlpdev_ctx::MatrixSide::kPanel;
+  const bool dense_unfused = c->dense.on && !(c->At.fuses_dense() && c->A.fuses_dense());
+  return !c->small_resident && both_panels && !dense_unfused;
+}
+// the l-infinity residuals are wanted: the host driver passes negative relative tolerances otherwise
+inline bool wants_linf(double eps_rel_primal, double eps_rel_dual) { return eps_rel_primal >= 0.0 && eps_rel_dual >= 0.0; }
 
 // A kernel that takes more dynamic LDS than the default limit allows: the attribute is per kernel and device, and set ONCE, under the
 // lock (batch solves create contexts from many threads), the first time the triple (kernel, device, size) comes by.  A kernel's

@@ -567,14 +567,22 @@ __global__ void __launch_bounds__(kBlock) k_slice_ranges(int64_t nnz, const int3
   if ((int)threadIdx.x < world && shi[threadIdx.x] >= 0) atomicMin(&lo[threadIdx.x], slo[threadIdx.x]), atomicMax(&hi[threadIdx.x], shi[threadIdx.x]);
 }
 
+// the columns a rank of a sliced dataflow (rsag, owner-computes) steps: `len` from `cs` on -- equal slices, the last ranks' clipped at n
+struct ColSlice { size_t cs; int len; };
+static ColSlice rank_slice(const pdlpdev_ctx* ctx)
+{
+  const size_t cs = (size_t)ctx->rank * ctx->slice;
+  return {cs, (int)std::max<int64_t>(0, std::min<int64_t>(ctx->slice, (int64_t)ctx->n - (int64_t)cs))};
+}
+
 extern "C" {
 
 int pdlpdev_owner_slice(pdlpdev_ctx* ctx, int32_t* col_begin, int32_t* ncols)
 {
   if (!ctx->owner) return fail(-1, "pdlpdev_owner_slice: the solver does not run the owner-computes dataflow");
-  const int64_t cs = (int64_t)ctx->rank * ctx->slice;
-  *col_begin       = (int32_t)std::min<int64_t>(cs, ctx->n);
-  *ncols           = (int32_t)std::max<int64_t>(0, std::min<int64_t>(ctx->slice, (int64_t)ctx->n - cs));
+  const ColSlice sl = rank_slice(ctx);
+  *col_begin        = (int32_t)std::min<int64_t>((int64_t)sl.cs, ctx->n);
+  *ncols            = sl.len;
   return 0;
 }
 int pdlpdev_shard_slice(pdlpdev_ctx* ctx, int32_t* col_begin, int32_t* ncols)
@@ -713,7 +721,12 @@ int fetch_ctl(pdlpdev_ctx* ctx, pdlpdev_ctl* out)
   if (out) *out = *ctx->ctl_h;
   return 0;
 }
-
+int fetch_ctl_counted(pdlpdev_ctx* ctx, pdlpdev_ctl* out)
+{
+  TRY(fetch_ctl(ctx, out));
+  ctx->stat_loop_syncs += 1;
+  return 0;
+}
 
 static int reduce_vec(pdlpdev_ctx* ctx, int mode, int64_t n, const double* a, const double* b, int slot)
 {
@@ -980,13 +993,19 @@ static unsigned long long* attempt_xmask(const pdlpdev_ctx* ctx)
   if (ctx->A.layout() != pdlpdev_ctx::MatrixSide::kPanel || pn.v.seg) return nullptr;
   return ctx->xmask;
 }
-// the primal step of a single-GPU attempt: with the bitmap where the A product reads it, else the kernel as it always was
+// k_primal on a slice of the columns; push (direct peer transport): xbar of the slice also lands in the peers' blocks
+static void launch_primal_slice(pdlpdev_ctx* ctx, const ColSlice& sl, const p2pdev::Push* push)
+{
+  launch_k(ctx, k_primal, grid_for(sl.len), kBlock, 0, sl.len, ctx->ctl, ctx->x[0] + sl.cs, ctx->x[1] + sl.cs, ctx->aty[0] + sl.cs, ctx->aty[1] + sl.cs, ctx->c + sl.cs,
+           ctx->lb + sl.cs, ctx->ub + sl.cs, ctx->xbar + sl.cs, ctx->sumx + sl.cs, push, ctx->ubd);
+}
+// the primal step of all columns: with the bitmap where the A product reads it (single GPU), else the kernel as it always was
 static void launch_primal(pdlpdev_ctx* ctx)
 {
   const int n = ctx->n;
   if (unsigned long long* xmask = attempt_xmask(ctx))
     return launch_k(ctx, k_primal_zs, grid_for(n), kBlock, 0, n, ctx->ctl, ctx->x[0], ctx->x[1], ctx->aty[0], ctx->aty[1], ctx->c, ctx->lb, ctx->ub, ctx->xbar, ctx->sumx, ctx->ubd, xmask, ctx->zcount);
-  launch_k(ctx, k_primal, grid_for(n), kBlock, 0, n, ctx->ctl, ctx->x[0], ctx->x[1], ctx->aty[0], ctx->aty[1], ctx->c, ctx->lb, ctx->ub, ctx->xbar, ctx->sumx, (const p2pdev::Push*)nullptr, ctx->ubd);
+  launch_primal_slice(ctx, ColSlice{0, n}, nullptr);
 }
 static void launch_a_dual(pdlpdev_ctx* ctx, double* ycopy = nullptr, const p2pdev::Push* push = nullptr)
 {
@@ -1029,9 +1048,9 @@ static void launch_decision(pdlpdev_ctx* ctx)
 }
 
 // owner-computes dataflow: A^T y' of this rank's columns from the gathered y' (complete sums) + the step statistics of the slice
-static void launch_oc_step(pdlpdev_ctx* ctx)
+static void launch_oc_step(pdlpdev_ctx* ctx, const ColSlice& sl)
 {
-  const size_t cs = (size_t)ctx->rank * ctx->slice;
+  const size_t cs = sl.cs;
   double *x0 = ctx->x[0] + cs, *x1 = ctx->x[1] + cs, *t0 = ctx->aty[0] + cs, *t1 = ctx->aty[1] + cs;
   const double* yg = ctx->ygather;  // the trial dual of every rank, whichever ping-pong buffer it lives in
   if (ctx->halpern) {
@@ -1047,112 +1066,127 @@ static void launch_oc_step(pdlpdev_ctx* ctx)
                        std::make_tuple(x0, x1, t0, t1, ctx->Oc.part));
 }
 
-// one PDHG attempt = 4 launches (single GPU) on ctx->stream
-static int enqueue_attempt(pdlpdev_ctx* ctx)
+// k_step_decision on sums a collective has reduced (the same bits on every rank): ||dy||^2 at dy2, the other two as nb_t partials at part_t
+static void launch_decision_reduced(pdlpdev_ctx* ctx, const double* part_t, int nb_t, const double* dy2)
 {
-  const int n = ctx->n;
-  // (Halpern mode: the single-GPU sequence at the end of this function or, behind a communicator, the owner-computes sequence; the
-  //  launch helpers pick the Halpern kernels -- k_primal is the same, pending_avg stays 0.  pdlpdev_set_halpern admits no other dataflow.)
-  if (ctx->halpern && ctx->comm && !ctx->owner) return fail(-7, "reflected Halpern mode: behind a communicator the owner-computes dataflow only");
-  if (ctx->owner) {
-    if (!ctx->Oc.hot.off) return fail(-1, "owner-computes dataflow: pdlpdev_owner_setup was not called");
-    const size_t cs = (size_t)ctx->rank * ctx->slice;
-    const int len   = (int)std::max<int64_t>(0, std::min<int64_t>(ctx->slice, (int64_t)n - (int64_t)cs));
-    launch_k(ctx, k_primal, grid_for(len), kBlock, 0, len, ctx->ctl, ctx->x[0] + cs, ctx->x[1] + cs, ctx->aty[0] + cs, ctx->aty[1] + cs,
-             ctx->c + cs, ctx->lb + cs, ctx->ub + cs, ctx->xbar + cs, ctx->sumx + cs, ctx->p2p.on ? ctx->p2p.push_dev : (const p2pdev::Push*)nullptr, ctx->ubd);
-    LAUNCH_CHECK();
-    if (ctx->p2p.on) {
-      // direct peer stores + epoch flags instead of collectives: the producing kernels (the primal step above, the dual step,
-      // the packing of the step-size sums) store into every rank's landing block and raise this rank's flag from their last
-      // workgroup; a consumer waits for the world flags and copies the landed vector into ordinary memory.  Kernels only,
-      // nothing between them but stream order: 7 launches per attempt.
-      pdlpdev_ctx::P2P& P = ctx->p2p;
-      const int W = ctx->world;
-      const unsigned long long* flags = reinterpret_cast<const unsigned long long*>(P.base + P.off_f);
-      auto pull = [&](int kind, double* dst, size_t land_off, int per_rank) {
-        const int count = W * per_rank, remote = count - per_rank;
-        const int g     = std::max(1, std::min((remote + 4095) / 4096, 1024));
-        launch_k(ctx, p2pdev::k_pull, g, 256, 0, ctx->ctl, dst, reinterpret_cast<const double*>(P.base + land_off), count, ctx->rank * per_rank, per_rank,
-                 flags, W, kind, P.epoch, P.fault, P.push_dev + kind);
-      };
-      // (halo exchange: only the ranges this rank's rows / columns reference were stored into its block, and only they are copied)
-      auto pull_ranges = [&](int kind, double* dst, size_t land_off) {
-        p2pdev::PullRanges R{};
-        int most = 0;
-        for (int q = 0; q < W; ++q) R.off[q] = ctx->halo.recv_off[kind][q], R.cnt[q] = ctx->halo.recv_cnt[kind][q], most = std::max(most, R.cnt[q]);
-        launch_k(ctx, p2pdev::k_pull_ranges, std::max(1, std::min((most + 255) / 256, 64)), 256, 0, ctx->ctl, dst, reinterpret_cast<const double*>(P.base + land_off), R, flags, W,
-                 kind, P.epoch, P.fault, P.push_dev + kind);
-      };
-      if (ctx->halo.on) pull_ranges(0, ctx->xbar, P.off_x);
-      else pull(0, ctx->xbar, P.off_x, ctx->slice);  // (this rank's slice: k_primal's ordinary store, above)
-      launch_a_dual(ctx, ctx->ygather + (size_t)ctx->rank * ctx->ypad, P.push_dev + 1);
-      if (ctx->halo.on) pull_ranges(1, ctx->ygather, P.off_y);
-      else pull(1, ctx->ygather, P.off_y, ctx->ypad);
-      launch_oc_step(ctx);
-      if (ctx->halpern)
-        launch_k(ctx, k_halpern_decision_p2p, 1, kBlock, 0, ctx->ctl, ctx->hal, ctx->A.part, ctx->A.partials(), ctx->Oc.part, ctx->Oc.partials(),
-                 reinterpret_cast<const double*>(P.base + P.off_s), flags, W, P.epoch, P.fault, P.push_dev + 2);
-      else
-      launch_k(ctx, k_step_decision_p2p, 1, kBlock, 0, ctx->ctl, ctx->A.part, ctx->A.partials(), ctx->Oc.part, ctx->Oc.partials(),
-               reinterpret_cast<const double*>(P.base + P.off_s), flags, W, P.epoch, P.fault, ctx->sp, P.push_dev + 2);
-      LAUNCH_CHECK();
-      return 0;
-    }
-    if (ctx->halo.on) TRY(halo_exchange(ctx, 0, ctx->xbar));  // (a structured LP: the ranges the rows reference, from their owners)
-    else TRY(all_gather(ctx, ctx->xbar, (size_t)ctx->slice));
-    launch_a_dual(ctx, ctx->ygather + (size_t)ctx->rank * ctx->ypad);
-    LAUNCH_CHECK();
-    if (ctx->halo.on) TRY(halo_exchange(ctx, 1, ctx->ygather));
-    else TRY(all_gather(ctx, ctx->ygather, (size_t)ctx->ypad));
-    launch_oc_step(ctx);
-    launch_k(ctx, k_pack_step_sums, 1, kBlock, 0, ctx->A.part, ctx->A.partials(), ctx->Oc.part, ctx->Oc.partials(), ctx->rs_scal);
-    LAUNCH_CHECK();
-    TRY(allreduce(ctx, ctx->rs_scal, 3, rccl::kSum));
-    if (ctx->halpern) launch_k(ctx, k_halpern_decision_sums, 1, 1, 0, ctx->ctl, ctx->hal, ctx->rs_scal);
-    else launch_k(ctx, k_step_decision, 1, kDecisionThreads, 0, ctx->ctl, nullptr, 0, ctx->rs_scal + 1, 1, ctx->rs_scal, ctx->sp);
-    LAUNCH_CHECK();
-    return 0;
-  }
-  if (ctx->rsag) {
-    // sliced primal: primal step on this rank's columns -> all-gather(xbar) -> local rows of A -> partial A^T y' ->
-    // reduce-scatter -> this rank's columns of A^T y' and of the step-size sums -> ONE 3-scalar all-reduce -> the same
-    // decision on every rank.  Same wire bytes as the all-reduce of the replicated dataflow, 1/world of its element-wise work.
-    const size_t cs = (size_t)ctx->rank * ctx->slice;
-    const int len   = (int)std::max<int64_t>(0, std::min<int64_t>(ctx->slice, (int64_t)n - (int64_t)cs));
-    launch_k(ctx, k_primal, grid_for(len), kBlock, 0, len, ctx->ctl, ctx->x[0] + cs, ctx->x[1] + cs, ctx->aty[0] + cs, ctx->aty[1] + cs,
-             ctx->c + cs, ctx->lb + cs, ctx->ub + cs, ctx->xbar + cs, ctx->sumx + cs, (const p2pdev::Push*)nullptr, ctx->ubd);
-    LAUNCH_CHECK();
-    TRY(all_gather(ctx, ctx->xbar, (size_t)ctx->slice));
-    launch_a_dual(ctx);
-    launch_at_cur(ctx, ctx->ar_buf, 1);
-    LAUNCH_CHECK();
-    TRY(reduce_scatter(ctx, ctx->ar_buf, ctx->rs_buf, (size_t)ctx->slice));
-    const int g = std::min(grid_for(len), kGenericBlocks);
-    launch_k(ctx, k_step_stats, g, kBlock, 0, len, g, ctx->ctl, ctx->rs_buf, ctx->x[0] + cs, ctx->x[1] + cs, ctx->aty[0] + cs, ctx->aty[1] + cs, ctx->part_g);
-    launch_k(ctx, k_pack_step_sums, 1, kBlock, 0, ctx->A.part, ctx->A.partials(), ctx->part_g, g, ctx->rs_scal);
-    LAUNCH_CHECK();
-    TRY(allreduce(ctx, ctx->rs_scal, 3, rccl::kSum));
-    launch_k(ctx, k_step_decision, 1, kDecisionThreads, 0, ctx->ctl, nullptr, 0, ctx->rs_scal + 1, 1, ctx->rs_scal, ctx->sp);
-    LAUNCH_CHECK();
-    return 0;
-  }
-  launch_primal(ctx);
-  launch_a_dual(ctx);
-  if (!ctx->comm) {
-    launch_at_step(ctx);
-    launch_decision(ctx);
-  } else {
-    // partial A^T y' of this row block -> ar_buf[0..n), ||dy||^2 partial -> ar_buf[n]; ONE all-reduce
-    launch_at_cur(ctx, ctx->ar_buf, 1);
-    launch_k(ctx, k_sum_partials_to, 1, kBlock, 0, ctx->A.part, ctx->A.partials(), ctx->ar_buf + n);
-    LAUNCH_CHECK();
-    TRY(allreduce(ctx, ctx->ar_buf, (size_t)n + 1, rccl::kSum));
-    const int g = std::min(grid_for(n), kGenericBlocks);
-    launch_k(ctx, k_step_stats, g, kBlock, 0, n, g, ctx->ctl, ctx->ar_buf, ctx->x[0], ctx->x[1], ctx->aty[0], ctx->aty[1], ctx->part_g);
-    launch_k(ctx, k_step_decision, 1, kDecisionThreads, 0, ctx->ctl, nullptr, 0, ctx->part_g, g, ctx->ar_buf + n, ctx->sp);
-  }
+  launch_k(ctx, k_step_decision, 1, kDecisionThreads, 0, ctx->ctl, nullptr, 0, part_t, nb_t, dy2, ctx->sp);
+}
+
+// ---- one attempt, per dataflow.  Halpern mode (single GPU and owner-computes only): the launch helpers pick the twins' kernels, k_primal is the
+// same, pending_avg stays 0.  Single GPU: 4 launches, the stages (id: PDLPDEV_K_*) in stream order; pdlpdev_time_kernel walks the same list.
+struct AttemptStage { int id; void (*launch)(pdlpdev_ctx*); };
+static const AttemptStage kSingleStages[4] = {{PDLPDEV_K_PRIMAL, launch_primal}, {PDLPDEV_K_SPMV_A_DUAL, [](pdlpdev_ctx* c) { launch_a_dual(c); }},
+                                              {PDLPDEV_K_SPMV_AT_STEP, launch_at_step}, {PDLPDEV_K_STEP_DECISION, launch_decision}};
+static int enqueue_single(pdlpdev_ctx* ctx)
+{
+  for (const AttemptStage& st : kSingleStages) st.launch(ctx);
   LAUNCH_CHECK();
   return 0;
+}
+// Replicated primal: partial A^T y' of this row block -> ar_buf[0..n), ||dy||^2 partial -> ar_buf[n]; ONE all-reduce.  (Here and below a
+// LAUNCH_CHECK stands in front of every collective: it decides what a failed capture leaves on the stream.)
+static int enqueue_replicated(pdlpdev_ctx* ctx)
+{
+  const int n = ctx->n, g = std::min(grid_for(n), kGenericBlocks);
+  launch_primal(ctx);
+  launch_a_dual(ctx);
+  launch_at_cur(ctx, ctx->ar_buf, 1);
+  launch_k(ctx, k_sum_partials_to, 1, kBlock, 0, ctx->A.part, ctx->A.partials(), ctx->ar_buf + n);
+  LAUNCH_CHECK();
+  TRY(allreduce(ctx, ctx->ar_buf, (size_t)n + 1, rccl::kSum));
+  launch_k(ctx, k_step_stats, g, kBlock, 0, n, g, ctx->ctl, ctx->ar_buf, ctx->x[0], ctx->x[1], ctx->aty[0], ctx->aty[1], ctx->part_g);
+  launch_decision_reduced(ctx, ctx->part_g, g, ctx->ar_buf + n);
+  LAUNCH_CHECK();
+  return 0;
+}
+// Sliced primal (rsag): primal step on this rank's columns -> all-gather(xbar) -> local rows of A -> partial A^T y' ->
+// reduce-scatter -> this rank's columns of A^T y' and of the step-size sums -> ONE 3-scalar all-reduce -> the same
+// decision on every rank.  Same wire bytes as the all-reduce of the replicated dataflow, 1/world of its element-wise work.
+static int enqueue_rsag(pdlpdev_ctx* ctx)
+{
+  const ColSlice sl = rank_slice(ctx);
+  const int g       = std::min(grid_for(sl.len), kGenericBlocks);
+  launch_primal_slice(ctx, sl, nullptr);
+  LAUNCH_CHECK();
+  TRY(all_gather(ctx, ctx->xbar, (size_t)ctx->slice));
+  launch_a_dual(ctx);
+  launch_at_cur(ctx, ctx->ar_buf, 1);
+  LAUNCH_CHECK();
+  TRY(reduce_scatter(ctx, ctx->ar_buf, ctx->rs_buf, (size_t)ctx->slice));
+  launch_k(ctx, k_step_stats, g, kBlock, 0, sl.len, g, ctx->ctl, ctx->rs_buf, ctx->x[0] + sl.cs, ctx->x[1] + sl.cs, ctx->aty[0] + sl.cs, ctx->aty[1] + sl.cs, ctx->part_g);
+  launch_k(ctx, k_pack_step_sums, 1, kBlock, 0, ctx->A.part, ctx->A.partials(), ctx->part_g, g, ctx->rs_scal);
+  LAUNCH_CHECK();
+  TRY(allreduce(ctx, ctx->rs_scal, 3, rccl::kSum));
+  launch_decision_reduced(ctx, ctx->rs_scal + 1, 1, ctx->rs_scal);
+  LAUNCH_CHECK();
+  return 0;
+}
+// Owner-computes over collectives: xbar and y' travel whole or, on a structured LP, as the ranges the rows / columns reference (halo exchange)
+static int enqueue_owner_collective(pdlpdev_ctx* ctx)
+{
+  const ColSlice sl = rank_slice(ctx);
+  launch_primal_slice(ctx, sl, nullptr);
+  LAUNCH_CHECK();
+  TRY(ctx->halo.on ? halo_exchange(ctx, 0, ctx->xbar) : all_gather(ctx, ctx->xbar, (size_t)ctx->slice));
+  launch_a_dual(ctx, ctx->ygather + (size_t)ctx->rank * ctx->ypad);
+  LAUNCH_CHECK();
+  TRY(ctx->halo.on ? halo_exchange(ctx, 1, ctx->ygather) : all_gather(ctx, ctx->ygather, (size_t)ctx->ypad));
+  launch_oc_step(ctx, sl);
+  launch_k(ctx, k_pack_step_sums, 1, kBlock, 0, ctx->A.part, ctx->A.partials(), ctx->Oc.part, ctx->Oc.partials(), ctx->rs_scal);
+  LAUNCH_CHECK();
+  TRY(allreduce(ctx, ctx->rs_scal, 3, rccl::kSum));
+  if (ctx->halpern) launch_k(ctx, k_halpern_decision_sums, 1, 1, 0, ctx->ctl, ctx->hal, ctx->rs_scal);
+  else launch_decision_reduced(ctx, ctx->rs_scal + 1, 1, ctx->rs_scal);
+  LAUNCH_CHECK();
+  return 0;
+}
+// Owner-computes over the direct peer transport: peer stores + epoch flags instead of collectives.  The producing kernels (primal step, dual
+// step, decision with its step-size sums) store into every rank's landing block and raise this rank's flag from their last workgroup; a
+// consumer waits for the world flags and copies the landed vector into ordinary memory.  Six launches, nothing between them but stream order.
+static const unsigned long long* p2p_flags(const pdlpdev_ctx::P2P& P) { return reinterpret_cast<const unsigned long long*>(P.base + P.off_f); }
+// what landed of kind 0 (xbar) / 1 (the gathered y') -> dst: the other ranks' per_rank entries or, with the halo exchange, the stored ranges only
+static void p2p_pull(pdlpdev_ctx* ctx, int kind, double* dst, size_t land_off, int per_rank)
+{
+  pdlpdev_ctx::P2P& P = ctx->p2p;
+  const double* land  = reinterpret_cast<const double*>(P.base + land_off);
+  if (ctx->halo.on) {
+    p2pdev::PullRanges R{};
+    int most = 0;
+    for (int q = 0; q < ctx->world; ++q) R.off[q] = ctx->halo.recv_off[kind][q], R.cnt[q] = ctx->halo.recv_cnt[kind][q], most = std::max(most, R.cnt[q]);
+    return launch_k(ctx, p2pdev::k_pull_ranges, std::max(1, std::min((most + 255) / 256, 64)), 256, 0, ctx->ctl, dst, land, R, p2p_flags(P), ctx->world, kind, P.epoch,
+                    P.fault, P.push_dev + kind);
+  }
+  const int count = ctx->world * per_rank, remote = count - per_rank;  // (this rank's own entries: the producing kernel's ordinary store)
+  const int g     = std::max(1, std::min((remote + 4095) / 4096, 1024));
+  launch_k(ctx, p2pdev::k_pull, g, 256, 0, ctx->ctl, dst, land, count, ctx->rank * per_rank, per_rank, p2p_flags(P), ctx->world, kind, P.epoch, P.fault, P.push_dev + kind);
+}
+static int enqueue_owner_p2p(pdlpdev_ctx* ctx)
+{
+  pdlpdev_ctx::P2P& P = ctx->p2p;
+  const ColSlice sl   = rank_slice(ctx);
+  const double* sums  = reinterpret_cast<const double*>(P.base + P.off_s);
+  launch_primal_slice(ctx, sl, P.push_dev);
+  LAUNCH_CHECK();
+  p2p_pull(ctx, 0, ctx->xbar, P.off_x, ctx->slice);
+  launch_a_dual(ctx, ctx->ygather + (size_t)ctx->rank * ctx->ypad, P.push_dev + 1);
+  p2p_pull(ctx, 1, ctx->ygather, P.off_y, ctx->ypad);
+  launch_oc_step(ctx, sl);
+  if (ctx->halpern) launch_k(ctx, k_halpern_decision_p2p, 1, kBlock, 0, ctx->ctl, ctx->hal, ctx->A.part, ctx->A.partials(), ctx->Oc.part, ctx->Oc.partials(), sums, p2p_flags(P),
+                             ctx->world, P.epoch, P.fault, P.push_dev + 2);
+  else launch_k(ctx, k_step_decision_p2p, 1, kBlock, 0, ctx->ctl, ctx->A.part, ctx->A.partials(), ctx->Oc.part, ctx->Oc.partials(), sums, p2p_flags(P), ctx->world, P.epoch,
+                P.fault, ctx->sp, P.push_dev + 2);
+  LAUNCH_CHECK();
+  return 0;
+}
+
+// one PDHG attempt on ctx->stream: the sequence of the context's dataflow
+static int enqueue_attempt(pdlpdev_ctx* ctx)
+{
+  if (ctx->halpern && ctx->comm && !ctx->owner) return fail(-7, "reflected Halpern mode: behind a communicator the owner-computes dataflow only");
+  if (ctx->owner && !ctx->Oc.hot.off) return fail(-1, "owner-computes dataflow: pdlpdev_owner_setup was not called");
+  if (ctx->owner) return ctx->p2p.on ? enqueue_owner_p2p(ctx) : enqueue_owner_collective(ctx);
+  if (ctx->rsag) return enqueue_rsag(ctx);
+  return ctx->comm ? enqueue_replicated(ctx) : enqueue_single(ctx);
 }
 
 static int get_graph(pdlpdev_ctx* ctx, int attempts, hipGraphExec_t* out)
@@ -1198,8 +1232,7 @@ static int enqueue_attempts(pdlpdev_ctx* ctx, int remaining)
   if (ctx->use_graph && (!ctx->comm || ctx->p2p.on || rccl_graphs)) {
     replayed = true;
     while (remaining > 0) {
-      int chunk = 1;
-      while (chunk * 2 <= remaining && chunk < 64) chunk *= 2;
+      const int chunk = attempt_chunk(remaining);
       hipGraphExec_t g;
       const int grc = get_graph(ctx, chunk, &g);
       if (grc != 0 && rccl_graphs) {  // (nothing of this chunk was enqueued: a failed capture leaves the stream empty)
@@ -1219,32 +1252,38 @@ static int enqueue_attempts(pdlpdev_ctx* ctx, int remaining)
   return 0;
 }
 
-// what a round of attempts left, read from the fresh ctl_h: `before` accepted steps and `attempts_before` attempts existed in front of it
-static int after_round(pdlpdev_ctx* ctx, int before, int attempts_before, int enqueued, int counted /* towards the 64-in-a-row rule */)
+// what `enqueued` attempts behind `before` accepted steps and `attempts_before` attempts left, from the fresh ctl_h (a Halpern burst asks too)
+static void note_attempts(pdlpdev_ctx* ctx, int before, int attempts_before, int enqueued)
 {
   const pdlpdev_ctl& c = *ctx->ctl_h;
   const int made       = c.attempts - attempts_before;  // an attempt that found the target reached (or an error raised) did nothing
   if (!ctx->comm) ctx->stat_empty_attempts += enqueued - made;
   if (c.steps_taken > before && c.error == 0 && !ctx->comm) ctx->aty_valid = true;  // k_*_at_step stored A^T y' and the decision flipped to it
   if (c.error != 0) ctx->aty_valid = false;
-  if (ctx->p2p.on && c.error != 0) {  // a wait of the direct peer transport ran out of patience: a peer is gone
+}
+static int after_round(pdlpdev_ctx* ctx, int before, int attempts_before, int enqueued, int counted /* towards the 64-in-a-row rule */)
+{
+  note_attempts(ctx, before, attempts_before, enqueued);
+  if (ctx->p2p.on && ctx->ctl_h->error != 0) {  // a wait of the direct peer transport ran out of patience: a peer is gone
     int fault = 0;
     HIP_TRY(hipMemcpy(&fault, ctx->p2p.fault, sizeof(int), hipMemcpyDeviceToHost));
     if (fault) return fail(-6, "direct peer transport: rank %d waited 5 s for another rank's data (a peer failed or is stuck)", ctx->rank);
   }
-  // every rejection shrinks the step size; 64 in a row leave nothing of it: report it like the reference's invalid step
-  // size instead of re-enqueueing forever.  Counted across rounds AND calls (a call asks for at most one major-iteration
-  // period: 40 steps under Stable2, fewer than 64).  A round without an accepted step consists of real attempts only.
-  ctx->rejected_in_a_row = c.steps_taken == before ? ctx->rejected_in_a_row + counted : 0;
-  if (c.error == 0 && ctx->rejected_in_a_row >= 64) {
-    ctx->rejected_in_a_row = 0;
+  if (too_many_rejections(ctx, before, counted)) {
     k_set_error<<<1, 1, 0, ctx->stream>>>(ctx->ctl);
     LAUNCH_CHECK();
-    TRY(fetch_ctl(ctx, nullptr));
-    ctx->stat_loop_syncs += 1;
+    TRY(fetch_ctl_counted(ctx, nullptr));
     ctx->aty_valid = false;
   }
   return 0;
+}
+// one round: `enqueue` attempts, ONE counted read-back of the control block, after_round; ctl_h is current on entry and on return
+static int run_round(pdlpdev_ctx* ctx, int attempts_before, int enqueue, int counted)
+{
+  const int before = ctx->ctl_h->steps_taken;
+  TRY(enqueue_attempts(ctx, enqueue));
+  TRY(fetch_ctl_counted(ctx, nullptr));
+  return after_round(ctx, before, attempts_before, enqueue, counted);
 }
 
 // rounds of attempts until the target is reached or the error flag is up; ctl_h is current on entry and on return
@@ -1254,11 +1293,8 @@ static int run_rounds(pdlpdev_ctx* ctx, int32_t target_steps, int* rounds)
   // attempts are made up for in the next round (one control-block read per round, not per step).
   int guard = 0;
   while (ctx->ctl_h->error == 0 && ctx->ctl_h->steps_taken < target_steps) {
-    const int before = ctx->ctl_h->steps_taken, attempts_before = ctx->ctl_h->attempts, asked = target_steps - before;
-    TRY(enqueue_attempts(ctx, asked));
-    TRY(fetch_ctl(ctx, nullptr));
-    ctx->stat_loop_syncs += 1;
-    TRY(after_round(ctx, before, attempts_before, asked, asked));
+    const int asked = target_steps - ctx->ctl_h->steps_taken;
+    TRY(run_round(ctx, ctx->ctl_h->attempts, asked, asked));
     if (++guard > 100000) return fail(-6, "pdlpdev_run: no progress");
   }
   if (rounds) *rounds += guard;
@@ -1294,9 +1330,7 @@ static int set_target(pdlpdev_ctx* ctx, int32_t target_steps)
     ctx->ctl_h->target_steps = target_steps;
     return 0;
   }
-  TRY(fetch_ctl(ctx, nullptr));
-  ctx->stat_loop_syncs += 1;
-  return 0;
+  return fetch_ctl_counted(ctx, nullptr);
 }
 
 int pdlpdev_run(pdlpdev_ctx* ctx, int32_t target_steps, pdlpdev_ctl* ctl)
@@ -1325,21 +1359,16 @@ int pdlpdev_debug_attempts(pdlpdev_ctx* ctx, int count, pdlpdev_ctl* ctl)
   const bool resident = ctx->small_resident && !ctx->comm && !ctx->halpern;
   if (ctx->halpern) return fail(-7, "pdlpdev_debug_attempts: the averaging attempt only, multi-launch, sharded or resident (not Halpern mode)");
   if (count < 1 || count > 64) return fail(-1, "pdlpdev_debug_attempts: count must be 1 .. 64");
+  TRY(fetch_ctl(ctx, nullptr));  // (not one of the loop's synchronisations: the hook's own)
   if (resident) {
-    TRY(fetch_ctl(ctx, nullptr));
     TRY(resident_attempts(ctx, count));
     if (ctl) *ctl = *ctx->ctl_h;
     return 0;
   }
-  TRY(fetch_ctl(ctx, nullptr));
-  const int before = ctx->ctl_h->steps_taken, attempts_before = ctx->ctl_h->attempts;
-  TRY(set_target(ctx, before + count));
+  TRY(set_target(ctx, ctx->ctl_h->steps_taken + count));
   int rounds = 0;
   if (ctx->ctl_h->error == 0) {  // (all-reduced scalars decide the error: every rank of a sharded context sees the same)
-    TRY(enqueue_attempts(ctx, count));
-    TRY(fetch_ctl(ctx, nullptr));
-    ctx->stat_loop_syncs += 1;
-    TRY(after_round(ctx, before, attempts_before, count, count));
+    TRY(run_round(ctx, ctx->ctl_h->attempts, count, count));
     rounds = 1;
   }
   return run_epilogue(ctx, rounds, ctl);
@@ -1365,7 +1394,7 @@ int pdlpdev_run_period(pdlpdev_ctx* ctx, int32_t target_steps, const pdlpdev_sma
     // the resident Halpern loop: the loop kernel with its target, the one-workgroup evaluation of T(z^k) right behind it (it computes
     // the l-infinity residuals itself, so that request stays on this path), one synchronisation for both
     roctx::Range range("pdlp: Halpern steps + evaluation (resident)");
-    const bool want_linf = rq->eps_p >= 0.0 && rq->eps_d >= 0.0;
+    const bool want_linf = wants_linf(rq->eps_p, rq->eps_d);
     TRY(resident_halpern_period(ctx, target_steps, rq->rule_finite, want_linf ? 1 : 0, rq->eps_p, rq->eps_d, evaluated));
     if (*evaluated) {
       read_eval(ctx->scal_h + 32, want_linf, out_current);
@@ -1374,10 +1403,8 @@ int pdlpdev_run_period(pdlpdev_ctx* ctx, int32_t target_steps, const pdlpdev_sma
     if (ctl) *ctl = *ctx->ctl_h;
     return 0;
   }
-  const bool both_panels   = ctx->A.layout() == pdlpdev_ctx::MatrixSide::kPanel && ctx->At.layout() == pdlpdev_ctx::MatrixSide::kPanel;
-  const bool dense_unfused = ctx->dense.on && !(ctx->At.fuses_dense() && ctx->A.fuses_dense());
-  const bool eligible = !ctx->comm && !ctx->small_resident && both_panels && !dense_unfused && ctx->ctl_h_current &&
-                        !(rq->eps_p >= 0.0 && rq->eps_d >= 0.0) && ctx->ctl_h->error == 0 && ctx->ctl_h->steps_taken < target_steps;
+  const bool eligible = !ctx->comm && has_guarded_eval(ctx) && ctx->ctl_h_current && !wants_linf(rq->eps_p, rq->eps_d) && ctx->ctl_h->error == 0 &&
+                        ctx->ctl_h->steps_taken < target_steps;
   if (!eligible) return pdlpdev_run(ctx, target_steps, ctl);
   roctx::Range range("pdlp: PDHG attempts + major iteration evaluation");
   TRY(set_target(ctx, target_steps));
@@ -1409,10 +1436,7 @@ int pdlpdev_run_period(pdlpdev_ctx* ctx, int32_t target_steps, const pdlpdev_sma
     if (ctx->ctl_h->error == 0 && ctx->ctl_h->steps_taken == before && spare > 0 && spare < asked) {
       // nothing was accepted: the spare attempts were the first ones of the make-up round pdlpdev_run would enqueue now; the rest of
       // that round follows, so that the 64-in-a-row rule sees the rounds -- and stops after the number of attempts -- it always did
-      TRY(enqueue_attempts(ctx, asked - spare));
-      TRY(fetch_ctl(ctx, nullptr));
-      ctx->stat_loop_syncs += 1;
-      TRY(after_round(ctx, before, attempts_before + asked + spare, asked - spare, asked));
+      TRY(run_round(ctx, attempts_before + asked + spare, asked - spare, asked));
       rounds += 1;
     }
     TRY(run_rounds(ctx, target_steps, &rounds));
@@ -1430,17 +1454,11 @@ int pdlpdev_set_halpern_device_major(pdlpdev_ctx* ctx, int on)
   if (!ctx->hmaj_ring) HIP_TRY(hipHostMalloc((void**)&ctx->hmaj_ring, 16 * sizeof(pdlpdev_halpern_major_record)));
   return 0;
 }
-static bool burst_panels(const pdlpdev_ctx* ctx)  // (pdlpdev_run_period's layouts: the guarded evaluation exists for them)
-{
-  const bool both_panels   = ctx->A.layout() == pdlpdev_ctx::MatrixSide::kPanel && ctx->At.layout() == pdlpdev_ctx::MatrixSide::kPanel;
-  const bool dense_unfused = ctx->dense.on && !(ctx->At.fuses_dense() && ctx->A.fuses_dense());
-  return !ctx->small_resident && both_panels && !dense_unfused;
-}
 int pdlpdev_halpern_burst_eligible(pdlpdev_ctx* ctx, const pdlpdev_small_eval* rq)
 {
   if (!ctx->halpern || ctx->comm || ctx->halpern_rays) return 0;
   if (ctx->small_resident) return 1;
-  return burst_panels(ctx) && !(rq->eps_p >= 0.0 && rq->eps_d >= 0.0) ? 1 : 0;
+  return has_guarded_eval(ctx) && !wants_linf(rq->eps_p, rq->eps_d) ? 1 : 0;
 }
 int pdlpdev_halpern_burst_stats(pdlpdev_ctx* ctx, int64_t out[4])
 {
@@ -1461,14 +1479,12 @@ int pdlpdev_run_halpern_burst(pdlpdev_ctx* ctx, int32_t first_target, int32_t pe
   if (!ctx->hmaj || !ctx->hmaj_ring) return fail(-7, "pdlpdev_run_halpern_burst: call pdlpdev_set_halpern_device_major first");
   if (!pdlpdev_halpern_burst_eligible(ctx, rq)) return fail(-7, "pdlpdev_run_halpern_burst: the context has no burst (the resident Halpern loop, or panels on both sides without an l-infinity request)");
   const bool resident = ctx->small_resident;
-  if (!ctx->ctl_h_current) {  // (something moved the control block behind the loop's back -- a cleared step error: read it, as set_target does)
-    TRY(fetch_ctl(ctx, nullptr));
-    ctx->stat_loop_syncs += 1;
-  }
+  // (something moved the control block behind the loop's back -- a cleared step error: read it, as set_target does)
+  if (!ctx->ctl_h_current) TRY(fetch_ctl_counted(ctx, nullptr));
   const int before = ctx->ctl_h->steps_taken, attempts_before = ctx->ctl_h->attempts;
   if (ctx->ctl_h->error != 0 || before >= first_target || first_target - before > period || (resident && period > (1 << 14)))
     return fail(-7, "pdlpdev_run_halpern_burst: the first period must start inside (step error down, target ahead, at most one period away)");
-  const bool want_linf = rq->eps_p >= 0.0 && rq->eps_d >= 0.0;
+  const bool want_linf = wants_linf(rq->eps_p, rq->eps_d);
   pdlpdev_halpern_major_params p = *params;
   p.want_linf = want_linf ? 1 : 0;
   for (int j = 0; j < count; ++j) ctx->hmaj_ring[j].steps_taken = -1;  // ("not written": a decision leaves its step count here)
@@ -1516,11 +1532,8 @@ int pdlpdev_run_halpern_burst(pdlpdev_ctx* ctx, int32_t first_target, int32_t pe
   *written = n_written;
   if (r_prev_out) *r_prev_out = r_prev;
   if (!resident) {
-    const pdlpdev_ctl& c = *ctx->ctl_h;
-    ctx->stat_empty_attempts += enqueued - (c.attempts - attempts_before);
-    if (c.steps_taken > before && c.error == 0) ctx->aty_valid = true;  // (after_round's bookkeeping: k_*_at_halpern stored A^T y of z^{k+1})
-    if (c.error != 0) ctx->aty_valid = false;
-    ctx->rejected_in_a_row = 0;  // (a Halpern step never fails)
+    note_attempts(ctx, before, attempts_before, enqueued);  // (k_*_at_halpern stored A^T y of z^{k+1})
+    ctx->rejected_in_a_row = 0;                             // (a Halpern step never fails)
   }
   if (ctl) *ctl = *ctx->ctl_h;
   return 0;
@@ -1841,8 +1854,7 @@ int pdlpdev_halpern_restart(pdlpdev_ctx* ctx, double theta, double dist[2], pdlp
   k_halpern_restart_ctl<<<1, 1, 0, s>>>(ctx->ctl, ctx->hal, ctx->scal, theta);
   LAUNCH_CHECK();
   HIP_TRY(hipMemcpyAsync(ctx->scal_h, ctx->scal, 2 * sizeof(double), hipMemcpyDeviceToHost, s));
-  TRY(fetch_ctl(ctx, ctl));  // (the weight changed on the device; aty[cur] is untouched, so aty_valid keeps its value)
-  ctx->stat_loop_syncs += 1;
+  TRY(fetch_ctl_counted(ctx, ctl));  // (the weight changed on the device; aty[cur] is untouched, so aty_valid keeps its value)
   if (dist) dist[0] = ctx->scal_h[0], dist[1] = ctx->scal_h[1];
   return 0;
 }
@@ -1868,6 +1880,8 @@ int pdlpdev_time_kernel(pdlpdev_ctx* ctx, int kernel_id, int reps, double* avg_m
   HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
   if (reps < 1) reps = 1;
+  const bool loop_kernel = kernel_id == PDLPDEV_K_PRIMAL || kernel_id == PDLPDEV_K_SPMV_A_DUAL || kernel_id == PDLPDEV_K_SPMV_AT_STEP || kernel_id == PDLPDEV_K_STEP_DECISION;
+  if (!loop_kernel && kernel_id != PDLPDEV_K_SPMV_A_PLAIN && kernel_id != PDLPDEV_K_SPMV_AT_PLAIN) return fail(-1, "pdlpdev_time_kernel: unknown kernel %d", kernel_id);
   // save what the timed launches may touch: control block and the running sums
   TRY(fetch_ctl(ctx, nullptr));
   loop_state_touched(ctx);  // (forced attempts run on the solver's own buffers)
@@ -1889,48 +1903,24 @@ int pdlpdev_time_kernel(pdlpdev_ctx* ctx, int kernel_id, int reps, double* avg_m
   HIP_TRY(hipMemcpyAsync(ctx->ctl, &forced, sizeof(forced), hipMemcpyHostToDevice, s));
   HIP_TRY(hipStreamSynchronize(s));
   for (hipEvent_t& e : ctx->prof_ev) HIP_TRY(hipEventCreate(&e));
-  auto one = [&]() {
-    switch (kernel_id) {
-      case PDLPDEV_K_PRIMAL:
-        launch_primal(ctx);
-        break;
-      case PDLPDEV_K_SPMV_A_DUAL: launch_a_dual(ctx); break;
-      case PDLPDEV_K_SPMV_AT_STEP: launch_at_step(ctx); break;
-      case PDLPDEV_K_STEP_DECISION: launch_decision(ctx); break;
-      case PDLPDEV_K_SPMV_A_PLAIN:
-        launch_plain(ctx, 0, ctx->xbar, ctx->tmp_m);
-        break;
-      case PDLPDEV_K_SPMV_AT_PLAIN:
-        launch_plain(ctx, 1, ctx->y[saved.cur], ctx->tmp_n);
-        break;
-      default: return fail(-1, "pdlpdev_time_kernel: unknown kernel %d", kernel_id);
-    }
-    return 0;
-  };
   // The kernels of an attempt evict each other's streams from L2 and the 256 MiB Infinity Cache; timing one of them
   // in a tight loop of its own would let its matrix sit in those caches and flatter it.  So every repetition enqueues
-  // the whole attempt in the solver's order and brackets only the kernel of interest with events.
-  const bool loop_kernel = kernel_id == PDLPDEV_K_PRIMAL || kernel_id == PDLPDEV_K_SPMV_A_DUAL ||
-                           kernel_id == PDLPDEV_K_SPMV_AT_STEP || kernel_id == PDLPDEV_K_STEP_DECISION;
+  // the whole single-GPU attempt, stage by stage as the solver does, and brackets only the kernel of interest with events.
+  // a plain SpMV takes the place of its fused twin
+  const int slot = loop_kernel ? kernel_id : (kernel_id == PDLPDEV_K_SPMV_A_PLAIN ? PDLPDEV_K_SPMV_A_DUAL : PDLPDEV_K_SPMV_AT_STEP);
   auto attempt = [&](bool timed) -> int {
-    const int order[4] = {PDLPDEV_K_PRIMAL, PDLPDEV_K_SPMV_A_DUAL, PDLPDEV_K_SPMV_AT_STEP, PDLPDEV_K_STEP_DECISION};
-    const int wanted   = kernel_id;
-    // a plain SpMV takes the place of its fused twin
-    const int slot = loop_kernel ? wanted : (wanted == PDLPDEV_K_SPMV_A_PLAIN ? PDLPDEV_K_SPMV_A_DUAL : PDLPDEV_K_SPMV_AT_STEP);
-    int rc = 0;
-    for (int id : order) {
-      const bool mine = id == slot;
-      kernel_id       = mine ? wanted : id;
+    for (const AttemptStage& st : kSingleStages) {
+      const bool mine = st.id == slot;
       ctx->prof_armed = mine && timed;
       if (ctx->prof_armed) ctx->prof_used = 0;
-      rc              = one();
+      if (!mine || loop_kernel) st.launch(ctx);
+      else if (kernel_id == PDLPDEV_K_SPMV_A_PLAIN) launch_plain(ctx, 0, ctx->xbar, ctx->tmp_m);
+      else launch_plain(ctx, 1, ctx->y[saved.cur], ctx->tmp_n);
       ctx->prof_armed = false;
-      if (rc != 0) break;
-      if (id == PDLPDEV_K_STEP_DECISION)  // the decision ended the forced step: arm the next repetition
+      if (st.id == PDLPDEV_K_STEP_DECISION)  // the decision ended the forced step: arm the next repetition
         HIP_TRY(hipMemcpyAsync(ctx->ctl, &forced, sizeof(forced), hipMemcpyHostToDevice, s));
     }
-    kernel_id = wanted;
-    return rc;
+    return 0;
   };
   TRY(attempt(false));  // warm
   float ms = 0.f;

@@ -397,7 +397,7 @@ static int enqueue_eval(pdlpdev_ctx* ctx, int which, int rc_rule_finite_bounds, 
   const int kwg      = kw | (guard ? kPeriodGuard : 0);  // (only the panel kernels know the flag: guarded_eval_layouts turned every other layout away)
   // the per-constraint (l-infinity) residuals are only consumed when per_constraint_residual is set: the host
   // driver passes negative eps_rel otherwise and the two extra vectors + four reduction launches are skipped
-  const bool want_linf = eps_rel_primal >= 0.0 && eps_rel_dual >= 0.0;
+  const bool want_linf = wants_linf(eps_rel_primal, eps_rel_dual);
   double* linf_m = want_linf ? ctx->tmp_m : nullptr;
   double* linf_n = want_linf ? ctx->tmp_n : nullptr;
   // layout of sc: [0..2] primal sums, [3] primal linf, [4..7] dual sums, [8] dual linf
@@ -455,7 +455,7 @@ int pdlpdev_eval(pdlpdev_ctx* ctx, int which, int rc_rule_finite_bounds, double 
   HIP_TRY(hipSetDevice(ctx->device));
   TRY(enqueue_eval(ctx, which, rc_rule_finite_bounds, eps_rel_primal, eps_rel_dual, ctx->scal));
   TRY(fetch_scalars(ctx, 9));
-  read_eval(ctx->scal_h, eps_rel_primal >= 0.0 && eps_rel_dual >= 0.0, out);
+  read_eval(ctx->scal_h, wants_linf(eps_rel_primal, eps_rel_dual), out);
   return 0;
 }
 
@@ -467,7 +467,7 @@ int pdlpdev_major_eval(pdlpdev_ctx* ctx, int average_mode, int rc_rule_finite_bo
 {
   roctx::Range range("pdlp: major iteration evaluation (averages + convergence information)");
   HIP_TRY(hipSetDevice(ctx->device));
-  const bool want_linf = eps_rel_primal >= 0.0 && eps_rel_dual >= 0.0;
+  const bool want_linf = wants_linf(eps_rel_primal, eps_rel_dual);
   if (ctx->halpern) {
     // one point to evaluate: T(z^k) of the last step, which the step kernels left in the average slots (no sums, no average to form)
     if (ctx->small_resident && !ctx->comm) {  // (one workgroup, results straight into the pinned block)
@@ -496,11 +496,10 @@ int pdlpdev_major_eval(pdlpdev_ctx* ctx, int average_mode, int rc_rule_finite_bo
   read_eval(ctx->scal_h + 32, want_linf, out_average);
   return 0;
 }
-// the guard travels inside `which`, and only the panel kernels know the flag (pdlpdev_run_period asks for it on panel contexts alone)
+// the guard travels inside `which`, and only the kernels has_guarded_eval speaks for know the flag (pdlpdev_run_period and the burst ask it first)
 static int guarded_eval_layouts(const pdlpdev_ctx* ctx, int guard, const char* who)
 {
-  const auto panel = pdlpdev_ctx::MatrixSide::kPanel;
-  if (guard && !(ctx->A.layout() == panel && ctx->At.layout() == panel)) return fail(-1, "%s: a guarded evaluation needs slab-major panels on both sides", who);
+  if (guard && !has_guarded_eval(ctx)) return fail(-1, "%s: a guarded evaluation needs slab-major panels on both sides (dense segments fused, not the resident loop)", who);
   return 0;
 }
 int enqueue_major_eval(pdlpdev_ctx* ctx, int average_mode, int rc_rule_finite_bounds, double eps_rel_primal, double eps_rel_dual, int guard)
@@ -611,10 +610,7 @@ int pdlpdev_halpern_eval_infeasibility(pdlpdev_ctx* ctx, int rc_rule_finite_boun
 {
   HIP_TRY(hipSetDevice(ctx->device));
   if (!ctx->halpern) return fail(-7, "pdlpdev_halpern_eval_infeasibility: the context is not in Halpern mode");
-  if (!ctx->ctl_h_current) {
-    TRY(fetch_ctl(ctx, nullptr));
-    ctx->stat_loop_syncs += 1;
-  }
+  if (!ctx->ctl_h_current) TRY(fetch_ctl_counted(ctx, nullptr));
   const int steps = ctx->ctl_h->steps_taken;
   if (steps < 1) return fail(-7, "pdlpdev_halpern_eval_infeasibility: no step has been taken: there is no displacement yet");
   const double rule = rc_rule_finite_bounds != 0 ? 1.0 : 0.0;

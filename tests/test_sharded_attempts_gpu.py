@@ -3,11 +3,13 @@
 
 W ranks -- host threads with a solver each, on one device behind the in-process communicator -- sit behind the scenario's interface
 (tests/sharded_ranks.py); tests/attempt_scenario.run_scenario and attempt_reference.check_attempt run unchanged on what the ranks'
-buffers assemble to.  This reaches what no single-GPU test does (cuopt_amd/csrc/pdlp_device.hip enqueue_attempt): k_primal on a column
-slice with a short or empty last slice, the partial A^T product with the dy2 partial behind it, k_sum_partials_to, k_step_stats,
-k_pack_step_sums, k_step_decision fed with all-reduced scalars, the owner-computes column block (its own layout, its own scaling
-order), the gathered dual at ypad strides, the direct peer transport's k_pull / k_pull_ranges / k_step_decision_p2p, the three
-all-gathers of run_epilogue -- and, for the evaluation, k_eval_dual_elementwise behind the n + 3 all-reduce.  No bound is wider than
+buffers assemble to.  This reaches what no single-GPU test does, the four sharded sequences that enqueue_attempt chooses among
+(cuopt_amd/csrc/pdlp_device.hip enqueue_replicated, enqueue_rsag, enqueue_owner_collective, enqueue_owner_p2p): k_primal on a column
+slice with a short or empty last slice (launch_primal_slice), the partial A^T product with the dy2 partial behind it,
+k_sum_partials_to, k_step_stats, k_pack_step_sums, k_step_decision fed with all-reduced scalars (launch_decision_reduced), the
+owner-computes column block (its own layout, its own scaling order), the gathered dual at ypad strides, the direct peer transport's
+k_pull / k_pull_ranges (p2p_pull) / k_step_decision_p2p, the three all-gathers of run_epilogue -- and, for the evaluation,
+k_eval_dual_elementwise behind the n + 3 all-reduce.  No bound is wider than
 the single-GPU tests' (attempt_reference's docstring, "THE SHARDED PATH", says why none needs to be).
 
 The 6000 x 6000 LP's row blocks (capi.partition_rows) and slices, asserted in tests/test_attempt_reference.py:
