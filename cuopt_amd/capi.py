@@ -464,6 +464,12 @@ if hasattr(lib, "pdlpdev_run_halpern_burst"):  # (... or no device-decided major
     _proto("pdlpdev_halpern_burst_stats", c_int, c_void_p, c_void_p)
     _proto("pdlpdev_debug_halpern_major_decide", c_int, c_int, c_void_p, c_void_p, P(Halpern), c_double, c_int, c_int, P(HalpernMajorParams),
            P(HalpernMajorRecord), P(c_double), P(c_int), P(c_int))
+if hasattr(lib, "cuoptamd_batch_set_halpern_device_major"):  # (... or no device-decided major iterations for the K-workgroup batch)
+    _proto("cuoptamd_batch_set_halpern_device_major", c_int, c_void_p, c_int)
+    _proto("cuoptamd_batch_halpern_device_major", c_int, c_void_p)
+    _proto("cuoptamd_batch_halpern_burst_stats", c_int, c_void_p, c_void_p)
+    _proto("pdlpdev_debug_halpern_major_decide_batch", c_int, c_int, c_int, c_void_p, P(Ctl), P(Halpern), c_void_p, c_void_p, c_void_p,
+           P(HalpernMajorParams), P(HalpernMajorRecord), c_void_p, c_void_p, c_void_p)
 PDLP_SOLVER_MODE_HALPERN1 = 4  # CUOPT_AMD_PDLP_SOLVER_MODE_HALPERN1 (cuopt_c_ext.h)
 
 # ids of pdlp_device.h
@@ -1036,6 +1042,27 @@ class SharedMatrixBatch:
             raise CuOptError(rc, lib.cuoptamd_last_error().decode())
         return dict(zip(("halpern", "tiers", "loop_launches", "eval_launches", "periods", "restart_rounds", "resets", "syncs"), out.tolist()))
 
+    def set_halpern_device_major(self, P):
+        """cuoptamd_batch_set_halpern_device_major: a K-workgroup Halpern batch advances in bursts of up to P (1 .. 16) whole periods, every
+        member's verdict and restart decided on the device, one synchronisation per burst; 0: the host-decided round.  CuOptError(-1) for P
+        outside 0 .. 16, CuOptError(-7) for any other batch and for members with halpern_infeasibility or an enabled acceptance set"""
+        rc = lib.cuoptamd_batch_set_halpern_device_major(self.handle, int(P))
+        if rc != 0:
+            raise CuOptError(rc, lib.cuoptamd_last_error().decode())
+
+    def halpern_device_major(self):
+        """cuoptamd_batch_halpern_device_major: the P the batch runs with (0: the host decides)"""
+        return int(lib.cuoptamd_batch_halpern_device_major(self.handle))
+
+    def burst_stats(self):
+        """cuoptamd_batch_halpern_burst_stats: dict bursts / periods (enqueued) / records (written) / empty_periods (member-periods enqueued
+        behind a member's stop)"""
+        out = np.zeros(4, np.int64)
+        rc = lib.cuoptamd_batch_halpern_burst_stats(self.handle, _ptr(out))
+        if rc != 0:
+            raise CuOptError(rc, lib.cuoptamd_last_error().decode())
+        return dict(zip(("bursts", "periods", "records", "empty_periods"), out.tolist()))
+
     def time_kernels(self, reps=20):
         """average dispatch time (ms) of the four kernels of a batched attempt: dict primal / a_dual / at_step / decisions"""
         out = np.zeros(4)
@@ -1552,3 +1579,21 @@ def debug_halpern_major_decide(ev, ctl, hal, r_prev, params, target=None, stoppe
     if rc != 0:
         raise CuOptError(rc, lib.pdlpdev_last_error().decode())
     return rec, rp.value, st.value, rs.value
+
+
+def debug_halpern_major_decide_batch(evs, ctls, hals, r_prevs, params, targets, stopped, records, device=0):
+    """pdlpdev_debug_halpern_major_decide_batch: k_halpern_major_decide_batch once over N cases as the N members of one launch -- per case what
+    debug_halpern_major_decide takes (evs: N x 8 figures, ctls / hals / params / records: lists of the structs, records in/out).
+    -> (records, r_prev [N], stopped [N], restart [N]) as the kernel left them."""
+    n = len(ctls)
+    e = _f64(np.asarray(evs, float).reshape(-1))
+    if e.shape != (8 * n,):
+        raise ValueError("debug_halpern_major_decide_batch: eight evaluation figures per case")
+    ctl, hal, par, rec = (Ctl * n)(*ctls), (Halpern * n)(*hals), (HalpernMajorParams * n)(*params), (HalpernMajorRecord * n)(*records)
+    rp, st, tg = _f64(r_prevs), _i32(stopped), _i32(targets)
+    rp_out, st_out, rs_out = np.zeros(n), np.zeros(n, np.int32), np.zeros(n, np.int32)
+    rc = lib.pdlpdev_debug_halpern_major_decide_batch(int(device), n, _ptr(e), ctl, hal, _ptr(rp), _ptr(st), _ptr(tg), par, rec, _ptr(rp_out),
+                                                      _ptr(st_out), _ptr(rs_out))
+    if rc != 0:
+        raise CuOptError(rc, lib.pdlpdev_last_error().decode())
+    return list(rec), rp_out, st_out, rs_out

@@ -13,6 +13,84 @@ struct pdlpdev_halpern_major_state {
   int32_t restart;  // 1: the decision in front asks for the restart (the guard of the three restart kernels)
 };
 
+// The decision of a major iteration: halpern_major_head's tests in its order and with its expressions (pdlp_solver.cpp: to_convergence,
+// verdict, the iteration limit of check_limits, the three restart tests) on the scalars that are on the device.  One thread runs it;
+// k_halpern_major_decide (one LP) and k_halpern_major_decide_batch (one wave per LP of a batch) both call it -- the tests do not fork.
+//   sc      the evaluation's nine raw sums (read_eval's input: the scalars' slot 32 on the multi-launch path, the pinned block's on
+//           the resident one)
+//   target  the period's accepted-step count
+//   rec     the record, in pinned host memory
+// Stopped: nothing.  The error flag up: a record marked "step error", stopped.  The steps short of the target (a resident launch that
+// hit its step cap): "fell short", stopped.  Otherwise the record with the verdict; any verdict but "go on" stops the burst.
+__device__ __forceinline__ void halpern_major_decide(const pdlpdev_ctl* __restrict__ ctl, const pdlpdev_halpern* __restrict__ hal,
+                                                     pdlpdev_halpern_major_state* __restrict__ st, const double* __restrict__ sc,
+                                                     const pdlpdev_halpern_major_params& p, int target, pdlpdev_halpern_major_record* __restrict__ rec)
+{
+  if (st->stopped) return;
+  pdlpdev_halpern_major_record out;
+  for (int i = 0; i < PDLPDEV_EV_COUNT; ++i) out.ev[i] = 0.0;
+  out.r = hal->r, out.r_first = hal->r_first, out.k = hal->k;
+  out.primal_weight = ctl->primal_weight;
+  out.dist[0] = out.dist[1] = 0.0, out.new_weight = 0.0;
+  out.steps_taken = ctl->steps_taken;
+  out.restart = 0;
+  st->restart = 0;
+  if (ctl->error != 0 || ctl->steps_taken < target) {
+    out.verdict = ctl->error != 0 ? PDLPDEV_MAJOR_STEP_ERROR : PDLPDEV_MAJOR_FELL_SHORT;
+    st->stopped = 1;
+    *rec        = out;
+    return;
+  }
+  // read_eval (pdlp_layouts.hpp)
+  double* ev = out.ev;
+  ev[PDLPDEV_EV_PRES2]         = sc[0];
+  ev[PDLPDEV_EV_DUAL_SUM]      = sc[1] + sc[5];
+  ev[PDLPDEV_EV_Y2]            = sc[2];
+  ev[PDLPDEV_EV_LINF_PRES_REL] = p.want_linf ? sc[3] : 0.0;
+  ev[PDLPDEV_EV_DRES2]         = sc[4];
+  ev[PDLPDEV_EV_CX]            = sc[6];
+  ev[PDLPDEV_EV_X2]            = sc[7];
+  ev[PDLPDEV_EV_LINF_DRES_REL] = p.want_linf ? sc[8] : 0.0;
+  // to_convergence
+  double pobj = ev[PDLPDEV_EV_CX], dobj = ev[PDLPDEV_EV_DUAL_SUM];
+  if (p.objective_scale != 1.0 || p.objective_offset != 0.0) {
+    pobj = p.objective_scale * pobj + p.objective_offset;
+    dobj = p.objective_scale * dobj + p.objective_offset;
+  }
+  const double gap = fabs(pobj - dobj), abs_objective = fabs(pobj) + fabs(dobj);
+  const double l2_primal = sqrt(ev[PDLPDEV_EV_PRES2]), l2_dual = sqrt(ev[PDLPDEV_EV_DRES2]);
+  // verdict: the three inequalities
+  const bool gap_ok = gap <= p.absolute_gap_tolerance + p.relative_gap_tolerance * abs_objective;
+  bool primal_ok, dual_ok;
+  if (p.per_constraint_residual) {
+    primal_ok = ev[PDLPDEV_EV_LINF_PRES_REL] <= p.absolute_primal_tolerance;
+    dual_ok   = ev[PDLPDEV_EV_LINF_DRES_REL] <= p.absolute_dual_tolerance;
+  } else {
+    primal_ok = l2_primal <= p.absolute_primal_tolerance + p.relative_primal_tolerance * p.norm_b;
+    dual_ok   = l2_dual <= p.absolute_dual_tolerance + p.relative_dual_tolerance * p.norm_c;
+  }
+  const int total_iterations = p.iteration_offset + ctl->steps_taken;
+  int verdict = PDLPDEV_MAJOR_GO_ON;
+  if (total_iterations > 1 && dual_ok && primal_ok && gap_ok) verdict = PDLPDEV_MAJOR_OPTIMAL;
+  else if (ctl->steps_taken >= p.iteration_limit) verdict = PDLPDEV_MAJOR_ITERATION_LIMIT;  // check_limits: internal_solver_iterations_
+  out.verdict = verdict;
+  if (verdict != PDLPDEV_MAJOR_GO_ON) {
+    st->stopped = 1;
+    *rec        = out;
+    return;
+  }
+  // the three restart tests
+  const double r = hal->r, r_first = hal->r_first, r_prev = st->r_prev;
+  bool restart = false;
+  if (r <= p.sufficient_reduction * r_first) restart = true;
+  else if (r <= p.necessary_reduction * r_first && r_prev >= 0.0 && r > r_prev) restart = true;
+  else if ((double)hal->k >= p.artificial_threshold * (double)total_iterations) restart = true;
+  st->r_prev  = restart ? -1.0 : r;  // (halpern_restart_done: no previous check behind a restart)
+  st->restart = restart ? 1 : 0;
+  out.restart = restart ? 1 : 0;
+  *rec        = out;
+}
+
 extern "C" {
 // <<<1, 1>>>: stopped <- 0, restart <- 0, r_prev <- the host's
 int halpern_major_launch_arm(pdlpdev_ctx* ctx, double r_prev);

@@ -2,8 +2,10 @@
 // docs/design/04d_halpern_mode.md, "Verdict and restart on the device").  A translation unit of its own: the four layout units, the
 // two resident units and the core's restart kernels (k_restart, k_finalize, k_copy_current, k_halpern_restart_ctl) compile as before.
 // Every kernel here asks the burst's block first and does nothing once a decision has stopped the burst; no kernel waits for another
-// -- the order is the stream's.
+// -- the order is the stream's.  The second half serves the K LPs of a Halpern small-LP batch (cuoptamd_batch_set_halpern_device_major;
+// "Bursts of a K-workgroup batch"): the same bodies with a workgroup per LP, each behind that LP's own block.
 #include "halpern_major.hpp"
+#include "halpern_major_batch.hpp"
 #include "pdlp_launch.hpp"
 #include "resident_halpern_bodies.hpp"
 
@@ -42,82 +44,13 @@ __global__ void __launch_bounds__(kMajorThreads) k_major_small_halpern_burst(Maj
   major_small_halpern_body(A, prod);
 }
 
-// The decision of a major iteration, one workgroup: halpern_major_head's tests in its order and with its expressions (pdlp_solver.cpp:
-// to_convergence, verdict, the iteration limit of check_limits, the three restart tests) on the scalars that are on the device.
-//   sc      the evaluation's nine raw sums (read_eval's input: the scalars' slot 32 on the multi-launch path, the pinned block's on
-//           the resident one)
-//   target  the period's accepted-step count
-//   rec     the record, in pinned host memory
-// Stopped: nothing.  The error flag up: a record marked "step error", stopped.  The steps short of the target (a resident launch that
-// hit its step cap): "fell short", stopped.  Otherwise the record with the verdict; any verdict but "go on" stops the burst.
+// The decision of a major iteration, one workgroup: thread 0 runs halpern_major_decide (halpern_major.hpp) on the context's own blocks.
 __global__ void __launch_bounds__(kDecideThreads)
 k_halpern_major_decide(const pdlpdev_ctl* __restrict__ ctl, const pdlpdev_halpern* __restrict__ hal, pdlpdev_halpern_major_state* __restrict__ st,
                        const double* __restrict__ sc, pdlpdev_halpern_major_params p, int target, pdlpdev_halpern_major_record* __restrict__ rec)
 {
   if (threadIdx.x != 0) return;
-  if (st->stopped) return;
-  pdlpdev_halpern_major_record out;
-  for (int i = 0; i < PDLPDEV_EV_COUNT; ++i) out.ev[i] = 0.0;
-  out.r = hal->r, out.r_first = hal->r_first, out.k = hal->k;
-  out.primal_weight = ctl->primal_weight;
-  out.dist[0] = out.dist[1] = 0.0, out.new_weight = 0.0;
-  out.steps_taken = ctl->steps_taken;
-  out.restart = 0;
-  st->restart = 0;
-  if (ctl->error != 0 || ctl->steps_taken < target) {
-    out.verdict = ctl->error != 0 ? PDLPDEV_MAJOR_STEP_ERROR : PDLPDEV_MAJOR_FELL_SHORT;
-    st->stopped = 1;
-    *rec        = out;
-    return;
-  }
-  // read_eval (pdlp_layouts.hpp)
-  double* ev = out.ev;
-  ev[PDLPDEV_EV_PRES2]         = sc[0];
-  ev[PDLPDEV_EV_DUAL_SUM]      = sc[1] + sc[5];
-  ev[PDLPDEV_EV_Y2]            = sc[2];
-  ev[PDLPDEV_EV_LINF_PRES_REL] = p.want_linf ? sc[3] : 0.0;
-  ev[PDLPDEV_EV_DRES2]         = sc[4];
-  ev[PDLPDEV_EV_CX]            = sc[6];
-  ev[PDLPDEV_EV_X2]            = sc[7];
-  ev[PDLPDEV_EV_LINF_DRES_REL] = p.want_linf ? sc[8] : 0.0;
-  // to_convergence
-  double pobj = ev[PDLPDEV_EV_CX], dobj = ev[PDLPDEV_EV_DUAL_SUM];
-  if (p.objective_scale != 1.0 || p.objective_offset != 0.0) {
-    pobj = p.objective_scale * pobj + p.objective_offset;
-    dobj = p.objective_scale * dobj + p.objective_offset;
-  }
-  const double gap = fabs(pobj - dobj), abs_objective = fabs(pobj) + fabs(dobj);
-  const double l2_primal = sqrt(ev[PDLPDEV_EV_PRES2]), l2_dual = sqrt(ev[PDLPDEV_EV_DRES2]);
-  // verdict: the three inequalities
-  const bool gap_ok = gap <= p.absolute_gap_tolerance + p.relative_gap_tolerance * abs_objective;
-  bool primal_ok, dual_ok;
-  if (p.per_constraint_residual) {
-    primal_ok = ev[PDLPDEV_EV_LINF_PRES_REL] <= p.absolute_primal_tolerance;
-    dual_ok   = ev[PDLPDEV_EV_LINF_DRES_REL] <= p.absolute_dual_tolerance;
-  } else {
-    primal_ok = l2_primal <= p.absolute_primal_tolerance + p.relative_primal_tolerance * p.norm_b;
-    dual_ok   = l2_dual <= p.absolute_dual_tolerance + p.relative_dual_tolerance * p.norm_c;
-  }
-  const int total_iterations = p.iteration_offset + ctl->steps_taken;
-  int verdict = PDLPDEV_MAJOR_GO_ON;
-  if (total_iterations > 1 && dual_ok && primal_ok && gap_ok) verdict = PDLPDEV_MAJOR_OPTIMAL;
-  else if (ctl->steps_taken >= p.iteration_limit) verdict = PDLPDEV_MAJOR_ITERATION_LIMIT;  // check_limits: internal_solver_iterations_
-  out.verdict = verdict;
-  if (verdict != PDLPDEV_MAJOR_GO_ON) {
-    st->stopped = 1;
-    *rec        = out;
-    return;
-  }
-  // the three restart tests
-  const double r = hal->r, r_first = hal->r_first, r_prev = st->r_prev;
-  bool restart = false;
-  if (r <= p.sufficient_reduction * r_first) restart = true;
-  else if (r <= p.necessary_reduction * r_first && r_prev >= 0.0 && r > r_prev) restart = true;
-  else if ((double)hal->k >= p.artificial_threshold * (double)total_iterations) restart = true;
-  st->r_prev  = restart ? -1.0 : r;  // (halpern_restart_done: no previous check behind a restart)
-  st->restart = restart ? 1 : 0;
-  out.restart = restart ? 1 : 0;
-  *rec        = out;
+  halpern_major_decide(ctl, hal, st, sc, p, target, rec);
 }
 
 // ---- the restart, guarded by the decision: twins of k_restart (candidate = the current iterate, scaled distances), k_copy_current
@@ -156,6 +89,100 @@ k_halpern_major_restart_finish(const double* __restrict__ part, int g, pdlpdev_c
   hal->k                 = 0;
   rec->dist[0] = dx, rec->dist[1] = dy, rec->new_weight = ctl->primal_weight;
   if (ctl_host) *ctl_host = *ctl, *hal_host = *hal;
+}
+
+// ---- the burst of a Halpern small-LP batch (halpern_major_batch.hpp): every kernel above once more with one workgroup (the restart:
+// its blocks) per LP, each behind that LP's own flags.  A member that has stopped rests; the others go on.
+__global__ void __launch_bounds__(kDecideThreads) k_halpern_major_arm_batch(const HalpernBurstMember* __restrict__ mem, const int* __restrict__ list, int count)
+{
+  const int i = blockIdx.x * kDecideThreads + threadIdx.x;
+  if (i >= count) return;
+  const HalpernBurstMember& M     = mem[list[i]];
+  pdlpdev_halpern_major_state* st = M.st;
+  st->r_prev   = M.r_prev;
+  st->dist2[0] = st->dist2[1] = 0.0;
+  st->stopped = 0, st->restart = 0;
+}
+// workgroup b serves LP list[b]: k_pdhg_resident_halpern_batch's arrangement (the record's pointers through as_global, so that the two
+// blocks stay in scalar registers) behind the guard, to the period's target
+template <int T, int Q, int U>
+__global__ void __launch_bounds__(T)
+k_pdhg_resident_halpern_burst_batch(const HalpernBurstMember* __restrict__ mem, const int* __restrict__ list, int add_target, int max_steps)
+{
+  extern __shared__ double lds[];
+  const HalpernBurstMember& M = mem[list[blockIdx.x]];
+  if (as_global(M.st)->stopped) return;  // (uniform)
+  const HalpernResidentArgs& A = M.run;
+  const HalpernSmallView& S    = A.V;
+  const HalpernSmallView V{S.m, S.n, S.nnz, as_global(S.a_off), as_global(S.a_idx), as_global(S.at_off), as_global(S.at_idx), as_global(S.a_val),
+                           as_global(S.at_val), as_global(S.c), as_global(S.lb), as_global(S.ub), as_global(S.lo), as_global(S.hi), as_global(S.x0),
+                           as_global(S.x1), as_global(S.y0), as_global(S.y1), as_global(S.aty0), as_global(S.aty1), as_global(S.ax), as_global(S.ay),
+                           as_global(S.aaty), as_global(S.tx), as_global(S.ty)};
+  resident_halpern_body<T, Q, U>(V, as_global(A.ctl), as_global(A.ctl_host), as_global(A.hal), as_global(A.hal_host), A.target_steps + add_target, max_steps,
+                                 lds);
+}
+// workgroup b evaluates LP list[b] behind the same guard, with that period's guard_target
+__global__ void __launch_bounds__(kMajorThreads)
+k_major_small_halpern_burst_batch(const MajorSmallArgs* __restrict__ args, const HalpernBurstMember* __restrict__ mem, const int* __restrict__ list, int add_target)
+{
+  extern __shared__ double prod[];
+  const int l = list[blockIdx.x];
+  if (mem[l].st->stopped) return;  // (uniform)
+  // major_small_halpern_body's guard with the period's target (the record's own guard_target is -1: the body asks nothing more)
+  const MajorSmallArgs& A = args[l];
+  const int guard_target  = mem[l].run.target_steps + add_target;
+  if (!(A.ctl->error != 0 || A.ctl->steps_taken >= guard_target)) {  // (uniform)
+    if (threadIdx.x == 0) A.sc[63] = 0.0;  // "not evaluated"
+    return;
+  }
+  major_small_halpern_body(A, prod);
+}
+// one wave per LP, thread 0 decides: ring slot [l][j]
+__global__ void __launch_bounds__(kDecideThreads)
+k_halpern_major_decide_batch(const HalpernBurstMember* __restrict__ mem, const int* __restrict__ list, int j, int add_target)
+{
+  if (threadIdx.x != 0) return;
+  const HalpernBurstMember& M = mem[list[blockIdx.x]];
+  halpern_major_decide(M.run.ctl, M.run.hal, M.st, M.sc, M.p, M.run.target_steps + add_target, M.ring + j);
+}
+// the twin of k_restart_batch: the (LP, block) table covers every member of the burst; a block returns unless its LP asked for a restart
+__global__ void __launch_bounds__(kBlock) k_halpern_major_restart_batch(const HalpernBurstMember* __restrict__ mem, const int2* __restrict__ blk)
+{
+  __shared__ double red[12];
+  const int2 b                = blk[blockIdx.x];
+  const HalpernBurstMember& M = mem[b.x];
+  if (M.st->stopped || !M.st->restart) return;  // (uniform)
+  restart_block(M.R, b.y, M.g, red);
+}
+// the twin of k_halpern_restart_finish_batch (no clear): the two sums by finalize_rows' tree, A^T y into the anchor's,
+// k_halpern_restart_ctl's arithmetic with this LP's theta; the distances and the new weight go to the record, both blocks to their mirrors
+__global__ void __launch_bounds__(kBlock) k_halpern_major_restart_finish_batch(const HalpernBurstMember* __restrict__ mem, const int* __restrict__ list, int j)
+{
+  __shared__ double red[8];
+  const HalpernBurstMember& M     = mem[list[blockIdx.x]];
+  pdlpdev_halpern_major_state* st = M.st;
+  if (st->stopped || !st->restart) return;  // (uniform; the flag is the decision's to write)
+  pdlpdev_ctl* ctl = M.run.ctl;
+  const int cur    = ctl->cur;  // (read by every thread in front of finalize_rows' barriers; thread 0 rewrites the block behind them)
+  finalize_rows(M.R.part, M.g, 2, 0u, st->dist2, red);
+  const double* __restrict__ v = cur ? M.aty1 : M.aty0;
+  for (int i = threadIdx.x; i < M.R.n; i += kBlock) M.lraty[i] = v[i];
+  if (threadIdx.x != 0) return;
+  pdlpdev_halpern* hal = M.run.hal;
+  const double theta   = M.theta;
+  const double dx = sqrt(st->dist2[0]), dy = sqrt(st->dist2[1]);  // k_halpern_restart_ctl
+  st->dist2[0] = dx, st->dist2[1] = dy;
+  if (theta >= 0.0 && dx > 1.0e-10 && dy > 1.0e-10) {
+    const double w     = exp(theta * log(dy / dx) + (1.0 - theta) * log(ctl->primal_weight));
+    ctl->primal_weight = w;
+    ctl->tau           = ctl->step_size / w;
+    ctl->sigma         = ctl->step_size * w;
+  }
+  ctl->its_since_restart = 0;
+  hal->k                 = 0;
+  pdlpdev_halpern_major_record* rec = M.ring + j;
+  rec->dist[0] = dx, rec->dist[1] = dy, rec->new_weight = ctl->primal_weight;
+  *M.run.ctl_host = *ctl, *M.run.hal_host = *hal;
 }
 
 }  // namespace
@@ -212,6 +239,108 @@ int halpern_major_launch_restart(pdlpdev_ctx* ctx, double theta, pdlpdev_halpern
   k_halpern_major_restart_finish<<<1, kBlock, 0, s>>>(ctx->part_g, g, ctx->ctl, ctx->hal, ctx->hmaj, theta, rec, mirrors ? ctx->ctl_h : nullptr,
                                                       mirrors ? ctx->hal_h : nullptr);
   HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// ---- the launches of a batch burst (pdlpdev_small_batch_run_halpern_burst, kernels_resident.hip) ----
+int halpern_batch_burst_arm(hipStream_t s, const HalpernBurstMember* mem, const int* list, int count)
+{
+  k_halpern_major_arm_batch<<<(count + kDecideThreads - 1) / kDecideThreads, kDecideThreads, 0, s>>>(mem, list, count);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+int halpern_batch_burst_loop(hipStream_t s, int device, int tier, const HalpernBurstMember* mem, const int* tier_list, int count, int32_t add_target)
+{
+  return for_resident_tier(
+    tier,
+    [&](auto I) {
+      constexpr ResidentTier r = kResidentTiers[decltype(I)::value];
+      return launch_resident_kernel(k_pdhg_resident_halpern_burst_batch<r.T, r.Q, r.U>, I, device, s, count, mem, tier_list, add_target, 1 << 14);
+    },
+    [&] { return fail(-1, "resident Halpern batch burst: no tier %d", tier); });
+}
+int halpern_batch_burst_eval(hipStream_t s, int device, size_t lds, const MajorSmallArgs* args, const HalpernBurstMember* mem, const int* list, int count,
+                             int32_t add_target)
+{
+  TRY(allow_dynamic_lds((const void*)k_major_small_halpern_burst_batch, device, 8192 * 8));
+  k_major_small_halpern_burst_batch<<<count, kMajorThreads, lds, s>>>(args, mem, list, add_target);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+int halpern_batch_burst_decide(hipStream_t s, const HalpernBurstMember* mem, const int* list, int count, int32_t j, int32_t add_target)
+{
+  k_halpern_major_decide_batch<<<count, kDecideThreads, 0, s>>>(mem, list, j, add_target);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+int halpern_batch_burst_restart(hipStream_t s, const HalpernBurstMember* mem, const int2* blk, int blocks, const int* list, int count, int32_t j)
+{
+  k_halpern_major_restart_batch<<<blocks, kBlock, 0, s>>>(mem, blk);
+  k_halpern_major_restart_finish_batch<<<count, kBlock, 0, s>>>(mem, list, j);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+int pdlpdev_debug_halpern_major_decide_batch(int device, int32_t count, const double* ev, const pdlpdev_ctl* ctl, const pdlpdev_halpern* hal,
+                                             const double* r_prev, const int32_t* stopped, const int32_t* target,
+                                             const pdlpdev_halpern_major_params* params, pdlpdev_halpern_major_record* records, double* r_prev_out,
+                                             int32_t* stopped_out, int32_t* restart_out)
+{
+  if (!ev || !ctl || !hal || !r_prev || !stopped || !target || !params || !records || count < 1)
+    return fail(-1, "pdlpdev_debug_halpern_major_decide_batch: null argument");
+  HIP_TRY(hipSetDevice(device));
+  // per member what pdlpdev_debug_halpern_major_decide holds for its one case, plus the member's record of the burst and the list
+  struct Blocks {
+    pdlpdev_halpern_major_state st;
+    pdlpdev_ctl ctl;
+    pdlpdev_halpern hal;
+    double sc[9];
+    pdlpdev_halpern_major_record rec;
+    HalpernBurstMember mem;
+    int list;
+  };
+  std::vector<Blocks> h((size_t)count);
+  Blocks* d = nullptr;
+  HIP_TRY(hipMalloc((void**)&d, sizeof(Blocks) * (size_t)count));
+  for (int l = 0; l < count; ++l) {
+    Blocks& b = h[l];
+    memset(&b, 0, sizeof(b));
+    const double* e = ev + (size_t)l * PDLPDEV_EV_COUNT;
+    b.st.r_prev = r_prev[l], b.st.stopped = stopped[l], b.st.restart = 0;
+    b.ctl = ctl[l], b.hal = hal[l], b.rec = records[l];
+    // (read_eval's input from its output: the dual objective's two halves as the sum and a zero)
+    b.sc[0] = e[PDLPDEV_EV_PRES2], b.sc[1] = e[PDLPDEV_EV_DUAL_SUM], b.sc[2] = e[PDLPDEV_EV_Y2], b.sc[3] = e[PDLPDEV_EV_LINF_PRES_REL];
+    b.sc[4] = e[PDLPDEV_EV_DRES2], b.sc[5] = 0.0, b.sc[6] = e[PDLPDEV_EV_CX], b.sc[7] = e[PDLPDEV_EV_X2], b.sc[8] = e[PDLPDEV_EV_LINF_DRES_REL];
+    b.mem.run.ctl = &d[l].ctl, b.mem.run.hal = &d[l].hal, b.mem.run.target_steps = target[l];
+    b.mem.st = &d[l].st, b.mem.sc = d[l].sc, b.mem.ring = &d[l].rec, b.mem.p = params[l];
+    b.list = count - 1 - l;  // (workgroup w serves member count - 1 - w: the list is looked at)
+  }
+  hipError_t e = hipMemcpy(d, h.data(), sizeof(Blocks) * (size_t)count, hipMemcpyHostToDevice);
+  // the member records and the list, each contiguous as the kernel indexes them
+  HalpernBurstMember* dmem = nullptr;
+  int* dlist               = nullptr;
+  if (e == hipSuccess) e = hipMalloc((void**)&dmem, sizeof(HalpernBurstMember) * (size_t)count);
+  if (e == hipSuccess) e = hipMalloc((void**)&dlist, sizeof(int) * (size_t)count);
+  for (int l = 0; e == hipSuccess && l < count; ++l) {
+    e = hipMemcpy(dmem + l, &h[l].mem, sizeof(HalpernBurstMember), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dlist + l, &h[l].list, sizeof(int), hipMemcpyHostToDevice);
+  }
+  if (e == hipSuccess) {
+    k_halpern_major_decide_batch<<<count, kDecideThreads>>>(dmem, dlist, 0, 0);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e == hipSuccess) e = hipMemcpy(h.data(), d, sizeof(Blocks) * (size_t)count, hipMemcpyDeviceToHost);
+  (void)hipFree(d);
+  if (dmem) (void)hipFree(dmem);
+  if (dlist) (void)hipFree(dlist);
+  HIP_TRY(e);
+  for (int l = 0; l < count; ++l) {
+    records[l] = h[l].rec;
+    if (r_prev_out) r_prev_out[l] = h[l].st.r_prev;
+    if (stopped_out) stopped_out[l] = h[l].st.stopped;
+    if (restart_out) restart_out[l] = h[l].st.restart;
+  }
   return 0;
 }
 

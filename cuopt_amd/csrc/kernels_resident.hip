@@ -6,6 +6,7 @@
 #include "pdlp_ctx.hpp"
 #include "pdlp_layouts.hpp"
 #include "resident_common.hpp"  // lds_row_sum, the tiers, MajorSmallArgs + small_rows: shared with kernels_resident_halpern.hip
+#include "halpern_major_batch.hpp"  // the records and launches of a Halpern batch's burst (kernels: kernels_halpern_major.hip)
 
 // ------------------------------------------------------------------------------------------------
 // Small LPs (MIP-style repeated re-solves, BASELINE config 5): the whole batch of PDHG attempts between two
@@ -489,6 +490,13 @@ struct pdlpdev_small_batch {
   // pass of a run in either mode; for a Halpern batch also restart rounds and resets, and one synchronisation per restart round, reset
   // and separate pdlpdev_small_batch_major_eval
   int64_t stat_loop_launches = 0, stat_eval_launches = 0, stat_periods = 0, stat_restart_rounds = 0, stat_resets = 0, stat_syncs = 0;
+  // pdlpdev_small_batch_set_halpern_device_major: per member a burst block on the device (hmaj[l]); in one pinned block of their own
+  // the members' burst records (burst[l]: params, theta, views) and the ring of 16 decision records per member (ring[16 l + j])
+  pdlpdev_halpern_major_state* hmaj = nullptr;
+  void* burst_pinned = nullptr;
+  HalpernBurstMember* burst = nullptr;
+  pdlpdev_halpern_major_record* ring = nullptr;
+  int64_t stat_bursts = 0, stat_burst_periods = 0, stat_burst_records = 0, stat_burst_empty = 0;  // pdlpdev_small_batch_halpern_burst_stats
   pdlpdev_small_batch() = default;
   pdlpdev_small_batch(const pdlpdev_small_batch&) = delete;
   pdlpdev_small_batch& operator=(const pdlpdev_small_batch&) = delete;
@@ -496,6 +504,8 @@ struct pdlpdev_small_batch {
   {
     if (stream) (void)hipStreamDestroy(stream);
     if (pinned) (void)hipHostFree(pinned);
+    if (burst_pinned) (void)hipHostFree(burst_pinned);
+    if (hmaj) (void)hipFree(hmaj);
   }
 };
 
@@ -663,6 +673,117 @@ int pdlpdev_small_batch_stats(pdlpdev_small_batch* b, int64_t out[8])
   for (int t = 0; t < 3; ++t) tiers += std::count(b->tier.begin(), b->tier.end(), t) > 0;
   out[0] = b->halpern, out[1] = tiers, out[2] = b->stat_loop_launches, out[3] = b->stat_eval_launches, out[4] = b->stat_periods;
   out[5] = b->stat_restart_rounds, out[6] = b->stat_resets, out[7] = b->stat_syncs;
+  return 0;
+}
+
+// ---- bursts of device-decided major iterations for a Halpern batch (kernels: kernels_halpern_major.hip) ----------------------------------
+int pdlpdev_small_batch_set_halpern_device_major(pdlpdev_small_batch* b, int on)
+{
+  if (!b) return fail(-1, "pdlpdev_small_batch_set_halpern_device_major: null batch");
+  if (!on) return 0;
+  if (!b->halpern) return fail(-7, "pdlpdev_small_batch_set_halpern_device_major: a batch of LPs in reflected Halpern mode only");
+  for (int l = 0; l < b->K; ++l)
+    if (b->ctx[l]->halpern_rays)
+      return fail(-7, "pdlpdev_small_batch_set_halpern_device_major: LP %d evaluates the infeasibility ray, whose verdict is the host's", l);
+  HIP_TRY(hipSetDevice(b->device));
+  const size_t K = (size_t)b->K;
+  if (!b->hmaj) HIP_TRY(hipMalloc((void**)&b->hmaj, sizeof(pdlpdev_halpern_major_state) * K));
+  if (!b->burst_pinned) {
+    const size_t o_ring = (sizeof(HalpernBurstMember) * K + 255) & ~(size_t)255;
+    HIP_TRY(hipHostMalloc(&b->burst_pinned, o_ring + sizeof(pdlpdev_halpern_major_record) * 16 * K, hipHostMallocDefault));
+    b->burst = (HalpernBurstMember*)b->burst_pinned;
+    b->ring  = (pdlpdev_halpern_major_record*)((char*)b->burst_pinned + o_ring);
+  }
+  return 0;
+}
+int pdlpdev_small_batch_halpern_burst_stats(pdlpdev_small_batch* b, int64_t out[4])
+{
+  if (!b || !out) return fail(-1, "pdlpdev_small_batch_halpern_burst_stats: null argument");
+  out[0] = b->stat_bursts, out[1] = b->stat_burst_periods, out[2] = b->stat_burst_records, out[3] = b->stat_burst_empty;
+  return 0;
+}
+// Enqueued in stream order, no kernel waiting for another: the arming kernel; then per period the loop kernel per tier in use, the guarded
+// evaluation, the decisions, the guarded restart over the (LP, block) table built once; ONE synchronisation behind the last period.
+int pdlpdev_small_batch_run_halpern_burst(pdlpdev_small_batch* b, const int32_t* first_target, int32_t period, int32_t count, const pdlpdev_small_eval* rq,
+                                          const pdlpdev_halpern_major_params* params, const double* theta, const double* r_prev,
+                                          pdlpdev_halpern_major_record* records, int32_t* written, double* r_prev_out, pdlpdev_ctl* ctl,
+                                          pdlpdev_halpern* hal)
+{
+  roctx::Range range("pdlp: Halpern burst of a small-LP batch (steps + evaluation + decision + restart, P periods)");
+  if (!b || !first_target || !rq || !params || !theta || !r_prev || !records || !written)
+    return fail(-1, "pdlpdev_small_batch_run_halpern_burst: null argument");
+  if (!b->halpern || !b->hmaj || !b->burst) return fail(-7, "pdlpdev_small_batch_run_halpern_burst: call pdlpdev_small_batch_set_halpern_device_major first");
+  if (count < 1 || count > 16 || period < 1 || period > (1 << 14))
+    return fail(-1, "pdlpdev_small_batch_run_halpern_burst: 1 .. 16 periods of at least one step");
+  HIP_TRY(hipSetDevice(b->device));
+  const int K = b->K;
+  int n = 0, blocks = 0, tier_count[3] = {0, 0, 0};
+  for (int l = 0; l < K; ++l) {
+    written[l] = 0;
+    if (first_target[l] <= 0) continue;
+    pdlpdev_ctx* c = b->ctx[l];
+    // (the caller holds the control block; where the pinned mirror is known to be the device's, the request is checked against it)
+    const bool known = c->ctl_h_current;
+    if (c->halpern_rays || (known && (c->ctl_h->error != 0 || c->ctl_h->steps_taken >= first_target[l] || first_target[l] - c->ctl_h->steps_taken > period)))
+      return fail(-7, "pdlpdev_small_batch_run_halpern_burst: LP %d: the first period must start inside (step error down, target ahead, at most one period away)", l);
+    const int want_linf = wants_linf(rq[l].eps_p, rq[l].eps_d) ? 1 : 0;
+    b->major[l]         = major_args(c, 3, rq[l].rule_finite, want_linf, rq[l].eps_p, rq[l].eps_d);  // (guard_target -1: the burst's kernel applies each period's)
+    HalpernBurstMember& M = b->burst[l];
+    M.run = HalpernResidentArgs{halpern_view(c), c->ctl, c->ctl_h, c->hal, c->hal_h, first_target[l], 0};
+    M.st = b->hmaj + l, M.sc = c->scal_h + 32, M.ring = b->ring + 16 * (size_t)l;
+    M.p = params[l], M.p.want_linf = want_linf;
+    M.theta = theta[l], M.r_prev = r_prev[l];
+    const RestartBatchArgs ra = restart_batch_args(c, PDLPDEV_CURRENT, 0);
+    M.R = ra.R, M.g = ra.g, M.pad = 0;
+    M.aty0 = c->aty[0], M.aty1 = c->aty[1], M.lraty = c->lraty;
+    for (int j = 0; j < count; ++j) M.ring[j].steps_taken = -1;  // ("not written": a decision leaves its step count here)
+    for (int i = 0; i < M.g; ++i) b->blk[blocks++] = make_int2(l, i);
+    b->run_list[b->tier[l] * K + tier_count[b->tier[l]]++] = l;
+    b->list[n++] = l;
+    loop_state_touched(c);
+  }
+  if (!n) return 0;
+  TRY(halpern_batch_burst_arm(b->stream, b->burst, b->list, n));
+  for (int j = 0; j < count; ++j) {
+    const int32_t add = j * period;
+    for (int tier = 0; tier < 3; ++tier)
+      if (tier_count[tier]) {
+        TRY(halpern_batch_burst_loop(b->stream, b->device, tier, b->burst, b->run_list + tier * K, tier_count[tier], add));
+        b->stat_loop_launches += 1;
+      }
+    TRY(halpern_batch_burst_eval(b->stream, b->device, b->major_lds, b->major, b->burst, b->list, n, add));
+    b->stat_eval_launches += 1;
+    TRY(halpern_batch_burst_decide(b->stream, b->burst, b->list, n, j, add));
+    TRY(halpern_batch_burst_restart(b->stream, b->burst, b->blk, blocks, b->list, n, j));
+  }
+  HIP_TRY(hipStreamSynchronize(b->stream));
+  b->stat_syncs += 1;
+  b->stat_bursts += 1, b->stat_burst_periods += count;
+  for (int q = 0; q < n; ++q) {
+    const int l    = b->list[q];
+    pdlpdev_ctx* c = b->ctx[l];
+    c->ctl_h_current = true;
+    double rp      = r_prev[l];
+    int n_written  = 0;
+    bool stop_seen = false;
+    for (int j = 0; j < count; ++j) {
+      const pdlpdev_halpern_major_record& r = b->ring[16 * (size_t)l + j];
+      if (r.steps_taken < 0) {
+        stop_seen = true;  // (a period behind the member's stop: its workgroups did nothing)
+        b->stat_burst_empty += 1;
+        continue;
+      }
+      if (stop_seen || n_written != j) return fail(-6, "pdlpdev_small_batch_run_halpern_burst: LP %d: a record was written behind the period that stopped it", l);
+      records[16 * (size_t)l + n_written++] = r;
+      if (r.verdict != PDLPDEV_MAJOR_GO_ON) stop_seen = true;
+      else rp = r.restart ? -1.0 : r.r;  // (what the decision left in the member's block)
+    }
+    b->stat_burst_records += n_written;
+    written[l] = n_written;
+    if (r_prev_out) r_prev_out[l] = rp;
+    if (ctl) ctl[l] = *c->ctl_h;
+    if (hal) hal[l] = *c->hal_h;
+  }
   return 0;
 }
 

@@ -17,15 +17,7 @@ k_pdhg_resident_halpern(HalpernSmallView V, pdlpdev_ctl* __restrict__ ctl, pdlpd
   extern __shared__ double lds[];
   resident_halpern_body<T, Q, U>(V, ctl, ctl_host, hal, hal_host, target_steps, max_steps, lds);
 }
-// p, which points to global memory, as a pointer the compiler knows that of (the empty statement keeps the two casts from cancelling
-// and names a scalar register: the value is uniform)
-template <class P>
-__device__ __forceinline__ P* as_global(P* p)
-{
-  __attribute__((address_space(1))) P* g = (__attribute__((address_space(1))) P*)p;
-  asm("" : "+s"(g));
-  return (P*)g;
-}
+// (as_global: resident_halpern_bodies.hpp)
 // K LPs, one workgroup each, ONE launch: workgroup b runs the Halpern loop of LP list[b] exactly as k_pdhg_resident_halpern would -- the
 // same body, so every LP's iterates, scalars and counters are bit for bit those of its own launch (k_pdhg_resident_batch's arrangement).
 template <int T, int Q, int U>

@@ -1604,23 +1604,24 @@ static void advance_begin(cuoptamd_solver* s, clock_type::time_point t0)
              s->power_products, s->result.initial_step_size, s->result.initial_primal_weight);
   log_line(s, "   Iter    Primal Obj.      Dual Obj.    Gap        Primal Res.  Dual Res.   Time\n");  // pdlp.cu:1077-1080
 }
-// cuoptamd_settings::halpern_device_major: a BURST in place of the period the loop was about to run (docs/design/04d_halpern_mode.md,
-// "Verdict and restart on the device").  `target`: the accepted-step count (the device's) next_target gave.  Taken only when that is a
-// whole period's end -- a budget that ends inside a period goes the host-decided way -- and then for as many whole periods as fit the
-// budget, at most P.  One synchronisation; afterwards the records are replayed in order: what halpern_major_head and
-// halpern_restart_done do to the host's state, with the device's verdict as the decision.  *taken: the burst ran (s->ctl, s->hal and
-// total_iterations are what it left); *terminated: a record ended the solve, or the time limit did between two bursts.
-static int advance_halpern_burst(cuoptamd_solver* s, int32_t budget_end, int32_t target, bool* taken, bool* terminated)
+// ---- bursts of device-decided major iterations: what cuoptamd_solver_advance (cuoptamd_settings::halpern_device_major) and the
+// K-workgroup batch (cuoptamd_batch_set_halpern_device_major, small_batch_advance) share ----
+// How many whole periods a burst of at most P may run when the next attempts end at `target` (the device's accepted-step count
+// next_target gave): 0 unless that is a whole period's end behind min_iteration_restart -- a budget that ends inside a period goes the
+// host-decided way -- else as many as fit the budget, at most P.
+static int32_t halpern_burst_periods(const cuoptamd_solver* s, int32_t budget_end, int32_t target, int32_t P)
 {
-  *taken = *terminated = false;
   const cuoptamd_hyper& H   = s->H;
   const int32_t period      = H.major_iteration;
   const int32_t total_after = s->iteration_offset + target;
-  if (s->device_major <= 0 || s->world != 1 || total_after % period != 0 || s->total_iterations + 1 <= H.min_iteration_restart) return 0;
-  const int32_t count = (int32_t)std::min<int64_t>(s->device_major, 1 + ((int64_t)budget_end - total_after) / period);
-  if (count < 1) return 0;
-  const pdlpdev_small_eval rq = major_eval_request_at(s, total_after, s->ctl.its_since_restart + (target - s->ctl.steps_taken));
-  const cuoptamd_settings& t  = s->S;
+  if (P <= 0 || s->world != 1 || total_after % period != 0 || s->total_iterations + 1 <= H.min_iteration_restart) return 0;
+  return (int32_t)std::max<int64_t>(0, std::min<int64_t>(P, 1 + ((int64_t)budget_end - total_after) / period));
+}
+// the constants of the device's decision: the termination rule's and the restart tests'
+static pdlpdev_halpern_major_params halpern_burst_params(const cuoptamd_solver* s)
+{
+  const cuoptamd_hyper& H    = s->H;
+  const cuoptamd_settings& t = s->S;
   pdlpdev_halpern_major_params p{};
   p.absolute_gap_tolerance = t.absolute_gap_tolerance, p.relative_gap_tolerance = t.relative_gap_tolerance;
   p.absolute_primal_tolerance = t.absolute_primal_tolerance, p.relative_primal_tolerance = t.relative_primal_tolerance;
@@ -1631,14 +1632,15 @@ static int advance_halpern_burst(cuoptamd_solver* s, int32_t budget_end, int32_t
   p.artificial_threshold = H.artificial_restart_threshold;
   p.per_constraint_residual = t.per_constraint_residual;
   p.iteration_limit = t.iteration_limit, p.iteration_offset = s->iteration_offset;
-  pdlpdev_halpern_major_record rec[16];
-  int32_t written = 0;
-  double r_prev   = s->halpern_r_prev;
-  int rc = pdlpdev_run_halpern_burst(s->dev, target, period, count, &rq, &p, H.primal_weight_update_smoothing, s->halpern_r_prev, rec, &written, &r_prev,
-                                     &s->ctl);
-  if (rc != 0) return fail(rc, "pdlpdev_run_halpern_burst: %s", pdlpdev_last_error());
-  *taken = true;
-  (void)pdlpdev_get_halpern(s->dev, &s->hal);
+  return p;
+}
+// Behind a burst's synchronisation (s->ctl and s->hal hold what it left): the records replayed in order -- what halpern_major_head and
+// halpern_restart_done do to the host's state, with the device's verdict as the decision.  r_prev: what the burst's block arrived at.
+// A step-error or fell-short record hands the solver to the host-decided path.  *terminated: a record ended the solve, or the time
+// limit did between two bursts.
+static int halpern_burst_replay(cuoptamd_solver* s, const pdlpdev_halpern_major_record* rec, int32_t written, double r_prev, bool* terminated)
+{
+  *terminated = false;
   HostRange range("pdlp: major iterations of a burst (records replayed)");
   for (int32_t i = 0; i < written && !*terminated; ++i) {
     const pdlpdev_halpern_major_record& r = rec[i];
@@ -1664,7 +1666,7 @@ static int advance_halpern_burst(cuoptamd_solver* s, int32_t budget_end, int32_t
     s->halpern_r_prev = r_prev;  // (the burst's block: the same value the replay arrived at)
     bool done  = false;
     int status = kNumericalError;
-    rc         = check_limits(s, &done, &status);  // the time limit, between bursts
+    int rc     = check_limits(s, &done, &status);  // the time limit, between bursts
     if (rc) return rc;
     if (done) {
       finish_solve(s, status, PDLPDEV_AVERAGE);
@@ -1673,6 +1675,29 @@ static int advance_halpern_burst(cuoptamd_solver* s, int32_t budget_end, int32_t
     }
   }
   return 0;
+}
+// cuoptamd_settings::halpern_device_major: a BURST in place of the period the loop was about to run (docs/design/04d_halpern_mode.md,
+// "Verdict and restart on the device").  `target`: the accepted-step count (the device's) next_target gave.  Taken only when
+// halpern_burst_periods says so, for that many whole periods.  One synchronisation; afterwards halpern_burst_replay.  *taken: the burst
+// ran (s->ctl, s->hal and total_iterations are what it left); *terminated: as halpern_burst_replay's.
+static int advance_halpern_burst(cuoptamd_solver* s, int32_t budget_end, int32_t target, bool* taken, bool* terminated)
+{
+  *taken = *terminated = false;
+  const cuoptamd_hyper& H = s->H;
+  const int32_t period    = H.major_iteration;
+  const int32_t count     = halpern_burst_periods(s, budget_end, target, s->device_major);
+  if (count < 1) return 0;
+  const pdlpdev_small_eval rq = major_eval_request_at(s, s->iteration_offset + target, s->ctl.its_since_restart + (target - s->ctl.steps_taken));
+  const pdlpdev_halpern_major_params p = halpern_burst_params(s);
+  pdlpdev_halpern_major_record rec[16];
+  int32_t written = 0;
+  double r_prev   = s->halpern_r_prev;
+  int rc = pdlpdev_run_halpern_burst(s->dev, target, period, count, &rq, &p, H.primal_weight_update_smoothing, s->halpern_r_prev, rec, &written, &r_prev,
+                                     &s->ctl);
+  if (rc != 0) return fail(rc, "pdlpdev_run_halpern_burst: %s", pdlpdev_last_error());
+  *taken = true;
+  (void)pdlpdev_get_halpern(s->dev, &s->hal);
+  return halpern_burst_replay(s, rec, written, r_prev, terminated);
 }
 
 static int32_t advance_budget_end(const cuoptamd_solver* s, int32_t max_new_iterations)
@@ -1737,6 +1762,7 @@ struct cuoptamd_batch {
   pdlpdev_small_batch* small = nullptr;  // ... K resident small LPs, one workgroup each (kernels_resident.hip)
   bool halpern = false;                  // every member in reflected Halpern mode: with `small`, K workgroups of the resident loop
                                          // (pdlpdev_small_batch_create_halpern); with `dev`, the Halpern lockstep batch (halpern_lockstep)
+  int32_t device_major = 0;              // cuoptamd_batch_set_halpern_device_major: P periods per burst, decided on the device (0: by the host)
 };
 
 int cuoptamd_solver_clone(cuoptamd_solver* parent, const double* lb, const double* ub, const double* lo, const double* hi,
@@ -1942,8 +1968,12 @@ static int small_batch_advance(cuoptamd_batch* b, const std::vector<int32_t>& bu
     }
     // ---- budgets and targets; what the attempts need first (new weights -- the Halpern restart set its own --, a cleared step error,
     // A^T y of a fresh iterate -- in Halpern mode it exists since the start of the run)
+    // (cuoptamd_batch_set_halpern_device_major: the round becomes a BURST when every member that is not done is burst-ready --
+    // halpern_burst_periods' conditions, no step error pending, nothing waiting for pdlpdev_small_batch_prepare -- for the fewest
+    // periods any member allows)
     any = false;
-    bool any_prepare = false;
+    bool any_prepare = false, burst = halpern && b->device_major > 0;
+    int32_t burst_count = 16;
     for (int l = 0; l < K; ++l) {
       target[l] = 0, clear[l] = 0, aty[l] = 0, ahead[l].mode = -1;
       if (weight[l] > 0.0) any_prepare = true;  // (also for an LP whose budget ends here: the device keeps what a later call continues from)
@@ -1954,6 +1984,12 @@ static int small_batch_advance(cuoptamd_batch* b, const std::vector<int32_t>& bu
         continue;
       }
       any = true;
+      if (burst) {
+        const int32_t fit = halpern_burst_periods(s, budget_end[l], target[l], b->device_major);
+        if (fit < 1 || s->step_error || s->need_aty || s->H.major_iteration != b->s[0]->H.major_iteration || s->S.halpern_infeasibility || s->S.accept_enabled)
+          burst = false;
+        burst_count = std::min(burst_count, fit);
+      }
       if (s->step_error) s->step_error = false, clear[l] = 1, any_prepare = true;
       if (s->need_aty) s->need_aty = false, aty[l] = 1, any_prepare = true;
       // the major iteration these attempts end in (when the target is a boundary of the schedule, the usual case): its evaluation is
@@ -1974,6 +2010,35 @@ static int small_batch_advance(cuoptamd_batch* b, const std::vector<int32_t>& bu
       if (rc != 0) return fail(rc, "pdlpdev_small_batch_prepare: %s", pdlpdev_last_error());
     }
     if (!any) return 0;
+    if (burst && !any_prepare) {
+      // up to burst_count whole periods for every member, verdict and restart decided on the device, ONE synchronisation; then each
+      // member's records replayed as cuoptamd_solver_advance replays its own (halpern_burst_replay)
+      std::vector<pdlpdev_halpern_major_params> params(K);
+      std::vector<pdlpdev_halpern_major_record> rec(16 * (size_t)K);
+      std::vector<double> r_prev(K), r_prev_out(K);
+      std::vector<int32_t> written(K, 0);
+      for (int l = 0; l < K; ++l) {
+        if (target[l] <= 0) continue;
+        const cuoptamd_solver* s = b->s[l];
+        ahead[l]   = major_eval_request_at(s, target[l] + s->iteration_offset, s->ctl.its_since_restart + (target[l] - s->ctl.steps_taken));
+        params[l]  = halpern_burst_params(s);
+        theta[l]   = s->H.primal_weight_update_smoothing;
+        r_prev[l]  = s->halpern_r_prev;
+      }
+      int rc = pdlpdev_small_batch_run_halpern_burst(b->small, target.data(), b->s[0]->H.major_iteration, burst_count, ahead.data(), params.data(), theta.data(),
+                                                     r_prev.data(), rec.data(), written.data(), r_prev_out.data(), ctl.data(), hal.data());
+      if (rc != 0) return fail(rc, "pdlpdev_small_batch_run_halpern_burst: %s", pdlpdev_last_error());
+      for (int l = 0; l < K; ++l) {
+        if (target[l] <= 0) continue;
+        cuoptamd_solver* s = b->s[l];
+        s->ctl = ctl[l], s->hal = hal[l];
+        bool terminated = false;
+        rc = halpern_burst_replay(s, &rec[16 * (size_t)l], written[l], r_prev_out[l], &terminated);
+        if (rc != 0) return rc;
+        if (terminated) done[l] = 1;
+      }
+      continue;
+    }
     int rc = pdlpdev_small_batch_run(b->small, target.data(), ctl.data(), ahead.data(), ev.data(), ev_avg.data(), evaluated.data());
     if (rc != 0) return fail(rc, "pdlpdev_small_batch_run: %s", pdlpdev_last_error());
     for (int l = 0; l < K; ++l)
@@ -2152,6 +2217,36 @@ int cuoptamd_batch_solution_views(cuoptamd_batch* b, const double** x, const dou
   for (int l = 0; l < b->K; ++l) which[l] = (b->s[l]->empty_problem || !b->s[l]->dev) ? -1 : b->s[l]->returned_which;
   int rc_ = pdlpdev_small_batch_solution_views(b->small, which.data(), x, y, rc);
   if (rc_ != 0) return fail(rc_, "pdlpdev_small_batch_solution_views: %s", pdlpdev_last_error());
+  return 0;
+}
+
+int cuoptamd_batch_set_halpern_device_major(cuoptamd_batch* b, int32_t P)
+{
+  const char* const who = "cuoptamd_batch_set_halpern_device_major";
+  if (!b) return fail(-1, "%s: null batch", who);
+  if (P < 0 || P > 16)
+    return fail(-1, "%s: %s: %s must lie in 0 .. 16 (periods per host synchronisation), not %d", who, kHalpernName, kDeviceMajorName, (int)P);
+  if (!b->small || !b->halpern)
+    return fail(-7, "%s: %s is the K-workgroup batch's of resident LPs in the %s (halpern_batch), not %s", who, kDeviceMajorName, kHalpernName,
+                b->small ? "an averaging small-LP batch's" : "a lockstep batch's");
+  if (P > 0) {
+    for (int l = 0; l < b->K; ++l) {  // (the single solver's own refusals: the ray verdict and the acceptance set's snapshot are the host's)
+      const cuoptamd_settings& st = b->s[l]->S;
+      const char* bad = st.halpern_infeasibility ? "halpern_infeasibility" : st.accept_enabled ? "accept_tolerance (an enabled acceptance set)" : nullptr;
+      if (bad) return fail(-7, "%s: %s: LP %d: %s is not supported together with %s", who, kHalpernName, l, bad, kDeviceMajorName);
+    }
+    int rc = pdlpdev_small_batch_set_halpern_device_major(b->small, 1);
+    if (rc != 0) return fail(rc, "%s: %s: %s", who, kDeviceMajorName, pdlpdev_last_error());
+  }
+  b->device_major = P;
+  return 0;
+}
+int cuoptamd_batch_halpern_device_major(cuoptamd_batch* b) { return b ? b->device_major : 0; }
+int cuoptamd_batch_halpern_burst_stats(cuoptamd_batch* b, int64_t out[4])
+{
+  if (!b || !out) return fail(-1, "cuoptamd_batch_halpern_burst_stats: null argument");
+  if (!b->small) return fail(-7, "cuoptamd_batch_halpern_burst_stats: a batch of resident small LPs only");
+  DEV(pdlpdev_small_batch_halpern_burst_stats(b->small, out));
   return 0;
 }
 

@@ -7,6 +7,16 @@
 #include "pdlp_layouts.hpp"
 #include "resident_common.hpp"
 
+// p, which points to global memory, as a pointer the compiler knows that of (the empty statement keeps the two casts from cancelling
+// and names a scalar register: the value is uniform)
+template <class P>
+__device__ __forceinline__ P* as_global(P* p)
+{
+  __attribute__((address_space(1))) P* g = (__attribute__((address_space(1))) P*)p;
+  asm("" : "+s"(g));
+  return (P*)g;
+}
+
 // (HalpernSmallView, HalpernResidentArgs: resident_common.hpp -- the batch object in kernels_resident.hip holds the records)
 // resident_body's layout, lanes and barriers (B1 ... B5, B5 inside block_sum_fast) with the Halpern epilogues in the two row phases:
 //   * registers per owned element: x, x', A^T y, y, y' and the anchor x^0, y^0, A^T y^0 (loaded once; no running sums: no average);

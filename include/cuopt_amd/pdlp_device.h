@@ -592,6 +592,35 @@ int pdlpdev_halpern_burst_stats(pdlpdev_ctx* ctx, int64_t out[4]);
 int pdlpdev_debug_halpern_major_decide(int device, const double ev[PDLPDEV_EV_COUNT], const pdlpdev_ctl* ctl, const pdlpdev_halpern* hal,
                                        double r_prev, int32_t stopped, int32_t target, const pdlpdev_halpern_major_params* params,
                                        pdlpdev_halpern_major_record* record, double* r_prev_out, int32_t* stopped_out, int32_t* restart_out);
+/* ---- bursts of device-decided major iterations for a Halpern small-LP batch (cuoptamd_batch_set_halpern_device_major; the design
+ * note's "Bursts of a K-workgroup batch").  The structs are the single burst's.
+ * _set_halpern_device_major(on != 0): allocates, once, per member a burst block on the device, a slot for its parameters and a ring of
+ * 16 records in pinned host memory (K x 16 in all).  -7: not a Halpern batch, or a member that evaluates the infeasibility ray.
+ * _run_halpern_burst: `count` (1 .. 16) whole periods for every member with first_target[l] > 0 (<= 0: the member rests) -- period j
+ * runs member l to first_target[l] + j * period accepted steps.  In stream order, no kernel waiting for another:
+ * k_halpern_major_arm_batch; then per period k_pdhg_resident_halpern_burst_batch (one launch per resident tier in use),
+ * k_major_small_halpern_burst_batch (the evaluation rq[l] of T(z^k)), k_halpern_major_decide_batch (one wave per LP, params[l]) and
+ * the restart guarded per LP by its decision (k_halpern_major_restart_batch over an (LP, block) table that covers every member,
+ * k_halpern_major_restart_finish_batch with theta[l]); ONE synchronisation.  A member whose decision is not "go on" rests for the
+ * rest of the burst -- nothing of it that can be read back changes -- while the others go on.  records[16 l .. 16 l + written[l])
+ * receive member l's decisions in order, r_prev_out[l] what r_prev[l] has become, ctl[l] / hal[l] its two blocks (the last three
+ * may be NULL).  Each member gets, bit for bit, what pdlpdev_run_halpern_burst gives it on its own.  The caller must KNOW that no
+ * major iteration is due in front of first_target[l] and that the member's step error is down.  -7: not armed, or a first period
+ * that does not start inside.
+ * _halpern_burst_stats: out = {bursts, periods enqueued, records written, member-periods enqueued behind a member's stop}. */
+int pdlpdev_small_batch_set_halpern_device_major(pdlpdev_small_batch* batch, int on);
+int pdlpdev_small_batch_run_halpern_burst(pdlpdev_small_batch* batch, const int32_t* first_target, int32_t period, int32_t count,
+                                          const pdlpdev_small_eval* rq, const pdlpdev_halpern_major_params* params, const double* theta,
+                                          const double* r_prev, pdlpdev_halpern_major_record* records, int32_t* written,
+                                          double* r_prev_out, pdlpdev_ctl* ctl, pdlpdev_halpern* hal);
+int pdlpdev_small_batch_halpern_burst_stats(pdlpdev_small_batch* batch, int64_t out[4]);
+/* Parity hook: k_halpern_major_decide_batch ONCE over `count` cases as the members of one launch, each with blocks, parameters and sums of
+ * its own (arrays of `count` entries; ev: PDLPDEV_EV_COUNT doubles per case; records in/out); workgroup w serves member count - 1 - w.
+ * What pdlpdev_debug_halpern_major_decide gives per case.  Solves nothing. */
+int pdlpdev_debug_halpern_major_decide_batch(int device, int32_t count, const double* ev, const pdlpdev_ctl* ctl, const pdlpdev_halpern* hal,
+                                             const double* r_prev, const int32_t* stopped, const int32_t* target,
+                                             const pdlpdev_halpern_major_params* params, pdlpdev_halpern_major_record* records, double* r_prev_out,
+                                             int32_t* stopped_out, int32_t* restart_out);
 /* Read-only counters since create: out = {evaluations of the current iterate that read A^T y from the loop's buffer, ... that ran the
  * product, host synchronisations inside pdlpdev_run / pdlpdev_run_period / pdlpdev_major_eval, attempts enqueued that found their
  * target reached (empty launches)}.  Single-GPU, non-resident contexts. */

@@ -205,7 +205,7 @@ typedef struct cuoptamd_settings {
    * inside a period and a period that is due at once go through the host-decided path.  Refused together with it, with -7 and by
    * name, at creation and at reset (a refused reset leaves the solver as it was): halpern_infeasibility, an enabled acceptance set
    * (accept_tolerance), halpern_sharded or any world > 1, halpern_batch, halpern_lockstep; cuoptamd_batch_create refuses a member that
-   * has it set.  A value outside 0 .. 16 answers -1.  0 (default): the host decides after every period, as before.  Ignored when
+   * has it set (a K-workgroup batch takes the option as a whole: cuoptamd_batch_set_halpern_device_major).  A value outside 0 .. 16 answers -1.  0 (default): the host decides after every period, as before.  Ignored when
    * algorithm == 0. */
   int32_t halpern_device_major;
 } cuoptamd_settings;
@@ -364,6 +364,26 @@ void cuoptamd_batch_destroy(cuoptamd_batch* batch);
  * launches behind the loop, runs (periods), restart rounds, resets, synchronisations}; restart rounds and resets are counted for a batch
  * in reflected Halpern mode, and an averaging batch counts the synchronisations of its runs only; -7: not a small-LP batch */
 int cuoptamd_batch_stats(cuoptamd_batch* batch, int64_t out[8]);
+/* ---- major iterations of a K-workgroup Halpern batch decided on the device (docs/design/04d_halpern_mode.md, "Bursts of a K-workgroup
+ * batch").  An option of the BATCH, not a field of cuoptamd_settings: cuoptamd_batch_create keeps refusing a member that has
+ * halpern_device_major set, and halpern_device_major + halpern_batch in the settings stays refused.
+ * cuoptamd_batch_set_halpern_device_major(P), P = 1 .. 16: cuoptamd_batch_advance runs the batch in BURSTS -- up to P whole periods
+ * for all members enqueued with no wait in between, each member's verdict and restart decided on the device
+ * (pdlpdev_small_batch_run_halpern_burst), ONE synchronisation, then each member's records replayed on the host.  A round is a burst
+ * when every member that is not done is burst-ready: its next target is a period's end, it is past min_iteration_restart, at least
+ * one whole period fits its budget, no step error is pending and nothing waits to be prepared; the burst runs the fewest periods any
+ * member allows.  Any other round is the host-decided one, for all members.  Every member gets, bit for bit, what its own
+ * cuoptamd_solver_advance with halpern_device_major = 0 gives it.  The time limit is looked at between bursts.  P = 0: back to the
+ * host-decided round.  -1: P outside 0 .. 16 or a null batch.  -7, by name: a batch that is no K-workgroup Halpern batch (an
+ * averaging small-LP batch, either lockstep batch), a member with halpern_infeasibility, a member with an enabled acceptance set;
+ * a refused call leaves the batch as it was.  cuoptamd_batch_reset and cuoptamd_batch_branch keep the option.
+ * cuoptamd_batch_solve has nowhere to carry P and keeps the host-decided round.
+ * cuoptamd_batch_halpern_device_major: the P the batch runs with.
+ * cuoptamd_batch_halpern_burst_stats: out = {bursts, periods enqueued, records written, member-periods enqueued behind a member's
+ * stop}; cuoptamd_batch_stats counts one synchronisation per burst and the bursts' loop and evaluation launches. */
+int cuoptamd_batch_set_halpern_device_major(cuoptamd_batch* batch, int32_t P);
+int cuoptamd_batch_halpern_device_major(cuoptamd_batch* batch);
+int cuoptamd_batch_halpern_burst_stats(cuoptamd_batch* batch, int64_t out[4]);
 /* the device-layer batch behind it (pdlpdev_batch_time_kernels) */
 struct pdlpdev_batch* cuoptamd_batch_device(cuoptamd_batch* batch);
 
