@@ -334,6 +334,8 @@ _proto("cuoptamd_solver_create", c_int, P(c_void_p), P(LP), P(Hyper), P(SolverSe
 _proto("cuoptamd_solver_destroy", None, c_void_p)
 _proto("cuoptamd_solver_reset", c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, P(SolverSettings), c_void_p,
        c_void_p)
+_proto("cuoptamd_solver_reset_objective", c_int, c_void_p, c_void_p, c_double, c_void_p, c_void_p, c_void_p, c_void_p, P(SolverSettings),
+       c_void_p, c_void_p)
 _proto("cuoptamd_solver_advance", c_int, c_void_p, c_int, P(Result))
 _proto("cuoptamd_solver_get_solution", c_int, c_void_p, c_void_p, c_void_p, c_void_p)
 _proto("cuoptamd_solver_device", c_void_p, c_void_p)
@@ -361,6 +363,7 @@ _proto("pdlpdev_problem_norms", c_int, c_void_p, P(c_double), P(c_double))
 _proto("pdlpdev_weight_norms", c_int, c_void_p, c_int, c_void_p)
 _proto("pdlpdev_initial_solution_stats", c_int, c_void_p, c_void_p, c_void_p, c_void_p)
 _proto("pdlpdev_reset", c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p)
+_proto("pdlpdev_set_objective", c_int, c_void_p, c_void_p, c_void_p)
 if hasattr(lib, "pdlpdev_scaling_stats"):  # (an older build given through CUOPT_AMD_LIB does not count the scaling's launches)
     _proto("pdlpdev_scaling_stats", c_int, c_void_p, c_void_p)
 _proto("pdlpdev_set_step_params", c_int, c_void_p, P(StepParams))
@@ -423,6 +426,8 @@ _proto("cuoptamd_batch_create", c_int, c_void_p, c_int, P(c_void_p))
 _proto("cuoptamd_batch_advance", c_int, c_void_p, c_int, c_void_p)
 _proto("cuoptamd_batch_destroy", None, c_void_p)
 _proto("cuoptamd_batch_reset", c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p)
+_proto("cuoptamd_batch_reset_objectives", c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int)
+_proto("cuoptamd_batch_reset_stats", c_int, c_void_p, c_void_p)
 _proto("cuoptamd_batch_get_solutions", c_int, c_void_p, c_void_p, c_void_p, c_void_p)
 _proto("cuoptamd_batch_branch", c_int, c_void_p, c_void_p, c_void_p, c_void_p)
 _proto("cuoptamd_batch_solution_views", c_int, c_void_p, c_void_p, c_void_p, c_void_p)
@@ -861,6 +866,24 @@ class Solver:
             raise CuOptError(rc, lib.cuoptamd_last_error().decode())
         self.result = Result()
 
+    def reset_objective(self, c, objective_offset=0.0, lb=None, ub=None, lo=None, hi=None, init_x=None, init_y=None, **setting_overrides):
+        """cuoptamd_solver_reset_objective: reset() with a new objective vector (the caller's column order and sense, as at creation) and
+        offset on the same A; afterwards the solver is indistinguishable from one freshly created on the LP with that objective (the
+        feasibility pump's re-solve without set-up).  c=None: reset().  ValueError for a c of the wrong length."""
+        cc = None if c is None else _f64(c)
+        if cc is not None and cc.shape != (self.n,):
+            raise ValueError("reset_objective: c has %d entries, the LP %d columns" % (cc.size, self.n))
+        arrays = [None if a is None else _f64(a) for a in (lb, ub, lo, hi, init_x, init_y)]
+        st = None
+        if setting_overrides:
+            self.settings = default_settings(**setting_overrides)
+            st = C.byref(self.settings)
+        rc = lib.cuoptamd_solver_reset_objective(self.handle, _ptr(cc), float(objective_offset), _ptr(arrays[0]), _ptr(arrays[1]), _ptr(arrays[2]),
+                                                 _ptr(arrays[3]), st, _ptr(arrays[4]), _ptr(arrays[5]))
+        if rc != 0:
+            raise CuOptError(rc, lib.cuoptamd_last_error().decode())
+        self.result = Result()
+
     def advance(self, iterations=2 ** 31 - 1):
         rc = lib.cuoptamd_solver_advance(self.handle, int(iterations), C.byref(self.result))
         if rc != 0:
@@ -994,6 +1017,51 @@ class SharedMatrixBatch:
             raise CuOptError(rc, lib.cuoptamd_last_error().decode())
         for s in self.solvers:
             s.result = Result()
+
+    def reset_objectives(self, c, objective_offset=None, lb=None, ub=None, init_x=None, init_y=None, warm_from_last=False):
+        """cuoptamd_batch_reset_objectives: reset() with a new objective per solver (a list; an entry None keeps that solver's objective
+        and offset), scaled, reduced and turned into the initial primal weights on the device in front of the reset -- launches
+        independent of K, one synchronisation.  objective_offset: a list of floats (None: 0 for the solvers that get an objective).
+        warm_from_last: every solver starts from the point its last solve returned, as in branch().  Afterwards every solver is what
+        Solver.reset_objective would have made it.  ValueError for a list or a vector of the wrong length."""
+        k = len(self.solvers)
+        if c is not None and len(c) != k:
+            raise ValueError("reset_objectives: %d objectives for %d solvers" % (len(c), k))
+        if objective_offset is not None and len(objective_offset) != k:
+            raise ValueError("reset_objectives: %d offsets for %d solvers" % (len(objective_offset), k))
+        keep = []
+
+        def ptrs(vs, what, size):
+            if vs is None:
+                return None
+            if len(vs) != k:
+                raise ValueError("reset_objectives: %s has %d entries for %d solvers" % (what, len(vs), k))
+            arr = (c_void_p * k)()
+            for i, v in enumerate(vs):
+                if v is not None:
+                    a = _f64(v)
+                    if a.shape != (size(self.solvers[i]),):
+                        raise ValueError("reset_objectives: %s[%d] has %d entries, expected %d" % (what, i, a.size, size(self.solvers[i])))
+                    keep.append(a)
+                    arr[i] = a.ctypes.data
+            return arr
+        cols, rows = (lambda s: s.n), (lambda s: s.m)
+        args = (ptrs(c, "c", cols), ptrs(lb, "lb", cols), ptrs(ub, "ub", cols), ptrs(init_x, "init_x", cols), ptrs(init_y, "init_y", rows))
+        off = None if objective_offset is None else _f64([0.0 if v is None else v for v in objective_offset])
+        self._views, self._view_key = None, None  # (the staging block is rewritten: views handed out before are not returned again)
+        rc = lib.cuoptamd_batch_reset_objectives(self.handle, args[0], _ptr(off), args[1], args[2], args[3], args[4], int(bool(warm_from_last)))
+        if rc != 0:
+            raise CuOptError(rc, lib.cuoptamd_last_error().decode())
+        for s in self.solvers:
+            s.result = Result()
+
+    def reset_stats(self):
+        """cuoptamd_batch_reset_stats of a small-LP batch: dict launches / syncs of all reset(), branch() and reset_objectives() calls"""
+        out = np.zeros(2, np.int64)
+        rc = lib.cuoptamd_batch_reset_stats(self.handle, _ptr(out))
+        if rc != 0:
+            raise CuOptError(rc, lib.cuoptamd_last_error().decode())
+        return dict(zip(("launches", "syncs"), out.tolist()))
 
     def branch(self, var, lb, ub):
         """cuoptamd_batch_branch: variable var[l] of solver l gets the bounds [lb[l], ub[l]] (var[l] < 0: none), every solver starts again
@@ -1480,6 +1548,16 @@ class Device:
         lb, ub, lo, hi = (None if v is None else _f64(v) for v in (lb, ub, lo, hi))
         self._ck(lib.pdlpdev_reset(self.handle, _ptr(lb), _ptr(ub), _ptr(lo), _ptr(hi)))
         self._ck(lib.pdlpdev_synchronize(self.handle))  # (the copies are asynchronous and the arrays are this call's own)
+
+    def set_objective(self, c):
+        """pdlpdev_set_objective: a new objective (the device's column order, minimise sense) written in place -> (sum c_j^2 of the
+        unscaled, of the scaled objective); iterate and loop state are not touched.  ValueError for a wrong length where it is known."""
+        cc, out = _f64(c), np.zeros(2)
+        n = getattr(self, "n", None)
+        if cc.ndim != 1 or (n is not None and cc.size != n):
+            raise ValueError("set_objective: c has shape %s, the LP %s columns" % (cc.shape, n))
+        self._ck(lib.pdlpdev_set_objective(self.handle, _ptr(cc), _ptr(out)))
+        return float(out[0]), float(out[1])
 
     def scaling_stats(self):
         """pdlpdev_scaling_stats: kernel launches of scaling_compute / scale_problem per site -> {"A" / "At": {"max" / "sum" / "scale":

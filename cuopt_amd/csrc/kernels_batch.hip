@@ -790,7 +790,7 @@ int pdlpdev_batch_create(pdlpdev_batch** out, pdlpdev_ctx** ctx, int K)
     if (halpern) b->hl_host.push_back(batch_halpern_lp_of(c)), b->ray_host.push_back(batch_ray_lp_of(c));
     b->ray_single0[l] = c->stat_single_rays;
     dargs[l] = pdlpdev_decision_args{c->ctl, c->A.part, side[0].W, c->At.part, side[1].W, c->sp};
-    c->batches_alive += 1;
+    c->batches_alive += 1, c->lockstep_batches_alive += 1;
   }
   HIP_TRY(hipMalloc((void**)&b->lp_dev, K * sizeof(BatchLp)));
   HIP_TRY(hipMalloc((void**)&b->xK, ((size_t)c0->n * K + 64) * sizeof(double)));
@@ -816,7 +816,7 @@ void pdlpdev_batch_destroy(pdlpdev_batch* b)
 {
   if (!b) return;
   for (int l = 0; l < b->K; ++l)
-    if (b->ctx[l]) b->ctx[l]->batches_alive -= 1;
+    if (b->ctx[l]) b->ctx[l]->batches_alive -= 1, b->ctx[l]->lockstep_batches_alive -= 1;
   (void)hipSetDevice(b->device);
   if (b->stream) (void)hipStreamSynchronize(b->stream);
   for (auto& kv : b->graphs) (void)hipGraphExecDestroy(kv.second);

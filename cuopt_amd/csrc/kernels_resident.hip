@@ -402,6 +402,7 @@ struct SmallResetArgs {
   double *x[2], *aty[2], *rc[2], *y[2], *xbar, *sumx, *avgx, *lrx, *sumy, *avgy, *lry;
   pdlpdev_ctl *ctl, *ctl_host;
   double step, weight;
+  const double* weight_dev;  // non-NULL: the weight k_small_objective_finish left on the device (a new objective), not `weight`
 };
 __global__ void __launch_bounds__(512) k_small_reset_batch(const SmallResetArgs* __restrict__ args, const int* __restrict__ list)
 {
@@ -433,9 +434,46 @@ __global__ void __launch_bounds__(512) k_small_reset_batch(const SmallResetArgs*
   if (threadIdx.x == 0) {
     pdlpdev_ctl c;
     memset(&c, 0, sizeof(c));
-    c.step_size = A.step, c.primal_weight = A.weight, c.tau = A.step / A.weight, c.sigma = A.step * A.weight;  // k_set_step
+    const double w = A.weight_dev ? *A.weight_dev : A.weight;
+    c.step_size = A.step, c.primal_weight = w, c.tau = A.step / w, c.sigma = A.step * w;  // k_set_step
     if (A.k >= 0) c.k = A.k;
     *A.ctl = c, *A.ctl_host = c;
+  }
+}
+// New objectives for the LPs of a batch (pdlpdev_small_batch_reset_objectives) in front of k_small_reset_batch, no host in between.
+// k_small_objective_batch: workgroup <-> (LP, block of the LP's virtual grid min(grid_for(n), kGenericBlocks)) -- per LP exactly
+// k_set_objective's launch, from the staging block.  k_small_objective_finish: workgroup <-> LP -- k_finalize's tree over both rows of
+// partials, then the initial primal weight (pdlp.cu:1260-1309) as the host forms it, sqrt and the division being correctly rounded on
+// both sides; weight_host >= 0 (cuoptamd_settings::initial_primal_weight) overrides what the reset takes, not what is reported.
+struct SmallObjectiveArgs {
+  int n, g, unscaled_sum;  // unscaled_sum: the weight's sum is sum c_u^2 (compute_initial_primal_weight_before_scaling), else sum c^2
+  const double* src;       // staging: the new objective, minimise sense, the device's column order
+  double *c_u, *c;
+  const double* dc;
+  double *part, *scal, *scal_h;  // scal / scal_h [kObjSums .. +3): sum c_u^2, sum c^2, the computed weight; scal[kObjWeight]: the one to use
+  double sum_b, c_scaling, b_scaling, importance, weight_host;
+};
+constexpr int kObjSums = 42, kObjWeight = 45;
+__global__ void __launch_bounds__(kBlock) k_small_objective_batch(const SmallObjectiveArgs* __restrict__ args, const int2* __restrict__ blk)
+{
+  __shared__ double red[8];
+  const int2 w                = blk[blockIdx.x];
+  const SmallObjectiveArgs& A = args[w.x];
+  set_objective_block(A.n, A.src, A.c_u, A.c, A.dc, A.part, w.y, A.g, red);
+}
+__global__ void __launch_bounds__(kBlock) k_small_objective_finish(const SmallObjectiveArgs* __restrict__ args, const int* __restrict__ list)
+{
+  __shared__ double red[8];
+  __shared__ double sums[2];
+  const SmallObjectiveArgs& A = args[list[blockIdx.x]];
+  finalize_rows(A.part, A.g, 2, 0u, sums, red);
+  if (threadIdx.x == 0) {
+    const double cn = sqrt(A.c_scaling * (A.unscaled_sum ? sums[0] : sums[1]));
+    const double bn = sqrt(A.b_scaling * A.sum_b);
+    const double w  = (bn > 0.0 && cn > 0.0) ? A.importance * (cn / bn) : A.importance;
+    A.scal[kObjSums] = sums[0], A.scal[kObjSums + 1] = sums[1], A.scal[kObjSums + 2] = w;
+    A.scal_h[kObjSums] = sums[0], A.scal_h[kObjSums + 1] = sums[1], A.scal_h[kObjSums + 2] = w;
+    A.scal[kObjWeight] = A.weight_host >= 0.0 ? A.weight_host : w;
   }
 }
 // pdlpdev_get_solution for K LPs: x = x^ * D_c, y = y^ * D_r (k_unscale), reduced costs as they are -- straight into the staging block
@@ -477,8 +515,11 @@ struct pdlpdev_small_batch {
   StreamAtCurArgs* at = nullptr;
   CtlOp* ops = nullptr;
   SmallResetArgs* reset = nullptr;
+  SmallObjectiveArgs* obj = nullptr;  // pdlpdev_small_batch_reset_objectives: the records and the (LP, block) table of its own (blk is
+  int2* obj_blk = nullptr;            // rewritten by a Halpern reset's tail while the objective kernel may still wait in the stream)
+  int obj_blocks_cap = 0;
   SmallSolutionArgs* sol = nullptr;
-  double* staging = nullptr;  // 3 n + m doubles per LP (new bounds + initial iterate in, solutions out), LP l at stage_off[l]
+  double* staging = nullptr;  // 4 n + m doubles per LP (new bounds + initial iterate in, solutions out; behind them a new objective), LP l at stage_off[l]
   std::vector<size_t> stage_off;
   // A batch of LPs in reflected Halpern mode (pdlpdev_small_batch_create_halpern): the loop, its evaluation and the restart are
   // kernels_resident_halpern.hip's, their records sit in the same pinned block; blk holds 2 * at_blocks_cap entries (a reset
@@ -490,6 +531,7 @@ struct pdlpdev_small_batch {
   // pass of a run in either mode; for a Halpern batch also restart rounds and resets, and one synchronisation per restart round, reset
   // and separate pdlpdev_small_batch_major_eval
   int64_t stat_loop_launches = 0, stat_eval_launches = 0, stat_periods = 0, stat_restart_rounds = 0, stat_resets = 0, stat_syncs = 0;
+  int64_t stat_reset_launches = 0, stat_reset_syncs = 0;  // pdlpdev_small_batch_reset_stats: of every reset call, in either mode
   // pdlpdev_small_batch_set_halpern_device_major: per member a burst block on the device (hmaj[l]); in one pinned block of their own
   // the members' burst records (burst[l]: params, theta, views) and the ring of 16 decision records per member (ring[16 l + j])
   pdlpdev_halpern_major_state* hmaj = nullptr;
@@ -565,24 +607,27 @@ static int small_batch_create(pdlpdev_small_batch** out, pdlpdev_ctx** ctx, int 
   b->device = ctx[0]->device, b->K = K, b->halpern = halpern;
   b->ctx.assign(ctx, ctx + K);
   HIP_TRY(hipSetDevice(b->device));
-  int blocks = 0;
+  int blocks = 0, obj_blocks = 0;
   for (int l = 0; l < K; ++l) {
+    obj_blocks += std::min(grid_for(ctx[l]->n), kGenericBlocks);
     b->tier.push_back(resident_tier(ctx[l]->m, ctx[l]->n, ctx[l]->nnz));
     b->major_lds = std::max(b->major_lds, sizeof(double) * (size_t)std::max<int64_t>(ctx[l]->nnz, 1));
     blocks += std::max(ctx[l]->At.nb, std::min(grid_for(std::max(ctx[l]->n, ctx[l]->m)), kGenericBlocks));
   }
   b->at_blocks_cap = blocks;
+  b->obj_blocks_cap = obj_blocks;
   auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
   const size_t o_run = 0, o_list3 = o_run + up(sizeof(ResidentArgs) * K), o_major = o_list3 + up(sizeof(int) * 3 * K),
                o_list = o_major + up(sizeof(MajorSmallArgs) * K), o_restart = o_list + up(sizeof(int) * K),
                o_blk = o_restart + up(sizeof(RestartBatchArgs) * K), o_at = o_blk + up(sizeof(int2) * (size_t)blocks * (halpern ? 2 : 1)),
                o_ops = o_at + up(sizeof(StreamAtCurArgs) * K), o_reset = o_ops + up(sizeof(CtlOp) * K), o_sol = o_reset + up(sizeof(SmallResetArgs) * K),
                o_hrun = o_sol + up(sizeof(SmallSolutionArgs) * K), o_hrestart = o_hrun + (halpern ? up(sizeof(HalpernResidentArgs) * K) : 0),
-               o_stage = o_hrestart + (halpern ? up(sizeof(HalpernRestartArgs) * K) : 0);
+               o_obj = o_hrestart + (halpern ? up(sizeof(HalpernRestartArgs) * K) : 0), o_objblk = o_obj + up(sizeof(SmallObjectiveArgs) * K),
+               o_stage = o_objblk + up(sizeof(int2) * (size_t)obj_blocks + sizeof(int) * K);
   size_t total = o_stage;
   for (int l = 0; l < K; ++l) {
     b->stage_off.push_back((total - o_stage) / sizeof(double));
-    total += up(sizeof(double) * (3 * (size_t)ctx[l]->n + (size_t)ctx[l]->m));
+    total += up(sizeof(double) * (4 * (size_t)ctx[l]->n + (size_t)ctx[l]->m));
   }
   HIP_TRY(hipHostMalloc(&b->pinned, total, hipHostMallocDefault));
   char* base  = (char*)b->pinned;
@@ -590,6 +635,7 @@ static int small_batch_create(pdlpdev_small_batch** out, pdlpdev_ctx** ctx, int 
   b->list = (int*)(base + o_list), b->restart = (RestartBatchArgs*)(base + o_restart), b->blk = (int2*)(base + o_blk);
   b->at = (StreamAtCurArgs*)(base + o_at), b->ops = (CtlOp*)(base + o_ops);
   b->reset = (SmallResetArgs*)(base + o_reset), b->sol = (SmallSolutionArgs*)(base + o_sol), b->staging = (double*)(base + o_stage);
+  b->obj = (SmallObjectiveArgs*)(base + o_obj), b->obj_blk = (int2*)(base + o_objblk);
   if (halpern) b->hrun = (HalpernResidentArgs*)(base + o_hrun), b->hrestart = (HalpernRestartArgs*)(base + o_hrestart);
   HIP_TRY(hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
   TRY(major_lds_attribute(b->device));
@@ -951,17 +997,25 @@ int pdlpdev_small_batch_prepare(pdlpdev_small_batch* b, const int32_t* clear_err
 // (UNSCALED; NULL = zeros), the projection of the initial primal (project != 0); ctl[l] receives the control block.  What
 // pdlpdev_reset(lb, ub, NULL, NULL), pdlpdev_set_step, pdlpdev_set_k, pdlpdev_set_initial, pdlpdev_project_primal and pdlpdev_get_ctl
 // do for one LP, bit for bit, in ONE launch.
-int pdlpdev_small_batch_reset(pdlpdev_small_batch* b, const int32_t* take, const double* const* lb, const double* const* ub, const double* const* x0,
-                              const double* const* y0, const double* step, const double* weight, const int32_t* k, int project, pdlpdev_ctl* ctl,
-                              const int32_t* var, const double* var_lb, const double* var_ub, const int32_t* warm)
+// (obj != NULL: pdlpdev_small_batch_reset_objectives -- LPs with obj->c[l] get the new objective and the device's weight first)
+struct SmallBatchObjectives {
+  const double* const* c;
+  const double *sum_b, *c_scaling, *b_scaling, *importance;
+  const int32_t* unscaled_sum;
+  double *sum_cu, *sum_c, *computed_weight;  // out, per LP with an objective
+};
+static int small_batch_reset_impl(pdlpdev_small_batch* b, const char* who, const SmallBatchObjectives* obj, const int32_t* take, const double* const* lb,
+                                  const double* const* ub, const double* const* x0, const double* const* y0, const double* step, const double* weight,
+                                  const int32_t* k, int project, pdlpdev_ctl* ctl, const int32_t* var, const double* var_lb, const double* var_ub,
+                                  const int32_t* warm)
 {
   HIP_TRY(hipSetDevice(b->device));
-  int count = 0;
+  int count = 0, nobj = 0, obj_blocks = 0;
   for (int l = 0; l < b->K; ++l) {
     if (!take[l]) continue;
     pdlpdev_ctx* c = b->ctx[l];
-    if (!c->scaled) return fail(-1, "pdlpdev_small_batch_reset: LP %d has not been scaled yet", l);
-    if (c->rows_aliased || c->clones_alive > 0) return fail(-7, "pdlpdev_small_batch_reset: LP %d shares arrays with clones", l);
+    if (!c->scaled) return fail(-1, "%s: LP %d has not been scaled yet", who, l);
+    if (c->rows_aliased || c->clones_alive > 0) return fail(-7, "%s: LP %d shares arrays with clones", who, l);
     c->rejected_in_a_row = 0;
     const size_t n = (size_t)c->n, m = (size_t)c->m;
     double* st     = b->staging + b->stage_off[l];
@@ -972,26 +1026,88 @@ int pdlpdev_small_batch_reset(pdlpdev_small_batch* b, const int32_t* take, const
     if (y0 && y0[l]) memcpy(st + 3 * n, y0[l], m * sizeof(double)), sy = st + 3 * n;
     c->note_uniform_bounds(lb ? lb[l] : nullptr, ub ? ub[l] : nullptr);
     const int v = var ? var[l] : -1, wm = warm ? warm[l] : -1;
-    if (v >= c->n) return fail(-1, "pdlpdev_small_batch_reset: LP %d has no variable %d", l, v);
+    if (v >= c->n) return fail(-1, "%s: LP %d has no variable %d", who, l, v);
     if (v >= 0) c->ubd.lb_same = 0, c->ubd.ub_same = 0;  // (one bound differs from the others now, or may)
-    if (wm == PDLPDEV_BEST && !c->bestx) return fail(-1, "pdlpdev_small_batch_reset: LP %d saved no best iterate to start from", l);
+    if (wm == PDLPDEV_BEST && !c->bestx) return fail(-1, "%s: LP %d saved no best iterate to start from", who, l);
     b->reset[l] = SmallResetArgs{c->n, c->m, k ? k[l] : -1, project, v, wm, v >= 0 ? var_lb[l] : 0.0, v >= 0 ? var_ub[l] : 0.0, c->bestx, c->besty,
                                  slb, sub, sx, sy, c->lb_u, c->ub_u, c->lb, c->ub, c->dc, c->dr,
                                  {c->x[0], c->x[1]}, {c->aty[0], c->aty[1]}, {c->rc[0], c->rc[1]}, {c->y[0], c->y[1]}, c->xbar, c->sumx, c->avgx, c->lrx,
-                                 c->sumy, c->avgy, c->lry, c->ctl, c->ctl_h, step[l], weight[l]};
+                                 c->sumy, c->avgy, c->lry, c->ctl, c->ctl_h, step[l], weight[l], nullptr};
+    if (obj && obj->c[l]) {
+      if (c->shared_with_parent || c->lockstep_batches_alive > 0) return fail(-7, "%s: LP %d shares its objective with other contexts", who, l);
+      double* sc = st + 3 * n + m;
+      memcpy(sc, obj->c[l], n * sizeof(double));
+      const int g = std::min(grid_for(c->n), kGenericBlocks);  // (pdlpdev_set_objective's grid for this n)
+      b->obj[l]   = SmallObjectiveArgs{c->n, g, obj->unscaled_sum[l], sc, c->c_u, c->c, c->dc, c->part_g, c->scal, c->scal_h,
+                                     obj->sum_b[l], obj->c_scaling[l], obj->b_scaling[l], obj->importance[l], weight[l]};
+      b->reset[l].weight_dev = c->scal + kObjWeight;
+      for (int i = 0; i < g; ++i) b->obj_blk[obj_blocks++] = make_int2(l, i);
+      nobj += 1;
+    }
     b->list[count++] = l;
   }
   if (!count) return 0;
+  if (nobj) {
+    int* olist = (int*)(b->obj_blk + b->obj_blocks_cap);  // (the LPs with an objective: K entries behind the table)
+    int q = 0;
+    for (int i = 0; i < count; ++i)
+      if (b->reset[b->list[i]].weight_dev) olist[q++] = b->list[i];
+    k_small_objective_batch<<<obj_blocks, kBlock, 0, b->stream>>>(b->obj, b->obj_blk);
+    k_small_objective_finish<<<nobj, kBlock, 0, b->stream>>>(b->obj, olist);
+    b->stat_reset_launches += 2;
+  }
   k_small_reset_batch<<<count, 512, 0, b->stream>>>(b->reset, b->list);
+  b->stat_reset_launches += 1;
   HIP_TRY(hipGetLastError());
   if (b->halpern) {
     TRY(halpern_batch_reset_tail(b, count));
     b->stat_resets += 1, b->stat_syncs += 1;
+    b->stat_reset_launches += 3;  // (A^T y of the starting points, k_restart_batch, the restart's finish -- halpern_batch_reset_tail)
   }
   HIP_TRY(hipStreamSynchronize(b->stream));
+  b->stat_reset_syncs += 1;
   if (ctl)
     for (int l = 0; l < b->K; ++l)
       if (take[l]) ctl[l] = *b->ctx[l]->ctl_h;
+  if (obj)
+    for (int l = 0; l < b->K; ++l)
+      if (take[l] && obj->c[l]) {
+        const double* sh = b->ctx[l]->scal_h + kObjSums;
+        if (obj->sum_cu) obj->sum_cu[l] = sh[0];
+        if (obj->sum_c) obj->sum_c[l] = sh[1];
+        if (obj->computed_weight) obj->computed_weight[l] = sh[2];
+      }
+  return 0;
+}
+int pdlpdev_small_batch_reset(pdlpdev_small_batch* b, const int32_t* take, const double* const* lb, const double* const* ub, const double* const* x0,
+                              const double* const* y0, const double* step, const double* weight, const int32_t* k, int project, pdlpdev_ctl* ctl,
+                              const int32_t* var, const double* var_lb, const double* var_ub, const int32_t* warm)
+{
+  return small_batch_reset_impl(b, "pdlpdev_small_batch_reset", nullptr, take, lb, ub, x0, y0, step, weight, k, project, ctl, var, var_lb, var_ub, warm);
+}
+// pdlpdev_small_batch_reset with new objectives: c[l] (n doubles, minimise sense, the device's column order; NULL: LP l keeps its
+// objective and takes weight[l], exactly pdlpdev_small_batch_reset's path).  An LP with c[l] gets, per LP bit for bit,
+// pdlpdev_set_objective(c[l]) and then the initial primal weight formed ON THE DEVICE from the sum that unscaled_sum[l] selects, the
+// host's sum_b[l] and the three hyper-parameters; weight[l] >= 0 there is an override the reset takes instead (weight[l] < 0: none).
+// No host round trip between objective and reset, launches independent of K, the one synchronisation of pdlpdev_small_batch_reset.
+// sum_cu / sum_c / computed_weight (each may be NULL) receive, for the LPs with c[l], both sums and the weight as computed.
+int pdlpdev_small_batch_reset_objectives(pdlpdev_small_batch* b, const int32_t* take, const double* const* c, const double* const* lb, const double* const* ub,
+                                         const double* const* x0, const double* const* y0, const double* step, const double* weight, const int32_t* k,
+                                         int project, pdlpdev_ctl* ctl, const int32_t* var, const double* var_lb, const double* var_ub, const int32_t* warm,
+                                         const double* sum_b, const double* c_scaling, const double* b_scaling, const double* importance,
+                                         const int32_t* unscaled_sum, double* sum_cu, double* sum_c, double* computed_weight)
+{
+  const char* const who = "pdlpdev_small_batch_reset_objectives";
+  if (!b || !take || !step || !weight) return fail(-1, "%s: null argument", who);
+  if (!c) return small_batch_reset_impl(b, who, nullptr, take, lb, ub, x0, y0, step, weight, k, project, ctl, var, var_lb, var_ub, warm);
+  if (!sum_b || !c_scaling || !b_scaling || !importance || !unscaled_sum) return fail(-1, "%s: null argument", who);
+  const SmallBatchObjectives obj{c, sum_b, c_scaling, b_scaling, importance, unscaled_sum, sum_cu, sum_c, computed_weight};
+  return small_batch_reset_impl(b, who, &obj, take, lb, ub, x0, y0, step, weight, k, project, ctl, var, var_lb, var_ub, warm);
+}
+int pdlpdev_small_batch_reset_stats(pdlpdev_small_batch* b, int64_t out[2])
+{
+  if (!b || !out) return fail(-1, "pdlpdev_small_batch_reset_stats: null argument");
+  out[0] = b->stat_reset_launches, out[1] = b->stat_reset_syncs;
   return 0;
 }
 

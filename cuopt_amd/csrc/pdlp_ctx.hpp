@@ -562,6 +562,7 @@ struct CtxOwned {
   int clones_alive = 0;             // contexts that alias this one's arrays
   bool rows_private = false;        // a parent whose lo / hi were re-allocated by a reset AFTER its last clone was made: no clone aliases them
   int batches_alive = 0;            // pdlpdev_batch / pdlpdev_small_batch objects that hold this context's pointer
+  int lockstep_batches_alive = 0;   // ... the pdlpdev_batch objects among them: their kb_* kernels read ONE objective for all members
   std::map<int, hipGraphExec_t> graphs;  // attempts-per-replay -> executable graph
   std::vector<void*> allocs;
   int64_t bytes = 0;

@@ -832,6 +832,36 @@ int pdlpdev_reset(pdlpdev_ctx* ctx, const double* lb, const double* ub, const do
   LAUNCH_CHECK();
   return 0;
 }
+// A new objective for the SAME matrix and bounds (the feasibility pump's distance objectives, feasibility_pump.cu:145-249): one upload
+// into c_u, one kernel that scales it into c (k_scale_vectors' expression) and leaves the partials of both sums of squares, one
+// k_finalize.  Both arrays are overwritten in place -- every kernel argument list and captured graph keeps reading the same addresses --
+// and D_c depends on A only, so nothing else of the context moves.  sums = {sum c_u^2, sum c^2}: the bits reduce_vec(1, n, c_u / c) gives.
+__global__ void __launch_bounds__(kBlock) k_set_objective(int n, double* c_u, double* c, const double* __restrict__ dc, double* __restrict__ part)
+{
+  __shared__ double red[8];
+  set_objective_block(n, c_u, c_u, c, dc, part, blockIdx.x, gridDim.x, red);
+}
+int pdlpdev_set_objective(pdlpdev_ctx* ctx, const double* c, double sums[2])
+{
+  if (!ctx || !c) return fail(-1, "pdlpdev_set_objective: null argument");
+  // c and c_u belong to the part a clone shares: refused, before anything is written, wherever they are not this context's alone
+  if (ctx->clones_alive > 0) return fail(-7, "pdlpdev_set_objective: %d live clone(s) share this context's objective", ctx->clones_alive);
+  if (ctx->shared_with_parent) return fail(-7, "pdlpdev_set_objective: a clone shares its parent's objective");
+  if (ctx->lockstep_batches_alive > 0) return fail(-7, "pdlpdev_set_objective: a member of a lockstep batch (pdlpdev_batch_*) shares the batch's objective");
+  if (ctx->comm) return fail(-7, "pdlpdev_set_objective: sharded contexts are not supported");
+  if (!ctx->scaled) return fail(-1, "pdlpdev_set_objective: the problem has not been scaled yet");
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  const int n   = ctx->n;
+  if (n > 0) HIP_TRY(hipMemcpyAsync(ctx->c_u, c, (size_t)n * sizeof(double), hipMemcpyHostToDevice, s));
+  const int g = std::min(grid_for(n), kGenericBlocks);  // (reduce_vec's grid: the same partials)
+  k_set_objective<<<g, kBlock, 0, s>>>(n, ctx->c_u, ctx->c, ctx->dc, ctx->part_g);
+  k_finalize<<<1, kBlock, 0, s>>>(ctx->part_g, g, 2, 0u, ctx->scal);
+  LAUNCH_CHECK();
+  TRY(fetch_scalars(ctx, 2));
+  if (sums) sums[0] = ctx->scal_h[0], sums[1] = ctx->scal_h[1];
+  return 0;
+}
 // out[0] = sum c_j^2, out[1] = sum bcomb_i^2 of the scaled (unscaled != 0: the user's) problem
 int pdlpdev_weight_norms(pdlpdev_ctx* ctx, int unscaled, double out[2])
 {

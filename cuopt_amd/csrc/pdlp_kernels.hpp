@@ -484,6 +484,29 @@ __device__ __forceinline__ void finalize_rows(const double* __restrict__ part, i
   }
 }
 
+// A new objective for an already scaled problem (pdlpdev_set_objective; the small-LP batch runs it per (LP, block) inside one launch):
+// c_u <- src (when src is not c_u itself), c <- c_u * D_c -- k_scale_vectors' expression -- and, in the same pass, this workgroup's
+// partials of sum c_u^2 (part[bid]) and sum c^2 (part[nblocks + bid]).  Workgroup `bid` of `nblocks` takes the columns k_reduce<1> gives
+// it, in its order, so k_finalize over either row of partials ends on the bits of reduce_vec(1, n, c_u / c).  No atomics.
+__device__ __forceinline__ void set_objective_block(int n, const double* src, double* c_u, double* c, const double* __restrict__ dc, double* __restrict__ part, int bid,
+                                                    int nblocks, double* red /* >= 8 */)
+{
+  double acc[2] = {0.0, 0.0};
+  for (int64_t i = bid * (int64_t)kBlock + threadIdx.x; i < n; i += (int64_t)nblocks * kBlock) {
+    const double v = src[i];
+    if (src != c_u) c_u[i] = v;
+    const double sc = v * dc[i];
+    c[i] = sc;
+    acc[0] += v * v;
+    acc[1] += sc * sc;
+  }
+  block_reduce<SumOp, 2>(acc, red);
+  if (threadIdx.x == 0) {
+    part[bid]           = acc[0];
+    part[nblocks + bid] = acc[1];
+  }
+}
+
 // restart: squared distances to the last-restart anchors, candidate -> iterate / anchors, sums <- 0
 // (pdlp_restart_strategy.cu:593-623,752-839).  Workgroup `bid` of `nblocks` (k_restart: blockIdx.x of gridDim.x).
 struct RestartView {

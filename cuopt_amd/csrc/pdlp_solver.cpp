@@ -140,6 +140,7 @@ struct SolverProblem {
   double objective_scale = 1.0, objective_offset = 0.0;
   double norm_b = 0.0, norm_c = 0.0;
   double computed_step = 0.0, computed_weight = 0.0;  // compute_initial_step_size / _primal_weight, before overrides
+  double weight_sum_b = 0.0;  // the row-bound sum of computed_weight (scaled, or unscaled with compute_initial_primal_weight_before_scaling): kept for a new objective
   // reflected Halpern mode: what the power iteration found
   double sigma_max = 0.0;
   int32_t power_products = 0;
@@ -1395,6 +1396,7 @@ int cuoptamd_solver_create(cuoptamd_solver** out, const cuoptamd_lp* lp, const c
     double nr[3];
     DEV(pdlpdev_init_norms(s->dev, nr));
     const double cn = std::sqrt(hyper->initial_primal_weight_c_scaling * nr[1]);
+    s->weight_sum_b = nr[2];
     const double bn = std::sqrt(hyper->initial_primal_weight_b_scaling * nr[2]);
     weight = (bn > 0.0 && cn > 0.0) ? hyper->primal_importance * (cn / bn) : hyper->primal_importance;
     return 0;
@@ -1460,20 +1462,36 @@ static void reset_host_state(cuoptamd_solver* s)
   s->best_quality.objective = s->maximize ? -std::numeric_limits<double>::infinity() : std::numeric_limits<double>::infinity();  // pdlp.cu:183-185
 }
 
-int cuoptamd_solver_reset(cuoptamd_solver* s, const double* lb, const double* ub, const double* lo, const double* hi,
-                          const cuoptamd_settings* settings, const double* init_x, const double* init_y)
+// cuoptamd_solver_reset (c == NULL) and cuoptamd_solver_reset_objective: c in the caller's sense and column order
+static int solver_reset_impl(cuoptamd_solver* s, const char* who, const double* c, double objective_offset, const double* lb, const double* ub,
+                             const double* lo, const double* hi, const cuoptamd_settings* settings, const double* init_x, const double* init_y)
 {
-  if (!s) return fail(-1, "cuoptamd_solver_reset: null solver");
   const auto t0 = clock_type::now();
   if (settings && halpern_mode(s))  // (refused before anything of the solver changes: it stays usable with its present settings)
-    if (const char* bad = halpern_refused_setting(settings)) return fail(-7, "cuoptamd_solver_reset: %s: %s is not supported", kHalpernName, bad);
+    if (const char* bad = halpern_refused_setting(settings)) return fail(-7, "%s: %s: %s is not supported", who, kHalpernName, bad);
   if (settings && halpern_mode(s))
-    if (int rc = halpern_device_major_check("cuoptamd_solver_reset", settings, s->world > 1 || s->behind_comm)) return rc;
+    if (int rc = halpern_device_major_check(who, settings, s->world > 1 || s->behind_comm)) return rc;
   if (settings && halpern_mode(s) && (s->world > 1 || s->behind_comm)) {  // (a sharded solver of the mode: likewise before anything changes)
-    if (!settings->halpern_sharded) return fail(-7, "cuoptamd_solver_reset: %s: a sharded solver needs halpern_sharded to stay set", kHalpernName);
+    if (!settings->halpern_sharded) return fail(-7, "%s: %s: a sharded solver needs halpern_sharded to stay set", who, kHalpernName);
     if (const char* bad = halpern_sharded_refused_setting(settings))
-      return fail(-7, "cuoptamd_solver_reset: %s: %s is not supported together with halpern_sharded (a sharded solver)", kHalpernName, bad);
+      return fail(-7, "%s: %s: %s is not supported together with halpern_sharded (a sharded solver)", who, kHalpernName, bad);
   }
+  // The new objective goes first: the device layer refuses it, before it writes anything, where c is not this solver's alone (clones, a
+  // lockstep batch), and the solver then stays as it was, settings included.
+  double csum[2] = {0.0, 0.0};
+  if (c && (s->world > 1 || s->behind_comm)) return fail(-7, "%s: sharded solvers are not supported", who);
+  if (c && !s->empty_problem) {
+    std::vector<double> neg, tc;
+    if (s->maximize) {  // maximise -> minimise, as at creation (problem_helpers.cuh:126-141)
+      neg.assign(c, c + s->n);
+      for (double& v : neg) v = -v;
+      c = neg.data();
+    }
+    const double* cd = s->cols_in(c, tc);
+    int rc = pdlpdev_set_objective(s->dev, cd, csum);
+    if (rc != 0) return fail(rc, "%s: %s", who, pdlpdev_last_error());
+  }
+  if (c) s->objective_offset = objective_offset;
   if (settings) {
     s->S = *settings;
     if (settings->log_file && settings->log_file[0]) s->log_path = settings->log_file;
@@ -1490,10 +1508,14 @@ int cuoptamd_solver_reset(cuoptamd_solver* s, const double* lb, const double* ub
   const double t_reset = seconds_since(t0);
   // ||b||, ||c|| of the termination rule: from the problem again (the previous settings may have overridden them)
   DEV(pdlpdev_problem_norms(s->dev, &s->norm_c, &s->norm_b));
-  if (lo || hi) {
-    // the initial primal weight depends on the row bounds (pdlp.cu:1260-1309)
-    double nr[2];
-    DEV(pdlpdev_weight_norms(s->dev, s->H.compute_initial_primal_weight_before_scaling, nr));
+  if (c) s->norm_c = std::sqrt(csum[0]);  // (the same bits: pdlpdev_set_objective's sum is pdlpdev_problem_norms')
+  if (lo || hi || c) {
+    // the initial primal weight depends on the row bounds and on the objective (pdlp.cu:1260-1309)
+    double nr[2] = {s->H.compute_initial_primal_weight_before_scaling ? csum[0] : csum[1], s->weight_sum_b};
+    if (lo || hi) {
+      DEV(pdlpdev_weight_norms(s->dev, s->H.compute_initial_primal_weight_before_scaling, nr));
+      s->weight_sum_b = nr[1];
+    }
     const double cn = std::sqrt(s->H.initial_primal_weight_c_scaling * nr[0]);
     const double bn = std::sqrt(s->H.initial_primal_weight_b_scaling * nr[1]);
     s->computed_weight = (bn > 0.0 && cn > 0.0) ? s->H.primal_importance * (cn / bn) : s->H.primal_importance;
@@ -1506,6 +1528,22 @@ int cuoptamd_solver_reset(cuoptamd_solver* s, const double* lb, const double* ub
     fprintf(stderr, "[cuopt_amd setup] reset: bounds to the device %.2f ms, norms + weight %.2f ms, initial iterate / step %.2f ms\n", 1e3 * t_reset,
             1e3 * (t_norms - t_reset), 1e3 * (s->result.setup_seconds - t_norms));
   return 0;
+}
+
+int cuoptamd_solver_reset(cuoptamd_solver* s, const double* lb, const double* ub, const double* lo, const double* hi,
+                          const cuoptamd_settings* settings, const double* init_x, const double* init_y)
+{
+  if (!s) return fail(-1, "cuoptamd_solver_reset: null solver");
+  return solver_reset_impl(s, "cuoptamd_solver_reset", nullptr, 0.0, lb, ub, lo, hi, settings, init_x, init_y);
+}
+// The feasibility pump's re-solve (feasibility_pump.cu:145-249: a distance objective per round over one LP, warm-started): a new
+// objective vector and offset on top of cuoptamd_solver_reset; afterwards the solver is, bit for bit, one freshly created on the LP
+// with that objective.  c == NULL: cuoptamd_solver_reset (objective and offset unchanged).
+int cuoptamd_solver_reset_objective(cuoptamd_solver* s, const double* c, double objective_offset, const double* lb, const double* ub, const double* lo,
+                                    const double* hi, const cuoptamd_settings* settings, const double* init_x, const double* init_y)
+{
+  if (!s) return fail(-1, "cuoptamd_solver_reset_objective: null solver");
+  return solver_reset_impl(s, "cuoptamd_solver_reset_objective", c, objective_offset, lb, ub, lo, hi, settings, init_x, init_y);
 }
 
 // One trip of the main loop up to the attempts (pdlp.cu:1099-1222): the major iteration when one is due (termination checks, restart,
@@ -2120,11 +2158,13 @@ int cuoptamd_batch_advance(cuoptamd_batch* b, int32_t max_new_iterations, cuopta
 // heuristics' re-solve: other variable bounds, the previous primal / dual as the start; relaxed_lp.cu:74-108).  Arrays and entries may
 // be NULL (all four entries NULL: that solver is reset to a cold start under its current bounds).  -7: not a small-LP batch, or a
 // solver whose preset updates step size / primal weight from the initial iterate (none does): use cuoptamd_solver_reset per solver.
+// (c != NULL: cuoptamd_batch_reset_objectives -- c[l] in the caller's sense and column order, objective_offset[l] with it)
 static int batch_reset_impl(cuoptamd_batch* b, const double* const* lb, const double* const* ub, const double* const* init_x, const double* const* init_y,
-                            const int32_t* var, const double* var_lb, const double* var_ub, bool warm_from_own)
+                            const int32_t* var, const double* var_lb, const double* var_ub, bool warm_from_own, const char* who = "cuoptamd_batch_reset",
+                            const double* const* c = nullptr, const double* objective_offset = nullptr)
 {
-  if (!b) return fail(-1, "cuoptamd_batch_reset: null batch");
-  if (!b->small) return fail(-7, "cuoptamd_batch_reset: a batch of resident small LPs only");
+  if (!b) return fail(-1, "%s: null batch", who);
+  if (!b->small) return fail(-7, "%s: a batch of resident small LPs only", who);
   const auto t0 = clock_type::now();
   const int K   = b->K;
   std::vector<int32_t> take(K, 1), k(K, -1), warm(K, -1);
@@ -2135,18 +2175,54 @@ static int batch_reset_impl(cuoptamd_batch* b, const double* const* lb, const do
     cuoptamd_solver* s = b->s[l];
     if (s->empty_problem) { take[l] = 0; continue; }
     if (s->H.update_step_size_on_initial_solution || s->H.update_primal_weight_on_initial_solution || !s->row_new2old.empty())
-      return fail(-7, "cuoptamd_batch_reset: solver %d needs cuoptamd_solver_reset", l);
-    if (project >= 0 && project != (s->H.project_initial_primal ? 1 : 0)) return fail(-7, "cuoptamd_batch_reset: the solvers' presets differ");
+      return fail(-7, "%s: solver %d needs cuoptamd_solver_reset", who, l);
+    if (project >= 0 && project != (s->H.project_initial_primal ? 1 : 0)) return fail(-7, "%s: the solvers' presets differ", who);
     project   = s->H.project_initial_primal ? 1 : 0;
     step[l]   = s->S.initial_step_size >= 0.0 ? s->S.initial_step_size : s->computed_step;      // start_run
     weight[l] = s->S.initial_primal_weight >= 0.0 ? s->S.initial_primal_weight : s->computed_weight;
     k[l]      = s->S.initial_k;
     if (warm_from_own) warm[l] = s->returned_which;  // what cuoptamd_solver_get_solution would have handed the caller
   }
+  // new objectives: minimise sense, the device's column order; the weight is formed on the device from the stored row-bound sum
+  std::vector<std::vector<double>> cmin(c ? K : 0);
+  std::vector<const double*> cdev(c ? K : 0, nullptr);
+  const int Kc = c ? K : 0;
+  std::vector<double> sum_b(Kc), c_scaling(Kc), b_scaling(Kc), importance(Kc), sum_cu(Kc), sum_c(Kc), computed(Kc);
+  std::vector<int32_t> unscaled_sum(Kc);
+  for (int l = 0; c && l < K; ++l) {
+    cuoptamd_solver* s = b->s[l];
+    if (!c[l] || !take[l]) continue;
+    cmin[l].assign(c[l], c[l] + s->n);
+    if (s->maximize)
+      for (double& v : cmin[l]) v = -v;
+    std::vector<double> tmp;
+    if (s->cols_in(cmin[l].data(), tmp) != cmin[l].data()) cmin[l].swap(tmp);
+    cdev[l]      = cmin[l].data();
+    sum_b[l]     = s->weight_sum_b, c_scaling[l] = s->H.initial_primal_weight_c_scaling, b_scaling[l] = s->H.initial_primal_weight_b_scaling;
+    importance[l] = s->H.primal_importance, unscaled_sum[l] = s->H.compute_initial_primal_weight_before_scaling ? 1 : 0;
+    weight[l]    = s->S.initial_primal_weight >= 0.0 ? s->S.initial_primal_weight : -1.0;  // (an override; otherwise the device's)
+  }
+  int rc = 0;
+  if (c) {
+    rc = pdlpdev_small_batch_reset_objectives(b->small, take.data(), cdev.data(), lb, ub, init_x, init_y, step.data(), weight.data(), k.data(),
+                                              std::max(project, 0), ctl.data(), var, var_lb, var_ub, warm_from_own ? warm.data() : nullptr, sum_b.data(),
+                                              c_scaling.data(), b_scaling.data(), importance.data(), unscaled_sum.data(), sum_cu.data(), sum_c.data(),
+                                              computed.data());
+    if (rc != 0) return fail(rc, "%s: %s", who, pdlpdev_last_error());
+  }
   for (int l = 0; l < K; ++l) reset_host_state(b->s[l]);
-  int rc = pdlpdev_small_batch_reset(b->small, take.data(), lb, ub, init_x, init_y, step.data(), weight.data(), k.data(), std::max(project, 0), ctl.data(), var,
-                                     var_lb, var_ub, warm_from_own ? warm.data() : nullptr);
+  if (!c) rc = pdlpdev_small_batch_reset(b->small, take.data(), lb, ub, init_x, init_y, step.data(), weight.data(), k.data(), std::max(project, 0), ctl.data(), var,
+                                         var_lb, var_ub, warm_from_own ? warm.data() : nullptr);
   if (rc != 0) return fail(rc, "pdlpdev_small_batch_reset: %s", pdlpdev_last_error());
+  for (int l = 0; c && l < K; ++l) {
+    cuoptamd_solver* s = b->s[l];
+    if (s->empty_problem && c[l] && objective_offset) s->objective_offset = objective_offset[l];
+    if (!cdev[l]) continue;
+    s->objective_offset = objective_offset ? objective_offset[l] : 0.0;
+    s->norm_c           = std::sqrt(sum_cu[l]);
+    s->computed_weight  = computed[l];
+    weight[l]           = ctl[l].primal_weight;  // (the override, or the device's weight: what the reset ran with)
+  }
   const double dt = seconds_since(t0);
   for (int l = 0; l < K; ++l) {
     cuoptamd_solver* s = b->s[l];
@@ -2166,6 +2242,16 @@ static int batch_reset_impl(cuoptamd_batch* b, const double* const* lb, const do
   return 0;
 }
 
+// cuoptamd_batch_reset with a new objective per member (the feasibility pump over K rounded points): see pdlp_solver.h
+int cuoptamd_batch_reset_objectives(cuoptamd_batch* b, const double* const* c, const double* objective_offset, const double* const* lb, const double* const* ub,
+                                    const double* const* init_x, const double* const* init_y, int warm_from_last)
+{
+  const char* const who = "cuoptamd_batch_reset_objectives";
+  if (!b) return fail(-1, "%s: null batch", who);
+  if (!b->small) return fail(-7, "%s: a batch of resident small LPs only (the members of a lockstep batch share one objective)", who);
+  if (warm_from_last && (init_x || init_y)) return fail(-1, "%s: warm_from_last starts from the last returned point: init_x and init_y must be NULL", who);
+  return batch_reset_impl(b, lb, ub, init_x, init_y, nullptr, nullptr, nullptr, warm_from_last != 0, who, c, objective_offset);
+}
 int cuoptamd_batch_reset(cuoptamd_batch* b, const double* const* lb, const double* const* ub, const double* const* init_x, const double* const* init_y)
 {
   return batch_reset_impl(b, lb, ub, init_x, init_y, nullptr, nullptr, nullptr, false);
@@ -2250,6 +2336,13 @@ int cuoptamd_batch_halpern_burst_stats(cuoptamd_batch* b, int64_t out[4])
   return 0;
 }
 
+int cuoptamd_batch_reset_stats(cuoptamd_batch* b, int64_t out[2])
+{
+  if (!b || !out) return fail(-1, "cuoptamd_batch_reset_stats: null argument");
+  if (!b->small) return fail(-7, "cuoptamd_batch_reset_stats: a batch of resident small LPs only");
+  DEV(pdlpdev_small_batch_reset_stats(b->small, out));
+  return 0;
+}
 int cuoptamd_batch_stats(cuoptamd_batch* b, int64_t out[8])
 {
   if (!b || !out) return fail(-1, "cuoptamd_batch_stats: null argument");

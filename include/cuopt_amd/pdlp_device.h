@@ -311,6 +311,19 @@ int pdlpdev_weight_norms(pdlpdev_ctx* ctx, int unscaled, double out[2]);
  * anchors and the control block back to their state right after pdlpdev_scale_problem.  Matrix, objective, D_r, D_c,
  * layouts and graphs are kept; continue with set_step / set_k / set_initial / project_primal as after create. */
 int pdlpdev_reset(pdlpdev_ctx* ctx, const double* lb, const double* ub, const double* lo, const double* hi);
+/* A new objective vector for the same matrix and bounds (the feasibility pump's call pattern, feasibility_pump.cu:145-249: a distance
+ * objective per round over one LP).  c: n host doubles in the DEVICE's column order, already in the minimise sense.  One upload into the
+ * unscaled copy, one kernel (k_set_objective) that writes the scaled working copy c_j * D_c[j] -- k_scale_vectors' expression; D_c depends
+ * on A only -- and leaves the per-workgroup partials of both sums of squares, one k_finalize, one read-back.  sums[0] = sum c_j^2 of the
+ * unscaled, sums[1] of the scaled objective: bit for bit what pdlpdev_problem_norms / pdlpdev_weight_norms / pdlpdev_init_norms reduce
+ * from those arrays (same grid, same order per thread, same trees; no atomics).  Both arrays are overwritten in place: kernel argument
+ * lists and captured attempt graphs stay valid, none is destroyed.  Iterate and loop state are NOT touched: follow with pdlpdev_reset.
+ * -7, before anything is written, where the objective is not this context's alone (it lives in the part a clone shares): a context
+ * with live clones, a clone, a member of a lockstep batch (pdlpdev_batch_*), a sharded context.
+ * Out of scope: per-member objectives for clones and lockstep shared-matrix batches (c would have to move into the part an LP owns and
+ * the kb_* kernels take K objectives), sharded contexts, a change of the optimisation sense (the caller negates), and anything that
+ * changes A (the pump's auxiliary variables for interior general integers). */
+int pdlpdev_set_objective(pdlpdev_ctx* ctx, const double* c, double sums[2]);
 /* l2 norms of the UNSCALED c and bcomb (termination constants, convergence_information.cu:76-84) */
 int pdlpdev_problem_norms(pdlpdev_ctx* ctx, double* norm_c, double* norm_b);
 int pdlpdev_set_step_params(pdlpdev_ctx* ctx, const pdlpdev_step_params* p);
@@ -423,6 +436,22 @@ int pdlpdev_small_batch_prepare(pdlpdev_small_batch* batch, const int32_t* clear
 int pdlpdev_small_batch_reset(pdlpdev_small_batch* batch, const int32_t* take, const double* const* lb, const double* const* ub, const double* const* x0,
                               const double* const* y0, const double* step, const double* weight, const int32_t* k, int project, pdlpdev_ctl* ctl,
                               const int32_t* var, const double* var_lb, const double* var_ub, const int32_t* warm);
+/* pdlpdev_small_batch_reset with new objectives, objective and reset in one stream with no host round trip between them: c[l] (n
+ * doubles, minimise sense, the device's column order) replaces LP l's objective -- per LP bit for bit pdlpdev_set_objective, inside ONE
+ * kernel over an (LP, block) table -- and a second kernel forms both sums with k_finalize's tree and the initial primal weight
+ * (pdlp.cu:1260-1309) on the device: cn = sqrt(c_scaling[l] * S), S = sum c_u^2 when unscaled_sum[l] != 0 else sum c^2,
+ * bn = sqrt(b_scaling[l] * sum_b[l]), importance[l] * (cn / bn) when both are positive, else importance[l].  The reset then runs with
+ * that weight, or with weight[l] when weight[l] >= 0 (an override; < 0: none).  c[l] == NULL: LP l keeps its objective and takes
+ * weight[l], exactly pdlpdev_small_batch_reset's path; c == NULL: that call.  Launches do not depend on K, the one synchronisation is
+ * pdlpdev_small_batch_reset's.  sum_cu / sum_c / computed_weight (each may be NULL): per LP with c[l], both sums and the weight as
+ * computed (read from the LP's pinned scalars).  -7 for a member that shares its objective (a clone, a parent with clones). */
+int pdlpdev_small_batch_reset_objectives(pdlpdev_small_batch* batch, const int32_t* take, const double* const* c, const double* const* lb,
+                                         const double* const* ub, const double* const* x0, const double* const* y0, const double* step, const double* weight,
+                                         const int32_t* k, int project, pdlpdev_ctl* ctl, const int32_t* var, const double* var_lb, const double* var_ub,
+                                         const int32_t* warm, const double* sum_b, const double* c_scaling, const double* b_scaling, const double* importance,
+                                         const int32_t* unscaled_sum, double* sum_cu, double* sum_c, double* computed_weight);
+/* out = {kernel launches, synchronisations} of all pdlpdev_small_batch_reset / _reset_objectives calls of the batch so far */
+int pdlpdev_small_batch_reset_stats(pdlpdev_small_batch* batch, int64_t out[2]);
 /* (var / var_lb / var_ub, may be NULL: a BRANCH -- the bounds of variable var[l] >= 0 of LP l become [var_lb[l], var_ub[l]], nothing
  *  crosses PCIe but three scalars; warm, may be NULL: warm[l] = PDLPDEV_CURRENT / AVERAGE / BEST starts LP l from that iterate of ITS
  *  OWN last solve, unscaled and scaled again on the device exactly as a read-back + set_initial would -- x0 / y0 are ignored then) */

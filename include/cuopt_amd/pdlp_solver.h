@@ -323,6 +323,24 @@ void cuoptamd_solver_destroy(cuoptamd_solver* s);
 int cuoptamd_solver_reset(cuoptamd_solver* s, const double* lb, const double* ub, const double* lo, const double* hi,
                           const cuoptamd_settings* settings, const double* init_x, const double* init_y);
 
+/* Persistent re-solve with a new OBJECTIVE vector, the feasibility pump's call pattern (linear_project_onto_polytope,
+ * cpp/src/mip/local_search/feasibility_pump/feasibility_pump.cu:145-249: per round a distance objective to the rounded point, mixed
+ * with alpha * c / ||c||, over the same constraints, warm-started from the previous point).  cuoptamd_solver_reset plus c (n doubles)
+ * and objective_offset, both in the caller's terms exactly as at creation: c in the caller's column order and in the caller's sense
+ * (a maximise solver negates it again; the sense itself cannot change), the offset as cuoptamd_lp::objective_offset.  c == NULL leaves
+ * objective and offset unchanged: the call is cuoptamd_solver_reset.  Nothing of the matrix side is redone -- D_r, D_c, the initial
+ * step, mode 4's sigma_max depend on A only; the scaled objective, ||c|| of the termination rule and the initial primal weight are
+ * formed again by one kernel and one reduction (pdlpdev_set_objective), under the same overrides as ever (initial_primal_weight,
+ * relative_dual_tolerance_factor).  Afterwards the solver is, bit for bit, a solver freshly created on the LP with that objective.
+ * Every refusal of cuoptamd_solver_reset applies; an empty problem (m == 0) keeps its verdict.  -7, by name and with the solver left
+ * exactly as it was, where the objective is not this solver's alone: a solver with live clones, a clone, a member of a lockstep
+ * batch, a sharded solver.
+ * Out of scope: per-member objectives for clones and lockstep shared-matrix batches (the objective would have to move into the part of
+ * the device context an LP owns, and the K-wide kernels take K objectives); sharded solvers; changing the sense; the pump's auxiliary
+ * variables for interior general integers, which change A. */
+int cuoptamd_solver_reset_objective(cuoptamd_solver* s, const double* c, double objective_offset, const double* lb, const double* ub, const double* lo,
+                                    const double* hi, const cuoptamd_settings* settings, const double* init_x, const double* init_y);
+
 /* Runs the PDLP loop until a termination criterion fires or `max_new_iterations` further PDLP
  * iterations (accepted steps) have been taken, whichever is first.  result->status == 0 means
  * "budget exhausted, not terminated"; calling again continues exactly where it stopped. */
@@ -359,6 +377,17 @@ int cuoptamd_batch_get_solutions(cuoptamd_batch* batch, double* const* x, double
  * reset / branch / solutions call of the batch). */
 int cuoptamd_batch_branch(cuoptamd_batch* batch, const int32_t* var, const double* lb, const double* ub);
 int cuoptamd_batch_solution_views(cuoptamd_batch* batch, const double** x, const double** y, const double** rc);
+/* cuoptamd_batch_reset_objectives: cuoptamd_solver_reset_objective(c[l], objective_offset[l], lb[l], ub[l], NULL, NULL, NULL, init_x[l],
+ * init_y[l]) for every solver of a small-LP batch, with a number of launches that does not depend on K and the one synchronisation of
+ * cuoptamd_batch_reset: the objectives are scaled, reduced and turned into the initial primal weights on the device, in front of the
+ * reset kernel.  Arrays and entries may be NULL; c[l] == NULL keeps solver l's objective and offset (objective_offset == NULL: offsets
+ * 0 for the solvers that get an objective).  warm_from_last != 0: every solver starts from the point its last solve returned, as in
+ * cuoptamd_batch_branch (init_x and init_y must then be NULL).  -7 by name for a lockstep batch, whose members share one objective;
+ * otherwise cuoptamd_batch_reset's refusals.
+ * cuoptamd_batch_reset_stats: {kernel launches, synchronisations} of all reset / branch / reset_objectives calls of a small-LP batch. */
+int cuoptamd_batch_reset_objectives(cuoptamd_batch* batch, const double* const* c, const double* objective_offset, const double* const* lb,
+                                    const double* const* ub, const double* const* init_x, const double* const* init_y, int warm_from_last);
+int cuoptamd_batch_reset_stats(cuoptamd_batch* batch, int64_t out[2]);
 void cuoptamd_batch_destroy(cuoptamd_batch* batch);
 /* counters of a small-LP batch (pdlpdev_small_batch_stats): {Halpern batch (0 / 1), resident tiers in use, loop launches, evaluation
  * launches behind the loop, runs (periods), restart rounds, resets, synchronisations}; restart rounds and resets are counted for a batch
