@@ -39,6 +39,22 @@ __device__ __forceinline__ void halpern_decision_from_sums(pdlpdev_ctl* __restri
   *ctl = lc;
 }
 
+// The scalar part of a restart, by one thread, behind the two squared distances in dist2: their roots in place, the smoothed primal weight
+// (theta < 0: the counters only), k <- 0.  The ONE copy: k_halpern_restart_ctl and every restart finish of a resident LP or a burst call it.
+__device__ __forceinline__ void halpern_restart_scalars(pdlpdev_ctl* ctl, pdlpdev_halpern* hal, double* dist2, double theta)
+{
+  const double dx = sqrt(dist2[0]), dy = sqrt(dist2[1]);
+  dist2[0] = dx, dist2[1] = dy;
+  if (theta >= 0.0 && dx > 1.0e-10 && dy > 1.0e-10) {
+    const double w     = exp(theta * log(dy / dx) + (1.0 - theta) * log(ctl->primal_weight));
+    ctl->primal_weight = w;
+    ctl->tau           = ctl->step_size / w;
+    ctl->sigma         = ctl->step_size * w;
+  }
+  ctl->its_since_restart = 0;
+  hal->k                 = 0;
+}
+
 __device__ __forceinline__ void halpern_decision_workgroup(pdlpdev_ctl* __restrict__ ctl, pdlpdev_halpern* __restrict__ hal, const double* __restrict__ part_dy,
                                                            int nb_dy, const double* __restrict__ part_t, int nb_t)
 {

@@ -1,7 +1,9 @@
 // The burst of device-decided major iterations of the reflected-Halpern mode (cuoptamd_settings::halpern_device_major,
 // docs/design/04d_halpern_mode.md "Verdict and restart on the device"): what pdlp_device.hip (pdlpdev_run_halpern_burst, the host side
-// of a burst) and kernels_halpern_major.hip (the kernels and their launch sites) share.
+// of a burst) and kernels_halpern_major.hip (the kernels and their launch sites) share, and the host's handling of a burst's ring of
+// records (halpern_burst_mark_ring, halpern_burst_collect), which the batch's burst (kernels_resident.hip) uses per member.
 #pragma once
+#include "halpern_restart_tests.hpp"
 #include "pdlp_ctx.hpp"
 
 // The burst's own device block, next to pdlpdev_halpern (whose size does not change): allocated by pdlpdev_set_halpern_device_major,
@@ -14,8 +16,8 @@ struct pdlpdev_halpern_major_state {
 };
 
 // The decision of a major iteration: halpern_major_head's tests in its order and with its expressions (pdlp_solver.cpp: to_convergence,
-// verdict, the iteration limit of check_limits, the three restart tests) on the scalars that are on the device.  One thread runs it;
-// k_halpern_major_decide (one LP) and k_halpern_major_decide_batch (one wave per LP of a batch) both call it -- the tests do not fork.
+// verdict, the iteration limit of check_limits) on the scalars that are on the device, then its three restart tests themselves
+// (halpern_restart_due).  k_halpern_major_decide (one LP) and k_halpern_major_decide_batch (one wave per LP) call it: no test forks.
 //   sc      the evaluation's nine raw sums (read_eval's input: the scalars' slot 32 on the multi-launch path, the pinned block's on
 //           the resident one)
 //   target  the period's accepted-step count
@@ -79,16 +81,43 @@ __device__ __forceinline__ void halpern_major_decide(const pdlpdev_ctl* __restri
     *rec        = out;
     return;
   }
-  // the three restart tests
-  const double r = hal->r, r_first = hal->r_first, r_prev = st->r_prev;
-  bool restart = false;
-  if (r <= p.sufficient_reduction * r_first) restart = true;
-  else if (r <= p.necessary_reduction * r_first && r_prev >= 0.0 && r > r_prev) restart = true;
-  else if ((double)hal->k >= p.artificial_threshold * (double)total_iterations) restart = true;
-  st->r_prev  = restart ? -1.0 : r;  // (halpern_restart_done: no previous check behind a restart)
+  const bool restart = halpern_restart_due(hal->r, hal->r_first, st->r_prev, hal->k, total_iterations, p.sufficient_reduction, p.necessary_reduction,
+                                           p.artificial_threshold);
+  st->r_prev  = restart ? -1.0 : hal->r;  // (halpern_restart_done: no previous check behind a restart)
   st->restart = restart ? 1 : 0;
   out.restart = restart ? 1 : 0;
   *rec        = out;
+}
+
+// ---- the host side of a burst's ring: pdlpdev_run_halpern_burst's, and pdlpdev_small_batch_run_halpern_burst's per member (the callers
+// count stats->bursts and stats->periods, once per burst).  In front of the launches every slot is "not written": a decision leaves its
+// step count there.  Behind the synchronisation the written records go to `records` in order, r_prev is carried forward as the decisions
+// left it in the burst's block.  Nonzero: a record was written behind the period that stopped the burst.
+static inline void halpern_burst_mark_ring(pdlpdev_halpern_major_record* ring, int count)
+{
+  for (int j = 0; j < count; ++j) ring[j].steps_taken = -1;
+}
+static inline int halpern_burst_collect(const pdlpdev_halpern_major_record* ring, int count, double r_prev, pdlpdev_halpern_major_record* records,
+                                        int32_t* written, double* r_prev_out, HalpernBurstStats* stats)
+{
+  int n_written  = 0;
+  bool stop_seen = false;
+  for (int j = 0; j < count; ++j) {
+    const pdlpdev_halpern_major_record& r = ring[j];
+    if (r.steps_taken < 0) {
+      stop_seen = true;  // (a period behind the stop: its launches were empty)
+      stats->empty += 1;
+      continue;
+    }
+    if (stop_seen || n_written != j) return 1;
+    records[n_written++] = r;
+    if (r.verdict != PDLPDEV_MAJOR_GO_ON) stop_seen = true;
+    else r_prev = r.restart ? -1.0 : r.r;
+  }
+  stats->records += n_written;
+  *written = n_written;
+  if (r_prev_out) *r_prev_out = r_prev;
+  return 0;
 }
 
 extern "C" {
@@ -102,7 +131,7 @@ int halpern_major_launch_resident_period(pdlpdev_ctx* ctx, int32_t target, int r
 // k_halpern_major_decide on the context's own blocks: sc = the nine raw sums of the evaluation (read_eval's input), rec = the record
 int halpern_major_launch_decide(pdlpdev_ctx* ctx, const double* sc, const pdlpdev_halpern_major_params& p, int32_t target,
                                 pdlpdev_halpern_major_record* rec);
-// the guarded restart: distances + anchor (restart_block), A^T y of the anchor, finalize_rows + k_halpern_restart_ctl's arithmetic.
+// the guarded restart: distances + anchor (restart_block), A^T y of the anchor, finalize_rows + halpern_restart_scalars.
 // mirrors != 0: the control block and the Halpern block also go to their pinned mirrors (the resident path reads no copy back)
 int halpern_major_launch_restart(pdlpdev_ctx* ctx, double theta, pdlpdev_halpern_major_record* rec, int mirrors);
 }

@@ -1,6 +1,7 @@
 // The burst of device-decided major iterations for the K LPs of a Halpern small-LP batch (cuoptamd_batch_set_halpern_device_major,
 // docs/design/04d_halpern_mode.md "Bursts of a K-workgroup batch"): what kernels_resident.hip (the batch object and the host side of a
-// burst) and kernels_halpern_major.hip (the kernels and their launch sites) share.
+// burst) and kernels_halpern_major.hip (the kernels and their launch sites) share.  A member's restart is finished by the batch
+// restart's own body (halpern_restart_finish_workgroup, resident_halpern_bodies.hpp) on the batch restart's own record.
 #pragma once
 #include "halpern_major.hpp"
 #include "resident_common.hpp"
@@ -13,11 +14,9 @@ struct HalpernBurstMember {
   const double* sc;                 // the evaluation's nine raw sums: the member's pinned scalar block, slot 32
   pdlpdev_halpern_major_record* ring;  // 16 records in pinned host memory
   pdlpdev_halpern_major_params p;
-  double theta, r_prev;             // the restart's smoothing; the host's r_prev (k_halpern_major_arm_batch)
+  double r_prev;                    // the host's r_prev (k_halpern_major_arm_batch)
   RestartView R;                    // k_restart_batch's view: candidate = the current iterate, scaled distances
-  int g, pad;                       // pdlpdev_small_batch_halpern_restart's block count: the same partials, the same tree
-  const double *aty0, *aty1;        // k_halpern_restart_finish_batch's copy of A^T y into the anchor's
-  double* lraty;
+  HalpernRestartArgs fin;           // k_halpern_restart_finish_batch's record (no clear; fin.g blocks of R); the distances go to st and the ring
 };
 
 extern "C" {

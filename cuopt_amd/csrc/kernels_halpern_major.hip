@@ -1,9 +1,11 @@
 // gfx950 kernels of the burst of device-decided major iterations in reflected-Halpern mode (cuoptamd_settings::halpern_device_major;
 // docs/design/04d_halpern_mode.md, "Verdict and restart on the device").  A translation unit of its own: the four layout units, the
-// two resident units and the core's restart kernels (k_restart, k_finalize, k_copy_current, k_halpern_restart_ctl) compile as before.
+// two resident units and the core's restart kernels (k_restart, k_finalize, k_copy_current) compile as before.
 // Every kernel here asks the burst's block first and does nothing once a decision has stopped the burst; no kernel waits for another
 // -- the order is the stream's.  The second half serves the K LPs of a Halpern small-LP batch (cuoptamd_batch_set_halpern_device_major;
 // "Bursts of a K-workgroup batch"): the same bodies with a workgroup per LP, each behind that LP's own block.
+// A restart's scalars are halpern_restart_scalars (halpern_decision.hpp), a resident LP's restart finish is halpern_restart_finish_workgroup
+// (resident_halpern_bodies.hpp), the decision's three restart tests are the host's (halpern_restart_tests.hpp): nothing is restated here.
 #include "halpern_major.hpp"
 #include "halpern_major_batch.hpp"
 #include "pdlp_launch.hpp"
@@ -54,7 +56,7 @@ k_halpern_major_decide(const pdlpdev_ctl* __restrict__ ctl, const pdlpdev_halper
 }
 
 // ---- the restart, guarded by the decision: twins of k_restart (candidate = the current iterate, scaled distances), k_copy_current
-// (A^T y -> the anchor's) and k_finalize + k_halpern_restart_ctl (the two sums by finalize_rows' tree, the smoothed weight, k <- 0)
+// (A^T y -> the anchor's, over a grid) and k_finalize + k_halpern_restart_ctl (finalize_rows' tree, then halpern_restart_scalars)
 __global__ void __launch_bounds__(kBlock) k_halpern_major_restart(RestartView R, const pdlpdev_halpern_major_state* __restrict__ st)
 {
   __shared__ double red[12];
@@ -77,17 +79,8 @@ k_halpern_major_restart_finish(const double* __restrict__ part, int g, pdlpdev_c
   if (st->stopped || !st->restart) return;  // (uniform; the flag is the decision's to write)
   finalize_rows(part, g, 2, 0u, st->dist2, red);
   if (threadIdx.x != 0) return;
-  const double dx = sqrt(st->dist2[0]), dy = sqrt(st->dist2[1]);  // k_halpern_restart_ctl
-  st->dist2[0] = dx, st->dist2[1] = dy;
-  if (theta >= 0.0 && dx > 1.0e-10 && dy > 1.0e-10) {
-    const double w     = exp(theta * log(dy / dx) + (1.0 - theta) * log(ctl->primal_weight));
-    ctl->primal_weight = w;
-    ctl->tau           = ctl->step_size / w;
-    ctl->sigma         = ctl->step_size * w;
-  }
-  ctl->its_since_restart = 0;
-  hal->k                 = 0;
-  rec->dist[0] = dx, rec->dist[1] = dy, rec->new_weight = ctl->primal_weight;
+  halpern_restart_scalars(ctl, hal, st->dist2, theta);
+  rec->dist[0] = st->dist2[0], rec->dist[1] = st->dist2[1], rec->new_weight = ctl->primal_weight;
   if (ctl_host) *ctl_host = *ctl, *hal_host = *hal;
 }
 
@@ -152,37 +145,24 @@ __global__ void __launch_bounds__(kBlock) k_halpern_major_restart_batch(const Ha
   const int2 b                = blk[blockIdx.x];
   const HalpernBurstMember& M = mem[b.x];
   if (M.st->stopped || !M.st->restart) return;  // (uniform)
-  restart_block(M.R, b.y, M.g, red);
+  restart_block(M.R, b.y, M.fin.g, red);
 }
-// the twin of k_halpern_restart_finish_batch (no clear): the two sums by finalize_rows' tree, A^T y into the anchor's,
-// k_halpern_restart_ctl's arithmetic with this LP's theta; the distances and the new weight go to the record, both blocks to their mirrors
+// k_halpern_restart_finish_batch's body behind the member's guard; the distances go to the member's block, they and the new weight to the record
 __global__ void __launch_bounds__(kBlock) k_halpern_major_restart_finish_batch(const HalpernBurstMember* __restrict__ mem, const int* __restrict__ list, int j)
 {
   __shared__ double red[8];
-  const HalpernBurstMember& M     = mem[list[blockIdx.x]];
-  pdlpdev_halpern_major_state* st = M.st;
-  if (st->stopped || !st->restart) return;  // (uniform; the flag is the decision's to write)
-  pdlpdev_ctl* ctl = M.run.ctl;
-  const int cur    = ctl->cur;  // (read by every thread in front of finalize_rows' barriers; thread 0 rewrites the block behind them)
-  finalize_rows(M.R.part, M.g, 2, 0u, st->dist2, red);
-  const double* __restrict__ v = cur ? M.aty1 : M.aty0;
-  for (int i = threadIdx.x; i < M.R.n; i += kBlock) M.lraty[i] = v[i];
-  if (threadIdx.x != 0) return;
-  pdlpdev_halpern* hal = M.run.hal;
-  const double theta   = M.theta;
-  const double dx = sqrt(st->dist2[0]), dy = sqrt(st->dist2[1]);  // k_halpern_restart_ctl
-  st->dist2[0] = dx, st->dist2[1] = dy;
-  if (theta >= 0.0 && dx > 1.0e-10 && dy > 1.0e-10) {
-    const double w     = exp(theta * log(dy / dx) + (1.0 - theta) * log(ctl->primal_weight));
-    ctl->primal_weight = w;
-    ctl->tau           = ctl->step_size / w;
-    ctl->sigma         = ctl->step_size * w;
-  }
-  ctl->its_since_restart = 0;
-  hal->k                 = 0;
+  const HalpernBurstMember& M = mem[list[blockIdx.x]];
+  if (M.st->stopped || !M.st->restart) return;  // (uniform; the flag is the decision's to write)
   pdlpdev_halpern_major_record* rec = M.ring + j;
-  rec->dist[0] = dx, rec->dist[1] = dy, rec->new_weight = ctl->primal_weight;
-  *M.run.ctl_host = *ctl, *M.run.hal_host = *hal;
+  halpern_restart_finish_workgroup(M.fin, M.st->dist2, rec->dist, red);
+  if (threadIdx.x == 0) rec->new_weight = M.fin.ctl->primal_weight;
+}
+
+// the two debug entry points: read_eval's input from its output (the dual objective's two halves as the sum and a zero)
+void raw_sums_of(const double* ev, double sc[9])
+{
+  sc[0] = ev[PDLPDEV_EV_PRES2], sc[1] = ev[PDLPDEV_EV_DUAL_SUM], sc[2] = ev[PDLPDEV_EV_Y2], sc[3] = ev[PDLPDEV_EV_LINF_PRES_REL];
+  sc[4] = ev[PDLPDEV_EV_DRES2], sc[5] = 0.0, sc[6] = ev[PDLPDEV_EV_CX], sc[7] = ev[PDLPDEV_EV_X2], sc[8] = ev[PDLPDEV_EV_LINF_DRES_REL];
 }
 
 }  // namespace
@@ -305,12 +285,9 @@ int pdlpdev_debug_halpern_major_decide_batch(int device, int32_t count, const do
   for (int l = 0; l < count; ++l) {
     Blocks& b = h[l];
     memset(&b, 0, sizeof(b));
-    const double* e = ev + (size_t)l * PDLPDEV_EV_COUNT;
     b.st.r_prev = r_prev[l], b.st.stopped = stopped[l], b.st.restart = 0;
     b.ctl = ctl[l], b.hal = hal[l], b.rec = records[l];
-    // (read_eval's input from its output: the dual objective's two halves as the sum and a zero)
-    b.sc[0] = e[PDLPDEV_EV_PRES2], b.sc[1] = e[PDLPDEV_EV_DUAL_SUM], b.sc[2] = e[PDLPDEV_EV_Y2], b.sc[3] = e[PDLPDEV_EV_LINF_PRES_REL];
-    b.sc[4] = e[PDLPDEV_EV_DRES2], b.sc[5] = 0.0, b.sc[6] = e[PDLPDEV_EV_CX], b.sc[7] = e[PDLPDEV_EV_X2], b.sc[8] = e[PDLPDEV_EV_LINF_DRES_REL];
+    raw_sums_of(ev + (size_t)l * PDLPDEV_EV_COUNT, b.sc);
     b.mem.run.ctl = &d[l].ctl, b.mem.run.hal = &d[l].hal, b.mem.run.target_steps = target[l];
     b.mem.st = &d[l].st, b.mem.sc = d[l].sc, b.mem.ring = &d[l].rec, b.mem.p = params[l];
     b.list = count - 1 - l;  // (workgroup w serves member count - 1 - w: the list is looked at)
@@ -360,9 +337,7 @@ int pdlpdev_debug_halpern_major_decide(int device, const double ev[PDLPDEV_EV_CO
   } h{}, *d = nullptr;
   h.st.r_prev = r_prev, h.st.stopped = stopped, h.st.restart = 0;
   h.ctl = *ctl, h.hal = *hal, h.rec = *record;
-  // (read_eval's input from its output: the dual objective's two halves as the sum and a zero)
-  h.sc[0] = ev[PDLPDEV_EV_PRES2], h.sc[1] = ev[PDLPDEV_EV_DUAL_SUM], h.sc[2] = ev[PDLPDEV_EV_Y2], h.sc[3] = ev[PDLPDEV_EV_LINF_PRES_REL];
-  h.sc[4] = ev[PDLPDEV_EV_DRES2], h.sc[5] = 0.0, h.sc[6] = ev[PDLPDEV_EV_CX], h.sc[7] = ev[PDLPDEV_EV_X2], h.sc[8] = ev[PDLPDEV_EV_LINF_DRES_REL];
+  raw_sums_of(ev, h.sc);
   HIP_TRY(hipMalloc((void**)&d, sizeof(Blocks)));
   hipError_t e = hipMemcpy(d, &h, sizeof(Blocks), hipMemcpyHostToDevice);
   if (e == hipSuccess) {

@@ -538,7 +538,7 @@ struct pdlpdev_small_batch {
   void* burst_pinned = nullptr;
   HalpernBurstMember* burst = nullptr;
   pdlpdev_halpern_major_record* ring = nullptr;
-  int64_t stat_bursts = 0, stat_burst_periods = 0, stat_burst_records = 0, stat_burst_empty = 0;  // pdlpdev_small_batch_halpern_burst_stats
+  HalpernBurstStats burst_stats;  // pdlpdev_small_batch_halpern_burst_stats
   pdlpdev_small_batch() = default;
   pdlpdev_small_batch(const pdlpdev_small_batch&) = delete;
   pdlpdev_small_batch& operator=(const pdlpdev_small_batch&) = delete;
@@ -577,6 +577,11 @@ static RestartBatchArgs restart_batch_args(const pdlpdev_ctx* c, int which, int 
   return RestartBatchArgs{RestartView{c->n, c->m, which, unscaled, c->dc, c->dr, c->ctl, c->x[0], c->x[1], c->y[0], c->y[1], c->avgx, c->avgy, c->lrx, c->lry,
                                       c->sumx, c->sumy, c->part_g},
                           std::min(grid_for(std::max(c->n, c->m)), kGenericBlocks), 0, c->scal_h};
+}
+// the record of the restart's finish behind it (halpern_restart_finish_workgroup): ra.g blocks' partials, the distances to the LP's scalars
+static HalpernRestartArgs halpern_restart_args(const pdlpdev_ctx* c, const RestartBatchArgs& ra, int clear, double theta)
+{
+  return HalpernRestartArgs{c->n, ra.g, clear, 0, theta, c->part_g, c->aty[0], c->aty[1], c->lraty, c->scal, c->scal_h, c->ctl, c->ctl_h, c->hal, c->hal_h};
 }
 static StreamAtCurArgs stream_at_cur_args(const pdlpdev_ctx* c)
 {
@@ -657,9 +662,8 @@ static int halpern_batch_enqueue_restart(pdlpdev_small_batch* b, int count, cons
     const int l    = b->list[q];
     pdlpdev_ctx* c = b->ctx[l];
     b->restart[l]  = restart_batch_args(c, PDLPDEV_CURRENT, 0);
-    const int g    = b->restart[l].g;
-    b->hrestart[l] = HalpernRestartArgs{c->n, g, clear, 0, theta[l], c->part_g, c->aty[0], c->aty[1], c->lraty, c->scal, c->scal_h, c->ctl, c->ctl_h, c->hal, c->hal_h};
-    for (int i = 0; i < g; ++i) b->blk[blocks++] = make_int2(l, i);
+    b->hrestart[l] = halpern_restart_args(c, b->restart[l], clear, theta[l]);
+    for (int i = 0; i < b->restart[l].g; ++i) b->blk[blocks++] = make_int2(l, i);
   }
   k_restart_batch<<<blocks - blk_first, kBlock, 0, b->stream>>>(b->restart, b->blk + blk_first);
   HIP_TRY(hipGetLastError());
@@ -745,7 +749,7 @@ int pdlpdev_small_batch_set_halpern_device_major(pdlpdev_small_batch* b, int on)
 int pdlpdev_small_batch_halpern_burst_stats(pdlpdev_small_batch* b, int64_t out[4])
 {
   if (!b || !out) return fail(-1, "pdlpdev_small_batch_halpern_burst_stats: null argument");
-  out[0] = b->stat_bursts, out[1] = b->stat_burst_periods, out[2] = b->stat_burst_records, out[3] = b->stat_burst_empty;
+  out[0] = b->burst_stats.bursts, out[1] = b->burst_stats.periods, out[2] = b->burst_stats.records, out[3] = b->burst_stats.empty;
   return 0;
 }
 // Enqueued in stream order, no kernel waiting for another: the arming kernel; then per period the loop kernel per tier in use, the guarded
@@ -777,13 +781,11 @@ int pdlpdev_small_batch_run_halpern_burst(pdlpdev_small_batch* b, const int32_t*
     HalpernBurstMember& M = b->burst[l];
     M.run = HalpernResidentArgs{halpern_view(c), c->ctl, c->ctl_h, c->hal, c->hal_h, first_target[l], 0};
     M.st = b->hmaj + l, M.sc = c->scal_h + 32, M.ring = b->ring + 16 * (size_t)l;
-    M.p = params[l], M.p.want_linf = want_linf;
-    M.theta = theta[l], M.r_prev = r_prev[l];
+    M.p = params[l], M.p.want_linf = want_linf, M.r_prev = r_prev[l];
     const RestartBatchArgs ra = restart_batch_args(c, PDLPDEV_CURRENT, 0);
-    M.R = ra.R, M.g = ra.g, M.pad = 0;
-    M.aty0 = c->aty[0], M.aty1 = c->aty[1], M.lraty = c->lraty;
-    for (int j = 0; j < count; ++j) M.ring[j].steps_taken = -1;  // ("not written": a decision leaves its step count here)
-    for (int i = 0; i < M.g; ++i) b->blk[blocks++] = make_int2(l, i);
+    M.R = ra.R, M.fin = halpern_restart_args(c, ra, 0, theta[l]);
+    halpern_burst_mark_ring(M.ring, count);
+    for (int i = 0; i < ra.g; ++i) b->blk[blocks++] = make_int2(l, i);
     b->run_list[b->tier[l] * K + tier_count[b->tier[l]]++] = l;
     b->list[n++] = l;
     loop_state_touched(c);
@@ -804,29 +806,14 @@ int pdlpdev_small_batch_run_halpern_burst(pdlpdev_small_batch* b, const int32_t*
   }
   HIP_TRY(hipStreamSynchronize(b->stream));
   b->stat_syncs += 1;
-  b->stat_bursts += 1, b->stat_burst_periods += count;
+  b->burst_stats.bursts += 1, b->burst_stats.periods += count;
   for (int q = 0; q < n; ++q) {
     const int l    = b->list[q];
     pdlpdev_ctx* c = b->ctx[l];
     c->ctl_h_current = true;
-    double rp      = r_prev[l];
-    int n_written  = 0;
-    bool stop_seen = false;
-    for (int j = 0; j < count; ++j) {
-      const pdlpdev_halpern_major_record& r = b->ring[16 * (size_t)l + j];
-      if (r.steps_taken < 0) {
-        stop_seen = true;  // (a period behind the member's stop: its workgroups did nothing)
-        b->stat_burst_empty += 1;
-        continue;
-      }
-      if (stop_seen || n_written != j) return fail(-6, "pdlpdev_small_batch_run_halpern_burst: LP %d: a record was written behind the period that stopped it", l);
-      records[16 * (size_t)l + n_written++] = r;
-      if (r.verdict != PDLPDEV_MAJOR_GO_ON) stop_seen = true;
-      else rp = r.restart ? -1.0 : r.r;  // (what the decision left in the member's block)
-    }
-    b->stat_burst_records += n_written;
-    written[l] = n_written;
-    if (r_prev_out) r_prev_out[l] = rp;
+    if (halpern_burst_collect(b->ring + 16 * (size_t)l, count, r_prev[l], records + 16 * (size_t)l, written + l, r_prev_out ? r_prev_out + l : nullptr,
+                              &b->burst_stats))
+      return fail(-6, "pdlpdev_small_batch_run_halpern_burst: LP %d: a record was written behind the period that stopped it", l);
     if (ctl) ctl[l] = *c->ctl_h;
     if (hal) hal[l] = *c->hal_h;
   }

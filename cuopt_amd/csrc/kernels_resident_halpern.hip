@@ -48,39 +48,13 @@ __global__ void __launch_bounds__(kMajorThreads) k_major_small_halpern_batch(con
   major_small_halpern_body(args[list[blockIdx.x]], prod);
 }
 
-// Behind k_restart_batch (candidate = the current iterate, scaled distances) for the LPs of a Halpern batch: what pdlpdev_halpern_restart
-// enqueues behind k_restart for one LP -- k_finalize's two sums (finalize_rows: the same tree), k_copy_current of A^T y into the anchor's,
-// k_halpern_restart_ctl's arithmetic with this LP's theta -- in one workgroup per LP; both blocks go to their pinned mirrors and the two
-// distances to the LP's pinned scalars.  clear != 0 (a reset): k_halpern_clear's values first.
+// Behind k_restart_batch for the LPs of a Halpern batch: halpern_restart_finish_workgroup (resident_halpern_bodies.hpp), one workgroup
+// per LP; the two distances go to the LP's scalar block on the device and to its pinned one.
 __global__ void __launch_bounds__(kBlock) k_halpern_restart_finish_batch(const HalpernRestartArgs* __restrict__ args, const int* __restrict__ list)
 {
   __shared__ double red[8];
   const HalpernRestartArgs& A = args[list[blockIdx.x]];
-  const int cur = A.ctl->cur;  // (read by every thread in front of finalize_rows' barriers; thread 0 rewrites the block behind them)
-  finalize_rows(A.part, A.g, 2, 0u, A.dist2, red);
-  const double* __restrict__ v = cur ? A.aty1 : A.aty0;
-  for (int i = threadIdx.x; i < A.n; i += kBlock) A.lraty[i] = v[i];
-  if (threadIdx.x == 0) {
-    pdlpdev_ctl* ctl     = A.ctl;
-    pdlpdev_halpern* hal = A.hal;
-    if (A.clear) {  // k_halpern_clear
-      hal->r = hal->r_first = hal->r2 = 0.0;
-      hal->r2_min = __builtin_huge_val();
-      hal->k = 0, hal->reserved = 0;
-    }
-    const double dx = sqrt(A.dist2[0]), dy = sqrt(A.dist2[1]);  // k_halpern_restart_ctl
-    A.dist2[0] = dx, A.dist2[1] = dy;
-    A.dist_host[0] = dx, A.dist_host[1] = dy;
-    if (A.theta >= 0.0 && dx > 1.0e-10 && dy > 1.0e-10) {
-      const double w     = exp(A.theta * log(dy / dx) + (1.0 - A.theta) * log(ctl->primal_weight));
-      ctl->primal_weight = w;
-      ctl->tau           = ctl->step_size / w;
-      ctl->sigma         = ctl->step_size * w;
-    }
-    ctl->its_since_restart = 0;
-    hal->k                 = 0;
-    *A.ctl_host = *ctl, *A.hal_host = *hal;  // the pinned mirrors save the read-back copies
-  }
+  halpern_restart_finish_workgroup(A, A.dist2, A.dist_host, red);
 }
 
 HalpernSmallView halpern_view(const pdlpdev_ctx* ctx)

@@ -462,6 +462,9 @@ struct CtxProblem {
   } p2p;
 };
 
+// bursts of device-decided major iterations, the periods they enqueued, the records written, the periods behind a stop (halpern_major.hpp)
+struct HalpernBurstStats { int64_t bursts = 0, periods = 0, records = 0, empty = 0; };
+
 // CtxLp: ONE LP over that problem -- its bounds, iterate, sums, averages, anchor, control block with the pinned mirror, partial buffers,
 // zero-skip bitmap and best-point snapshot on the device, and what the host knows about them without asking (validity flags, counters,
 // profiling events).  Written by everything that moves the LP (pdlpdev_reset, the loop, the evaluations).  A clone starts from the
@@ -502,7 +505,7 @@ struct CtxLp {
   // ring of 16 records in pinned host memory -- allocated only when the option is set; a clone starts without them like every CtxLp field
   struct pdlpdev_halpern_major_state* hmaj = nullptr;
   pdlpdev_halpern_major_record* hmaj_ring = nullptr;
-  int64_t stat_bursts = 0, stat_burst_periods = 0, stat_burst_records = 0, stat_burst_empty = 0;  // pdlpdev_halpern_burst_stats
+  HalpernBurstStats burst_stats;  // pdlpdev_halpern_burst_stats
   // n + pad doubles: A^T y partial + packed scalars between attempts (pdlpdev_compute_aty, the evaluation, pdlpdev_spectral_norm).  A
   // sharded context in Halpern mode (owner-computes dataflow) ALSO keeps x' of a run's last step there, on the rank's slice, from the
   // column block's product of that step until run_epilogue has all-gathered it and copied it into avgx (which has no spare entries for

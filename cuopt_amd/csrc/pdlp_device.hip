@@ -321,16 +321,7 @@ __global__ void k_halpern_clear(pdlpdev_halpern* hal)
 // behind k_restart + k_finalize (dist2 = the two squared distances): the smoothed primal weight on the device, the anchor's A^T y, k <- 0
 __global__ void k_halpern_restart_ctl(pdlpdev_ctl* ctl, pdlpdev_halpern* hal, double* dist2, double theta)
 {
-  const double dx = sqrt(dist2[0]), dy = sqrt(dist2[1]);
-  dist2[0] = dx, dist2[1] = dy;
-  if (theta >= 0.0 && dx > 1.0e-10 && dy > 1.0e-10) {
-    const double w     = exp(theta * log(dy / dx) + (1.0 - theta) * log(ctl->primal_weight));
-    ctl->primal_weight = w;
-    ctl->tau           = ctl->step_size / w;
-    ctl->sigma         = ctl->step_size * w;
-  }
-  ctl->its_since_restart = 0;
-  hal->k                 = 0;
+  halpern_restart_scalars(ctl, hal, dist2, theta);  // (halpern_decision.hpp: shared with every other restart of the mode)
 }
 __global__ void __launch_bounds__(kBlock)
 k_copy_current(int n, const pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ v0, const double* __restrict__ v1, double* __restrict__ out)
@@ -1492,7 +1483,7 @@ int pdlpdev_halpern_burst_eligible(pdlpdev_ctx* ctx, const pdlpdev_small_eval* r
 }
 int pdlpdev_halpern_burst_stats(pdlpdev_ctx* ctx, int64_t out[4])
 {
-  out[0] = ctx->stat_bursts, out[1] = ctx->stat_burst_periods, out[2] = ctx->stat_burst_records, out[3] = ctx->stat_burst_empty;
+  out[0] = ctx->burst_stats.bursts, out[1] = ctx->burst_stats.periods, out[2] = ctx->burst_stats.records, out[3] = ctx->burst_stats.empty;
   return 0;
 }
 // Per period, in stream order: the steps to the period's target (multi-launch: the guarded twin of k_set_target, then the attempt graphs
@@ -1517,7 +1508,7 @@ int pdlpdev_run_halpern_burst(pdlpdev_ctx* ctx, int32_t first_target, int32_t pe
   const bool want_linf = wants_linf(rq->eps_p, rq->eps_d);
   pdlpdev_halpern_major_params p = *params;
   p.want_linf = want_linf ? 1 : 0;
-  for (int j = 0; j < count; ++j) ctx->hmaj_ring[j].steps_taken = -1;  // ("not written": a decision leaves its step count here)
+  halpern_burst_mark_ring(ctx->hmaj_ring, count);
   TRY(halpern_major_launch_arm(ctx, r_prev));
   int enqueued = 0;
   for (int j = 0; j < count; ++j) {
@@ -1543,24 +1534,9 @@ int pdlpdev_run_halpern_burst(pdlpdev_ctx* ctx, int32_t first_target, int32_t pe
   HIP_TRY(hipStreamSynchronize(ctx->stream));
   ctx->stat_loop_syncs += 1;
   ctx->ctl_h_current = true;
-  ctx->stat_bursts += 1, ctx->stat_burst_periods += count;
-  int n_written = 0;
-  bool stop_seen = false;
-  for (int j = 0; j < count; ++j) {
-    const pdlpdev_halpern_major_record& r = ctx->hmaj_ring[j];
-    if (r.steps_taken < 0) {
-      stop_seen = true;  // (a period behind the stop: its launches were empty)
-      ctx->stat_burst_empty += 1;
-      continue;
-    }
-    if (stop_seen || n_written != j) return fail(-6, "pdlpdev_run_halpern_burst: a record was written behind the period that stopped the burst");
-    records[n_written++] = r;
-    if (r.verdict != PDLPDEV_MAJOR_GO_ON) stop_seen = true;
-    else r_prev = r.restart ? -1.0 : r.r;  // (what the decision left in the burst's block)
-  }
-  ctx->stat_burst_records += n_written;
-  *written = n_written;
-  if (r_prev_out) *r_prev_out = r_prev;
+  ctx->burst_stats.bursts += 1, ctx->burst_stats.periods += count;
+  if (halpern_burst_collect(ctx->hmaj_ring, count, r_prev, records, written, r_prev_out, &ctx->burst_stats))
+    return fail(-6, "pdlpdev_run_halpern_burst: a record was written behind the period that stopped the burst");
   if (!resident) {
     note_attempts(ctx, before, attempts_before, enqueued);  // (k_*_at_halpern stored A^T y of z^{k+1})
     ctx->rejected_in_a_row = 0;                             // (a Halpern step never fails)

@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "cuopt_amd/pdlp_solver.h"
+#include "halpern_restart_tests.hpp"
 #include "host_parallel.hpp"
 
 namespace {
@@ -778,14 +779,10 @@ int halpern_major_head(cuoptamd_solver* s, const double* ev_t, const double* ray
     *terminated = true;
     return 0;
   }
-  // ---- restart tests ----
-  const double r = s->hal.r, r_first = s->hal.r_first;
-  bool restart = false;
-  if (r <= H.sufficient_reduction_for_restart * r_first) restart = true;
-  else if (r <= H.necessary_reduction_for_restart * r_first && s->halpern_r_prev >= 0.0 && r > s->halpern_r_prev) restart = true;
-  else if ((double)s->hal.k >= H.artificial_restart_threshold * (double)s->total_iterations) restart = true;
-  s->halpern_r_prev = r;
-  *restart_out      = restart;
+  // ---- restart tests (halpern_restart_tests.hpp: the device's decision runs the same function) ----
+  *restart_out = halpern_restart_due(s->hal.r, s->hal.r_first, s->halpern_r_prev, s->hal.k, s->total_iterations, H.sufficient_reduction_for_restart,
+                                     H.necessary_reduction_for_restart, H.artificial_restart_threshold);
+  s->halpern_r_prev = s->hal.r;
   return 0;
 }
 // behind the device's restart (s->ctl and s->hal hold what it left)

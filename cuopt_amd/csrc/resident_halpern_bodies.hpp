@@ -1,11 +1,12 @@
-// The two one-workgroup bodies of the reflected-Halpern mode on the resident small-LP path: the loop (resident_halpern_body) and the
-// evaluation of T(z^k) (major_small_halpern_body).  In a header since kernels_halpern_major.hip wraps both in kernels of its own (the
-// burst of device-decided major iterations, cuoptamd_settings::halpern_device_major); kernels_resident_halpern.hip instantiates them
-// exactly as it did while they stood in that file: its kernels keep their instructions.
+// The three one-workgroup bodies of the reflected-Halpern mode on the resident small-LP path: the loop (resident_halpern_body), the
+// evaluation of T(z^k) (major_small_halpern_body) and the finish of a restart (halpern_restart_finish_workgroup).  In a header since
+// kernels_halpern_major.hip wraps all three in kernels of its own (the burst of device-decided major iterations,
+// cuoptamd_settings::halpern_device_major); kernels_resident_halpern.hip instantiates the first two exactly as while they stood there.
 #pragma once
 #include "pdlp_ctx.hpp"
 #include "pdlp_layouts.hpp"
 #include "resident_common.hpp"
+#include "halpern_decision.hpp"
 
 // p, which points to global memory, as a pointer the compiler knows that of (the empty statement keeps the two casts from cancelling
 // and names a scalar register: the value is uniform)
@@ -284,4 +285,27 @@ __device__ __forceinline__ void major_small_halpern_body(const MajorSmallArgs& A
     }
   }
   if (t == 0) A.sc[63] = 1.0;
+}
+
+// The finish of the restart of ONE resident LP by one workgroup of kBlock threads, behind k_restart_batch's blocks: what
+// pdlpdev_halpern_restart enqueues behind k_restart for one LP -- k_finalize's two sums (finalize_rows: the same tree) into dist2,
+// k_copy_current of A^T y into the anchor's, halpern_restart_scalars with this LP's theta; the distances also go to dist_out, both blocks
+// to their pinned mirrors.  A.clear != 0 (a reset): k_halpern_clear's values first.  red: 8 doubles of LDS.
+__device__ __forceinline__ void halpern_restart_finish_workgroup(const HalpernRestartArgs& A, double* dist2, double* dist_out, double* red)
+{
+  const int cur = A.ctl->cur;  // (read by every thread in front of finalize_rows' barriers; thread 0 rewrites the block behind them)
+  finalize_rows(A.part, A.g, 2, 0u, dist2, red);
+  const double* __restrict__ v = cur ? A.aty1 : A.aty0;
+  for (int i = threadIdx.x; i < A.n; i += kBlock) A.lraty[i] = v[i];
+  if (threadIdx.x != 0) return;
+  pdlpdev_halpern* hal = A.hal;
+  if (A.clear) {  // k_halpern_clear
+    hal->r = hal->r_first = hal->r2 = 0.0;
+    hal->r2_min = __builtin_huge_val();
+    hal->k = 0, hal->reserved = 0;
+  }
+  double d[2] = {dist2[0], dist2[1]};  // (in registers: a store to the blocks may alias dist2, and each reload behind one is a round trip)
+  halpern_restart_scalars(A.ctl, hal, d, A.theta);
+  dist2[0] = dist_out[0] = d[0], dist2[1] = dist_out[1] = d[1];
+  *A.ctl_host = *A.ctl, *A.hal_host = *hal;
 }

@@ -117,7 +117,7 @@ def main():
             if ia == ib:
                 continue
             diff_k += 1
-            short = name.split("(")[0]
+            short = name.replace("(anonymous namespace)::", "").split("(")[0]
             detail.append(f"  {u}: {short}: {len(ia) if ia is not None else 'absent'} -> {len(ib) if ib is not None else 'absent'}"
                           f" instructions, {differing(ia or [], ib or [])} differ")
         whole = sum(x != y for x, y in zip(a[2:], b[2:])) + abs(len(a) - len(b))  # (by position: a count, not an alignment)
