@@ -23,7 +23,7 @@ namespace cuopt_amd {
 // Knobs that only tests, harnesses and tuning sweeps turn live in ONE environment string, read at every query (set-up time only):
 //   CUOPT_AMD_TUNE="slab_bytes=65536,panel_nnz=4096,dense=0"
 // keys: slab_bytes, panel_nnz, panel_ws_bytes, panel_seg, jag_waves, dense, roctx, transpose_direct, fault_inject, soft_communicator,
-// simplex_grade, simplex_pricing, simplex_solves, simplex_debug, eval_reuse_aty, period_path, zero_skip, panel_sort, panel_req_order (each documented where it is read).
+// simplex_grade, simplex_pricing, simplex_solves, simplex_debug, eval_reuse_aty, period_path, zero_skip, panel_sort, panel_req_order, primal_decides, primal_decide_grid (each documented where it is read).
 inline bool tune_get(const char* key, std::string* out)
 {
   const char* e = getenv("CUOPT_AMD_TUNE");

@@ -545,6 +545,9 @@ static int create_impl(pdlpdev_ctx** out, int device, int32_t m, int32_t n, cons
     const char* small_env = getenv("CUOPT_AMD_SMALL");
     const int tier        = resident_tier(m, n, ctx->nnz);
     ctx->eval_reuse_aty   = cuopt_amd::tune_int("eval_reuse_aty", 1) != 0;
+    const long long decides_key = cuopt_amd::tune_int("primal_decides", -1);
+    ctx->primal_decides   = decides_key < 0 ? n >= pdlpdev_ctx::kPrimalDecidesMinCols : decides_key != 0;
+    ctx->primal_decide_grid_cap = (int)std::max<long long>(1, std::min<long long>(cuopt_amd::tune_int("primal_decide_grid", 512), 512));
     ctx->small_resident   = tier >= 0 && !(small_env && atoi(small_env) == 0) && !ctx->A.dense_add && !ctx->At.dense_add && !g_create_no_resident;
     g_create_no_resident  = 0;
     if (small_env && atoi(small_env) != 0 && tier < 0)

@@ -406,6 +406,18 @@ struct CtxProblem {
   double *dr = nullptr, *dc = nullptr;
   bool scaled = false;
   int eval_reuse_aty = 1;   // CUOPT_AMD_TUNE=eval_reuse_aty
+  // CUOPT_AMD_TUNE=primal_decides=0|1 (default: by n, below): on one GPU in the averaging modes a chunk of N attempts -- one graph, or the plain
+  // launches of a round -- decides the step of attempts 1 .. N - 1 at the head of the NEXT attempt's primal kernel, under its operand
+  // loads, and launches the decision kernel once, behind the last attempt (enqueue_single_chunk, pdlp_device.hip: 3 N + 1 launches).
+  // 0: the decision kernel behind every attempt, 4 N launches (A/B runs, tests).  The same bits either way.
+  // Without the key: on from kPrimalDecidesMinCols columns.  Measured against the parent's sequence (three alternating runs each,
+  // profiles/primal_decides_other_workloads.jsonl): n = 1e5 (C2, stream layout: 25 workgroups of the fused kernel, nothing to hide the
+  // chain under) 32.5 k against 33.5 k it/s, 2.9 % SLOWER at a spread of 0.7 %; n = 1e6: C3 + 1.7 %, banded + 3.1 %.  The break-even lies
+  // between the two and was not located: the constant stays near the measured gain -- 192 workgroups of 4096 columns, three quarters of
+  // the 256 CUs.
+  static constexpr int kPrimalDecidesMinCols = 786432;
+  int primal_decides = 1;
+  int primal_decide_grid_cap = 512;  // most workgroups of k_primal_decide (kPrimalDecideMaxGrid; CUOPT_AMD_TUNE=primal_decide_grid=1 .. 512: tests)
   int batch_lanes = 0;  // jagged layouts built for lockstep batches of up to this many LPs (cuoptamd_settings::batch_lanes)
   bool small_resident = false;  // whole attempt batches inside one workgroup (k_pdhg_small)
   // multi-GPU (a sharded context is never cloned: the dataflow's own buffers stay with what describes it)
@@ -484,6 +496,10 @@ struct CtxLp {
   unsigned long long* xmask = nullptr;
   int* zcount = nullptr;  // k_primal's per-workgroup counts of the set bits (grid_for(n) of them): the density guard's input
   int zs_mode = 0;        // 1: the product skips when the control block's flag is up (pdlpdev_ctl::zskip); 2: always
+  // A chunk of attempts that decides in the primal kernel (CtxProblem::primal_decides): the two scratch control blocks its decided blocks
+  // alternate between and the second buffer of counts (zcount is the first).  Allocated at the first such chunk (chunk_blocks_ready).
+  pdlpdev_ctl* chunk_ctl[2] = {nullptr, nullptr};
+  int* zcount_alt = nullptr;
   double *lrx = nullptr, *lry = nullptr, *rc[2] = {nullptr, nullptr};
   double *tmp_n = nullptr, *tmp_m = nullptr;
   double *ax_u[3] = {nullptr, nullptr, nullptr}, *aty_u[3] = {nullptr, nullptr, nullptr};  // unscaled A x / A^T y of pdlpdev_eval(which)

@@ -122,6 +122,42 @@ __global__ void __launch_bounds__(kBlock) k_finalize(const double* __restrict__ 
 //     deferred averaging of the previously accepted iterate (weighted_average_solution.cu:73-108).
 // primal_body<false> is k_primal as it was, argument list included; <true> (k_primal_zs) also writes the bitmap of xbar's non-zeros and
 // counts them.
+// One column of the step: the projected x' into xn, the extrapolated xbar (returned) and, ZS, the wave's ballot of its non-zeros.
+// (xmask: one bit per column, set where xbar is not 0.0 -- what the panels of A need to skip the gathers of zeros.  A wave's 64
+//  columns are consecutive and start at a multiple of 64, so its ballot is one whole word of the bitmap; lanes beyond n are not in the
+//  call and count as zeros.  -0.0 compares equal to 0.0: clear; NaN and infinities: set.  nz: the set bits the wave has seen.)
+template <bool ZS>
+__device__ __forceinline__ double primal_column(int j, double xj, double cj, double atyj, double lbj, double ubj, double tau, double* __restrict__ xn,
+                                                double* __restrict__ xbar, unsigned long long* __restrict__ xmask, int& nz)
+{
+  const double gradient = cj - atyj;
+  double next           = xj - (tau * gradient);
+  next                  = dmax(dmin(next, ubj), lbj);
+  xn[j]                 = next;
+  const double xb       = next - xj + next;
+  xbar[j]               = xb;
+  if constexpr (ZS) {
+    const unsigned long long bits = __ballot(xb != 0.0);
+    if ((threadIdx.x & 63) == 0) xmask[j >> 6] = bits;
+    nz += __popcll(bits);
+  }
+  return xb;
+}
+// zcount, with xmask: the set bits per workgroup of WAVES waves, an exact integer that the decision adds up for the density guard
+// (lane 0 of a wave is in every call its wave makes, so its count is the wave's)
+template <int WAVES>
+__device__ __forceinline__ void primal_store_zcount(int nz, int* __restrict__ zcount)
+{
+  __shared__ int wave_nz[WAVES];
+  if ((threadIdx.x & 63) == 0) wave_nz[threadIdx.x >> 6] = nz;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int sum = 0;
+#pragma unroll
+    for (int w = 0; w < WAVES; ++w) sum += wave_nz[w];
+    zcount[blockIdx.x] = sum;
+  }
+}
 template <bool ZS>
 __device__ __forceinline__ void
 primal_body(int n, const pdlpdev_ctl* __restrict__ ctl, double* __restrict__ x0, double* __restrict__ x1,
@@ -130,10 +166,6 @@ primal_body(int n, const pdlpdev_ctl* __restrict__ ctl, double* __restrict__ x0,
          double* __restrict__ xbar, double* __restrict__ sumx, const p2pdev::Push* __restrict__ push, pdlpdev_ctx::UniformBounds ubd,
          unsigned long long* __restrict__ xmask, int* __restrict__ zcount)
 {
-  // (xmask, may be null: one bit per column, set where xbar is not 0.0 -- what the panels of A need to skip the gathers of zeros.  A
-  //  wave's 64 columns are consecutive and start at a multiple of 64, so its ballot is one whole word of the bitmap; lanes beyond n
-  //  have left the loop and count as zeros.  -0.0 compares equal to 0.0: clear; NaN and infinities: set.
-  //  zcount, with xmask: the set bits per workgroup, an exact integer that k_step_decision_zs adds up for the density guard.)
   [[maybe_unused]] int nz = 0;
   // (ubd: every lower / upper bound is the same 0 or infinity -- x >= 0 is the usual LP -- so the bound arrays, 16 of the kernel's
   //  72 bytes per column, are not read at all; scaling keeps 0 and infinity what they are)
@@ -146,35 +178,15 @@ primal_body(int n, const pdlpdev_ctl* __restrict__ ctl, double* __restrict__ x0,
   double* __restrict__ xn        = cur ? x0 : x1;
   const double* __restrict__ aty = cur ? aty1 : aty0;
   for (int j = blockIdx.x * kBlock + threadIdx.x; j < n; j += gridDim.x * kBlock) {
-    const double xj       = x[j];
-    const double gradient = c[j] - aty[j];
-    double next           = xj - (tau * gradient);
-    next                  = dmax(dmin(next, ubd.ub_same ? ubd.ub : ub[j]), ubd.lb_same ? ubd.lb : lb[j]);
-    xn[j]                 = next;
-    const double xb       = next - xj + next;
-    xbar[j]               = xb;
-    if constexpr (ZS) {
-      const unsigned long long bits = __ballot(xb != 0.0);
-      if ((threadIdx.x & 63) == 0) xmask[j >> 6] = bits;
-      nz += __popcll(bits);
-    }
+    const double xj = x[j];
+    const double xb = primal_column<ZS>(j, xj, c[j], aty[j], ubd.lb_same ? ubd.lb : lb[j], ubd.ub_same ? ubd.ub : ub[j], tau, xn, xbar, xmask, nz);
     if (push)  // sharded solve, direct peer transport: this rank's slice of xbar lands in every OTHER rank's block (its own copy is
                // the ordinary store above: write-through stores cost 17 us per attempt at C3 and buy nothing at home)
       for (int q = 0; q < push->world; ++q)
         if (push->wants(q, j)) p2pdev::put(push->slot(q) + j, xb);
     if (pend) sumx[j] = sumx[j] + weight * xj;
   }
-  if constexpr (ZS) {  // (lane 0 of a wave is in every iteration its wave makes, so its count is the wave's)
-    __shared__ int wave_nz[kBlock / 64];
-    if ((threadIdx.x & 63) == 0) wave_nz[threadIdx.x >> 6] = nz;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      int sum = 0;
-#pragma unroll
-      for (int w = 0; w < kBlock / 64; ++w) sum += wave_nz[w];
-      zcount[blockIdx.x] = sum;
-    }
-  }
+  if constexpr (ZS) primal_store_zcount<kBlock / 64>(nz, zcount);
   if (push) p2pdev::count_exchange(push);
 }
 __global__ void __launch_bounds__(kBlock)
@@ -235,71 +247,230 @@ static_assert(kDecisionThreads == kHalpernDecisionThreads, "k_halpern_decision r
 // are added up as a fourth sum (integers below 2^31 as doubles: exact in any order) and set the flag the NEXT attempt's A product
 // reads: up at 25 % zeros or more, down at 13 % or fewer (measured break-even on the 1e6 x 1e6 LP: docs/design/09_next.md item
 // 9), unchanged in between; zmode 2 keeps it up.  The flag never changes a result, only which code path forms it.
-template <bool ZS = false>
-__device__ __forceinline__ void step_decision_workgroup(pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ part_dy, int nb_dy,
-                                                        const double* __restrict__ part_t, int nb_t, const double* __restrict__ dy2_reduced,
-                                                        const pdlpdev_step_params& sp, const int* __restrict__ zcount = nullptr, int nb_z = 0,
-                                                        int zn = 0, int zmode = 0)
+//
+// step_decision_form is the decision without its loads and stores of the control block: `lc` comes in as the block the attempt ran with
+// (loop active) and leaves as the decided one -- in thread 0, or, EVERY, in every thread (the sums end in every lane, each thread then
+// applies the rule to the same values: k_primal_decide, whose workgroups all go on with the decided block).
+// step_decision_workgroup reads the block at `in` and stores the decided one at `out`.  in == out: the loop's own block, nothing is
+// stored when the attempt was empty (the loop is not active).  in != out (the end of a chunk of attempts that went from scratch block
+// to scratch block, enqueue_single_chunk): `out` always ends up current -- an empty attempt copies the block through.
+// Each thread's FIRST partial of every sum is requested up front, then `ahead()` runs (k_primal_decide: its operand requests, which
+// thereby stand BEHIND the partials in the order the loads return and are not waited for by the sums), then the sums are formed in the
+// order they always were: thread t adds partials t, t + 1024, ... to 0.0.
+template <bool ZS, bool EVERY, class Ahead>
+__device__ __forceinline__ void step_decision_form(pdlpdev_ctl& lc, const double* __restrict__ part_dy, int nb_dy, const double* __restrict__ part_t, int nb_t,
+                                                   const double* __restrict__ dy2_reduced, const pdlpdev_step_params& sp, const int* __restrict__ zcount,
+                                                   int nb_z, int zn, int zmode, Ahead&& ahead)
 {
   __shared__ double red[(ZS ? 4 : 3) * 16];
   __shared__ double pw[2];
-  pdlpdev_ctl lc = *ctl;
-  if (!(lc.error == 0 && lc.steps_taken < lc.target_steps)) return;
   const int t = threadIdx.x;
+  // (a thread beyond an array's end requests the last entry and leaves it unused: the requests stay one straight run of loads, which the
+  //  compiler does not tie to the sums' conditions)
+  const bool has_dy = dy2_reduced == nullptr && t < nb_dy, has_t = t < nb_t, has_z = ZS && t < nb_z;
+  const int i_t = min(t, nb_t - 1);
+  const double first_dy = dy2_reduced == nullptr && nb_dy > 0 ? part_dy[min(t, nb_dy - 1)] : 0.0;
+  const double first_t0 = nb_t > 0 ? part_t[i_t] : 0.0, first_t1 = nb_t > 0 ? part_t[nb_t + i_t] : 0.0;
+  [[maybe_unused]] int first_z = 0;
+  if constexpr (ZS) first_z = nb_z > 0 ? zcount[min(t, nb_z - 1)] : 0;
+  ahead();
   if (t >= kDecisionThreads - 2) {
     const double knext = (double)(lc.k + 1) + 1.0;
     pw[t - (kDecisionThreads - 2)] = pow(knext, t == kDecisionThreads - 2 ? -sp.reduction_exponent : -sp.growth_exponent);
   }
-  double acc[ZS ? 4 : 3] = {0.0, 0.0, 0.0};
+  // (the sums start from a zero the compiler cannot see through: it would otherwise form "0.0 + first" right behind each request, in
+  //  front of ahead(), and wait for the partial there)
+  double zero = 0.0;
+  int izero   = 0;
+  asm volatile("" : "+v"(zero), "+v"(izero));
+  double acc[ZS ? 4 : 3] = {zero, zero, zero};
   if (dy2_reduced == nullptr) {
+    if (has_dy) acc[0] += first_dy;
 #pragma unroll 4
-    for (int i = t; i < nb_dy; i += kDecisionThreads) acc[0] += part_dy[i];
+    for (int i = t + kDecisionThreads; i < nb_dy; i += kDecisionThreads) acc[0] += part_dy[i];
   }
+  if (has_t) acc[1] += first_t0, acc[2] += first_t1;
 #pragma unroll 4
-  for (int i = t; i < nb_t; i += kDecisionThreads) {
+  for (int i = t + kDecisionThreads; i < nb_t; i += kDecisionThreads) {
     acc[1] += part_t[i];
     acc[2] += part_t[nb_t + i];
   }
   if constexpr (ZS) {
-    acc[3] = 0.0;
+    acc[3] = zero;
+    if (has_z) acc[3] += (double)(first_z + izero);
 #pragma unroll 2
-    for (int i = t; i < nb_z; i += kDecisionThreads) acc[3] += (double)zcount[i];
+    for (int i = t + kDecisionThreads; i < nb_z; i += kDecisionThreads) acc[3] += (double)zcount[i];
   }
   block_sum_fast<ZS ? 4 : 3, kDecisionThreads / 64>(acc, red);
-  if (t != 0) return;
+  if (!EVERY && t != 0) return;
   apply_step_decision(&lc, dy2_reduced ? dy2_reduced[0] : acc[0], acc[1], acc[2], sp, pw);
   if constexpr (ZS) {
     const long long nonzeros = (long long)acc[3];
     lc.zs_nonzeros           = (int32_t)nonzeros;
     if (zmode == 2 || nonzeros * 4 <= 3ll * zn) lc.zskip = 1;
     else if (nonzeros * 100 >= 87ll * zn) lc.zskip = 0;
-    *ctl = lc;
+  }
+}
+// one thread's store of a control block
+template <bool ZS>
+__device__ __forceinline__ void store_ctl(pdlpdev_ctl* out, const pdlpdev_ctl& lc)
+{
+  if constexpr (ZS) {
+    *out = lc;
   } else {
     // (the decision without the guard neither reads nor writes the guard's two fields at the block's end: the loads and stores of this
     //  latency-bound kernel are the ones it had before the block grew)
-    __builtin_memcpy(ctl, &lc, offsetof(pdlpdev_ctl, zskip));
+    __builtin_memcpy(out, &lc, offsetof(pdlpdev_ctl, zskip));
   }
 }
+template <bool ZS = false>
+__device__ __forceinline__ void step_decision_workgroup(const pdlpdev_ctl* in, pdlpdev_ctl* out, const double* __restrict__ part_dy, int nb_dy,
+                                                        const double* __restrict__ part_t, int nb_t, const double* __restrict__ dy2_reduced,
+                                                        const pdlpdev_step_params& sp, const int* __restrict__ zcount = nullptr, int nb_z = 0,
+                                                        int zn = 0, int zmode = 0)
+{
+  pdlpdev_ctl lc = *in;
+  if (!(lc.error == 0 && lc.steps_taken < lc.target_steps)) {
+    if (in != out && threadIdx.x == 0) store_ctl<ZS>(out, lc);
+    return;
+  }
+  step_decision_form<ZS, false>(lc, part_dy, nb_dy, part_t, nb_t, dy2_reduced, sp, zcount, nb_z, zn, zmode, [] {});
+  if (threadIdx.x == 0) store_ctl<ZS>(out, lc);
+}
+// (in: the block the attempt ran with; out: where the decided one goes -- the same block everywhere but at the end of a chunk)
 __global__ void __launch_bounds__(kDecisionThreads)
-k_step_decision(pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ part_dy, int nb_dy,
+k_step_decision(const pdlpdev_ctl* in, pdlpdev_ctl* out, const double* __restrict__ part_dy, int nb_dy,
                 const double* __restrict__ part_t, int nb_t, const double* __restrict__ dy2_reduced,
                 pdlpdev_step_params sp)
 {
-  step_decision_workgroup(ctl, part_dy, nb_dy, part_t, nb_t, dy2_reduced, sp);
+  step_decision_workgroup(in, out, part_dy, nb_dy, part_t, nb_t, dy2_reduced, sp);
 }
 // (single GPU, averaging modes, with the bitmap of xbar in use: attempt_xmask)
 __global__ void __launch_bounds__(kDecisionThreads)
-k_step_decision_zs(pdlpdev_ctl* __restrict__ ctl, const double* __restrict__ part_dy, int nb_dy,
+k_step_decision_zs(const pdlpdev_ctl* in, pdlpdev_ctl* out, const double* __restrict__ part_dy, int nb_dy,
                    const double* __restrict__ part_t, int nb_t, pdlpdev_step_params sp, const int* __restrict__ zcount, int nb_z, int zn, int zmode)
 {
-  step_decision_workgroup<true>(ctl, part_dy, nb_dy, part_t, nb_t, nullptr, sp, zcount, nb_z, zn, zmode);
+  step_decision_workgroup<true>(in, out, part_dy, nb_dy, part_t, nb_t, nullptr, sp, zcount, nb_z, zn, zmode);
+}
+
+// ---- the decision of the PREVIOUS attempt at the head of the primal step (attempts 2 .. N of a chunk: enqueue_single_chunk) ---------
+// k_primal's 56 bytes per column take their 10 us in any order, and more than 98 % of the 1e6 x 1e6 LP's attempts are accepted.  So
+// every workgroup (1) reads the block the previous attempt ran with and REQUESTS the operands of its first kPrimalDecideCols columns per
+// thread as if that attempt was accepted -- the flipped side of x and A^T y, c, sum_x, the bounds unless they are uniform --, (2) forms
+// the decision while they are in flight: step_decision_form, the association and the pow() calls of the one-workgroup kernel, so the
+// same bits in every workgroup, (3) after a rejection loads x and A^T y again from the side the decision names (rare, slower),
+// (4, 5) and goes through its columns with the decided tau, step size, pending_avg and cur, unless the decided block ends the loop.
+// Workgroup 0 stores the decided block at `out`: the block this attempt's two products and the next decision read.  `in` is never
+// written by this kernel and `zcount_in` (the previous primal step's counts) is not the buffer this one writes: a workgroup may be done
+// before another has started.  An empty previous attempt (loop not active at `in`) copies the block through and leaves the columns alone.
+constexpr int kPrimalDecideCols = 4;     // columns per thread requested ahead of the decision: 245 workgroups at n = 1e6, one per CU
+constexpr int kPrimalDecideMaxGrid = 512;  // (every workgroup reads all partials: a few hundred of them keep that traffic negligible)
+// (cap: kPrimalDecideMaxGrid, or what CUOPT_AMD_TUNE=primal_decide_grid asks for -- tests reach the grid-stride remainder with a small LP)
+static inline int primal_decide_grid(int n, int cap)
+{
+  const int per = kDecisionThreads * kPrimalDecideCols;
+  return std::max(1, std::min((n + per - 1) / per, cap));
+}
+template <bool ZS>
+__device__ __forceinline__ void
+primal_decide_body(int n, const pdlpdev_ctl* in, pdlpdev_ctl* out, double* __restrict__ x0, double* __restrict__ x1,
+                   const double* __restrict__ aty0, const double* __restrict__ aty1, const double* __restrict__ c, const double* __restrict__ lb,
+                   const double* __restrict__ ub, double* __restrict__ xbar, double* __restrict__ sumx, pdlpdev_ctx::UniformBounds ubd,
+                   unsigned long long* __restrict__ xmask, int* __restrict__ zcount_out, const double* __restrict__ part_dy, int nb_dy,
+                   const double* __restrict__ part_t, int nb_t, const pdlpdev_step_params& sp, const int* __restrict__ zcount_in, int nb_z, int zmode)
+{
+  constexpr int U = kPrimalDecideCols, T = kDecisionThreads;
+  [[maybe_unused]] int nz = 0;
+  pdlpdev_ctl lc = *in;
+  if (!(lc.error == 0 && lc.steps_taken < lc.target_steps)) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) store_ctl<ZS>(out, lc);
+    return;
+  }
+  // (1) the first columns' operands, as if accepted: requested right behind the decision's partials, (2) the decision
+  const int ahead = lc.cur ^ 1;
+  const int j0    = blockIdx.x * (U * T) + threadIdx.x;
+  double xj[U], tj[U], cj[U], sj[U], lbj[U], ubj[U];
+  step_decision_form<ZS, true>(lc, part_dy, nb_dy, part_t, nb_t, nullptr, sp, zcount_in, nb_z, n, zmode, [&] {
+    // (a thread beyond column n - 1 requests that column and leaves it unused, n > 0: one straight run of loads behind the partials', so
+    //  that the sums' wait counts them and lets them fly)
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int j = min(j0 + u * T, n - 1);
+      xj[u]  = (ahead ? x1 : x0)[j];
+      tj[u]  = (ahead ? aty1 : aty0)[j];
+      cj[u]  = c[j];
+      sj[u]  = sumx[j];
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) lbj[u] = ubd.lb_same ? ubd.lb : lb[min(j0 + u * T, n - 1)];
+#pragma unroll
+    for (int u = 0; u < U; ++u) ubj[u] = ubd.ub_same ? ubd.ub : ub[min(j0 + u * T, n - 1)];
+  });
+  if (blockIdx.x == 0 && threadIdx.x == 0) store_ctl<ZS>(out, lc);
+  if (!(lc.error == 0 && lc.steps_taken < lc.target_steps)) return;  // (4)
+  const int cur       = __builtin_amdgcn_readfirstlane(lc.cur);  // (the same in every thread: scalar)
+  const bool pend     = __builtin_amdgcn_readfirstlane(lc.pending_avg) != 0;
+  const double tau    = lc.tau;
+  const double weight = lc.step_size;
+  const double* __restrict__ x   = cur ? x1 : x0;
+  double* __restrict__ xn        = cur ? x0 : x1;
+  const double* __restrict__ aty = cur ? aty1 : aty0;
+  // (3) rejected: the iterate did not flip
+  if (cur != ahead) {
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int j = j0 + u * T;
+      if (j < n) xj[u] = x[j], tj[u] = aty[j];
+    }
+  }
+  // (5) the columns: k_primal's expressions
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    const int j = j0 + u * T;
+    if (j < n) {
+      primal_column<ZS>(j, xj[u], cj[u], tj[u], lbj[u], ubj[u], tau, xn, xbar, xmask, nz);
+      if (pend) sumx[j] = sj[u] + weight * xj[u];
+    }
+  }
+  // (an LP of more columns than the grid's first pass holds: the rest as k_primal takes them)
+  for (long long base = ((long long)blockIdx.x + gridDim.x) * (U * T); base < n; base += (long long)gridDim.x * (U * T)) {
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const long long jj = base + threadIdx.x + u * T;
+      if (jj < n) {
+        const int j = (int)jj;
+        const double xv = x[j];
+        primal_column<ZS>(j, xv, c[j], aty[j], ubd.lb_same ? ubd.lb : lb[j], ubd.ub_same ? ubd.ub : ub[j], tau, xn, xbar, xmask, nz);
+        if (pend) sumx[j] = sumx[j] + weight * xv;
+      }
+    }
+  }
+  if constexpr (ZS) primal_store_zcount<T / 64>(nz, zcount_out);
+}
+__global__ void __launch_bounds__(kDecisionThreads)
+k_primal_decide(int n, const pdlpdev_ctl* in, pdlpdev_ctl* out, double* __restrict__ x0, double* __restrict__ x1,
+                const double* __restrict__ aty0, const double* __restrict__ aty1, const double* __restrict__ c, const double* __restrict__ lb,
+                const double* __restrict__ ub, double* __restrict__ xbar, double* __restrict__ sumx, pdlpdev_ctx::UniformBounds ubd,
+                const double* __restrict__ part_dy, int nb_dy, const double* __restrict__ part_t, int nb_t, pdlpdev_step_params sp)
+{
+  primal_decide_body<false>(n, in, out, x0, x1, aty0, aty1, c, lb, ub, xbar, sumx, ubd, nullptr, nullptr, part_dy, nb_dy, part_t, nb_t, sp, nullptr, 0, 0);
+}
+__global__ void __launch_bounds__(kDecisionThreads)
+k_primal_decide_zs(int n, const pdlpdev_ctl* in, pdlpdev_ctl* out, double* __restrict__ x0, double* __restrict__ x1,
+                   const double* __restrict__ aty0, const double* __restrict__ aty1, const double* __restrict__ c, const double* __restrict__ lb,
+                   const double* __restrict__ ub, double* __restrict__ xbar, double* __restrict__ sumx, pdlpdev_ctx::UniformBounds ubd,
+                   unsigned long long* __restrict__ xmask, int* __restrict__ zcount_out, const double* __restrict__ part_dy, int nb_dy,
+                   const double* __restrict__ part_t, int nb_t, pdlpdev_step_params sp, const int* __restrict__ zcount_in, int nb_z, int zmode)
+{
+  primal_decide_body<true>(n, in, out, x0, x1, aty0, aty1, c, lb, ub, xbar, sumx, ubd, xmask, zcount_out, part_dy, nb_dy, part_t, nb_t, sp, zcount_in, nb_z,
+                           zmode);
 }
 // the decisions of the K LPs of a shared-matrix batch (kernels_batch.hip): workgroup <-> LP, each exactly k_step_decision
 __global__ void __launch_bounds__(kDecisionThreads)
 k_step_decision_batch(const pdlpdev_decision_args* __restrict__ args)
 {
   const pdlpdev_decision_args a = args[blockIdx.x];
-  step_decision_workgroup(a.ctl, a.part_dy, a.nb_dy, a.part_t, a.nb_t, nullptr, a.sp);
+  step_decision_workgroup(a.ctl, a.ctl, a.part_dy, a.nb_dy, a.part_t, a.nb_t, nullptr, a.sp);
 }
 
 // The decision of a Halpern step (docs/design/04d_halpern_mode.md): nothing to decide -- a step never fails -- but the same one workgroup
@@ -1059,13 +1230,29 @@ void launch_plain(pdlpdev_ctx* ctx, int transpose, const double* vec, double* ou
 {
   (void)launch_product(ctx, transpose ? ctx->At : ctx->A, products::plain, Gathered::fixed(vec), std::make_tuple(), std::make_tuple(vec), std::make_tuple(out));
 }
+// the decision of the attempt that ran with the block at ctx->ctl, into `out`; zc: the counts its primal step left, nb_z of them
+static void launch_decision_into(pdlpdev_ctx* ctx, pdlpdev_ctl* out, const int* zc, int nb_z)
+{
+  if (attempt_xmask(ctx))
+    return launch_k(ctx, k_step_decision_zs, 1, kDecisionThreads, 0, ctx->ctl, out, ctx->A.part, ctx->A.partials(), ctx->At.part, ctx->At.partials(), ctx->sp, zc, nb_z,
+                    ctx->n, ctx->zs_mode);
+  launch_k(ctx, k_step_decision, 1, kDecisionThreads, 0, ctx->ctl, out, ctx->A.part, ctx->A.partials(), ctx->At.part, ctx->At.partials(), nullptr, ctx->sp);
+}
 static void launch_decision(pdlpdev_ctx* ctx)
 {
   if (ctx->halpern) return launch_k(ctx, k_halpern_decision, 1, kDecisionThreads, 0, ctx->ctl, ctx->hal, ctx->A.part, ctx->A.partials(), ctx->At.part, ctx->At.partials());
-  if (attempt_xmask(ctx))
-    return launch_k(ctx, k_step_decision_zs, 1, kDecisionThreads, 0, ctx->ctl, ctx->A.part, ctx->A.partials(), ctx->At.part, ctx->At.partials(), ctx->sp, ctx->zcount,
-                    grid_for(ctx->n), ctx->n, ctx->zs_mode);
-  launch_k(ctx, k_step_decision, 1, kDecisionThreads, 0, ctx->ctl, ctx->A.part, ctx->A.partials(), ctx->At.part, ctx->At.partials(), nullptr, ctx->sp);
+  launch_decision_into(ctx, ctx->ctl, ctx->zcount, grid_for(ctx->n));
+}
+// the primal step of all columns behind the decision of the attempt that ran with the block at `in` (k_primal_decide); the decided block
+// goes to `out`, this step's counts to zc_out
+static void launch_primal_decide(pdlpdev_ctx* ctx, const pdlpdev_ctl* in, pdlpdev_ctl* out, const int* zc_in, int nb_z, int* zc_out)
+{
+  const int n = ctx->n;
+  if (unsigned long long* xmask = attempt_xmask(ctx))
+    return launch_k(ctx, k_primal_decide_zs, primal_decide_grid(n, ctx->primal_decide_grid_cap), kDecisionThreads, 0, n, in, out, ctx->x[0], ctx->x[1], ctx->aty[0], ctx->aty[1], ctx->c, ctx->lb, ctx->ub,
+                    ctx->xbar, ctx->sumx, ctx->ubd, xmask, zc_out, ctx->A.part, ctx->A.partials(), ctx->At.part, ctx->At.partials(), ctx->sp, zc_in, nb_z, ctx->zs_mode);
+  launch_k(ctx, k_primal_decide, primal_decide_grid(n, ctx->primal_decide_grid_cap), kDecisionThreads, 0, n, in, out, ctx->x[0], ctx->x[1], ctx->aty[0], ctx->aty[1], ctx->c, ctx->lb, ctx->ub, ctx->xbar,
+           ctx->sumx, ctx->ubd, ctx->A.part, ctx->A.partials(), ctx->At.part, ctx->At.partials(), ctx->sp);
 }
 
 // owner-computes dataflow: A^T y' of this rank's columns from the gathered y' (complete sums) + the step statistics of the slice
@@ -1090,7 +1277,7 @@ static void launch_oc_step(pdlpdev_ctx* ctx, const ColSlice& sl)
 // k_step_decision on sums a collective has reduced (the same bits on every rank): ||dy||^2 at dy2, the other two as nb_t partials at part_t
 static void launch_decision_reduced(pdlpdev_ctx* ctx, const double* part_t, int nb_t, const double* dy2)
 {
-  launch_k(ctx, k_step_decision, 1, kDecisionThreads, 0, ctx->ctl, nullptr, 0, part_t, nb_t, dy2, ctx->sp);
+  launch_k(ctx, k_step_decision, 1, kDecisionThreads, 0, ctx->ctl, ctx->ctl, nullptr, 0, part_t, nb_t, dy2, ctx->sp);
 }
 
 // ---- one attempt, per dataflow.  Halpern mode (single GPU and owner-computes only): the launch helpers pick the twins' kernels, k_primal is the
@@ -1101,6 +1288,59 @@ static const AttemptStage kSingleStages[4] = {{PDLPDEV_K_PRIMAL, launch_primal},
 static int enqueue_single(pdlpdev_ctx* ctx)
 {
   for (const AttemptStage& st : kSingleStages) st.launch(ctx);
+  LAUNCH_CHECK();
+  return 0;
+}
+// A chunk of N attempts on the single GPU in the averaging modes (CUOPT_AMD_TUNE=primal_decides, pdlp_ctx.hpp): 3 N + 1 launches,
+//     primal,        a_dual, at_step        attempt 1: reads ctx->ctl, like the attempt above
+//     primal_decide, a_dual, at_step        attempts 2 .. N: the decision of the attempt before at the head of the primal step
+//     decision                              the last attempt's, into ctx->ctl
+// N = 1 is the attempt above, launch for launch.  The decided blocks go from one of the two scratch blocks to the other: attempt k's
+// primal_decide reads the block attempt k - 1 ran with and writes the other one, which its own products and the next decision read;
+// nothing outside the chunk ever sees them, and the last decision always leaves ctx->ctl current (step_decision_workgroup).  The counts
+// of xbar's non-zeros alternate between two buffers the same way: a primal step reads the previous one's for the decision while its
+// own workgroups write theirs.  Stream order between the kernels is all the synchronisation there is.
+// (While the chunk is enqueued ctx->ctl points at the block the launches of the attempt in hand read -- the launch helpers, the dense
+//  prologue and phase P of the gather-free layout all take it from there --; ChunkBlocks puts the loop's own block back.)
+static bool chunk_decides_in_primal(const pdlpdev_ctx* ctx) { return ctx->primal_decides && !ctx->halpern && !ctx->comm && !ctx->small_resident && ctx->n > 0; }
+// the chunk's scratch blocks and second count buffer: on first use, never inside a stream capture
+static int chunk_blocks_ready(pdlpdev_ctx* ctx)
+{
+  if (!chunk_decides_in_primal(ctx) || ctx->chunk_ctl[0]) return 0;
+  TRY(dev_alloc(ctx, &ctx->chunk_ctl[0], 1));
+  TRY(dev_alloc(ctx, &ctx->chunk_ctl[1], 1));
+  if (ctx->zcount) {  // (primal_decide_grid(n, cap) <= grid_for(n))
+    TRY(dev_alloc(ctx, &ctx->zcount_alt, (size_t)grid_for(ctx->n)));
+  }
+  return 0;
+}
+static int enqueue_single_chunk(pdlpdev_ctx* ctx, int attempts)
+{
+  if (!chunk_decides_in_primal(ctx) || attempts == 1) {
+    for (int k = 0; k < attempts; ++k) TRY(enqueue_single(ctx));
+    return 0;
+  }
+  if (!ctx->chunk_ctl[0]) return fail(-1, "enqueue_single_chunk: chunk_blocks_ready was not called");
+  struct ChunkBlocks {
+    pdlpdev_ctx* c;
+    pdlpdev_ctl* const home;
+    ~ChunkBlocks() { c->ctl = home; }
+  } blocks{ctx, ctx->ctl};
+  int* const zc[2] = {ctx->zcount, ctx->zcount_alt};
+  int nb_z         = grid_for(ctx->n);  // the counts the primal step in hand leaves in zc[k & 1]
+  for (int k = 0; k < attempts; ++k) {
+    if (k == 0) {
+      launch_primal(ctx);
+    } else {
+      pdlpdev_ctl* const decided = ctx->chunk_ctl[k & 1];
+      launch_primal_decide(ctx, ctx->ctl, decided, zc[(k - 1) & 1], nb_z, zc[k & 1]);
+      ctx->ctl = decided;
+      nb_z     = primal_decide_grid(ctx->n, ctx->primal_decide_grid_cap);
+    }
+    launch_a_dual(ctx);
+    launch_at_step(ctx);
+  }
+  launch_decision_into(ctx, blocks.home, zc[(attempts - 1) & 1], nb_z);
   LAUNCH_CHECK();
   return 0;
 }
@@ -1209,6 +1449,13 @@ static int enqueue_attempt(pdlpdev_ctx* ctx)
   if (ctx->rsag) return enqueue_rsag(ctx);
   return ctx->comm ? enqueue_replicated(ctx) : enqueue_single(ctx);
 }
+// a chunk of attempts that go out together (one graph, or the plain launches of a round): the single GPU has a sequence for the chunk
+static int enqueue_chunk(pdlpdev_ctx* ctx, int attempts)
+{
+  if (!ctx->comm && !ctx->owner && !ctx->rsag) return enqueue_single_chunk(ctx, attempts);
+  for (int i = 0; i < attempts; ++i) TRY(enqueue_attempt(ctx));
+  return 0;
+}
 
 static int get_graph(pdlpdev_ctx* ctx, int attempts, hipGraphExec_t* out)
 {
@@ -1217,10 +1464,10 @@ static int get_graph(pdlpdev_ctx* ctx, int attempts, hipGraphExec_t* out)
     *out = it->second;
     return 0;
   }
+  TRY(chunk_blocks_ready(ctx));
   hipGraph_t graph;
   HIP_TRY(hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
-  int rc = 0;
-  for (int i = 0; i < attempts && rc == 0; ++i) rc = enqueue_attempt(ctx);
+  const int rc = enqueue_chunk(ctx, attempts);
   hipError_t e = hipStreamEndCapture(ctx->stream, &graph);
   if (rc != 0) return rc;
   HIP_TRY(e);
@@ -1267,8 +1514,9 @@ static int enqueue_attempts(pdlpdev_ctx* ctx, int remaining)
       remaining -= chunk;
     }
   }
-  if (!replayed) {
-    for (int i = 0; i < remaining; ++i) TRY(enqueue_attempt(ctx));
+  if (!replayed && remaining > 0) {  // (plain launches: what is left of the round is one chunk)
+    TRY(chunk_blocks_ready(ctx));
+    TRY(enqueue_chunk(ctx, remaining));
   }
   return 0;
 }
