@@ -206,7 +206,9 @@ __device__ __forceinline__ void resident_halpern_body(const HalpernSmallView& V,
 // tried and both change k_major_small / k_major_small_batch: a mode-3 branch inside major_small_body, and a __forceinline__
 // per-point helper called by both bodies (1206 lines of llvm-objdump -d of kernels_resident's gfx950 code object differ) -- and
 // the existing kernels are to keep the instructions they had.  guard_target as in
-// k_major_small_batch; sc[63] says whether the evaluation ran.
+// k_major_small_batch; sc[63] says whether the evaluation ran.  Guarded by
+// tests/test_halpern_resident_steps_gpu.py::test_major_small_halpern_against_the_reference (this copy against tests/eval_reference.py,
+// as tests/test_resident_attempts_gpu.py holds the original).
 __device__ __forceinline__ void major_small_halpern_body(const MajorSmallArgs& A, double* prod /* nnz doubles of LDS */)
 {
   __shared__ double red[4 * kMajorThreads / 64];

@@ -70,7 +70,44 @@ THE RESTART (check_restart; pdlpdev_halpern_restart(theta)):
     tau = step_size / w_new and sigma = step_size * w_new, bit for bit from the device's own new weight.
 
 The reference's own error is at most N 2^-64 of the same magnitude sums (1/2048 of a bound).  The bounds are derived, not measured:
-a layout that exceeds one is a finding about the kernel concerned, not a reason to touch a bound."""
+a layout that exceeds one is a finding about the kernel concerned, not a reason to touch a bound.
+
+THE RESIDENT ONE-WORKGROUP LOOP (check_step(resident=True); resident_halpern_body, cuopt_amd/csrc/resident_halpern_bodies.hpp, through
+any of its three wrapper kernels).  There the owning lane of every row and of every column adds it up left to right in float64 from
+products rounded once (prod[] = val * vec[col], then lds_row_sum), so MORE is bit for bit than in the layouts, and nothing of a step
+is seen through a bound but its three sums.  `prob` carries AT_VALUES, the values the device holds for A^T's own CSR: scaling
+multiplies A by D_r then D_c and A^T by D_c then D_r, so an entry of the two may differ in its last bit, and the loop reads A^T's.
+  NOT READ: XBAR (the loop keeps xbar in LDS and never stores it) and PART_A / PART_AT (one workgroup: there are no partials; the
+  `part` ratio is 0).
+  (0) what the step must not change.  X_OTHER and Y_OTHER hold the bits of X and Y in front of the step: on the LAST step of a launch
+      the loop stores z^k into the side `cur` selects at that moment, which the step's flip makes the other one (the ray pass of the
+      evaluation reads it there).  The three anchors (read once into registers, never written), SUM_X and SUM_Y keep their bits.
+      ATY_OTHER holds the bits of ATY in front of the step BEHIND A SINGLE-STEP LAUNCH ONLY: that launch read that side and never
+      writes it.  Behind a multi-step launch ATY_OTHER is NOT PROMISED: the loop stores no A^T y^k (nothing reads it), so that side
+      holds whatever an earlier launch left.  check_step is only ever called behind a single-step launch (asserted), so it asserts all
+      three; halpern_step_scenario.check_composition, which looks behind a launch of 12 steps, leaves ATY_OTHER out.
+      check_last_step_store asserts the store behind a launch of any length from one state alone: AVG_Y is, bit for bit, stage (2)
+      applied to (X_OTHER, Y_OTHER) and AVG_X -- so what the ray pass reads as z^k is the point whose image the average slots hold.
+  (1) the primal half.  AVG_X = attempt_reference.primal()'s xn bit for bit (every launch that made a step stores the x' of its last
+      one); xbar is taken from primal() -- it is bit-exact from x', x -- and the new X = combine(k, xn, X, anchor X) bit for bit.
+  (2) the dual half.  AVG_Y = dual_f64(prob, ctl, before, rowsums_f64(A_VALUES, xbar, off, idx)) BIT FOR BIT on every row, which on
+      an empty row is dual_f64 at v = +0.0; the new Y = combine(k, AVG_Y, Y, anchor Y).
+  (3) the A^T product.  v = rowsums_f64(AT_VALUES, AVG_Y, t_off, t_rows) over A^T's own CSR (the stable transposition of A:
+      Structure.order), from the device's own AVG_Y; the new ATY = combine(k, v, ATY, anchor ATY) BIT FOR BIT -- on an empty column
+      combine(k, +0.0, ATY, anchor ATY).
+  (4) the three sums go through block_sum_fast's fixed tree, which is not left to right: they stay bounded.  Every lane adds its own
+      terms in registers, then the tree: any order of n (m) terms.  dy2 and dx2 keep step_sums' bounds, (m + 16) u and (n + 16) u of
+      the sums of squares (dy = fl(y' - y) is one rounding of the exact difference, its square two more, the tree at most N - 1 per
+      term).  The interaction: the device adds fl(t^_j dx^_j) with t^ = fl(v_j - a_j) and dx^ = fl(x'_j - x_j), v the SAME float64
+      number the reference holds (stage 3 is bit for bit).  One rounding each for t^, dx^ and the product and at most n - 1 for the
+      tree give, to first order,
+          |inter - sum t_j dx_j| <= (n + 2) u sum |t_j dx_j| <= (n + 16) u sum |t_j dx_j|,        t = v - a exactly.
+      The layouts' second term, sum |dx_j| bound_v_j, carries the error of the device's v^ against the extended product; here
+      v^ = v, so the carried term is 0.
+  (5) the decision: check_decision unchanged -- r2, r, r_first, r2_min, the counters and the error branch from the device's own three
+      sums.  In the loop every lane repeats it on its own copy of both blocks; lane 0's copy is what the launch stores.
+check_restart applies as it stands: the restart of a resident context is pdlpdev_halpern_restart's, and a batch's
+halpern_restart_finish_workgroup is compared bit for bit with it through whole solves."""
 import math
 
 import numpy as np
@@ -83,6 +120,7 @@ HAL_FIELDS = ("r", "r_first", "r2", "r2_min", "k")
 ANCHORS = ("LAST_RESTART_X", "LAST_RESTART_Y", "LAST_RESTART_ATY")
 BEFORE = ("X", "Y", "ATY", "SUM_X", "SUM_Y") + ANCHORS
 AFTER = BEFORE + ("XBAR", "AVG_X", "AVG_Y", "X_OTHER", "Y_OTHER", "ATY_OTHER", "PART_A", "PART_AT")
+AFTER_RESIDENT = BEFORE + ("AVG_X", "AVG_Y", "X_OTHER", "Y_OTHER", "ATY_OTHER")  # the resident loop: no XBAR, no partials
 RATIOS = ("y", "aty", "dy2", "dx2", "inter", "part", "dist", "weight")
 UNCHANGED = ("step_size", "primal_weight", "tau", "sigma", "sum_weights", "pending_avg")
 OVERFLOW = 1.0e100
@@ -202,6 +240,58 @@ def check_sums(S, before, after, vec, tag="", exact=None):
                 inter_bound_rel=(inter_bound / float(absinter) if float(absinter) > 0.0 else math.inf))
 
 
+def check_resident_vectors(S, prob, before, after, tag=""):
+    """stages (0) - (3) by the rules of the resident loop: every buffer bit for bit -> dict(xn, yp, v: the float64 A^T y')"""
+    cb, k = ar.ctl_dict(before["ctl"]), hal_dict(before["hal"])["k"]
+    assert cb["pending_avg"] == 0, (tag, "an average pending in Halpern mode", cb)
+    # (0) what the step reads and never writes; z^k where the last step of a launch stores it
+    for name in ("X", "Y", "ATY"):
+        _same_bits(tag, "the step changed its own input " + name, after[name + "_OTHER"], before[name])
+    for name in ANCHORS + ("SUM_X", "SUM_Y"):
+        _same_bits(tag, "the step changed " + name, after[name], before[name])
+    # (1) the primal half
+    p = primal(prob, cb, before)
+    _same_bits(tag, "x' (AVG_X)", after["AVG_X"], p["xn"])
+    _same_bits(tag, "x^{k+1}", after["X"], combine(k, p["xn"], before["X"], before["LAST_RESTART_X"]))
+    # (2) the dual half: every row left to right from the reference's own xbar (bit-exact from x')
+    yp = after["AVG_Y"]
+    want = dual_f64(prob, cb, before, ar.rowsums_f64(prob["A_VALUES"], p["xbar"], S.off, S.idx))
+    assert yp.shape == (S.m,) and np.isfinite(want).all(), (tag, "the reference's own y'")
+    _same_bits(tag, "y' (AVG_Y)", yp, want)
+    _same_bits(tag, "y^{k+1}", after["Y"], combine(k, yp, before["Y"], before["LAST_RESTART_Y"]))
+    # (3) the A^T product over A^T's own CSR and values, from the device's own y'
+    at_values = prob["AT_VALUES"] if "AT_VALUES" in prob else prob["A_VALUES"][S.order]
+    v = ar.rowsums_f64(at_values, yp, S.t_off, S.t_rows)
+    assert after["ATY"].shape == (S.n,) and np.isfinite(v).all(), (tag, "the reference's own A^T y'")
+    _same_bits(tag, "A^T y^{k+1}", after["ATY"], combine(k, v, before["ATY"], before["LAST_RESTART_ATY"]))
+    return dict(xn=p["xn"], yp=yp, v=v)
+
+
+def check_resident_sums(S, before, after, vec, tag="", exact=None):
+    """stage (4) by the rules of the resident loop: the three sums against step_sums of x', y' and the float64 v (no carried term,
+    no partials) -> what check_sums returns"""
+    ca = ar.ctl_dict(after["ctl"])
+    s = step_sums(before, vec["xn"], vec["yp"], vec["v"], exact)
+    ex = s["_exact"]
+    ratios = dict(dy2=scalar_ratio(s["dy2"], ca["last_dy2"], ex), dx2=scalar_ratio(s["dx2"], ca["last_dx2"], ex),
+                  inter=scalar_ratio(s["inter"], ca["last_interaction"], ex), part=0.0)
+    for key, field in (("dy2", "last_dy2"), ("dx2", "last_dx2"), ("inter", "last_interaction")):
+        assert ratios[key] <= 1.0, (tag, key + " outside its bound", ratios[key], float(s[key][0]), ca[field])
+    absinter = s["inter"][1] / ((S.n + 16) * U)
+    return dict(ratios=ratios, dy2=float(s["dy2"][0]), dx2=float(s["dx2"][0]), inter=float(s["inter"][0]), absinter=float(absinter),
+                inter_bound_rel=(S.n + 16) * U)  # (no carried term: the bound is that share of sum |t_j dx_j| whatever the step)
+
+
+def check_last_step_store(S, prob, after, tag=""):
+    """Behind a launch of ANY number of steps on the resident path: X_OTHER / Y_OTHER hold the z^k whose image T(z^k) the average
+    slots hold -- y' = dual_f64 at Y_OTHER of the row sums of A (2 x' - x^k), bit for bit as stage (2) forms it.  A launch that left
+    its last z^k in registers fails here: the side then holds the iterate of an earlier launch.  (tau and sigma are those of the last
+    step: nothing but a restart moves them.)"""
+    xn, xk = after["AVG_X"], after["X_OTHER"]
+    want = dual_f64(prob, ar.ctl_dict(after["ctl"]), dict(Y=after["Y_OTHER"]), ar.rowsums_f64(prob["A_VALUES"], xn - xk + xn, S.off, S.idx))
+    _same_bits(tag, "z^k (X_OTHER, Y_OTHER) is not the point whose image the average slots hold", after["AVG_Y"], want)
+
+
 def check_decision(before, after, tag=""):
     """stage (5): halpern_decision_workgroup from the device's OWN three sums -> dict(r2, error)"""
     cb, ca = ar.ctl_dict(before["ctl"]), ar.ctl_dict(after["ctl"])
@@ -227,15 +317,22 @@ def check_decision(before, after, tag=""):
     return dict(r2=r2, error=0)
 
 
-def check_step(S, prob, before, after, tag="", exact=None):
+def check_step(S, prob, before, after, tag="", exact=None, resident=False):
     """Every rule of the module's docstring for ONE step behind a single-step run.  before: dict(ctl, hal, X, Y, ATY, SUM_X, SUM_Y,
     LAST_RESTART_X/Y/ATY) as downloaded in front of it; after: the same plus XBAR, AVG_X, AVG_Y, X_OTHER, Y_OTHER, ATY_OTHER,
-    PART_A, PART_AT (X: the CURRENT side at that moment).  Raises AssertionError naming the stage; returns dict(ratios: y, aty,
-    dy2, dx2, inter, part; compared; dy2, dx2, inter, absinter, inter_bound_rel, r2, error, k_before, cur_before)."""
+    PART_A, PART_AT (X: the CURRENT side at that moment).  resident: the rules of the resident one-workgroup loop -- `after` needs
+    neither XBAR nor the partials (AFTER_RESIDENT), `prob` carries AT_VALUES.  Raises AssertionError naming the stage; returns
+    dict(ratios: y, aty, dy2, dx2, inter, part; compared; dy2, dx2, inter, absinter, inter_bound_rel, r2, error, k_before,
+    cur_before)."""
     cb, ca = ar.ctl_dict(before["ctl"]), ar.ctl_dict(after["ctl"])
     assert cb["error"] == 0 and ca["target_steps"] == cb["steps_taken"] + 1, (tag, "not one step behind a single-step run", cb, ca)
-    vec = check_vectors(S, prob, before, after, tag, exact)
-    sums = check_sums(S, before, after, vec, tag, exact)
+    if resident:
+        vec = check_resident_vectors(S, prob, before, after, tag)
+        vec.update(ratios=dict(y=0.0, aty=0.0), compared=dict(y=S.m, aty=S.n))  # (bit for bit on every row and column)
+        sums = check_resident_sums(S, before, after, vec, tag, exact)
+    else:
+        vec = check_vectors(S, prob, before, after, tag, exact)
+        sums = check_sums(S, before, after, vec, tag, exact)
     dec = check_decision(before, after, tag)
     out = dict(sums, **dec)
     out.update(ratios=dict(vec["ratios"], **sums["ratios"]), compared=vec["compared"], k_before=hal_dict(before["hal"])["k"], cur_before=cb["cur"])

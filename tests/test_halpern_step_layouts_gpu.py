@@ -61,7 +61,7 @@ class OnDevice:
 
     def get(self, name):
         d = self.dev
-        count = d.nnz if name == "A_VALUES" else MOST_PARTIALS if name.startswith("PART_") else d.m if name in M_SIZED else d.n
+        count = d.nnz if name in ("A_VALUES", "AT_VALUES") else MOST_PARTIALS if name.startswith("PART_") else d.m if name in M_SIZED else d.n
         out = d.download(name, count)
         assert len(out) < MOST_PARTIALS or not name.startswith("PART_"), "more partials than the test downloads"
         return out
@@ -76,10 +76,11 @@ class OnDevice:
         return self.dev.halpern_restart(theta)[:2]
 
 
-def prepared(raw, p, x0, y0, scale=True, graph=1):
+def prepared(raw, p, x0, y0, scale=True, graph=1, resident=False):
     """Ruiz 10 + Pock-Chambolle (or the identity), Halpern mode, eta = STEP_SAFETY / sigma_max, omega from the norms of c and b (as
     test_halpern_gpu.halpern_device), the start scaled and projected, A^T y, the start its own anchor
-    -> (OnDevice, Structure, the scaled problem as the device holds it)"""
+    -> (OnDevice, Structure, the scaled problem as the device holds it; resident: with AT_VALUES, for
+    tests/test_halpern_resident_steps_gpu.py)"""
     raw.call("set_graph_mode", int(graph))
     if scale:
         raw.call("scaling_compute", 1, 10, 1, 1.0)
@@ -103,7 +104,7 @@ def prepared(raw, p, x0, y0, scale=True, graph=1):
     if not scale:
         assert (dev.get("DROW") == 1.0).all() and (dev.get("DCOL") == 1.0).all(), "the identity scaling"
     S = ar.Structure(p["m"], p["n"], p["offsets"], p["indices"])
-    return dev, S, sc.download_problem(dev)
+    return dev, S, sc.download_problem(dev, resident)
 
 
 def scenario(name, raw, p, x0, y0):

@@ -19,8 +19,11 @@ import pytest
 import attempt_reference as ar
 import attempt_scenario as asc
 import eval_reference as er
+import frame_reference as fr
+import halpern_reference as H
 import halpern_step_reference as hr
 import halpern_step_scenario as sc
+import resident_lps as rl
 from eval_lps import DENSE_ROWS, EMPTY_COLS, LONG_COLS, LONG_ROWS, SEEDS, WIDE_N, edge_lp
 from test_attempt_reference import arrays, ctl_of, scaling_of
 
@@ -287,3 +290,159 @@ def test_overflow_on_the_stand_in():
     assert after["hal"] == before["hal"] and (after["ctl"]["attempts"], after["ctl"]["steps_taken"], after["ctl"]["cur"]) == (1, 1, 1)
     dev.run(2)
     assert dev.ctl()["attempts"] == 1
+
+
+# ---- the resident one-workgroup loop: its rules, its LPs and its cases on the resident stand-in -----------------------------------------
+# What tests/test_halpern_resident_steps_gpu.py needs of tests/resident_lps.py, asserted below on the reference alone; the GPU file takes
+# its id lists from here.
+EVAL_STEPS = (1, 2, 3, 4, 40)  # T(z^k) behind these many steps is looked at; the GPU test evaluates behind 3 and 4
+G_IS_ZERO = tuple(rl.SCENARIO) + tuple(rl.FULL) + ("past-n", "past-nnz", "cols-only")  # ids with a column whose reduced-cost gradient is exactly 0
+LINF_POSITIVE = tuple(k for k in rl.ALL if not k.startswith("minimal"))                # ids on which both l-infinity figures are positive
+EVALUATED = tuple(k for k in rl.ALL if k in G_IS_ZERO and k in LINF_POSITIVE)          # where test_eval_layouts_gpu's checks apply as they stand
+COMPOSITION_LPS = ("t0", "minimal-1x2")
+RESTARTS_IN_1000 = 6
+
+
+def resident_stand_in(name, **kw):
+    p, x0, y0 = rl.lp(name)
+    dr, dc = fr.scaling(p)
+    return sc.stand_in(p, x0, y0, dr, dc, resident=True, **kw) + (p, dr, dc)
+
+
+@pytest.mark.parametrize("name", list(rl.ALL))
+def test_resident_scenario_on_the_stand_in(name):
+    """the six-part scenario by the resident rules: y' and A^T y^{k+1} bit for bit, the three sums and the distances inside their bounds"""
+    dev, S, prob, p, dr, dc = resident_stand_in(name)
+    record = []
+    worst = sc.run_scenario(dev, S, prob, name, record, resident=True)
+    print(worst.line("stand-in " + name))
+    assert max(worst.values()) <= 1.0 and worst["y"] == worst["aty"] == worst["part"] == 0.0, worst
+    assert len(record) == 6 and all(r["error"] == 0 and r["compared"] == dict(y=S.m, aty=S.n) for r in record)
+    assert all(r["inter_bound_rel"] <= INTER_BOUND_REL for r in record)
+
+
+@pytest.mark.parametrize("name", list(rl.FULL) + list(rl.EDGE))
+def test_edge_steps_on_the_stand_in(name):
+    """the GPU test's edge case: each of the three steps moves both halves and the restart behind them is smoothed, on every edge LP"""
+    dev, S, prob = resident_stand_in(name)[:3]
+    worst, record = sc.edge_steps(dev, S, prob, name)
+    print(worst.line("stand-in edge " + name))
+    assert max(worst.values()) <= 1.0 and len(record) == 5, worst
+
+
+@pytest.mark.parametrize("name", list(rl.ALL))
+def test_resident_lps_hold_what_the_halpern_tests_need(name):
+    """the scenario's conditions (the test above asserts them on every id); hardly a reduced-cost tie at any evaluated T(z^k); which ids
+    hold a column with g = 0 and positive l-infinity figures (test_eval_layouts_gpu's checks ask for both); and the restatement
+    restarts at its first major iteration, so that a solve of 400 steps runs the restart kernels"""
+    dev, S, prob, p, dr, dc = resident_stand_in(name)
+    share = 0.0
+    for steps in EVAL_STEPS:
+        dev.run(steps)
+        c = dev.ctl()
+        assert (c["steps_taken"], c["error"]) == (steps, 0), c
+        for rule in (True, False):
+            ref = er.evaluate(p, dev.get("AVG_X") * dc, dev.get("AVG_Y") * dr, rule_finite=rule, eps_p=1e-4, eps_d=1e-4)
+            share = max(share, float(ref["near_tie"].mean()))
+            assert ref["near_tie"].mean() <= 0.005, (name, steps, rule)
+            assert bool(ref["g_is_zero"].any()) == (name in G_IS_ZERO), (name, steps, rule)
+            positive = ref["LINF_PRES_REL"] > 0.0 and ref["LINF_DRES_REL"] > 0.0
+            assert positive == (name in LINF_POSITIVE), (name, steps, rule, ref["LINF_PRES_REL"], ref["LINF_DRES_REL"])
+    import scipy.sparse as sp
+    fresh = resident_stand_in(name)[0]
+    it = H.HalpernIteration(sp.csr_matrix((prob["A_VALUES"], S.idx, S.off), shape=(S.m, S.n)), prob["C"], prob["LB"], prob["UB"], prob["LO"], prob["HI"],
+                            fresh.it.eta, fresh.it.omega, x=fresh.it.x, y=fresh.it.y)
+    r = H.run(p, it, dr, dc, eps=0.0, max_iterations=1000)
+    print("TIES %s worst share %.4f; restarts %d flags %s" % (name, share, r["restarts"], "".join("R" if f else "." for f in r["flags"])))
+    assert r["status"] == "IterationLimit" and r["flags"][0] and r["restarts"] == RESTARTS_IN_1000 and sum(r["flags"][:10]) >= 1, r["flags"]
+
+
+def test_evaluated_ids_are_what_the_issue_names():
+    assert EVALUATED == ("t0", "t1", "t2", "t0-full", "t1-full", "t2-full", "past-n", "past-nnz", "cols-only")
+    assert set(rl.ALL) - set(G_IS_ZERO) == {"rows-only", "spanning", "minimal-1x2", "minimal-2x1"}
+
+
+@pytest.mark.parametrize("start", sc.STARTS)
+@pytest.mark.parametrize("name", COMPOSITION_LPS)
+def test_composition_case_on_the_stand_in(name, start):
+    """the three starts exist on these LPs -- the restart of `restarted` is smoothed and moves the anchor -- and the stand-in passes
+    (the equality itself is trivial on the host)"""
+    assert sc.check_composition(lambda: resident_stand_in(name)[:3], name, start) == sc.LAUNCH_STEPS == 12
+
+
+def _seen_row(name="t0"):
+    """an equality row of at least two entries, and the position of the entry that weighs most in the first step's A xbar"""
+    dev, S, prob, p, dr, dc = resident_stand_in(name)
+    st = sc.snapshot(dev)
+    xbar = hr.primal(prob, st["ctl"], st)["xbar"]
+    for row in np.nonzero((p["lo"] == p["hi"]) & (S.len_r >= 2))[0]:
+        a, b = S.off[row], S.off[row + 1]
+        weight = np.abs(prob["A_VALUES"][a:b] * xbar[S.idx[a:b]])
+        if weight.max() > 0.0:
+            return int(row), int(np.argmax(weight))
+    raise AssertionError("no equality row whose sum is seen")
+
+
+def _seen_at_entry(name="t0"):
+    """(entry of A^T's CSR, its column): one ulp on that value changes the bits of the first step's A^T y^{k+1} in that column"""
+    dev, S, prob, p, dr, dc = resident_stand_in(name)
+    st = sc.snapshot(dev)
+    dev.run(1)
+    yp, base = dev.get("AVG_Y"), prob["A_VALUES"][S.order]
+    for j in np.nonzero(S.len_c >= 1)[0]:
+        e = S.t_off[j]
+        sums = []
+        for first in (base[e], np.nextafter(base[e], np.inf)):
+            v = np.float64(0.0)
+            for q in range(e, S.t_off[j + 1]):
+                v = v + (first if q == e else base[q]) * yp[S.t_rows[q]]
+            sums.append(hr.combine(0, v, st["ATY"][j], st["LAST_RESTART_ATY"][j]))
+        if not ar.bits_equal([sums[0]], [sums[1]]):
+            return int(e), int(j)
+    raise AssertionError("no entry of A^T whose last bit is seen")
+
+
+@pytest.mark.parametrize("wrong,stage,steps", [
+    ("w", r"x\^\{k\+1\}", 1), ("anchor", r"'A\^T y\^\{k\+1\}', \d+", 1), ("avg_y", r"\"y' \(AVG_Y\)\", \d+", 1), ("r_first", "r_first", 2),
+    ("factor2", r"r2 \(last_movement\)", 1), ("row-entry", r"\"y' \(AVG_Y\)\", %d\)", 1), ("xprime", r"x' \(AVG_X\)", 1),
+    ("at-values", r"'A\^T y\^\{k\+1\}', %d\)", 1)])
+def test_the_resident_rules_name_the_stage(wrong, stage, steps):
+    """every wrong stand-in of the layouts' rules, and the one whose A^T values are A's, fails check_step(resident=True) at its stage --
+    the dropped entry at its row, the last bit of one A^T value at its column.  (AVG_Y holding y^{k+1} shows on the FIRST step here:
+    fl(fl(2 y' - y) / 2 + y / 2) is y' to within the layouts' bound, not to the bit.)"""
+    kw = {}
+    if wrong == "row-entry":
+        row, position = _seen_row()
+        kw, stage = dict(drop=(row, position)), stage % row
+    if wrong == "at-values":
+        entry, column = _seen_at_entry()
+        kw, stage = dict(at_entry=entry), stage % column
+        dev, S, prob = resident_stand_in("t0", **kw)[:3]  # (the stand-in that reads AT_VALUES passes with that entry)
+        assert (prob["AT_VALUES"] != prob["A_VALUES"][S.order]).sum() == 1
+        sc.one_step(dev, S, prob, "AT_VALUES read", resident=True)
+    dev, S, prob = resident_stand_in("t0", wrong=wrong, **kw)[:3]
+    for i in range(steps - 1):
+        sc.one_step(dev, S, prob, "%s step %d" % (wrong, i), resident=True)  # (nothing is wrong yet)
+    with pytest.raises(AssertionError, match=stage):
+        sc.one_step(dev, S, prob, wrong, resident=True)
+
+
+@pytest.mark.parametrize("wrong,stage", [("last-store", r"one launch against single steps', 'X_OTHER'"),
+                                         ("made", r"a launch without a step changed', 'AVG_X'")])
+def test_the_composition_case_names_the_buffer(wrong, stage):
+    """z^k not stored on the last step of a multi-step launch, and a launch without a step that rewrites AVG_X: a single-step check
+    sees neither (there the store is of what the side holds already, and every checked launch makes a step); check_composition does"""
+    dev, S, prob = resident_stand_in("t0", wrong=wrong)[:3]
+    for i in range(3):
+        sc.one_step(dev, S, prob, "%s step %d" % (wrong, i), resident=True)
+        hr.check_last_step_store(S, prob, sc.snapshot(dev, hr.AFTER_RESIDENT), wrong)
+    for steps in (5, 4):  # (an odd and an even number of steps in one launch)
+        dev.run(dev.ctl()["steps_taken"] + steps)
+        if wrong == "last-store":
+            with pytest.raises(AssertionError, match="is not the point whose image the average slots hold"):
+                hr.check_last_step_store(S, prob, sc.snapshot(dev, hr.AFTER_RESIDENT), wrong)
+        else:
+            hr.check_last_step_store(S, prob, sc.snapshot(dev, hr.AFTER_RESIDENT), wrong)
+    for start in sc.STARTS:
+        with pytest.raises(AssertionError, match=stage):
+            sc.check_composition(lambda: resident_stand_in("t0", wrong=wrong)[:3], "t0", start)
